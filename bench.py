@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """Rollout throughput of the GrainGNN hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs when --dump-outputs is given and
+prints the result line.  --full adds everything else beside the headline: back-to-back repeats of the timed region,
+the roofline and forward-only timings, the CPU baseline, the native-fp32 child run and the training-step and
+event-mode records.
 
 One *step* = Rmodel.forward + Cmodel.forward + Rmodel.update + z advance + edge-length
 refresh (test.py:382-407, 562-575) on the synthetic 10 000-grain / 20 000-junction periodic
@@ -557,6 +562,26 @@ def event_mode_record():
         return {"error": f"{type(e).__name__}: {e}"[:200]}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, ro, gathered):
+    """--dump-outputs: what the timed path left after its last step, one float32 .npy per array -- the step's predictions
+    (pred_*, what GrainRollout.run returns), the node features it advanced (x_*) and the states gathered over the ranks
+    (state_*, with _rank<r> when there are several).  Every workload's arrays stay far below 64 MB in all."""
+    arrays = {f"pred_{k}": v for k, v in ro.pred.items()}
+    arrays.update({f"x_{k}": v for k, v in ro.x.items()})
+    for r, g in enumerate(gathered):
+        arrays.update({f"state_{k}" + (f"_rank{r}" if len(gathered) > 1 else ""): v for k, v in g.items()})
+    arrays = {k: v.detach().cpu().numpy().astype(np.float32) for k, v in sorted(arrays.items())}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes of outputs, more than {DUMP_MAX_BYTES}")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -564,6 +589,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of hipGraph replay")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline as well: repeats of the timed region, roofline and forward-only "
+                         "timings, CPU baseline, native-fp32 child run, training-step and event-mode records")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed path computed in its last step (predictions, node features, gathered "
+                         "states) as DIR/<name>.npy")
     ap.add_argument("--profile", action="store_true",
                     help="for rocprofv3 runs: only the rollout steps (no roofline timing, forward-only figure, "
                          "CPU baseline or native-fp32 child run), so every traced kernel belongs to a step")
@@ -740,11 +771,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     finite = all(bool(torch.isfinite(v).all()) for g in gathered for v in g.values())
-    # The same region -- exactly args.steps steps + the gather, bracketed the same way -- repeated back to back: `value` /
-    # `ms_per_step` stay the single shot above (what the driver's clock brackets), the median of the repeats says how
-    # much of a 7 ms region's number is the region (GGNN_BENCH_REPEATS, default 15; 0 switches it off)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ro, gathered)
+    # --full: the same region -- exactly args.steps steps + the gather, bracketed the same way -- repeated back to back:
+    # `value` / `ms_per_step` stay the single shot above (what the driver's clock brackets), the median of the repeats says
+    # how much of a 7 ms region's number is the region (GGNN_BENCH_REPEATS, default 15; 0 switches it off)
     repeats = []
-    for _ in range(0 if args.events else int(os.environ.get("GGNN_BENCH_REPEATS", "15"))):
+    for _ in range(0 if args.events or not args.full else int(os.environ.get("GGNN_BENCH_REPEATS", "15"))):
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
@@ -764,18 +797,20 @@ def main():
         repeats.append(units_per_step * args.steps / dtr)
 
     if rank == 0:
-        roof, roof_enc, roof_gemm, roof_sweep = (None, None, [], None) if args.profile else measure_roofline(ro, 10)
-        # forward-only rate beside the full step (eager launches, R then C on one stream)
-        forward_only = 0.0
-        with torch.no_grad():
-            for _ in range(0 if args.profile else 5):
-                R(X, EI, EA), Cm(X, EI, EA)
-            torch.cuda.synchronize()
-            tf = time.perf_counter()
-            for _ in range(0 if args.profile else 100):
-                R(X, EI, EA), Cm(X, EI, EA)
-            torch.cuda.synchronize()
-            forward_only = 100 / (time.perf_counter() - tf)
+        extras = args.full and not args.profile
+        roof, roof_enc, roof_gemm, roof_sweep = measure_roofline(ro, 10) if extras else (None, None, [], None)
+        # --full, SURVEY 8(d): forward-only rate beside the full step (eager launches, R then C on one stream)
+        forward_only = None
+        if extras:
+            with torch.no_grad():
+                for _ in range(5):
+                    R(X, EI, EA), Cm(X, EI, EA)
+                torch.cuda.synchronize()
+                tf = time.perf_counter()
+                for _ in range(100):
+                    R(X, EI, EA), Cm(X, EI, EA)
+                torch.cuda.synchronize()
+                forward_only = 100 / (time.perf_counter() - tf)
         line = {
             "metric": "rollout steps/sec (10k-grain heterograph)",
             "value": round(units_per_step * args.steps / dt, 2),
@@ -812,7 +847,8 @@ def main():
                                 if default_backend().lib.ggnn_gemm_mode() == 1 else "native fp32 MFMA (GGNN_GEMM=fp32)"),
                        "results_finite": finite, "untimed_steps": untimed_steps,
                        "forward_only": {"steps_per_s_per_gpu": round(forward_only * (units_per_step // world), 2),
-                                        "launch": "eager, R then C on one stream (no update / refresh)"},
+                                        "launch": "eager, R then C on one stream (no update / refresh)"}
+                                       if forward_only is not None else None,
                        **({"events": {"grains_eliminated": int(sum(len(e) for e in ro.grain_events)),
                                       "edges_switched": int(sum(len(e) for e in ro.switched)),
                                       "edges_left": int(ro.edge_index[("joint", "connect", "joint")].size(1)),
@@ -823,7 +859,7 @@ def main():
             "roofline_encoder_cell": roof_enc,
             "roofline_gemm": roof_gemm,
         }
-        if not args.no_cpu_baseline and not args.profile and args.workload == "cfg3" and world == 1:  # N = 1 only: a reported baseline
+        if extras and not args.no_cpu_baseline and args.workload == "cfg3" and world == 1:  # N = 1 only: a reported baseline
             line["cpu_baseline"] = cpu_baseline(inputs)
             if default_backend().lib.ggnn_gemm_mode() == 1 and not args.events:
                 # the same workload with the decoder GEMMs on the native fp32 matrix path, in a child

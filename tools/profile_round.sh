@@ -89,11 +89,11 @@ python3 tools/kernel_table.py $OUT/serial_fused_kernel_stats.csv $OUT/serial_spl
 cat $OUT/kernel_table.txt
 fi
 if want bench; then
-timeout 700 python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+timeout 700 python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 timeout 700 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_command.json 2> $OUT/bench_driver_command.err
-GGNN_DEC=split timeout 400 python3 bench.py --no-cpu-baseline > $OUT/bench_split_plan.json 2> $OUT/bench_split_plan.err
-timeout 400 python3 bench.py --workload gen368 --steps 100 --warmup 10 --no-cpu-baseline > $OUT/bench_gen368.json 2> $OUT/bench_gen368.err
-timeout 400 python3 bench.py --workload cfg2 --steps 120 --warmup 10 --no-cpu-baseline > $OUT/bench_cfg2.json 2> $OUT/bench_cfg2.err
-timeout 400 python3 bench.py --workload cfg4 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_cfg4.json 2> $OUT/bench_cfg4.err
+GGNN_DEC=split timeout 400 python3 bench.py --full --no-cpu-baseline > $OUT/bench_split_plan.json 2> $OUT/bench_split_plan.err
+timeout 400 python3 bench.py --workload gen368 --steps 100 --warmup 10 --no-cpu-baseline --full > $OUT/bench_gen368.json 2> $OUT/bench_gen368.err
+timeout 400 python3 bench.py --workload cfg2 --steps 120 --warmup 10 --no-cpu-baseline --full > $OUT/bench_cfg2.json 2> $OUT/bench_cfg2.err
+timeout 400 python3 bench.py --workload cfg4 --steps 20 --warmup 5 --no-cpu-baseline --full > $OUT/bench_cfg4.json 2> $OUT/bench_cfg4.err
 for f in default driver_command split_plan gen368 cfg2 cfg4; do tail -1 $OUT/bench_$f.json | cut -c1-200; done
 fi
