@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
-"""One-off GPU fuzz (not collected by pytest): parameter gradients of the HIP training path against
-autograd of the CPU oracle on random Voronoi structures, random targets / masks / labels.  The reference is
-the oracle evaluated in fp64; the fp32 oracle's own distance from it is printed beside the product's.
-Tolerance per parameter tensor: max|g - g_ref| <= 2e-4 * max|g_ref| + 1e-6 * (largest gradient entry).
-Typical worst error 1e-6 of a tensor's scale.  One case in ten shows 2.8e-4 on a small lin_value.weight gradient,
-confined to ONE of its 96 rows: an edge value within rounding of 0 whose relu mask (periodGATconv.py:233) falls on
-the other side in the product's projection arithmetic -- 4.5e-7 of the largest gradient entry, inside the bar.
-    python tests/fuzz_training.py [--n 10] [--seed 0]
+"""One-off GPU fuzz (not collected by pytest; a fixed set of its cases runs in the suite:
+test_training_kernels.py::test_gradient_fuzz_with_relu_kinks_proven): parameter gradients of the HIP training path against
+autograd of the CPU oracle on random Voronoi structures, random targets / masks / labels.  The reference is the oracle
+evaluated in fp64; the fp32 oracle's own distance from it is printed beside the product's.
+Tolerance per parameter tensor: max|g - g_ref| <= 2e-4 * max|g_ref| + 1e-6 * (largest gradient entry).  A tensor beyond it
+is excused only as a relu kink PROVEN by the fp64 record of its PeriodConv (gradcheck.judge_tensor: a lin_value weight /
+bias, <= 2 off rows, each with an edge whose pre-activation is within TAU of 0 and a deviation no larger than flipping
+those edges' masks can make); every excused row is printed with its proof.
+    python tests/fuzz_training.py [--n 10] [--seed 0] [--only K]
 """
 import argparse
 import os
@@ -18,26 +19,8 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
-from helpers import oracle_models, product_models, tt  # noqa: E402
-from graingraphnn_amd import synthetic, training  # noqa: E402
-
-JJ = ("joint", "connect", "joint")
-
-
-def grads(R, Cm, x, ei, ea, y, mask, dev, dtype=torch.float32):
-    R.train(), Cm.train()
-    R.zero_grad(), Cm.zero_grad()
-    cast = lambda d: {k: (v.to(dtype) if v.is_floating_point() else v) for k, v in tt(d, dev).items()}
-    Y, M = cast(y), cast(mask)
-    lr = training.regressor_loss(Y, R(cast(x), tt(ei, dev), cast(ea)), M)
-    lc = training.classifier_loss(Y, Cm(cast(x), tt(ei, dev), cast(ea)), 1.0)
-    lr.backward()
-    lc.backward()
-    out = {}
-    for tag, m in (("R", R), ("C", Cm)):
-        for n, p in m.named_parameters():
-            out[f"{tag}/{n}"] = (torch.zeros_like(p) if p.grad is None else p.grad).detach().cpu()
-    return float(lr.detach()), float(lc.detach()), out
+import gradcheck as gc  # noqa: E402
+from helpers import oracle_models, product_models  # noqa: E402
 
 
 def main():
@@ -47,66 +30,44 @@ def main():
     ap.add_argument("--only", type=int, default=None, help="run this case of the sequence only (the others are drawn, not computed)")
     args = ap.parse_args()
     rs = np.random.RandomState(args.seed)
-    worst, kinks, kink_rows = 0.0, 0, []
+    worst, n_excused, failed = 0.0, 0, []
     for it in range(args.n):
-        n_g = int(rs.choice([12, 40, 150, 400]))
-        noise = None if rs.rand() < 0.5 else float(rs.uniform(0.05, 0.3))
-        wseed, scale = int(rs.randint(1, 10 ** 6)), float(rs.choice([0.5, 1.0, 2.0]))
-        x, ei, ea = synthetic.voronoi(n_g, seed=int(rs.randint(1, 10 ** 6)), lattice_noise=noise)
-        n_j, n_gr, E = x["joint"].shape[0], x["grain"].shape[0], ei[JJ].shape[1]
-        y = {"joint": rs.uniform(-1, 1, (n_j, 2)).astype(np.float32), "grain": rs.uniform(-1, 1, (n_gr, 2)).astype(np.float32),
-             "edge_event": rs.randint(-1, 2, size=E).astype(np.int64)}
-        mask = {"joint": (rs.rand(n_j, 1) > 0.1).astype(np.float32), "grain": (rs.rand(n_gr, 1) > 0.1).astype(np.float32)}
+        n_g, noise, wseed, scale, vseed = gc.fuzz_params(rs)
+        x, ei, ea, y, mask = gc.fuzz_data(rs, n_g, noise, vseed)
         if args.only is not None and it != args.only:
             continue
         R, Cm = product_models(wseed, scale, "cuda")
         oR, oC = oracle_models(wseed, scale)
-        la, lca, ga = grads(R, Cm, x, ei, ea, y, mask, "cuda")
-        _, _, g32 = grads(oR, oC, x, ei, ea, y, mask, "cpu")
-        lb, lcb, gb = grads(oR.double(), oC.double(), x, ei, ea, y, mask, "cpu", torch.float64)
+        la, lca, ga = gc.model_grads(R, Cm, x, ei, ea, y, mask, "cuda")
+        _, _, g32 = gc.model_grads(oR, oC, x, ei, ea, y, mask, "cpu")
+        lb, lcb, gb, records, _ = gc.oracle_fp64_grads(wseed, scale, x, ei, ea, y, mask)
         assert abs(la - lb) <= 1e-5 * abs(lb) and abs(lca - lcb) <= 1e-5 * abs(lcb), (la, lb, lca, lcb)
-        atol = 1e-6 * max(float(g.abs().max()) for g in gb.values())
+        fails, excused = gc.judge_gradients(ga, gb, records)
+        atol = gc.GRAD_ATOL * max(float(g.abs().max()) for g in gb.values())
         w = w32 = 0.0
         wname = ""
+        kinked = {n for n, _ in excused}
         for n, g in gb.items():
-            err, sc = float((ga[n].double() - g).abs().max()), float(g.abs().max())
-            # (a relu mask that flips at a value within fp32 rounding of zero moves a gradient by a whole term: the fp32 ORACLE
-            # then misses its own fp64 evaluation by as much -- such a tensor is judged against that deviation and counted)
-            err32 = float((g32[n].double() - g).abs().max())
-            if err > 2e-4 * sc + atol and err <= 4 * err32:
-                kinks += 1
+            sc = float(g.abs().max())
+            if sc <= 100 * atol or n in kinked:
                 continue
-            # ... and the same on this side: the value a relu sees is a sum in ANOTHER order here (two-piece products), so a
-            # value within rounding of zero can flip here and not in the oracle -- it shows as exactly ONE output channel of one
-            # lin_value (weight row and bias element) off by a whole term, everything else of the tensor within the bound
-            if err > 2e-4 * sc + atol and ".lin_value." in n:
-                d = (ga[n].double() - g).abs().reshape(g.size(0), -1).max(1).values
-                if int((d > 2e-4 * sc + atol).sum()) == 1:
-                    kinks += 1
-                    kink_rows.append((it, n, int(d.argmax()), err / sc))
-                    continue
-            if err > 2e-4 * sc + atol and args.only is not None:   # (diagnosis: where the tensor deviates)
-                d = (ga[n].double() - g).abs()
-                rows = d.reshape(d.size(0), -1).max(1).values
-                bad = torch.nonzero(rows > 1e-5 * sc).reshape(-1)
-                print(f"   {n} {tuple(g.shape)}: err {err:.3e} scale {sc:.3e}; rows off: {bad.tolist()[:12]} ({bad.numel()} of {g.size(0)}); "
-                      f"columns off in the worst row: {torch.nonzero(d.reshape(d.size(0), -1)[int(rows.argmax())] > 1e-5 * sc).reshape(-1).tolist()[:16]}", flush=True)
-                continue
-            assert err <= 2e-4 * sc + atol, (it, n, err, sc, err32)
-            if sc > 100 * atol:
-                if err / sc > w:
-                    wname = f"{n} (scale {sc / (atol * 1e6):.1e} of the largest gradient)"
-                    if g.dim() == 2:  # a relu mask that flips at a value within rounding of 0 shows as ONE bad row
-                        rows = (ga[n].double() - g).abs().max(1).values
-                        wname += f"; rows above 1e-5 of the scale: {int((rows > 1e-5 * sc).sum())} of {g.size(0)}"
-                w = max(w, err / sc)
-                w32 = max(w32, float((g32[n].double() - g).abs().max()) / sc)
+            err = float((ga[n].double() - g).abs().max())
+            if err / sc > w:
+                w, wname = err / sc, f"{n} (scale {sc / (atol * 1e6):.1e} of the largest gradient)"
+            w32 = max(w32, float((g32[n].double() - g).abs().max()) / sc)
         worst = max(worst, w)
-        print(f"{it:3d} grains {n_gr:4d} weights x{scale}: losses {la:.4f} / {lca:.4f}, worst gradient error "
+        n_excused += len(excused)
+        print(f"{it:3d} grains {x['grain'].shape[0]:4d} weights x{scale}: losses {la:.4f} / {lca:.4f}, worst gradient error "
               f"{w:.2e} (fp32 oracle against its fp64 self: {w32:.2e}) at {wname}", flush=True)
-    print(f"{args.n} random structures: worst per-tensor relative gradient error {worst:.2e}"
-          + (f"; {kinks} tensors set aside as relu kinks (the fp32 oracle misses its own fp64 evaluation by as much, or exactly one "
-             f"output channel of a lin_value is off: {kink_rows})" if kinks else ""))
+        for n, proof in excused:
+            print("     " + gc.format_excuse(n, proof), flush=True)
+        for n, e in fails:
+            print(f"     FAIL {n}: error {e:.3e} of its scale", flush=True)
+        failed += [(it, n) for n, _ in fails]
+    print(f"{args.n} random structures: worst per-tensor relative gradient error {worst:.2e} (kinks aside); "
+          f"{n_excused} tensors excused as proven relu kinks; {len(failed)} failures {failed}")
+    if failed:
+        sys.exit(1)
 
 
 if __name__ == "__main__":
