@@ -28,11 +28,13 @@ GGNN_ADAM_CHUNK, GGNN_ADAM_MAX_TENSORS, GGNN_ADAM_MAX_GROUPS = 4096, 384, 8
 GGNN_ROWGEMM_MAX_PACK = 8
 GGNN_MSE_MAX_TERMS, GGNN_MSE_BLOCKS = 4, 64
 MODE_LSTM, MODE_LSTM_H0, MODE_RAW = 0, 1, 2
+BC_PERIODIC, BC_NOFLUX = 0, 1   # GGNN_BC_*
 
 # Every symbol include/ggnn.h declares (tests/test_cabi.py checks the library exports them all).
 EXPORTED_SYMBOLS = (
     "ggnn_version", "ggnn_error_string", "ggnn_gemm_mode", "ggnn_csr_workspace_bytes", "ggnn_csr_max_units",
-    "ggnn_build_csr", "ggnn_build_csr_batch",
+    "ggnn_build_csr", "ggnn_build_csr_batch", "ggnn_build_csr_masked_batch", "ggnn_noflux_boundary", "ggnn_grain_centres_bc",
+    "ggnn_detect_events_skip",
     "ggnn_edge_prepare", "ggnn_project", "ggnn_project_batch", "ggnn_period_gat_aggregate",
     "ggnn_period_gat_aggregate_batch", "ggnn_period_gat_aggregate_enc_batch", "ggnn_encoder_cell_batch",
     "ggnn_decoder_cell_batch",
@@ -143,6 +145,14 @@ class CsrArgs(Structure):
         ("rowptr", c_void_p), ("col", c_void_p), ("perm", c_void_p), ("row", c_void_p), ("unit_ptr", c_void_p),
         ("units", c_void_p), ("flags", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_size_t),
     ]
+
+
+class CsrMask(Structure):
+    """Mirror of `ggnn_csr_mask`: -1 = no node skipped."""
+    _fields_ = [("skip_src", c_int64), ("skip_dst", c_int64), ("E_kept", c_void_p)]
+
+    def __init__(self, skip_src=-1, skip_dst=-1, E_kept=None):
+        super().__init__(skip_src, skip_dst, E_kept)
 
 
 class TopologyArgs(Structure):
@@ -308,6 +318,17 @@ def _declare(lib):
                                    c_size_t, c_void_p]
     lib.ggnn_build_csr_batch.restype = c_int
     lib.ggnn_build_csr_batch.argtypes = [POINTER(CsrArgs), c_int, c_void_p]
+    lib.ggnn_build_csr_masked_batch.restype = c_int
+    lib.ggnn_build_csr_masked_batch.argtypes = [POINTER(CsrArgs), POINTER(CsrMask), c_int, c_void_p]
+    lib.ggnn_noflux_boundary.restype = c_int
+    lib.ggnn_noflux_boundary.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_float, c_float,
+                                         c_void_p, c_int64, c_int, c_void_p, c_void_p]
+    lib.ggnn_grain_centres_bc.restype = c_int
+    lib.ggnn_grain_centres_bc.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_float, c_void_p,
+                                          c_int64, c_int64, c_void_p, c_int, c_void_p]
+    lib.ggnn_detect_events_skip.restype = c_int
+    lib.ggnn_detect_events_skip.argtypes = [c_void_p, c_void_p, c_int64, c_float, c_void_p, c_void_p, c_int64, c_void_p,
+                                            c_float, c_void_p, c_void_p, c_int64, c_void_p]
     lib.ggnn_edge_prepare.restype = c_int
     lib.ggnn_edge_prepare.argtypes = [POINTER(PrepareEdge), c_int, c_void_p]
     lib.ggnn_project.restype = c_int

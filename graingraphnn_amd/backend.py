@@ -28,10 +28,12 @@ class CSR:
 class CsrInPlace:
     """See HipBackend.csr_in_place."""
 
-    def __init__(self, backend, shapes, device):
+    def __init__(self, backend, shapes, device, masks=None):
         if not 1 <= len(shapes) <= 4:
             raise _lib.GGNNError("csr_in_place: one to four lists")
         self.be, self.shapes = backend, [tuple(int(v) for v in s) for s in shapes]
+        # masked lists (ggnn_csr_mask): refilled with the same mask; their tables' edge count lives in a device word
+        self.masks, self.kept = _csr_masks(masks, len(self.shapes), device)
         lib = backend.lib
         r4 = lambda n: (n + 3) & ~3
         words = sum(backend.csr_arena_words(cap, n_dst) for cap, _, n_dst in self.shapes)
@@ -58,6 +60,7 @@ class CsrInPlace:
             self.csr.append(CSR(rowptr, col, perm, row, unit_ptr, units, 0))
 
     def rebuild(self, lists):
+        """-> the CSR objects; those of masked lists carry E_dev = their kept-edge word."""
         for a, csr, ei, (cap, _, _) in zip(self.args, self.csr, lists, self.shapes):
             if ei.dtype != torch.int64 or ei.dim() != 2 or ei.size(0) != 2 or not ei.is_contiguous() or not ei.is_cuda:
                 raise _lib.GGNNError("edge_index must be a contiguous int64 [2, E] device tensor")
@@ -66,8 +69,33 @@ class CsrInPlace:
                 raise _lib.GGNNError("csr_in_place: a list grew beyond its capacity")
             a.edge_index, a.E = ei.data_ptr(), E
             csr.E = E
-        _lib.check(self.be.lib.ggnn_build_csr_batch(self.args, len(self.shapes), _lib.current_stream()), "ggnn_build_csr_batch")
+        for csr, w in zip(self.csr, self.kept):
+            if w is not None:
+                csr.E_dev = w
+        if self.masks is None:
+            _lib.check(self.be.lib.ggnn_build_csr_batch(self.args, len(self.shapes), _lib.current_stream()), "ggnn_build_csr_batch")
+        else:
+            _lib.check(self.be.lib.ggnn_build_csr_masked_batch(self.args, self.masks, len(self.shapes), _lib.current_stream()),
+                       "ggnn_build_csr_masked_batch")
         return self.csr
+
+
+def _csr_masks(masks, n, device):
+    """[(skip_src, skip_dst) or None] -> (ctypes array of CsrMask, [int64 [1] kept-edge word or None]); (None, [None] * n)
+    when nothing is masked."""
+    if masks is None or all(m is None or tuple(m) == (-1, -1) for m in masks):
+        return None, [None] * n
+    if len(masks) != n:
+        raise _lib.GGNNError("one mask per list")
+    arr, kept = (_lib.CsrMask * n)(), []
+    for a, m in zip(arr, masks):
+        s, d = (-1, -1) if m is None else (int(m[0]), int(m[1]))
+        if s < -1 or d < -1:
+            raise _lib.GGNNError("skip_src / skip_dst: a node index or -1")
+        w = torch.zeros(1, dtype=torch.int64, device=device) if (s, d) != (-1, -1) else None
+        a.skip_src, a.skip_dst, a.E_kept = s, d, (w.data_ptr() if w is not None else None)
+        kept.append(w)
+    return arr, kept
 
 
 def _require_cuda(*tensors):
@@ -159,22 +187,27 @@ class HipBackend:
         return 2 * r4(n_dst + 1) + 3 * r4(max(int(E_cap), 1)) + 8 * self.lib.ggnn_csr_max_units(int(E_cap), n_dst) + 4 \
             + r4(self.lib.ggnn_csr_workspace_bytes(int(E_cap), n_dst) // 4 + 1)
 
-    def csr_in_place(self, shapes, device):
+    def csr_in_place(self, shapes, device, masks=None):
         """Tables that are rebuilt in place: `shapes` = [(E_cap, n_src, n_dst)] (at most four lists) -> a CsrInPlace whose
         `rebuild([edge_index [2, E <= E_cap]])` fills the SAME device tables for the new lists (unchecked: validated lists)
         and returns the same CSR objects with their E updated -- tensors of capacity size, addresses that never change, so
         launches captured on an earlier, longer version of a list keep reading valid tables."""
-        return CsrInPlace(self, shapes, device)
+        return CsrInPlace(self, shapes, device, masks)
 
-    def build_csr_batch(self, lists, check=True):
+    def build_csr_batch(self, lists, check=True, masks=None):
         """[(edge_index [2, E] int64 cuda, n_src, n_dst)] -> [CSR]: ggnn_build_csr_batch, up to four lists per sequence of
         launches (engine.GraphCSR builds the three edge types of a topology in one; a topological event rebuilds them),
         one range check = one host synchronisation behind the last (`check=False`: lists the caller has validated -- the
         kernels skip an out-of-range edge either way --: no read-back, the host goes on enqueueing).  (Tables that are
-        refilled IN PLACE per event: `csr_in_place`.)"""
+        refilled IN PLACE per event: `csr_in_place`.)  masks: None, or per list None / (skip_src, skip_dst) -- the tables of
+        the list without the edges from skip_src / into skip_dst (ggnn_build_csr_masked_batch); the CSR of a masked list has
+        E = the list's length and E_dev = the number of edges it kept (device word)."""
         out, todo = [], list(lists)
+        mtodo = list(masks) if masks is not None else [None] * len(todo)
         while todo:
             chunk, todo = todo[:4], todo[4:]
+            mchunk, mtodo = mtodo[:4], mtodo[4:]
+            marr, kept = _csr_masks(mchunk, len(chunk), chunk[0][0].device)
             arr = (_lib.CsrArgs * len(chunk))()
             keep = []
             arena = None
@@ -214,8 +247,12 @@ class HipBackend:
                 a.unit_ptr, a.units, a.flags = unit_ptr.data_ptr(), units.data_ptr(), flags.data_ptr()
                 a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
                 keep.append((ei, ws, flags, n_src, n_dst))
-                out.append(CSR(rowptr, col, perm, row, unit_ptr, units, E))
-            _lib.check(self.lib.ggnn_build_csr_batch(arr, len(chunk), _lib.current_stream()), "ggnn_build_csr_batch")
+                out.append(CSR(rowptr, col, perm, row, unit_ptr, units, E, kept[len(keep) - 1]))
+            if marr is None:
+                _lib.check(self.lib.ggnn_build_csr_batch(arr, len(chunk), _lib.current_stream()), "ggnn_build_csr_batch")
+            else:
+                _lib.check(self.lib.ggnn_build_csr_masked_batch(arr, marr, len(chunk), _lib.current_stream()),
+                           "ggnn_build_csr_masked_batch")
             if not check:   # (ei / ws / flags are only used by launches on this stream: the allocator keeps them until those ran)
                 continue
             bad = torch.stack([k[2][0] for k in keep]).cpu()   # (the synchronisation; also keeps ei / ws alive until here)
@@ -958,10 +995,13 @@ class HipBackend:
                                         x_grain.size(1), ptr(y_joint), ptr(y_grain), dz, zmax,
                                         ptr(flags), _lib.current_stream()), "ggnn_step_update")
 
-    def grain_centres(self, csr_jg, x_joint, x_grain, domain_factor=1.0, domain_offset=None, centres_before=None):
+    def grain_centres(self, csr_jg, x_joint, x_grain, domain_factor=1.0, domain_offset=None, centres_before=None,
+                      boundary="periodic"):
         """x_grain[:, :2] <- region centres of the grains' junction polygons (graph.update(),
-        graph_datastruct.py:681-708 + test.py:556-559).  csr_jg: CSR of (joint, pull, grain).  centres_before
+        graph_datastruct.py:681-708 + test.py:556-559).  csr_jg: CSR of (joint, pull, grain) (the FULL list for
+        boundary="noflux": no min-image chaining, grain 0 included).  centres_before
         ([n_grain, 2] fp32, contiguous): receives x_grain[:, :2] as the call found them."""
+        bc = _boundary_code(boundary)
         _require_cuda(x_joint, x_grain, csr_jg.rowptr, domain_offset, centres_before)
         if centres_before is not None:
             _f32c(centres_before, "centres_before")
@@ -975,26 +1015,63 @@ class HipBackend:
                 raise _lib.GGNNError("domain_offset must be [n_joint, 2]")
         elif domain_factor > 1:
             raise _lib.GGNNError("domain_factor > 1 needs the domain_offset of scale_feature_patchs")
-        check(self.lib.ggnn_grain_centres(ptr(csr_jg.rowptr), ptr(csr_jg.col), ptr(x_joint),
-                                          x_joint.size(0), x_joint.stride(0),
-                                          ptr(domain_offset) if domain_offset is not None else None,
-                                          float(domain_factor), ptr(x_grain), x_grain.size(0),
-                                          x_grain.stride(0), ptr(centres_before), _lib.current_stream()),
-              "ggnn_grain_centres")
+        if bc == _lib.BC_PERIODIC:
+            check(self.lib.ggnn_grain_centres(ptr(csr_jg.rowptr), ptr(csr_jg.col), ptr(x_joint),
+                                              x_joint.size(0), x_joint.stride(0),
+                                              ptr(domain_offset) if domain_offset is not None else None,
+                                              float(domain_factor), ptr(x_grain), x_grain.size(0),
+                                              x_grain.stride(0), ptr(centres_before), _lib.current_stream()),
+                  "ggnn_grain_centres")
+        else:
+            check(self.lib.ggnn_grain_centres_bc(ptr(csr_jg.rowptr), ptr(csr_jg.col), ptr(x_joint), x_joint.size(0),
+                                                 x_joint.stride(0), ptr(domain_offset), float(domain_factor), ptr(x_grain),
+                                                 x_grain.size(0), x_grain.stride(0), ptr(centres_before), bc,
+                                                 _lib.current_stream()), "ggnn_grain_centres_bc")
+
+    def noflux_boundary(self, csr_jg, x_joint, x_grain, domain_factor=1.0, domain_offset=None, max_y=1.0,
+                        joints_before=None):
+        """The no-flux boundary step of test.py:446-463 (include/ggnn.h, ggnn_noflux_boundary): grain 0's features
+        reset, its junctions (row 0 of csr_jg, the FULL joint->grain CSR) snapped to the nearest wall, every junction
+        clamped to [0,1] x [0,max_y] in the global frame.  joints_before ([n_joint, 2] fp32): receives x_joint[:, :2]
+        as the call found them."""
+        _require_cuda(x_joint, x_grain, csr_jg.rowptr, domain_offset, joints_before)
+        _f32c(x_joint, "x_joint")
+        _f32c(x_grain, "x_grain")
+        if csr_jg.rowptr.numel() != x_grain.size(0) + 1:
+            raise _lib.GGNNError("csr_jg must have one row per grain")
+        for t, name in ((domain_offset, "domain_offset"), (joints_before, "joints_before")):
+            if t is not None:
+                _f32c(t, name)
+                if tuple(t.shape) != (x_joint.size(0), 2):
+                    raise _lib.GGNNError(f"{name} must be [n_joint, 2]")
+        if domain_offset is None and domain_factor > 1:
+            raise _lib.GGNNError("domain_factor > 1 needs the domain_offset of scale_feature_patchs")
+        check(self.lib.ggnn_noflux_boundary(ptr(csr_jg.rowptr), ptr(csr_jg.col), ptr(x_joint), x_joint.size(0),
+                                            x_joint.stride(0), ptr(domain_offset), float(domain_factor), float(max_y),
+                                            ptr(x_grain), x_grain.stride(0), x_grain.size(1), ptr(joints_before),
+                                            _lib.current_stream()), "ggnn_noflux_boundary")
 
     def detect_events(self, grain_area, live_grain, area_threshold, edge_event, edge_index_jj,
-                      logit_threshold, flags, range_word=None, E_dev=None):
+                      logit_threshold, flags, range_word=None, E_dev=None, skip_grain=-1):
         """flags[0:2] (int32, device) <- (#grain events, #switch candidates); with `range_word` (int32 [1]) flags[2] <- the
-        word, which is cleared; `E_dev` (int64 [1], device): the number of junction edges at RUN time; see ggnn.h."""
+        word, which is cleared; `E_dev` (int64 [1], device): the number of junction edges at RUN time; `skip_grain`: a
+        grain never counted (the no-flux boundary grain, 0; -1 = none); see ggnn.h."""
         _require_cuda(grain_area, live_grain, edge_event, edge_index_jj, flags, range_word, E_dev)
         if live_grain.dtype != torch.int32 or flags.dtype != torch.int32 or flags.numel() < (2 if range_word is None else 3):
             raise _lib.GGNNError("live_grain / flags must be int32 (flags: two words, three with a range word)")
         if range_word is not None and (range_word.dtype != torch.int32 or range_word.numel() < 1):
             raise _lib.GGNNError("range_word must be an int32 word")
-        check(self.lib.ggnn_detect_events_n(ptr(grain_area), ptr(live_grain), grain_area.numel(),
-                                            float(area_threshold), ptr(edge_event), ptr(edge_index_jj),
-                                            edge_index_jj.size(1), ptr(E_dev), float(logit_threshold), ptr(flags),
-                                            ptr(range_word), _lib.current_stream()), "ggnn_detect_events")
+        if skip_grain < 0:
+            check(self.lib.ggnn_detect_events_n(ptr(grain_area), ptr(live_grain), grain_area.numel(),
+                                                float(area_threshold), ptr(edge_event), ptr(edge_index_jj),
+                                                edge_index_jj.size(1), ptr(E_dev), float(logit_threshold), ptr(flags),
+                                                ptr(range_word), _lib.current_stream()), "ggnn_detect_events")
+        else:
+            check(self.lib.ggnn_detect_events_skip(ptr(grain_area), ptr(live_grain), grain_area.numel(),
+                                                   float(area_threshold), ptr(edge_event), ptr(edge_index_jj),
+                                                   edge_index_jj.size(1), ptr(E_dev), float(logit_threshold), ptr(flags),
+                                                   ptr(range_word), int(skip_grain), _lib.current_stream()),
+                  "ggnn_detect_events_skip")
 
     def step_refresh(self, x_joint, x_grain, zmax, flags, edges):
         """edges: list of (edge_index [2,E] int64, x_src, x_dst, edge_attr_out [E][, E_dev int64 [1] or None])."""
@@ -1011,6 +1088,13 @@ class HipBackend:
                                          ptr(x_grain), x_grain.size(0), x_grain.stride(0), zmax,
                                          ptr(flags), arr, len(edges), _lib.current_stream()),
               "ggnn_step_refresh")
+
+
+def _boundary_code(boundary):
+    codes = {"periodic": _lib.BC_PERIODIC, "noflux": _lib.BC_NOFLUX}
+    if boundary not in codes:
+        raise _lib.GGNNError(f"boundary must be 'periodic' or 'noflux', got {boundary!r}")
+    return codes[boundary]
 
 
 _default = None

@@ -17,7 +17,12 @@ namespace ggnn {
 constexpr int CSR_MAX_BATCH = 4;
 struct CsrBatch {
   ggnn_csr_args p[CSR_MAX_BATCH];
+  ggnn_csr_mask m[CSR_MAX_BATCH];   // (all -1 / NULL for ggnn_build_csr_batch)
 };
+// an edge of a masked list (ggnn_csr_mask) that the tables leave out
+__device__ __forceinline__ bool csr_skipped(const ggnn_csr_mask& M, int64_t s, int64_t d) {
+  return s == M.skip_src || d == M.skip_dst;
+}
 __device__ __forceinline__ int32_t* csr_counts(const ggnn_csr_args& P) { return reinterpret_cast<int32_t*>(P.workspace); }
 __device__ __forceinline__ int32_t* csr_cursor(const ggnn_csr_args& P) { return csr_counts(P) + P.n_dst + 1; }
 
@@ -25,6 +30,9 @@ __global__ __launch_bounds__(256) void csr_zero_batch_kernel(const CsrBatch B) {
   const ggnn_csr_args& P = B.p[blockIdx.y];
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < P.n_dst) csr_counts(P)[i] = 0;
+  // a masked list fills only its first rowptr[n_dst] slots: the rest of [0, E) holds valid indices (0), never stale words
+  const ggnn_csr_mask& M = B.m[blockIdx.y];
+  if ((M.skip_src >= 0 || M.skip_dst >= 0) && i < P.E) P.col[i] = P.perm[i] = P.row[i] = 0;
 }
 __global__ __launch_bounds__(256) void csr_count_batch_kernel(const CsrBatch B) {
   const ggnn_csr_args& P = B.p[blockIdx.y];
@@ -35,6 +43,7 @@ __global__ __launch_bounds__(256) void csr_count_batch_kernel(const CsrBatch B) 
     atomicOr(P.flags, 1);
     return;
   }
+  if (csr_skipped(B.m[blockIdx.y], s, d)) return;
   atomicAdd(&csr_counts(P)[d], 1);
 }
 // Single-workgroup exclusive scan over a list's n_dst counts (a few 10^4 here), one workgroup per list: writes out[0..n] and
@@ -74,7 +83,10 @@ __global__ __launch_bounds__(1024) void csr_scan_batch_kernel(const CsrBatch B) 
     if (tid == 1023) s_carry = carry + wave_off + incl;
     __syncthreads();
   }
-  if (tid == 0) out[n] = s_carry;
+  if (tid == 0) {
+    out[n] = s_carry;
+    if (!UNITS && B.m[blockIdx.x].E_kept) *B.m[blockIdx.x].E_kept = s_carry;
+  }
 }
 __global__ __launch_bounds__(256) void csr_fill_batch_kernel(const CsrBatch B) {
   const ggnn_csr_args& P = B.p[blockIdx.y];
@@ -82,6 +94,7 @@ __global__ __launch_bounds__(256) void csr_fill_batch_kernel(const CsrBatch B) {
   if (e >= P.E) return;
   const int64_t s = P.edge_index[e], d = P.edge_index[P.E + e];
   if ((uint64_t)s >= (uint64_t)P.n_src || (uint64_t)d >= (uint64_t)P.n_dst) return;
+  if (csr_skipped(B.m[blockIdx.y], s, d)) return;
   const int32_t pos = atomicAdd(&csr_cursor(P)[d], 1);
   P.perm[pos] = (int32_t)e;
 }
@@ -146,6 +159,11 @@ extern "C" int64_t ggnn_csr_max_units(int64_t E, int64_t n_dst) {
 }
 
 extern "C" int ggnn_build_csr_batch(const ggnn_csr_args* problems, int n_problems, ggnn_stream_t stream_) {
+  return ggnn_build_csr_masked_batch(problems, nullptr, n_problems, stream_);
+}
+
+extern "C" int ggnn_build_csr_masked_batch(const ggnn_csr_args* problems, const ggnn_csr_mask* masks, int n_problems,
+                                           ggnn_stream_t stream_) {
   using namespace ggnn;
   hipStream_t stream = (hipStream_t)stream_;
   if (!problems || n_problems < 1 || n_problems > CSR_MAX_BATCH) return GGNN_EINVAL;
@@ -153,7 +171,13 @@ extern "C" int ggnn_build_csr_batch(const ggnn_csr_args* problems, int n_problem
   int64_t max_E = 0, max_n = 0;
   for (int k = 0; k < CSR_MAX_BATCH; ++k) {
     B.p[k] = problems[k < n_problems ? k : 0];
+    B.m[k] = ggnn_csr_mask{-1, -1, nullptr};
     if (k >= n_problems) continue;
+    if (masks) {
+      const ggnn_csr_mask& M = masks[k];
+      if (M.skip_src < -1 || M.skip_dst < -1 || (M.E_kept && ((uintptr_t)M.E_kept & 7))) return GGNN_EINVAL;
+      B.m[k] = M;
+    }
     const ggnn_csr_args& P = B.p[k];
     if (P.E < 0 || P.n_src < 0 || P.n_dst <= 0 || !P.rowptr || !P.flags || !P.workspace) return GGNN_EINVAL;
     if (P.E > 0 && (!P.edge_index || !P.col || !P.perm || !P.row)) return GGNN_EINVAL;
@@ -165,7 +189,9 @@ extern "C" int ggnn_build_csr_batch(const ggnn_csr_args* problems, int n_problem
   }
   const unsigned ny = (unsigned)n_problems;
   const unsigned eb = (unsigned)((max_E + 255) / 256), nb = (unsigned)((max_n + 255) / 256);
-  hipLaunchKernelGGL(csr_zero_batch_kernel, dim3(nb, ny), dim3(256), 0, stream, B);
+  bool masked = false;
+  for (int k = 0; k < n_problems; ++k) masked = masked || B.m[k].skip_src >= 0 || B.m[k].skip_dst >= 0;
+  hipLaunchKernelGGL(csr_zero_batch_kernel, dim3(masked && eb > nb ? eb : nb, ny), dim3(256), 0, stream, B);
   if (max_E > 0) hipLaunchKernelGGL(csr_count_batch_kernel, dim3(eb, ny), dim3(256), 0, stream, B);
   hipLaunchKernelGGL(csr_scan_batch_kernel<false>, dim3(ny), dim3(1024), 0, stream, B);
   if (max_E > 0) hipLaunchKernelGGL(csr_fill_batch_kernel, dim3(eb, ny), dim3(256), 0, stream, B);

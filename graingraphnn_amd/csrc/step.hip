@@ -2,6 +2,7 @@
 //   ggnn_step_update  = GrainNN_regressor.update, periodic branch (models.py:503-516)
 //                       + z advance (test.py:401-402)
 //   ggnn_step_refresh = z clamp (test.py:405-407) + edge-length refresh (test.py:562-575)
+//   ggnn_noflux_boundary = the no-flux boundary step (test.py:446-463), after the topology update
 //   ggnn_grain_centres = region centres of graph.update() (graph_datastruct.py:681-708) written
 //                       to x_grain[:, :2] (test.py:468-478, 556-559), between the two
 // Separate launches because each stage needs every node's updated coordinates.
@@ -38,6 +39,8 @@ __global__ __launch_bounds__(256) void step_update_kernel(
 // One thread per grain: walk the grain's junctions (CSR row of the joint->grain edge type),
 // min-image each to the previous moved one, shift by +1 where any vertex is below -eps, mean.
 // ~6 junctions x 8 B per grain: the launch is latency-, not bandwidth-bound.
+// PERIODIC = false: the no-flux branch (graph_datastruct.py:689-692), no min-image chaining.
+template <bool PERIODIC>
 __global__ __launch_bounds__(256) void grain_centres_kernel(
     const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
     const float* __restrict__ x_joint, int64_t ldxj, const float* __restrict__ offset,
@@ -74,7 +77,7 @@ __global__ __launch_bounds__(256) void grain_centres_kernel(
 #pragma unroll
       for (int c = 0; c < 2; ++c) {
         float t = raw[k][c];
-        if (q0 + k > p0) {  // periodic_move, graph_datastruct.py:55-72
+        if (PERIODIC && q0 + k > p0) {  // periodic_move, graph_datastruct.py:55-72
           const float rel = t - prev[c];
           t += rel > 0.5f ? -1.0f : (rel < -0.5f ? 1.0f : 0.0f);
         }
@@ -105,13 +108,13 @@ __global__ __launch_bounds__(256) void detect_events_kernel(
     const float* __restrict__ grain_area, const int32_t* __restrict__ live_grain, int64_t n_grain,
     float area_threshold, const float* __restrict__ edge_event, const int64_t* __restrict__ ei_jj,
     int64_t E_cap, const int64_t* __restrict__ E_dev, float logit_threshold, int32_t* __restrict__ flags,
-    int32_t* __restrict__ range_word) {
+    int32_t* __restrict__ range_word, int64_t skip_grain) {
   const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t E = E_dev ? *E_dev : E_cap;   // (E_dev: include/ggnn.h, ggnn_prepare_edge)
   // (the caller's fp16-range word travels with the counts and starts its next use clean: one thread moves it)
   if (range_word != nullptr && t == 0) flags[2] = atomicExch(range_word, 0);
   bool g = false, e = false;
-  if (t < n_grain) g = live_grain[t] > 0 && grain_area[t] < area_threshold;
+  if (t < n_grain) g = t != skip_grain && live_grain[t] > 0 && grain_area[t] < area_threshold;
   else if (t - n_grain < E) {
     const int64_t k = t - n_grain;
     e = edge_event[k] > logit_threshold && ei_jj[k] < ei_jj[E + k];
@@ -120,6 +123,72 @@ __global__ __launch_bounds__(256) void detect_events_kernel(
   if ((threadIdx.x & 63) == 0) {
     if (ng) atomicAdd(&flags[0], ng);
     if (ne) atomicAdd(&flags[1], ne);
+  }
+}
+
+// The no-flux boundary step (test.py:446-463): one thread per junction.  Whether a junction is one of grain 0's (row 0 of
+// the full joint->grain CSR, a few dozen to a few hundred junctions on the walls) is looked up in LDS, one chunk of the
+// row at a time.  Every fp32 operation is rounded on its own, in the reference's order: torch evaluates
+// (xy + off) / f and xy * f - off as separate ops, which a contraction into an fma would not reproduce.
+constexpr int BND_CHUNK = 1024;
+__global__ __launch_bounds__(256) void noflux_boundary_kernel(
+    const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, float* __restrict__ x_joint, int64_t n_joint,
+    int64_t ldxj, const float* __restrict__ offset, float factor, float max_y, float* __restrict__ x_grain, int f_grain,
+    float* __restrict__ joints_before) {
+  __shared__ int32_t s_b[BND_CHUNK];
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (t == 0) {   // test.py:450-452
+    x_grain[0] = 0.5f;
+    x_grain[1] = 0.5f;
+    x_grain[3] = 0.0f;
+    x_grain[4] = 0.0f;
+    x_grain[f_grain - 1] = 0.0f;
+  }
+  const bool live = t < n_joint;
+  float xy[2] = {0.f, 0.f};
+  if (live) {
+    float* x = x_joint + t * ldxj;
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      const float v = x[c];
+      if (joints_before) joints_before[2 * t + c] = v;
+      xy[c] = __fdiv_rn(offset ? __fadd_rn(v, offset[2 * t + c]) : v, factor);   // test.py:453
+    }
+  }
+  const int32_t b0 = rowptr[0], b1 = rowptr[1];
+  bool bound = false;
+  for (int32_t q0 = b0; q0 < b1; q0 += BND_CHUNK) {   // (uniform trip count: every thread reaches the barriers)
+    const int32_t nq = min(BND_CHUNK, b1 - q0);
+    __syncthreads();
+    for (int k = threadIdx.x; k < nq; k += 256) s_b[k] = col[q0 + k];
+    __syncthreads();
+    if (live)
+      for (int k = 0; k < nq; ++k) bound = bound || s_b[k] == (int32_t)t;
+  }
+  if (!live) return;
+  if (bound) {   // move_to_boundary, test.py:58-71: torch.argmin keeps the first of equal minima
+    const float d[4] = {xy[0], __fsub_rn(1.0f, xy[0]), xy[1], __fsub_rn(max_y, xy[1])};
+    int k = 0;
+    float m = d[0];
+#pragma unroll
+    for (int i = 1; i < 4; ++i)
+      if (d[i] < m) {
+        m = d[i];
+        k = i;
+      }
+    if (k == 0) xy[0] = 0.0f;
+    else if (k == 1) xy[0] = 1.0f;
+    else if (k == 2) xy[1] = 0.0f;
+    else xy[1] = max_y;
+  }
+  const float hi[2] = {1.0f, max_y};   // test.py:461-462
+  float* x = x_joint + t * ldxj;
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    float v = xy[c];
+    v = v < 0.0f ? 0.0f : (v > hi[c] ? hi[c] : v);
+    const float w = __fmul_rn(v, factor);   // test.py:466
+    x[c] = offset ? __fsub_rn(w, offset[2 * t + c]) : w;
   }
 }
 
@@ -197,9 +266,44 @@ extern "C" int ggnn_grain_centres(const int32_t* rowptr, const int32_t* col, con
   if (!(domain_factor >= 1.0f)) return GGNN_EINVAL;
   const int64_t nblk = (n_grain + 255) / 256;
   if (nblk >= INT32_MAX) return GGNN_EINVAL;
-  hipLaunchKernelGGL(grain_centres_kernel, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(grain_centres_kernel<true>, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream,
                      rowptr, col, x_joint, ldx_joint, domain_offset, domain_factor, x_grain,
                      ldx_grain, n_grain, n_joint, centres_before);
+  return launch_status();
+}
+
+extern "C" int ggnn_grain_centres_bc(const int32_t* rowptr, const int32_t* col, const float* x_joint, int64_t n_joint,
+                                     int64_t ldx_joint, const float* domain_offset, float domain_factor, float* x_grain,
+                                     int64_t n_grain, int64_t ldx_grain, float* centres_before, int boundary,
+                                     ggnn_stream_t stream) {
+  using namespace ggnn;
+  if (boundary == GGNN_BC_PERIODIC)
+    return ggnn_grain_centres(rowptr, col, x_joint, n_joint, ldx_joint, domain_offset, domain_factor, x_grain, n_grain,
+                              ldx_grain, centres_before, stream);
+  if (boundary != GGNN_BC_NOFLUX) return GGNN_EINVAL;
+  if (!rowptr || !col || !x_joint || !x_grain) return GGNN_EINVAL;
+  if (n_joint <= 0 || n_grain <= 0 || ldx_joint < 2 || ldx_grain < 2) return GGNN_EINVAL;
+  if (!(domain_factor >= 1.0f)) return GGNN_EINVAL;
+  const int64_t nblk = (n_grain + 255) / 256;
+  if (nblk >= INT32_MAX) return GGNN_EINVAL;
+  hipLaunchKernelGGL(grain_centres_kernel<false>, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream,
+                     rowptr, col, x_joint, ldx_joint, domain_offset, domain_factor, x_grain,
+                     ldx_grain, n_grain, n_joint, centres_before);
+  return launch_status();
+}
+
+extern "C" int ggnn_noflux_boundary(const int32_t* rowptr_jg, const int32_t* col_jg, float* x_joint, int64_t n_joint,
+                                    int64_t ldx_joint, const float* domain_offset, float domain_factor, float max_y,
+                                    float* x_grain, int64_t ldx_grain, int f_grain, float* joints_before,
+                                    ggnn_stream_t stream) {
+  using namespace ggnn;
+  if (!rowptr_jg || !col_jg || !x_joint || !x_grain || n_joint <= 0) return GGNN_EINVAL;
+  if (ldx_joint < 2 || f_grain < 6 || ldx_grain < f_grain) return GGNN_EINVAL;
+  if (!(domain_factor >= 1.0f) || !(max_y > 0.0f)) return GGNN_EINVAL;
+  const int64_t nblk = (n_joint + 255) / 256;
+  if (nblk >= INT32_MAX) return GGNN_EINVAL;
+  hipLaunchKernelGGL(noflux_boundary_kernel, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, rowptr_jg, col_jg,
+                     x_joint, n_joint, ldx_joint, domain_offset, domain_factor, max_y, x_grain, f_grain, joints_before);
   return launch_status();
 }
 
@@ -215,6 +319,14 @@ extern "C" int ggnn_detect_events_n(const float* grain_area, const int32_t* live
                                     float area_threshold, const float* edge_event, const int64_t* edge_index_jj,
                                     int64_t E, const int64_t* E_dev, float logit_threshold, int32_t* flags,
                                     int32_t* range_word, ggnn_stream_t stream) {
+  return ggnn_detect_events_skip(grain_area, live_grain, n_grain, area_threshold, edge_event, edge_index_jj, E, E_dev,
+                                 logit_threshold, flags, range_word, -1, stream);
+}
+
+extern "C" int ggnn_detect_events_skip(const float* grain_area, const int32_t* live_grain, int64_t n_grain,
+                                       float area_threshold, const float* edge_event, const int64_t* edge_index_jj,
+                                       int64_t E, const int64_t* E_dev, float logit_threshold, int32_t* flags,
+                                       int32_t* range_word, int64_t skip_grain, ggnn_stream_t stream) {
   using namespace ggnn;
   if (!grain_area || !live_grain || !flags || n_grain <= 0 || E < 0) return GGNN_EINVAL;
   if (E > 0 && (!edge_event || !edge_index_jj)) return GGNN_EINVAL;
@@ -223,7 +335,7 @@ extern "C" int ggnn_detect_events_n(const float* grain_area, const int32_t* live
   if (hipMemsetAsync(flags, 0, (range_word ? 3 : 2) * sizeof(int32_t), (hipStream_t)stream) != hipSuccess) return GGNN_ELAUNCH;
   hipLaunchKernelGGL(detect_events_kernel, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream,
                      grain_area, live_grain, n_grain, area_threshold, edge_event, edge_index_jj, E, E_dev,
-                     logit_threshold, flags, range_word);
+                     logit_threshold, flags, range_word, skip_grain);
   return launch_status();
 }
 

@@ -17,22 +17,50 @@ from .packing import C, EDGE_TYPES, NODE_TYPES, PackedCell
 ET = Tuple[str, str, str]
 
 
+JG = ("joint", "pull", "grain")
+# no-flux boundary (test.py:363-375): the forwards see the lists without grain 0's edges -- grain->joint without source 0,
+# joint->grain without destination 0 -- in the masked tables of ggnn_build_csr_masked_batch
+NOFLUX_MASKS = {("grain", "push", "joint"): (0, -1), JG: (-1, 0), ("joint", "connect", "joint"): None}
+
+
 class GraphCSR:
     """Destination-grouped neighbour lists of the three edge types of one topology."""
 
-    def __init__(self, backend, edge_index_dict, n_nodes: Dict[str, int], trusted: bool = False, into=None, counts=None):
+    def __init__(self, backend, edge_index_dict, n_nodes: Dict[str, int], trusted: bool = False, into=None, counts=None,
+                 boundary: str = "periodic"):
         """trusted: the lists come from the library's own topology update (validated on the host, topology.py): the
         range check of the build -- a read-back, i.e. a host synchronisation -- is skipped.
         into = a backend.CsrInPlace: the tables are refilled IN PLACE (same device tensors, same addresses);
-        counts = {et: int64 [1] device tensor}: where the per-edge kernels find the number of edges at run time (CSR.E_dev)."""
+        counts = {et: int64 [1] device tensor}: where the per-edge kernels find the number of edges at run time (CSR.E_dev).
+        boundary = "noflux": `csr` holds the FORWARD graph (NOFLUX_MASKS; a masked table's E_dev is its kept-edge count)
+        and `csr_full[JG]` the full joint->grain table (grain centres, boundary step), built in the same launches (`into`
+        then has four lists); `edge_index` stays the full lists (the topology).  `count_dev[et]`: the device word with the
+        length of the full list edge_index[et] (or None)."""
         self.csr = {}
         self.edge_index = {}
         self.n_nodes = dict(n_nodes)
+        self.boundary = boundary
         for et in EDGE_TYPES:
             if et not in edge_index_dict:
                 raise KeyError(f"edge_index_dict lacks edge type {et}")
             self.edge_index[et] = edge_index_dict[et].contiguous()
         lists = [(self.edge_index[et], n_nodes[et[0]], n_nodes[et[-1]]) for et in EDGE_TYPES]
+        self.count_dev = {et: None if counts is None else counts[et] for et in EDGE_TYPES}
+        if boundary == "noflux":
+            masks = [NOFLUX_MASKS[et] for et in EDGE_TYPES] + [None]
+            lists.append((self.edge_index[JG], n_nodes["joint"], n_nodes["grain"]))
+            if into is not None:
+                built = into.rebuild([l[0] for l in lists])
+                for k, et in enumerate(EDGE_TYPES + (JG,)):
+                    if masks[k] is None:
+                        built[k].E_dev = self.count_dev[et]
+            else:
+                built = backend.build_csr_batch(lists, check=not trusted, masks=masks)
+            self.csr = dict(zip(EDGE_TYPES, built[:3]))
+            self.csr_full = {JG: built[3]}
+            return
+        if boundary != "periodic":
+            raise _lib.GGNNError(f"boundary must be 'periodic' or 'noflux', got {boundary!r}")
         if into is not None:   # a backend.CsrInPlace: the same tables, refilled
             built = into.rebuild([l[0] for l in lists])
             for et, csr in zip(EDGE_TYPES, built):
@@ -42,6 +70,7 @@ class GraphCSR:
         else:
             built = [backend.build_csr(*l) for l in lists]
         self.csr = dict(zip(EDGE_TYPES, built))
+        self.csr_full = self.csr
 
     def n_edges(self, et):
         return self.edge_index[et].size(1)
@@ -51,15 +80,17 @@ _graph_cache: Dict[tuple, GraphCSR] = {}
 _GRAPH_CACHE_MAX = 8
 
 
-def graph_for(backend, edge_index_dict, n_nodes, trusted: bool = False) -> GraphCSR:
+def graph_for(backend, edge_index_dict, n_nodes, trusted: bool = False, boundary: str = "periodic") -> GraphCSR:
     """CSR of `edge_index_dict`, rebuilt only when a tensor is replaced or modified in place
     (Cmodel.update swaps the tensors after a topological event, models.py:841-845)."""
     key = tuple((et, edge_index_dict[et].data_ptr(), edge_index_dict[et]._version,
                  tuple(edge_index_dict[et].shape)) for et in EDGE_TYPES if et in edge_index_dict)
     key = key + tuple(sorted(n_nodes.items()))
+    if boundary != "periodic":
+        key = key + (boundary,)
     g = _graph_cache.get(key)
     if g is None:
-        g = GraphCSR(backend, edge_index_dict, n_nodes, trusted)
+        g = GraphCSR(backend, edge_index_dict, n_nodes, trusted, boundary=boundary)
         if len(_graph_cache) >= _GRAPH_CACHE_MAX:
             _graph_cache.pop(next(iter(_graph_cache)))
         _graph_cache[key] = g

@@ -26,6 +26,7 @@ from .packing import EDGE_TYPES, NODE_TYPES, pack_classifier_heads, pack_regress
 
 TRAIN_FRAMES = 120  # test.py:190
 ET_JJ = ("joint", "connect", "joint")
+JG = ("joint", "pull", "grain")
 
 
 class GrainRollout:
@@ -35,7 +36,7 @@ class GrainRollout:
                  edge_attr_dict, span: int, use_graph: bool = False, concurrent: bool = True,
                  refresh_centres: bool = False,
                  domain_factor: float = 1.0, domain_offset: Optional[torch.Tensor] = None,
-                 joint_launches: Optional[bool] = None):
+                 joint_launches: Optional[bool] = None, boundary: str = "periodic", max_y: float = 1.0):
         """refresh_centres: also recompute x_grain[:, :2] from the junction polygons every step,
         like the reference's traj.GNN_update + test.py:556-559 (default off = the static-geometry
         goldens).  domain_factor / domain_offset: `geometry_scaling` of test.py:310-312 when the
@@ -46,7 +47,15 @@ class GrainRollout:
         joint launches below JOINT_LAUNCH_MAX_JOINTS junctions, where a step is launch-bound
         (cfg2: 0.139 vs 0.162 ms per step); above it every kernel fills the chip by itself and the
         two-stream plan wins by overlapping kernels of different kinds -- one model's matrix-bound
-        projection beside the other's memory-bound sweep (cfg3: 0.61 vs 0.66 ms per step)."""
+        projection beside the other's memory-bound sweep (cfg3: 0.61 vs 0.66 ms per step).
+        boundary: "periodic" (default) or "noflux" -- grain 0 is the boundary grain that wraps the domain (the reference's
+        traj.BC == 'noflux', test.py:363-375, 418-422, 446-463): both forwards see the lists without grain 0's edges,
+        grain 0 never takes part in events, and after every step's topology update the boundary step resets grain 0 and
+        pins the junctions to [0,1] x [0,max_y] ("No-flux boundary")."""
+        if boundary not in ("periodic", "noflux"):
+            raise _lib.GGNNError(f"boundary must be 'periodic' or 'noflux', got {boundary!r}")
+        self.boundary, self.max_y = boundary, float(max_y)
+        self.noflux = boundary == "noflux"
         self.be = default_backend()
         self.rmodel, self.cmodel = rmodel, cmodel
         self.x = {nt: x_dict[nt] for nt in NODE_TYPES}  # mutated in place, like the reference
@@ -95,7 +104,7 @@ class GrainRollout:
         self.refresh_centres = refresh_centres
         self.domain_factor = float(domain_factor)
         self.domain_offset = None
-        if refresh_centres and self.domain_factor > 1:
+        if (refresh_centres or self.noflux) and self.domain_factor > 1:
             if domain_offset is None:
                 raise _lib.GGNNError("domain_factor > 1 needs domain_offset")
             self.domain_offset = domain_offset.to(dev, torch.float32).contiguous()
@@ -152,7 +161,7 @@ class GrainRollout:
             self._cap = None   # (a caller's own topology, or one that grew: back to buffers of its own; the segment graphs go)
             self._drop_segment_graphs()
         self.edge_index = {et: edge_index_dict[et] for et in EDGE_TYPES}
-        self.graph = graph_for(self.be, self.edge_index, self.n_nodes, trusted)
+        self.graph = graph_for(self.be, self.edge_index, self.n_nodes, trusted, self.boundary)
         if trusted and edge_attr_dict is None:
             return self._set_topology_buffers_from_one_allocation(dev)
         if edge_attr_dict is not None:
@@ -170,6 +179,7 @@ class GrainRollout:
         self.pred["edge_event"] = torch.empty(E, dtype=torch.float32, device=dev)
         self.pred["edge"] = torch.empty(E, 2, dtype=torch.float32, device=dev)
         self.einfo = alloc_einfo(self.graph, dev)
+        self._zero_records(self.einfo)
         # second set of edge records (_enqueue_steps_overlapped): made on first use; the classifier's copies of x keep
         # their buffers (the node sets never change) but no longer mirror x
         self._einfo_other = None
@@ -199,6 +209,7 @@ class GrainRollout:
         shape = lambda et: (E[et] + _lib.GGNN_UNIT_EDGES, _lib.GGNN_EINFO_ROW)
         self.einfo = {et: take(rec[et], shape(et)) for et in EDGE_TYPES}
         self._einfo_other = {et: take(rec[et], shape(et)) for et in EDGE_TYPES}
+        self._zero_records(self.einfo, self._einfo_other)
         self._einfo_fresh = False
         self.pred["edge_event"] = take(E[ET_JJ])
         self.pred["edge"] = take(2 * E[ET_JJ], (E[ET_JJ], 2))
@@ -231,9 +242,11 @@ class GrainRollout:
         old_ea = {et: self.edge_attr[et] for et in EDGE_TYPES}
         old_ei = {et: self.edge_index[et] for et in EDGE_TYPES}
         self._cap = {
-            "cap": cap, "off": off, "buf": torch.empty(at, dtype=torch.float32, device=dev),
+            # (noflux: a masked table's records end before the capacity; the sweeps' clamps may read the rest as padding,
+            # which must be finite: zeros until a record is written there)
+            "cap": cap, "off": off, "buf": (torch.zeros if self.noflux else torch.empty)(at, dtype=torch.float32, device=dev),
             "lists": {et: torch.empty(2 * max(cap[et], 1), dtype=torch.int64, device=dev) for et in EDGE_TYPES},
-            "csr": be.csr_in_place([(cap[et], self.n_nodes[et[0]], self.n_nodes[et[-1]]) for et in EDGE_TYPES], dev),
+            "csr": self._csr_in_place(be, cap, dev),
             "counts": torch.zeros(len(EDGE_TYPES), dtype=torch.int64, device=dev),
             "counts_host": torch.zeros(len(EDGE_TYPES), dtype=torch.int64).pin_memory(),
         }
@@ -259,7 +272,8 @@ class GrainRollout:
         C["counts"].copy_(C["counts_host"], non_blocking=True)
         counts = {et: C["counts"][k:k + 1] for k, et in enumerate(EDGE_TYPES)}
         from .engine import GraphCSR
-        self.graph = GraphCSR(self.be, self.edge_index, self.n_nodes, trusted=True, into=C["csr"], counts=counts)
+        self.graph = GraphCSR(self.be, self.edge_index, self.n_nodes, trusted=True, into=C["csr"], counts=counts,
+                              boundary=self.boundary)
         buf, off = C["buf"], C["off"]
         cut = lambda name, n, shape=None: buf[off[name]:off[name] + n] if shape is None else buf[off[name]:off[name] + n].view(shape)
         rows = lambda et: E[et] + _lib.GGNN_UNIT_EDGES
@@ -295,6 +309,36 @@ class GrainRollout:
         self._xc_fresh = False
         if getattr(self, "_spec", None) is not None:
             self._spec["xs_valid"] = None
+
+    # -- no-flux boundary ------------------------------------------------------------------
+    def _csr_in_place(self, be, cap, dev):
+        """The in-place CSR tables of the event loop: the three edge types, and for the no-flux boundary the forward's
+        masked grain tables plus the full joint->grain table (engine.GraphCSR)."""
+        shapes = [(cap[et], self.n_nodes[et[0]], self.n_nodes[et[-1]]) for et in EDGE_TYPES]
+        if not self.noflux:
+            return be.csr_in_place(shapes, dev)
+        from .engine import NOFLUX_MASKS
+        return be.csr_in_place(shapes + [(cap[JG], self.n_nodes["joint"], self.n_nodes["grain"])], dev,
+                               [NOFLUX_MASKS[et] for et in EDGE_TYPES] + [None])
+
+    def _zero_records(self, *sets):
+        """noflux: edge records of masked tables end before the list's length; what lies behind must be finite."""
+        if self.noflux:
+            for d in sets:
+                for t in d.values():
+                    t.zero_()
+
+    def _enqueue_boundary(self, joints_before=None):
+        """test.py:446-463 (noflux only): grain 0 reset, its junctions onto the walls, every junction into the domain."""
+        if self.noflux:
+            self.be.noflux_boundary(self.graph.csr_full[JG], self.x["joint"], self.x["grain"], self.domain_factor,
+                                    self.domain_offset, self.max_y, joints_before)
+
+    def _enqueue_centres(self, centres_before=None):
+        """graph.update()'s region centres + test.py:556-559 (refresh_centres); noflux: from the full joint->grain table,
+        without min-image chaining."""
+        self.be.grain_centres(self.graph.csr_full[JG], self.x["joint"], self.x["grain"], self.domain_factor,
+                              self.domain_offset, centres_before=centres_before, boundary=self.boundary)
 
     # -- one step, enqueued on the current stream --------------------------------------
     def _pipelined(self):
@@ -355,9 +399,9 @@ class GrainRollout:
             # heads + Rmodel.update in one launch; z clamp + edge lengths + next records in one launch
             be.heads_regressor_update(hr["joint"], hr["grain"], x["joint"], x["grain"], self.w_reg[0], self.w_reg[1],
                                       p["joint"], p["grain"], p["grain_area"], self.dz, self.zmax, self.flags)
+            self._enqueue_boundary()
             if self.refresh_centres:
-                be.grain_centres(self.graph.csr[("joint", "pull", "grain")], x["joint"], x["grain"],
-                                 self.domain_factor, self.domain_offset)
+                self._enqueue_centres()
             be.step_refresh_prepare(x["joint"], x["grain"], self.zmax, self.flags,
                                     [(self.graph.csr[et], ea_next[et], x[et[0]], x[et[-1]], einfo[et])
                                      for et in EDGE_TYPES])
@@ -373,6 +417,7 @@ class GrainRollout:
         if self._pipelined() and self.overlap_tail:
             if self._einfo_other is None:
                 self._einfo_other = alloc_einfo(self.graph, self.x["joint"].device)
+                self._zero_records(self._einfo_other)
             if self._xc is None:
                 self._xc = {nt: torch.empty_like(self.x[nt]) for nt in NODE_TYPES}
                 self._xc_other = {nt: torch.empty_like(self.x[nt]) for nt in NODE_TYPES}
@@ -436,9 +481,9 @@ class GrainRollout:
             # heads + Rmodel.update in one launch; z clamp + edge lengths + next records + next copy of x in one launch
             be.heads_regressor_update(hr["joint"], hr["grain"], x["joint"], x["grain"], self.w_reg[0], self.w_reg[1],
                                       p["joint"], p["grain"], p["grain_area"], self.dz, self.zmax, self.flags)
+            self._enqueue_boundary()
             if self.refresh_centres:
-                be.grain_centres(self.graph.csr[("joint", "pull", "grain")], x["joint"], x["grain"],
-                                 self.domain_factor, self.domain_offset)
+                self._enqueue_centres()
             if headed_prev is not None:
                 main.wait_event(headed_prev)   # the previous step's classifier has read the set this refresh writes
             be.step_refresh_prepare(x["joint"], x["grain"], self.zmax, self.flags,
@@ -528,13 +573,14 @@ class GrainRollout:
         be.step_update(x["joint"], x["grain"], p["joint"], p["grain"], self.dz, self.zmax, self.flags)
 
     def _enqueue_refresh(self):
-        """test.py:405-407, 468-478 + 556-559, 562-575: z clamp, grain centres, edge lengths."""
+        """test.py:405-407, [446-463 noflux], 468-478 + 556-559, 562-575: z clamp, boundary step, grain centres, edge
+        lengths (of the full lists)."""
         be, x, ea = self.be, self.x, self.edge_attr
+        self._enqueue_boundary()
         if self.refresh_centres:
-            be.grain_centres(self.graph.csr[("joint", "pull", "grain")], x["joint"], x["grain"],
-                             self.domain_factor, self.domain_offset)
+            self._enqueue_centres()
         be.step_refresh(x["joint"], x["grain"], self.zmax, self.flags,
-                        [(self.graph.edge_index[et], x[et[0]], x[et[-1]], ea[et], self.graph.csr[et].E_dev) for et in EDGE_TYPES])
+                        [(self.graph.edge_index[et], x[et[0]], x[et[-1]], ea[et], self.graph.count_dev[et]) for et in EDGE_TYPES])
 
     def _capture(self, n_steps: int = 1):
         """Record `n_steps` steps into a hipGraph (torch.cuda.CUDAGraph is hipGraph on ROCm); the
@@ -608,6 +654,10 @@ class GrainRollout:
         self.grain_events, self.switched = [], []
         self._enter_capacity_mode()
 
+    def _skip_grain(self):
+        """The grain that never takes part in events: the no-flux boundary grain (test.py:421-422), or none."""
+        return 0 if self.noflux else -1
+
     def _drop_segment_graphs(self):
         """The hipGraphs of step_events()' two segments, all variants (one per set of buffers they were captured on)."""
         self._graph_fwd = self._graph_ref = None
@@ -663,7 +713,7 @@ class GrainRollout:
         self._run_segment("fwd")
         p = self.pred
         self.be.detect_events(p["grain_area"], self._live_grain, self.area_threshold, p["edge_event"],
-                              self.graph.edge_index[ET_JJ], self._logit_trigger, self._ev_flags)
+                              self.graph.edge_index[ET_JJ], self._logit_trigger, self._ev_flags, skip_grain=self._skip_grain())
         self._ev_host.copy_(self._ev_flags, non_blocking=True)
         # behind an eventful step the next one is eventful too, on the reference's trajectories (README.md:68-69: events at
         # nearly every step): what the rewiring reads travels to the host behind the counts, one synchronisation instead of two
@@ -726,6 +776,7 @@ class GrainRollout:
                     "flat": torch.empty(3 * D * Ea, dtype=torch.float32, device=dev),
                     "xs": [{nt: torch.empty_like(self.x[nt]) for nt in NODE_TYPES} for _ in range(D)],
                     "cen": [torch.empty(self.n_nodes["grain"], 2, device=dev) for _ in range(D)],
+                    "jb": [torch.empty(self.n_nodes["joint"], 2, device=dev) for _ in range(D)],
                     "evf": [torch.zeros(4, dtype=torch.int32, device=dev) for _ in range(D)],
                     "evh": [torch.zeros(4, dtype=torch.int32).pin_memory() for _ in range(D)],
                     "zf": [torch.zeros(2, dtype=torch.int32, device=dev) for _ in range(D)],
@@ -750,7 +801,7 @@ class GrainRollout:
         if S is not None and S["D"] == D:
             # a new topology (after an event): the per-node slots, the centre snapshots and the (pinned) count words stay --
             # the node sets never change -- only the per-edge predictions follow the new edge list
-            keep = {k: S[k] for k in ("xs", "cen", "evf", "evh", "zf", "rw")}
+            keep = {k: S[k] for k in ("xs", "cen", "jb", "evf", "evh", "zf", "rw")}
             E = self.pred["edge_event"].numel()
             Ea = (E + 3) & ~3                                                     # (16-byte aligned segments)
             flat = torch.empty(3 * D * Ea, dtype=torch.float32, device=dev)   # one allocation for all slots
@@ -761,6 +812,7 @@ class GrainRollout:
         else:
             keep = {"xs": [{nt: torch.empty_like(self.x[nt]) for nt in NODE_TYPES} for _ in range(D)],
                     "cen": [torch.empty(self.n_nodes["grain"], 2, device=dev) for _ in range(D)],
+                    "jb": [torch.empty(self.n_nodes["joint"], 2, device=dev) for _ in range(D)],
                     "evf": [torch.zeros(4, dtype=torch.int32, device=dev) for _ in range(D)],
                     "evh": [torch.zeros(4, dtype=torch.int32).pin_memory() for _ in range(D)],
                     "zf": [torch.zeros(2, dtype=torch.int32, device=dev) for _ in range(D)],
@@ -805,11 +857,12 @@ class GrainRollout:
         be.heads_regressor_update(hr["joint"], hr["grain"], x["joint"], x["grain"], self.w_reg[0], self.w_reg[1],
                                   p["joint"], p["grain"], p["grain_area"], self.dz, self.zmax, zf)
         updated.record(main)
-        if self.refresh_centres:   # (the snapshot of the centres the events must see rides with the launch that replaces them)
-            be.grain_centres(self.graph.csr[("joint", "pull", "grain")], x["joint"], x["grain"],
-                             self.domain_factor, self.domain_offset, centres_before=S["cen"][slot])
-        else:
+        if not self.refresh_centres:
             S["cen"][slot].copy_(x["grain"][:, :2])
+        # (noflux: the junctions as the step's events must see them -- before the boundary step -- ride with it)
+        self._enqueue_boundary(joints_before=S["jb"][slot] if self.noflux else None)
+        if self.refresh_centres:   # (the snapshot of the centres the events must see rides with the launch that replaces them)
+            self._enqueue_centres(centres_before=S["cen"][slot])
         if headed_prev is not None:
             main.wait_event(headed_prev)   # the previous step's classifier has read the edge set this refresh writes
         be.step_refresh_prepare(x["joint"], x["grain"], self.zmax, zf,
@@ -821,7 +874,7 @@ class GrainRollout:
             # (the slot's range word travels in flags[2] and is cleared by the same launch: it is sticky on the device)
             be.detect_events(p["grain_area"], self._live_grain, self.area_threshold, p["edge_event"],
                              self.graph.edge_index[ET_JJ], self._logit_trigger, S["evf"][slot], S["rw"][slot],
-                             E_dev=self.graph.csr[ET_JJ].E_dev)
+                             E_dev=self.graph.csr[ET_JJ].E_dev, skip_grain=self._skip_grain())
             S["evh"][slot].copy_(S["evf"][slot], non_blocking=True)
         return [ready, lead, updated, headed]
 
@@ -959,8 +1012,13 @@ class GrainRollout:
                 self._einfo_fresh = False
             keep_centres = self.x["grain"][:, :2].clone()
             self.x["grain"][:, :2].copy_(S["cen"][slot])     # the centres the events must see: before the refresh
+            if self.noflux:   # ... and the junctions: before the boundary step
+                keep_joints = self.x["joint"][:, :2].clone()
+                self.x["joint"][:, :2].copy_(S["jb"][slot])
             def stands():   # the step stands as enqueued (its refresh ran on the unchanged topology)
                 self.x["grain"][:, :2].copy_(keep_centres)
+                if self.noflux:
+                    self.x["joint"][:, :2].copy_(keep_joints)
                 if void:   # ... but its edge lengths were overwritten by the void steps: the same kernel on the same x
                     self.be.step_refresh(self.x["joint"], self.x["grain"], self.zmax, self.flags,
                                          [(self.graph.edge_index[et], self.x[et[0]], self.x[et[-1]], self.edge_attr[et])
@@ -1061,6 +1119,8 @@ class GrainRollout:
         live = self.mask["grain"][:, 0] > 0
         ge = np.flatnonzero(live & (area < np.float32(self.area_threshold)))
         ge = ge[np.argsort(area[ge], kind="stable")]                         # test.py:418-420
+        if self.noflux:
+            ge = ge[ge != 0]                                                  # test.py:421-422
         if getattr(self, "max_grain_events", None) is not None:   # probe hook (tests/bench_event_step.py): random weights
             ge = ge[:int(self.max_grain_events)]                  # tie the predicted areas of hundreds of grains
         # (the session ignores edges at or below the threshold and the (dst, src) twin of every pair: with no grain below
@@ -1170,4 +1230,11 @@ class GrainRollout:
         return {"joint_xy": self.x["joint"][:, :2].clone(), "grain_area_v": self.x["grain"][:, 3:5].clone()}
 
     def edge_attr_dict(self):
+        if self.noflux:
+            # the step's fused refresh writes the lengths of the forward's edges (the masked tables' slots); grain 0's
+            # edges of the full lists get theirs here -- the same kernel expression, z clamp off
+            off = torch.zeros(2, dtype=torch.int32, device=self.x["joint"].device)
+            self.be.step_refresh(self.x["joint"], self.x["grain"], self.zmax, off,
+                                 [(self.edge_index[et], self.x[et[0]], self.x[et[-1]], self.edge_attr[et])
+                                  for et in EDGE_TYPES])
         return {et: self.edge_attr[et].view(-1, 1) for et in EDGE_TYPES}

@@ -44,10 +44,13 @@ def edge_lengths(x_dict, edge_index_dict):
     return out
 
 
-def scale_feature_patchs(factor: float, x, ea):
-    """Host-side data preparation of test.py:29-55 (periodic BC) on numpy fp32 dicts, in place:
+def scale_feature_patchs(factor: float, x, ea, boundary: str = "periodic"):
+    """Host-side data preparation of test.py:29-55 on numpy fp32 dicts, in place:
     fold a `factor`-times larger domain onto unit training-size patches.  Returns the
-    junctions' `domain_offset` [n_joint, 2] that the grain-centre refresh needs (test.py:474)."""
+    junctions' `domain_offset` [n_joint, 2] that the grain-centre refresh needs (test.py:474).
+    boundary="noflux": the grains' offset is floor(xy) (test.py:50-51) instead of xy - xy % 1."""
+    if boundary not in ("periodic", "noflux"):
+        raise ValueError(f"boundary must be 'periodic' or 'noflux', got {boundary!r}")
     f = np.float32(factor)
     for et in ea:
         ea[et] *= f
@@ -55,8 +58,28 @@ def scale_feature_patchs(factor: float, x, ea):
     x["joint"][:, :2] *= f
     domain_offset = np.floor(x["joint"][:, :2])
     x["joint"][:, :2] -= domain_offset
-    x["grain"][:, :2] -= x["grain"][:, :2] - np.mod(x["grain"][:, :2], np.float32(1))
+    if boundary == "noflux":
+        x["grain"][:, :2] -= np.floor(x["grain"][:, :2])
+    else:
+        x["grain"][:, :2] -= x["grain"][:, :2] - np.mod(x["grain"][:, :2], np.float32(1))
     return domain_offset.astype(np.float32)
+
+
+def noflux_forward_edges(edge_index_dict, edge_attr_dict):
+    """The lists both forwards see under the no-flux boundary (test.py:363-375): every grain->* edge from grain 0 and
+    every *->grain edge into grain 0 removed, column order kept; junction-junction lists untouched.  For callers of the
+    drop-in models' forward(); GrainRollout(boundary="noflux") does this on the device (masked CSR tables)."""
+    ei, ea = dict(edge_index_dict), dict(edge_attr_dict)
+    for et, index in edge_index_dict.items():
+        keep = None
+        if et[0] == "grain":
+            keep = index[0] > 0
+        if et[-1] == "grain":
+            keep = index[1] > 0
+        if keep is not None:
+            ei[et] = index[:, keep]
+            ea[et] = edge_attr_dict[et][keep]
+    return ei, ea
 
 
 def honeycomb(n: int = 100, fold: int = 10, seed: int = 0, shuffle_edges: bool = True,

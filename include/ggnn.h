@@ -94,6 +94,21 @@ typedef struct ggnn_csr_args {
   size_t workspace_bytes;
 } ggnn_csr_args;
 int ggnn_build_csr_batch(const ggnn_csr_args* problems, int n_problems, ggnn_stream_t stream);
+/* Masked build (no-flux boundary, additive to ABI 25): the tables of the list WITHOUT every edge whose source equals
+ * skip_src or whose destination equals skip_dst (-1 = none) -- the copies of test.py:363-375 that both forwards see when
+ * grain 0 is the boundary grain (skip_src = 0 for grain->joint, skip_dst = 0 for joint->grain).  Inside a row the slots
+ * stay in original-edge order (the order `index[:, mask]` produces); perm maps every slot to its edge id in the FULL
+ * list, so ggnn_edge_prepare reads the full list's edge_attr and writes the filtered records.  The kept slots are
+ * [0, rowptr[n_dst]); the rest of col / perm / row up to E is written with zeros.  E_kept (NULL = none, 8-byte aligned):
+ * receives rowptr[n_dst] as an int64 device word -- the E_dev of the per-edge kernels (ggnn_prepare_edge.E_dev) that
+ * read this table, whose launches are sized for E.  masks == NULL: ggnn_build_csr_batch.  An in-place refill of the
+ * same tables (the event loop) passes the same mask again. */
+typedef struct ggnn_csr_mask {
+  int64_t skip_src, skip_dst;
+  int64_t* E_kept;
+} ggnn_csr_mask;
+int ggnn_build_csr_masked_batch(const ggnn_csr_args* problems, const ggnn_csr_mask* masks, int n_problems,
+                                ggnn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Per-edge record in CSR order, computed once per forward and shared by every gate of the
@@ -589,6 +604,34 @@ int ggnn_detect_events_n(const float* grain_area, const int32_t* live_grain, int
                          float area_threshold, const float* edge_event, const int64_t* edge_index_jj,
                          int64_t E, const int64_t* E_dev, float logit_threshold, int32_t* flags,
                          int32_t* range_word, ggnn_stream_t stream);
+/* --- No-flux boundary (test.py:446-466, graph_datastruct.py:689-708 with traj.BC == 'noflux'; additive to ABI 25) ---
+ * Grain 0 is the boundary grain that wraps the domain.
+ * ggnn_noflux_boundary = the boundary step of test.py:446-463, one launch, after the topology update and before the
+ * grain centres:  x_grain[0, 0:2] = 0.5, x_grain[0, 3:5] = 0, x_grain[0, f_grain-1] = 0; every junction to the global
+ * frame, xy = (xy + domain_offset[j]) / domain_factor; every junction of grain 0's row of the FULL joint->grain CSR
+ * (rowptr_jg / col_jg from ggnn_build_csr) snapped to the nearest wall, argmin(x, 1-x, y, max_y-y), first minimum
+ * wins (move_to_boundary, test.py:58-71); every junction clamped to [0,1] x [0,max_y]; back, xy = xy * domain_factor -
+ * domain_offset[j].  fp32, each operation rounded on its own in the reference's order (no contraction).  domain_offset:
+ * [n_joint, 2] or NULL (= 0).  joints_before: NULL, or [n_joint, 2] that receives x_joint[:, 0:2] as the call found
+ * them (the speculative event loop's snapshot: a topological event of the step must see the junctions before it). */
+int ggnn_noflux_boundary(const int32_t* rowptr_jg, const int32_t* col_jg, float* x_joint, int64_t n_joint,
+                         int64_t ldx_joint, const float* domain_offset, float domain_factor, float max_y,
+                         float* x_grain, int64_t ldx_grain, int f_grain, float* joints_before, ggnn_stream_t stream);
+/* ggnn_grain_centres with the boundary of the structure: boundary = GGNN_BC_PERIODIC is ggnn_grain_centres;
+ * GGNN_BC_NOFLUX skips the min-image chaining of the junctions (graph_datastruct.py:689-692 runs periodic_move for the
+ * periodic BC only) and reads the FULL joint->grain CSR, so that grain 0 gets its centre too. */
+#define GGNN_BC_PERIODIC 0
+#define GGNN_BC_NOFLUX 1
+int ggnn_grain_centres_bc(const int32_t* rowptr, const int32_t* col, const float* x_joint, int64_t n_joint,
+                          int64_t ldx_joint, const float* domain_offset, float domain_factor, float* x_grain,
+                          int64_t n_grain, int64_t ldx_grain, float* centres_before, int boundary, ggnn_stream_t stream);
+/* ggnn_detect_events_n that never counts grain skip_grain (-1 = none): the boundary grain, which test.py:421-422 drops
+ * from the candidates (its area feature is reset to 0 every step, so it is always below the threshold).  live_grain is
+ * not touched: the topology session reads the same mask. */
+int ggnn_detect_events_skip(const float* grain_area, const int32_t* live_grain, int64_t n_grain, float area_threshold,
+                            const float* edge_event, const int64_t* edge_index_jj, int64_t E, const int64_t* E_dev,
+                            float logit_threshold, int32_t* flags, int32_t* range_word, int64_t skip_grain,
+                            ggnn_stream_t stream);
 /* The host-side topology update those counts trigger: one call of the reference's `Cmodel.update`
  * (models.py:612-842 with delete_grain_index :861-893, switching_edge_index :896-1051, point_in_triangle :1055-1070,
  * periodic_move :1103-1106), nucleation off.  HOST memory throughout, no stream: grains of `grain_event` (those below the
