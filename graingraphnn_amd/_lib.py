@@ -19,6 +19,7 @@ GGNN_EINFO_ROW = 20
 GGNN_C = 96
 GGNN_EDGE_PARAM_ROWS = 3
 GGNN_DC_SLICE_BYTES = 14336
+GGNN_ENC_VALUES_MAX_BLOCKS = 8
 GGNN_PRECISION_BF16 = 1
 GGNN_PRECISION_F16X2 = 2
 GGNN_OUT_BLOCK_MAJOR = 0x100
@@ -37,6 +38,7 @@ EXPORTED_SYMBOLS = (
     "ggnn_detect_events_skip",
     "ggnn_edge_prepare", "ggnn_project", "ggnn_project_batch", "ggnn_period_gat_aggregate",
     "ggnn_period_gat_aggregate_batch", "ggnn_period_gat_aggregate_enc_batch", "ggnn_encoder_cell_batch",
+    "ggnn_encoder_cell_values_batch",
     "ggnn_decoder_cell_batch",
     "ggnn_aggregate_bwd_partials", "ggnn_period_gat_aggregate_backward",
     "ggnn_lstm_epilogue", "ggnn_lstm_epilogue_batch", "ggnn_heads_regressor", "ggnn_heads_regressor_update",
@@ -115,6 +117,12 @@ class EncCellArgs(Structure):
         ("n_dst", c_int64), ("ldx", c_int64),
         ("n_in", c_int32), ("f_dst", c_int32),
     ]
+
+
+class EncValuesArgs(Structure):
+    """Mirror of `ggnn_enc_values_args`."""
+    _fields_ = [("cell", EncCellArgs), ("vstream", c_void_p), ("v_out", c_void_p), ("n_blocks", c_int32),
+                ("reserved", c_int32)]
 
 
 class DecCellSweep(Structure):
@@ -344,6 +352,8 @@ def _declare(lib):
     lib.ggnn_period_gat_aggregate_enc_batch.argtypes = [POINTER(AggregateEncArgs), c_int, c_void_p]
     lib.ggnn_encoder_cell_batch.restype = c_int
     lib.ggnn_encoder_cell_batch.argtypes = [POINTER(EncCellArgs), c_int, c_void_p]
+    lib.ggnn_encoder_cell_values_batch.restype = c_int
+    lib.ggnn_encoder_cell_values_batch.argtypes = [POINTER(EncValuesArgs), c_int, c_void_p]
     lib.ggnn_decoder_cell_batch.restype = c_int
     lib.ggnn_decoder_cell_batch.argtypes = [POINTER(DecCellArgs), c_int, c_void_p]
     lib.ggnn_aggregate_bwd_partials.restype = c_int64

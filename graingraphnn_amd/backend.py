@@ -8,7 +8,7 @@ import os
 import torch
 
 from . import _lib
-from ._lib import (AggregateArgs, AggregateBwdArgs, AggregateEncArgs, DecCellArgs, EncCellArgs, EpilogueArgs, PrepareEdge, ProjectArgs,
+from ._lib import (AggregateArgs, AggregateBwdArgs, AggregateEncArgs, DecCellArgs, EncCellArgs, EncValuesArgs, EpilogueArgs, PrepareEdge, ProjectArgs,
                    RefreshEdge, check, ptr)
 
 
@@ -146,6 +146,14 @@ class HipBackend:
         # dec_cell_kernel 110.2 -> 105.5 us, project_x6_kernel 22.8 -> 21.9 us per launch, 3 020 -> 3 054 steps/s on one box,
         # profiles/r6_value_rows_layout.txt); GGNN_VLAYOUT=rows: [N, ncols] (A/B runs)
         self.value_rows_block_major = os.environ.get("GGNN_VLAYOUT", "block") != "rows"
+        # the fused decoder plan's value rows written by the ENCODER cell of the same model, behind its LSTM update
+        # (ggnn_encoder_cell_values_batch; engine.value_epilogues decides where it applies): one launch and one dependent
+        # stage less per model, and no re-read of x | h1.  GGNN_ENC_VALUES=0 keeps the separate projection (A/B runs).
+        # With the decoder plan left to the graph's size (GGNN_DEC unset) the epilogue goes wherever the fused decoder does;
+        # a forced decoder plan (GGNN_DEC=fused...: development, the decoder cell alone) keeps the projection launch below
+        # FUSED_DECODER_MIN_JOINTS junctions, as the plan around the cell was before.
+        self.encoder_values = os.environ.get("GGNN_ENC_VALUES", "1") != "0"
+        self.encoder_values_min_joints = 0 if dec == "auto" else self.FUSED_DECODER_MIN_JOINTS
 
     def f16_projection(self) -> bool:
         """The fused decoder plan's value projection in the cells' three-product arithmetic (GGNN_PRECISION_F16X2) when the
@@ -374,37 +382,65 @@ class HipBackend:
         node type) problems in one launch.  Each item: (sweeps, x_dst, wstream, w2_tail, h_out, c_out) with sweeps =
         [(csr, einfo)] for the 1 or 2 incoming edge types; wstream / w2_tail: packing.encoder_cell_stream."""
         arr = (EncCellArgs * len(problems))()
-        for a, (sweeps, x_dst, wstream, w2_tail, h_out, c_out, *rest) in zip(arr, problems):
-            _require_cuda(x_dst, wstream, w2_tail, h_out, c_out)
-            n, n_in = x_dst.size(0), len(sweeps)
-            for t, name in ((x_dst, "x_dst"), (h_out, "h_out"), (c_out, "c_out"), (w2_tail, "w2_tail")):
-                if t.dtype != torch.float32 or t.dim() < 2 or t.stride(-1) != 1:
-                    raise _lib.GGNNError(f"ggnn_encoder_cell_batch: {name} must be float32 with unit column stride")
-            if n_in not in (1, 2) or tuple(h_out.shape) != (n, 96) or not h_out.is_contiguous() \
-                    or tuple(c_out.shape) != (n, 96) or not c_out.is_contiguous():
-                raise _lib.GGNNError("ggnn_encoder_cell_batch: h_out / c_out must be contiguous [n_dst, 96], 1 or 2 "
-                                     "incoming edge types")
-            if wstream.dtype != torch.int16 or not wstream.is_contiguous() \
-                    or wstream.numel() * 2 != 3 * (4 * n_in + 1) * _lib.GGNN_DC_SLICE_BYTES:
-                raise _lib.GGNNError("ggnn_encoder_cell_batch: wstream is not packing.encoder_cell_stream of this "
-                                     "number of incoming edge types")
-            if tuple(w2_tail.shape) != (3, n_in, 6, 64) or not w2_tail.is_contiguous():
-                raise _lib.GGNNError("ggnn_encoder_cell_batch: w2_tail must be contiguous [3, n_in, 6, 64]")
-            for sw, (csr, einfo) in zip(a.sweeps, sweeps):
-                _require_cuda(csr.rowptr, einfo)
-                if csr.rowptr.numel() != n + 1:
-                    raise _lib.GGNNError("the sweep's CSR does not have one row per destination node")
-                if einfo.dtype != torch.float32 or not einfo.is_contiguous() or einfo.dim() != 2 \
-                        or einfo.size(1) != _lib.GGNN_EINFO_ROW or einfo.size(0) < csr.E + _lib.GGNN_UNIT_EDGES:
-                    raise _lib.GGNNError("einfo must be contiguous float32 [E + GGNN_UNIT_EDGES, GGNN_EINFO_ROW]")
-                sw.rowptr, sw.einfo, sw.E = csr.rowptr.data_ptr(), einfo.data_ptr(), csr.E
-            a.x_dst, a.h_out, a.c_out = x_dst.data_ptr(), h_out.data_ptr(), c_out.data_ptr()
-            a.wstream, a.w2_tail = wstream.data_ptr(), w2_tail.data_ptr()
-            # (optional last element of a problem: the caller's own flag word -- a rollout's -- instead of the device-wide one)
-            a.flags = (rest[0] if rest and rest[0] is not None else self.range_flag(x_dst.device)).data_ptr()
-            a.n_dst, a.ldx, a.n_in, a.f_dst = n, x_dst.stride(0), n_in, x_dst.size(1)
+        for a, prob in zip(arr, problems):
+            self._enc_cell_args(a, prob)
         self._launch(self.lib.ggnn_encoder_cell_batch, "ggnn_encoder_cell_batch", arr, len(problems),
                      _lib.current_stream())
+
+    def encoder_cell_values_batch(self, problems):
+        """ggnn_encoder_cell_values_batch (include/ggnn.h): encoder_cell_batch's problems, each with the decoder's value
+        rows of its node type as an epilogue.  Each item: (cell problem as for encoder_cell_batch, vstream, v_out) with
+        vstream = packing.encoder_values_stream (int16 [4 n_blocks, GGNN_DC_SLICE_BYTES / 2]) and v_out the projection
+        buffer the decoder cell reads block-major: its first n_blocks 96 n_dst floats are [n_blocks][n_dst][96]."""
+        arr = (EncValuesArgs * len(problems))()
+        for a, (prob, vstream, v_out) in zip(arr, problems):
+            self._enc_cell_args(a.cell, prob)
+            _require_cuda(vstream, v_out)
+            n = prob[1].size(0)
+            nslices = vstream.numel() * 2 // _lib.GGNN_DC_SLICE_BYTES
+            if vstream.dtype != torch.int16 or not vstream.is_contiguous() or nslices % 4 \
+                    or vstream.numel() * 2 != nslices * _lib.GGNN_DC_SLICE_BYTES \
+                    or not 1 <= nslices // 4 <= _lib.GGNN_ENC_VALUES_MAX_BLOCKS:
+                raise _lib.GGNNError("ggnn_encoder_cell_values_batch: vstream is not packing.encoder_values_stream")
+            nb = nslices // 4
+            if v_out.dtype != torch.float32 or not v_out.is_contiguous() or v_out.numel() < nb * n * 96:
+                raise _lib.GGNNError(f"ggnn_encoder_cell_values_batch: v_out must be contiguous float32 with at least "
+                                     f"{nb} x {n} x 96 elements")
+            a.vstream, a.v_out, a.n_blocks = vstream.data_ptr(), v_out.data_ptr(), nb
+        self._launch(self.lib.ggnn_encoder_cell_values_batch, "ggnn_encoder_cell_values_batch", arr, len(problems),
+                     _lib.current_stream())
+
+    def _enc_cell_args(self, a, problem):
+        """Fill one ggnn_enc_cell_args from an encoder_cell_batch item (checked)."""
+        sweeps, x_dst, wstream, w2_tail, h_out, c_out, *rest = problem
+        _require_cuda(x_dst, wstream, w2_tail, h_out, c_out)
+        n, n_in = x_dst.size(0), len(sweeps)
+        for t, name in ((x_dst, "x_dst"), (h_out, "h_out"), (c_out, "c_out"), (w2_tail, "w2_tail")):
+            if t.dtype != torch.float32 or t.dim() < 2 or t.stride(-1) != 1:
+                raise _lib.GGNNError(f"ggnn_encoder_cell_batch: {name} must be float32 with unit column stride")
+        if n_in not in (1, 2) or tuple(h_out.shape) != (n, 96) or not h_out.is_contiguous() \
+                or tuple(c_out.shape) != (n, 96) or not c_out.is_contiguous():
+            raise _lib.GGNNError("ggnn_encoder_cell_batch: h_out / c_out must be contiguous [n_dst, 96], 1 or 2 "
+                                 "incoming edge types")
+        if wstream.dtype != torch.int16 or not wstream.is_contiguous() \
+                or wstream.numel() * 2 != 3 * (4 * n_in + 1) * _lib.GGNN_DC_SLICE_BYTES:
+            raise _lib.GGNNError("ggnn_encoder_cell_batch: wstream is not packing.encoder_cell_stream of this "
+                                 "number of incoming edge types")
+        if tuple(w2_tail.shape) != (3, n_in, 6, 64) or not w2_tail.is_contiguous():
+            raise _lib.GGNNError("ggnn_encoder_cell_batch: w2_tail must be contiguous [3, n_in, 6, 64]")
+        for sw, (csr, einfo) in zip(a.sweeps, sweeps):
+            _require_cuda(csr.rowptr, einfo)
+            if csr.rowptr.numel() != n + 1:
+                raise _lib.GGNNError("the sweep's CSR does not have one row per destination node")
+            if einfo.dtype != torch.float32 or not einfo.is_contiguous() or einfo.dim() != 2 \
+                    or einfo.size(1) != _lib.GGNN_EINFO_ROW or einfo.size(0) < csr.E + _lib.GGNN_UNIT_EDGES:
+                raise _lib.GGNNError("einfo must be contiguous float32 [E + GGNN_UNIT_EDGES, GGNN_EINFO_ROW]")
+            sw.rowptr, sw.einfo, sw.E = csr.rowptr.data_ptr(), einfo.data_ptr(), csr.E
+        a.x_dst, a.h_out, a.c_out = x_dst.data_ptr(), h_out.data_ptr(), c_out.data_ptr()
+        a.wstream, a.w2_tail = wstream.data_ptr(), w2_tail.data_ptr()
+        # (optional last element of a problem: the caller's own flag word -- a rollout's -- instead of the device-wide one)
+        a.flags = (rest[0] if rest and rest[0] is not None else self.range_flag(x_dst.device)).data_ptr()
+        a.n_dst, a.ldx, a.n_in, a.f_dst = n, x_dst.stride(0), n_in, x_dst.size(1)
 
     def range_flag(self, device):
         """The device word the two-piece fp16 kernels OR GGNN_FLAG_F16_RANGE into when they clamp an activation

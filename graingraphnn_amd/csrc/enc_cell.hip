@@ -57,9 +57,22 @@ struct EncCellBatch {
   int wg_off[EC_MAX_PROBLEMS + 1];
   int n;
 };
+// ggnn_encoder_cell_values_batch: the cell's problems plus, per problem, the decoder's value rows to write behind the
+// LSTM update (value stream, block-major output, number of 96-column blocks)
+struct EncValuesBatch {
+  EncCellBatch c;
+  const void* vstream[EC_MAX_PROBLEMS];
+  float* v_out[EC_MAX_PROBLEMS];
+  int n_blocks[EC_MAX_PROBLEMS];
+};
+constexpr int EC_NPV = 6 * DC_PL;   // pieces of a value-row slice (6 column tiles of one k-step)
 
+// VALUES: behind the last gate, the tile's value rows V = [h1 | x slots] . W_v^T of the decoder that runs next
+// (ggnn_encoder_cell_values_batch); `vstream` / `v_out` / `n_blocks` are read only then
+template <bool VALUES>
 __device__ __forceinline__ void enc_cell_body(const ggnn_enc_cell_args& A, const int tileset,
-                                              unsigned char* __restrict__ smem) {
+                                              unsigned char* __restrict__ smem, const void* vstream = nullptr,
+                                              float* __restrict__ v_out = nullptr, const int n_blocks = 0) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lr = lane & 15, kq = lane >> 4;   // node lr of the tile; k-group of a fragment = output rows 4 kq .. of a D tile
@@ -76,7 +89,9 @@ __device__ __forceinline__ void enc_cell_body(const ggnn_enc_cell_args& A, const
   const unsigned char* __restrict__ wsrc = reinterpret_cast<const unsigned char*>(A.wstream) + lane * 16;
   const uint32_t slice_lds =
       __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(reinterpret_cast<uintptr_t>(smem)));
-  const int per_gate = 4 * n_in + 1, n_groups = 3 * n_in;
+  const int per_gate = 4 * n_in + 1, n_gate_groups = 3 * n_in;
+  // VALUES: group 3 n_in + b = the 4 slices (3 k-steps over h1, 1 over the feature slots) of value block b
+  const int n_groups = VALUES ? n_gate_groups + n_blocks : n_gate_groups;
   int q_cur = 0;
   [[maybe_unused]] unsigned long long st_wait = 0, st_a = 0, st_p3 = 0, st_p4 = 0, st_lstm = 0;
   GGNN_STAMP(0);
@@ -87,6 +102,21 @@ __device__ __forceinline__ void enc_cell_body(const ggnn_enc_cell_args& A, const
   // precedes it (development, profiles/r6_enc_cell_experiments.txt; 1 = all of them at the top of the pass)
   auto dma_group = [&](int q, int part = 0) {
     if (q >= n_groups) return;
+    if constexpr (VALUES) {
+      if (q >= n_gate_groups) {   // a value block: 4 slices of 12 pieces, all requested with the first instalment
+        if (part != 0) return;
+        // (relative to wsrc: one per-lane address for both streams, the difference is wave-uniform)
+        const unsigned char* src = wsrc + (reinterpret_cast<const unsigned char*>(vstream) -
+                                           reinterpret_cast<const unsigned char*>(A.wstream)) +
+                                   (size_t)(q - n_gate_groups) * 4 * EC_SLICE;
+        const uint32_t dst = slice_lds + (q & 1) * (EC_GROUP * EC_SLICE);
+        for (int p = wave; p < 4 * EC_NPV; p += EC_WAVES) {
+          const int off = (p / EC_NPV) * EC_SLICE + (p % EC_NPV) * 1024;
+          dc_dma16(src + off, dst + off);
+        }
+        return;
+      }
+    }
     const int g = q / n_in, e = q - g * n_in;
     const int s0 = g * per_gate + 4 * e;                  // first slice of the group in the stream
     const int ns = 4 + (e == n_in - 1 ? 1 : 0);           // ... and their number (the gate's skip slice rides with its last pass)
@@ -328,17 +358,50 @@ __device__ __forceinline__ void enc_cell_body(const ggnn_enc_cell_args& A, const
       for (int ct = 0; ct < 6; ++ct)
 #pragma unroll
         for (int r = 0; r < 4; ++r) run[ct][r] *= tanhf_(pre[ct][r]);
-      float* crow = A.c_out + (int64_t)node_m * C + 4 * kq;
+      // (VALUES: 32-bit row offsets, n_dst 96 < 2^31 -- a 64-bit one would stay live across the gates and spill)
+      float* crow = VALUES ? A.c_out + ((uint32_t)node_m * C + 4 * kq) : A.c_out + (int64_t)node_m * C + 4 * kq;
 #pragma unroll
       for (int ct = 0; ct < 6; ++ct) *reinterpret_cast<f32x4*>(crow + 16 * ct) = run[ct];
     } else {
-      float* hrow = A.h_out + (int64_t)node_m * C + 4 * kq;
+      float* hrow = VALUES ? A.h_out + ((uint32_t)node_m * C + 4 * kq) : A.h_out + (int64_t)node_m * C + 4 * kq;
+      f32x4 hv[6];
 #pragma unroll
       for (int ct = 0; ct < 6; ++ct) {
         f32x4 h;
 #pragma unroll
         for (int r = 0; r < 4; ++r) h[r] = sigmoidf_(pre[ct][r]) * tanhf_(run[ct][r]);
         *reinterpret_cast<f32x4*>(hrow + 16 * ct) = h;
+        hv[ct] = h;
+      }
+      if constexpr (VALUES) {
+        // ================= value rows of the decoder: V[b] = [h1 | x slots] . W_v[b]^T, b = 0 .. n_blocks-1 =================
+        // h1 sits in lane (node lr, kq) as channels 16 ct + 4 kq ..+3: the channels {32 ks + 4 kq ..+3, 32 ks + 16 + 4 kq
+        // ..+3} of k-step ks are the B fragment of the lin_l2 k-steps (GGNN_CELL_P3_CHANNEL order, permuted on the host);
+        // the feature slots (x[:3] meet zero weights, slot 12 the bias) are the tile's own planes `xs`.  |h1| < 1: no
+        // range to track.  Block b's weights landed at the previous end_group (the first during the last gate's pass).
+        u32x4 hb[3][DC_PL];
+#pragma unroll
+        for (int ks = 0; ks < 3; ++ks) dc_split(hv[2 * ks], hv[2 * ks + 1], hb[ks]);
+        // 32-bit offsets (n_blocks n_dst 96 < 2^31, checked by the entry point)
+        const uint32_t voff = (uint32_t)node_m * C + 4 * kq;
+#pragma unroll 1
+        for (int b = 0; b < n_blocks; ++b) {
+          const u32x4* pv = begin_group();
+          DcAcc acc[6];
+#pragma unroll
+          for (int nb = 0; nb < 6; ++nb) acc[nb].zero();
+#pragma unroll
+          for (int ks = 0; ks < 3; ++ks) dc_kstep<6>(pv + ks * (EC_SLICE / 16), hb[ks], acc);
+          dc_kstep<6>(pv + 3 * (EC_SLICE / 16), xs, acc);
+          f32x4 v[6];
+#pragma unroll
+          for (int nb = 0; nb < 6; ++nb) v[nb] = acc[nb].value();
+          end_group();
+          // stored behind the barrier: they drain while the next block is computed (the next end_group's wait)
+          float* vb = v_out + (voff + (uint32_t)(b * n_dst * C));
+#pragma unroll
+          for (int nb = 0; nb < 6; ++nb) *reinterpret_cast<f32x4*>(vb + 16 * nb) = v[nb];
+        }
       }
     }
     st_lstm += GGNN_STAMP_NOW() - t_f;
@@ -361,15 +424,22 @@ __global__ __launch_bounds__(EC_WAVES * 64) void enc_cell_kernel(const EncCellBa
   while (k + 1 < B.n && (int)blockIdx.x >= B.wg_off[k + 1]) ++k;
   const int nwg = B.wg_off[k + 1] - B.wg_off[k];
   const int ts = xcd_remap((int)blockIdx.x - B.wg_off[k], nwg);
-  enc_cell_body(B.a[k], ts, s_raw);
+  enc_cell_body<false>(B.a[k], ts, s_raw);
 }
 
-}  // namespace ggnn
+// the same cell with the decoder's value rows as an epilogue (same LDS, same two waves per SIMD)
+__global__ __launch_bounds__(EC_WAVES * 64) void enc_cell_values_kernel(const EncValuesBatch B) {
+  __shared__ __attribute__((aligned(16))) unsigned char s_raw[EC_LDS];
+  int k = 0;
+  while (k + 1 < B.c.n && (int)blockIdx.x >= B.c.wg_off[k + 1]) ++k;
+  const int nwg = B.c.wg_off[k + 1] - B.c.wg_off[k];
+  const int ts = xcd_remap((int)blockIdx.x - B.c.wg_off[k], nwg);
+  enc_cell_body<true>(B.c.a[k], ts, s_raw, B.vstream[k], B.v_out[k], B.n_blocks[k]);
+}
 
-extern "C" int ggnn_encoder_cell_batch(const ggnn_enc_cell_args* args, int n_problems, ggnn_stream_t stream) {
-  using namespace ggnn;
+// validation and workgroup ranges of a batch of encoder-cell problems (both entry points)
+static int enc_cell_plan(const ggnn_enc_cell_args* args, int n_problems, EncCellBatch& B) {
   if (!args || n_problems < 1 || n_problems > EC_MAX_PROBLEMS) return GGNN_EINVAL;
-  EncCellBatch B;
   B.n = n_problems;
   B.wg_off[0] = 0;
   for (int k = 0; k < EC_MAX_PROBLEMS; ++k) {
@@ -392,7 +462,41 @@ extern "C" int ggnn_encoder_cell_batch(const ggnn_enc_cell_args* args, int n_pro
     if (B.wg_off[k] + n_ts >= INT32_MAX) return GGNN_EINVAL;
     B.wg_off[k + 1] = B.wg_off[k] + (int)n_ts;
   }
+  return GGNN_OK;
+}
+
+}  // namespace ggnn
+
+extern "C" int ggnn_encoder_cell_batch(const ggnn_enc_cell_args* args, int n_problems, ggnn_stream_t stream) {
+  using namespace ggnn;
+  EncCellBatch B;
+  const int rc = enc_cell_plan(args, n_problems, B);
+  if (rc != GGNN_OK) return rc;
   hipLaunchKernelGGL(enc_cell_kernel, dim3((unsigned)B.wg_off[EC_MAX_PROBLEMS]), dim3(EC_WAVES * 64), 0,
+                     (hipStream_t)stream, B);
+  return launch_status();
+}
+
+extern "C" int ggnn_encoder_cell_values_batch(const ggnn_enc_values_args* args, int n_problems, ggnn_stream_t stream) {
+  using namespace ggnn;
+  if (!args || n_problems < 1 || n_problems > EC_MAX_PROBLEMS) return GGNN_EINVAL;
+  ggnn_enc_cell_args cells[EC_MAX_PROBLEMS];
+  EncValuesBatch B;
+  for (int k = 0; k < EC_MAX_PROBLEMS; ++k) {
+    const ggnn_enc_values_args& V = args[k < n_problems ? k : 0];
+    if (k < n_problems) {
+      if (V.n_blocks < 1 || V.n_blocks > GGNN_ENC_VALUES_MAX_BLOCKS || !V.vstream || !V.v_out) return GGNN_EINVAL;
+      if (!aligned16(V.vstream) || !aligned16(V.v_out)) return GGNN_EINVAL;
+      if (V.cell.n_dst * V.n_blocks * (int64_t)C >= INT32_MAX) return GGNN_EINVAL;   // 32-bit row offsets
+      cells[k] = V.cell;
+    }
+    B.vstream[k] = V.vstream;
+    B.v_out[k] = V.v_out;
+    B.n_blocks[k] = V.n_blocks;
+  }
+  const int rc = enc_cell_plan(cells, n_problems, B.c);
+  if (rc != GGNN_OK) return rc;
+  hipLaunchKernelGGL(enc_cell_values_kernel, dim3((unsigned)B.c.wg_off[EC_MAX_PROBLEMS]), dim3(EC_WAVES * 64), 0,
                      (hipStream_t)stream, B);
   return launch_status();
 }

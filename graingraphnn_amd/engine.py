@@ -150,40 +150,71 @@ def prepare_edges(backend, graph: GraphCSR, x: Dict[str, torch.Tensor],
     return einfo
 
 
+def fused_decoder_plan(backend, pc: PackedCell, x: Dict[str, torch.Tensor]) -> bool:
+    """Whether run_cells runs decoder cell `pc` as ONE kernel (ggnn_decoder_cell_batch) on this graph."""
+    fd = getattr(backend, "fused_decoder", False)
+    if fd not in (False, True):   # one model's decoder only: the classifier's has one live destination type
+        fd = fd == ("classifier" if sum(bool(pc.layout[nt].live) for nt in NODE_TYPES) == 1 else "regressor")
+    if fd and x["joint"].size(0) < getattr(backend, "fused_decoder_min_joints", 0):
+        fd = False   # a small graph: three short kernels beat one long dependent chain per tile (backend.py)
+    return bool(pc.dcs) and bool(fd)
+
+
+def value_epilogues(backend, enc: PackedCell, dec: PackedCell, x: Dict[str, torch.Tensor]) -> Tuple[str, ...]:
+    """The node types whose decoder value rows the ENCODER cell of the same model writes behind its LSTM update
+    (ggnn_encoder_cell_values_batch) instead of a separate projection: only where the decoder runs the fused plan and
+    that projection would be GGNN_PRECISION_F16X2 | GGNN_OUT_BLOCK_MAJOR, the encoder runs as one kernel with a problem
+    of that node type, the graph has at least backend.encoder_values_min_joints junctions (a small graph under a forced
+    decoder plan keeps its projection) and the backend allows it (encoder_values; a backend without it: never)."""
+    if not getattr(backend, "encoder_values", False) or not getattr(backend, "fused_encoder", False):
+        return ()
+    if x["joint"].size(0) < getattr(backend, "encoder_values_min_joints", 0):
+        return ()
+    if not (dec.evs and enc.ecs and dec.wpv_f16 and fused_decoder_plan(backend, dec, x)):
+        return ()
+    if not (getattr(backend, "value_rows_block_major", False) and backend.f16_projection()):
+        return ()
+    return tuple(nt for nt in NODE_TYPES if nt in dec.wpv and nt in dec.evs and nt in enc.ecs and enc.layout[nt].live)
+
+
 def run_cells(backend, cells, graph: GraphCSR, x: Dict[str, torch.Tensor], einfo: Dict[ET, torch.Tensor],
-              after_projection=None, after_sweeps=None, range_flag=None):
+              after_projection=None, after_sweeps=None, range_flag=None, values=None, values_done=None):
     """One HeteroPGCLSTM.forward for every entry of `cells` -- (pc, h_in, c_in, proj, agg, h_out,
     c_out), the same cell (encoder or decoder) of one or more models on the same graph, x and edge
     geometry (test.py:382-383 runs the regressor and the classifier on the same x_dict) -- in THREE
     launches: all projections, all aggregation sweeps, all gate GEMM + LSTM epilogues.
     Encoder cells (pc.k2 == 0) ignore h_in / c_in (zeros).  `after_projection`: called right behind the last
     launch of the cell that reads x (the projection; with the fused decoder cell, that kernel) and `after_sweeps`
-    behind the last launch that reads the edge records (a caller may record stream events there)."""
-    projs, sweeps, enc_sweeps, gates, enc_cells, dec_cells = [], [], [], [], [], []
+    behind the last launch that reads the edge records (a caller may record stream events there).
+    `values` (encoder cells): per entry of `cells`, {node type: (vstream, v_out)} -- that problem also writes the
+    decoder's value rows (ggnn_encoder_cell_values_batch); `values_done` (decoder cells): per entry, the node types whose
+    value rows are already written that way (value_epilogues), so their projection is left out."""
+    projs, sweeps, enc_sweeps, gates, enc_cells, enc_values, dec_cells = [], [], [], [], [], [], []
     flag = () if range_flag is None else (range_flag,)   # the caller's own range-flag word for the fused cells
-    for pc, h_in, c_in, proj, agg, h_out, c_out in cells:
+    for i, (pc, h_in, c_in, proj, agg, h_out, c_out) in enumerate(cells):
         lay = pc.layout
         if pc.ecs and getattr(backend, "fused_encoder", False):
             # encoder: everything of a destination node type in one kernel (ggnn_encoder_cell_batch): no projection, no
             # aggregate or pre-activation buffer
+            vals = values[i] if values else {}
             for nt in NODE_TYPES:
                 if lay[nt].live:
-                    enc_cells.append(([(graph.csr[et], einfo[et]) for et in lay[nt].dst_ets], x[nt], pc.ecs[nt],
-                                      pc.ect[nt], h_out[nt], c_out[nt], *flag))
+                    prob = ([(graph.csr[et], einfo[et]) for et in lay[nt].dst_ets], x[nt], pc.ecs[nt], pc.ect[nt],
+                            h_out[nt], c_out[nt], *flag)
+                    if nt in vals:
+                        enc_values.append((prob, *vals[nt]))
+                    else:
+                        enc_cells.append(prob)
             continue
-        fd = getattr(backend, "fused_decoder", False)
-        if fd not in (False, True):   # one model's decoder only: the classifier's has one live destination type
-            fd = fd == ("classifier" if sum(bool(lay[nt].live) for nt in NODE_TYPES) == 1 else "regressor")
-        if fd and x["joint"].size(0) < getattr(backend, "fused_decoder_min_joints", 0):
-            fd = False   # a small graph: three short kernels beat one long dependent chain per tile (backend.py)
-        if pc.dcs and fd:
+        if fused_decoder_plan(backend, pc, x):
             # decoder: everything on the destination side in one kernel (ggnn_decoder_cell_batch); the projection only
             # emits the source-side value rows
             # the value rows: written once by the projection, gathered 96 columns (one edge type and gate) at a time by the
             # cell -- as [blocks][N][96] (GGNN_OUT_BLOCK_MAJOR) every workgroup of the projection stores one contiguous run
             vbm = getattr(backend, "value_rows_block_major", False)
+            done = values_done[i] if values_done else ()
             for nt in NODE_TYPES:
-                if nt in pc.wpv:
+                if nt in pc.wpv and nt not in done:
                     projs.append((x[nt], lay[nt].F, h_in[nt], pc.wpv[nt], pc.bpv[nt], proj[nt][:, :pc.wpv[nt].size(0)],
                                   (_lib.GGNN_PRECISION_F16X2 if pc.wpv_f16 and backend.f16_projection() else 0)
                                   | (_lib.GGNN_OUT_BLOCK_MAJOR if vbm else 0)))
@@ -214,6 +245,8 @@ def run_cells(backend, cells, graph: GraphCSR, x: Dict[str, torch.Tensor], einfo
         after_projection()
     if enc_cells:
         backend.encoder_cell_batch(enc_cells)
+    if enc_values:
+        backend.encoder_cell_values_batch(enc_values)
     if enc_sweeps:
         backend.aggregate_enc_batch(enc_sweeps)
     if sweeps:
@@ -262,11 +295,14 @@ def run_encoder_decoder_multi(backend, models, graph: GraphCSR, x: Dict[str, tor
     """The encoder cells of all `models` = [(enc, dec, workspace), ...] in three launches, then
     their decoder cells in three more (every model keeps its own weights, workspace and state)."""
     flag = getattr(models[0][2], "range_flag", None)   # (models launched together belong to one rollout: one word)
+    # the decoders' value rows, where they can be, come out of the encoder cells (value_epilogues)
+    done = [value_epilogues(backend, enc, dec, x) for enc, dec, _ in models]
     run_cells(backend, [(enc, None, None, ws.proj, ws.agg_enc, ws.h1, ws.c1) for enc, _, ws in models],
-              graph, x, einfo, range_flag=flag)
+              graph, x, einfo, range_flag=flag,
+              values=[{nt: (dec.evs[nt], ws.proj[nt]) for nt in d} for d, (_, dec, ws) in zip(done, models)])
     if after_encoder is not None:
         after_encoder()
     # (x_read / einfo_read: called once the last launch that reads x -- the decoder projection -- / the edge
     # records -- the decoder sweeps -- is enqueued)
     run_cells(backend, [(dec, ws.h1, ws.c1, ws.proj, ws.agg_dec, ws.h2, ws.c2) for _, dec, ws in models],
-              graph, x, einfo, after_projection=x_read, after_sweeps=einfo_read, range_flag=flag)
+              graph, x, einfo, after_projection=x_read, after_sweeps=einfo_read, range_flag=flag, values_done=done)

@@ -132,6 +132,9 @@ class PackedCell:
     ect: Dict[str, torch.Tensor] = field(default_factory=dict)
     dcs: Dict[str, torch.Tensor] = field(default_factory=dict)   # node type -> decoder_cell_stream (int16)
     dct: Dict[str, torch.Tensor] = field(default_factory=dict)   # node type -> decoder_cell_tail [4, n_in, 6, 64]
+    # ... and the same value rows as the ENCODER cell's epilogue (ggnn_encoder_cell_values_batch): node type ->
+    # encoder_values_stream of wpv / bpv (empty when a value weight or bias is beyond fp16's range)
+    evs: Dict[str, torch.Tensor] = field(default_factory=dict)
 
 
 @torch.no_grad()
@@ -311,6 +314,26 @@ def encoder_cell_stream(wp, bp, w2, lay: "NodeLayout", values, F_src):
         for k, slot in enumerate((0, 3)):   # b_l2 meets sum alpha in k-group 0, w_edge meets sum alpha a_e in k-group 3
             tail[:, d, :, slot, :] = w2[:, :, n_in * C + 2 * d + k].view(G, 6, 16)
     return stream.view(-1), tail.view(G, n_in, 6, 64).contiguous()
+
+
+@torch.no_grad()
+def encoder_values_stream(wpv, bpv, F: int):
+    """`ggnn_enc_values_args.vstream` (include/ggnn.h) from the fused decoder plan's value rows `wpv` [96 n_blocks, Fp + 96]
+    (input order [x, pad to Fp | h]) / `bpv`: per 96-column block four slices -- three k-steps over h in the encoder's
+    h1 layout (column k = h channel CELL_P3_CHANNEL[k]) and one over the 16 feature slots (_spread16: x_0 .. x_{F-1},
+    bias in slot 12).  Raises ValueError when a weight or bias is not finite or beyond fp16's range."""
+    rows, K = wpv.shape
+    Fp = K - C
+    assert rows % C == 0 and 1 <= rows // C <= 8 and F <= 12 and Fp == roundup4(F)
+    p3 = torch.tensor(CELL_P3_CHANNEL, device=wpv.device)
+    slices = []
+    for b in range(rows // C):
+        W = wpv[b * C:(b + 1) * C].float()
+        S = torch.zeros(C, 16, dtype=torch.float32, device=wpv.device)
+        S[:, :F] = W[:, :F]
+        S[:, 12] = bpv[b * C:(b + 1) * C]
+        slices.append(_plane_slices(torch.cat([W[:, Fp:][:, p3], _spread16(S)], dim=1)))   # [96, 128]: 4 slices
+    return torch.cat(slices).contiguous().view(-1)
 
 
 def _conv(cell, gate, et):
@@ -500,8 +523,15 @@ def pack_cell(cell, in_channels: Dict[str, int], encoder: bool, edge_types=EDGE_
             dcs, dct = {}, {}   # plan (projection + sweeps + gate GEMM, bf16 x 3: the full fp32 range, NaNs propagate)
     # the value projection of the fused plan runs in the cells' arithmetic (three products) when its weights allow
     wpv_f16 = bool(dcs) and all(bool(torch.isfinite(w).all()) and float(w.abs().max()) < 65504.0 for w in wpv.values())
+    # ... and can be the encoder cell's epilogue when its biases also fit (same rule) and the features its 16 slots
+    evs = {}
+    if wpv_f16 and all(F <= 12 for F in in_channels.values()):
+        try:
+            evs = {nt: encoder_values_stream(wpv[nt], bpv[nt], layout[nt].F) for nt in wpv}
+        except ValueError:
+            evs = {}
     return PackedCell(G=G, k2=k2, layout=layout, wp=wp, bp=bp, ep=ep, w2=w2, w2p=w2p, wvf=wvf, ecs=ecs, ect=ect,
-                      wpv=wpv, bpv=bpv, vof=vof, dcs=dcs, dct=dct, wpv_f16=wpv_f16)
+                      wpv=wpv, bpv=bpv, vof=vof, dcs=dcs, dct=dct, wpv_f16=wpv_f16, evs=evs)
 
 
 @torch.no_grad()

@@ -392,6 +392,26 @@ typedef struct ggnn_enc_cell_args {
 } ggnn_enc_cell_args;
 int ggnn_encoder_cell_batch(const ggnn_enc_cell_args* args, int n_problems, ggnn_stream_t stream);
 
+/* The encoder cell of ggnn_encoder_cell_batch (same h_out, c_out, flags, bit for bit) with the DECODER's source-side
+ * value rows of the same node type as an epilogue: V = [x | h_out] . Wv^T + bv, the rows ggnn_project_batch writes
+ * with GGNN_PRECISION_F16X2 | GGNN_OUT_BLOCK_MAJOR (same two-piece, three-product arithmetic, the bias as one more
+ * product against the constant slot), so the decoder cell reads them where it always does.
+ *   vstream : [4 n_blocks][GGNN_DC_SLICE_BYTES] (packing.encoder_values_stream): per 96-column block b, three k-steps
+ *             over h (column k = 32 ks + 8 kq + j <-> h channel GGNN_CELL_P3_CHANNEL(k)) and one over the 16 feature
+ *             slots (as A(e, g) above: x_0 .. x_{f_dst-1}, slot 12 = bv, the rest zero) -- 6 column tiles per slice
+ *   v_out   : [n_blocks][n_dst][96], 16-byte aligned
+ *   n_blocks: 1 .. GGNN_ENC_VALUES_MAX_BLOCKS
+ * Range: h_out is below 1 in magnitude; x is covered by the cell's own flag; the weights are checked when packed. */
+#define GGNN_ENC_VALUES_MAX_BLOCKS 8
+typedef struct ggnn_enc_values_args {
+  ggnn_enc_cell_args cell;
+  const void* vstream;  /* [4 n_blocks][GGNN_DC_SLICE_BYTES] */
+  float* v_out;         /* [n_blocks][n_dst][96] */
+  int32_t n_blocks;
+  int32_t reserved;
+} ggnn_enc_values_args;
+int ggnn_encoder_cell_values_batch(const ggnn_enc_values_args* args, int n_problems, ggnn_stream_t stream);
+
 /* Decoder HeteroPGCLSTM cell (h, c from the encoder; heteropgclstm.py:101-183 with the PeriodConv of
  * periodGATconv.py:204-236) with EVERYTHING that belongs to a destination node in one kernel: replaces the
  * destination-side columns of ggnn_project_batch (u_h, u4, S), ggnn_period_gat_aggregate_batch and
