@@ -178,14 +178,14 @@ def value_epilogues(backend, enc: PackedCell, dec: PackedCell, x: Dict[str, torc
 
 
 def run_cells(backend, cells, graph: GraphCSR, x: Dict[str, torch.Tensor], einfo: Dict[ET, torch.Tensor],
-              after_projection=None, after_sweeps=None, range_flag=None, values=None, values_done=None):
+              after_projection=None, range_flag=None, values=None, values_done=None):
     """One HeteroPGCLSTM.forward for every entry of `cells` -- (pc, h_in, c_in, proj, agg, h_out,
     c_out), the same cell (encoder or decoder) of one or more models on the same graph, x and edge
     geometry (test.py:382-383 runs the regressor and the classifier on the same x_dict) -- in THREE
     launches: all projections, all aggregation sweeps, all gate GEMM + LSTM epilogues.
     Encoder cells (pc.k2 == 0) ignore h_in / c_in (zeros).  `after_projection`: called right behind the last
-    launch of the cell that reads x (the projection; with the fused decoder cell, that kernel) and `after_sweeps`
-    behind the last launch that reads the edge records (a caller may record stream events there).
+    launch of the cell that reads x (the projection; with the fused decoder cell, that kernel): a caller may record a
+    stream event there.
     `values` (encoder cells): per entry of `cells`, {node type: (vstream, v_out)} -- that problem also writes the
     decoder's value rows (ggnn_encoder_cell_values_batch); `values_done` (decoder cells): per entry, the node types whose
     value rows are already written that way (value_epilogues), so their projection is left out."""
@@ -255,8 +255,6 @@ def run_cells(backend, cells, graph: GraphCSR, x: Dict[str, torch.Tensor], einfo
         backend.decoder_cell_batch(dec_cells)   # reads the destination nodes' features: x's last reader
         if after_projection is not None:
             after_projection()
-    if after_sweeps is not None:
-        after_sweeps()
     if gates:
         backend.lstm_epilogue_batch(gates)
 
@@ -278,20 +276,19 @@ def gate_problems(pc: PackedCell, proj, agg, c_in, h_out, c_out):
 
 def run_encoder_decoder(backend, enc: PackedCell, dec: PackedCell, graph: GraphCSR, ws: Workspace,
                         x: Dict[str, torch.Tensor], edge_attr: Dict[ET, torch.Tensor],
-                        einfo: Optional[Dict[ET, torch.Tensor]] = None, x_read=None, einfo_read=None, after_encoder=None):
+                        einfo: Optional[Dict[ET, torch.Tensor]] = None, x_read=None):
     """models.py:422-426 / 581-585: encoder from zero state, decoder from the encoder's (h, c),
     both on the same x_dict.  `einfo` (from prepare_edges) may be shared by several models that
-    see the same x / edge_attr; when absent it is computed here.  Returns the decoder's (h, c).
-    `after_encoder`: called once the encoder cell's launches are enqueued (a caller may record a stream event there)."""
+    see the same x / edge_attr; when absent it is computed here.  Returns the decoder's (h, c)."""
     if einfo is None:
         ea = {et: _edge_attr_1d(edge_attr[et]) for et in EDGE_TYPES}
         einfo = ws.einfo = prepare_edges(backend, graph, x, ea, ws.einfo)
-    run_encoder_decoder_multi(backend, [(enc, dec, ws)], graph, x, einfo, x_read, einfo_read, after_encoder)
+    run_encoder_decoder_multi(backend, [(enc, dec, ws)], graph, x, einfo, x_read)
     return ws.h2, ws.c2
 
 
 def run_encoder_decoder_multi(backend, models, graph: GraphCSR, x: Dict[str, torch.Tensor],
-                              einfo: Dict[ET, torch.Tensor], x_read=None, einfo_read=None, after_encoder=None):
+                              einfo: Dict[ET, torch.Tensor], x_read=None):
     """The encoder cells of all `models` = [(enc, dec, workspace), ...] in three launches, then
     their decoder cells in three more (every model keeps its own weights, workspace and state)."""
     flag = getattr(models[0][2], "range_flag", None)   # (models launched together belong to one rollout: one word)
@@ -300,9 +297,6 @@ def run_encoder_decoder_multi(backend, models, graph: GraphCSR, x: Dict[str, tor
     run_cells(backend, [(enc, None, None, ws.proj, ws.agg_enc, ws.h1, ws.c1) for enc, _, ws in models],
               graph, x, einfo, range_flag=flag,
               values=[{nt: (dec.evs[nt], ws.proj[nt]) for nt in d} for d, (_, dec, ws) in zip(done, models)])
-    if after_encoder is not None:
-        after_encoder()
-    # (x_read / einfo_read: called once the last launch that reads x -- the decoder projection -- / the edge
-    # records -- the decoder sweeps -- is enqueued)
+    # (x_read: called once the last launch that reads x -- the decoder projection -- is enqueued)
     run_cells(backend, [(dec, ws.h1, ws.c1, ws.proj, ws.agg_dec, ws.h2, ws.c2) for _, dec, ws in models],
-              graph, x, einfo, after_projection=x_read, after_sweeps=einfo_read, range_flag=flag, values_done=done)
+              graph, x, einfo, after_projection=x_read, range_flag=flag, values_done=done)

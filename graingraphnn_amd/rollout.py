@@ -27,6 +27,7 @@ from .packing import EDGE_TYPES, NODE_TYPES, pack_classifier_heads, pack_regress
 TRAIN_FRAMES = 120  # test.py:190
 ET_JJ = ("joint", "connect", "joint")
 JG = ("joint", "pull", "grain")
+GJ = ("grain", "push", "joint")
 
 
 class GrainRollout:
@@ -65,6 +66,18 @@ class GrainRollout:
                 raise _lib.GGNNError("x_dict tensors must be contiguous")
         dev = self.x["joint"].device
         self.n_nodes = {nt: self.x[nt].size(0) for nt in NODE_TYPES}
+        self.pred = {}                        # this step's predictions (run_events: one of its slots' dicts)
+        self.mask = None                      # enable_events()
+        self._cap = None                      # the in-place topology of the event loop (_enter_capacity_mode)
+        self._spec = None                     # run_events' ring of slots and its block graphs (_spec_state)
+        self._spec_quiet_blocks = 0           # run_events' quiet blocks in a row: the next block's size
+        self._range_hit = False               # an fp16-range report of a step run_events committed (range_exceeded)
+        self._evb = None                      # pinned staging of the event round trip (_event_buffers)
+        self._topo = None                     # (session, its jj list, its jg list, their versions): _topology_session
+        self._xc = self._xc_other = None      # the classifier's two alternating copies of x (_overlap_buffers)
+        self._xc_fresh = False
+        self._graphs = None                   # run() / step() graphs per (steps, buffers): _replay
+        self._drop_segment_graphs()           # step_events()' segment graphs: _segment_graphs, _graph_fwd, _graph_ref
         self._set_topology(edge_index_dict, edge_attr_dict)
         self.span = span
         # test.py:401-406 computes in fp32: z += fp32(span/121); clamp at fp32(120/121)
@@ -91,15 +104,6 @@ class GrainRollout:
             joint_launches = self.n_nodes["joint"] < self.JOINT_LAUNCH_MAX_JOINTS
         self.joint_launches = joint_launches
         self.concurrent = concurrent and not joint_launches
-        # GGNN_TAIL=join (development, A/B runs): the plain two-stream plan -- update, centres, refresh and edge
-        # records behind a join of both streams -- instead of the pipelined one
-        self.pipeline_tail = os.environ.get("GGNN_TAIL", "") != "join"
-        # GGNN_PIPE=r4 (development, A/B runs): the round-4 pipelined plan, whose Rmodel.update waits for the classifier's
-        # decoder; default: the regressor's tail runs UNDER the classifier's decoder (_enqueue_steps_overlapped)
-        self.overlap_tail = os.environ.get("GGNN_PIPE", "") != "r4"
-        # where the classifier's chain of a step starts relative to the regressor's: "none" = together with it (default),
-        # "enc" / "dec" = behind its encoder / decoder cell (development switch, see _enqueue_steps_overlapped)
-        self.classifier_lead = os.environ.get("GGNN_C_AFTER", "none")
         self._side = (torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev)) if self.concurrent else None
         self.refresh_centres = refresh_centres
         self.domain_factor = float(domain_factor)
@@ -155,7 +159,7 @@ class GrainRollout:
         outputs.  Called once at construction and after every topological event (`trusted`: lists the
         library's own update produced -- no range check, no read-back)."""
         dev = self.x["joint"].device
-        if getattr(self, "_cap", None) is not None:
+        if self._cap is not None:
             if trusted and edge_attr_dict is None and all(edge_index_dict[et].size(1) <= self._cap["cap"][et] for et in EDGE_TYPES):
                 return self._install_topology_in_place(edge_index_dict)
             self._cap = None   # (a caller's own topology, or one that grew: back to buffers of its own; the segment graphs go)
@@ -169,22 +173,18 @@ class GrainRollout:
                               for et in EDGE_TYPES}
         else:  # lengths are recomputed by the refresh that follows an event (every element: nothing to initialise)
             self.edge_attr = {et: torch.empty(self.edge_index[et].size(1), device=dev) for et in EDGE_TYPES}
-        # second buffer of the pipelined step (_enqueue_step_pipelined): the refresh writes the lengths of step
+        # second buffer of the two-stream step (_enqueue_overlapped_step): the refresh writes the lengths of step
         # k + 1 while the classifier's head still reads those of step k
         self._ea_other = {et: torch.empty_like(self.edge_attr[et]) for et in EDGE_TYPES}
         self._einfo_fresh = False   # True: self.einfo already holds the records of the step to come
         E = self.graph.edge_index[ET_JJ].size(1)
-        if not hasattr(self, "pred"):
-            self.pred = {}
         self.pred["edge_event"] = torch.empty(E, dtype=torch.float32, device=dev)
         self.pred["edge"] = torch.empty(E, 2, dtype=torch.float32, device=dev)
         self.einfo = alloc_einfo(self.graph, dev)
         self._zero_records(self.einfo)
-        # second set of edge records (_enqueue_steps_overlapped): made on first use; the classifier's copies of x keep
-        # their buffers (the node sets never change) but no longer mirror x
+        # second set of edge records (_enqueue_overlapped_step): made on first use (_overlap_buffers); the classifier's
+        # copies of x keep their buffers (the node sets never change) but no longer mirror x
         self._einfo_other = None
-        if not hasattr(self, "_xc"):
-            self._xc = self._xc_other = None
         self._x_written_outside()
         self._graphs = None
         self._seen = None
@@ -249,6 +249,7 @@ class GrainRollout:
             "csr": self._csr_in_place(be, cap, dev),
             "counts": torch.zeros(len(EDGE_TYPES), dtype=torch.int64, device=dev),
             "counts_host": torch.zeros(len(EDGE_TYPES), dtype=torch.int64).pin_memory(),
+            "captured": None,   # the smallest list sizes the segment graphs were captured at (_run_segment)
         }
         self._install_topology_in_place(old_ei)
         for et in EDGE_TYPES:
@@ -282,22 +283,19 @@ class GrainRollout:
                 {et: cut(("rec2", et), rows(et) * _lib.GGNN_EINFO_ROW, (rows(et), _lib.GGNN_EINFO_ROW)) for et in EDGE_TYPES}]
         # which of the two sets is the current one follows the speculative loop's slot parity while its state lives
         # (run_events' graphs alternate the sets by slot: _spec_state); step_events() alone stays on the first
-        S = getattr(self, "_spec", None)
-        par = (S["cur"] & 1) if (S is not None and S.get("in_place")) else 0
+        S = self._spec
+        par = (S["cur"] & 1) if (S is not None and S["in_place"]) else 0
         C["sets"], C["recs"] = sets, recs
         self.edge_attr, self._ea_other = sets[par], sets[1 - par]
         self.einfo, self._einfo_other = recs[par], recs[1 - par]
         self._einfo_fresh = False
-        if not hasattr(self, "pred"):
-            self.pred = {}
         self.pred["edge_event"] = cut("edge_event", E[ET_JJ])
         self.pred["edge"] = cut("edge", 2 * E[ET_JJ], (E[ET_JJ], 2))
         self._x_written_outside()
         self._graphs = None
         self._seen = None
         # a segment graph was captured for the sizes of ITS moment: it stays valid while nothing has grown since
-        got = C.get("captured")
-        if got is not None and any(E[et] > got[et] for et in EDGE_TYPES):
+        if self._outgrown(C["captured"]):
             self._drop_segment_graphs()
             C["captured"] = None
             if S is not None:
@@ -307,8 +305,18 @@ class GrainRollout:
         """x was (or is about to be) advanced by something other than the overlapped two-stream step / the speculative
         event step: their mirrors of x (the copies the classifier's forward reads) are stale."""
         self._xc_fresh = False
-        if getattr(self, "_spec", None) is not None:
+        if self._spec is not None:
             self._spec["xs_valid"] = None
+
+    def _outgrown(self, captured):
+        """Whether a list is longer now than the smallest sizes `captured` (or None) that a set of graphs was captured at:
+        graphs on the in-place topology stay valid only while none has grown."""
+        return captured is not None and any(int(self.edge_index[et].size(1)) > captured[et] for et in EDGE_TYPES)
+
+    def _smallest_sizes(self, captured):
+        """`captured` (the smallest list sizes a set of graphs was captured at, or None) with a capture at the current sizes."""
+        now = {et: int(self.edge_index[et].size(1)) for et in EDGE_TYPES}
+        return now if captured is None else {et: min(now[et], captured[et]) for et in EDGE_TYPES}
 
     # -- no-flux boundary ------------------------------------------------------------------
     def _csr_in_place(self, be, cap, dev):
@@ -342,79 +350,26 @@ class GrainRollout:
 
     # -- one step, enqueued on the current stream --------------------------------------
     def _pipelined(self):
-        """Two streams, static topology: update, grain centres, edge refresh and the NEXT step's edge records
-        run on the regressor's stream beside the classifier's last kernels (_enqueue_step_pipelined)."""
-        return self._side is not None and not self.joint_launches and self.pipeline_tail
+        """Two streams and no joint launches: step() and run() enqueue the overlapped step (_enqueue_overlapped_step).
+        Otherwise -- joint launches, one stream, or `_side = None` -- a step is _enqueue_forward_update + _enqueue_refresh."""
+        return self._side is not None and not self.joint_launches
 
     def _enqueue_step(self):
         self._enqueue_steps(1)
 
     def _enqueue_steps(self, n_steps: int):
         if self._pipelined():
-            if self.overlap_tail:
-                return self._enqueue_steps_overlapped(n_steps)
-            return self._enqueue_steps_pipelined(n_steps)
+            return self._enqueue_steps_overlapped(n_steps)
         for _ in range(n_steps):
             self._enqueue_forward_update()
             self._enqueue_refresh()
         self._einfo_fresh = False
         self._x_written_outside()
 
-    def _enqueue_steps_pipelined(self, n_steps: int):
-        """`n_steps` static-topology steps on two streams with the small launches hidden and no join between
-        steps.  After both forwards only four small kernels remain -- Rmodel.update, grain centres, z clamp + edge
-        lengths, and the edge records of the next forward -- during which the chip is nearly idle (~34 us of a
-        ~530 us step at 10 000 grains, plus a join and a fork).  None of them needs the classifier's results: they
-        run on the regressor's stream, beside the classifier's gate GEMM and heads, and the regressor's next forward
-        follows them directly.  Cross-stream edges per step (each costs a few us inside a hipGraph, so there are
-        exactly two):
-          * regressor stream waits for the classifier's decoder sweeps of this step (event `swept`) before
-            Rmodel.update: by then the classifier has read x for the last time (its decoder projection) and the edge
-            records too, so x (update, centres, z clamp) and einfo (next step's records) may be overwritten;
-          * classifier stream waits for the regressor stream's edge records (event `ready`) before its next forward.
-        The refreshed edge lengths go to the OTHER edge_attr buffer: the classifier's head still reads this step's
-        (models.py:595-609); the buffers swap every step.  Needs self.einfo to hold the records of the first step
-        already (step() / run() see to that)."""
-        be, x, p = self.be, self.x, self.pred
-        einfo = self.einfo
-        # the regressor's chain stays on the current stream (it carries every step-to-step dependency), the
-        # classifier forks from it at the top of every step and is joined once, behind the last one
-        main = torch.cuda.current_stream()
-        st_c = self._side[1]
-        events = []  # kept alive until the streams are joined (and a capture has ended)
-        for _ in range(n_steps):
-            ea, ea_next = self.edge_attr, self._ea_other
-            swept = torch.cuda.Event()
-            events.append(swept)
-            st_c.wait_stream(main)   # x, einfo and edge_attr of this step are final on `main`
-            enc, dec = self.packed["R"]
-            hr, _ = run_encoder_decoder(be, enc, dec, self.graph, self.ws["R"], x, ea, einfo)
-            with torch.cuda.stream(st_c):
-                enc, dec = self.packed["C"]
-                h, _ = run_encoder_decoder(be, enc, dec, self.graph, self.ws["C"], x, ea, einfo,
-                                           None, lambda: swept.record(st_c))
-                be.heads_classifier(h["joint"], self.graph.edge_index[ET_JJ], ea[ET_JJ], self.w_cls[0],
-                                    self.w_cls[1], self._tmp, p["edge_event"], p["edge"])
-            main.wait_event(swept)
-            # heads + Rmodel.update in one launch; z clamp + edge lengths + next records in one launch
-            be.heads_regressor_update(hr["joint"], hr["grain"], x["joint"], x["grain"], self.w_reg[0], self.w_reg[1],
-                                      p["joint"], p["grain"], p["grain_area"], self.dz, self.zmax, self.flags)
-            self._enqueue_boundary()
-            if self.refresh_centres:
-                self._enqueue_centres()
-            be.step_refresh_prepare(x["joint"], x["grain"], self.zmax, self.flags,
-                                    [(self.graph.csr[et], ea_next[et], x[et[0]], x[et[-1]], einfo[et])
-                                     for et in EDGE_TYPES])
-            self.edge_attr, self._ea_other = ea_next, ea
-        main.wait_stream(st_c)
-        self._einfo_fresh = True
-        self._x_written_outside()
-        return events
-
     def _overlap_buffers(self):
         """The second set of edge records and the classifier's two alternating copies of x (outside any capture:
         _capture calls this first)."""
-        if self._pipelined() and self.overlap_tail:
+        if self._pipelined():
             if self._einfo_other is None:
                 self._einfo_other = alloc_einfo(self.graph, self.x["joint"].device)
                 self._zero_records(self._einfo_other)
@@ -423,88 +378,95 @@ class GrainRollout:
                 self._xc_other = {nt: torch.empty_like(self.x[nt]) for nt in NODE_TYPES}
                 self._xc_fresh = False
 
-    def _enqueue_steps_overlapped(self, n_steps: int):
-        """`n_steps` static-topology steps on two streams with the regressor's tail -- heads + Rmodel.update, grain
-        centres, z clamp + edge lengths + the NEXT step's edge records -- UNDER the classifier's decoder cell.  In the
-        round-4 plan (_enqueue_steps_pipelined) that tail waited for the classifier's decoder, the last reader of x and of
-        the edge records: at 10 000 grains the two decoder cells are 393 workgroups in two rounds of the chip, the
-        regressor's finishes ~100 us before the classifier's, and the tail (three launch-bound kernels, ~25 us + the
-        cross-stream hand-overs) then ran on an idle chip (profiles/r5_step_timeline.txt).  Here the classifier reads a
-        private copy of x and the copies / edge lengths / edge records alternate between two sets -- the refresh of step
-        k writes the set of step k + 1 (the copy of x as a by-product of its pass over the nodes: ggnn_step_refresh_prepare's
-        mirror, ABI 24; round 5 copied x at the top of the classifier's step, two copy kernels at the head of its chain)
-        while the classifier still reads the set of step k -- so nothing the tail writes is read by the classifier's
-        forward of the same step.  Cross-stream edges per step:
-          * the classifier waits for `ready` (its copy of x, edge lengths and records of this step are final; recorded by
-            the regressor's stream at the top of the step);
-          * the NEXT step's refresh (the first launch that writes into the set this step's classifier reads: copy of x,
-            edge lengths, edge records) waits for `headed` (the classifier's heads -- the last reader, of the edge lengths
-            -- are done).  Round 5 held the whole next regressor forward back until the classifier's decoder had
-            finished ("the chip is free"); when the classifier's decoder is the one that ends last -- which of the two
-            decoder cells gets the compute units first is the hardware's choice -- that left 60 us per step with only
-            its last workgroups running (profiles/r6_step_timeline.txt): now the regressor's next encoder fills them.
-        Needs self._xc to mirror x already (step() / run() see to that: _ensure_edge_records).
+    def _enqueue_overlapped_step(self, ea, ea_next, einfo, einfo_next, xc, xc_next, p, zf, headed_prev, slot=None):
+        """One static-topology step on two streams with the regressor's tail -- heads + Rmodel.update, boundary step, grain
+        centres, z clamp + edge lengths + the NEXT step's edge records -- UNDER the classifier's forward, where the chip
+        would otherwise run the last workgroups of one decoder cell alone (profiles/r6_step_timeline.txt).  The regressor's
+        chain stays on the current stream: it carries every step-to-step dependency.  The classifier reads its own copy of x
+        (`xc`), and the copies of x, the edge lengths and the edge records alternate between two sets: this step reads
+        `xc`, `ea`, `einfo`, its refresh writes `xc_next` (ggnn_step_refresh_prepare's mirror, a by-product of its pass over
+        the nodes), `ea_next` and `einfo_next`, so nothing the tail writes is read by the classifier's forward of the same
+        step.  Cross-stream edges:
+          * the classifier waits for `ready`, recorded at the top of the step (its copy of x, the edge lengths and records
+            are final);
+          * the refresh, the first launch that writes into the set the previous step's classifier read, waits for that
+            step's `headed_prev` (its heads, the last reader, are done).
+        `p`: the predictions the heads write; `zf`: the z-clamp flag word Rmodel.update writes and the refresh reads.
+        With a ring `slot` of the speculative event loop (_spec_state), the fused cells report to the slot's own range word,
+        `updated` is recorded behind Rmodel.update, and the grain centres (noflux: and the junctions) as the step's events
+        must see them -- before the boundary step and the centre refresh -- go to the slot's snapshots.
         Same kernels on the same operands as the single-stream plan: bit-identical results
-        (test_pipelined_two_stream_rollout_equals_the_single_stream_plan)."""
-        be, x, p = self.be, self.x, self.pred
-        self._overlap_buffers()
-        main = torch.cuda.current_stream()
-        st_c = self._side[1]
-        events = []        # kept alive until the streams are joined (and a capture has ended)
-        headed_prev = None    # the classifier's heads of the previous step of this block
-        for _ in range(n_steps):
-            ea, ea_next = self.edge_attr, self._ea_other
-            einfo, einfo_next = self.einfo, self._einfo_other
-            xc, xc_next = self._xc, self._xc_other
-            ready, headed, lead = torch.cuda.Event(), torch.cuda.Event(), torch.cuda.Event()
-            events += [ready, headed, lead]
+        (test_pipelined_two_stream_rollout_equals_the_single_stream_plan).  Returns (ready, updated or None, headed): the
+        caller keeps them alive until the streams are joined and a capture has ended."""
+        be, x, S = self.be, self.x, self._spec
+        main, st_c = torch.cuda.current_stream(), self._side[1]
+        ready, headed = torch.cuda.Event(), torch.cuda.Event()
+        updated = None if slot is None else torch.cuda.Event()
+        word = self._range_word if slot is None else S["rw"][slot]   # (a void step's report is dropped with its slot)
+        for name in ("R", "C"):
+            self.ws[name].range_flag = word
+        try:
             ready.record(main)
             enc, dec = self.packed["R"]
-            # GGNN_C_AFTER=enc / dec (development; default: none) start the classifier's chain BEHIND the regressor's encoder
-            # / decoder cell instead of beside it (`lead`), so that the regressor's tail -- three launch-bound kernels,
-            # ~40 us -- runs under the classifier's decoder cell rather than on an idle chip.  Measured a wash: one box
-            # 3 288-3 491 steps/s (none) vs 3 460-3 503 (enc) vs 3 176-3 201 (dec), a second box 3 523-3 626 (none) vs
-            # 3 466-3 536 (enc) -- profiles/r6_step_timeline.txt; the results are bit-identical either way.
-            stage = self.classifier_lead
-            hr, _ = run_encoder_decoder(be, enc, dec, self.graph, self.ws["R"], x, ea, einfo,
-                                        x_read=(lambda: lead.record(main)) if stage == "dec" else None,
-                                        after_encoder=(lambda: lead.record(main)) if stage == "enc" else None)
+            hr, _ = run_encoder_decoder(be, enc, dec, self.graph, self.ws["R"], x, ea, einfo)
             with torch.cuda.stream(st_c):
                 st_c.wait_event(ready)
-                if stage in ("enc", "dec"):
-                    st_c.wait_event(lead)
                 enc, dec = self.packed["C"]
                 h, _ = run_encoder_decoder(be, enc, dec, self.graph, self.ws["C"], xc, ea, einfo)
-                be.heads_classifier(h["joint"], self.graph.edge_index[ET_JJ], ea[ET_JJ], self.w_cls[0],
-                                    self.w_cls[1], self._tmp, p["edge_event"], p["edge"])
+                be.heads_classifier(h["joint"], self.graph.edge_index[ET_JJ], ea[ET_JJ], self.w_cls[0], self.w_cls[1],
+                                    self._tmp, p["edge_event"], p["edge"], E_dev=self.graph.csr[ET_JJ].E_dev)
                 headed.record(st_c)
-            # heads + Rmodel.update in one launch; z clamp + edge lengths + next records + next copy of x in one launch
-            be.heads_regressor_update(hr["joint"], hr["grain"], x["joint"], x["grain"], self.w_reg[0], self.w_reg[1],
-                                      p["joint"], p["grain"], p["grain_area"], self.dz, self.zmax, self.flags)
-            self._enqueue_boundary()
-            if self.refresh_centres:
-                self._enqueue_centres()
-            if headed_prev is not None:
-                main.wait_event(headed_prev)   # the previous step's classifier has read the set this refresh writes
-            be.step_refresh_prepare(x["joint"], x["grain"], self.zmax, self.flags,
-                                    [(self.graph.csr[et], ea_next[et], x[et[0]], x[et[-1]], einfo_next[et])
-                                     for et in EDGE_TYPES], mirror=(xc_next["joint"], xc_next["grain"]))
-            headed_prev = headed
-            self.edge_attr, self._ea_other = ea_next, ea
-            self.einfo, self._einfo_other = einfo_next, einfo
-            self._xc, self._xc_other = xc_next, xc
-        main.wait_stream(st_c)
-        self._einfo_fresh = True
-        self._xc_fresh = True
-        if getattr(self, "_spec", None) is not None:
+        finally:
+            for name in ("R", "C"):
+                self.ws[name].range_flag = self._range_word
+        # heads + Rmodel.update in one launch; z clamp + edge lengths + next records + next copy of x in one launch
+        be.heads_regressor_update(hr["joint"], hr["grain"], x["joint"], x["grain"], self.w_reg[0], self.w_reg[1],
+                                  p["joint"], p["grain"], p["grain_area"], self.dz, self.zmax, zf)
+        joints_before = centres_before = None
+        if slot is not None:
+            updated.record(main)
+            joints_before, centres_before = (S["jb"][slot] if self.noflux else None), S["cen"][slot]
+            if not self.refresh_centres:   # (otherwise the snapshot rides with the launch that replaces the centres)
+                centres_before.copy_(x["grain"][:, :2])
+        self._enqueue_boundary(joints_before)
+        if self.refresh_centres:
+            self._enqueue_centres(centres_before)
+        if headed_prev is not None:
+            main.wait_event(headed_prev)   # the previous step's classifier has read the set this refresh writes
+        be.step_refresh_prepare(x["joint"], x["grain"], self.zmax, zf,
+                                [(self.graph.csr[et], ea_next[et], x[et[0]], x[et[-1]], einfo_next[et])
+                                 for et in EDGE_TYPES], mirror=(xc_next["joint"], xc_next["grain"]))
+        return ready, updated, headed
+
+    def _enqueue_steps_overlapped(self, n_steps: int):
+        """`n_steps` overlapped steps (_enqueue_overlapped_step) on the rollout's own buffers, the two sets swapped behind
+        every step, no join between the steps; the classifier's stream is joined behind the last one.  Needs self.einfo to
+        hold the records of the first step and self._xc to mirror x (step() / run() see to that: _ensure_edge_records)."""
+        self._overlap_buffers()
+        keep, headed = [], None
+        for _ in range(n_steps):
+            keep.append(self._enqueue_overlapped_step(self.edge_attr, self._ea_other, self.einfo, self._einfo_other,
+                                                      self._xc, self._xc_other, self.pred, self.flags, headed))
+            headed = keep[-1][-1]
+            self.edge_attr, self._ea_other = self._ea_other, self.edge_attr
+            self.einfo, self._einfo_other = self._einfo_other, self.einfo
+            self._xc, self._xc_other = self._xc_other, self._xc
+        torch.cuda.current_stream().wait_stream(self._side[1])
+        self._next_step_prepared()
+        return keep
+
+    def _next_step_prepared(self):
+        """Behind overlapped steps: the last refresh prepared the edge records of the step to come and left its mirror of x
+        in the current copy (run_events' copies of x do not follow)."""
+        self._einfo_fresh = self._xc_fresh = True
+        if self._spec is not None:
             self._spec["xs_valid"] = None
-        return events
 
     def _ensure_edge_records(self, mirror=True):
-        """Before a pipelined step outside a capture: einfo must hold the records of the step to come and (overlapped
-        plan, `mirror`) the classifier's copy of x must equal x.  They are stale after construction, a topology change,
-        an event-mode or single-stream step, and when the caller wrote into x / edge_attr (in-place Python writes bump
-        the tensors' version counters; the kernels do not)."""
+        """Before an overlapped step outside a capture: einfo must hold the records of the step to come and (`mirror`) the
+        classifier's copy of x must equal x.  They are stale after construction, a topology change, an event-mode or
+        single-stream step, and when the caller wrote into x / edge_attr (in-place Python writes bump the tensors' version
+        counters; the kernels do not)."""
         seen = tuple(t._version for t in self.x.values()) + tuple(sorted(
             t._version for t in (*self.edge_attr.values(), *self._ea_other.values())))
         if seen != self._seen:
@@ -513,7 +475,7 @@ class GrainRollout:
             prepare_edges(self.be, self.graph, self.x, self.edge_attr, self.einfo)
             self._einfo_fresh = True
         self._seen = seen
-        if mirror and self.overlap_tail and not self._xc_fresh:
+        if mirror and not self._xc_fresh:
             self._overlap_buffers()
             for nt in NODE_TYPES:
                 self._xc[nt].copy_(self.x[nt])
@@ -526,7 +488,6 @@ class GrainRollout:
         joint = self.joint_launches if joint is None else joint
         # edge geometry once per step, shared by both models and all four cells
         einfo = prepare_edges(be, self.graph, x, ea, self.einfo)
-
 
         def regressor():
             enc, dec = self.packed["R"]
@@ -582,30 +543,35 @@ class GrainRollout:
         be.step_refresh(x["joint"], x["grain"], self.zmax, self.flags,
                         [(self.graph.edge_index[et], x[et[0]], x[et[-1]], ea[et], self.graph.count_dev[et]) for et in EDGE_TYPES])
 
-    def _capture(self, n_steps: int = 1):
-        """Record `n_steps` steps into a hipGraph (torch.cuda.CUDAGraph is hipGraph on ROCm); the
-        kernels are launched through the C ABI on the capturing stream.  A pipelined step swaps the two
-        edge_attr buffers: a graph is only valid from the buffer it was captured on, so graphs are kept per
-        buffer (`_graphs[(n_steps, id of the current buffer)]`), and an odd number of steps leaves the other one
-        current after every replay."""
-        self._overlap_buffers()
+    @staticmethod
+    def _captured(enqueue):
+        """A hipGraph (torch.cuda.CUDAGraph is hipGraph on ROCm) of the launches `enqueue()` makes through the C ABI,
+        captured on a side stream: the capture records, it does not execute.  What `enqueue` returns (its stream events)
+        lives until the capture has ended."""
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
-        state = (self.edge_attr, self._ea_other, self._einfo_fresh, self.einfo, self._einfo_other, self._xc,
-                 self._xc_other, self._xc_fresh)
         with torch.cuda.stream(s):
-            # the capture records, it does not execute: x / edge_attr are left untouched
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, stream=s):
-                keep = self._enqueue_steps(n_steps)   # (its stream events outlive the capture)
+                keep = enqueue()
         torch.cuda.current_stream().wait_stream(s)
         del keep
+        return g
+
+    def _capture(self, n_steps: int = 1):
+        """Record `n_steps` steps into a hipGraph, leaving the rollout's buffers as they were.  An overlapped step swaps the
+        two sets of edge lengths / edge records / copies of x: a graph is only valid from the set it was captured on, so
+        graphs are kept per set (_replay), and an odd number of steps leaves the other set current after every replay."""
+        self._overlap_buffers()
+        state = (self.edge_attr, self._ea_other, self._einfo_fresh, self.einfo, self._einfo_other, self._xc,
+                 self._xc_other, self._xc_fresh)
+        g = self._captured(lambda: self._enqueue_steps(n_steps))
         (self.edge_attr, self._ea_other, self._einfo_fresh, self.einfo, self._einfo_other, self._xc, self._xc_other,
          self._xc_fresh) = state
         return g
 
     def _replay(self, n_steps: int):
-        """`n_steps` steps from the hipGraph captured for this step count and the current edge_attr buffer."""
+        """`n_steps` steps from the hipGraph captured for this step count and the current set of buffers."""
         if self._graphs is None:
             self._graphs = {}
         key = (n_steps, self.edge_attr[ET_JJ].data_ptr(), self.einfo[ET_JJ].data_ptr(),
@@ -617,16 +583,9 @@ class GrainRollout:
         if self._pipelined():
             if n_steps % 2:
                 self.edge_attr, self._ea_other = self._ea_other, self.edge_attr
-                if self.overlap_tail:   # (the edge records and the classifier's copies of x alternate with the edge lengths)
-                    self.einfo, self._einfo_other = self._einfo_other, self.einfo
-                    self._xc, self._xc_other = self._xc_other, self._xc
-            self._einfo_fresh = True
-            if self.overlap_tail:   # (the last step's refresh left its mirror of x in the now-current copy)
-                self._xc_fresh = True
-                if getattr(self, "_spec", None) is not None:
-                    self._spec["xs_valid"] = None
-            else:
-                self._x_written_outside()
+                self.einfo, self._einfo_other = self._einfo_other, self.einfo
+                self._xc, self._xc_other = self._xc_other, self._xc
+            self._next_step_prepared()
         else:
             self._einfo_fresh = False
             self._x_written_outside()
@@ -668,35 +627,32 @@ class GrainRollout:
         first step on and across events; otherwise once the topology has been quiet for two steps (an event then drops the
         graphs with the topology, and a capture is not worth it while events fire every step)."""
         fn = self._enqueue_forward_update if which == "fwd" else self._enqueue_refresh
-        attr = "_graph_fwd" if which == "fwd" else "_graph_ref"
-        in_place = getattr(self, "_cap", None) is not None   # (the graphs survive events: captured once, at the first step)
+        in_place = self._cap is not None   # (the graphs survive events: captured once, at the first step)
         if self.use_graph and (self._quiet_steps >= 2 or in_place):
-            # a segment graph holds the addresses of the buffers that were current when it was captured; run_events() leaves
-            # other ones current (its slots' predictions, the other set of edge lengths / records): a graph per set
-            key = (which, self.edge_attr[ET_JJ].data_ptr(), self.einfo[ET_JJ].data_ptr(), self.pred["joint"].data_ptr(),
-                   self.pred["edge_event"].data_ptr(), self.graph.csr[ET_JJ].rowptr.data_ptr())
-            graphs = self.__dict__.setdefault("_segment_graphs", {})
-            if getattr(self, attr) is None:   # (dropped from outside: `ro._graph_fwd = None`)
-                graphs.pop(key, None)
-            if key not in graphs:
+            # a segment graph holds the addresses of the buffers it reads and writes; run_events() leaves other ones current
+            # (its slots' predictions, the other set of edge lengths / records): a graph per set.  The forwards read the edge
+            # lengths and records and write the predictions; the refresh writes the edge lengths
+            tables = self.graph.csr[ET_JJ].rowptr.data_ptr()
+            if which == "fwd":
+                key = (which, self.edge_attr[ET_JJ].data_ptr(), self.einfo[ET_JJ].data_ptr(), self.pred["joint"].data_ptr(),
+                       self.pred["edge_event"].data_ptr(), tables)
+            else:
+                key = (which, self.edge_attr[ET_JJ].data_ptr(), tables)
+            g = self._segment_graphs.get(key)
+            if g is None:
                 if in_place:   # valid for as long as no list is longer than now (_install_topology_in_place)
-                    now = {et: int(self.edge_index[et].size(1)) for et in EDGE_TYPES}
-                    got = self._cap.get("captured")
-                    self._cap["captured"] = now if got is None else {et: min(now[et], got[et]) for et in EDGE_TYPES}
-                st = torch.cuda.Stream()
-                st.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(st):
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g, stream=st):
-                        fn()
-                torch.cuda.current_stream().wait_stream(st)
-                graphs[key] = g
-            setattr(self, attr, graphs[key])
-            getattr(self, attr).replay()
+                    self._cap["captured"] = self._smallest_sizes(self._cap["captured"])
+                g = self._segment_graphs[key] = self._captured(fn)
+            if which == "fwd":
+                self._graph_fwd = g
+            else:
+                self._graph_ref = g
+            g.replay()
         elif which == "fwd":
             # eager launches (GGNN_EVENT_GRAPHS=0 / a caller's own topology: the steps around an event, which replaces the
-            # topology the graphs were captured on) are bound by the HOST's launch rate at any graph size -- ~20 launches + stream forks of the two-stream plan take
-            # 0.49 ms where the kernels take 0.35 (profiles/r6_event_step_breakdown.txt): R and C share every launch here
+            # topology the graphs were captured on) are bound by the HOST's launch rate at any graph size -- ~20 launches +
+            # stream forks of the two-stream plan take 0.49 ms where the kernels take 0.35
+            # (profiles/r6_event_step_breakdown.txt): R and C share every launch here
             self._enqueue_forward_update(joint=True)
         else:
             fn()
@@ -705,7 +661,7 @@ class GrainRollout:
         """One step with topological events.  Returns (pred, grain_events, switching_list); the
         last two are empty numpy arrays on a quiet step.  One 8-byte read-back per step is the only
         host synchronisation unless an event fires."""
-        if not hasattr(self, "mask"):
+        if self.mask is None:
             raise _lib.GGNNError("call enable_events(mask, ...) first")
         self.refresh_weights(sample=self.steps_done % 16 != 0)
         self._einfo_fresh = False   # this mode prepares its edge records at the start of every step
@@ -717,7 +673,7 @@ class GrainRollout:
         self._ev_host.copy_(self._ev_flags, non_blocking=True)
         # behind an eventful step the next one is eventful too, on the reference's trajectories (README.md:68-69: events at
         # nearly every step): what the rewiring reads travels to the host behind the counts, one synchronisation instead of two
-        payload = self._quiet_steps == 0 and getattr(self, "_evb", None) is not None and getattr(self, "rewire_hook", None) is None
+        payload = self._quiet_steps == 0 and self._evb is not None
         if payload:
             self._enqueue_event_readback()
         torch.cuda.current_stream().synchronize()
@@ -754,7 +710,7 @@ class GrainRollout:
         plus the two alternating sets of edge lengths / edge records (set = slot parity).  Graphs are captured per
         (first slot, number of steps).  On the in-place topology (_enter_capacity_mode) the ring and the graphs survive events
         (the views are re-cut); otherwise the per-edge half and the graphs are rebuilt after every topology change."""
-        S = getattr(self, "_spec", None)
+        S = self._spec
         if S is not None and S["topology"] is self.graph and S["ea"][S["cur"] & 1] is self.edge_attr \
                 and S["einfo"][S["cur"] & 1] is self.einfo:
             return S
@@ -762,30 +718,20 @@ class GrainRollout:
         dev = self.x["joint"].device
         D = 2 * max(1, int(self.EVENTS_UNROLL))
         per_edge = ("edge_event", "edge")   # the predictions that follow the junction edge list
-        C = getattr(self, "_cap", None)
+        C = self._cap
         if C is not None:
             # The topology lives in place (_enter_capacity_mode): the two sets of edge lengths / records are the SAME
             # allocations before and after an event, the slots' per-edge predictions are cut from one allocation of the
             # capacity, and the graphs of the blocks -- whose per-edge kernels read the number of edges from device memory --
             # stay valid across events for as long as no list has grown: an event re-cuts the views, nothing else.
-            Ecap, E = C["cap"][ET_JJ], self.pred["edge_event"].numel()
-            Ea = (Ecap + 3) & ~3
-            if S is None or not S.get("in_place") or S["D"] != D or S["flat"].numel() != 3 * D * Ea:
+            Ea = (C["cap"][ET_JJ] + 3) & ~3
+            if S is None or not S["in_place"] or S["D"] != D or S["flat"].numel() != 3 * D * Ea:
                 S = self._spec = {
                     "in_place": True, "cur": 0, "D": D, "graphs": {}, "captured": None, "xs_valid": None,
-                    "flat": torch.empty(3 * D * Ea, dtype=torch.float32, device=dev),
-                    "xs": [{nt: torch.empty_like(self.x[nt]) for nt in NODE_TYPES} for _ in range(D)],
-                    "cen": [torch.empty(self.n_nodes["grain"], 2, device=dev) for _ in range(D)],
-                    "jb": [torch.empty(self.n_nodes["joint"], 2, device=dev) for _ in range(D)],
-                    "evf": [torch.zeros(4, dtype=torch.int32, device=dev) for _ in range(D)],
-                    "evh": [torch.zeros(4, dtype=torch.int32).pin_memory() for _ in range(D)],
-                    "zf": [torch.zeros(2, dtype=torch.int32, device=dev) for _ in range(D)],
-                    "rw": [torch.zeros(1, dtype=torch.int32, device=dev) for _ in range(D)],
+                    "flat": torch.empty(3 * D * Ea, dtype=torch.float32, device=dev), **self._spec_node_slots(D),
                     "pred": [{k: torch.empty_like(v) for k, v in self.pred.items() if k not in per_edge} for _ in range(D)]}
-            flat = S["flat"]
-            for i, slot in enumerate(S["pred"]):
-                slot["edge_event"] = flat[3 * i * Ea:3 * i * Ea + E]
-                slot["edge"] = flat[3 * i * Ea + Ea:3 * i * Ea + Ea + 2 * E].view(E, 2)
+            for slot, edge in zip(S["pred"], self._spec_edge_slots(S["flat"], D, Ea)):
+                slot.update(edge)
             par = S["cur"] & 1
             S["topology"], S["ea"], S["einfo"] = self.graph, C["sets"], C["recs"]
             if self.edge_attr is not C["sets"][par]:   # (step_events() in between left the first set current: move over)
@@ -794,105 +740,68 @@ class GrainRollout:
                 self._einfo_fresh = False
             self.edge_attr, self._ea_other = C["sets"][par], C["sets"][1 - par]
             self.einfo, self._einfo_other = C["recs"][par], C["recs"][1 - par]
-            sizes = {et: int(self.edge_index[et].size(1)) for et in EDGE_TYPES}
-            if S["captured"] is not None and any(sizes[et] > S["captured"][et] for et in EDGE_TYPES):
+            if self._outgrown(S["captured"]):
                 S["graphs"], S["captured"] = {}, None
             return S
         if S is not None and S["D"] == D:
             # a new topology (after an event): the per-node slots, the centre snapshots and the (pinned) count words stay --
             # the node sets never change -- only the per-edge predictions follow the new edge list
             keep = {k: S[k] for k in ("xs", "cen", "jb", "evf", "evh", "zf", "rw")}
-            E = self.pred["edge_event"].numel()
-            Ea = (E + 3) & ~3                                                     # (16-byte aligned segments)
+            Ea = (self.pred["edge_event"].numel() + 3) & ~3                    # (16-byte aligned segments)
             flat = torch.empty(3 * D * Ea, dtype=torch.float32, device=dev)   # one allocation for all slots
-            edge_bufs = [{"edge_event": flat[3 * i * Ea:3 * i * Ea + E],
-                          "edge": flat[3 * i * Ea + Ea:3 * i * Ea + Ea + 2 * E].view(E, 2)} for i in range(D)]
-            pred = [{k: (edge_bufs[i][k] if k in per_edge else v) for k, v in slot.items()}
-                    for i, slot in enumerate(S["pred"])]
+            pred = [{**slot, **edge} for slot, edge in zip(S["pred"], self._spec_edge_slots(flat, D, Ea))]
         else:
-            keep = {"xs": [{nt: torch.empty_like(self.x[nt]) for nt in NODE_TYPES} for _ in range(D)],
-                    "cen": [torch.empty(self.n_nodes["grain"], 2, device=dev) for _ in range(D)],
-                    "jb": [torch.empty(self.n_nodes["joint"], 2, device=dev) for _ in range(D)],
-                    "evf": [torch.zeros(4, dtype=torch.int32, device=dev) for _ in range(D)],
-                    "evh": [torch.zeros(4, dtype=torch.int32).pin_memory() for _ in range(D)],
-                    "zf": [torch.zeros(2, dtype=torch.int32, device=dev) for _ in range(D)],
-                    "rw": [torch.zeros(1, dtype=torch.int32, device=dev) for _ in range(D)]}
+            keep = self._spec_node_slots(D)
             pred = [{k: torch.empty_like(v) for k, v in self.pred.items()} for _ in range(D)]
         S = self._spec = {
-            "topology": self.graph, "cur": 0, "D": D,
+            "in_place": False, "topology": self.graph, "cur": 0, "D": D,
             "ea": [self.edge_attr, self._ea_other], "einfo": [self.einfo, self._einfo_other],
-            "pred": pred, "graphs": {}, "xs_valid": None, **keep}
+            "pred": pred, "graphs": {}, "captured": None, "xs_valid": None, **keep}
         return S
 
-    def _enqueue_spec_step(self, slot: int, headed_prev=None):
-        """One step with events ASSUMED ABSENT: the overlapped two-stream step (_enqueue_steps_overlapped) on the edge
-        set of the slot's parity + a snapshot of the grain centres before they are refreshed + the event counts of this
-        step's predictions (ggnn_detect_events) copied to pinned host memory.  Nothing an event would need is
-        overwritten by the steps enqueued behind it: they use other slots of the ring (the copy of x the step leaves
-        for the next one, its z-clamp flag and its range word included).  Needs S["xs"][slot] to equal x (_spec_launch)."""
-        S, be, x = self._spec, self.be, self.x
-        s = slot & 1
-        ea, ea_next, einfo, einfo_next = S["ea"][s], S["ea"][1 - s], S["einfo"][s], S["einfo"][1 - s]
-        p, xc, xc_next, zf = S["pred"][slot], S["xs"][slot], S["xs"][(slot + 1) % S["D"]], S["zf"][slot]
-        main, st_c = torch.cuda.current_stream(), self._side[1]
-        ready, updated, headed = (torch.cuda.Event() for _ in range(3))
-        st_d = self._side[0]   # the event counts go out on a stream of their own: neither model's chain waits for them
-        for name in ("R", "C"):   # the fused cells of this step report to the slot's own word (a void step's report is dropped)
-            self.ws[name].range_flag = S["rw"][slot]
-        ready.record(main)
-        lead, stage = torch.cuda.Event(), self.classifier_lead   # (the classifier behind the regressor's encoder cell: see _enqueue_steps_overlapped)
-        enc, dec = self.packed["R"]
-        hr, _ = run_encoder_decoder(be, enc, dec, self.graph, self.ws["R"], x, ea, einfo,
-                                    x_read=(lambda: lead.record(main)) if stage == "dec" else None,
-                                    after_encoder=(lambda: lead.record(main)) if stage == "enc" else None)
-        with torch.cuda.stream(st_c):
-            st_c.wait_event(ready)
-            if stage in ("enc", "dec"):
-                st_c.wait_event(lead)
-            enc, dec = self.packed["C"]
-            h, _ = run_encoder_decoder(be, enc, dec, self.graph, self.ws["C"], xc, ea, einfo)
-            be.heads_classifier(h["joint"], self.graph.edge_index[ET_JJ], ea[ET_JJ], self.w_cls[0],
-                                self.w_cls[1], self._tmp, p["edge_event"], p["edge"], E_dev=self.graph.csr[ET_JJ].E_dev)
-            headed.record(st_c)
-        be.heads_regressor_update(hr["joint"], hr["grain"], x["joint"], x["grain"], self.w_reg[0], self.w_reg[1],
-                                  p["joint"], p["grain"], p["grain_area"], self.dz, self.zmax, zf)
-        updated.record(main)
-        if not self.refresh_centres:
-            S["cen"][slot].copy_(x["grain"][:, :2])
-        # (noflux: the junctions as the step's events must see them -- before the boundary step -- ride with it)
-        self._enqueue_boundary(joints_before=S["jb"][slot] if self.noflux else None)
-        if self.refresh_centres:   # (the snapshot of the centres the events must see rides with the launch that replaces them)
-            self._enqueue_centres(centres_before=S["cen"][slot])
-        if headed_prev is not None:
-            main.wait_event(headed_prev)   # the previous step's classifier has read the edge set this refresh writes
-        be.step_refresh_prepare(x["joint"], x["grain"], self.zmax, zf,
-                                [(self.graph.csr[et], ea_next[et], x[et[0]], x[et[-1]], einfo_next[et])
-                                 for et in EDGE_TYPES], mirror=(xc_next["joint"], xc_next["grain"]))
-        with torch.cuda.stream(st_d):
-            st_d.wait_event(updated)   # grain_area of this step (and every cell of the regressor has reported its range)
-            st_d.wait_event(headed)    # ... and its edge_event (the classifier's cells have, too)
-            # (the slot's range word travels in flags[2] and is cleared by the same launch: it is sticky on the device)
-            be.detect_events(p["grain_area"], self._live_grain, self.area_threshold, p["edge_event"],
-                             self.graph.edge_index[ET_JJ], self._logit_trigger, S["evf"][slot], S["rw"][slot],
-                             E_dev=self.graph.csr[ET_JJ].E_dev, skip_grain=self._skip_grain())
-            S["evh"][slot].copy_(S["evf"][slot], non_blocking=True)
-        return [ready, lead, updated, headed]
+    def _spec_node_slots(self, D: int):
+        """The per-node buffers of the ring's `D` slots (_spec_state)."""
+        dev = self.x["joint"].device
+        return {"xs": [{nt: torch.empty_like(self.x[nt]) for nt in NODE_TYPES} for _ in range(D)],
+                "cen": [torch.empty(self.n_nodes["grain"], 2, device=dev) for _ in range(D)],
+                "jb": [torch.empty(self.n_nodes["joint"], 2, device=dev) for _ in range(D)],
+                "evf": [torch.zeros(4, dtype=torch.int32, device=dev) for _ in range(D)],
+                "evh": [torch.zeros(4, dtype=torch.int32).pin_memory() for _ in range(D)],
+                "zf": [torch.zeros(2, dtype=torch.int32, device=dev) for _ in range(D)],
+                "rw": [torch.zeros(1, dtype=torch.int32, device=dev) for _ in range(D)]}
+
+    def _spec_edge_slots(self, flat, D: int, Ea: int):
+        """The per-edge predictions of the ring's `D` slots for the current junction edge list, cut from `flat` (3 x Ea
+        floats per slot)."""
+        E = self.pred["edge_event"].numel()
+        return [{"edge_event": flat[3 * i * Ea:3 * i * Ea + E], "edge": flat[3 * i * Ea + Ea:3 * i * Ea + Ea + 2 * E].view(E, 2)}
+                for i in range(D)]
 
     def _enqueue_spec_steps(self, slots):
-        """The steps of a block back to back (a step's refresh waits for the previous step's classifier heads -- the last
-        reader of the edge set it writes --, nothing else of a step waits for the step before on the other stream), the
-        streams joined behind the last one."""
-        keep, headed = [], None
-        try:
-            for sl in slots:
-                ev = self._enqueue_spec_step(sl, headed)
-                headed = ev[-1]
-                keep += ev
-        finally:
-            for name in ("R", "C"):
-                self.ws[name].range_flag = self._range_word
-        torch.cuda.current_stream().wait_stream(self._side[1])
-        torch.cuda.current_stream().wait_stream(self._side[0])
+        """The steps of a block with events ASSUMED ABSENT: the overlapped step (_enqueue_overlapped_step) on the edge set of
+        the slot's parity and the slot's buffers -- nothing an event would need is overwritten by the steps enqueued behind
+        it: they use other slots of the ring (the copy of x the step leaves for the next one, its z-clamp flag and its range
+        word included) -- each followed by the event counts of its predictions (ggnn_detect_events) copied to pinned host
+        memory.  The streams are joined behind the last step.  Needs S["xs"][slots[0]] to equal x (_spec_launch)."""
+        S, be = self._spec, self.be
+        main, st_d = torch.cuda.current_stream(), self._side[0]   # (the event counts on a stream of their own: neither
+        keep, headed = [], None                                   #  model's chain waits for them)
+        for slot in slots:
+            s, p = slot & 1, S["pred"][slot]
+            ready, updated, headed = self._enqueue_overlapped_step(
+                S["ea"][s], S["ea"][1 - s], S["einfo"][s], S["einfo"][1 - s], S["xs"][slot], S["xs"][(slot + 1) % S["D"]],
+                p, S["zf"][slot], headed, slot)
+            keep.append((ready, updated, headed))
+            with torch.cuda.stream(st_d):
+                st_d.wait_event(updated)   # grain_area of this step (and every cell of the regressor has reported its range)
+                st_d.wait_event(headed)    # ... and its edge_event (the classifier's cells have, too)
+                # (the slot's range word travels in flags[2] and is cleared by the same launch: it is sticky on the device)
+                be.detect_events(p["grain_area"], self._live_grain, self.area_threshold, p["edge_event"],
+                                 self.graph.edge_index[ET_JJ], self._logit_trigger, S["evf"][slot], S["rw"][slot],
+                                 E_dev=self.graph.csr[ET_JJ].E_dev, skip_grain=self._skip_grain())
+                S["evh"][slot].copy_(S["evf"][slot], non_blocking=True)
+        main.wait_stream(self._side[1])
+        main.wait_stream(st_d)
         return keep
 
     def _spec_launch(self, n: int):
@@ -907,19 +816,9 @@ class GrainRollout:
         if self.use_graph and n > 1:
             g = S["graphs"].get((slots[0], n))
             if g is None:
-                if S.get("in_place"):   # valid for as long as no list is longer than now (_spec_state)
-                    now = {et: int(self.edge_index[et].size(1)) for et in EDGE_TYPES}
-                    got = S["captured"]
-                    S["captured"] = now if got is None else {et: min(now[et], got[et]) for et in EDGE_TYPES}
-                st = torch.cuda.Stream()
-                st.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(st):
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g, stream=st):
-                        keep = self._enqueue_spec_steps(slots)
-                torch.cuda.current_stream().wait_stream(st)
-                del keep
-                S["graphs"][(slots[0], n)] = g
+                if S["in_place"]:   # valid for as long as no list is longer than now (_spec_state)
+                    S["captured"] = self._smallest_sizes(S["captured"])
+                g = S["graphs"][(slots[0], n)] = self._captured(lambda: self._enqueue_spec_steps(slots))
             g.replay()
         else:
             self._enqueue_spec_steps(slots)
@@ -950,9 +849,9 @@ class GrainRollout:
         the next step.  Same results, bit for bit, as n_steps x step_events()
         (test_speculative_event_loop_equals_step_events).  Needs the two-stream launch plan (joint_launches=False,
         concurrent=True); otherwise runs step_events in a loop.  Returns (grain_events, switching_lists): one entry per step."""
-        if not hasattr(self, "mask"):
+        if self.mask is None:
             raise _lib.GGNNError("call enable_events(mask, ...) first")
-        if not (self._pipelined() and self.overlap_tail):
+        if not self._pipelined():
             out = [self.step_events()[1:] for _ in range(n_steps)]
             return [e for e, _ in out], [sw for _, sw in out]
         self.refresh_weights()
@@ -967,7 +866,7 @@ class GrainRollout:
             self.steps_done += 1
 
         K = max(1, int(self.EVENTS_UNROLL))
-        quiet_blocks = getattr(self, "_spec_quiet_blocks", 0)
+        quiet_blocks = self._spec_quiet_blocks
         blocks = []   # enqueued, unchecked: (slots, done event), oldest first
         while len(ev_out) < n_steps:
             in_flight = sum(len(b[0]) for b in blocks)
@@ -1043,8 +942,8 @@ class GrainRollout:
     def _event_buffers(self):
         """Pinned host staging of the event round trip, sized once (the lists only shrink: a removed grain appends two
         junction columns and drops at least eight; a list that grows past its room gets new buffers)."""
-        E, n_pq = self.edge_index[ET_JJ].size(1), self.edge_index[("joint", "pull", "grain")].size(1)
-        B = getattr(self, "_evb", None)
+        E, n_pq = self.edge_index[ET_JJ].size(1), self.edge_index[JG].size(1)
+        B = self._evb
         if B is not None and B["cap"] >= 2 * (E + n_pq) and B["prob_cap"] >= E:
             return B
         nj, ng = self.n_nodes["joint"], self.n_nodes["grain"]
@@ -1069,8 +968,8 @@ class GrainRollout:
         event (one read-back), afterwards patched by every update -- as long as the rollout's edge lists are the ones the
         session produced last."""
         from .topology import TopologySession
-        jj, jg = self.edge_index[ET_JJ], self.edge_index[("joint", "pull", "grain")]
-        T = getattr(self, "_topo", None)
+        jj, jg = self.edge_index[ET_JJ], self.edge_index[JG]
+        T = self._topo
         if T is not None and T[1] is jj and T[2] is jg and T[3] == (jj._version, jg._version):
             return T[0]
         if T is not None:
@@ -1093,92 +992,89 @@ class GrainRollout:
 
     def _apply_events(self, payload_ready=False):
         """Host round trip of an eventful step: the predictions and junction coordinates travel to pinned host memory in
-        one batch of asynchronous copies behind ONE synchronisation, the library's session rewires its lists in place
-        (ggnn_topology_apply: a refused update leaves everything as it was), the new lists, coordinates and masks travel
-        back asynchronously and the CSR tables are rebuilt without a read-back -- the host returns to enqueueing the next
-        step while the device is still uploading (round 5: six synchronous read-backs, three pageable uploads, the lists
-        copied five times on the host and every lookup table rebuilt per call; profiles/r6_event_step_breakdown.txt)."""
-        from .topology import TopologyError  # noqa: F401  (raised by the session; callers catch it from here)
-        import time
-        p, dev = self.pred, self.x["joint"].device
-        JG, GJ = ("joint", "pull", "grain"), ("grain", "push", "joint")
-        hook = getattr(self, "rewire_hook", None)   # test infrastructure: see below
-        T = getattr(self, "event_timing", None)      # a dict: host-side seconds of the pieces (tests/bench_event_step.py)
-        t0 = time.perf_counter()
-        ses = self._topology_session() if hook is None else None
-        B = self._event_buffers()
-        N = B["np"]
-        E = self.edge_index[ET_JJ].size(1)
-        if ses is not None and ses.n_pp != E:
-            raise _lib.GGNNError("the topology session and the rollout's junction edge list disagree")
+        one batch of asynchronous copies behind ONE synchronisation (_read_back_events), the library's session rewires its
+        lists in place (_rewire), the new lists, coordinates and masks travel back asynchronously (_upload_events) and the
+        CSR tables are rebuilt without a read-back (_install_event_topology) -- the host returns to enqueueing the next step
+        while the device is still uploading (profiles/r6_event_step_breakdown.txt).  Returns (grain events, switched edges)."""
+        self._read_back_events(payload_ready)
+        rewired = self._rewire(self._grain_candidates())
+        if rewired is None:
+            return np.zeros(0, np.int64), np.zeros((0, 2), np.int64)
+        events, switches, n_pp, n_pq = rewired
+        self._install_event_topology(self._upload_events(events, n_pp, n_pq))
+        return events, switches
+
+    def _read_back_events(self, payload_ready=False):
+        """What the rewiring reads, in the pinned staging buffers, and the host synchronised with the device
+        (`payload_ready`: step_events enqueued the copies behind the step's event counts and has synchronised)."""
         if not payload_ready:
             self._enqueue_event_readback()
             torch.cuda.current_stream().synchronize()
-        t1 = time.perf_counter()
-        area, prob = N["area"], N["prob"][:E]
+
+    def _grain_candidates(self):
+        """test.py:418-422: the live grains whose predicted area fell below the threshold, smallest first; for noflux never
+        the boundary grain."""
+        area = self._evb["np"]["area"]
         live = self.mask["grain"][:, 0] > 0
         ge = np.flatnonzero(live & (area < np.float32(self.area_threshold)))
-        ge = ge[np.argsort(area[ge], kind="stable")]                         # test.py:418-420
+        ge = ge[np.argsort(area[ge], kind="stable")]
         if self.noflux:
-            ge = ge[ge != 0]                                                  # test.py:421-422
-        if getattr(self, "max_grain_events", None) is not None:   # probe hook (tests/bench_event_step.py): random weights
-            ge = ge[:int(self.max_grain_events)]                  # tie the predicted areas of hundreds of grains
-        # (the session ignores edges at or below the threshold and the (dst, src) twin of every pair: with no grain below
-        # the area threshold either, the update is the identity -- the device-side trigger was conservative)
+            ge = ge[ge != 0]
+        return ge
+
+    def _rewire(self, ge):
+        """The library's session applies the step's events to its lists, the masks and the staged junction coordinates and
+        displacements (ggnn_topology_apply: a refused update leaves everything as it was) and exports its new lists into
+        the pinned list buffer.  Returns (grain events, switched edges, junction edges, junction-grain edges), or None when
+        nothing changed: the session ignores edges at or below the threshold and the (dst, src) twin of every pair, so with
+        no grain below the area threshold either the update is the identity (the device-side trigger was conservative)."""
+        ses = self._topology_session()
+        N = self._evb["np"]
+        E = self.edge_index[ET_JJ].size(1)
+        if ses.n_pp != E:
+            raise _lib.GGNNError("the topology session and the rollout's junction edge list disagree")
         mg, mj = self.mask["grain"], self.mask["joint"]
         if not (mg.dtype == np.int64 and mg.flags.c_contiguous and mj.dtype == np.int64 and mj.flags.c_contiguous):
             mg, mj = self.mask["grain"], self.mask["joint"] = np.ascontiguousarray(mg, np.int64), np.ascontiguousarray(mj, np.int64)
-        lists = N["lists"]
-        if hook is None:
-            events, switches = ses.apply(N["xj"], N["yj"], N["yg"][:, 0], prob, ge, mg, mj, self.edge_threshold)
-            if len(events) == 0 and len(switches) == 0:
-                return np.zeros(0, np.int64), np.zeros((0, 2), np.int64)
-            n_pp, n_pq = ses.n_pp, ses.n_pq
-            ses.export(lists[:2 * n_pp].reshape(2, n_pp), lists[2 * n_pp:2 * (n_pp + n_pq)].reshape(2, n_pq))
-        else:
-            # `rewire_hook`: another implementation of the update with topology.update_topology's signature (the tests'
-            # scan oracle, tests/fuzz_events.py) on copies that are committed together, like the reference's call
-            if len(ge) == 0 and not np.any(prob > np.float32(self.edge_threshold)):
-                return np.zeros(0, np.int64), np.zeros((0, 2), np.int64)
-            xj, yj, mg2, mj2 = N["xj"].copy(), N["yj"].copy(), mg.copy(), mj.copy()
-            pp, pq, _, switches, events = hook(xj, self.edge_index[ET_JJ].cpu().numpy(), self.edge_index[JG].cpu().numpy(),
-                                               yj, N["yg"], prob.copy(), ge, mg2, mj2, self.edge_threshold)
-            if len(events) == 0 and len(switches) == 0:
-                return np.zeros(0, np.int64), np.zeros((0, 2), np.int64)
-            N["xj"][...], N["yj"][...], mg[...], mj[...] = xj, yj, mg2, mj2
-            n_pp, n_pq = pp.shape[1], pq.shape[1]
-            lists[:2 * n_pp] = pp.reshape(-1)
-            lists[2 * n_pp:2 * (n_pp + n_pq)] = pq.reshape(-1)
-        t2 = time.perf_counter()
+        events, switches = ses.apply(N["xj"], N["yj"], N["yg"][:, 0], N["prob"][:E], ge, mg, mj, self.edge_threshold)
+        if len(events) == 0 and len(switches) == 0:
+            return None
+        n_pp, n_pq, lists = ses.n_pp, ses.n_pq, N["lists"]
+        ses.export(lists[:2 * n_pp].reshape(2, n_pp), lists[2 * n_pp:2 * (n_pp + n_pq)].reshape(2, n_pq))
+        self._topo = (ses, None, None, None)   # (its lists are the ones to come: _install_event_topology)
+        return events, switches, n_pp, n_pq
+
+    def _upload_events(self, events, n_pp, n_pq):
+        """The rewired junction coordinates and displacements, the live grains and the new lists back to the device,
+        asynchronously; the lists go straight into the buffers the topology lives in while they fit
+        (_install_topology_in_place finds them there).  Returns the new edge lists."""
+        B, dev = self._evb, self.x["joint"].device
         self.x["joint"].copy_(B["xj"], non_blocking=True)
-        p["joint"].copy_(B["yj"], non_blocking=True)
+        self.pred["joint"].copy_(B["yj"], non_blocking=True)
         if len(events):
-            N["live"][:] = mg[:, 0]
+            B["np"]["live"][:] = self.mask["grain"][:, 0]
             self._live_grain.copy_(B["live"], non_blocking=True)
-        C = getattr(self, "_cap", None)
+        C = self._cap
         if C is not None and n_pp <= C["cap"][ET_JJ] and n_pq <= C["cap"][JG] and n_pq <= C["cap"][GJ]:
-            # the lists go straight into the buffers the topology lives in (_install_topology_in_place finds them there)
             jj, jg = C["lists"][ET_JJ][:2 * n_pp].view(2, n_pp), C["lists"][JG][:2 * n_pq].view(2, n_pq)
             jj.copy_(B["lists"][:2 * n_pp].view(2, n_pp), non_blocking=True)
             jg.copy_(B["lists"][2 * n_pp:2 * (n_pp + n_pq)].view(2, n_pq), non_blocking=True)
             gj = C["lists"][GJ][:2 * n_pq].view(2, n_pq)
             torch.stack((jg[1], jg[0]), out=gj)
-            new_ei = {ET_JJ: jj, JG: jg, GJ: gj}
-        else:
-            d = torch.empty(2 * (n_pp + n_pq), dtype=torch.int64, device=dev)
-            d.copy_(B["lists"][:2 * (n_pp + n_pq)], non_blocking=True)
-            jj, jg = d[:2 * n_pp].view(2, n_pp), d[2 * n_pp:].view(2, n_pq)
-            new_ei = {ET_JJ: jj, JG: jg, GJ: torch.stack((jg[1], jg[0]))}
-        t3 = time.perf_counter()
+            return {ET_JJ: jj, JG: jg, GJ: gj}
+        d = torch.empty(2 * (n_pp + n_pq), dtype=torch.int64, device=dev)
+        d.copy_(B["lists"][:2 * (n_pp + n_pq)], non_blocking=True)
+        jj, jg = d[:2 * n_pp].view(2, n_pp), d[2 * n_pp:].view(2, n_pq)
+        return {ET_JJ: jj, JG: jg, GJ: torch.stack((jg[1], jg[0]))}
+
+    def _install_event_topology(self, new_ei):
+        """The rewired lists become the rollout's topology (_set_topology); the session that exported them follows them."""
         self._set_topology(new_ei, lasting=False, trusted=True)
-        if ses is not None:
+        if self._topo is not None and self._topo[1] is None:
             jj, jg = self.edge_index[ET_JJ], self.edge_index[JG]
-            self._topo = (ses, jj, jg, (jj._version, jg._version))
-        if getattr(self, "_cap", None) is None:   # (in place: the segment graphs stay)
+            self._topo = (self._topo[0], jj, jg, (jj._version, jg._version))
+        if self._cap is None:   # (in place: the segment graphs stay)
             self._drop_segment_graphs()
-        if T is not None:
-            T.update(readback_s=t1 - t0, rewiring_s=t2 - t1, upload_enqueue_s=t3 - t2, set_topology_s=time.perf_counter() - t3)
-        return events, switches
 
     def step(self):
         """Advance one rollout step; returns the prediction dict (tensors are reused)."""
@@ -1216,7 +1112,7 @@ class GrainRollout:
         """True when a fused cell has clamped an activation to fp16's range since the last check (include/ggnn.h,
         OPERAND RANGE): the trajectory since then is NOT the reference's -- re-run with GGNN_DEC=split GGNN_ENC=split.
         state() checks it (it synchronises anyway); one 4-byte read-back."""
-        hit = getattr(self, "_range_hit", False)   # (reports of run_events' committed steps, read with their event counts)
+        hit = self._range_hit   # (reports of run_events' committed steps, read with their event counts)
         if clear:
             self._range_hit = False
         return self.be.range_exceeded(self.x["joint"].device, clear, flag=self._range_word) or hit

@@ -58,11 +58,11 @@ def rollout_for(workload):
 
 def kth_area_threshold(ro, k):
     """A threshold just above the k-th smallest predicted area of the live grains.  Random weights tie the predicted areas of
-    hundreds of grains: `GrainRollout.max_grain_events` (a probe hook: at most that many grains per step, smallest
-    first) keeps a step at k eliminations + whatever they force."""
+    hundreds of grains: the rollout's grain selection cut to its first k (smallest first) keeps a step at k eliminations +
+    whatever they force."""
     area = ro.pred["grain_area"].cpu().numpy()
     live = ro.mask["grain"][:, 0] > 0
-    ro.max_grain_events = k
+    ro._grain_candidates = lambda: GrainRollout._grain_candidates(ro)[:k]
     return float(np.nextafter(np.float32(np.sort(area[live])[k - 1]), np.float32(1))), int(live.sum())
 
 
@@ -116,6 +116,28 @@ def sparse_events(period, cycles):
             "ms_per_step": round(t / (period * cycles), 3), "steps_per_s": round(period * cycles / t * 1e3, 1)}
 
 
+# the host-side pieces of GrainRollout._apply_events: (method, key of its interval)
+PIECES = (("_read_back_events", "readback_ms"), ("_grain_candidates", "rewiring_ms"), ("_rewire", "rewiring_ms"),
+          ("_upload_events", "upload_enqueue_ms"), ("_install_event_topology", "set_topology_ms"))
+
+
+def timed_pieces(ro, T):
+    """ro's _apply_events pieces wrapped with host-side timers whose intervals add up in T (ms); returns the undo."""
+    inner = {name: getattr(ro, name) for name, _ in PIECES}
+
+    def wrap(name, key):
+        def piece(*args):
+            t0 = time.perf_counter()
+            try:
+                return inner[name](*args)
+            finally:
+                T[key] = T.get(key, 0.0) + (time.perf_counter() - t0) * 1e3
+        return piece
+    for name, key in PIECES:
+        setattr(ro, name, wrap(name, key))
+    return lambda: [setattr(ro, name, fn) for name, fn in inner.items()]
+
+
 ro, X, mask = rollout_for("cfg3")
 ro.run(4 * ro.RUN_UNROLL)
 t_static, _ = timed(lambda: ro.run(20 * ro.RUN_UNROLL))
@@ -132,15 +154,16 @@ for rnd in range(6):
     ro.area_threshold, _ = kth_area_threshold(ro, 3)
     ro._einfo_fresh = False
     t_fwd, _ = timed(lambda: ro._run_segment("fwd"))
-    T = ro.event_timing = {}
+    T = {}
+    untime = timed_pieces(ro, T)
     t_apply, (events, switches) = timed(ro._apply_events)
+    untime()
     t_ref, _ = timed(lambda: ro._run_segment("ref"))
-    ro.event_timing = None
     ro._einfo_fresh = False
     ro._x_written_outside()
     ro.steps_done += 1
     rounds.append({"grains": int(len(events)), "forwards_update_ms": round(t_fwd, 3), "apply_events_ms": round(t_apply, 3),
-                   "refresh_ms": round(t_ref, 3), **{k[:-2] + "_ms": round(v * 1e3, 3) for k, v in T.items()}})
+                   "refresh_ms": round(t_ref, 3), **{k: round(v, 3) for k, v in T.items()}})
 steady = rounds[1:]   # (the first event of a process pays one-off allocations and opens the session)
 med = lambda key: round(float(np.median([r[key] for r in steady])), 3)
 out = {
@@ -148,7 +171,7 @@ out = {
     "static_step_us": round(static_us, 1), "quiet_event_step_us": round(quiet_us, 1),
     "quiet_over_static": round(quiet_us / static_us, 3),
     "eventful_step_ms": round(med("forwards_update_ms") + med("apply_events_ms") + med("refresh_ms"), 3),
-    "topology_in_place": getattr(ro, "_cap", None) is not None,   # (the segments' hipGraphs survive events: DESIGN section 6)
+    "topology_in_place": ro._cap is not None,   # (the segments' hipGraphs survive events: DESIGN section 6)
     "of_which": {"forwards_update_ms": med("forwards_update_ms"), "apply_events_ms": med("apply_events_ms"),
                  "apply_events_host_pieces_ms": {k: med(k) for k in ("readback_ms", "rewiring_ms", "upload_enqueue_ms",
                                                                       "set_topology_ms")},

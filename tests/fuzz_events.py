@@ -18,6 +18,8 @@ from graingraphnn_amd import rollout as rollout_mod, topology as native
 from graingraphnn_amd.synthetic import EDGE_TYPES
 from oracle import topology_scan as scan
 
+JJ, JG = ("joint", "connect", "joint"), ("joint", "pull", "grain")
+
 DEV = torch.device("cuda", 0)
 n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 24
 rs = np.random.RandomState(7)
@@ -42,13 +44,29 @@ with torch.no_grad():
         ev_a, sw_a, err_a = [], [], None
         # rollout a: one step at a time, rewiring by the scan oracle
 
-        def scan_update(*args, **kw2):
+        def scan_rewire(ge, ro=ra):
+            """GrainRollout._rewire by the scan oracle (topology.update_topology's signature), on copies that are committed
+            together, like the reference's call."""
+            N, E = ro._evb["np"], ro.edge_index[JJ].size(1)
+            prob, mg, mj = N["prob"][:E], ro.mask["grain"], ro.mask["joint"]
+            if len(ge) == 0 and not np.any(prob > np.float32(ro.edge_threshold)):
+                return None
+            xj, yj, mg2, mj2 = N["xj"].copy(), N["yj"].copy(), mg.copy(), mj.copy()
             try:
-                return scan.update_topology(*args, **kw2)
+                pp, pq, _, switches, events = scan.update_topology(
+                    xj, ro.edge_index[JJ].cpu().numpy(), ro.edge_index[JG].cpu().numpy(), yj, N["yg"], prob.copy(), ge, mg2,
+                    mj2, ro.edge_threshold)
             except (scan.TopologyError, IndexError, ValueError) as err:
                 raise native.TopologyError(str(err)) from None
+            if len(events) == 0 and len(switches) == 0:
+                return None
+            N["xj"][...], N["yj"][...], mg[...], mj[...] = xj, yj, mg2, mj2
+            n_pp, n_pq = pp.shape[1], pq.shape[1]
+            N["lists"][:2 * n_pp] = pp.reshape(-1)
+            N["lists"][2 * n_pp:2 * (n_pp + n_pq)] = pq.reshape(-1)
+            return events, switches, n_pp, n_pq
         try:
-            ra.rewire_hook = scan_update   # (GrainRollout._apply_events: the update by another implementation)
+            ra._rewire = scan_rewire   # (GrainRollout._apply_events: the update by another implementation)
             for _ in range(steps):
                 _, e, sw = ra.step_events()
                 ev_a.append(e), sw_a.append(sw)
