@@ -13,7 +13,7 @@ import torch  # noqa: F401  (must precede the dlopen below)
 LIB_NAME = "libggnn.so"
 LIB_PATH = os.environ.get("GGNN_LIB_PATH") or os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 
-GGNN_ABI_VERSION = 25
+GGNN_ABI_VERSION = 26
 GGNN_UNIT_EDGES = 3
 GGNN_EINFO_ROW = 20
 GGNN_C = 96
@@ -34,20 +34,19 @@ BC_PERIODIC, BC_NOFLUX = 0, 1   # GGNN_BC_*
 # Every symbol include/ggnn.h declares (tests/test_cabi.py checks the library exports them all).
 EXPORTED_SYMBOLS = (
     "ggnn_version", "ggnn_error_string", "ggnn_gemm_mode", "ggnn_csr_workspace_bytes", "ggnn_csr_max_units",
-    "ggnn_build_csr", "ggnn_build_csr_batch", "ggnn_build_csr_masked_batch", "ggnn_noflux_boundary", "ggnn_grain_centres_bc",
-    "ggnn_detect_events_skip",
-    "ggnn_edge_prepare", "ggnn_project", "ggnn_project_batch", "ggnn_period_gat_aggregate",
+    "ggnn_build_csr_batch", "ggnn_noflux_boundary",
+    "ggnn_edge_prepare", "ggnn_project_batch",
     "ggnn_period_gat_aggregate_batch", "ggnn_period_gat_aggregate_enc_batch", "ggnn_encoder_cell_batch",
     "ggnn_encoder_cell_values_batch",
     "ggnn_decoder_cell_batch",
     "ggnn_aggregate_bwd_partials", "ggnn_period_gat_aggregate_backward",
-    "ggnn_lstm_epilogue", "ggnn_lstm_epilogue_batch", "ggnn_heads_regressor", "ggnn_heads_regressor_update",
-    "ggnn_step_refresh_prepare", "ggnn_lstm_train_forward", "ggnn_lstm_train_backward",
+    "ggnn_lstm_epilogue_batch", "ggnn_heads_regressor", "ggnn_heads_regressor_update",
+    "ggnn_step_refresh_prepare",
     "ggnn_lstm_train_forward_batch", "ggnn_lstm_train_backward_batch", "ggnn_train_input_rows", "ggnn_sum_rows_batch",
     "ggnn_pack_weights_batch", "ggnn_pack_weights_backward_batch",
     "ggnn_wgrad_splits", "ggnn_wgrad", "ggnn_rowgemm_workspace_bytes", "ggnn_rowgemm_pack", "ggnn_rowgemm", "ggnn_rowgemm_pair", "ggnn_heads_regressor_backward",
-    "ggnn_adam_step", "ggnn_masked_mse", "ggnn_sum_rows", "ggnn_pack_weights", "ggnn_pack_weights_backward",
-    "ggnn_heads_classifier", "ggnn_heads_classifier_n", "ggnn_step_update", "ggnn_grain_centres", "ggnn_detect_events", "ggnn_detect_events_n", "ggnn_topology_update", "ggnn_topology_open", "ggnn_topology_apply",
+    "ggnn_adam_step", "ggnn_masked_mse", "ggnn_sum_rows",
+    "ggnn_heads_classifier", "ggnn_step_update", "ggnn_grain_centres", "ggnn_detect_events", "ggnn_topology_update", "ggnn_topology_open", "ggnn_topology_apply",
     "ggnn_topology_counts", "ggnn_topology_export", "ggnn_topology_close", "ggnn_step_refresh",
     "ggnn_workspace_bytes",
 )
@@ -318,34 +317,17 @@ def _declare(lib):
     lib.ggnn_error_string.argtypes = [c_int]
     lib.ggnn_csr_workspace_bytes.restype = c_size_t
     lib.ggnn_csr_workspace_bytes.argtypes = [c_int64, c_int64]
-    lib.ggnn_build_csr.restype = c_int
     lib.ggnn_csr_max_units.restype = c_int64
     lib.ggnn_csr_max_units.argtypes = [c_int64, c_int64]
-    lib.ggnn_build_csr.argtypes = [c_void_p, c_int64, c_int64, c_int64, c_void_p, c_void_p,
-                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                   c_size_t, c_void_p]
     lib.ggnn_build_csr_batch.restype = c_int
-    lib.ggnn_build_csr_batch.argtypes = [POINTER(CsrArgs), c_int, c_void_p]
-    lib.ggnn_build_csr_masked_batch.restype = c_int
-    lib.ggnn_build_csr_masked_batch.argtypes = [POINTER(CsrArgs), POINTER(CsrMask), c_int, c_void_p]
+    lib.ggnn_build_csr_batch.argtypes = [POINTER(CsrArgs), POINTER(CsrMask), c_int, c_void_p]
     lib.ggnn_noflux_boundary.restype = c_int
     lib.ggnn_noflux_boundary.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_float, c_float,
                                          c_void_p, c_int64, c_int, c_void_p, c_void_p]
-    lib.ggnn_grain_centres_bc.restype = c_int
-    lib.ggnn_grain_centres_bc.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_float, c_void_p,
-                                          c_int64, c_int64, c_void_p, c_int, c_void_p]
-    lib.ggnn_detect_events_skip.restype = c_int
-    lib.ggnn_detect_events_skip.argtypes = [c_void_p, c_void_p, c_int64, c_float, c_void_p, c_void_p, c_int64, c_void_p,
-                                            c_float, c_void_p, c_void_p, c_int64, c_void_p]
     lib.ggnn_edge_prepare.restype = c_int
     lib.ggnn_edge_prepare.argtypes = [POINTER(PrepareEdge), c_int, c_void_p]
-    lib.ggnn_project.restype = c_int
-    lib.ggnn_project.argtypes = [c_void_p, c_int64, c_int, c_void_p, c_int64, c_int, c_void_p,
-                                 c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p]
     lib.ggnn_project_batch.restype = c_int
     lib.ggnn_project_batch.argtypes = [POINTER(ProjectArgs), c_int, c_void_p]
-    lib.ggnn_period_gat_aggregate.restype = c_int
-    lib.ggnn_period_gat_aggregate.argtypes = [POINTER(AggregateArgs), c_void_p]
     lib.ggnn_period_gat_aggregate_batch.restype = c_int
     lib.ggnn_period_gat_aggregate_batch.argtypes = [POINTER(AggregateArgs), c_int, c_void_p]
     lib.ggnn_period_gat_aggregate_enc_batch.restype = c_int
@@ -360,8 +342,6 @@ def _declare(lib):
     lib.ggnn_aggregate_bwd_partials.argtypes = [c_int64]
     lib.ggnn_period_gat_aggregate_backward.restype = c_int
     lib.ggnn_period_gat_aggregate_backward.argtypes = [POINTER(AggregateBwdArgs), c_void_p]
-    lib.ggnn_lstm_epilogue.restype = c_int
-    lib.ggnn_lstm_epilogue.argtypes = [POINTER(EpilogueArgs), c_void_p]
     lib.ggnn_lstm_epilogue_batch.restype = c_int
     lib.ggnn_lstm_epilogue_batch.argtypes = [POINTER(EpilogueArgs), c_int, c_void_p]
     lib.ggnn_heads_regressor.restype = c_int
@@ -374,12 +354,6 @@ def _declare(lib):
     lib.ggnn_step_refresh_prepare.restype = c_int
     lib.ggnn_step_refresh_prepare.argtypes = [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_float, c_void_p,
                                               POINTER(PrepareEdge), c_int, c_void_p, c_void_p, c_void_p]
-    lib.ggnn_lstm_train_forward.restype = c_int
-    lib.ggnn_lstm_train_forward.argtypes = [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int64,
-                                            c_int, c_void_p]
-    lib.ggnn_lstm_train_backward.restype = c_int
-    lib.ggnn_lstm_train_backward.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
-                                             c_int64, c_int, c_void_p, c_int64, c_int, c_void_p]
     for fn in (lib.ggnn_lstm_train_forward_batch, lib.ggnn_lstm_train_backward_batch):
         fn.restype = c_int
         fn.argtypes = [POINTER(LstmTrainProblem), c_int, c_int, c_void_p]
@@ -405,10 +379,6 @@ def _declare(lib):
     lib.ggnn_sum_rows.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p]
     lib.ggnn_masked_mse.restype = c_int
     lib.ggnn_masked_mse.argtypes = [POINTER(MseArgs), c_void_p]
-    lib.ggnn_pack_weights.restype = c_int
-    lib.ggnn_pack_weights.argtypes = [POINTER(PackArgs), c_void_p]
-    lib.ggnn_pack_weights_backward.restype = c_int
-    lib.ggnn_pack_weights_backward.argtypes = [POINTER(PackBwdArgs), c_void_p]
     lib.ggnn_pack_weights_batch.restype = c_int
     lib.ggnn_pack_weights_batch.argtypes = [POINTER(PackArgs), c_int, c_void_p]
     lib.ggnn_pack_weights_backward_batch.restype = c_int
@@ -416,11 +386,8 @@ def _declare(lib):
     lib.ggnn_heads_regressor_backward.restype = c_int
     lib.ggnn_heads_regressor_backward.argtypes = [c_int64, c_int64] + [c_void_p] * 11
     lib.ggnn_heads_classifier.restype = c_int
-    lib.ggnn_heads_classifier.argtypes = [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
+    lib.ggnn_heads_classifier.argtypes = [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
-    lib.ggnn_heads_classifier_n.restype = c_int
-    lib.ggnn_heads_classifier_n.argtypes = [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
-                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.ggnn_step_update.restype = c_int
     lib.ggnn_step_update.argtypes = [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int,
                                      c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p]
@@ -428,14 +395,11 @@ def _declare(lib):
     lib.ggnn_step_refresh.argtypes = [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64,
                                       c_float, c_void_p, POINTER(RefreshEdge), c_int, c_void_p]
     lib.ggnn_grain_centres.restype = c_int
-    lib.ggnn_grain_centres.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
-                                       c_float, c_void_p, c_int64, c_int64, c_void_p, c_void_p]
+    lib.ggnn_grain_centres.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_float, c_void_p,
+                                       c_int64, c_int64, c_void_p, c_int, c_void_p]
     lib.ggnn_detect_events.restype = c_int
-    lib.ggnn_detect_events.argtypes = [c_void_p, c_void_p, c_int64, c_float, c_void_p, c_void_p, c_int64,
-                                       c_float, c_void_p, c_void_p, c_void_p]
-    lib.ggnn_detect_events_n.restype = c_int
-    lib.ggnn_detect_events_n.argtypes = [c_void_p, c_void_p, c_int64, c_float, c_void_p, c_void_p, c_int64, c_void_p,
-                                         c_float, c_void_p, c_void_p, c_void_p]
+    lib.ggnn_detect_events.argtypes = [c_void_p, c_void_p, c_int64, c_float, c_void_p, c_void_p, c_int64, c_void_p,
+                                       c_float, c_void_p, c_void_p, c_int64, c_void_p]
     lib.ggnn_topology_update.restype = c_int
     lib.ggnn_topology_update.argtypes = [POINTER(TopologyArgs)]
     lib.ggnn_topology_open.restype = c_int

@@ -25,6 +25,37 @@ class CSR:
         self.E_dev = E_dev
 
 
+class _WordArena:
+    """Hands out int32 tables one behind the other, each starting on a 16-byte boundary; without a buffer it only counts."""
+
+    def __init__(self, buf=None):
+        self.buf, self.at = buf, 0
+
+    def take(self, n):
+        t = None if self.buf is None else self.buf[self.at:self.at + n]
+        self.at += (n + 3) & ~3
+        return t
+
+
+def _csr_tables(lib, take, E_cap, n_src, n_dst, args=None):
+    """The tables of one list with up to E_cap edges, each from `take(n int32 words)`, in the one order and with the sizes
+    everything else relies on: -> (rowptr, col, perm, row, unit_ptr, units [n_units, 8], flags, workspace), their addresses
+    written into `args` (a CsrArgs; edge_index and E are the caller's).  args=None: `take` only counts, nothing is returned."""
+    E_cap, n_dst = int(E_cap), int(n_dst)
+    n_e, n_units = max(E_cap, 1), lib.ggnn_csr_max_units(E_cap, n_dst)
+    nbytes = lib.ggnn_csr_workspace_bytes(E_cap, n_dst)   # (sized for the capacity: enough for any shorter list)
+    rowptr, col, perm, row, unit_ptr, units, flags, ws = [
+        take(n) for n in (n_dst + 1, n_e, n_e, n_e, n_dst + 1, 8 * n_units, 2, nbytes // 4 + 1)]
+    if args is None:
+        return None
+    a = args
+    a.n_src, a.n_dst = n_src, n_dst
+    a.rowptr, a.col, a.perm, a.row = rowptr.data_ptr(), col.data_ptr(), perm.data_ptr(), row.data_ptr()
+    a.unit_ptr, a.units, a.flags = unit_ptr.data_ptr(), units.data_ptr(), flags.data_ptr()
+    a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+    return rowptr, col, perm, row, unit_ptr, units.view(n_units, 8), flags, ws
+
+
 class CsrInPlace:
     """See HipBackend.csr_in_place."""
 
@@ -34,30 +65,11 @@ class CsrInPlace:
         self.be, self.shapes = backend, [tuple(int(v) for v in s) for s in shapes]
         # masked lists (ggnn_csr_mask): refilled with the same mask; their tables' edge count lives in a device word
         self.masks, self.kept = _csr_masks(masks, len(self.shapes), device)
-        lib = backend.lib
-        r4 = lambda n: (n + 3) & ~3
         words = sum(backend.csr_arena_words(cap, n_dst) for cap, _, n_dst in self.shapes)
-        self.arena = torch.empty(words, dtype=torch.int32, device=device)
+        arena = _WordArena(torch.empty(words, dtype=torch.int32, device=device))
         self.args = (_lib.CsrArgs * len(self.shapes))()
-        self.csr, at = [], 0
-
-        def take(n, shape=None):
-            nonlocal at
-            t = self.arena[at:at + n]
-            at += r4(n)
-            return t if shape is None else t.view(shape)
-        for a, (cap, n_src, n_dst) in zip(self.args, self.shapes):
-            rowptr, col, perm, row = take(n_dst + 1), take(max(cap, 1)), take(max(cap, 1)), take(max(cap, 1))
-            unit_ptr = take(n_dst + 1)
-            n_units = lib.ggnn_csr_max_units(cap, n_dst)
-            units, flags = take(8 * n_units, (n_units, 8)), take(2)
-            nbytes = lib.ggnn_csr_workspace_bytes(cap, n_dst)
-            ws = take(nbytes // 4 + 1)
-            a.n_src, a.n_dst = n_src, n_dst
-            a.rowptr, a.col, a.perm, a.row = rowptr.data_ptr(), col.data_ptr(), perm.data_ptr(), row.data_ptr()
-            a.unit_ptr, a.units, a.flags = unit_ptr.data_ptr(), units.data_ptr(), flags.data_ptr()
-            a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes   # (sized for the capacity: enough for any shorter list)
-            self.csr.append(CSR(rowptr, col, perm, row, unit_ptr, units, 0))
+        self.csr = [CSR(*_csr_tables(backend.lib, arena.take, cap, n_src, n_dst, a)[:6], 0)
+                    for a, (cap, n_src, n_dst) in zip(self.args, self.shapes)]
 
     def rebuild(self, lists):
         """-> the CSR objects; those of masked lists carry E_dev = their kept-edge word."""
@@ -72,11 +84,8 @@ class CsrInPlace:
         for csr, w in zip(self.csr, self.kept):
             if w is not None:
                 csr.E_dev = w
-        if self.masks is None:
-            _lib.check(self.be.lib.ggnn_build_csr_batch(self.args, len(self.shapes), _lib.current_stream()), "ggnn_build_csr_batch")
-        else:
-            _lib.check(self.be.lib.ggnn_build_csr_masked_batch(self.args, self.masks, len(self.shapes), _lib.current_stream()),
-                       "ggnn_build_csr_masked_batch")
+        _lib.check(self.be.lib.ggnn_build_csr_batch(self.args, self.masks, len(self.shapes), _lib.current_stream()),
+                   "ggnn_build_csr_batch")
         return self.csr
 
 
@@ -110,6 +119,27 @@ def _f32c(t, name):
     if t.dtype != torch.float32 or not t.is_contiguous():
         raise _lib.GGNNError(f"{name} must be a contiguous float32 tensor")
     return t
+
+
+def _check_einfo(einfo, E):
+    if einfo.dtype != torch.float32 or not einfo.is_contiguous() or einfo.dim() != 2 \
+            or einfo.size(1) != _lib.GGNN_EINFO_ROW or einfo.size(0) < E + _lib.GGNN_UNIT_EDGES:
+        raise _lib.GGNNError("einfo must be contiguous float32 [E + GGNN_UNIT_EDGES, GGNN_EINFO_ROW]")
+
+
+def _prepare_edges(items):
+    """-> the ggnn_prepare_edge array of edge_prepare's items."""
+    arr = (PrepareEdge * max(len(items), 1))()
+    for a, (csr, ea, xs, xd, einfo) in zip(arr, items):
+        _require_cuda(csr.col, ea, xs, xd, einfo)
+        if einfo.size(0) < ea.numel() + _lib.GGNN_UNIT_EDGES or einfo.size(1) != _lib.GGNN_EINFO_ROW:
+            raise _lib.GGNNError("einfo must be [E + GGNN_UNIT_EDGES, GGNN_EINFO_ROW]")
+        a.col, a.perm, a.row = csr.col.data_ptr(), csr.perm.data_ptr(), csr.row.data_ptr()
+        a.edge_attr, a.x_src, a.x_dst = ea.data_ptr(), xs.data_ptr(), xd.data_ptr()
+        a.einfo = einfo.data_ptr()
+        a.ldx_src, a.ldx_dst, a.E, a.f_src = xs.stride(0), xd.stride(0), ea.numel(), xs.size(1)
+        a.E_dev = ptr(csr.E_dev)   # (a topology that shrinks in place under captured launches)
+    return arr
 
 
 class HipBackend:
@@ -191,9 +221,9 @@ class HipBackend:
     def csr_arena_words(self, E_cap, n_dst):
         """int32 words of one list's tables (row pointers, columns, permutation, rows, unit tables, flags, workspace) for up
         to E_cap edges, every table starting on a 16-byte boundary."""
-        r4 = lambda n: (n + 3) & ~3
-        return 2 * r4(n_dst + 1) + 3 * r4(max(int(E_cap), 1)) + 8 * self.lib.ggnn_csr_max_units(int(E_cap), n_dst) + 4 \
-            + r4(self.lib.ggnn_csr_workspace_bytes(int(E_cap), n_dst) // 4 + 1)
+        count = _WordArena()
+        _csr_tables(self.lib, count.take, E_cap, 0, n_dst)
+        return count.at
 
     def csr_in_place(self, shapes, device, masks=None):
         """Tables that are rebuilt in place: `shapes` = [(E_cap, n_src, n_dst)] (at most four lists) -> a CsrInPlace whose
@@ -208,7 +238,7 @@ class HipBackend:
         one range check = one host synchronisation behind the last (`check=False`: lists the caller has validated -- the
         kernels skip an out-of-range edge either way --: no read-back, the host goes on enqueueing).  (Tables that are
         refilled IN PLACE per event: `csr_in_place`.)  masks: None, or per list None / (skip_src, skip_dst) -- the tables of
-        the list without the edges from skip_src / into skip_dst (ggnn_build_csr_masked_batch); the CSR of a masked list has
+        the list without the edges from skip_src / into skip_dst (ggnn_csr_mask); the CSR of a masked list has
         E = the list's length and E_dev = the number of edges it kept (device word)."""
         out, todo = [], list(lists)
         mtodo = list(masks) if masks is not None else [None] * len(todo)
@@ -224,43 +254,22 @@ class HipBackend:
                 # dozen allocator calls and six fills otherwise; the unit table's unused tail and the range flags that
                 # nobody reads stay uninitialised)
                 need = sum(self.csr_arena_words(int(ei_.size(1)), n_dst) for ei_, _, n_dst in chunk)
-                arena = [torch.empty(need, dtype=torch.int32, device=chunk[0][0].device), 0]
-
-            def take(n, like_zeros=False, shape=None, dev=None):
-                if arena is None:
-                    t = (torch.zeros if like_zeros else torch.empty)(n, dtype=torch.int32, device=dev)
-                else:
-                    t = arena[0][arena[1]:arena[1] + n]
-                    arena[1] += (n + 3) & ~3
-                return t if shape is None else t.view(shape)
+                arena = _WordArena(torch.empty(need, dtype=torch.int32, device=chunk[0][0].device))
             for a, (edge_index, n_src, n_dst) in zip(arr, chunk):
                 _require_cuda(edge_index)
                 if edge_index.dtype != torch.int64 or edge_index.dim() != 2 or edge_index.size(0) != 2:
                     raise _lib.GGNNError("edge_index must be int64 [2, E]")
                 ei = edge_index.contiguous()
                 E, dev = ei.size(1), ei.device
-                rowptr = take(n_dst + 1, dev=dev)
-                col = take(max(E, 1), dev=dev)
-                perm = take(max(E, 1), dev=dev)
-                row = take(max(E, 1), dev=dev)
-                unit_ptr = take(n_dst + 1, dev=dev)
-                n_units = self.lib.ggnn_csr_max_units(E, n_dst)
-                units = take(8 * n_units, True, (n_units, 8), dev)
-                flags = take(2, True, dev=dev)
-                nbytes = self.lib.ggnn_csr_workspace_bytes(E, n_dst)
-                ws = take(nbytes // 4 + 1, dev=dev).view(torch.uint8)[:nbytes] if arena is not None else \
-                    torch.empty(nbytes, dtype=torch.uint8, device=dev)
-                a.edge_index, a.E, a.n_src, a.n_dst = ei.data_ptr(), E, n_src, n_dst
-                a.rowptr, a.col, a.perm, a.row = rowptr.data_ptr(), col.data_ptr(), perm.data_ptr(), row.data_ptr()
-                a.unit_ptr, a.units, a.flags = unit_ptr.data_ptr(), units.data_ptr(), flags.data_ptr()
-                a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+                take = arena.take if arena is not None else (lambda n: torch.empty(n, dtype=torch.int32, device=dev))
+                *tables, flags, ws = _csr_tables(self.lib, take, E, n_src, n_dst, a)
+                if arena is None:   # (a checked build: the flags are read back, the unit table is defined to its end)
+                    tables[-1].zero_()
+                    flags.zero_()
+                a.edge_index, a.E = ei.data_ptr(), E
                 keep.append((ei, ws, flags, n_src, n_dst))
-                out.append(CSR(rowptr, col, perm, row, unit_ptr, units, E, kept[len(keep) - 1]))
-            if marr is None:
-                _lib.check(self.lib.ggnn_build_csr_batch(arr, len(chunk), _lib.current_stream()), "ggnn_build_csr_batch")
-            else:
-                _lib.check(self.lib.ggnn_build_csr_masked_batch(arr, marr, len(chunk), _lib.current_stream()),
-                           "ggnn_build_csr_masked_batch")
+                out.append(CSR(*tables, E, kept[len(keep) - 1]))
+            _lib.check(self.lib.ggnn_build_csr_batch(arr, marr, len(chunk), _lib.current_stream()), "ggnn_build_csr_batch")
             if not check:   # (ei / ws / flags are only used by launches on this stream: the allocator keeps them until those ran)
                 continue
             bad = torch.stack([k[2][0] for k in keep]).cpu()   # (the synchronisation; also keeps ei / ws alive until here)
@@ -272,31 +281,16 @@ class HipBackend:
     # -- per-edge geometry -------------------------------------------------------------
     def edge_prepare(self, items):
         """items: list of (csr, edge_attr [E] COO order, x_src, x_dst, einfo_out [E + 3, GGNN_EINFO_ROW])."""
-        arr = (PrepareEdge * max(len(items), 1))()
-        for k, (csr, ea, xs, xd, einfo) in enumerate(items):
-            _require_cuda(csr.col, ea, xs, xd, einfo)
-            if einfo.size(0) < ea.numel() + _lib.GGNN_UNIT_EDGES or einfo.size(1) != _lib.GGNN_EINFO_ROW:
-                raise _lib.GGNNError("einfo must be [E + GGNN_UNIT_EDGES, GGNN_EINFO_ROW]")
-            a = arr[k]
-            a.col, a.perm, a.row = csr.col.data_ptr(), csr.perm.data_ptr(), csr.row.data_ptr()
-            a.edge_attr, a.x_src, a.x_dst = ea.data_ptr(), xs.data_ptr(), xd.data_ptr()
-            a.einfo = einfo.data_ptr()
-            a.ldx_src, a.ldx_dst, a.E, a.f_src = xs.stride(0), xd.stride(0), ea.numel(), xs.size(1)
-            a.E_dev = ptr(getattr(csr, "E_dev", None))   # (a topology that shrinks in place under captured launches)
+        arr = _prepare_edges(items)
         self._launch(self.lib.ggnn_edge_prepare, "ggnn_edge_prepare", arr, len(items), _lib.current_stream())
 
     # -- projection --------------------------------------------------------------------
     def project(self, x, F, h, wp, bp, out):
-        _require_cuda(x, h, wp, bp, out)
-        M = x.size(0)
-        k2 = 0 if h is None else h.size(1)
-        self._launch(self.lib.ggnn_project, "ggnn_project", ptr(x), x.stride(0), F, ptr(h),
-                     0 if h is None else h.stride(0), k2, ptr(wp), ptr(bp), M, wp.size(0), ptr(out),
-                     out.stride(0), _lib.current_stream())
+        self.project_batch([(x, F, h, wp, bp, out)])
 
     def project_batch(self, problems):
-        """Up to four projections in one launch (ggnn_project_batch); each item is the argument tuple
-        of `project`: (x, F, h, wp, bp, out[, precision]).  All with h or all without."""
+        """Up to four projections in one launch (ggnn_project_batch); each item: (x, F, h, wp, bp, out[, precision]).
+        All with h or all without."""
         arr = (ProjectArgs * len(problems))()
         if len({pr[2] is None for pr in problems}) > 1:
             raise _lib.GGNNError("ggnn_project_batch: every problem with a hidden state or none of them "
@@ -343,14 +337,11 @@ class HipBackend:
         a.pad_n = pad_n
 
     def aggregate(self, *sweep):
-        """One sweep of ggnn_period_gat_aggregate (include/ggnn.h): (csr, einfo, p_src, p_dst, h_src,
+        """One sweep (include/ggnn.h, ggnn_aggregate_args): (csr, einfo, p_src, p_dst, h_src,
         ep, agg, v_off, u_off, u4_off, a_off, a_gstride, sc_off, n_gates[, pad_n]).  h_src: the source node
         type's hidden state [n_src, 96] or None (encoder); pad_n: columns behind the sweep's scalars that it zeroes in
         every gate row (the training path's padded gate rows)."""
-        a = AggregateArgs()
-        self._sweep_args(a, *sweep)
-        check(self.lib.ggnn_period_gat_aggregate(ctypes.byref(a), _lib.current_stream()),
-              "ggnn_period_gat_aggregate")
+        self.aggregate_batch([sweep])
 
     def aggregate_batch(self, sweeps):
         """The 1..3 sweeps of one cell in one launch (ggnn_period_gat_aggregate_batch); each item
@@ -432,9 +423,7 @@ class HipBackend:
             _require_cuda(csr.rowptr, einfo)
             if csr.rowptr.numel() != n + 1:
                 raise _lib.GGNNError("the sweep's CSR does not have one row per destination node")
-            if einfo.dtype != torch.float32 or not einfo.is_contiguous() or einfo.dim() != 2 \
-                    or einfo.size(1) != _lib.GGNN_EINFO_ROW or einfo.size(0) < csr.E + _lib.GGNN_UNIT_EDGES:
-                raise _lib.GGNNError("einfo must be contiguous float32 [E + GGNN_UNIT_EDGES, GGNN_EINFO_ROW]")
+            _check_einfo(einfo, csr.E)
             sw.rowptr, sw.einfo, sw.E = csr.rowptr.data_ptr(), einfo.data_ptr(), csr.E
         a.x_dst, a.h_out, a.c_out = x_dst.data_ptr(), h_out.data_ptr(), c_out.data_ptr()
         a.wstream, a.w2_tail = wstream.data_ptr(), w2_tail.data_ptr()
@@ -493,9 +482,7 @@ class HipBackend:
                 _require_cuda(csr.rowptr, csr.col, einfo, h_src, v_src, ep)
                 if csr.rowptr.numel() != n + 1:
                     raise _lib.GGNNError("the sweep's CSR does not have one row per destination node")
-                if einfo.dtype != torch.float32 or not einfo.is_contiguous() or einfo.dim() != 2 \
-                        or einfo.size(1) != _lib.GGNN_EINFO_ROW or einfo.size(0) < csr.E + _lib.GGNN_UNIT_EDGES:
-                    raise _lib.GGNNError("einfo must be contiguous float32 [E + GGNN_UNIT_EDGES, GGNN_EINFO_ROW]")
+                _check_einfo(einfo, csr.E)
                 for t, name in ((h_src, "h_src"), (v_src, "v_src")):
                     if t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1 or t.size(0) != h_src.size(0):
                         raise _lib.GGNNError(f"ggnn_decoder_cell_batch: {name} must be float32 [n_src, *] with unit "
@@ -602,12 +589,9 @@ class HipBackend:
                 raise _lib.GGNNError("w2_planes does not match w2 (see packing.bf16_planes)")
             a.w2_planes = w2_planes.data_ptr()
 
-    def lstm_epilogue(self, *problem, **kw):
-        """(agg, w2, p_dst, s_off, c_in, h_out, c_out, raw_out, n_gates, mode, w2_planes=None, g_stride=0);
-        w2_planes: packing.bf16_planes(w2) (selects the bf16x6 kernel unless GGNN_GEMM=fp32)."""
-        a = EpilogueArgs()
-        self._epilogue_args(a, *problem, **kw)
-        self._launch(self.lib.ggnn_lstm_epilogue, "ggnn_lstm_epilogue", ctypes.byref(a), _lib.current_stream())
+    def lstm_epilogue(self, agg, w2, p_dst, s_off, c_in, h_out, c_out, raw_out, n_gates, mode, w2_planes=None, g_stride=0):
+        """w2_planes: packing.bf16_planes(w2) (selects the bf16x6 kernel unless GGNN_GEMM=fp32)."""
+        self.lstm_epilogue_batch([(agg, w2, p_dst, s_off, c_in, h_out, c_out, raw_out, n_gates, mode, w2_planes, g_stride)])
 
     def lstm_epilogue_batch(self, problems):
         """Up to four gate GEMM + LSTM problems (node types of a cell and / or both models) in one
@@ -620,27 +604,12 @@ class HipBackend:
 
     # -- LSTM update of the training path -----------------------------------------------
     def lstm_train_forward(self, z, p_dst, s_off, c_in, h_out, c_out):
-        """ggnn_lstm_train_forward: z [G, N, 96] (gate GEMM output in, pre-activations out)."""
-        _require_cuda(z, p_dst, c_in, h_out, c_out)
-        G, N = z.size(0), z.size(1)
-        if not z.is_contiguous() or z.size(2) != _lib.GGNN_C or not (h_out.is_contiguous() and c_out.is_contiguous()) \
-                or (c_in is not None and not c_in.is_contiguous()):
-            raise _lib.GGNNError("z [G, N, 96], c_in, h_out, c_out [N, 96] must be contiguous")
-        self._launch(self.lib.ggnn_lstm_train_forward, "ggnn_lstm_train_forward", ptr(z), ptr(p_dst), p_dst.stride(0),
-                     s_off, ptr(c_in), ptr(h_out), ptr(c_out), N, G, _lib.current_stream())
+        """One problem of lstm_train_forward_batch: z [G, N, 96] (gate GEMM output in, pre-activations out)."""
+        self.lstm_train_forward_batch([(z, p_dst, s_off, c_in, h_out, c_out)], z.size(0))
 
     def lstm_train_backward(self, z, c_in, c_out, g_h, g_c, g_z, g_p_dst, s_off, g_c_in):
-        """ggnn_lstm_train_backward: g_h / g_c / g_p_dst / g_c_in may be None."""
-        _require_cuda(z, c_in, c_out, g_h, g_c, g_z, g_p_dst, g_c_in)
-        G, N = z.size(0), z.size(1)
-        for t in (z, c_in, c_out, g_h, g_c, g_z, g_c_in):
-            if t is not None and not t.is_contiguous():
-                raise _lib.GGNNError("lstm_train_backward: z, g_z [G, N, 96] and the [N, 96] operands must be contiguous")
-        if g_z.shape != z.shape:
-            raise _lib.GGNNError("g_z must have the shape of z")
-        self._launch(self.lib.ggnn_lstm_train_backward, "ggnn_lstm_train_backward", ptr(z), ptr(c_in), ptr(c_out),
-                     ptr(g_h), ptr(g_c), ptr(g_z), ptr(g_p_dst), 0 if g_p_dst is None else g_p_dst.stride(0), s_off,
-                     ptr(g_c_in), N, G, _lib.current_stream())
+        """One problem of lstm_train_backward_batch (no padding columns): g_h / g_c / g_p_dst / g_c_in may be None."""
+        self.lstm_train_backward_batch([(z, c_in, c_out, g_h, g_c, g_z, g_p_dst, s_off, g_c_in, 0, 0)], z.size(0))
 
     def lstm_train_forward_batch(self, problems, n_gates):
         """ggnn_lstm_train_forward_batch: [(z [G, N, 96], p_dst, s_off, c_in or None, h_out, c_out)] -- the node types of a
@@ -850,7 +819,7 @@ class HipBackend:
             a.flat2, a.kq, a.kq_idx, a.idx3 = flat2.data_ptr(), kq.data_ptr(), plan.kq_idx.data_ptr(), plan.idx3.data_ptr()
         else:   # the parameters read where they lie: encoded index tables + the DEVICE table of their addresses
             if params.dtype != torch.int64 or params.numel() != len(plan.sizes) or not params.is_cuda:
-                raise _lib.GGNNError("ggnn_pack_weights: params must be a device int64 table with one address per parameter tensor")
+                raise _lib.GGNNError("ggnn_pack_weights_batch: params must be a device int64 table with one address per parameter tensor")
             a.flat2, a.kq, a.kq_idx, a.idx3 = flat2.data_ptr(), kq.data_ptr(), plan.kq_idx_enc.data_ptr(), plan.idx3_enc.data_ptr()
             a.params = params.data_ptr()
         a.packed = 0 if packed is None else packed.data_ptr()
@@ -860,7 +829,7 @@ class HipBackend:
         return a
 
     def pack_weights(self, plan, flat2, kq, packed, params=None):
-        """ggnn_pack_weights: `flat2` [plan.n_flat2] holds the parameters in its first n_flat entries -- or, with `params` (a
+        """One cell of pack_weights_batch: `flat2` [plan.n_flat2] holds the parameters in its first n_flat entries -- or, with `params` (a
         device int64 table of the parameter tensors' addresses), they are read where they lie and that part of flat2 is not
         touched; fills the operands `kq` [plan.n_kq], the products and `packed` [plan.n_packed] (train_pack._PackWeights)."""
         self.pack_weights_batch([(plan, flat2, kq, packed, params)])
@@ -873,12 +842,12 @@ class HipBackend:
             if flat2.dtype != torch.float32 or packed.dtype != torch.float32 or kq.dtype != torch.float32 \
                     or flat2.numel() != plan.n_flat2 or kq.numel() != plan.n_kq or packed.numel() != plan.n_packed \
                     or not flat2.is_contiguous() or not packed.is_contiguous() or not kq.is_contiguous():
-                raise _lib.GGNNError("ggnn_pack_weights: flat2 [n_flat2], kq [n_kq] and packed [n_packed] must be contiguous float32")
+                raise _lib.GGNNError("ggnn_pack_weights_batch: flat2 [n_flat2], kq [n_kq] and packed [n_packed] must be contiguous float32")
             arr[k] = self._pack_args(plan, flat2, kq, packed, params)
         self._launch(self.lib.ggnn_pack_weights_batch, "ggnn_pack_weights_batch", arr, len(cells), _lib.current_stream())
 
     def pack_weights_backward(self, plan, flat2, kq, grads, g_flat2, g_kq, g_flat):
-        """ggnn_pack_weights_backward: `grads` = the gradients of the nine packed outputs (None: zero), contiguous float32 of
+        """One cell of pack_weights_backward_batch: `grads` = the gradients of the nine packed outputs (None: zero), contiguous float32 of
         plan.out_sizes; workspaces g_flat2 [n_flat2], g_kq [n_kq]; g_flat [>= n_flat] receives the parameters' gradient in its
         first n_flat entries and zeros behind them (n_tail: the parameters without effect)."""
         self.pack_weights_backward_batch([(plan, flat2, kq, grads, g_flat2, g_kq, g_flat)])
@@ -895,13 +864,13 @@ class HipBackend:
         _require_cuda(flat2, g_flat2, g_kq, g_flat, *[g for g in grads if g is not None])
         if len(grads) != _lib.GGNN_PACK_OUTPUTS or g_flat2.numel() != plan.n_flat2 or g_kq.numel() != plan.n_kq \
                 or g_flat.numel() < plan.n_flat or not g_flat.is_contiguous():
-            raise _lib.GGNNError("ggnn_pack_weights_backward: nine output gradients and workspaces of the plan's sizes")
+            raise _lib.GGNNError("ggnn_pack_weights_backward_batch: nine output gradients and workspaces of the plan's sizes")
         b.fwd = self._pack_args(plan, flat2, kq)
         b.fwd.packed = g_flat.data_ptr()   # (unused by the backward; must not be NULL)
         off = 0
         for s, (g, n) in enumerate(zip(grads, plan.out_sizes)):
             if g is not None and (g.dtype != torch.float32 or g.numel() != n):
-                raise _lib.GGNNError("ggnn_pack_weights_backward: output gradients must be float32 of the outputs' sizes")
+                raise _lib.GGNNError("ggnn_pack_weights_backward_batch: output gradients must be float32 of the outputs' sizes")
             b.g_out[s] = None if g is None else g.data_ptr()
             b.g_off[s] = off
             off += n
@@ -912,7 +881,7 @@ class HipBackend:
             elif g.dim() == 1:          # a column of a matrix
                 b.g_w[s], b.g_rs[s], b.g_cs[s] = 1, g.stride(0), 1
             else:
-                raise _lib.GGNNError("ggnn_pack_weights_backward: a non-contiguous output gradient must be 1-D or 2-D")
+                raise _lib.GGNNError("ggnn_pack_weights_backward_batch: a non-contiguous output gradient must be 1-D or 2-D")
         b.g_off[_lib.GGNN_PACK_OUTPUTS] = off
         b.inv, b.inv_kq = plan.inv.data_ptr(), plan.inv_kq.data_ptr()
         b.g_flat2, b.g_kq, b.g_flat = g_flat2.data_ptr(), g_kq.data_ptr(), g_flat.data_ptr()
@@ -997,31 +966,21 @@ class HipBackend:
             if mj.shape != x_joint.shape or mg.shape != x_grain.shape or mj.stride() != x_joint.stride() \
                     or mg.stride() != x_grain.stride() or mj.dtype != torch.float32 or mg.dtype != torch.float32:
                 raise _lib.GGNNError("mirror tensors must have the shape and strides of x_joint / x_grain")
-        arr = (PrepareEdge * max(len(items), 1))()
-        for k, (csr, ea, xs, xd, einfo) in enumerate(items):
-            _require_cuda(csr.col, ea, xs, xd, einfo)
-            if einfo.size(0) < ea.numel() + _lib.GGNN_UNIT_EDGES or einfo.size(1) != _lib.GGNN_EINFO_ROW:
-                raise _lib.GGNNError("einfo must be [E + GGNN_UNIT_EDGES, GGNN_EINFO_ROW]")
-            a = arr[k]
-            a.col, a.perm, a.row = csr.col.data_ptr(), csr.perm.data_ptr(), csr.row.data_ptr()
-            a.edge_attr, a.x_src, a.x_dst = ea.data_ptr(), xs.data_ptr(), xd.data_ptr()
-            a.einfo = einfo.data_ptr()
-            a.ldx_src, a.ldx_dst, a.E, a.f_src = xs.stride(0), xd.stride(0), ea.numel(), xs.size(1)
-            a.E_dev = ptr(getattr(csr, "E_dev", None))   # (a topology that shrinks in place under captured launches)
+        arr = _prepare_edges(items)
         self._launch(self.lib.ggnn_step_refresh_prepare, "ggnn_step_refresh_prepare", ptr(x_joint), x_joint.size(0),
                      x_joint.stride(0), ptr(x_grain), x_grain.size(0), x_grain.stride(0), zmax, ptr(flags), arr,
                      len(items), None if mj is None else ptr(mj), None if mg is None else ptr(mg), _lib.current_stream())
 
     def heads_classifier(self, h_joint, edge_index_jj, edge_attr_jj, w_node, w_edge, node_tmp,
                          edge_event, edge, E_dev=None):
-        """`E_dev` (int64 [1], device): the number of edges at RUN time (ggnn_heads_classifier_n; edge_index_jj's own width is
-        then the capacity the launch is sized for)."""
+        """`E_dev` (int64 [1], device): the number of edges at RUN time (edge_index_jj's own width is then the capacity the
+        launch is sized for)."""
         _require_cuda(h_joint, edge_index_jj, edge_attr_jj, w_node, w_edge, node_tmp, edge_event, edge, E_dev)
         E = edge_index_jj.size(1)
-        check(self.lib.ggnn_heads_classifier_n(ptr(h_joint), h_joint.size(0), ptr(edge_index_jj), E, ptr(E_dev),
-                                               ptr(edge_attr_jj), ptr(w_node), ptr(w_edge),
-                                               ptr(node_tmp), ptr(edge_event), ptr(edge),
-                                               _lib.current_stream()), "ggnn_heads_classifier")
+        check(self.lib.ggnn_heads_classifier(ptr(h_joint), h_joint.size(0), ptr(edge_index_jj), E, ptr(E_dev),
+                                             ptr(edge_attr_jj), ptr(w_node), ptr(w_edge),
+                                             ptr(node_tmp), ptr(edge_event), ptr(edge),
+                                             _lib.current_stream()), "ggnn_heads_classifier")
 
     # -- rollout-step glue -------------------------------------------------------------
     def step_update(self, x_joint, x_grain, y_joint, y_grain, dz, zmax, flags):
@@ -1051,18 +1010,10 @@ class HipBackend:
                 raise _lib.GGNNError("domain_offset must be [n_joint, 2]")
         elif domain_factor > 1:
             raise _lib.GGNNError("domain_factor > 1 needs the domain_offset of scale_feature_patchs")
-        if bc == _lib.BC_PERIODIC:
-            check(self.lib.ggnn_grain_centres(ptr(csr_jg.rowptr), ptr(csr_jg.col), ptr(x_joint),
-                                              x_joint.size(0), x_joint.stride(0),
-                                              ptr(domain_offset) if domain_offset is not None else None,
-                                              float(domain_factor), ptr(x_grain), x_grain.size(0),
-                                              x_grain.stride(0), ptr(centres_before), _lib.current_stream()),
-                  "ggnn_grain_centres")
-        else:
-            check(self.lib.ggnn_grain_centres_bc(ptr(csr_jg.rowptr), ptr(csr_jg.col), ptr(x_joint), x_joint.size(0),
-                                                 x_joint.stride(0), ptr(domain_offset), float(domain_factor), ptr(x_grain),
-                                                 x_grain.size(0), x_grain.stride(0), ptr(centres_before), bc,
-                                                 _lib.current_stream()), "ggnn_grain_centres_bc")
+        check(self.lib.ggnn_grain_centres(ptr(csr_jg.rowptr), ptr(csr_jg.col), ptr(x_joint), x_joint.size(0),
+                                          x_joint.stride(0), ptr(domain_offset), float(domain_factor), ptr(x_grain),
+                                          x_grain.size(0), x_grain.stride(0), ptr(centres_before), bc,
+                                          _lib.current_stream()), "ggnn_grain_centres")
 
     def noflux_boundary(self, csr_jg, x_joint, x_grain, domain_factor=1.0, domain_offset=None, max_y=1.0,
                         joints_before=None):
@@ -1097,17 +1048,10 @@ class HipBackend:
             raise _lib.GGNNError("live_grain / flags must be int32 (flags: two words, three with a range word)")
         if range_word is not None and (range_word.dtype != torch.int32 or range_word.numel() < 1):
             raise _lib.GGNNError("range_word must be an int32 word")
-        if skip_grain < 0:
-            check(self.lib.ggnn_detect_events_n(ptr(grain_area), ptr(live_grain), grain_area.numel(),
-                                                float(area_threshold), ptr(edge_event), ptr(edge_index_jj),
-                                                edge_index_jj.size(1), ptr(E_dev), float(logit_threshold), ptr(flags),
-                                                ptr(range_word), _lib.current_stream()), "ggnn_detect_events")
-        else:
-            check(self.lib.ggnn_detect_events_skip(ptr(grain_area), ptr(live_grain), grain_area.numel(),
-                                                   float(area_threshold), ptr(edge_event), ptr(edge_index_jj),
-                                                   edge_index_jj.size(1), ptr(E_dev), float(logit_threshold), ptr(flags),
-                                                   ptr(range_word), int(skip_grain), _lib.current_stream()),
-                  "ggnn_detect_events_skip")
+        check(self.lib.ggnn_detect_events(ptr(grain_area), ptr(live_grain), grain_area.numel(),
+                                          float(area_threshold), ptr(edge_event), ptr(edge_index_jj),
+                                          edge_index_jj.size(1), ptr(E_dev), float(logit_threshold), ptr(flags),
+                                          ptr(range_word), int(skip_grain), _lib.current_stream()), "ggnn_detect_events")
 
     def step_refresh(self, x_joint, x_grain, zmax, flags, edges):
         """edges: list of (edge_index [2,E] int64, x_src, x_dst, edge_attr_out [E][, E_dev int64 [1] or None])."""

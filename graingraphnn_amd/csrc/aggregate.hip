@@ -10,7 +10,7 @@
 //   alpha = exp(s_e - max_i) / (sum_i exp(.) + 1e-16)                            (PyG softmax)
 //   r_e   = relu(V0_j + Wv3 . reloc_e)          V0 = value WITHOUT its first three input columns
 //   agg_i = sum_e alpha_e r_e,  sa_i = sum_e alpha_e,  sae_i = sum_e alpha_e a_e
-// The KEY never exists: the destination-side projection (ggnn_project) delivers u_i, s1_i, s2_i
+// The KEY never exists: the destination-side projection (ggnn_project_batch) delivers u_i, s1_i, s2_i
 // (all affine in the destination's [x_i | h_i]: one row of W_k^T W_q per source feature), and
 // the sweep dots u_i with the source's RAW [x_j | h_j] row.  Against gathering a projected key
 // this removes a quarter of the projection's output columns, and the 384-byte h_j row is shared
@@ -484,8 +484,4 @@ extern "C" int ggnn_period_gat_aggregate_batch(const ggnn_aggregate_args* args, 
   else GGNN_AG_LAUNCH(1);
 #undef GGNN_AG_LAUNCH
   return launch_status();
-}
-
-extern "C" int ggnn_period_gat_aggregate(const ggnn_aggregate_args* args, ggnn_stream_t stream) {
-  return ggnn_period_gat_aggregate_batch(args, 1, stream);
 }

@@ -1,5 +1,5 @@
 // Backward of the periodic-boundary GAT aggregation sweep (training path): the
-// gradient of ggnn_period_gat_aggregate with respect to its floating-point operands.  Replaces
+// gradient of ggnn_period_gat_aggregate_batch with respect to its floating-point operands.  Replaces
 // what autograd does for PeriodConv.message + PyG propagate (periodGATconv.py:174-175, 204-236):
 // segment-softmax backward, the relu mask, scatter of the value gradient to the source rows.
 //

@@ -1,6 +1,6 @@
 // Encoder aggregation sweep (h = c = 0: the cell sees only the 8 / 11 node features) with the edge
 // values on the matrix cores.  Same contract as the h_src == NULL form of
-// ggnn_period_gat_aggregate (aggregate.hip) -- PeriodConv.message (periodGATconv.py:204-236) +
+// ggnn_period_gat_aggregate_batch (aggregate.hip) -- PeriodConv.message (periodGATconv.py:204-236) +
 // propagate's gather / scatter-add, all gates of one edge type --, but nothing is gathered from a
 // projected source row: with h = 0 the value of edge e = (j -> i) is
 //     r_e = relu(W_value . x~_e + b_value),   x~_e = [reloc_e, x_j[3:F]]
@@ -16,7 +16,7 @@
 //     ITS unit: the alpha-weighted sum over the unit's edges is lane-local (registers r = 0..2 of
 //     D) and every 8-byte store instruction of a group covers one whole 128-byte line;
 //   * SCORES: the same A x a [16 x 16] operand whose column 4u + g is the destination-side tail
-//     u4 of unit u's row for gate g (ggnn_project: u . x + s1 + a_e s2, see aggregate.hip) and
+//     u4 of unit u's row for gate g (ggnn_project_batch: u . x + s1 + a_e s2, see aggregate.hip) and
 //     whose column 4u + 3 picks a_e: one more MFMA chain; the softmax of a unit is local to lane
 //     4q + g of group q, its 3 weights and the rescale factor reach the group through
 //     ds_bpermute;

@@ -158,12 +158,8 @@ extern "C" int64_t ggnn_csr_max_units(int64_t E, int64_t n_dst) {
   return (n_dst > 0 ? n_dst : 0) + (E > 0 ? E : 0) / GGNN_UNIT_EDGES + 1;
 }
 
-extern "C" int ggnn_build_csr_batch(const ggnn_csr_args* problems, int n_problems, ggnn_stream_t stream_) {
-  return ggnn_build_csr_masked_batch(problems, nullptr, n_problems, stream_);
-}
-
-extern "C" int ggnn_build_csr_masked_batch(const ggnn_csr_args* problems, const ggnn_csr_mask* masks, int n_problems,
-                                           ggnn_stream_t stream_) {
+extern "C" int ggnn_build_csr_batch(const ggnn_csr_args* problems, const ggnn_csr_mask* masks, int n_problems,
+                                    ggnn_stream_t stream_) {
   using namespace ggnn;
   hipStream_t stream = (hipStream_t)stream_;
   if (!problems || n_problems < 1 || n_problems > CSR_MAX_BATCH) return GGNN_EINVAL;
@@ -201,14 +197,4 @@ extern "C" int ggnn_build_csr_masked_batch(const ggnn_csr_args* problems, const 
   hipLaunchKernelGGL(csr_scan_batch_kernel<true>, dim3(ny), dim3(1024), 0, stream, B);
   hipLaunchKernelGGL(csr_unit_fill_batch_kernel, dim3(nb, ny), dim3(256), 0, stream, B);
   return launch_status();
-}
-
-extern "C" int ggnn_build_csr(const int64_t* edge_index, int64_t E, int64_t n_src, int64_t n_dst,
-                              int32_t* rowptr, int32_t* col, int32_t* perm, int32_t* row,
-                              int32_t* unit_ptr, int32_t* units, int32_t* flags, void* workspace, size_t workspace_bytes, ggnn_stream_t stream_) {
-  ggnn_csr_args P;
-  P.edge_index = edge_index, P.E = E, P.n_src = n_src, P.n_dst = n_dst;
-  P.rowptr = rowptr, P.col = col, P.perm = perm, P.row = row, P.unit_ptr = unit_ptr, P.units = units, P.flags = flags;
-  P.workspace = workspace, P.workspace_bytes = workspace_bytes;
-  return ggnn_build_csr_batch(&P, 1, stream_);
 }

@@ -4,7 +4,7 @@
 // W2[g] packs, per incoming edge type, lin_l2.weight (periodGATconv.py:218) and the two
 // rank-1 columns (lin_l2.bias x sum alpha, lin_edge.weight x sum alpha*a, :231-235); skip[g]
 // (lin_skip summed over incoming edge types, :186, HeteroConv aggr='sum', + b_g) was written
-// by ggnn_project.  The epilogue is the cell of heteropgclstm.py:111-146:
+// by ggnn_project_batch.  The epilogue is the cell of heteropgclstm.py:111-146:
 //   i = sig(pre_i); f = sig(pre_f); c' = f*c + i*tanh(pre_c); o = sig(pre_o); h' = o*tanh(c')
 // (encoder: h = c = 0, so f is never needed and c' = i*tanh(pre_c)).
 //
@@ -94,7 +94,7 @@ __global__ __launch_bounds__(GT_MAXG * 192, 1) void gates_kernel(const ggnn_epil
   // chunk c of a gate covers columns [c * 100, min(KA, c * 100 + 100))
   auto kc_of = [](int c) { return (c + 1) * GT_KC <= KA ? GT_KC : KA - c * GT_KC; };
 
-  // The accumulators START from the skip / bias term written by ggnn_project (pre = skip +
+  // The accumulators START from the skip / bias term written by ggnn_project_batch (pre = skip +
   // agg . W2^T): its loads fly together with the first chunk's, and the epilogue has nothing
   // left to fetch but c.
   const int64_t m = m0 + lr, m_c = min(m, A.N - 1);
@@ -249,8 +249,4 @@ extern "C" int ggnn_lstm_epilogue_batch(const ggnn_epilogue_args* args, int n_pr
     if (rc != GGNN_OK) return rc;
   }
   return GGNN_OK;
-}
-
-extern "C" int ggnn_lstm_epilogue(const ggnn_epilogue_args* args, ggnn_stream_t stream) {
-  return ggnn_lstm_epilogue_batch(args, 1, stream);
 }

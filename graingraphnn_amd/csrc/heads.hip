@@ -120,7 +120,7 @@ __global__ __launch_bounds__(256) void heads_classifier_edge_kernel(
   if (e >= E) return;
   const int64_t s = ei[e], d = ei[E + e];
   if ((uint64_t)s >= (uint64_t)n_joint || (uint64_t)d >= (uint64_t)n_joint) {
-    edge_event[e] = NAN;  // never reached when the same edge_index passed ggnn_build_csr
+    edge_event[e] = NAN;  // never reached when the same edge_index passed ggnn_build_csr_batch
     edge[2 * e] = NAN;
     edge[2 * e + 1] = NAN;
     return;
@@ -220,19 +220,10 @@ extern "C" int ggnn_heads_regressor_update(const float* h_joint, int64_t n_joint
   return launch_status();
 }
 
-extern "C" int ggnn_heads_classifier(const float* h_joint, int64_t n_joint,
-                                     const int64_t* edge_index_jj, int64_t E,
-                                     const float* edge_attr_jj, const float* w_node,
-                                     const float* w_edge, float* node_tmp, float* edge_event,
-                                     float* edge, ggnn_stream_t stream) {
-  return ggnn_heads_classifier_n(h_joint, n_joint, edge_index_jj, E, nullptr, edge_attr_jj, w_node, w_edge, node_tmp, edge_event,
-                                 edge, stream);
-}
-
-extern "C" int ggnn_heads_classifier_n(const float* h_joint, int64_t n_joint, const int64_t* edge_index_jj, int64_t E,
-                                       const int64_t* E_dev, const float* edge_attr_jj, const float* w_node,
-                                       const float* w_edge, float* node_tmp, float* edge_event, float* edge,
-                                       ggnn_stream_t stream) {
+extern "C" int ggnn_heads_classifier(const float* h_joint, int64_t n_joint, const int64_t* edge_index_jj, int64_t E,
+                                     const int64_t* E_dev, const float* edge_attr_jj, const float* w_node,
+                                     const float* w_edge, float* node_tmp, float* edge_event, float* edge,
+                                     ggnn_stream_t stream) {
   using namespace ggnn;
   if (!h_joint || !w_node || !w_edge || !node_tmp || n_joint <= 0 || E < 0) return GGNN_EINVAL;
   if (E > 0 && (!edge_index_jj || !edge_attr_jj || !edge_event || !edge)) return GGNN_EINVAL;

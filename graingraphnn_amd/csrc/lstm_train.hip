@@ -169,21 +169,3 @@ extern "C" int ggnn_lstm_train_backward_batch(const ggnn_lstm_train_problem* pro
     hipLaunchKernelGGL(lstm_train_bwd_kernel<3>, dim3((unsigned)B.blk_off[B.n]), dim3(256), 0, stream, B);
   return hipGetLastError() == hipSuccess ? 0 : GGNN_ELAUNCH;
 }
-
-extern "C" int ggnn_lstm_train_forward(float* z, const float* p_dst, int64_t ldp, int s_off, const float* c_in,
-                                       float* h_out, float* c_out, int64_t N, int n_gates, ggnn_stream_t stream) {
-  ggnn_lstm_train_problem P = {};
-  P.z = z, P.p_dst = p_dst, P.c_in = c_in, P.h_out = h_out, P.c_out = c_out;
-  P.ldp = ldp, P.N = N, P.s_off = s_off;
-  return ggnn_lstm_train_forward_batch(&P, 1, n_gates, stream);
-}
-
-extern "C" int ggnn_lstm_train_backward(const float* z, const float* c_in, const float* c_out, const float* g_h,
-                                        const float* g_c, float* g_z, float* g_p_dst, int64_t ldp, int s_off,
-                                        float* g_c_in, int64_t N, int n_gates, ggnn_stream_t stream) {
-  ggnn_lstm_train_problem P = {};
-  P.z = const_cast<float*>(z), P.c_in = c_in, P.c_out = const_cast<float*>(c_out), P.g_h = g_h, P.g_c = g_c;
-  P.g_z = g_z, P.g_p_dst = g_p_dst, P.g_c_in = g_c_in;
-  P.ldp = ldp, P.N = N, P.s_off = s_off;
-  return ggnn_lstm_train_backward_batch(&P, 1, n_gates, stream);
-}

@@ -274,9 +274,3 @@ extern "C" int ggnn_pack_weights_backward_batch(const ggnn_pack_bwd_args* args, 
   hipLaunchKernelGGL(pack_bwd_params_kernel, dim3((unsigned)B.off[n_cells]), dim3(256), 0, st, B);
   return launch_status();
 }
-
-extern "C" int ggnn_pack_weights(const ggnn_pack_args* args, ggnn_stream_t stream) { return ggnn_pack_weights_batch(args, 1, stream); }
-
-extern "C" int ggnn_pack_weights_backward(const ggnn_pack_bwd_args* args, ggnn_stream_t stream) {
-  return ggnn_pack_weights_backward_batch(args, 1, stream);
-}

@@ -268,10 +268,3 @@ extern "C" int ggnn_project_batch(const ggnn_project_args* args, int n_problems,
   else hipLaunchKernelGGL((project_kernel<96>), dim3(n_wg), dim3(PJ_WAVES * 64), 0, s, B);
   return launch_status();
 }
-
-extern "C" int ggnn_project(const float* X, int64_t ldx, int F, const float* H, int64_t ldh,
-                            int k2, const float* Wp, const float* bias, int64_t M, int ncols,
-                            float* out, int64_t ldo, ggnn_stream_t stream) {
-  const ggnn_project_args a = {X, H, Wp, bias, out, ldx, ldh, M, ldo, F, k2, ncols, 0};
-  return ggnn_project_batch(&a, 1, stream);
-}

@@ -223,7 +223,7 @@ __global__ __launch_bounds__(256) void step_refresh_kernel(
   if (e >= E) return;
   const int64_t s = T.edge_index[e], d = T.edge_index[E + e];
   if ((uint64_t)s >= (uint64_t)T.n_src || (uint64_t)d >= (uint64_t)T.n_dst) {
-    T.edge_attr[e] = NAN;  // never reached for an edge_index that passed ggnn_build_csr
+    T.edge_attr[e] = NAN;  // never reached for an edge_index that passed ggnn_build_csr_batch
     return;
   }
   const float* xs = T.x_src + s * T.ldx_src;
@@ -256,39 +256,20 @@ extern "C" int ggnn_step_update(float* x_joint, int64_t n_joint, int64_t ldx_joi
   return launch_status();
 }
 
-extern "C" int ggnn_grain_centres(const int32_t* rowptr, const int32_t* col, const float* x_joint,
-                                  int64_t n_joint, int64_t ldx_joint, const float* domain_offset,
-                                  float domain_factor, float* x_grain, int64_t n_grain,
-                                  int64_t ldx_grain, float* centres_before, ggnn_stream_t stream) {
+extern "C" int ggnn_grain_centres(const int32_t* rowptr, const int32_t* col, const float* x_joint, int64_t n_joint,
+                                  int64_t ldx_joint, const float* domain_offset, float domain_factor, float* x_grain,
+                                  int64_t n_grain, int64_t ldx_grain, float* centres_before, int boundary,
+                                  ggnn_stream_t stream) {
   using namespace ggnn;
+  if (boundary != GGNN_BC_PERIODIC && boundary != GGNN_BC_NOFLUX) return GGNN_EINVAL;
   if (!rowptr || !col || !x_joint || !x_grain) return GGNN_EINVAL;
   if (n_joint <= 0 || n_grain <= 0 || ldx_joint < 2 || ldx_grain < 2) return GGNN_EINVAL;
   if (!(domain_factor >= 1.0f)) return GGNN_EINVAL;
   const int64_t nblk = (n_grain + 255) / 256;
   if (nblk >= INT32_MAX) return GGNN_EINVAL;
-  hipLaunchKernelGGL(grain_centres_kernel<true>, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream,
-                     rowptr, col, x_joint, ldx_joint, domain_offset, domain_factor, x_grain,
-                     ldx_grain, n_grain, n_joint, centres_before);
-  return launch_status();
-}
-
-extern "C" int ggnn_grain_centres_bc(const int32_t* rowptr, const int32_t* col, const float* x_joint, int64_t n_joint,
-                                     int64_t ldx_joint, const float* domain_offset, float domain_factor, float* x_grain,
-                                     int64_t n_grain, int64_t ldx_grain, float* centres_before, int boundary,
-                                     ggnn_stream_t stream) {
-  using namespace ggnn;
-  if (boundary == GGNN_BC_PERIODIC)
-    return ggnn_grain_centres(rowptr, col, x_joint, n_joint, ldx_joint, domain_offset, domain_factor, x_grain, n_grain,
-                              ldx_grain, centres_before, stream);
-  if (boundary != GGNN_BC_NOFLUX) return GGNN_EINVAL;
-  if (!rowptr || !col || !x_joint || !x_grain) return GGNN_EINVAL;
-  if (n_joint <= 0 || n_grain <= 0 || ldx_joint < 2 || ldx_grain < 2) return GGNN_EINVAL;
-  if (!(domain_factor >= 1.0f)) return GGNN_EINVAL;
-  const int64_t nblk = (n_grain + 255) / 256;
-  if (nblk >= INT32_MAX) return GGNN_EINVAL;
-  hipLaunchKernelGGL(grain_centres_kernel<false>, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream,
-                     rowptr, col, x_joint, ldx_joint, domain_offset, domain_factor, x_grain,
-                     ldx_grain, n_grain, n_joint, centres_before);
+  const auto kernel = boundary == GGNN_BC_PERIODIC ? grain_centres_kernel<true> : grain_centres_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, rowptr, col, x_joint, ldx_joint,
+                     domain_offset, domain_factor, x_grain, ldx_grain, n_grain, n_joint, centres_before);
   return launch_status();
 }
 
@@ -308,25 +289,9 @@ extern "C" int ggnn_noflux_boundary(const int32_t* rowptr_jg, const int32_t* col
 }
 
 extern "C" int ggnn_detect_events(const float* grain_area, const int32_t* live_grain, int64_t n_grain,
-                                  float area_threshold, const float* edge_event,
-                                  const int64_t* edge_index_jj, int64_t E, float logit_threshold,
-                                  int32_t* flags, int32_t* range_word, ggnn_stream_t stream) {
-  return ggnn_detect_events_n(grain_area, live_grain, n_grain, area_threshold, edge_event, edge_index_jj, E, nullptr,
-                              logit_threshold, flags, range_word, stream);
-}
-
-extern "C" int ggnn_detect_events_n(const float* grain_area, const int32_t* live_grain, int64_t n_grain,
-                                    float area_threshold, const float* edge_event, const int64_t* edge_index_jj,
-                                    int64_t E, const int64_t* E_dev, float logit_threshold, int32_t* flags,
-                                    int32_t* range_word, ggnn_stream_t stream) {
-  return ggnn_detect_events_skip(grain_area, live_grain, n_grain, area_threshold, edge_event, edge_index_jj, E, E_dev,
-                                 logit_threshold, flags, range_word, -1, stream);
-}
-
-extern "C" int ggnn_detect_events_skip(const float* grain_area, const int32_t* live_grain, int64_t n_grain,
-                                       float area_threshold, const float* edge_event, const int64_t* edge_index_jj,
-                                       int64_t E, const int64_t* E_dev, float logit_threshold, int32_t* flags,
-                                       int32_t* range_word, int64_t skip_grain, ggnn_stream_t stream) {
+                                  float area_threshold, const float* edge_event, const int64_t* edge_index_jj,
+                                  int64_t E, const int64_t* E_dev, float logit_threshold, int32_t* flags,
+                                  int32_t* range_word, int64_t skip_grain, ggnn_stream_t stream) {
   using namespace ggnn;
   if (!grain_area || !live_grain || !flags || n_grain <= 0 || E < 0) return GGNN_EINVAL;
   if (E > 0 && (!edge_event || !edge_index_jj)) return GGNN_EINVAL;

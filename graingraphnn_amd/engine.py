@@ -19,7 +19,7 @@ ET = Tuple[str, str, str]
 
 JG = ("joint", "pull", "grain")
 # no-flux boundary (test.py:363-375): the forwards see the lists without grain 0's edges -- grain->joint without source 0,
-# joint->grain without destination 0 -- in the masked tables of ggnn_build_csr_masked_batch
+# joint->grain without destination 0 -- in the masked tables of ggnn_build_csr_batch
 NOFLUX_MASKS = {("grain", "push", "joint"): (0, -1), JG: (-1, 0), ("joint", "connect", "joint"): None}
 
 
@@ -267,7 +267,7 @@ def run_cell(backend, pc: PackedCell, graph: GraphCSR, x: Dict[str, torch.Tensor
 
 
 def gate_problems(pc: PackedCell, proj, agg, c_in, h_out, c_out):
-    """Argument tuples of ggnn_lstm_epilogue for the live node types of one cell."""
+    """Argument tuples of ggnn_lstm_epilogue_batch for the live node types of one cell."""
     mode = _lib.MODE_LSTM if pc.k2 else _lib.MODE_LSTM_H0
     lay = pc.layout
     return [(agg[nt], pc.w2[nt], proj[nt], lay[nt].s_off, c_in[nt] if pc.k2 else None, h_out[nt], c_out[nt],

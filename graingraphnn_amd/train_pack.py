@@ -126,7 +126,7 @@ def assemble(get, get_s, mr, zeros, sum_of, F, G, sees_h):
         n_rows = sum(b.size(0) for b in blocks)
         blocks.append(zeros(lay.ncols - n_rows, D + 1))
         rows = torch.cat(blocks)
-        wp[nt] = torch.cat([rows[:, :Fn], zeros(lay.ncols, Fp - Fn), rows[:, Fn:D]], 1)   # ggnn_project's input order
+        wp[nt] = torch.cat([rows[:, :Fn], zeros(lay.ncols, Fp - Fn), rows[:, Fn:D]], 1)   # ggnn_project_batch's input order
         bp[nt] = rows[:, D]
         layout[nt] = lay
         n_in = len(lay.dst_ets)

@@ -11,7 +11,7 @@ and the module is in training mode, i.e. inside the reference's loop (train.py:1
     projection `ggnn_project_batch`, the sweeps `ggnn_period_gat_aggregate_batch` (PeriodConv.message + propagate,
     periodGATconv.py:174-175, 204-236) with their hand-written backward `ggnn_period_gat_aggregate_backward`
     (segment-softmax backward, relu mask, atomics-free scatter to the source rows), the LSTM update
-    `ggnn_lstm_train_forward / _backward`, every weight gradient through the split-K `ggnn_wgrad`; the gate GEMM,
+    `ggnn_lstm_train_forward_batch / _backward_batch`, every weight gradient through the split-K `ggnn_wgrad`; the gate GEMM,
     its input gradient and the hidden-state gradient of the projection through `ggnn_rowgemm` (round 4: they were
     library GEMMs) -- no BLAS call is left inside a cell;
   * the regressor's heads are `_RegressorHeads` (the inference head kernel forward, `ggnn_heads_regressor_backward`
@@ -132,8 +132,8 @@ class _PackedCell(torch.autograd.Function):
       forward   P[nt] = [x | h] Wp^T + bp             ggnn_project_batch (the inference kernel; one launch)
                 agg   = sweeps(P, h)                   ggnn_period_gat_aggregate_batch (one launch)
                 z     = agg W2^T (per gate, batched)   ggnn_rowgemm
-                h', c' = LSTM(z + skip(P), c)          ggnn_lstm_train_forward
-      backward  g_z, gP[skip], g_c                     ggnn_lstm_train_backward
+                h', c' = LSTM(z + skip(P), c)          ggnn_lstm_train_forward_batch
+      backward  g_z, gP[skip], g_c                     ggnn_lstm_train_backward_batch
                 g_W2 = g_z^T agg                       ggnn_wgrad (reduction over the nodes, split over the chip)
                 g_agg = g_z W2                         ggnn_rowgemm
                 gP[u, u4, v], g_h (source side), g_ep  ggnn_period_gat_aggregate_backward per edge type

@@ -25,7 +25,7 @@
 extern "C" {
 #endif
 
-#define GGNN_ABI_VERSION 25
+#define GGNN_ABI_VERSION 26
 #define GGNN_C 96              /* hidden width (hyper.layer_size of every shipped model) */
 #define GGNN_MAX_GATES 4       /* i, f, c, o */
 #define GGNN_EDGE_PARAM_ROWS 3 /* per gate: W_value[:, 0:3] (the value side of the min-image correction) */
@@ -38,14 +38,14 @@ extern "C" {
 
 typedef void* ggnn_stream_t; /* hipStream_t */
 
-/* Gate-epilogue modes of ggnn_lstm_epilogue */
+/* Gate-epilogue modes of ggnn_lstm_epilogue_batch */
 #define GGNN_MODE_LSTM 0    /* 4 gates (i,f,c,o), c_in given: c' = f*c + i*tanh(.), h' = o*tanh(c') */
 #define GGNN_MODE_LSTM_H0 1 /* 3 gates (i,c,o), h = c = 0 (encoder): c' = i*tanh(.), h' = o*tanh(c') */
 #define GGNN_MODE_RAW 2     /* no LSTM: write the n_gates pre-activations (used for PeriodConv parity) */
 
 int ggnn_version(void);
 const char* ggnn_error_string(int code);
-/* Arithmetic of the K >= 100 GEMMs (decoder ggnn_project, ggnn_lstm_epilogue), fixed per process
+/* Arithmetic of the K >= 100 GEMMs (decoder ggnn_project_batch, ggnn_lstm_epilogue_batch), fixed per process
  * by the environment variable GGNN_GEMM: GGNN_GEMM_BF16X6 (default) = every fp32 operand split
  * exactly into three bf16 pieces, six bf16 MFMA products per k-step, fp32 accumulate (dropped
  * terms <= 2^-25 of a product: fp32-equivalent); GGNN_GEMM_FP32 ("fp32") = native fp32 MFMA. */
@@ -57,6 +57,8 @@ int ggnn_gemm_mode(void);
  * CSR build.  Replaces the COO bookkeeping inside PyG MessagePassing.propagate as used at
  * periodGATconv.py:174-175 (gather by edge_index[0]/[1], scatter-add by edge_index[1]):
  * edges are grouped by destination once per topology, so aggregation needs no atomics.
+ * One to four lists per call, in one sequence of seven launches (a topological event rebuilds
+ * the three edge types' tables).  Per list (ggnn_csr_args):
  *   edge_index : [2, E] int64, row 0 = source node, row 1 = destination node (device)
  *   rowptr     : [n_dst + 1] int32 out
  *   col        : [E] int32 out, source node of each CSR slot
@@ -74,12 +76,6 @@ int ggnn_gemm_mode(void);
  */
 size_t ggnn_csr_workspace_bytes(int64_t E, int64_t n_dst);
 int64_t ggnn_csr_max_units(int64_t E, int64_t n_dst); /* upper bound: n_dst + E / GGNN_UNIT_EDGES */
-int ggnn_build_csr(const int64_t* edge_index, int64_t E, int64_t n_src, int64_t n_dst,
-                   int32_t* rowptr, int32_t* col, int32_t* perm, int32_t* row, int32_t* unit_ptr,
-                   int32_t* units, int32_t* flags, void* workspace, size_t workspace_bytes,
-                   ggnn_stream_t stream);
-/* The same build for up to four lists in one sequence of launches (a topological event rebuilds the three edge types'
- * tables: seven launches instead of twenty-four).  Fields as the arguments of ggnn_build_csr. */
 typedef struct ggnn_csr_args {
   const int64_t* edge_index;
   int64_t E, n_src, n_dst;
@@ -93,22 +89,19 @@ typedef struct ggnn_csr_args {
   void* workspace;
   size_t workspace_bytes;
 } ggnn_csr_args;
-int ggnn_build_csr_batch(const ggnn_csr_args* problems, int n_problems, ggnn_stream_t stream);
-/* Masked build (no-flux boundary, additive to ABI 25): the tables of the list WITHOUT every edge whose source equals
- * skip_src or whose destination equals skip_dst (-1 = none) -- the copies of test.py:363-375 that both forwards see when
- * grain 0 is the boundary grain (skip_src = 0 for grain->joint, skip_dst = 0 for joint->grain).  Inside a row the slots
- * stay in original-edge order (the order `index[:, mask]` produces); perm maps every slot to its edge id in the FULL
- * list, so ggnn_edge_prepare reads the full list's edge_attr and writes the filtered records.  The kept slots are
- * [0, rowptr[n_dst]); the rest of col / perm / row up to E is written with zeros.  E_kept (NULL = none, 8-byte aligned):
- * receives rowptr[n_dst] as an int64 device word -- the E_dev of the per-edge kernels (ggnn_prepare_edge.E_dev) that
- * read this table, whose launches are sized for E.  masks == NULL: ggnn_build_csr_batch.  An in-place refill of the
- * same tables (the event loop) passes the same mask again. */
+/* A mask (no-flux boundary): the tables of the list WITHOUT every edge whose source equals skip_src or whose destination
+ * equals skip_dst (-1 = none) -- the copies of test.py:363-375 that both forwards see when grain 0 is the boundary grain
+ * (skip_src = 0 for grain->joint, skip_dst = 0 for joint->grain).  Inside a row the slots stay in original-edge order (the
+ * order `index[:, mask]` produces); perm maps every slot to its edge id in the FULL list, so ggnn_edge_prepare reads the
+ * full list's edge_attr and writes the filtered records.  The kept slots are [0, rowptr[n_dst]); the rest of col / perm /
+ * row up to E is written with zeros.  An in-place refill of the same tables (the event loop) passes the same mask again. */
 typedef struct ggnn_csr_mask {
   int64_t skip_src, skip_dst;
-  int64_t* E_kept;
+  int64_t* E_kept; /* NULL, or an 8-byte aligned int64 device word that receives rowptr[n_dst]: the E_dev of the per-edge
+                      kernels (ggnn_prepare_edge.E_dev) that read this table, whose launches are sized for E */
 } ggnn_csr_mask;
-int ggnn_build_csr_masked_batch(const ggnn_csr_args* problems, const ggnn_csr_mask* masks, int n_problems,
-                                ggnn_stream_t stream);
+int ggnn_build_csr_batch(const ggnn_csr_args* problems, const ggnn_csr_mask* masks /* [n_problems], or NULL: no list masked */,
+                         int n_problems, ggnn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Per-edge record in CSR order, computed once per forward and shared by every gate of the
@@ -132,7 +125,7 @@ typedef struct ggnn_prepare_edge {
   const float* x_dst;     /* [n_dst, ldx_dst] */
   float* einfo;           /* [E + GGNN_UNIT_EDGES, GGNN_EINFO_ROW] out, 16-byte aligned (tail rows are padding) */
   int64_t ldx_src, ldx_dst, E, f_src; /* 3 <= f_src <= 12 source features */
-  const int64_t* E_dev;   /* ABI 25, or NULL: the number of edges read from DEVICE memory when the kernel runs (E is then the
+  const int64_t* E_dev;   /* NULL, or the number of edges read from DEVICE memory when the kernel runs (E is then the
                              capacity the launch is sized for, *E_dev <= E) -- a launch captured in a hipGraph follows an
                              edge list that SHRINKS in place (GrainRollout's event loop: grain eliminations remove edges;
                              the lists, CSR tables and per-edge buffers keep their addresses and capacity) */
@@ -146,20 +139,16 @@ int ggnn_edge_prepare(const ggnn_prepare_edge* edges, int n_edge_types, ggnn_str
  * (heteropgclstm.py:112,120,128,137), using linearity to hoist them from edges to nodes.  What
  * the rows of Wp hold is the caller's business (graingraphnn_amd/packing.py: value rows for the
  * node as a source; W_k^T W_q / sqrt(96) rows for it as a destination, see
- * ggnn_period_gat_aggregate; summed skip rows).
+ * ggnn_period_gat_aggregate_batch; summed skip rows).
  *   X  : [M, ldx] node features, first F columns used (F <= 12)
  *   H  : [M, ldh] hidden state (k2 = 96) or NULL (k2 = 0, encoder: h = 0)
  *   Wp : [ncols, Kp] packed weight rows, Kp = roundup4(F) + k2; columns [F, roundup4(F)) zero
  *   ncols % 96 == 0; ldo % 4 == 0; H, Wp, bias, out 16-byte aligned.
+ * One to four projections per launch: the node types of one cell and / or the same cell of the
+ * regressor and the classifier (both see the same x_dict, test.py:382-383).  All problems must share
+ * k2.  Rows are addressed with a 64-bit tile base and 32-bit offsets inside a 16-row tile:
+ * 16 * max(ldx, ldh, ldo) < 2^31 is the only size limit.
  */
-int ggnn_project(const float* X, int64_t ldx, int F, const float* H, int64_t ldh, int k2,
-                 const float* Wp, const float* bias, int64_t M, int ncols, float* out,
-                 int64_t ldo, ggnn_stream_t stream);
-/* Up to four projections in ONE launch: the node types of one cell and / or the same cell of the
- * regressor and the classifier (both see the same x_dict, test.py:382-383).  Fields as the
- * arguments of ggnn_project; all problems must share k2.  Rows are addressed with a 64-bit tile base
- * and 32-bit offsets inside a 16-row tile: 16 * max(ldx, ldh, ldo) < 2^31 is the only size limit.
- * Same result as n single calls. */
 typedef struct ggnn_project_args {
   const float* X;
   const float* H; /* NULL when k2 == 0 */
@@ -175,7 +164,7 @@ typedef struct ggnn_project_args {
                         ones ggnn_decoder_cell_batch checks and reports) -- the value rows of the fused decoder plan;
                         GGNN_PRECISION_BF16 (k2 == 96 only): operands rounded to bf16, ONE bf16 MFMA product per
                         k-step, fp32 accumulate -- what torch.autocast(bfloat16) asks of a linear (training path).
-                        | GGNN_OUT_BLOCK_MAJOR (k2 == 96 only, ABI 24): `out` is [ncols / 96][M][96] -- every block of 96
+                        | GGNN_OUT_BLOCK_MAJOR (k2 == 96 only): `out` is [ncols / 96][M][96] -- every block of 96
                         columns a contiguous [M, 96] matrix of its own (ldo is ignored) -- instead of [M, ldo]: the layout
                         of the fused decoder plan's value rows, which are written once here and gathered 96 columns
                         (one edge type and gate) at a time by ggnn_decoder_cell_batch (v_block_major) */
@@ -190,7 +179,7 @@ int ggnn_project_batch(const ggnn_project_args* args, int n_problems, ggnn_strea
  * x~_j = [reloc_e, x_j[3:F], h_j] the score q_i.(W_k x~_j + b_k + w_edge a_e)/sqrt(96) equals
  * u_i . x~_j + s1_i + a_e s2_i, where u_i = W_k^T q_i/sqrt(96), s1_i = b_k.q_i/sqrt(96) and
  * s2_i = w_edge.q_i/sqrt(96) are affine in the destination's [x_i | h_i] and come from
- * ggnn_project.  Per destination i and gate g the projections hold
+ * ggnn_project_batch.  Per destination i and gate g the projections hold
  *   p_dst[i, u_off  + g*96 + 0..95] = u_i[F ..]   (hidden-state part; absent when h_src == NULL)
  *   p_dst[i, u4_off + g*16 + 0..15] = (u_i[0..F-1], 0.., s1_i at 12, s2_i at 13, 0, 0), dotted
  *                                     with einfo[e, 0..15]
@@ -200,11 +189,11 @@ int ggnn_project_batch(const ggnn_project_args* args, int n_problems, ggnn_strea
  *   agg[i, g*a_gstride + sc_off + 0]    = sum_e alpha_e            (1, or 0 if no in-edge)
  *   agg[i, g*a_gstride + sc_off + 1]    = sum_e alpha_e * edge_attr_e
  * (lin_l2, its bias, the value-side lin_edge term and lin_skip are applied afterwards by
- * ggnn_lstm_epilogue, which is exact because they are linear in these sums.)
+ * ggnn_lstm_epilogue_batch, which is exact because they are linear in these sums.)
  */
 typedef struct ggnn_aggregate_args {
-  const int32_t* unit_ptr;  /* [n_dst + 1] from ggnn_build_csr */
-  const int32_t* units;     /* [n_units, 8] from ggnn_build_csr */
+  const int32_t* unit_ptr;  /* [n_dst + 1] from ggnn_build_csr_batch */
+  const int32_t* units;     /* [n_units, 8] from ggnn_build_csr_batch */
   const float* einfo;       /* [E + GGNN_UNIT_EDGES, GGNN_EINFO_ROW] from ggnn_edge_prepare */
   const float* p_src;       /* [n_src, ldp_src] projections of the source node type */
   const float* p_dst;       /* [n_dst, ldp_dst] projections of the destination node type */
@@ -213,15 +202,14 @@ typedef struct ggnn_aggregate_args {
   float* agg;               /* [n_dst, ld_agg] */
   int64_t ldp_src, ldp_dst, ld_agg, ldh_src, n_src, n_dst, E;
   int32_t v_off, u_off, u4_off, a_off, a_gstride, sc_off, n_gates;
-  int32_t pad_n;            /* ABI 25: the sweep also writes zeros into agg[i, g a_gstride + sc_off + 2 .. + pad_n) of every gate
+  int32_t pad_n;            /* the sweep also writes zeros into agg[i, g a_gstride + sc_off + 2 .. + pad_n) of every gate
                                row (the padding between the last edge type's scalars and the next gate row, which the training
                                path's gate GEMM multiplies with zero weight columns: it has to be finite); 0 = nothing */
 } ggnn_aggregate_args;
-int ggnn_period_gat_aggregate(const ggnn_aggregate_args* args, ggnn_stream_t stream);
 /* The 1..6 sweeps of one cell (HeteroConv over the edge types, heteropgclstm.py:148-183; of one
  * model, or of the regressor and the classifier, which see the same graph: test.py:382-383) in ONE
  * launch: args[0..n_sweeps).  All must have the same n_gates and agree on h_src == NULL; they may
- * write disjoint columns of the same agg rows.  Same result as n_sweeps single calls. */
+ * write disjoint columns of the same agg rows. */
 int ggnn_period_gat_aggregate_batch(const ggnn_aggregate_args* args, int n_sweeps,
                                     ggnn_stream_t stream);
 
@@ -235,11 +223,11 @@ int ggnn_period_gat_aggregate_batch(const ggnn_aggregate_args* args, int n_sweep
  *            Bp[11][.] = b_value_g, 0 elsewhere (F_src <= 11; einfo[:, 11] = 1):
  *            element [t][s][l] = Bp[4 s + (l >> 4)][(t / 6) * 96 + 32 ((t % 6) / 2) + 2 (l & 15) + t % 2].
  * p_dst, u4_off, agg, a_off, a_gstride, sc_off and the result are those of the h_src == NULL form
- * of ggnn_period_gat_aggregate (same sums up to fp32 re-association).  n_gates = 3; a_off, a_gstride,
+ * of ggnn_period_gat_aggregate_batch (same sums up to fp32 re-association).  n_gates = 3; a_off, a_gstride,
  * ld_agg even.  Up to six sweeps per launch (three edge types x two models). */
 typedef struct ggnn_aggregate_enc_args {
-  const int32_t* unit_ptr; /* [n_dst + 1] from ggnn_build_csr */
-  const int32_t* units;    /* [n_units, 8] from ggnn_build_csr */
+  const int32_t* unit_ptr; /* [n_dst + 1] from ggnn_build_csr_batch */
+  const int32_t* units;    /* [n_units, 8] from ggnn_build_csr_batch */
   const float* einfo;      /* [E + GGNN_UNIT_EDGES, GGNN_EINFO_ROW] from ggnn_edge_prepare */
   const float* p_dst;      /* [n_dst, ldp_dst] destination projections (the u4 tails) */
   const float* wv_frag;    /* [6 * n_gates][3][64] */
@@ -266,7 +254,7 @@ int ggnn_period_gat_aggregate_enc_batch(const ggnn_aggregate_enc_args* args, int
  * The geometry (einfo) is data, not a parameter: no gradient.
  */
 typedef struct ggnn_aggregate_bwd_args {
-  const int32_t* rowptr;   /* [n_dst + 1] destination-grouped CSR (ggnn_build_csr) */
+  const int32_t* rowptr;   /* [n_dst + 1] destination-grouped CSR (ggnn_build_csr_batch) */
   const int32_t* col;      /* [E] source node of every CSR slot */
   const float* einfo;      /* [E + GGNN_UNIT_EDGES, GGNN_EINFO_ROW] */
   const float* p_src;      /* forward operands, as ggnn_aggregate_args */
@@ -286,7 +274,7 @@ typedef struct ggnn_aggregate_bwd_args {
   float* g_h_src;          /* [n_src, ldh_src] out, or NULL */
   int64_t ldp_src, ldp_dst, ld_agg, ldh_src, n_src, n_dst, E, n_partials;
   int32_t v_off, u_off, u4_off, a_off, a_gstride, sc_off, n_gates;
-  int32_t g_h_accumulate;  /* ABI 25: 1 = g_h_src += (the sweeps of a cell that share a source node type add into one buffer
+  int32_t g_h_accumulate;  /* 1 = g_h_src += (the sweeps of a cell that share a source node type add into one buffer
                               the first of them wrote), 0 = g_h_src is written */
 } ggnn_aggregate_bwd_args;
 int64_t ggnn_aggregate_bwd_partials(int64_t n_dst); /* rows of ep_partial the call writes (one per workgroup of its destination pass) */
@@ -296,13 +284,16 @@ int ggnn_period_gat_aggregate_backward(const ggnn_aggregate_bwd_args* args, ggnn
  * Gate GEMM + LSTM epilogue (arithmetic per ggnn_gemm_mode).  For every node and gate:
  *   pre[g] = agg[:, g, 0:Ka] . W2[g]^T + p_dst[:, s_off + g*96 ...]
  * where W2[g] = [lin_l2.weight of each incoming edge type | b_l2, w_edge per edge type]
- * (periodGATconv.py:218, 231-235), the skip/bias term was produced by ggnn_project
+ * (periodGATconv.py:218, 231-235), the skip/bias term was produced by ggnn_project_batch
  * (lin_skip summed over incoming edge types = HeteroConv aggr 'sum', plus b_{i,f,c,o}),
  * followed by the cell update of heteropgclstm.py:111-146.
  *   mode GGNN_MODE_LSTM    : n_gates = 4, needs c_in, writes h_out, c_out   [N, 96]
  *   mode GGNN_MODE_LSTM_H0 : n_gates = 3 (i, c, o), writes h_out, c_out
  *   mode GGNN_MODE_RAW     : writes raw_out [N, n_gates*96] = pre
  * Ka % 4 == 0, Ka <= 200.
+ * One to four problems per launch: the node types of one cell (heteropgclstm.py:111-146 runs the
+ * update per node type) and / or the same cell of the regressor and the classifier (test.py:382-383
+ * calls both models on the same x_dict).  All problems must share `mode` and `n_gates`; Ka may differ.
  */
 typedef struct ggnn_epilogue_args {
   const float* agg;   /* [N, n_gates*Ka] */
@@ -329,11 +320,6 @@ typedef struct ggnn_epilogue_args {
   int64_t ld_agg;
   int32_t g_stride, reserved;
 } ggnn_epilogue_args;
-int ggnn_lstm_epilogue(const ggnn_epilogue_args* args, ggnn_stream_t stream);
-/* Up to four gate GEMM + LSTM problems in ONE launch: the node types of one cell
- * (heteropgclstm.py:111-146 runs the update per node type) and / or the same cell of the
- * regressor and the classifier (test.py:382-383 calls both models on the same x_dict).  All
- * problems must share `mode` and `n_gates`; Ka may differ.  Same result as n single calls. */
 int ggnn_lstm_epilogue_batch(const ggnn_epilogue_args* args, int n_problems, ggnn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
@@ -357,7 +343,7 @@ int ggnn_lstm_epilogue_batch(const ggnn_epilogue_args* args, int n_problems, ggn
  * gate bias); i = sig, c' = i tanh(c~), h' = sig(o) tanh(c').  Arithmetic and OPERAND RANGE as for
  * ggnn_decoder_cell_batch (two fp16 pieces, three products; |x| < 65504, reported through *flags).
  *
- * Per incoming edge type: rowptr [n_dst + 1] (ggnn_build_csr), einfo (ggnn_edge_prepare), E.
+ * Per incoming edge type: rowptr [n_dst + 1] (ggnn_build_csr_batch), einfo (ggnn_edge_prepare), E.
  * Per problem:
  *   x_dst   : [n_dst, ldx] features of the destination nodes (first f_dst <= 12 columns)
  *   wstream : the weight slices in the order the kernel consumes them (packing.encoder_cell_stream):
@@ -423,7 +409,7 @@ int ggnn_encoder_cell_values_batch(const ggnn_enc_values_args* args, int n_probl
  * gates in the order i, c~, f, o (the LSTM update is folded in as the gates arrive).  Per gate g and incoming
  * edge type e a wave (P1) multiplies its tile's [h | x | 1] rows with the (e, g) score weights -> u_h | u4 of its
  * 16 nodes, (P2) sweeps the tile's in-edges of that edge type (gathers of h_src and V rows, periodic min-image
- * correction, online-max softmax, relu, alpha-weighted sum: exactly ggnn_period_gat_aggregate's arithmetic),
+ * correction, online-max softmax, relu, alpha-weighted sum: exactly ggnn_period_gat_aggregate_batch's arithmetic),
  * (P3) multiplies the 16 x 98 aggregate block with lin_l2 | (b_l2, w_edge) of (e, g) into the gate's
  * pre-activation, then (P4) adds the summed skip term of the gate.  Arithmetic of the three GEMMs: every fp32
  * operand as TWO fp16 pieces, hi = rne16(x) and lo' = rne16((x - hi) * 2048), and three of the four products
@@ -444,7 +430,7 @@ int ggnn_encoder_cell_values_batch(const ggnn_enc_values_args* args, int n_probl
  * flag word reports non-finite operands either way.
  *
  * Per incoming edge type:
- *   rowptr, col : destination-grouped CSR of the edge type (ggnn_build_csr)
+ *   rowptr, col : destination-grouped CSR of the edge type (ggnn_build_csr_batch)
  *   einfo       : edge records in CSR order (ggnn_edge_prepare)
  *   h_src       : [n_src, ldh_src] hidden state of the source node type
  *   v_src       : [n_src, ldv] projection of the source node type; columns v_off + g * 96 .. + 95 = the value
@@ -481,7 +467,7 @@ typedef struct ggnn_dec_cell_sweep {
   const float* edge_params;  /* [4][GGNN_EDGE_PARAM_ROWS][96] */
   int64_t E, n_src, ldh_src, ldv;
   int32_t v_off;         /* first of the four gates' 96 value columns inside a v_src row (a multiple of 96 when block-major) */
-  int32_t v_block_major; /* ABI 24: 0 = v_src is [n_src, ldv]; 1 = v_src is GGNN_OUT_BLOCK_MAJOR: [blocks][n_src][96], the
+  int32_t v_block_major; /* 0 = v_src is [n_src, ldv]; 1 = v_src is GGNN_OUT_BLOCK_MAJOR: [blocks][n_src][96], the
                             four gates' blocks v_off / 96 .. + 3 (ldv is ignored) */
 } ggnn_dec_cell_sweep;
 typedef struct ggnn_dec_cell_args {
@@ -535,7 +521,7 @@ typedef struct ggnn_rowgemm_args {
 size_t ggnn_rowgemm_workspace_bytes(int32_t K, int32_t n_out, int32_t batch);
 int ggnn_rowgemm_pack(const ggnn_rowgemm_args* args, int n_products, ggnn_stream_t stream); /* reads w, K, n_out, batch, precision, workspace */
 int ggnn_rowgemm(const ggnn_rowgemm_args* args, ggnn_stream_t stream);
-/* ABI 25: TWO long products (args[0], args[1]: the streamed form -- K / 32 beyond what stays in LDS --, batch == 1, prepacked
+/* TWO long products (args[0], args[1]: the streamed form -- K / 32 beyond what stays in LDS --, batch == 1, prepacked
  * planes, the same precision and n_out rounded to the same instantiated width) side by side in one grid: a wave walks the whole
  * reduction of its 16 rows, so such a product is M / 128 workgroups -- the hidden-state gradients of a training cell's two node
  * types (79 and 157 workgroups at the 10k-grain graph) then take the time of the longer one.  Same results as two calls;
@@ -567,16 +553,12 @@ int ggnn_heads_regressor_update(const float* h_joint, int64_t n_joint, const flo
  *   w_node : [6][96] = lin1.w[0,0:96], lin1.w[1,0:96], lin2.w[0,0:96], lin1.w[0,96:192], lin1.w[1,96:192], lin2.w[0,96:192]
  *   w_edge : [6]     = lin1.w[0,192], lin1.w[1,192], lin2.w[0,192], lin1.b[0], lin1.b[1], lin2.b[0]
  */
-int ggnn_heads_classifier(const float* h_joint, int64_t n_joint, const int64_t* edge_index_jj,
-                          int64_t E, const float* edge_attr_jj, const float* w_node,
-                          const float* w_edge, float* node_tmp, float* edge_event, float* edge,
-                          ggnn_stream_t stream);
-/* ABI 25: the same with the number of edges read from device memory when the kernels run (E_dev != NULL: edge_index_jj is
- * [2, *E_dev], E the capacity the launch is sized for; see ggnn_prepare_edge.E_dev). */
-int ggnn_heads_classifier_n(const float* h_joint, int64_t n_joint, const int64_t* edge_index_jj,
-                            int64_t E, const int64_t* E_dev, const float* edge_attr_jj, const float* w_node,
-                            const float* w_edge, float* node_tmp, float* edge_event, float* edge,
-                            ggnn_stream_t stream);
+int ggnn_heads_classifier(const float* h_joint, int64_t n_joint, const int64_t* edge_index_jj, int64_t E,
+                          const int64_t* E_dev /* NULL, or the number of edges read from device memory when the kernels run:
+                                                  edge_index_jj is [2, *E_dev] then, E the capacity the launch is sized for
+                                                  (see ggnn_prepare_edge.E_dev) */,
+                          const float* edge_attr_jj, const float* w_node, const float* w_edge, float* node_tmp,
+                          float* edge_event, float* edge, ggnn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Rollout-step glue on device.
@@ -593,43 +575,52 @@ int ggnn_step_update(float* x_joint, int64_t n_joint, int64_t ldx_joint, float* 
                      const float* y_grain, float dz, float zmax, int32_t* flags,
                      ggnn_stream_t stream);
 /* Grain-centre refresh: replaces traj.GNN_update -> graph.update()
- * (graph_trajectory.py:1010-1085, graph_datastruct.py:681-708; periodic BC) + the write-back of
+ * (graph_trajectory.py:1010-1085, graph_datastruct.py:681-708) + the write-back of
  * test.py:556-559.  For every grain with >= 2 junctions (CSR row of the joint->grain edge type
- * from ggnn_build_csr): junction xy, brought to the global frame ((x + domain_offset[j]) /
+ * from ggnn_build_csr_batch): junction xy, brought to the global frame ((x + domain_offset[j]) /
  * domain_factor when domain_factor > 1, test.py:474), are chained by min-image to the previous
  * junction, shifted by +1 in a coordinate where any of them is below -1e-12, and averaged;
  * x_grain[g, 0:2] = centre, or frac(centre * domain_factor) when domain_factor > 1.
  * fp32 (the reference's numpy scalars promote to fp64: differences are <= 1 ulp of fp32).
- * domain_offset: [n_joint, 2] or NULL (= 0).  Runs between ggnn_step_update and
- * ggnn_step_refresh so that the refreshed edge lengths see the new centres.
- * centres_before (ABI 24): NULL, or [n_grain, 2] that receives x_grain[:, 0:2] as the call found them (what a topological
- * event of this step must see: the speculative event loop keeps it per step instead of copying the columns out). */
-int ggnn_grain_centres(const int32_t* rowptr, const int32_t* col, const float* x_joint,
-                       int64_t n_joint, int64_t ldx_joint, const float* domain_offset,
-                       float domain_factor, float* x_grain, int64_t n_grain, int64_t ldx_grain,
-                       float* centres_before, ggnn_stream_t stream);
+ * Runs between ggnn_step_update and ggnn_step_refresh so that the refreshed edge lengths see the
+ * new centres. */
+#define GGNN_BC_PERIODIC 0
+#define GGNN_BC_NOFLUX 1
+int ggnn_grain_centres(const int32_t* rowptr, const int32_t* col, const float* x_joint, int64_t n_joint, int64_t ldx_joint,
+                       const float* domain_offset /* [n_joint, 2], or NULL (= 0) */, float domain_factor, float* x_grain,
+                       int64_t n_grain, int64_t ldx_grain,
+                       float* centres_before /* NULL, or [n_grain, 2] that receives x_grain[:, 0:2] as the call found them (what
+                                                a topological event of this step must see: the speculative event loop keeps it
+                                                per step instead of copying the columns out) */,
+                       int boundary /* GGNN_BC_PERIODIC: as above.  GGNN_BC_NOFLUX: no min-image chaining of the junctions
+                                       (graph_datastruct.py:689-692 runs periodic_move for the periodic BC only), and
+                                       rowptr / col are the FULL joint->grain CSR, so that grain 0 gets its centre too */,
+                       ggnn_stream_t stream);
 /* Event detection for the host-side topology update (test.py:418, models.py:624-626):
  * flags[0] = number of grains with live_grain > 0 and grain_area < area_threshold,
  * flags[1] = number of junction-junction edges with src < dst and edge_event (a logit) >
- * logit_threshold.  flags: [2] int32 device words (zeroed by the call).
- * range_word (ABI 24; NULL = none): an OPERAND RANGE word (below) of the step whose predictions these are -- flags must
- * then hold THREE words: flags[2] = the word's value, and the word is cleared for its next use (the speculative event loop
- * reads a step's counts and its range report in one copy and drops the report of a step it voids: rollout.py). */
-int ggnn_detect_events(const float* grain_area, const int32_t* live_grain, int64_t n_grain,
-                       float area_threshold, const float* edge_event, const int64_t* edge_index_jj,
-                       int64_t E, float logit_threshold, int32_t* flags, int32_t* range_word, ggnn_stream_t stream);
-/* ABI 25: the same with the number of junction edges read from device memory when the kernel runs (E_dev != NULL:
- * edge_index_jj is [2, *E_dev], E the capacity the launch is sized for; see ggnn_prepare_edge.E_dev). */
-int ggnn_detect_events_n(const float* grain_area, const int32_t* live_grain, int64_t n_grain,
-                         float area_threshold, const float* edge_event, const int64_t* edge_index_jj,
-                         int64_t E, const int64_t* E_dev, float logit_threshold, int32_t* flags,
-                         int32_t* range_word, ggnn_stream_t stream);
-/* --- No-flux boundary (test.py:446-466, graph_datastruct.py:689-708 with traj.BC == 'noflux'; additive to ABI 25) ---
+ * logit_threshold.  flags: [2] int32 device words, [3] with a range_word (zeroed by the call). */
+int ggnn_detect_events(const float* grain_area, const int32_t* live_grain, int64_t n_grain, float area_threshold,
+                       const float* edge_event, const int64_t* edge_index_jj, int64_t E,
+                       const int64_t* E_dev /* NULL, or the number of junction edges read from device memory when the kernel
+                                               runs: edge_index_jj is [2, *E_dev] then, E the capacity the launch is sized for
+                                               (see ggnn_prepare_edge.E_dev) */,
+                       float logit_threshold, int32_t* flags,
+                       int32_t* range_word /* NULL, or an OPERAND RANGE word (ggnn_decoder_cell_batch) of the step whose
+                                              predictions these are: flags[2] = the word's value, and the word is cleared for
+                                              its next use (the speculative event loop reads a step's counts and its range
+                                              report in one copy and drops the report of a step it voids: rollout.py) */,
+                       int64_t skip_grain /* -1, or a grain that is never counted: the no-flux boundary grain, which
+                                             test.py:421-422 drops from the candidates (its area feature is reset to 0 every
+                                             step, so it is always below the threshold).  live_grain is not touched: the
+                                             topology session reads the same mask */,
+                       ggnn_stream_t stream);
+/* --- No-flux boundary (test.py:446-466, graph_datastruct.py:689-708 with traj.BC == 'noflux') ---
  * Grain 0 is the boundary grain that wraps the domain.
  * ggnn_noflux_boundary = the boundary step of test.py:446-463, one launch, after the topology update and before the
  * grain centres:  x_grain[0, 0:2] = 0.5, x_grain[0, 3:5] = 0, x_grain[0, f_grain-1] = 0; every junction to the global
  * frame, xy = (xy + domain_offset[j]) / domain_factor; every junction of grain 0's row of the FULL joint->grain CSR
- * (rowptr_jg / col_jg from ggnn_build_csr) snapped to the nearest wall, argmin(x, 1-x, y, max_y-y), first minimum
+ * (rowptr_jg / col_jg from ggnn_build_csr_batch) snapped to the nearest wall, argmin(x, 1-x, y, max_y-y), first minimum
  * wins (move_to_boundary, test.py:58-71); every junction clamped to [0,1] x [0,max_y]; back, xy = xy * domain_factor -
  * domain_offset[j].  fp32, each operation rounded on its own in the reference's order (no contraction).  domain_offset:
  * [n_joint, 2] or NULL (= 0).  joints_before: NULL, or [n_joint, 2] that receives x_joint[:, 0:2] as the call found
@@ -637,21 +628,6 @@ int ggnn_detect_events_n(const float* grain_area, const int32_t* live_grain, int
 int ggnn_noflux_boundary(const int32_t* rowptr_jg, const int32_t* col_jg, float* x_joint, int64_t n_joint,
                          int64_t ldx_joint, const float* domain_offset, float domain_factor, float max_y,
                          float* x_grain, int64_t ldx_grain, int f_grain, float* joints_before, ggnn_stream_t stream);
-/* ggnn_grain_centres with the boundary of the structure: boundary = GGNN_BC_PERIODIC is ggnn_grain_centres;
- * GGNN_BC_NOFLUX skips the min-image chaining of the junctions (graph_datastruct.py:689-692 runs periodic_move for the
- * periodic BC only) and reads the FULL joint->grain CSR, so that grain 0 gets its centre too. */
-#define GGNN_BC_PERIODIC 0
-#define GGNN_BC_NOFLUX 1
-int ggnn_grain_centres_bc(const int32_t* rowptr, const int32_t* col, const float* x_joint, int64_t n_joint,
-                          int64_t ldx_joint, const float* domain_offset, float domain_factor, float* x_grain,
-                          int64_t n_grain, int64_t ldx_grain, float* centres_before, int boundary, ggnn_stream_t stream);
-/* ggnn_detect_events_n that never counts grain skip_grain (-1 = none): the boundary grain, which test.py:421-422 drops
- * from the candidates (its area feature is reset to 0 every step, so it is always below the threshold).  live_grain is
- * not touched: the topology session reads the same mask. */
-int ggnn_detect_events_skip(const float* grain_area, const int32_t* live_grain, int64_t n_grain, float area_threshold,
-                            const float* edge_event, const int64_t* edge_index_jj, int64_t E, const int64_t* E_dev,
-                            float logit_threshold, int32_t* flags, int32_t* range_word, int64_t skip_grain,
-                            ggnn_stream_t stream);
 /* The host-side topology update those counts trigger: one call of the reference's `Cmodel.update`
  * (models.py:612-842 with delete_grain_index :861-893, switching_edge_index :896-1051, point_in_triangle :1055-1070,
  * periodic_move :1103-1106), nucleation off.  HOST memory throughout, no stream: grains of `grain_event` (those below the
@@ -696,7 +672,7 @@ typedef struct ggnn_topology_args {
   char error[192];
 } ggnn_topology_args;
 int ggnn_topology_update(ggnn_topology_args* args);
-/* The same update on lists that live in the library between calls (ABI 24; graingraphnn_amd/rollout.py keeps one session per
+/* The same update on lists that live in the library between calls (graingraphnn_amd/rollout.py keeps one session per
  * trajectory): the reference's loop calls Cmodel.update at EVERY step (test.py:418-426), and a stateless call rebuilds its
  * lookup tables from the whole lists each time (four O(E) sorts for a handful of events).  A session keeps the lists, the
  * tables and the per-grain counts and patches them as the events rewrite columns; a call costs what its events touch plus
@@ -724,7 +700,7 @@ typedef struct ggnn_refresh_edge {
   const float* x_dst;
   float* edge_attr; /* [E] out */
   int64_t ldx_src, ldx_dst, n_src, n_dst, E;
-  const int64_t* E_dev;      /* ABI 25, or NULL: as in ggnn_prepare_edge (edge_index is [2, *E_dev] then) */
+  const int64_t* E_dev;      /* NULL, or as in ggnn_prepare_edge (edge_index is [2, *E_dev] then) */
 } ggnn_refresh_edge;
 int ggnn_step_refresh(float* x_joint, int64_t n_joint, int64_t ldx_joint, float* x_grain,
                       int64_t n_grain, int64_t ldx_grain, float zmax, const int32_t* flags,
@@ -734,7 +710,7 @@ int ggnn_step_refresh(float* x_joint, int64_t n_joint, int64_t ldx_joint, float*
  * flags[1] is set, then per CSR slot the edge length from the min-image xy offsets (written to
  * edge_attr[perm[p]], the COO order: edges[k].edge_attr is an OUTPUT here) and the einfo record with that
  * length.  Same values as the two calls in sequence (the length is the same expression on the same operands).
- * x_joint_mirror / x_grain_mirror (ABI 24; both or neither, NULL = none; same shape and leading dimension as x_joint /
+ * x_joint_mirror / x_grain_mirror (both or neither, NULL = none; same shape and leading dimension as x_joint /
  * x_grain, not x itself): every row of x as it stands behind this call (the clamped z included) is also written there --
  * the copy of the node features that the classifier's forward of the NEXT step reads (test.py:382-383 hands both models
  * the same x_dict) while Rmodel.update of that step already rewrites x in place (graingraphnn_amd/rollout.py). */
@@ -749,21 +725,16 @@ int ggnn_step_refresh_prepare(float* x_joint, int64_t n_joint, int64_t ldx_joint
  * multiply / add chain of `i, f, c, o` (one launch each way instead of ~40).  n_gates = 4: (i, f, c, o) with
  * c_in; n_gates = 3: (i, c, o), zero state (encoder), c_in = NULL.
  *   forward : z [n_gates, N, 96] holds the gate GEMM's output (lin_l2 part) on entry; on exit the
- *             pre-activations z_g = gemm_g + p_dst[n, s_off + g*96 ..] (skip rows of ggnn_project); writes
+ *             pre-activations z_g = gemm_g + p_dst[n, s_off + g*96 ..] (skip rows of ggnn_project_batch); writes
  *             h_out, c_out [N, 96].
  *   backward: g_h / g_c (gradients of h_out / c_out; NULL = zero) -> g_z [n_gates, N, 96], the same values
  *             into g_p_dst[n, s_off + g*96 ..] (gradient of the skip rows; NULL = skip), g_c_in (NULL = skip).
- * ldp % 4 == 0, s_off % 4 == 0, every pointer 16-byte aligned. */
-int ggnn_lstm_train_forward(float* z, const float* p_dst, int64_t ldp, int s_off, const float* c_in,
-                            float* h_out, float* c_out, int64_t N, int n_gates, ggnn_stream_t stream);
-int ggnn_lstm_train_backward(const float* z, const float* c_in, const float* c_out, const float* g_h,
-                             const float* g_c, float* g_z, float* g_p_dst, int64_t ldp, int s_off,
-                             float* g_c_in, int64_t N, int n_gates, ggnn_stream_t stream);
-/* ABI 25: the same two updates for the node types of a cell (1..GGNN_LSTM_TRAIN_MAX problems of one gate count) in ONE launch
- * each way.  The forward reads (z, p_dst, ldp, s_off, c_in) and writes (z, h_out, c_out); the backward reads (z, c_in,
- * c_out, g_h, g_c) and writes (g_z, g_p_dst, g_c_in), fields as in the single calls.  Backward only: it also writes zeros
- * into g_p_dst[n, pad_off .. pad_off + pad_n) (the projection gradient's padding columns, which no kernel of the cell's
- * backward writes and the weight gradient reads: pad_off % 4 == 0, pad_n % 4 == 0, pad_n <= 96; 0 = nothing). */
+ * ldp % 4 == 0, s_off % 4 == 0, every pointer 16-byte aligned.
+ * The node types of a cell (1..GGNN_LSTM_TRAIN_MAX problems of one gate count) in ONE launch each way.  The forward reads
+ * (z, p_dst, ldp, s_off, c_in) and writes (z, h_out, c_out); the backward reads (z, c_in, c_out, g_h, g_c) and writes
+ * (g_z, g_p_dst, g_c_in).  Backward only: it also writes zeros into g_p_dst[n, pad_off .. pad_off + pad_n) (the
+ * projection gradient's padding columns, which no kernel of the cell's backward writes and the weight gradient reads:
+ * pad_off % 4 == 0, pad_n % 4 == 0, pad_n <= 96; 0 = nothing). */
 #define GGNN_LSTM_TRAIN_MAX 4
 typedef struct ggnn_lstm_train_problem {
   float* z;
@@ -801,7 +772,7 @@ int ggnn_heads_regressor_backward(int64_t n_joint, int64_t n_grain, const float*
  * six products per k-step (2e-8 of sum |a||b| against an fp64 product; gradients of 1e-10 keep their 24 bits, which a
  * two-piece fp16 split would not give them).  M, Nc, lda, ldb, a_bstride, b_bstride multiples of 4 (pad B with zero columns
  * otherwise); a, b 16-byte aligned.
- * ABI 25, b_ins != NULL: B is `b` with the ins_w columns of `b_ins` [K, ld_ins] INSERTED at column ins_off -- column c of B is
+ * b_ins != NULL: B is `b` with the ins_w columns of `b_ins` [K, ld_ins] INSERTED at column ins_off -- column c of B is
  * b[c] for c < ins_off, b_ins[c - ins_off] for the next ins_w columns, b[c - ins_w] behind them (Nc counts all of them; b holds
  * Nc - ins_w columns) -- so that the weight gradient of a projection reads [x | 0 | h | 1 0 0 0] from the data skeleton
  * [x | 0 | 1 0 0 0] (ggnn_train_input_rows, once per step) and the hidden state where it lies, without a concatenated copy.
@@ -820,7 +791,7 @@ typedef struct ggnn_wgrad_args {
 int ggnn_wgrad_splits(int64_t K, int M, int Nc, int batch);
 int ggnn_wgrad(const ggnn_wgrad_args* args, ggnn_stream_t stream);
 
-/* Training path (ABI 25): the data part of the weight gradients' B operands, for the node types of a step in one launch:
+/* Training path: the data part of the weight gradients' B operands, for the node types of a step in one launch:
  * out[n, 0 .. Fp + 4) = [x[n, 0 .. F) | 0 .. (Fp - F zeros) | 1 0 0 0], Fp = F rounded up to 4 -- what the encoder's projection
  * gradient multiplies with as it is, and the decoder's with the hidden state inserted at column Fp (ggnn_wgrad, b_ins).
  * out 16-byte aligned, ldo >= Fp + 4, ldo % 4 == 0; 3 <= F <= 12. */
@@ -837,7 +808,7 @@ int ggnn_train_input_rows(const ggnn_train_rows_problem* problems, int n_problem
  * ggnn_period_gat_aggregate_backward (ep_partial: n_rows = ggnn_aggregate_bwd_partials rows of n_cols = n_gates * 288 floats
  * per edge type), in a fixed order.  in: [batch, n_rows, n_cols] contiguous, n_cols % 4 == 0, 16-byte aligned. */
 int ggnn_sum_rows(const float* in, float* out, int64_t n_rows, int64_t n_cols, int32_t batch, ggnn_stream_t stream);
-/* ABI 25: 1..GGNN_SUM_ROWS_MAX such sums in one launch, each with its own shape -- the reductions a cell's backward pass can
+/* 1..GGNN_SUM_ROWS_MAX such sums in one launch, each with its own shape -- the reductions a cell's backward pass can
  * postpone to its end: the split-K partials of its weight gradients (ggnn_wgrad with out == NULL: in = partial, n_rows =
  * n_split, n_cols = batch M Nc, batch = 1) and the edge-parameter partials of its sweeps.  Same fixed summation tree as
  * ggnn_sum_rows (32 interleaved row groups, combined in index order). */
@@ -856,8 +827,8 @@ int ggnn_sum_rows_batch(const ggnn_sum_rows_problem* problems, int n_problems, g
  *   flat2 = [ the cell's parameters, concatenated (n_flat) | nb products [r, c] | one zero slot ],  zero = n_flat + nb r c,
  * every packed entry is the sum of L elements of flat2 (idx3 [n_packed, L]; the index `zero` reads 0), and product b is
  * (coef K_b) Q_b with K_b [r, 96], Q_b [96, c] themselves gathered from flat2: kq_idx = [K entries (nb r 96) | Q entries
- * (nb 96 c)].  ggnn_pack_weights: the caller has written the parameters to flat2[0 .. n_flat); the call fills the products
- * and `packed`.  ggnn_pack_weights_backward: g_out[s] = gradient of output s (NULL: zero), output s being
+ * (nb 96 c)].  ggnn_pack_weights_batch: the caller has written the parameters to flat2[0 .. n_flat); the call fills the products
+ * and `packed`.  ggnn_pack_weights_backward_batch: g_out[s] = gradient of output s (NULL: zero), output s being
  * packed[g_off[s] .. g_off[s + 1]); inv [n_flat2, inv_m] = the packed entries that read each element of flat2 (padding:
  * n_packed), inv_kq [n_flat, inv_kq_m] = the operand entries that read each parameter (padding: n_kq = nb 96 (r + c));
  * g_flat2 [n_flat2] and g_kq [n_kq] are workspaces, g_flat [n_flat] receives the parameters' gradient.  Plain fp32 fmas. */
@@ -872,7 +843,7 @@ typedef struct ggnn_pack_args {
   int32_t nb, r, c, L;
   float coef;
   int32_t reserved;
-  const float* const* params;   /* ABI 25, or NULL: DEVICE array of the parameter tensors' addresses.  With it the entries of kq_idx
+  const float* const* params;   /* NULL, or the DEVICE array of the parameter tensors' addresses.  With it the entries of kq_idx
                                    and idx3 that address a parameter are ENCODED as ((t + 1) << GGNN_PACK_TENSOR_SHIFT) | (offset
                                    inside tensor t) and read from params[t] where the tensor lies (flat2[0 .. n_flat) is then not
                                    read: no concatenated copy of the parameters); entries >= n_flat (products, zero slot) stay
@@ -893,14 +864,12 @@ typedef struct ggnn_pack_bwd_args {
   float* g_flat;
   int64_t n_flat2, n_kq;
   int32_t inv_m, inv_kq_m;
-  int64_t n_tail;   /* ABI 25: g_flat has n_flat + n_tail elements; the tail is written with zeros (the gradient of the parameters
+  int64_t n_tail;   /* g_flat has n_flat + n_tail elements; the tail is written with zeros (the gradient of the parameters
                        the reference's forward reads without effect: the encoder's forget gate) */
 } ggnn_pack_bwd_args;
-int ggnn_pack_weights(const ggnn_pack_args* args, ggnn_stream_t stream);
-int ggnn_pack_weights_backward(const ggnn_pack_bwd_args* args, ggnn_stream_t stream);
-/* ABI 25: the same for 1..GGNN_PACK_MAX cells (the encoder's and the decoder's of a training step) with every launch shared:
- * three launches forward and four backward whatever the number of cells (each of these kernels is a few microseconds of
- * latency on ~1 MB of data).  Same results as the single calls. */
+/* 1..GGNN_PACK_MAX cells per call (the encoder's and the decoder's of a training step) with every launch shared: three
+ * launches forward and four backward whatever the number of cells (each of these kernels is a few microseconds of latency
+ * on ~1 MB of data). */
 #define GGNN_PACK_MAX 2
 int ggnn_pack_weights_batch(const ggnn_pack_args* args, int n_cells, ggnn_stream_t stream);
 int ggnn_pack_weights_backward_batch(const ggnn_pack_bwd_args* args, int n_cells, ggnn_stream_t stream);

@@ -74,6 +74,40 @@ def test_build_csr_rejects_out_of_range_indices():
         backend().build_csr(ei, 5, 3)
 
 
+@pytest.mark.parametrize("mask", [None, (0, -1)])
+def test_csr_in_place_refills_the_same_tables(mask):
+    """Tables carved once for 12 edges and refilled with 12, 7 and 0: every refill equals a fresh build of the same list
+    (one arena per build), and no table moves.  The smallest shapes at which a carving or capacity mistake shows."""
+    be, rs = backend(), np.random.RandomState(26)
+    cap, n_src, n_dst = 12, 5, 4
+    masks = None if mask is None else [mask]
+    ip = be.csr_in_place([(cap, n_src, n_dst)], DEV, masks)
+    names = ("rowptr", "col", "perm", "row", "unit_ptr", "units")
+    where = [getattr(ip.csr[0], a).data_ptr() for a in names]
+    assert len(set(where)) == len(where) and all(p % 16 == 0 for p in where)
+    for dst in ([0] * 5 + [1] * 3 + [2] * 4, [0] * 4 + [2] * 3, []):   # (row 3 never has an edge, row 0 more than a unit's)
+        E = len(dst)
+        dst = rs.permutation(dst).astype(np.int64)
+        src = rs.randint(1, n_src, E)
+        src[np.flatnonzero(dst != 0)[:2]] = 0                          # (what the mask drops; row 0 keeps all its edges)
+        ei = torch.from_numpy(np.stack([src, dst]).reshape(2, E)).to(DEV)
+        got = ip.rebuild([ei])[0]
+        ref = be.build_csr_batch([(ei, n_src, n_dst)], check=False, masks=masks)[0]
+        deg = np.diff(ref.rowptr.cpu().numpy())
+        assert got.E == ref.E == E and deg[3] == 0 and (E == 0 or deg.max() > _lib.GGNN_UNIT_EDGES)
+        assert torch.equal(got.rowptr, ref.rowptr) and torch.equal(got.unit_ptr, ref.unit_ptr)
+        for a in ("col", "perm", "row"):
+            assert torch.equal(getattr(got, a)[:E], getattr(ref, a)[:E]), a
+        nu = int(ref.unit_ptr[-1])
+        assert nu >= n_dst and torch.equal(got.units[:nu], ref.units[:nu])
+        if mask is None:
+            assert got.E_dev is None and ref.E_dev is None and int(ref.rowptr[-1]) == E
+        else:
+            kept = int(((ei[0] != mask[0]) & (ei[1] != mask[1])).sum())
+            assert int(got.E_dev.item()) == int(ref.E_dev.item()) == int(ref.rowptr[-1]) == kept < max(E, 1)
+        assert [getattr(got, a).data_ptr() for a in names] == where
+
+
 # ---------------------------------------------------------------------------------------
 # projection GEMM (fp32 MFMA) against a plain fp32 torch reference
 # ---------------------------------------------------------------------------------------

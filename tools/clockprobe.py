@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Is the projection GEMM MFMA-bound at a power-throttled clock?  Time ggnn_project on random
+"""Is the projection GEMM MFMA-bound at a power-throttled clock?  Time ggnn_project_batch on random
 vs all-zero operands (same instruction stream; zeros let the chip hold a higher clock --
 MI355X_MICROARCH.md 'DVFS give-back')."""
 import os, sys

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Development aid: time ggnn_lstm_epilogue alone on cfg3-sized problems (workspace layout: gate
+"""Development aid: time ggnn_lstm_epilogue_batch alone on cfg3-sized problems (workspace layout: gate
 stride padded to 32 floats), single problems and the batches a rollout step launches."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Development aid: time ggnn_project alone for a range of M (prologue vs per-tile cost)."""
+"""Development aid: time ggnn_project_batch alone for a range of M (prologue vs per-tile cost)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
