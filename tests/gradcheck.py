@@ -223,6 +223,7 @@ def sweep_reference(prob, info, einfo, L, dtype=torch.float64):
     mag = {k: (None if v is None else torch.zeros_like(v)) for k, v in ref.items()}
     mag["edge"] = {"alpha": torch.zeros(E, G, dtype=dtype), "ds": torch.zeros(E, G, dtype=dtype),
                    "S_sae": torch.zeros(n_dst, G, dtype=dtype), "dst": dst, "col": col, "x4": x4}
+    mag["fwd"] = {}
     P, H = prob["p_dst"].double(), (prob["h"].double() if has_h else None)
     for g, (s, alpha, r, go, gd, gs) in enumerate(terms):
         out, sa, sae = fwd[g]
@@ -245,10 +246,32 @@ def sweep_reference(prob, info, einfo, L, dtype=torch.float64):
                 torch.zeros(n_dst, C, dtype=dtype).index_add(0, dst, dsm[:, None] * H[col].abs())
             mag["g_h_src"] += torch.zeros(n_src, C, dtype=dtype).index_add(0, col, dsm[:, None] * uh[dst].abs())
         vm = alpha * (1 + KAPPA_W * kappa[dst])
+        # the forward's own columns: sum alpha |r| (1 + KAPPA_W kappa), with |r| = 1 for sum alpha and |a| for sum alpha a
+        mag["fwd"][g] = (torch.zeros(n_dst, C, dtype=dtype).index_add(0, dst, vm[:, None] * r.abs()),
+                         torch.zeros(n_dst, dtype=dtype).index_add(0, dst, vm),
+                         torch.zeros(n_dst, dtype=dtype).index_add(0, dst, vm * a.abs()))
         mag["g_p_src"][:, L["v_off"] + g * C:L["v_off"] + (g + 1) * C] += \
             torch.zeros(n_src, C, dtype=dtype).index_add(0, col, vm[:, None] * go[dst].abs())
         mag["g_ep"][g] += (reloc.abs().t() @ (vm[:, None] * go[dst].abs()))
     return fwd, ref, mag, pre_all
+
+
+def forward_excess(agg, fwd, mag, L, tol=SWEEP_TOL):
+    """{column group: (worst ratio, index)} of the forward sweep's columns of `agg` -- the aggregate, sum alpha and
+    sum alpha a of every gate -- against the fp64 forward `fwd` of sweep_reference, each element against
+    sum alpha |r| (1 + KAPPA_W kappa) (mag["fwd"]; |r| = 1 for sum alpha, |a| for sum alpha a); <= 1 passes.  The factor
+    is alpha's relative error: it reaches every alpha-weighted sum of different terms (the aggregate, sum alpha a).  In
+    sum alpha = den / (den + 1e-16) it cancels, so that column is graded more loosely than it could be
+    (cellcheck.cell_magnitudes takes the term without the factor)."""
+    res = {}
+    for g in range(L["G"]):
+        base = g * L["a_gstride"]
+        got = (agg[:, base + L["a_off"]:base + L["a_off"] + C], agg[:, base + L["sc_off"]], agg[:, base + L["sc_off"] + 1])
+        for name, a, b, m in zip(("agg", "sum_alpha", "sum_alpha_a"), got, fwd[g], mag["fwd"][g]):
+            r = bound_excess(a.detach(), b.detach(), m.detach(), tol)
+            if r[0] >= res.get(name, (-1.0, None))[0]:
+                res[name] = (r[0], None if r[1] is None else (g,) + tuple(int(v) for v in r[1]))
+    return res
 
 
 def owned_columns(L, has_h):

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from cellcheck import _cell_reference, _rebuild_wide_call, _wide, _wide_cell_problem
 from helpers import (EDGE_TYPES, assert_close, etk, fold_120, golden, load_graph,
                      oracle_models, product_models, random_state, rel_err, tt)
 from graingraphnn_amd import _lib, synthetic
@@ -1723,116 +1724,6 @@ def test_fused_encoder_cell_batch_of_four_equals_single_calls():
         be.encoder_cell_batch(probs + probs[:1])                    # at most four problems
 
 
-def _wide(rs, shape, lo, hi, signed=True):
-    """Magnitudes 10^U(lo, hi), element by element (a dynamic range no single scale has), random signs."""
-    v = 10.0 ** rs.uniform(lo, hi, shape)
-    if signed:
-        v = v * rs.choice([-1.0, 1.0], shape)
-    return torch.from_numpy(v.astype(np.float32))
-
-
-def _cell_reference(kind, P, dtype):
-    """One HeteroPGCLSTM cell of the contract (include/ggnn.h), evaluated on the CPU in `dtype` from the ORIGINAL fp32
-    operands and weights of `P` -- nothing decoded from a weight stream: what the reference formulation computes.
-    kind = "dec" (h, c given; four gates) or "enc" (zero state; three gates)."""
-    t = lambda v: v.cpu().to(dtype)
-    x, n = t(P["x_dst"]), P["x_dst"].size(0)
-    G = 4 if kind == "dec" else 3
-    if kind == "dec":
-        xin = torch.cat([t(P["h_dst"]), x, torch.ones(n, 1, dtype=dtype)], 1)                  # [h | x | 1]
-    else:
-        xin = torch.cat([x, torch.ones(n, 1, dtype=dtype)], 1)                                # [x | 1]
-    pre = []
-    for g in range(G):
-        z = xin @ t(P["skip"][g]).t()
-        for d, sw in enumerate(P["sweeps"]):
-            rowptr = sw["rowptr"].cpu().long()
-            E = int(rowptr[-1])
-            dst = torch.repeat_interleave(torch.arange(n), rowptr[1:] - rowptr[:-1])
-            src = sw["col"].cpu().long()[:E]
-            einfo = t(sw["einfo"])
-            x4, reloc, a = einfo[:E, :16], einfo[:E, 16:19], einfo[:E, 19]
-            u = xin @ t(sw["score"][g]).t()                                                    # dec: [n, 96 + 16]; enc: [n, 16]
-            if kind == "dec":
-                sc = (u[dst, :96] * t(sw["h_src"])[src]).sum(-1) + (u[dst, 96:] * x4).sum(-1)
-                val = torch.relu(t(sw["v_src"])[src][:, sw["v_off"] + g * 96: sw["v_off"] + (g + 1) * 96] + reloc @ t(sw["ep"])[g])
-            else:
-                sc = (u[dst] * x4).sum(-1)
-                val = torch.relu(x4 @ t(sw["value"][g]).t())
-            smax = torch.full((n,), float("-inf"), dtype=dtype).scatter_reduce(0, dst, sc, "amax")
-            p = (sc - smax[dst]).exp()
-            den = torch.zeros(n, dtype=dtype).index_add(0, dst, p)
-            alpha = p / (den[dst] + 1e-16)
-            A = torch.zeros(n, 96, dtype=dtype).index_add(0, dst, alpha[:, None] * val)
-            sa = torch.zeros(n, dtype=dtype).index_add(0, dst, alpha)
-            sae = torch.zeros(n, dtype=dtype).index_add(0, dst, alpha * a)
-            z = z + A @ t(sw["l2"][g]).t() + sa[:, None] * t(sw["b_l2"][g])[None] + sae[:, None] * t(sw["w_edge"][g])[None]
-        pre.append(z)
-    if kind == "dec":
-        c = torch.sigmoid(pre[1]) * t(P["c_in"]) + torch.sigmoid(pre[0]) * torch.tanh(pre[2])
-        return torch.sigmoid(pre[3]) * torch.tanh(c), c
-    c = torch.sigmoid(pre[0]) * torch.tanh(pre[1])
-    return torch.sigmoid(pre[2]) * torch.tanh(c), c
-
-
-def _wide_cell_problem(be, kind, rs, n_dst, ins, F_dst, with_edges=True):
-    """A decoder / encoder cell problem whose operands span 1e-4 .. 1e2 element by element, with weights scaled so that
-    the pre-activations stay O(1).  Returns (the C-ABI call tuple, the dict of ORIGINAL fp32 operands and weights)."""
-    G = 4 if kind == "dec" else 3
-    d_ = lambda v: v.to(DEV)
-    xd = _wide(rs, (n_dst, F_dst), -4, 2, signed=False)
-    P = {"x_dst": d_(xd), "sweeps": []}
-    K = (96 if kind == "dec" else 0) + F_dst + 1
-    if kind == "dec":
-        P["h_dst"] = d_(torch.tanh(_wide(rs, (n_dst, 96), -4, 0.5)))
-        P["c_in"] = d_(_wide(rs, (n_dst, 96), -4, 0.3))
-    # every weight row is scaled by what it multiplies, so that sum |x||w| ~ 1 .. 10 per output
-    feat_scale = 1.0 / (float(xd.abs().mean()) * F_dst + (30.0 if kind == "dec" else 0.0) + 1.0)
-    wrow = lambda rows, cols, s: _wide(rs, (rows, cols), -2, 0) * s
-    P["skip"] = [d_(wrow(96, K, feat_scale)) for _ in range(G)]
-    for d, (n_src, F, E) in enumerate(ins):
-        E = E if with_edges else 0
-        src = rs.randint(0, max(n_src - 5, 1), size=E)
-        dst = rs.randint(1 if n_dst > 1 else 0, n_dst, size=E)
-        ei = torch.from_numpy(np.stack([src, dst]).astype(np.int64)).to(DEV)
-        xs = _wide(rs, (n_src, F), -4, 2, signed=False)
-        xs[:, :3] = torch.from_numpy(rs.uniform(0, 1, (n_src, 3)).astype(np.float32))   # coordinates stay in the unit box
-        ea = torch.from_numpy(rs.uniform(0.01, 0.1, E).astype(np.float32)).to(DEV)
-        csr = be.build_csr(ei, n_src, n_dst)
-        einfo = torch.zeros(E + 3, 20, device=DEV)
-        be.edge_prepare([(csr, ea, d_(xs), P["x_dst"], einfo)])
-        rec_scale = 1.0 / (float(xs[:, 3:].abs().mean()) * max(F - 3, 1) + 2.0)
-        sw = {"rowptr": csr.rowptr, "col": csr.col, "einfo": einfo, "csr": csr,
-              "l2": [d_(wrow(96, 96, 0.05)) for _ in range(G)], "b_l2": [d_(wrow(96, 1, 0.3)[:, 0]) for _ in range(G)],
-              "w_edge": [d_(wrow(96, 1, 0.3)[:, 0]) for _ in range(G)]}
-        if kind == "dec":
-            sw["h_src"] = d_(torch.tanh(_wide(rs, (n_src, 96), -4, 0.5)))
-            sw["v_src"] = d_(_wide(rs, (n_src, 384 * (d + 1) + 96), -4, 1))
-            sw["v_off"] = 384 * d
-            sw["ep"] = d_(_wide(rs, (4, 3, 96), -2, 0))
-            score = []
-            for g in range(G):
-                W1 = torch.zeros(112, K)
-                W1[:96] = wrow(96, K, 0.02 * feat_scale)            # u_h rows (they meet h_src in (-1, 1))
-                W1[96:110] = wrow(14, K, rec_scale * feat_scale)     # u4 rows (they meet the edge record)
-                score.append(d_(W1))
-            sw["score"] = score
-        else:
-            score, value = [], []
-            for g in range(G):
-                T = torch.zeros(16, K)
-                T[:14] = wrow(14, K, rec_scale * feat_scale)
-                if F <= 11:
-                    T[11] = 0
-                V = torch.zeros(96, 16)
-                V[:, :F], V[:, 12] = wrow(96, F, rec_scale), wrow(96, 1, 0.3)[:, 0]
-                score.append(d_(T))
-                value.append(d_(V))
-            sw["score"], sw["value"] = score, value
-        P["sweeps"].append(sw)
-    return _rebuild_wide_call(be, kind, P)
-
-
 @pytest.mark.parametrize("kind", ["dec", "enc"])
 @torch.no_grad()
 def test_fused_cells_are_fp32_equivalent_on_wide_range_operands(kind):
@@ -1884,49 +1775,6 @@ def test_fused_cells_are_fp32_equivalent_on_wide_range_operands(kind):
     err = float((((pre - ref).abs() - floor).clamp(min=0) / norm)[ok].max())
     assert err < 2e-7, f"{kind} cell, skip product alone: {err:.2e} of sum |x||w|"
     assert not be.range_exceeded(DEV)
-
-
-def _rebuild_wide_call(be, kind, P):
-    """(call tuple, P): the operands and ORIGINAL weights of `P` in the kernels' weight-stream image; again after an
-    in-place edit of the weights."""
-    from graingraphnn_amd.packing import CELL_P3_CHANNEL, DC_GATE_ORDER, _plane_slices, _spread16
-    G = 4 if kind == "dec" else 3
-    n_dst, F_dst = P["x_dst"].shape
-    n_in = len(P["sweeps"])
-    K = (96 if kind == "dec" else 0) + F_dst + 1
-    p3 = torch.tensor(CELL_P3_CHANNEL, device=DEV)
-
-    def in128(W):
-        out = torch.zeros(W.size(0), 128, device=DEV)
-        out[:, :K] = W
-        return out
-
-    def slots16(W):
-        out = torch.zeros(W.size(0), 16, device=DEV)
-        out[:, :F_dst], out[:, 12] = W[:, :F_dst], W[:, F_dst]
-        return out
-
-    slices = []
-    for gi, g in enumerate(DC_GATE_ORDER if kind == "dec" else range(3)):
-        for sw in (P["sweeps"][::-1] if kind == "dec" and gi & 1 else P["sweeps"]):   # decoder: backwards for the 2nd / 4th gate
-            if kind == "dec":
-                slices += [_plane_slices(in128(sw["score"][g])), _plane_slices(sw["l2"][g])]
-            else:
-                slices += [_plane_slices(_spread16(torch.cat([sw["value"][g], slots16(sw["score"][g])]))),
-                           _plane_slices(sw["l2"][g][:, p3].contiguous())]
-        slices.append(_plane_slices(in128(P["skip"][g]) if kind == "dec" else _spread16(slots16(P["skip"][g]))))
-    wstream = torch.cat(slices).contiguous().view(-1)
-    tail = torch.zeros(G, n_in, 6, 4, 16, device=DEV)
-    for d, sw in enumerate(P["sweeps"]):
-        for g in range(G):
-            tail[g, d, :, 0] = sw["b_l2"][g].view(6, 16)
-            tail[g, d, :, 1 if kind == "dec" else 3] = sw["w_edge"][g].view(6, 16)
-    tail = tail.view(G, n_in, 6, 64).contiguous()
-    out = [torch.empty(n_dst, 96, device=DEV), torch.empty(n_dst, 96, device=DEV)]
-    if kind == "dec":
-        return ([(sw["csr"], sw["einfo"], sw["h_src"], sw["v_src"], sw["v_off"], sw["ep"]) for sw in P["sweeps"]],
-                P["x_dst"], P["h_dst"], P["c_in"], wstream, tail, *out), P
-    return ([(sw["csr"], sw["einfo"]) for sw in P["sweeps"]], P["x_dst"], wstream, tail, *out), P
 
 
 @pytest.mark.parametrize("kind", ["dec", "enc"])

@@ -28,6 +28,16 @@ def _sweep_case(variant, seed, empty=False):
     return L, has_h, gc.sweep_problem(L, has_h, seed, **kw)
 
 
+def _agg_of(fwd, L, n_dst):
+    """A forward {gate: (aggregate, sum alpha, sum alpha a)} laid out as the sweep writes its agg rows."""
+    agg = torch.zeros(n_dst, L["ld_agg"], dtype=fwd[0][0].dtype if fwd else torch.float32)
+    for g, (out, sa, sae) in fwd.items():
+        base = g * L["a_gstride"]
+        agg[:, base + L["a_off"]:base + L["a_off"] + 96] = out
+        agg[:, base + L["sc_off"]], agg[:, base + L["sc_off"] + 1] = sa, sae
+    return agg
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # 1. The sweep backward against the fp64 restatement
 # ---------------------------------------------------------------------------------------------------------------------
@@ -53,6 +63,15 @@ def test_hip_sweep_backward_against_fp64(variant, seed, empty):
               f"(fp32 restatement: {res32[k][0]:.3f})")
     for k, (r, idx) in res.items():
         assert r <= 1.0, (variant, k, r, idx)
+    # the forward split sweep on the same problem: its aggregate, sum alpha and sum alpha a columns of every gate
+    fres = gc.forward_excess(agg, fwd, mag, L)
+    fwd32, _, _, _ = gc.sweep_reference(prob, info, einfo, L, torch.float32)
+    fres32 = gc.forward_excess(_agg_of(fwd32, L, prob["n_dst"]), fwd, mag, L)
+    for k, (r, idx) in fres.items():
+        print(f"{variant} E={info['col'].numel()} forward {k}: worst |hip - ref64| / bound {r:.3f} at {idx} "
+              f"(fp32 restatement: {fres32[k][0]:.3f})")
+    for k, (r, idx) in fres.items():
+        assert r <= 1.0, (variant, "forward", k, r, idx)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -286,6 +305,15 @@ def test_sweep_check_accepts_the_emulator_and_sees_one_edge_bugs(variant):
     gc.check_relu_margin(pre)
     worst = lambda got: max(r for r, _ in gc.sweep_excess(got, ref, mag, L, has_h).values())
     assert worst(out) <= 0.2                          # the fp32 emulator: well inside the bound
+    # the forward columns: the emulator and the fp32 restatement inside the bound, one edge's term of a hub row is not
+    fworst = lambda a: max(r for r, _ in gc.forward_excess(a, fwd, mag, L).values())
+    fwd32, _, _, _ = gc.sweep_reference(prob, info, einfo, L, torch.float32)
+    print(f"{variant} forward: emulator {fworst(agg):.3f}, fp32 restatement {fworst(_agg_of(fwd32, L, prob['n_dst'])):.3f}")
+    assert fworst(agg) <= 0.5 and fworst(_agg_of(fwd32, L, prob["n_dst"])) <= 0.5
+    e = int(prob["deg"][:5].sum()) + 450              # an edge in the middle of the 900-edge hub row (row 5)
+    bad = agg.clone()
+    bad[5, L["sc_off"]] -= float(mag["edge"]["alpha"][e, 0])     # its alpha missing from gate 0's sum alpha
+    assert fworst(bad) > 1.0
     ed, G = mag["edge"], L["G"]
     # (a) one edge's fp64 contribution removed from the 900-edge hub row (the edge of median |ds|)
     hub, rp = 5, info["rowptr"]
