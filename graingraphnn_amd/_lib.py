@@ -25,6 +25,7 @@ GGNN_PRECISION_F16X2 = 2
 GGNN_OUT_BLOCK_MAJOR = 0x100
 GGNN_ETOPOLOGY = -3
 GGNN_FLAG_F16_RANGE = 1
+GGNN_FLAG_QOI_OVERFLOW = 2
 GGNN_ADAM_CHUNK, GGNN_ADAM_MAX_TENSORS, GGNN_ADAM_MAX_GROUPS = 4096, 384, 8
 GGNN_ROWGEMM_MAX_PACK = 8
 GGNN_MSE_MAX_TERMS, GGNN_MSE_BLOCKS = 4, 64
@@ -49,6 +50,7 @@ EXPORTED_SYMBOLS = (
     "ggnn_heads_classifier", "ggnn_step_update", "ggnn_grain_centres", "ggnn_detect_events", "ggnn_topology_update", "ggnn_topology_open", "ggnn_topology_apply",
     "ggnn_topology_counts", "ggnn_topology_export", "ggnn_topology_close", "ggnn_step_refresh",
     "ggnn_workspace_bytes",
+    "ggnn_qoi_accumulate", "ggnn_qoi_finalize",
 )
 
 
@@ -305,6 +307,19 @@ class RefreshEdge(Structure):
     ]
 
 
+class QoiArgs(Structure):
+    """Mirror of `ggnn_qoi_args`."""
+    _fields_ = [
+        ("x_grain", c_void_p), ("live_grain", c_void_p), ("traj_offsets", c_void_p), ("area0", c_void_p),
+        ("a_prev", c_void_p), ("T_in", c_void_p), ("V0", c_void_p), ("a_cur", c_void_p), ("T_out", c_void_p),
+        ("e_cur", c_void_p), ("history", c_void_p), ("area_sum", c_void_p), ("layer_in", c_void_p), ("layer_out", c_void_p),
+        ("sync_word", c_void_p), ("flags", c_void_p),
+        ("ldx_grain", c_int64), ("n_grain", c_int64), ("n_traj", c_int64), ("capacity", c_int64),
+        ("domain_factor", ctypes.c_double), ("s", ctypes.c_double), ("delta_h", ctypes.c_double),
+        ("init", c_int32), ("reserved", c_int32),
+    ]
+
+
 _lib = None
 
 
@@ -413,6 +428,11 @@ def _declare(lib):
     lib.ggnn_topology_export.argtypes = [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64]
     lib.ggnn_topology_close.restype = None
     lib.ggnn_topology_close.argtypes = [c_void_p]
+    lib.ggnn_qoi_accumulate.restype = c_int
+    lib.ggnn_qoi_accumulate.argtypes = [POINTER(QoiArgs), c_void_p]
+    lib.ggnn_qoi_finalize.restype = c_int
+    lib.ggnn_qoi_finalize.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, ctypes.c_double, c_void_p,
+                                      c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.ggnn_workspace_bytes.restype = c_size_t
     lib.ggnn_workspace_bytes.argtypes = [c_int64, c_int64, c_int64]
 

@@ -1038,6 +1038,68 @@ class HipBackend:
                                             ptr(x_grain), x_grain.stride(0), x_grain.size(1), ptr(joints_before),
                                             _lib.current_stream()), "ggnn_noflux_boundary")
 
+    def qoi_accumulate(self, x_grain, live_grain, traj_offsets, const, state_in, state_out, V0, sync_word, flags,
+                       history=None, capacity=0, area_sum=None, init=False, area0=None):
+        """One layer of the rollout's quantities of interest (include/ggnn.h, ggnn_qoi_accumulate), one launch.
+        const = (domain_factor, s, delta_h); state_in / state_out: dicts of fp32 [n_grain] `a`, `T`, `e` and the int32 word
+        `layer` (the same dict twice: in place); V0 fp32 [n_grain] (written when `init`); history: None or fp32
+        [capacity + 1, n_grain]; live_grain: int32 [n_grain] or None; traj_offsets: int64 [n_traj + 1] on the device."""
+        n = x_grain.size(0)
+        _require_cuda(x_grain, live_grain, traj_offsets, V0, sync_word, flags, history, area_sum, area0)
+        _f32c(x_grain, "x_grain")
+        for t, name in ((state_in["a"], "a_prev"), (state_in["T"], "T_in"), (state_out["a"], "a_cur"), (state_out["T"], "T_out"),
+                        (state_out["e"], "e_cur"), (V0, "V0"), (area0, "area0")):
+            if t is not None:
+                _f32c(t, name)
+                if t.numel() != n:
+                    raise _lib.GGNNError(f"{name} must have one element per grain")
+        if traj_offsets.dtype != torch.int64 or traj_offsets.numel() < 2 or not traj_offsets.is_contiguous():
+            raise _lib.GGNNError("traj_offsets must be a contiguous int64 [n_traj + 1]")
+        if live_grain is not None and (live_grain.dtype != torch.int32 or live_grain.numel() != n):
+            raise _lib.GGNNError("live_grain must be int32 [n_grain]")
+        for w in (state_in["layer"], state_out["layer"], sync_word, flags):
+            if w.dtype != torch.int32 or w.numel() < 1:
+                raise _lib.GGNNError("layer / sync_word / flags must be int32 words")
+        if history is not None:
+            _f32c(history, "history")
+            if history.numel() != (int(capacity) + 1) * n:
+                raise _lib.GGNNError("history must be [capacity + 1, n_grain]")
+        if area_sum is not None and (area_sum.dtype != torch.float32 or area_sum.numel() != traj_offsets.numel() - 1):
+            raise _lib.GGNNError("area_sum must be fp32 [n_traj]")
+        A = _lib.QoiArgs()
+        A.x_grain, A.live_grain, A.traj_offsets, A.area0 = ptr(x_grain), ptr(live_grain), ptr(traj_offsets), ptr(area0)
+        A.a_prev, A.T_in, A.layer_in = ptr(state_in["a"]), ptr(state_in["T"]), ptr(state_in["layer"])
+        A.a_cur, A.T_out, A.e_cur, A.layer_out = ptr(state_out["a"]), ptr(state_out["T"]), ptr(state_out["e"]), ptr(state_out["layer"])
+        A.V0, A.history, A.area_sum, A.sync_word, A.flags = ptr(V0), ptr(history), ptr(area_sum), ptr(sync_word), ptr(flags)
+        A.ldx_grain, A.n_grain, A.n_traj, A.capacity = x_grain.stride(0), n, traj_offsets.numel() - 1, int(capacity)
+        A.domain_factor, A.s, A.delta_h = (float(c) for c in const)
+        A.init = 1 if init else 0
+        check(self.lib.ggnn_qoi_accumulate(ctypes.byref(A), _lib.current_stream()), "ggnn_qoi_accumulate")
+
+    def qoi_finalize(self, V0, T, e, traj_offsets, mesh_size, bin_edges=None):
+        """(volume [n_grain], size [n_grain], d_mu [n_traj], d_std [n_traj], counts [n_traj, n_edges - 1] int32 or None) of
+        ggnn_qoi_finalize; bin_edges: ascending fp32 [n_edges] on the device, or None."""
+        _require_cuda(V0, T, e, traj_offsets, bin_edges)
+        n, n_traj = V0.numel(), traj_offsets.numel() - 1
+        for t, name in ((V0, "V0"), (T, "T"), (e, "e")):
+            _f32c(t, name)
+            if t.numel() != n:
+                raise _lib.GGNNError(f"{name} must have one element per grain")
+        if traj_offsets.dtype != torch.int64 or n_traj < 1 or not traj_offsets.is_contiguous():
+            raise _lib.GGNNError("traj_offsets must be a contiguous int64 [n_traj + 1]")
+        dev = V0.device
+        volume, size = torch.empty(n, device=dev), torch.empty(n, device=dev)
+        d_mu, d_std = torch.empty(n_traj, device=dev), torch.empty(n_traj, device=dev)
+        n_edges, hist = 0, None
+        if bin_edges is not None:
+            _f32c(bin_edges, "bin_edges")
+            n_edges = bin_edges.numel()
+            hist = torch.zeros(n_traj, max(n_edges - 1, 0), dtype=torch.int32, device=dev)
+        check(self.lib.ggnn_qoi_finalize(ptr(V0), ptr(T), ptr(e), n, ptr(traj_offsets), n_traj, float(mesh_size), ptr(bin_edges),
+                                         n_edges, ptr(volume), ptr(size), ptr(d_mu), ptr(d_std), ptr(hist),
+                                         _lib.current_stream()), "ggnn_qoi_finalize")
+        return volume, size, d_mu, d_std, hist
+
     def detect_events(self, grain_area, live_grain, area_threshold, edge_event, edge_index_jj,
                       logit_threshold, flags, range_word=None, E_dev=None, skip_grain=-1):
         """flags[0:2] (int32, device) <- (#grain events, #switch candidates); with `range_word` (int32 [1]) flags[2] <- the

@@ -144,13 +144,16 @@ def run_sharded(n_traj: int, run_one: Callable[[int], torch.Tensor], rank: int, 
 
 def rollout_trajectories(rmodel, cmodel, graphs, span: int, n_steps: int, rank: int = 0,
                          world: int = 1, device="cuda", use_graph: bool = True,
-                         refresh_centres: bool = False):
+                         refresh_centres: bool = False, qoi=None):
     """BASELINE config 4: `graphs[t]` = (x, ei, ea) numpy dicts of independent trajectories with
     EQUAL node counts.  Rank r rolls out trajectories t = r (mod world) as ONE disjoint-union
     graph on its GPU (one set of launches for the whole shard), then all ranks all-gather the
     final joint coordinates and grain (area, extraV): returns {'joint_xy': [T, N_j, 2],
 'grain_area_v': [T, N_g, 2]} in trajectory order on every rank.  `refresh_centres`: also
-    recompute the grain centres every step (unfolded domains: factor 1), as `GrainRollout` does."""
+    recompute the grain centres every step (unfolded domains: factor 1), as `GrainRollout` does.
+    `qoi`: the keywords of GrainRollout.enable_qoi (patch_size, mesh_size, ini_height, final_height, ...; the union's
+    trajectory offsets are filled in): every trajectory's grain volumes and equivalent diameters are accumulated on the
+    device during the rollout and travel with the states, 'volume' and 'size' [T, N_g]."""
     from . import synthetic
     from .rollout import GrainRollout
 
@@ -159,11 +162,24 @@ def rollout_trajectories(rmodel, cmodel, graphs, span: int, n_steps: int, rank: 
     x, ei, ea, slices = synthetic.disjoint_union([graphs[t] for t in mine])
     X, EI, EA = synthetic.to_torch(x, ei, ea, device)
     ro = GrainRollout(rmodel, cmodel, X, EI, EA, span, use_graph=use_graph, refresh_centres=refresh_centres)
+    grains = [s["grain"] for s in slices]
+    if qoi is not None:
+        ro.enable_qoi(**dict(qoi, traj_offsets=[lo for lo, _ in grains] + [grains[-1][1]]))
     ro.run(n_steps)
     local = {"joint_xy": torch.stack([X["joint"][lo:hi, :2] for lo, hi in (s["joint"] for s in slices)]),
-             "grain_area_v": torch.stack([X["grain"][lo:hi, 3:5] for lo, hi in (s["grain"] for s in slices)])}
-    out = {}
-    for k, v in local.items():
-        it = iter(range(len(mine)))
-        out[k] = run_sharded(len(graphs), lambda t, v=v, it=it: v[next(it)], rank, world)
+             "grain_area_v": torch.stack([X["grain"][lo:hi, 3:5] for lo, hi in grains])}
+    if qoi is not None:
+        q = ro.qoi()
+        for k in ("volume", "size"):
+            local[k] = torch.stack([q[k][lo:hi] for lo, hi in grains])
+    # every key of a trajectory in ONE row: one packed all-gather whatever the number of keys
+    keys = sorted(local)
+    rows = torch.cat([local[k].reshape(len(mine), -1) for k in keys], dim=1)
+    it = iter(range(len(mine)))
+    gathered = run_sharded(len(graphs), lambda t: rows[next(it)], rank, world)
+    out, at = {}, 0
+    for k in keys:
+        n = local[k][0].numel()
+        out[k] = gathered[:, at:at + n].reshape((len(graphs),) + tuple(local[k].shape[1:]))
+        at += n
     return out

@@ -77,6 +77,7 @@ class GrainRollout:
         self._xc = self._xc_other = None      # the classifier's two alternating copies of x (_overlap_buffers)
         self._xc_fresh = False
         self._graphs = None                   # run() / step() graphs per (steps, buffers): _replay
+        self._qoi = None                      # enable_qoi(): the accumulator of grain volumes and its launch constants
         self._drop_segment_graphs()           # step_events()' segment graphs: _segment_graphs, _graph_fwd, _graph_ref
         self._set_topology(edge_index_dict, edge_attr_dict)
         self.span = span
@@ -348,6 +349,143 @@ class GrainRollout:
         self.be.grain_centres(self.graph.csr_full[JG], self.x["joint"], self.x["grain"], self.domain_factor,
                               self.domain_offset, centres_before=centres_before, boundary=self.boundary)
 
+    # -- quantities of interest: grain volumes and size statistics (graph_trajectory.py:1042-1051, 221-256) -----------
+    def enable_qoi(self, patch_size, mesh_size, ini_height, final_height, frames=None, capacity=None, area0=None,
+                   history=True, traj_offsets=None):
+        """Accumulate, from now on and on the device, what the reference's rollout records at every frame and integrates at
+        its end: the normalised live-grain areas and scaled excess volumes (GNN_update's "qoi", graph_trajectory.py:1042-1051),
+        their trapezoid integral over the layers (volume('graph'), :221-242) and, in qoi(), the equivalent diameters with
+        d_mu, d_std and the histogram (:244-256).  One launch per step (ggnn_qoi_accumulate, include/ggnn.h) behind the
+        step's topology update and boundary step, in step() / run() / step_events() / run_events() and inside their
+        hipGraphs.  Layer 0 -- the state as it is now -- is computed at once.
+        patch_size, mesh_size, ini_height, final_height: the trajectory object's (40, 0.08, 2, 50 by default there);
+        frames: test.py:307, int((final_height - ini_height) / 0.4) + 1; capacity: the number of layers a kept history has
+        room for beyond layer 0 (default: the steps the frames allow, (frames - 1) // span); area0 [n_grain]: layer 0's
+        areas when they are not the formula's (the reference keeps its rasterised pixel counts there, test.py:340);
+        history=False keeps no volume_traj; traj_offsets: the first grain of every trajectory of a disjoint-union graph and
+        the total, [n_traj + 1] (default: one trajectory)."""
+        dev, ng = self.x["grain"].device, self.n_nodes["grain"]
+        if frames is None:
+            frames = int((final_height - ini_height) / 0.4) + 1   # test.py:191, 307
+        if not (mesh_size > 0 and patch_size > 0 and frames > 1):
+            raise _lib.GGNNError("enable_qoi: mesh_size and patch_size must be positive, frames at least 2")
+        if capacity is None:
+            capacity = (int(frames) - 1) // self.span
+        off = np.asarray([0, ng] if traj_offsets is None else traj_offsets, dtype=np.int64).reshape(-1)
+        if off.size < 2 or off[0] != 0 or off[-1] != ng or (np.diff(off) < 0).any():
+            raise _lib.GGNNError("traj_offsets must rise from 0 to the number of grains")
+        delta_h = self.span * (final_height - ini_height) / mesh_size / (frames - 1)
+        f32 = dict(dtype=torch.float32, device=dev)
+        Q = self._qoi = {
+            "const": (self.domain_factor, patch_size / mesh_size + 1, delta_h), "mesh_size": float(mesh_size),
+            "capacity": int(capacity), "offsets_host": off, "offsets": torch.from_numpy(off).to(dev),
+            "V0": torch.empty(ng, **f32), "home": self._qoi_state(), "words": torch.zeros(2, dtype=torch.int32, device=dev),
+            "history": torch.zeros(int(capacity) + 1, ng, **f32) if history else None,
+            "area_sum": torch.empty(off.size - 1, **f32),
+            "ring": None, "entries": None, "launched": 0, "at": None}
+        if area0 is not None:
+            area0 = torch.as_tensor(area0).to(dev, torch.float32).contiguous().view(-1)
+            if area0.numel() != ng:
+                raise _lib.GGNNError("area0 must have one entry per grain")
+        # graphs captured so far lack the launch
+        self._graphs = None
+        self._drop_segment_graphs()
+        if self._spec is not None:
+            self._spec["graphs"], self._spec["captured"] = {}, None
+        self._enqueue_qoi(init=True, area0=area0)
+
+    def _qoi_state(self):
+        """One accumulator: a_k, T_k, e_k per grain and the layer counter, in ONE allocation (a state is copied in one
+        copy).  The rollout's own (`home`) is advanced in place; run_events keeps one per ring slot."""
+        ng, dev = self.n_nodes["grain"], self.x["grain"].device
+        n4 = (ng + 3) & ~3
+        flat = torch.zeros(3 * n4 + 4, dtype=torch.float32, device=dev)
+        return {"flat": flat, "a": flat[:ng], "T": flat[n4:n4 + ng], "e": flat[2 * n4:2 * n4 + ng],
+                "layer": flat[3 * n4:].view(torch.int32)[:1]}
+
+    def _enqueue_qoi(self, slot=None, init=False, area0=None):
+        """This step's layer (off unless enable_qoi was called): on the rollout's own accumulator in place, or -- a ring
+        `slot` of the speculative event loop -- from the slot before to the slot's own."""
+        Q = self._qoi
+        if Q is None:
+            return
+        src = dst = Q["home"]
+        if slot is not None:
+            src, dst = Q["ring"][(slot - 1) % len(Q["ring"])], Q["ring"][slot]
+        self.be.qoi_accumulate(self.x["grain"], self._live_grain if self.mask is not None else None, Q["offsets"],
+                               Q["const"], src, dst, Q["V0"], Q["words"][:1], Q["words"][1:], Q["history"], Q["capacity"],
+                               Q["area_sum"], init=init, area0=area0)
+
+    def _qoi_home(self):
+        """Behind run_events the current accumulator is the last committed step's ring slot: back into the rollout's own."""
+        Q = self._qoi
+        if Q is not None and Q["at"] is not None:
+            self._qoi_take(Q["ring"][Q["at"]])
+
+    def _qoi_take(self, state):
+        self._qoi["home"]["flat"].copy_(state["flat"])
+        self._qoi["at"] = None
+
+    def _qoi_enter_block(self, slots):
+        """Before a block of speculative steps: the slot before its first one holds the current accumulator, and a copy of
+        it is kept for the case that the block's first step is eventful (two full blocks in flight fill the ring: the last
+        step of the second one overwrites that slot).  Two copies alternate: at most two blocks are unchecked."""
+        Q = self._qoi
+        if Q is None:
+            return None
+        D = self._spec["D"]
+        if Q["ring"] is None or len(Q["ring"]) != D:
+            self._qoi_home()
+            Q["ring"], Q["entries"] = [self._qoi_state() for _ in range(D)], [self._qoi_state() for _ in range(2)]
+            self._spec["graphs"], self._spec["captured"] = {}, None
+        before = Q["ring"][(slots[0] - 1) % D]
+        if Q["at"] != (slots[0] - 1) % D:
+            self._qoi_home()
+            before["flat"].copy_(Q["home"]["flat"])
+        entry = Q["entries"][Q["launched"] & 1]
+        Q["launched"] += 1
+        entry["flat"].copy_(before["flat"])
+        Q["at"] = slots[-1]
+        return entry
+
+    def qoi(self):
+        """The quantities of interest up to the last step (one synchronisation).  For one trajectory: `volume` and `size`
+        [n_grain] (device tensors: V0 + T + e of the last layer and cbrt(6 volume / pi) * mesh_size), `d_mu`, `d_std`
+        (floats, over all grains, eliminated ones included, population std), `hist` (np.histogram(size, np.arange(0, 20,
+        1 if n_grain > 400 else 2), density=True)), `hist_counts`, `bin_centres`, `layers` (steps accumulated) and, with a
+        history, `volume_traj` [layers + 1, n_grain].  With traj_offsets: `d_mu` / `d_std` arrays and `hist` / `hist_counts` /
+        `bin_centres` lists, one entry per trajectory.  Raises when a layer went beyond the history's capacity."""
+        Q = self._qoi
+        if Q is None:
+            raise _lib.GGNNError("call enable_qoi(...) first")
+        self._qoi_home()
+        H = Q["home"]
+        words = torch.cat([H["layer"], Q["words"][1:]]).cpu()
+        layers = int(words[0])
+        if int(words[1]) & _lib.GGNN_FLAG_QOI_OVERFLOW:
+            raise _lib.GGNNError(f"the volume history has room for {Q['capacity']} layers, {layers} were accumulated: "
+                                 "enable_qoi(capacity=...) or history=False")
+        off, dev = Q["offsets_host"], self.x["grain"].device
+        steps = [1 if n > 400 else 2 for n in np.diff(off)]   # graph_trajectory.py:251
+        out, hist, counts, centres = None, [None] * len(steps), [None] * len(steps), [None] * len(steps)
+        for step in sorted(set(steps)):
+            edges = np.arange(0, 20, step).astype(np.float32)
+            out = self.be.qoi_finalize(Q["V0"], H["T"], H["e"], Q["offsets"], Q["mesh_size"], torch.from_numpy(edges).to(dev))
+            c = out[4].cpu().numpy().astype(np.int64)
+            for t, st in enumerate(steps):
+                if st == step:
+                    counts[t] = c[t]
+                    hist[t] = c[t] / max(int(c[t].sum()), 1) / np.diff(edges.astype(np.float64))
+                    centres[t] = 0.5 * (edges[:-1] + edges[1:]).astype(np.float64)
+        d_mu, d_std = out[2].cpu().numpy().astype(np.float64), out[3].cpu().numpy().astype(np.float64)
+        one = len(steps) == 1
+        res = {"volume": out[0], "size": out[1], "d_mu": float(d_mu[0]) if one else d_mu,
+               "d_std": float(d_std[0]) if one else d_std, "hist": hist[0] if one else hist,
+               "hist_counts": counts[0] if one else counts, "bin_centres": centres[0] if one else centres, "layers": layers}
+        if Q["history"] is not None:
+            res["volume_traj"] = Q["history"][:layers + 1]
+        return res
+
     # -- one step, enqueued on the current stream --------------------------------------
     def _pipelined(self):
         """Two streams and no joint launches: step() and run() enqueue the overlapped step (_enqueue_overlapped_step).
@@ -431,6 +569,7 @@ class GrainRollout:
         self._enqueue_boundary(joints_before)
         if self.refresh_centres:
             self._enqueue_centres(centres_before)
+        self._enqueue_qoi(slot)
         if headed_prev is not None:
             main.wait_event(headed_prev)   # the previous step's classifier has read the set this refresh writes
         be.step_refresh_prepare(x["joint"], x["grain"], self.zmax, zf,
@@ -540,6 +679,7 @@ class GrainRollout:
         self._enqueue_boundary()
         if self.refresh_centres:
             self._enqueue_centres()
+        self._enqueue_qoi()
         be.step_refresh(x["joint"], x["grain"], self.zmax, self.flags,
                         [(self.graph.edge_index[et], x[et[0]], x[et[-1]], ea[et], self.graph.count_dev[et]) for et in EDGE_TYPES])
 
@@ -610,6 +750,8 @@ class GrainRollout:
         self._ev_host = torch.zeros(2, dtype=torch.int32).pin_memory()
         self._quiet_steps = 0
         self._drop_segment_graphs()
+        if self._qoi is not None:   # (its launches read the live mask from now on)
+            self._graphs = None
         self.grain_events, self.switched = [], []
         self._enter_capacity_mode()
 
@@ -664,6 +806,7 @@ class GrainRollout:
         if self.mask is None:
             raise _lib.GGNNError("call enable_events(mask, ...) first")
         self.refresh_weights(sample=self.steps_done % 16 != 0)
+        self._qoi_home()
         self._einfo_fresh = False   # this mode prepares its edge records at the start of every step
         self._x_written_outside()
         self._run_segment("fwd")
@@ -805,7 +948,8 @@ class GrainRollout:
         return keep
 
     def _spec_launch(self, n: int):
-        """Enqueue `n` speculative steps from the current slot on; returns (their slots, the event behind them)."""
+        """Enqueue `n` speculative steps from the current slot on; returns (their slots, the event behind them, the QoI
+        accumulator the block started from or None: _qoi_enter_block)."""
         S = self._spec
         slots = [(S["cur"] + i) % S["D"] for i in range(n)]
         if S["xs_valid"] != slots[0]:   # the first step's copy of x (later ones get theirs from the refresh before them)
@@ -813,6 +957,7 @@ class GrainRollout:
                 S["xs"][slots[0]][nt].copy_(self.x[nt])
         S["xs_valid"] = (slots[-1] + 1) % S["D"]
         self._xc_fresh = False
+        entry = self._qoi_enter_block(slots)
         if self.use_graph and n > 1:
             g = S["graphs"].get((slots[0], n))
             if g is None:
@@ -826,7 +971,7 @@ class GrainRollout:
         done.record()
         self._spec_adopt(slots[-1])
         self._einfo_fresh = True   # (the last step's refresh prepared the records of the step to come)
-        return slots, done
+        return slots, done, entry
 
     def _spec_adopt(self, slot: int):
         """The rollout's current buffers := the state behind the step of `slot`."""
@@ -879,7 +1024,7 @@ class GrainRollout:
                 if len(blocks) < 2 and len(ev_out) + in_flight + len(blocks[-1][0]) < n_steps:
                     continue   # keep one block queued behind the one whose counts are read
             S = self._spec
-            slots, done = blocks.pop(0)
+            slots, done, entry = blocks.pop(0)
             done.synchronize()
             hit = next((i for i, sl in enumerate(slots) if int(S["evh"][sl][0]) or int(S["evh"][sl][1])), None)
             # the fp16-range reports of the steps that stand (a void step ran on a topology the trajectory never had)
@@ -909,6 +1054,8 @@ class GrainRollout:
                 self._spec_adopt(slot)
                 # the void steps refreshed the edge sets past this point: lengths and records are recomputed from x below
                 self._einfo_fresh = False
+            if self._qoi is not None:   # the accumulator as the eventful step found it: its layer is computed again
+                self._qoi_take(self._qoi["ring"][slots[hit - 1]] if hit else entry)
             keep_centres = self.x["grain"][:, :2].clone()
             self.x["grain"][:, :2].copy_(S["cen"][slot])     # the centres the events must see: before the refresh
             if self.noflux:   # ... and the junctions: before the boundary step
@@ -916,6 +1063,8 @@ class GrainRollout:
                 self.x["joint"][:, :2].copy_(S["jb"][slot])
             def stands():   # the step stands as enqueued (its refresh ran on the unchanged topology)
                 self.x["grain"][:, :2].copy_(keep_centres)
+                if self._qoi is not None:
+                    self._qoi_take(self._qoi["ring"][slot])
                 if self.noflux:
                     self.x["joint"][:, :2].copy_(keep_joints)
                 if void:   # ... but its edge lengths were overwritten by the void steps: the same kernel on the same x
@@ -1080,6 +1229,7 @@ class GrainRollout:
         """Advance one rollout step; returns the prediction dict (tensors are reused)."""
         if self.steps_done % 16 == 0:
             self.refresh_weights()
+        self._qoi_home()
         if self._pipelined():
             self._ensure_edge_records()
         if self.use_graph:
@@ -1097,6 +1247,7 @@ class GrainRollout:
         """`n_steps` static-topology steps.  With hipGraph replay the bulk goes through a graph of
         RUN_UNROLL consecutive steps (same kernels, same order, same results as step() x n)."""
         self.refresh_weights()
+        self._qoi_home()
         if self.use_graph and n_steps >= self.RUN_UNROLL:
             if self._pipelined():
                 self._ensure_edge_records()

@@ -628,6 +628,60 @@ int ggnn_detect_events(const float* grain_area, const int32_t* live_grain, int64
 int ggnn_noflux_boundary(const int32_t* rowptr_jg, const int32_t* col_jg, float* x_joint, int64_t n_joint,
                          int64_t ldx_joint, const float* domain_offset, float domain_factor, float max_y,
                          float* x_grain, int64_t ldx_grain, int f_grain, float* joints_before, ggnn_stream_t stream);
+/* --- Quantities of interest of a rollout (graph_trajectory.py:1042-1051 GNN_update "qoi", :221-242 volume('graph'),
+ * :244-256 qoi) ---
+ * Per trajectory t = grains [traj_offsets[t], traj_offsets[t+1]) of a disjoint-union graph, with F = domain_factor,
+ * s = patch_size / mesh_size + 1, live = live_grain > 0 (NULL: every grain):
+ *   A_k    = sum_g live * x_grain[g, 3] / F^2
+ *   a_k[g] = live ? x_grain[g, 3] * s^2 / A_k : 0        (a trajectory without a live grain: all zeros, no division)
+ *   e_k[g] = live ? x_grain[g, 4] / 20 * s^3 : 0
+ *   T_k    = T_{k-1} + delta_h / 2 * (a_{k-1} + a_k)     (delta_h = span * (final_height - ini_height) / mesh_size / (frames - 1))
+ *   volume_k = V0 + T_k + e_k
+ * ggnn_qoi_accumulate = ONE layer, one launch, behind the step's topology update and boundary step.  The layer index is
+ * k = *layer_in + 1, read from device memory when the kernel runs, and the launch leaves k in *layer_out: a captured
+ * graph replays with the counter where the replay before left it.  layer_in / layer_out, a_prev / a_cur and T_in / T_out
+ * may be the same buffers (every element is read and written by one thread; the counter is advanced by the last block to
+ * finish, through sync_word) or different ones (the speculative event loop keeps one state per ring slot).
+ * init != 0 = layer 0: k = 0, a_0 by the formula above or copied from area0 (the reference keeps the rasterised pixel
+ * counts there, test.py:340), V0 = 4 / (3 sqrt(pi)) a_0^1.5 is WRITTEN, T_0 = 0, history row 0 = V0.
+ * history: NULL, or [capacity + 1, n_grain]: row k = volume_k.  A layer k > capacity writes no row and ORs
+ * GGNN_FLAG_QOI_OVERFLOW into *flags; a_cur / T_out / e_cur are still advanced.  Nothing outside the arrays is addressed
+ * for any traj_offsets (entries are clamped to [0, n_grain]).
+ * Arithmetic: fp64 per grain and in the sums, rounded to fp32 where stored.  A_k is a tree of fixed shape over the
+ * trajectory's grains counted from its first one (no floating-point atomics): the results do not depend on the grid, on
+ * the launch plan or on where the trajectory sits in a union, bit for bit.  Inputs must be finite.
+ * sync_word: one zeroed int32 device word, left zero by every launch; not shared by launches that may run concurrently. */
+#define GGNN_FLAG_QOI_OVERFLOW 2  /* ggnn_qoi_accumulate: a layer beyond the history's capacity */
+typedef struct ggnn_qoi_args {
+  const float* x_grain;         /* [n_grain, ldx_grain >= 5]: column 3 area, column 4 excess volume */
+  const int32_t* live_grain;    /* [n_grain] or NULL */
+  const int64_t* traj_offsets;  /* [n_traj + 1], device */
+  const float* area0;           /* init only: NULL or [n_grain] */
+  const float* a_prev;          /* [n_grain] a_{k-1} */
+  const float* T_in;            /* [n_grain] T_{k-1} */
+  float* V0;                    /* [n_grain]: read; written by init */
+  float* a_cur;                 /* [n_grain] a_k */
+  float* T_out;                 /* [n_grain] T_k */
+  float* e_cur;                 /* [n_grain] e_k */
+  float* history;               /* NULL or [capacity + 1, n_grain] */
+  float* area_sum;              /* NULL or [n_traj]: A_k */
+  const int32_t* layer_in;      /* k - 1 */
+  int32_t* layer_out;           /* receives k */
+  int32_t* sync_word;
+  int32_t* flags;
+  int64_t ldx_grain, n_grain, n_traj, capacity;
+  double domain_factor, s, delta_h;
+  int32_t init, reserved;
+} ggnn_qoi_args;
+int ggnn_qoi_accumulate(const ggnn_qoi_args* args, ggnn_stream_t stream);
+/* ggnn_qoi_finalize: volume = V0 + T + e, size = cbrt(6 volume / pi) * mesh_size per grain, and per trajectory over ALL of
+ * its grains (eliminated ones included, as np.mean / np.std there): d_mu, d_std (population; two passes: the mean, then
+ * the squared deviations from it, fp64 trees of fixed shape) and hist [n_traj, n_edges - 1] = the counts of np.histogram
+ * for bin_edges ([n_edges] ascending fp32, device; half-open bins, the last one closed; sizes are compared as fp32).
+ * n_edges = 0: no histogram; at most 1025 edges. */
+int ggnn_qoi_finalize(const float* V0, const float* T, const float* e, int64_t n_grain, const int64_t* traj_offsets,
+                      int64_t n_traj, double mesh_size, const float* bin_edges, int n_edges, float* volume, float* size,
+                      float* d_mu, float* d_std, int32_t* hist, ggnn_stream_t stream);
 /* The host-side topology update those counts trigger: one call of the reference's `Cmodel.update`
  * (models.py:612-842 with delete_grain_index :861-893, switching_edge_index :896-1051, point_in_triangle :1055-1070,
  * periodic_move :1103-1106), nucleation off.  HOST memory throughout, no stream: grains of `grain_event` (those below the
