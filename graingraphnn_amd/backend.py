@@ -1115,6 +1115,32 @@ class HipBackend:
                                           edge_index_jj.size(1), ptr(E_dev), float(logit_threshold), ptr(flags),
                                           ptr(range_word), int(skip_grain), _lib.current_stream()), "ggnn_detect_events")
 
+    def detect_events_traj(self, grain_area, live_grain, area_threshold, edge_event, edge_index_jj, logit_threshold,
+                           traj_grain_off, traj_joint_off, counts, flags, ended=None, range_word=None, E_dev=None,
+                           skip_local_grain=-1):
+        """detect_events for a disjoint union (ggnn_detect_events_traj, see ggnn.h): traj_grain_off / traj_joint_off int64
+        [n_traj + 1] on the device; counts int32 [n_traj, 2] <- (grain, switch) candidates per trajectory; flags[0:2] <- their
+        totals; ended: int32 [n_traj] or None, a non-zero word keeps a trajectory's candidates out of both."""
+        _require_cuda(grain_area, live_grain, edge_event, edge_index_jj, traj_grain_off, traj_joint_off, counts, flags, ended,
+                      range_word, E_dev)
+        n_traj = traj_grain_off.numel() - 1
+        for off in (traj_grain_off, traj_joint_off):
+            if off.dtype != torch.int64 or off.numel() != n_traj + 1 or n_traj < 1 or not off.is_contiguous():
+                raise _lib.GGNNError("traj_grain_off / traj_joint_off must be contiguous int64 [n_traj + 1]")
+        if live_grain.dtype != torch.int32 or flags.dtype != torch.int32 or flags.numel() < (2 if range_word is None else 3):
+            raise _lib.GGNNError("live_grain / flags must be int32 (flags: two words, three with a range word)")
+        if counts.dtype != torch.int32 or counts.numel() != 2 * n_traj or not counts.is_contiguous():
+            raise _lib.GGNNError("counts must be a contiguous int32 [n_traj, 2]")
+        if ended is not None and (ended.dtype != torch.int32 or ended.numel() != n_traj or not ended.is_contiguous()):
+            raise _lib.GGNNError("ended must be a contiguous int32 [n_traj]")
+        if range_word is not None and (range_word.dtype != torch.int32 or range_word.numel() < 1):
+            raise _lib.GGNNError("range_word must be an int32 word")
+        check(self.lib.ggnn_detect_events_traj(ptr(grain_area), ptr(live_grain), grain_area.numel(), float(area_threshold),
+                                               ptr(edge_event), ptr(edge_index_jj), edge_index_jj.size(1), ptr(E_dev),
+                                               float(logit_threshold), ptr(traj_grain_off), ptr(traj_joint_off), n_traj,
+                                               ptr(ended), int(skip_local_grain), ptr(counts), ptr(flags), ptr(range_word),
+                                               _lib.current_stream()), "ggnn_detect_events_traj")
+
     def step_refresh(self, x_joint, x_grain, zmax, flags, edges):
         """edges: list of (edge_index [2,E] int64, x_src, x_dst, edge_attr_out [E][, E_dev int64 [1] or None])."""
         _require_cuda(x_joint, x_grain, flags)

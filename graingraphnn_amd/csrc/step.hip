@@ -126,6 +126,73 @@ __global__ __launch_bounds__(256) void detect_events_kernel(
   }
 }
 
+// ggnn_detect_events for a disjoint union of trajectories: the same candidates, counted per trajectory.  A grain
+// belongs to the trajectory whose range of traj_grain_off holds it, a junction edge to the trajectory of its source junction;
+// the boundaries fall anywhere inside a wave.  Candidates are rare: a block without one leaves at once; one with candidates
+// stages the offsets in LDS while they fit (DET_LDS_TRAJ) and only its candidate lanes search them.  A wave's candidates of
+// one (trajectory, kind) go out as one pair of integer atomics: exact and order-free.
+constexpr int DET_LDS_TRAJ = 511;   // 2 x 512 offsets of 8 bytes: 8 KiB
+__global__ __launch_bounds__(256) void detect_events_traj_kernel(
+    const float* __restrict__ grain_area, const int32_t* __restrict__ live_grain, int64_t n_grain,
+    float area_threshold, const float* __restrict__ edge_event, const int64_t* __restrict__ ei_jj,
+    int64_t E_cap, const int64_t* __restrict__ E_dev, float logit_threshold,
+    const int64_t* __restrict__ traj_grain_off, const int64_t* __restrict__ traj_joint_off, int n_traj,
+    const int32_t* __restrict__ ended, int32_t* __restrict__ counts, int32_t* __restrict__ flags,
+    int32_t* __restrict__ range_word) {
+  __shared__ int64_t s_off[2][DET_LDS_TRAJ + 1];
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t E = E_dev ? *E_dev : E_cap;
+  if (range_word != nullptr && t == 0) flags[2] = atomicExch(range_word, 0);
+  bool cand = false;
+  int kind = 0;       // 0: grain, 1: junction edge
+  int64_t node = 0;   // the grain, or the edge's source junction
+  if (t < n_grain) {
+    cand = live_grain[t] > 0 && grain_area[t] < area_threshold;
+    node = t;
+  } else if (t - n_grain < E) {
+    const int64_t k = t - n_grain;
+    node = ei_jj[k];
+    cand = edge_event[k] > logit_threshold && node < ei_jj[E + k];
+    kind = 1;
+  }
+  if (!__syncthreads_or(cand)) return;   // (uniform over the block: nobody waits at the barrier below)
+  const bool staged = n_traj <= DET_LDS_TRAJ;
+  if (staged) {
+    for (int i = threadIdx.x; i <= n_traj; i += 256) {
+      s_off[0][i] = traj_grain_off[i];
+      s_off[1][i] = traj_joint_off[i];
+    }
+    __syncthreads();
+  }
+  int key = 0;   // 2 x trajectory + kind: the candidate's word of counts [n_traj, 2]
+  if (cand) {
+    // the last trajectory whose offset is <= node (offsets rise from 0; equal ones are empty trajectories): any node lands
+    // inside [0, n_traj)
+    const int64_t* off = staged ? s_off[kind] : (kind ? traj_joint_off : traj_grain_off);
+    int lo = 0, hi = n_traj;
+    while (hi - lo > 1) {
+      const int mid = lo + ((hi - lo) >> 1);
+      if (off[mid] <= node) lo = mid;
+      else hi = mid;
+    }
+    if (ended != nullptr && ended[lo] != 0) cand = false;
+    key = 2 * lo + kind;
+  }
+  const int lane = threadIdx.x & 63;
+  unsigned long long todo = __ballot(cand);
+  while (todo) {   // (wave-uniform)
+    const int lead = __ffsll(todo) - 1;
+    const int lead_key = __shfl(key, lead);
+    const unsigned long long same = __ballot(cand && key == lead_key);
+    if (lane == lead) {
+      const int n = __popcll(same);
+      atomicAdd(&counts[lead_key], n);
+      atomicAdd(&flags[lead_key & 1], n);
+    }
+    todo &= ~same;
+  }
+}
+
 // The no-flux boundary step (test.py:446-463): one thread per junction.  Whether a junction is one of grain 0's (row 0 of
 // the full joint->grain CSR, a few dozen to a few hundred junctions on the walls) is looked up in LDS, one chunk of the
 // row at a time.  Every fp32 operation is rounded on its own, in the reference's order: torch evaluates
@@ -301,6 +368,33 @@ extern "C" int ggnn_detect_events(const float* grain_area, const int32_t* live_g
   hipLaunchKernelGGL(detect_events_kernel, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream,
                      grain_area, live_grain, n_grain, area_threshold, edge_event, edge_index_jj, E, E_dev,
                      logit_threshold, flags, range_word, skip_grain);
+  return launch_status();
+}
+
+extern "C" int ggnn_detect_events_traj(const float* grain_area, const int32_t* live_grain, int64_t n_grain,
+                                       float area_threshold, const float* edge_event, const int64_t* edge_index_jj,
+                                       int64_t E, const int64_t* E_dev, float logit_threshold,
+                                       const int64_t* traj_grain_off, const int64_t* traj_joint_off, int64_t n_traj,
+                                       const int32_t* ended, int64_t skip_local_grain, int32_t* counts, int32_t* flags,
+                                       int32_t* range_word, ggnn_stream_t stream) {
+  using namespace ggnn;
+  if (!grain_area || !live_grain || !flags || !counts || n_grain <= 0 || E < 0) return GGNN_EINVAL;
+  if (E > 0 && (!edge_event || !edge_index_jj)) return GGNN_EINVAL;
+  if (!traj_grain_off || !traj_joint_off || n_traj < 1 || n_traj > (1 << 29)) return GGNN_EINVAL;
+  if (skip_local_grain != -1) return GGNN_EINVAL;   // (no-flux unions: not yet)
+  const int64_t nblk = (n_grain + E + 255) / 256;
+  if (nblk >= INT32_MAX) return GGNN_EINVAL;
+  const hipStream_t s = (hipStream_t)stream;
+  const size_t n_flags = range_word ? 3 : 2, n_counts = 2 * (size_t)n_traj;
+  if (counts == flags + n_flags) {   // one buffer, the totals first: one memset
+    if (hipMemsetAsync(flags, 0, (n_flags + n_counts) * sizeof(int32_t), s) != hipSuccess) return GGNN_ELAUNCH;
+  } else {
+    if (hipMemsetAsync(flags, 0, n_flags * sizeof(int32_t), s) != hipSuccess) return GGNN_ELAUNCH;
+    if (hipMemsetAsync(counts, 0, n_counts * sizeof(int32_t), s) != hipSuccess) return GGNN_ELAUNCH;
+  }
+  hipLaunchKernelGGL(detect_events_traj_kernel, dim3((unsigned)nblk), dim3(256), 0, s, grain_area, live_grain, n_grain,
+                     area_threshold, edge_event, edge_index_jj, E, E_dev, logit_threshold, traj_grain_off, traj_joint_off,
+                     (int)n_traj, ended, counts, flags, range_word);
   return launch_status();
 }
 

@@ -5,6 +5,7 @@ results at the end.  The reference's only parallel code i
 (dist_train.py:76-93); inference there is single-process."""
 from typing import Callable, Dict, List
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -144,7 +145,7 @@ def run_sharded(n_traj: int, run_one: Callable[[int], torch.Tensor], rank: int, 
 
 def rollout_trajectories(rmodel, cmodel, graphs, span: int, n_steps: int, rank: int = 0,
                          world: int = 1, device="cuda", use_graph: bool = True,
-                         refresh_centres: bool = False, qoi=None):
+                         refresh_centres: bool = False, qoi=None, events=None):
     """BASELINE config 4: `graphs[t]` = (x, ei, ea) numpy dicts of independent trajectories with
     EQUAL node counts.  Rank r rolls out trajectories t = r (mod world) as ONE disjoint-union
     graph on its GPU (one set of launches for the whole shard), then all ranks all-gather the
@@ -153,7 +154,12 @@ def rollout_trajectories(rmodel, cmodel, graphs, span: int, n_steps: int, rank: 
     recompute the grain centres every step (unfolded domains: factor 1), as `GrainRollout` does.
     `qoi`: the keywords of GrainRollout.enable_qoi (patch_size, mesh_size, ini_height, final_height, ...; the union's
     trajectory offsets are filled in): every trajectory's grain volumes and equivalent diameters are accumulated on the
-    device during the rollout and travel with the states, 'volume' and 'size' [T, N_g]."""
+    device during the rollout and travel with the states, 'volume' and 'size' [T, N_g].
+    `events`: None (static topology), or {'area_threshold', 'edge_threshold'[, 'mask': per trajectory a dict of 'grain' and
+    'joint' masks, default all ones]}: the shard's union runs n_steps of step_events() with events PER TRAJECTORY
+    (GrainRollout.enable_events(traj_offsets=...)); a trajectory whose update is refused ends with the state of that
+    moment, the others go on.  Every trajectory's row then also carries 'grain_live' [T, N_g], 'joint_live' [T, N_j],
+    'ended_at' [T] (-1: it ran to the end) and 'n_eliminated' [T], small integers as float32 in the same packed gather."""
     from . import synthetic
     from .rollout import GrainRollout
 
@@ -163,11 +169,35 @@ def rollout_trajectories(rmodel, cmodel, graphs, span: int, n_steps: int, rank: 
     X, EI, EA = synthetic.to_torch(x, ei, ea, device)
     ro = GrainRollout(rmodel, cmodel, X, EI, EA, span, use_graph=use_graph, refresh_centres=refresh_centres)
     grains = [s["grain"] for s in slices]
+    if events is not None:
+        joints = [s["joint"] for s in slices]
+        ones = lambda n: np.ones((n, 1), np.int64)
+        masks = events.get("mask")
+        if masks is None:
+            mask = {"grain": ones(grains[-1][1]), "joint": ones(joints[-1][1])}
+        else:
+            mask = {k: np.concatenate([np.asarray(masks[t][k], np.int64).reshape(-1, 1) for t in mine]) for k in ("grain", "joint")}
+        live0 = [int((mask["grain"][lo:hi] > 0).sum()) for lo, hi in grains]
+        ro.enable_events(mask, events["area_threshold"], events["edge_threshold"],
+                         traj_offsets={"grain": [lo for lo, _ in grains] + [grains[-1][1]],
+                                       "joint": [lo for lo, _ in joints] + [joints[-1][1]]})
     if qoi is not None:
         ro.enable_qoi(**dict(qoi, traj_offsets=[lo for lo, _ in grains] + [grains[-1][1]]))
-    ro.run(n_steps)
-    local = {"joint_xy": torch.stack([X["joint"][lo:hi, :2] for lo, hi in (s["joint"] for s in slices)]),
-             "grain_area_v": torch.stack([X["grain"][lo:hi, 3:5] for lo, hi in grains])}
+    if events is None:
+        ro.run(n_steps)
+        local = {"joint_xy": torch.stack([X["joint"][lo:hi, :2] for lo, hi in (s["joint"] for s in slices)]),
+                 "grain_area_v": torch.stack([X["grain"][lo:hi, 3:5] for lo, hi in grains])}
+    else:
+        for _ in range(n_steps):
+            ro.step_events()
+        states = ro.trajectory_states()
+        f32 = lambda a: torch.as_tensor(np.asarray(a, dtype=np.float32), device=X["joint"].device)
+        local = {"joint_xy": torch.stack([st["x_joint"][:, :2] for st in states]),
+                 "grain_area_v": torch.stack([st["x_grain"][:, 3:5] for st in states]),
+                 "grain_live": f32([(st["mask"]["grain"][:, 0] > 0) for st in states]),
+                 "joint_live": f32([(st["mask"]["joint"][:, 0] > 0) for st in states]),
+                 "ended_at": f32([[-1 if st["ended_at"] is None else st["ended_at"]] for st in states]),
+                 "n_eliminated": f32([[n0 - int((st["mask"]["grain"] > 0).sum())] for n0, st in zip(live0, states)])}
     if qoi is not None:
         q = ro.qoi()
         for k in ("volume", "size"):
@@ -182,4 +212,7 @@ def rollout_trajectories(rmodel, cmodel, graphs, span: int, n_steps: int, rank: 
         n = local[k][0].numel()
         out[k] = gathered[:, at:at + n].reshape((len(graphs),) + tuple(local[k].shape[1:]))
         at += n
+    for k in ("ended_at", "n_eliminated"):
+        if k in out:
+            out[k] = out[k].reshape(len(graphs))
     return out

@@ -74,6 +74,7 @@ class GrainRollout:
         self._range_hit = False               # an fp16-range report of a step run_events committed (range_exceeded)
         self._evb = None                      # pinned staging of the event round trip (_event_buffers)
         self._topo = None                     # (session, its jj list, its jg list, their versions): _topology_session
+        self._ens = None                      # enable_events(traj_offsets=...): the per-trajectory event layer (_enable_ensemble)
         self._xc = self._xc_other = None      # the classifier's two alternating copies of x (_overlap_buffers)
         self._xc_fresh = False
         self._graphs = None                   # run() / step() graphs per (steps, buffers): _replay
@@ -454,13 +455,26 @@ class GrainRollout:
         (floats, over all grains, eliminated ones included, population std), `hist` (np.histogram(size, np.arange(0, 20,
         1 if n_grain > 400 else 2), density=True)), `hist_counts`, `bin_centres`, `layers` (steps accumulated) and, with a
         history, `volume_traj` [layers + 1, n_grain].  With traj_offsets: `d_mu` / `d_std` arrays and `hist` / `hist_counts` /
-        `bin_centres` lists, one entry per trajectory.  Raises when a layer went beyond the history's capacity."""
+        `bin_centres` lists, one entry per trajectory.  With enable_events(traj_offsets=...): `layers` is an array, one
+        entry per trajectory, and a trajectory that ended (trajectory_states) reports the volumes, sizes and layers of its
+        last completed step; `volume_traj` keeps the union's rows.  Raises when a layer went beyond the history's capacity."""
         Q = self._qoi
         if Q is None:
             raise _lib.GGNNError("call enable_qoi(...) first")
         self._qoi_home()
         H = Q["home"]
-        words = torch.cat([H["layer"], Q["words"][1:]]).cpu()
+        T, e, ended = H["T"], H["e"], []
+        if self._ens is not None:
+            # a trajectory that ended keeps the accumulator rows and the layer count of its last completed step: patched into
+            # a copy (one block per trajectory, position-independent: the finalize launch below sees nothing else of it)
+            ens = self._ens["sessions"]
+            ended = [(t, sn["qoi"]) for t, sn in enumerate(self._ens["snapshot"]) if sn is not None and sn["qoi"] is not None]
+            if ended:
+                T, e = T.clone(), e.clone()
+                for t, q in ended:
+                    g0, g1 = int(ens.grain_off[t]), int(ens.grain_off[t + 1])
+                    T[g0:g1], e[g0:g1] = q["T"], q["e"]
+        words = torch.cat([H["layer"], Q["words"][1:]] + [q["layer"] for _, q in ended]).cpu()
         layers = int(words[0])
         if int(words[1]) & _lib.GGNN_FLAG_QOI_OVERFLOW:
             raise _lib.GGNNError(f"the volume history has room for {Q['capacity']} layers, {layers} were accumulated: "
@@ -470,7 +484,7 @@ class GrainRollout:
         out, hist, counts, centres = None, [None] * len(steps), [None] * len(steps), [None] * len(steps)
         for step in sorted(set(steps)):
             edges = np.arange(0, 20, step).astype(np.float32)
-            out = self.be.qoi_finalize(Q["V0"], H["T"], H["e"], Q["offsets"], Q["mesh_size"], torch.from_numpy(edges).to(dev))
+            out = self.be.qoi_finalize(Q["V0"], T, e, Q["offsets"], Q["mesh_size"], torch.from_numpy(edges).to(dev))
             c = out[4].cpu().numpy().astype(np.int64)
             for t, st in enumerate(steps):
                 if st == step:
@@ -484,6 +498,11 @@ class GrainRollout:
                "hist_counts": counts[0] if one else counts, "bin_centres": centres[0] if one else centres, "layers": layers}
         if Q["history"] is not None:
             res["volume_traj"] = Q["history"][:layers + 1]
+        if self._ens is not None:   # per trajectory of the event layer: an ended one stopped counting
+            per = np.full(self._ens["n_traj"], layers, dtype=np.int64)
+            for k, (t, _) in enumerate(ended):
+                per[t] = int(words[2 + k])
+            res["layers"] = per
         return res
 
     # -- one step, enqueued on the current stream --------------------------------------
@@ -731,13 +750,21 @@ class GrainRollout:
             self._x_written_outside()
 
     # -- event-driven mode ------------------------------------------------
-    def enable_events(self, mask, area_threshold: float = 1e-4, edge_threshold: float = 0.6):
+    def enable_events(self, mask, area_threshold: float = 1e-4, edge_threshold: float = 0.6, traj_offsets=None):
         """Switch to the full loop of test.py:382-575: after the device forwards + Rmodel.update,
         grains whose predicted area fell below `area_threshold` (Rmodel.threshold, test.py:187,
         418) are eliminated and junction edges with sigmoid(edge_event) above `edge_threshold`
         (Cmodel.threshold, :188) are switched by the host-side `topology.update_topology`; then
         grain centres and edge lengths are refreshed on the NEW topology.  `mask` = the
-        reference's `data['mask']` ({'grain': [N_g, 1], 'joint': [N_j, 1]}, any integer dtype)."""
+        reference's `data['mask']` ({'grain': [N_g, 1], 'joint': [N_j, 1]}, any integer dtype).
+        traj_offsets: None, or {'grain': [n_traj + 1], 'joint': [n_traj + 1]} -- the graph is a disjoint union of
+        trajectories (node offsets rising from 0 to the node counts, as in enable_qoi) and the events are detected, applied
+        and refused PER TRAJECTORY: a trajectory whose update is refused ends, the others go on
+        (trajectory_states)."""
+        if traj_offsets is not None and self.noflux:
+            raise _lib.GGNNError("enable_events(traj_offsets=...) with boundary='noflux' is not supported: the boundary step "
+                                 "knows one boundary grain")
+        ens = None if traj_offsets is None else self._ensemble_sessions(traj_offsets)
         self.mask = {k: np.array(torch.as_tensor(mask[k]).cpu().numpy(), dtype=np.int64, copy=True).reshape(-1, 1)
                      for k in ("grain", "joint")}
         dev = self.x["joint"].device
@@ -754,6 +781,90 @@ class GrainRollout:
             self._graphs = None
         self.grain_events, self.switched = [], []
         self._enter_capacity_mode()
+        self._ens = None
+        if ens is not None:
+            self._enable_ensemble(ens)
+
+    # -- events per trajectory of a disjoint union --------------------------------------------------------------
+    def _ensemble_sessions(self, traj_offsets):
+        """One topology session per trajectory from the current lists (one read-back); GGNNError unless they are a disjoint
+        union with the segments in trajectory order."""
+        from .topology import EnsembleSessions, check_traj_offsets, union_edge_segments
+        og, oj = check_traj_offsets(traj_offsets, self.n_nodes["grain"], self.n_nodes["joint"])
+        union_edge_segments(self.edge_index[GJ].cpu().numpy(), og, oj, "grain-junction list")
+        return EnsembleSessions(self.edge_index[ET_JJ].cpu().numpy(), self.edge_index[JG].cpu().numpy(), og, oj)
+
+    def _enable_ensemble(self, ens):
+        """The device side of the per-trajectory layer: the offsets, the `ended` words and ONE buffer of 2 + 2 n_traj count
+        words (totals first: step_events reads them as it reads the two words of a single trajectory)."""
+        dev, n = self.x["joint"].device, ens.n_traj
+        self._ev_flags = torch.zeros(2 + 2 * n, dtype=torch.int32, device=dev)
+        self._ev_host = torch.zeros(2 + 2 * n, dtype=torch.int32).pin_memory()
+        self._ens = {
+            "sessions": ens, "n_traj": n, "grain_off": torch.from_numpy(ens.grain_off).to(dev),
+            "joint_off": torch.from_numpy(ens.joint_off).to(dev), "ended": torch.zeros(n, dtype=torch.int32, device=dev),
+            "ended_host": torch.zeros(n, dtype=torch.int32).pin_memory(), "ended_at": [None] * n, "error": [None] * n,
+            "snapshot": [None] * n, "rewired": 0}
+
+    def _rewire_union(self):
+        """_rewire for a union: every trajectory with candidates gets its own update from its own session
+        (topology.EnsembleSessions.apply); a refused one ends (_end_trajectory).  Same return value."""
+        E, N = self._ens, self._evb["np"]
+        ens, n_e = E["sessions"], self.edge_index[ET_JJ].size(1)
+        if ens.n_pp != n_e:
+            raise _lib.GGNNError("the topology sessions and the rollout's junction edge list disagree")
+        mg, mj = self.mask["grain"], self.mask["joint"]
+        if not (mg.dtype == np.int64 and mg.flags.c_contiguous and mj.dtype == np.int64 and mj.flags.c_contiguous):
+            mg, mj = self.mask["grain"], self.mask["joint"] = np.ascontiguousarray(mg, np.int64), np.ascontiguousarray(mj, np.int64)
+        E["rewired"] += 1
+        ended = E["ended_host"].numpy()
+        res = ens.apply(N["xj"], N["yj"], N["yg"][:, 0], N["prob"][:n_e], N["area"], mg, mj, self._ev_host.numpy()[2:], ended,
+                        self.area_threshold, self.edge_threshold, N["lists"])
+        for t, message in res["refused"].items():
+            self._end_trajectory(t, message)
+        if res["refused"]:
+            E["ended"].copy_(E["ended_host"], non_blocking=True)
+        if not res["changed"]:
+            return None
+        return res["events"], res["switches"], res["n_pp"], res["n_pq"]
+
+    def _end_trajectory(self, t, message):
+        """Trajectory t's update was refused: it takes part in no events from now on, and what its own rollout would hold
+        where its step_events() raised -- features updated, topology and masks untouched, the accumulator of the layers
+        completed so far -- is kept (device-side copies, ordered before anything that overwrites the rows)."""
+        E = self._ens
+        ens = E["sessions"]
+        g0, g1, j0, j1 = (int(v) for v in (ens.grain_off[t], ens.grain_off[t + 1], ens.joint_off[t], ens.joint_off[t + 1]))
+        snap = {"x_joint": self.x["joint"][j0:j1].clone(), "x_grain": self.x["grain"][g0:g1].clone(),
+                "mask": {"grain": self.mask["grain"][g0:g1].copy(), "joint": self.mask["joint"][j0:j1].copy()},
+                "edge_index": ens.local_lists(t), "steps": self.steps_done, "qoi": None}
+        if self._qoi is not None:
+            H = self._qoi["home"]
+            snap["qoi"] = {"T": H["T"][g0:g1].clone(), "e": H["e"][g0:g1].clone(), "a": H["a"][g0:g1].clone(),
+                           "layer": H["layer"].clone()}
+        E["snapshot"][t], E["ended_at"][t], E["error"][t] = snap, self.steps_done, message
+        E["ended_host"][t] = 1
+
+    def trajectory_states(self):
+        """Per trajectory of enable_events(traj_offsets=...): a list of dicts with `x_joint`, `x_grain` (device tensors),
+        `mask` ({'grain', 'joint'}: int64 [n, 1]), `edge_index` (the three lists in the trajectory's own indices, numpy),
+        `ended_at` (the number of steps it completed when its update was refused; None while it runs) and `error` (the
+        refusal's message).  A running trajectory: views of its live rows; an ended one: what its own rollout held when its
+        step_events() raised."""
+        E = self._ens
+        if E is None:
+            raise _lib.GGNNError("call enable_events(mask, ..., traj_offsets=...) first")
+        ens, out = E["sessions"], []
+        for t in range(E["n_traj"]):
+            snap = E["snapshot"][t]
+            if snap is None:
+                g0, g1, j0, j1 = (int(v) for v in (ens.grain_off[t], ens.grain_off[t + 1], ens.joint_off[t], ens.joint_off[t + 1]))
+                snap = {"x_joint": self.x["joint"][j0:j1], "x_grain": self.x["grain"][g0:g1],
+                        "mask": {"grain": self.mask["grain"][g0:g1].copy(), "joint": self.mask["joint"][j0:j1].copy()},
+                        "edge_index": ens.local_lists(t)}
+            out.append({"x_joint": snap["x_joint"], "x_grain": snap["x_grain"], "mask": snap["mask"],
+                        "edge_index": snap["edge_index"], "ended_at": E["ended_at"][t], "error": E["error"][t]})
+        return out
 
     def _skip_grain(self):
         """The grain that never takes part in events: the no-flux boundary grain (test.py:421-422), or none."""
@@ -811,8 +922,14 @@ class GrainRollout:
         self._x_written_outside()
         self._run_segment("fwd")
         p = self.pred
-        self.be.detect_events(p["grain_area"], self._live_grain, self.area_threshold, p["edge_event"],
-                              self.graph.edge_index[ET_JJ], self._logit_trigger, self._ev_flags, skip_grain=self._skip_grain())
+        if self._ens is None:
+            self.be.detect_events(p["grain_area"], self._live_grain, self.area_threshold, p["edge_event"],
+                                  self.graph.edge_index[ET_JJ], self._logit_trigger, self._ev_flags, skip_grain=self._skip_grain())
+        else:   # per trajectory: [2 + 2 n_traj] words, the totals over the running trajectories first
+            E = self._ens
+            self.be.detect_events_traj(p["grain_area"], self._live_grain, self.area_threshold, p["edge_event"],
+                                       self.graph.edge_index[ET_JJ], self._logit_trigger, E["grain_off"], E["joint_off"],
+                                       self._ev_flags[2:], self._ev_flags[:2], ended=E["ended"])
         self._ev_host.copy_(self._ev_flags, non_blocking=True)
         # behind an eventful step the next one is eventful too, on the reference's trajectories (README.md:68-69: events at
         # nearly every step): what the rewiring reads travels to the host behind the counts, one synchronisation instead of two
@@ -996,6 +1113,9 @@ class GrainRollout:
         concurrent=True); otherwise runs step_events in a loop.  Returns (grain_events, switching_lists): one entry per step."""
         if self.mask is None:
             raise _lib.GGNNError("call enable_events(mask, ...) first")
+        if self._ens is not None:
+            raise _lib.GGNNError("run_events() does not run on a union with traj_offsets (nearly every union step is "
+                                 "eventful: speculation buys nothing); call step_events()")
         if not self._pipelined():
             out = [self.step_events()[1:] for _ in range(n_steps)]
             return [e for e, _ in out], [sw for _, sw in out]
@@ -1146,7 +1266,7 @@ class GrainRollout:
         CSR tables are rebuilt without a read-back (_install_event_topology) -- the host returns to enqueueing the next step
         while the device is still uploading (profiles/r6_event_step_breakdown.txt).  Returns (grain events, switched edges)."""
         self._read_back_events(payload_ready)
-        rewired = self._rewire(self._grain_candidates())
+        rewired = self._rewire(self._grain_candidates()) if self._ens is None else self._rewire_union()
         if rewired is None:
             return np.zeros(0, np.int64), np.zeros((0, 2), np.int64)
         events, switches, n_pp, n_pq = rewired

@@ -152,22 +152,172 @@ class TopologySession:
         events = np.concatenate([ge, self._extra[:A.n_extra]]) if A.n_extra else ge
         return events, self._switching[:A.n_switching].copy()
 
-    def export(self, pp: Optional[np.ndarray] = None, pq: Optional[np.ndarray] = None, qp: Optional[np.ndarray] = None):
+    def export(self, pp: Optional[np.ndarray] = None, pq: Optional[np.ndarray] = None, qp: Optional[np.ndarray] = None,
+               at: Sequence[int] = (0, 0)):
         """The current lists into int64 arrays [2, >= n] whose rows are contiguous (row stride = shape[1] elements); with
-        no arguments: three fresh arrays (ei_jj [2, n_pp], ei_jg [2, n_pq], ei_gj [2, n_pq])."""
+        no arguments: three fresh arrays (ei_jj [2, n_pp], ei_jg [2, n_pq], ei_gj [2, n_pq]).  `at` = (first column of pp's
+        window, first column of pq's and qp's): the lists land in a column window of a wider array (a union's lists)."""
         fresh = pp is None and pq is None and qp is None
         if fresh:
             pp = np.empty((2, self.n_pp), np.int64)
             pq = np.empty((2, self.n_pq), np.int64)
             qp = np.empty((2, self.n_pq), np.int64)
-        for a, n in ((pp, self.n_pp), (pq, self.n_pq), (qp, self.n_pq)):
-            if a is not None and (a.dtype != np.int64 or a.ndim != 2 or a.shape[0] != 2 or a.shape[1] < n
+        at_pp, at_pq = int(at[0]), int(at[1])
+        for a, n, lo in ((pp, self.n_pp, at_pp), (pq, self.n_pq, at_pq), (qp, self.n_pq, at_pq)):
+            if a is not None and (a.dtype != np.int64 or a.ndim != 2 or a.shape[0] != 2 or lo < 0 or a.shape[1] < lo + n
                                   or not a.flags.c_contiguous):
                 raise ValueError("export targets must be C-contiguous int64 arrays [2, >= n]")
         ld = lambda a: 0 if a is None else a.shape[1]
-        _lib.check(self._lib.ggnn_topology_export(self._h, _p(pp), ld(pp), _p(pq), ld(pq), _p(qp), ld(qp)),
-                   "ggnn_topology_export")
+        win = lambda a, lo: None if a is None else ctypes.c_void_p(a.ctypes.data + 8 * lo)
+        _lib.check(self._lib.ggnn_topology_export(self._h, win(pp, at_pp), ld(pp), win(pq, at_pq), ld(pq), win(qp, at_pq),
+                                                  ld(qp)), "ggnn_topology_export")
         return (pp, pq, qp) if fresh else None
+
+
+def union_edge_segments(edge_index, offsets_src, offsets_dst, what="edge list"):
+    """The columns of a disjoint union's edge list [2, E] per trajectory: [n_traj + 1] rising column offsets.  Raises
+    GGNNError unless every edge lies inside ONE trajectory (source in offsets_src's range t, destination in offsets_dst's
+    range t) and the segments stand in trajectory order -- what the per-trajectory event loop relies on."""
+    ei = np.asarray(edge_index, dtype=np.int64)
+    off_s, off_d = np.asarray(offsets_src, np.int64).reshape(-1), np.asarray(offsets_dst, np.int64).reshape(-1)
+    n_traj = off_s.size - 1
+    if ei.ndim != 2 or ei.shape[0] != 2:
+        raise _lib.GGNNError(f"{what}: must be [2, E]")
+    if ei.size and (ei.min() < 0 or ei[0].max() >= off_s[-1] or ei[1].max() >= off_d[-1]):
+        raise _lib.GGNNError(f"{what}: a node index is outside the union")
+    ts = np.searchsorted(off_s, ei[0], side="right") - 1
+    td = np.searchsorted(off_d, ei[1], side="right") - 1
+    bad = np.flatnonzero(ts != td)
+    if bad.size:
+        k = int(bad[0])
+        raise _lib.GGNNError(f"{what}: edge {k} ({int(ei[0, k])} -> {int(ei[1, k])}) crosses from trajectory {int(ts[k])} "
+                             f"to trajectory {int(td[k])}: not a disjoint union")
+    if (np.diff(ts) < 0).any():
+        k = int(np.flatnonzero(np.diff(ts) < 0)[0]) + 1
+        raise _lib.GGNNError(f"{what}: the segments are not in trajectory order (edge {k} of trajectory {int(ts[k])} stands "
+                             f"behind one of trajectory {int(ts[k - 1])})")
+    return np.searchsorted(ts, np.arange(n_traj + 1), side="left").astype(np.int64)
+
+
+def check_traj_offsets(traj_offsets, n_grain: int, n_joint: int):
+    """{'grain': [...], 'joint': [...]} -> two int64 arrays [n_traj + 1] rising from 0 to the node counts, or GGNNError."""
+    try:
+        og = np.asarray(traj_offsets["grain"], dtype=np.int64).reshape(-1)
+        oj = np.asarray(traj_offsets["joint"], dtype=np.int64).reshape(-1)
+    except (KeyError, TypeError, IndexError):
+        raise _lib.GGNNError("traj_offsets must be {'grain': [n_traj + 1], 'joint': [n_traj + 1]}") from None
+    for off, n, nt in ((og, n_grain, "grain"), (oj, n_joint, "joint")):
+        if off.size < 2 or off[0] != 0 or off[-1] != n or (np.diff(off) < 0).any():
+            raise _lib.GGNNError(f"traj_offsets['{nt}'] must rise from 0 to the number of {nt}s ({n})")
+    if og.size != oj.size:
+        raise _lib.GGNNError("traj_offsets: 'grain' and 'joint' must list the same number of trajectories")
+    return og, oj
+
+
+class EnsembleSessions:
+    """One TopologySession per trajectory of a disjoint-union graph: the reference's `Cmodel.update` sweeps,
+    sorts and asserts over the WHOLE lists it is given (models.py:712-757, 730), so a union's events must be applied
+    trajectory by trajectory, each on its own lists in its own (local) indices, and a refused update ends ONE trajectory.
+    The union's lists are kept as the concatenation of the trajectories' lists in trajectory order."""
+
+    def __init__(self, ei_jj: np.ndarray, ei_jg: np.ndarray, grain_offsets, joint_offsets):
+        self.grain_off = np.asarray(grain_offsets, np.int64).reshape(-1)
+        self.joint_off = np.asarray(joint_offsets, np.int64).reshape(-1)
+        self.n_traj = self.grain_off.size - 1
+        pp, pq = np.asarray(ei_jj, dtype=np.int64), np.asarray(ei_jg, dtype=np.int64)
+        seg_pp = union_edge_segments(pp, self.joint_off, self.joint_off, "junction-junction list")
+        seg_pq = union_edge_segments(pq, self.joint_off, self.grain_off, "junction-grain list")
+        self.sessions = []
+        for t in range(self.n_traj):
+            j0, g0 = self.joint_off[t], self.grain_off[t]
+            self.sessions.append(TopologySession(
+                pp[:, seg_pp[t]:seg_pp[t + 1]] - j0, pq[:, seg_pq[t]:seg_pq[t + 1]] - np.array([[j0], [g0]], np.int64),
+                int(self.joint_off[t + 1] - j0), int(self.grain_off[t + 1] - g0)))
+
+    def close(self):
+        for ses in self.sessions:
+            ses.close()
+
+    @property
+    def n_pp(self):
+        return sum(s.n_pp for s in self.sessions)
+
+    @property
+    def n_pq(self):
+        return sum(s.n_pq for s in self.sessions)
+
+    def segments(self):
+        """Column offsets [n_traj + 1] of the trajectories' segments in the union's junction and junction-grain lists."""
+        seg = lambda ns: np.concatenate([[0], np.cumsum(ns)]).astype(np.int64)
+        return seg([s.n_pp for s in self.sessions]), seg([s.n_pq for s in self.sessions])
+
+    def local_lists(self, t: int):
+        """Trajectory t's current lists in its own indices: {GJ, JG, JJ: int64 [2, n]}."""
+        pp, pq, qp = self.sessions[t].export()
+        return {GJ: qp, JG: pq, JJ: pp}
+
+    def apply(self, x_joint: np.ndarray, y_joint: np.ndarray, y_grain_area: np.ndarray, edge_prob: np.ndarray,
+              grain_area: np.ndarray, mask_grain: np.ndarray, mask_joint: np.ndarray, counts, ended, area_threshold: float,
+              threshold: float, lists: Optional[np.ndarray] = None):
+        """One update of the union.  The arrays are the union's (x_joint [N_j, >= 8], y_joint [N_j, 2] fp32 C-contiguous,
+        y_grain_area a float32 vector view [N_g] of the predicted area changes, edge_prob [n_pp] fp32, grain_area [N_g] the
+        predicted areas, the int64 masks [N, 1] or [N]); every trajectory that has not `ended` and has a non-zero row of
+        `counts` [n_traj, 2] gets its own update on its contiguous slices, in place: grain candidates = its live grains with
+        grain_area < area_threshold, smallest first (stable), as test.py:418-420 on that trajectory alone.  A TopologyError ends at that trajectory: its slices and its session stay untouched.
+        When a trajectory changed, the new union lists -- every trajectory's lists plus its node offsets, concatenated in
+        trajectory order -- are written into `lists` (flat int64: [2, n_pp] then [2, n_pq]; default: a fresh array).
+        Returns a dict: events (global grain ids: trajectory order, each trajectory's own order inside), switches
+        ([S, 2] global junction ids), changed (trajectory indices), refused ({trajectory: message}), per_traj
+        ({trajectory: (local events, local switches)}), n_pp, n_pq, lists (None when nothing changed)."""
+        counts = np.asarray(counts).reshape(self.n_traj, 2)
+        seg_pp, _ = self.segments()
+        if edge_prob.shape[0] < seg_pp[-1]:
+            raise ValueError(f"edge_prob needs one entry per junction edge of the union ({int(seg_pp[-1])})")
+        mg, mj = mask_grain.reshape(-1), mask_joint.reshape(-1)
+        if not (np.shares_memory(mg, mask_grain) and np.shares_memory(mj, mask_joint)):
+            raise ValueError("the masks must be contiguous int64 arrays (they are rewritten in place)")
+        events, switches, changed, refused, per_traj = [], [], [], {}, {}
+        thr = np.float32(area_threshold)
+        for t in range(self.n_traj):
+            if (ended is not None and ended[t]) or not counts[t].any():
+                continue
+            j0, j1, g0, g1 = self.joint_off[t], self.joint_off[t + 1], self.grain_off[t], self.grain_off[t + 1]
+            area = grain_area[g0:g1]
+            ge = np.flatnonzero((mg[g0:g1] > 0) & (area < thr))
+            ge = ge[np.argsort(area[ge], kind="stable")]
+            try:
+                ev, sw = self.sessions[t].apply(x_joint[j0:j1], y_joint[j0:j1], y_grain_area[g0:g1], edge_prob[seg_pp[t]:seg_pp[t + 1]], ge,
+                                                mg[g0:g1], mj[j0:j1], threshold)
+            except TopologyError as err:
+                refused[t] = str(err)
+                continue
+            if len(ev) == 0 and len(sw) == 0:
+                continue   # (the device-side trigger was conservative: the update was the identity)
+            changed.append(t)
+            per_traj[t] = (ev, sw)
+            events.append(ev + g0)
+            switches.append(sw + j0)
+        out = {"events": np.concatenate(events) if events else np.zeros(0, np.int64),
+               "switches": np.concatenate(switches) if switches else np.zeros((0, 2), np.int64),
+               "changed": changed, "refused": refused, "per_traj": per_traj, "n_pp": self.n_pp, "n_pq": self.n_pq,
+               "lists": None}
+        if changed:
+            out["lists"] = self.export(lists)
+        return out
+
+    def export(self, lists: Optional[np.ndarray] = None):
+        """The union's lists, global indices, trajectory order, into flat int64 `lists` ([2, n_pp] then [2, n_pq])."""
+        n_pp, n_pq = self.n_pp, self.n_pq
+        if lists is None:
+            lists = np.empty(2 * (n_pp + n_pq), np.int64)
+        pp, pq = lists[:2 * n_pp].reshape(2, n_pp), lists[2 * n_pp:2 * (n_pp + n_pq)].reshape(2, n_pq)
+        seg_pp, seg_pq = self.segments()
+        for t, ses in enumerate(self.sessions):
+            ses.export(pp, pq, at=(seg_pp[t], seg_pq[t]))
+            pp[:, seg_pp[t]:seg_pp[t + 1]] += self.joint_off[t]
+            pq[0, seg_pq[t]:seg_pq[t + 1]] += self.joint_off[t]
+            pq[1, seg_pq[t]:seg_pq[t + 1]] += self.grain_off[t]
+        return lists
 
 
 def update_topology(x_joint: np.ndarray, ei_jj: np.ndarray, ei_jg: np.ndarray, y_joint: np.ndarray,

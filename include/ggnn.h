@@ -615,6 +615,20 @@ int ggnn_detect_events(const float* grain_area, const int32_t* live_grain, int64
                                              step, so it is always below the threshold).  live_grain is not touched: the
                                              topology session reads the same mask */,
                        ggnn_stream_t stream);
+/* ggnn_detect_events for a disjoint union of n_traj trajectories (one rollout of an ensemble): the same candidates, counted
+ * per trajectory.  A grain belongs to the trajectory t with traj_grain_off[t] <= grain < traj_grain_off[t + 1], a junction
+ * edge to the trajectory of its source junction (traj_joint_off); the offsets rise from 0 to the node counts, trajectories
+ * may have any sizes.  counts [n_traj, 2] int32 = (grain candidates, switch candidates) of every trajectory whose `ended` word
+ * is 0; flags[0:2] = their totals over those trajectories, flags[2] the range word as above.  counts and flags are zeroed by
+ * the call (in one memset when counts directly follows the flag words).  Integer atomics only: exact, order-free. */
+int ggnn_detect_events_traj(const float* grain_area, const int32_t* live_grain, int64_t n_grain, float area_threshold,
+                            const float* edge_event, const int64_t* edge_index_jj, int64_t E, const int64_t* E_dev,
+                            float logit_threshold, const int64_t* traj_grain_off /* [n_traj + 1], device */,
+                            const int64_t* traj_joint_off /* [n_traj + 1], device */, int64_t n_traj,
+                            const int32_t* ended /* NULL, or [n_traj] device words: non-zero = the trajectory takes part in
+                                                    no events any more, its candidates are not counted */,
+                            int64_t skip_local_grain /* must be -1: no-flux unions are not supported yet */,
+                            int32_t* counts, int32_t* flags, int32_t* range_word, ggnn_stream_t stream);
 /* --- No-flux boundary (test.py:446-466, graph_datastruct.py:689-708 with traj.BC == 'noflux') ---
  * Grain 0 is the boundary grain that wraps the domain.
  * ggnn_noflux_boundary = the boundary step of test.py:446-463, one launch, after the topology update and before the
