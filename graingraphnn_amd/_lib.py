@@ -35,7 +35,7 @@ BC_PERIODIC, BC_NOFLUX = 0, 1   # GGNN_BC_*
 # Every symbol include/ggnn.h declares (tests/test_cabi.py checks the library exports them all).
 EXPORTED_SYMBOLS = (
     "ggnn_version", "ggnn_error_string", "ggnn_gemm_mode", "ggnn_csr_workspace_bytes", "ggnn_csr_max_units",
-    "ggnn_build_csr_batch", "ggnn_noflux_boundary",
+    "ggnn_build_csr_batch", "ggnn_build_csr_batch_traj", "ggnn_noflux_boundary", "ggnn_noflux_boundary_traj",
     "ggnn_edge_prepare", "ggnn_project_batch",
     "ggnn_period_gat_aggregate_batch", "ggnn_period_gat_aggregate_enc_batch", "ggnn_encoder_cell_batch",
     "ggnn_encoder_cell_values_batch",
@@ -162,6 +162,11 @@ class CsrMask(Structure):
 
     def __init__(self, skip_src=-1, skip_dst=-1, E_kept=None):
         super().__init__(skip_src, skip_dst, E_kept)
+
+
+class CsrUnion(Structure):
+    """Mirror of `ggnn_csr_union`: NULL = that side is not split."""
+    _fields_ = [("src_off", c_void_p), ("dst_off", c_void_p), ("n_traj", c_int64)]
 
 
 class TopologyArgs(Structure):
@@ -336,6 +341,11 @@ def _declare(lib):
     lib.ggnn_csr_max_units.argtypes = [c_int64, c_int64]
     lib.ggnn_build_csr_batch.restype = c_int
     lib.ggnn_build_csr_batch.argtypes = [POINTER(CsrArgs), POINTER(CsrMask), c_int, c_void_p]
+    lib.ggnn_build_csr_batch_traj.restype = c_int
+    lib.ggnn_build_csr_batch_traj.argtypes = [POINTER(CsrArgs), POINTER(CsrMask), POINTER(CsrUnion), c_int, c_void_p]
+    lib.ggnn_noflux_boundary_traj.restype = c_int
+    lib.ggnn_noflux_boundary_traj.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_float, c_float,
+                                              c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]
     lib.ggnn_noflux_boundary.restype = c_int
     lib.ggnn_noflux_boundary.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_float, c_float,
                                          c_void_p, c_int64, c_int, c_void_p, c_void_p]

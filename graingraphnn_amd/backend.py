@@ -59,12 +59,14 @@ def _csr_tables(lib, take, E_cap, n_src, n_dst, args=None):
 class CsrInPlace:
     """See HipBackend.csr_in_place."""
 
-    def __init__(self, backend, shapes, device, masks=None):
+    def __init__(self, backend, shapes, device, masks=None, unions=None):
         if not 1 <= len(shapes) <= 4:
             raise _lib.GGNNError("csr_in_place: one to four lists")
         self.be, self.shapes = backend, [tuple(int(v) for v in s) for s in shapes]
         # masked lists (ggnn_csr_mask): refilled with the same mask; their tables' edge count lives in a device word
         self.masks, self.kept = _csr_masks(masks, len(self.shapes), device)
+        # a disjoint union (ggnn_csr_union): the masks' indices are local ones, every refill (the offset tensors are kept)
+        self.unions, self._union_tensors = _csr_unions(unions, len(self.shapes))
         words = sum(backend.csr_arena_words(cap, n_dst) for cap, _, n_dst in self.shapes)
         arena = _WordArena(torch.empty(words, dtype=torch.int32, device=device))
         self.args = (_lib.CsrArgs * len(self.shapes))()
@@ -84,8 +86,7 @@ class CsrInPlace:
         for csr, w in zip(self.csr, self.kept):
             if w is not None:
                 csr.E_dev = w
-        _lib.check(self.be.lib.ggnn_build_csr_batch(self.args, self.masks, len(self.shapes), _lib.current_stream()),
-                   "ggnn_build_csr_batch")
+        _build_csr(self.be.lib, self.args, self.masks, self.unions, len(self.shapes))
         return self.csr
 
 
@@ -105,6 +106,34 @@ def _csr_masks(masks, n, device):
         a.skip_src, a.skip_dst, a.E_kept = s, d, (w.data_ptr() if w is not None else None)
         kept.append(w)
     return arr, kept
+
+
+def _csr_unions(unions, n):
+    """[(src_off, dst_off) or None], each offset an int64 [n_traj + 1] device tensor or None -> (ctypes array of CsrUnion,
+    the tensors it points into); (None, ()) when no list is split."""
+    if unions is None or all(u is None or (u[0] is None and u[1] is None) for u in unions):
+        return None, ()
+    if len(unions) != n:
+        raise _lib.GGNNError("one union per list")
+    arr, keep = (_lib.CsrUnion * n)(), []
+    for a, u in zip(arr, unions):
+        offs = [t for t in (u or ()) if t is not None]
+        for t in offs:
+            if t.dtype != torch.int64 or t.dim() != 1 or t.numel() < 2 or not t.is_contiguous() or not t.is_cuda \
+                    or t.numel() != offs[0].numel():
+                raise _lib.GGNNError("union offsets must be contiguous int64 [n_traj + 1] device tensors of one length")
+        if offs:
+            a.src_off, a.dst_off, a.n_traj = ptr(u[0]), ptr(u[1]), offs[0].numel() - 1
+            keep += offs
+    return arr, tuple(keep)
+
+
+def _build_csr(lib, args, masks, unions, n):
+    """ggnn_build_csr_batch, or -- lists of a disjoint union -- ggnn_build_csr_batch_traj."""
+    if unions is None:
+        _lib.check(lib.ggnn_build_csr_batch(args, masks, n, _lib.current_stream()), "ggnn_build_csr_batch")
+    else:
+        _lib.check(lib.ggnn_build_csr_batch_traj(args, masks, unions, n, _lib.current_stream()), "ggnn_build_csr_batch_traj")
 
 
 def _require_cuda(*tensors):
@@ -225,27 +254,34 @@ class HipBackend:
         _csr_tables(self.lib, count.take, E_cap, 0, n_dst)
         return count.at
 
-    def csr_in_place(self, shapes, device, masks=None):
+    def csr_in_place(self, shapes, device, masks=None, unions=None):
         """Tables that are rebuilt in place: `shapes` = [(E_cap, n_src, n_dst)] (at most four lists) -> a CsrInPlace whose
         `rebuild([edge_index [2, E <= E_cap]])` fills the SAME device tables for the new lists (unchecked: validated lists)
         and returns the same CSR objects with their E updated -- tensors of capacity size, addresses that never change, so
-        launches captured on an earlier, longer version of a list keep reading valid tables."""
-        return CsrInPlace(self, shapes, device, masks)
+        launches captured on an earlier, longer version of a list keep reading valid tables.  masks / unions: as in
+        build_csr_batch, applied at every refill."""
+        return CsrInPlace(self, shapes, device, masks, unions)
 
-    def build_csr_batch(self, lists, check=True, masks=None):
+    def build_csr_batch(self, lists, check=True, masks=None, unions=None):
         """[(edge_index [2, E] int64 cuda, n_src, n_dst)] -> [CSR]: ggnn_build_csr_batch, up to four lists per sequence of
         launches (engine.GraphCSR builds the three edge types of a topology in one; a topological event rebuilds them),
         one range check = one host synchronisation behind the last (`check=False`: lists the caller has validated -- the
         kernels skip an out-of-range edge either way --: no read-back, the host goes on enqueueing).  (Tables that are
         refilled IN PLACE per event: `csr_in_place`.)  masks: None, or per list None / (skip_src, skip_dst) -- the tables of
         the list without the edges from skip_src / into skip_dst (ggnn_csr_mask); the CSR of a masked list has
-        E = the list's length and E_dev = the number of edges it kept (device word)."""
+        E = the list's length and E_dev = the number of edges it kept (device word).  unions: None, or per list None /
+        (src_off, dst_off) -- the lists of a disjoint union of trajectories, int64 [n_traj + 1] device offsets of the
+        source / destination node type or None (that side is not split): the list's mask then skips LOCAL indices
+        (ggnn_csr_union, ggnn_build_csr_batch_traj)."""
         out, todo = [], list(lists)
         mtodo = list(masks) if masks is not None else [None] * len(todo)
+        utodo = list(unions) if unions is not None else [None] * len(todo)
         while todo:
             chunk, todo = todo[:4], todo[4:]
             mchunk, mtodo = mtodo[:4], mtodo[4:]
+            uchunk, utodo = utodo[:4], utodo[4:]
             marr, kept = _csr_masks(mchunk, len(chunk), chunk[0][0].device)
+            uarr, _ = _csr_unions(uchunk, len(chunk))
             arr = (_lib.CsrArgs * len(chunk))()
             keep = []
             arena = None
@@ -269,7 +305,7 @@ class HipBackend:
                 a.edge_index, a.E = ei.data_ptr(), E
                 keep.append((ei, ws, flags, n_src, n_dst))
                 out.append(CSR(*tables, E, kept[len(keep) - 1]))
-            _lib.check(self.lib.ggnn_build_csr_batch(arr, marr, len(chunk), _lib.current_stream()), "ggnn_build_csr_batch")
+            _build_csr(self.lib, arr, marr, uarr, len(chunk))
             if not check:   # (ei / ws / flags are only used by launches on this stream: the allocator keeps them until those ran)
                 continue
             bad = torch.stack([k[2][0] for k in keep]).cpu()   # (the synchronisation; also keeps ei / ws alive until here)
@@ -1016,12 +1052,14 @@ class HipBackend:
                                           _lib.current_stream()), "ggnn_grain_centres")
 
     def noflux_boundary(self, csr_jg, x_joint, x_grain, domain_factor=1.0, domain_offset=None, max_y=1.0,
-                        joints_before=None):
+                        joints_before=None, traj_offsets=None):
         """The no-flux boundary step of test.py:446-463 (include/ggnn.h, ggnn_noflux_boundary): grain 0's features
         reset, its junctions (row 0 of csr_jg, the FULL joint->grain CSR) snapped to the nearest wall, every junction
         clamped to [0,1] x [0,max_y] in the global frame.  joints_before ([n_joint, 2] fp32): receives x_joint[:, :2]
-        as the call found them."""
-        _require_cuda(x_joint, x_grain, csr_jg.rowptr, domain_offset, joints_before)
+        as the call found them.  traj_offsets: None, or (grain offsets, junction offsets), int64 [n_traj + 1] device
+        tensors of a disjoint union whose caller has validated them (topology.check_noflux_union): every trajectory's
+        first grain is its boundary grain (ggnn_noflux_boundary_traj)."""
+        _require_cuda(x_joint, x_grain, csr_jg.rowptr, domain_offset, joints_before, *(traj_offsets or ()))
         _f32c(x_joint, "x_joint")
         _f32c(x_grain, "x_grain")
         if csr_jg.rowptr.numel() != x_grain.size(0) + 1:
@@ -1033,6 +1071,18 @@ class HipBackend:
                     raise _lib.GGNNError(f"{name} must be [n_joint, 2]")
         if domain_offset is None and domain_factor > 1:
             raise _lib.GGNNError("domain_factor > 1 needs the domain_offset of scale_feature_patchs")
+        if traj_offsets is not None:
+            og, oj = traj_offsets
+            for off in (og, oj):
+                if off.dtype != torch.int64 or off.dim() != 1 or off.numel() != og.numel() or og.numel() < 2 \
+                        or not off.is_contiguous():
+                    raise _lib.GGNNError("traj_offsets must be two contiguous int64 [n_traj + 1] tensors")
+            check(self.lib.ggnn_noflux_boundary_traj(ptr(csr_jg.rowptr), ptr(csr_jg.col), ptr(x_joint), x_joint.size(0),
+                                                     x_joint.stride(0), ptr(domain_offset), float(domain_factor),
+                                                     float(max_y), ptr(x_grain), x_grain.stride(0), x_grain.size(1),
+                                                     ptr(joints_before), ptr(og), ptr(oj), og.numel() - 1,
+                                                     _lib.current_stream()), "ggnn_noflux_boundary_traj")
+            return
         check(self.lib.ggnn_noflux_boundary(ptr(csr_jg.rowptr), ptr(csr_jg.col), ptr(x_joint), x_joint.size(0),
                                             x_joint.stride(0), ptr(domain_offset), float(domain_factor), float(max_y),
                                             ptr(x_grain), x_grain.stride(0), x_grain.size(1), ptr(joints_before),

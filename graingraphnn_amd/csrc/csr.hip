@@ -17,11 +17,26 @@ namespace ggnn {
 constexpr int CSR_MAX_BATCH = 4;
 struct CsrBatch {
   ggnn_csr_args p[CSR_MAX_BATCH];
-  ggnn_csr_mask m[CSR_MAX_BATCH];   // (all -1 / NULL for ggnn_build_csr_batch)
+  ggnn_csr_mask m[CSR_MAX_BATCH];   // (all -1 / NULL without masks)
+  ggnn_csr_union u[CSR_MAX_BATCH];  // (all NULL for ggnn_build_csr_batch: skip_src / skip_dst are global indices)
 };
-// an edge of a masked list (ggnn_csr_mask) that the tables leave out
-__device__ __forceinline__ bool csr_skipped(const ggnn_csr_mask& M, int64_t s, int64_t d) {
-  return s == M.skip_src || d == M.skip_dst;
+// a node's index inside its trajectory of a disjoint union: off [n_traj + 1] rises from 0 to the node count, the node
+// belongs to the last trajectory whose offset is <= node (equal offsets are empty trajectories).  At most a few hundred
+// offsets, searched once per masked edge and topological event: read from global memory (they stay in the caches).
+__device__ __forceinline__ int64_t csr_local(const int64_t* __restrict__ off, int64_t n_traj, int64_t node) {
+  int64_t lo = 0, hi = n_traj;
+  while (hi - lo > 1) {
+    const int64_t mid = lo + ((hi - lo) >> 1);
+    if (off[mid] <= node) lo = mid;
+    else hi = mid;
+  }
+  return node - off[lo];
+}
+// an edge of a masked list (ggnn_csr_mask) that the tables leave out; with a union (ggnn_csr_union) the skipped index is
+// the node's LOCAL one on the sides that are split
+__device__ __forceinline__ bool csr_skipped(const ggnn_csr_mask& M, const ggnn_csr_union& U, int64_t s, int64_t d) {
+  if (M.skip_src >= 0 && (U.src_off ? csr_local(U.src_off, U.n_traj, s) : s) == M.skip_src) return true;
+  return M.skip_dst >= 0 && (U.dst_off ? csr_local(U.dst_off, U.n_traj, d) : d) == M.skip_dst;
 }
 __device__ __forceinline__ int32_t* csr_counts(const ggnn_csr_args& P) { return reinterpret_cast<int32_t*>(P.workspace); }
 __device__ __forceinline__ int32_t* csr_cursor(const ggnn_csr_args& P) { return csr_counts(P) + P.n_dst + 1; }
@@ -43,7 +58,7 @@ __global__ __launch_bounds__(256) void csr_count_batch_kernel(const CsrBatch B) 
     atomicOr(P.flags, 1);
     return;
   }
-  if (csr_skipped(B.m[blockIdx.y], s, d)) return;
+  if (csr_skipped(B.m[blockIdx.y], B.u[blockIdx.y], s, d)) return;
   atomicAdd(&csr_counts(P)[d], 1);
 }
 // Single-workgroup exclusive scan over a list's n_dst counts (a few 10^4 here), one workgroup per list: writes out[0..n] and
@@ -94,7 +109,7 @@ __global__ __launch_bounds__(256) void csr_fill_batch_kernel(const CsrBatch B) {
   if (e >= P.E) return;
   const int64_t s = P.edge_index[e], d = P.edge_index[P.E + e];
   if ((uint64_t)s >= (uint64_t)P.n_src || (uint64_t)d >= (uint64_t)P.n_dst) return;
-  if (csr_skipped(B.m[blockIdx.y], s, d)) return;
+  if (csr_skipped(B.m[blockIdx.y], B.u[blockIdx.y], s, d)) return;
   const int32_t pos = atomicAdd(&csr_cursor(P)[d], 1);
   P.perm[pos] = (int32_t)e;
 }
@@ -158,8 +173,8 @@ extern "C" int64_t ggnn_csr_max_units(int64_t E, int64_t n_dst) {
   return (n_dst > 0 ? n_dst : 0) + (E > 0 ? E : 0) / GGNN_UNIT_EDGES + 1;
 }
 
-extern "C" int ggnn_build_csr_batch(const ggnn_csr_args* problems, const ggnn_csr_mask* masks, int n_problems,
-                                    ggnn_stream_t stream_) {
+extern "C" int ggnn_build_csr_batch_traj(const ggnn_csr_args* problems, const ggnn_csr_mask* masks,
+                                         const ggnn_csr_union* unions, int n_problems, ggnn_stream_t stream_) {
   using namespace ggnn;
   hipStream_t stream = (hipStream_t)stream_;
   if (!problems || n_problems < 1 || n_problems > CSR_MAX_BATCH) return GGNN_EINVAL;
@@ -168,7 +183,12 @@ extern "C" int ggnn_build_csr_batch(const ggnn_csr_args* problems, const ggnn_cs
   for (int k = 0; k < CSR_MAX_BATCH; ++k) {
     B.p[k] = problems[k < n_problems ? k : 0];
     B.m[k] = ggnn_csr_mask{-1, -1, nullptr};
+    B.u[k] = ggnn_csr_union{nullptr, nullptr, 0};
     if (k >= n_problems) continue;
+    if (unions && (unions[k].src_off || unions[k].dst_off)) {
+      if (unions[k].n_traj < 1 || unions[k].n_traj > (1 << 29)) return GGNN_EINVAL;
+      B.u[k] = unions[k];
+    }
     if (masks) {
       const ggnn_csr_mask& M = masks[k];
       if (M.skip_src < -1 || M.skip_dst < -1 || (M.E_kept && ((uintptr_t)M.E_kept & 7))) return GGNN_EINVAL;
@@ -197,4 +217,9 @@ extern "C" int ggnn_build_csr_batch(const ggnn_csr_args* problems, const ggnn_cs
   hipLaunchKernelGGL(csr_scan_batch_kernel<true>, dim3(ny), dim3(1024), 0, stream, B);
   hipLaunchKernelGGL(csr_unit_fill_batch_kernel, dim3(nb, ny), dim3(256), 0, stream, B);
   return launch_status();
+}
+
+extern "C" int ggnn_build_csr_batch(const ggnn_csr_args* problems, const ggnn_csr_mask* masks, int n_problems,
+                                    ggnn_stream_t stream) {
+  return ggnn_build_csr_batch_traj(problems, masks, nullptr, n_problems, stream);
 }

@@ -2,7 +2,7 @@
 //   ggnn_step_update  = GrainNN_regressor.update, periodic branch (models.py:503-516)
 //                       + z advance (test.py:401-402)
 //   ggnn_step_refresh = z clamp (test.py:405-407) + edge-length refresh (test.py:562-575)
-//   ggnn_noflux_boundary = the no-flux boundary step (test.py:446-463), after the topology update
+//   ggnn_noflux_boundary[_traj] = the no-flux boundary step (test.py:446-463), after the topology update
 //   ggnn_grain_centres = region centres of graph.update() (graph_datastruct.py:681-708) written
 //                       to x_grain[:, :2] (test.py:468-478, 556-559), between the two
 // Separate launches because each stage needs every node's updated coordinates.
@@ -193,24 +193,37 @@ __global__ __launch_bounds__(256) void detect_events_traj_kernel(
   }
 }
 
-// The no-flux boundary step (test.py:446-463): one thread per junction.  Whether a junction is one of grain 0's (row 0 of
-// the full joint->grain CSR, a few dozen to a few hundred junctions on the walls) is looked up in LDS, one chunk of the
-// row at a time.  Every fp32 operation is rounded on its own, in the reference's order: torch evaluates
+// The no-flux boundary step (test.py:446-463): one thread per junction.  Whether a junction is one of its boundary grain's
+// (that grain's row of the full joint->grain CSR, a few dozen to a few hundred junctions on the walls) is looked up in LDS,
+// one chunk of the row at a time.  Every fp32 operation is rounded on its own, in the reference's order: torch evaluates
 // (xy + off) / f and xy * f - off as separate ops, which a contraction into an fma would not reproduce.
+// One rollout (traj_joint_off == nullptr): one trajectory, every junction, boundary grain 0.  A disjoint union of n_traj
+// trajectories: trajectory t owns the junctions [traj_joint_off[t], traj_joint_off[t + 1]) and its boundary grain is its
+// first one, traj_grain_off[t].  A block's 256 junctions span a contiguous range of trajectories, found once per block; the
+// block walks that range -- a trip count that is uniform over the block, so that every thread reaches every barrier -- and
+// stages each trajectory's boundary row, against which only that trajectory's lanes compare: a junction pays for the length
+// of its own trajectory's row.  UNION = false compiles the same body without the walk: the single rollout's launch costs
+// what it cost before unions.
 constexpr int BND_CHUNK = 1024;
+// the last trajectory whose offset is <= node (offsets rise from 0; equal ones are empty trajectories)
+__device__ __forceinline__ int bnd_traj_of(const int64_t* __restrict__ off, int n_traj, int64_t node) {
+  int lo = 0, hi = n_traj;
+  while (hi - lo > 1) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if (off[mid] <= node) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+template <bool UNION>
 __global__ __launch_bounds__(256) void noflux_boundary_kernel(
     const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, float* __restrict__ x_joint, int64_t n_joint,
-    int64_t ldxj, const float* __restrict__ offset, float factor, float max_y, float* __restrict__ x_grain, int f_grain,
-    float* __restrict__ joints_before) {
+    int64_t ldxj, const float* __restrict__ offset, float factor, float max_y, float* __restrict__ x_grain, int64_t ldxg,
+    int f_grain, float* __restrict__ joints_before, const int64_t* __restrict__ traj_grain_off,
+    const int64_t* __restrict__ traj_joint_off, int n_traj) {
   __shared__ int32_t s_b[BND_CHUNK];
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (t == 0) {   // test.py:450-452
-    x_grain[0] = 0.5f;
-    x_grain[1] = 0.5f;
-    x_grain[3] = 0.0f;
-    x_grain[4] = 0.0f;
-    x_grain[f_grain - 1] = 0.0f;
-  }
+  const int64_t first = (int64_t)blockIdx.x * 256;
+  const int64_t t = first + threadIdx.x;
   const bool live = t < n_joint;
   float xy[2] = {0.f, 0.f};
   if (live) {
@@ -222,15 +235,39 @@ __global__ __launch_bounds__(256) void noflux_boundary_kernel(
       xy[c] = __fdiv_rn(offset ? __fadd_rn(v, offset[2 * t + c]) : v, factor);   // test.py:453
     }
   }
-  const int32_t b0 = rowptr[0], b1 = rowptr[1];
+  // the trajectories of the block's first and last junction (block-uniform)
+  int tr = 0, tr_last = 0;
+  if (UNION) {
+    tr = bnd_traj_of(traj_joint_off, n_traj, first);
+    tr_last = bnd_traj_of(traj_joint_off, n_traj, min(first + 255, n_joint - 1));
+  }
   bool bound = false;
-  for (int32_t q0 = b0; q0 < b1; q0 += BND_CHUNK) {   // (uniform trip count: every thread reaches the barriers)
-    const int32_t nq = min(BND_CHUNK, b1 - q0);
-    __syncthreads();
-    for (int k = threadIdx.x; k < nq; k += 256) s_b[k] = col[q0 + k];
-    __syncthreads();
-    if (live)
-      for (int k = 0; k < nq; ++k) bound = bound || s_b[k] == (int32_t)t;
+  for (; tr <= tr_last; ++tr) {
+    int64_t j0 = 0, j1 = n_joint, g0 = 0;
+    if (UNION) {
+      j0 = traj_joint_off[tr];
+      j1 = traj_joint_off[tr + 1];
+      g0 = traj_grain_off[tr];
+    }
+    if (j0 >= j1) continue;   // an empty trajectory inside the range (block-uniform)
+    if (t == j0) {   // test.py:450-452, once per trajectory: by its first junction, wherever in a block that falls
+      float* g = x_grain + g0 * ldxg;
+      g[0] = 0.5f;
+      g[1] = 0.5f;
+      g[3] = 0.0f;
+      g[4] = 0.0f;
+      g[f_grain - 1] = 0.0f;
+    }
+    const bool mine = live && t >= j0 && t < j1;
+    const int32_t b0 = rowptr[g0], b1 = rowptr[g0 + 1];
+    for (int32_t q0 = b0; q0 < b1; q0 += BND_CHUNK) {   // (uniform trip count: every thread reaches the barriers)
+      const int32_t nq = min(BND_CHUNK, b1 - q0);
+      __syncthreads();
+      for (int k = threadIdx.x; k < nq; k += 256) s_b[k] = col[q0 + k];
+      __syncthreads();
+      if (mine)
+        for (int k = 0; k < nq; ++k) bound = bound || s_b[k] == (int32_t)t;
+    }
   }
   if (!live) return;
   if (bound) {   // move_to_boundary, test.py:58-71: torch.argmin keeps the first of equal minima
@@ -340,6 +377,25 @@ extern "C" int ggnn_grain_centres(const int32_t* rowptr, const int32_t* col, con
   return launch_status();
 }
 
+extern "C" int ggnn_noflux_boundary_traj(const int32_t* rowptr_jg, const int32_t* col_jg, float* x_joint, int64_t n_joint,
+                                         int64_t ldx_joint, const float* domain_offset, float domain_factor, float max_y,
+                                         float* x_grain, int64_t ldx_grain, int f_grain, float* joints_before,
+                                         const int64_t* traj_grain_off, const int64_t* traj_joint_off, int64_t n_traj,
+                                         ggnn_stream_t stream) {
+  using namespace ggnn;
+  if (!rowptr_jg || !col_jg || !x_joint || !x_grain || n_joint <= 0) return GGNN_EINVAL;
+  if (ldx_joint < 2 || f_grain < 6 || ldx_grain < f_grain) return GGNN_EINVAL;
+  if (!(domain_factor >= 1.0f) || !(max_y > 0.0f)) return GGNN_EINVAL;
+  if (!traj_grain_off || !traj_joint_off || n_traj < 1 || n_traj > (1 << 29)) return GGNN_EINVAL;
+  const int64_t nblk = (n_joint + 255) / 256;
+  if (nblk >= INT32_MAX) return GGNN_EINVAL;
+  hipLaunchKernelGGL(noflux_boundary_kernel<true>, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, rowptr_jg, col_jg,
+                     x_joint, n_joint, ldx_joint, domain_offset, domain_factor, max_y, x_grain, ldx_grain, f_grain,
+                     joints_before, traj_grain_off, traj_joint_off, (int)n_traj);
+  return launch_status();
+}
+
+// (one rollout = the one-trajectory case of the kernel: every junction, boundary grain 0)
 extern "C" int ggnn_noflux_boundary(const int32_t* rowptr_jg, const int32_t* col_jg, float* x_joint, int64_t n_joint,
                                     int64_t ldx_joint, const float* domain_offset, float domain_factor, float max_y,
                                     float* x_grain, int64_t ldx_grain, int f_grain, float* joints_before,
@@ -350,8 +406,9 @@ extern "C" int ggnn_noflux_boundary(const int32_t* rowptr_jg, const int32_t* col
   if (!(domain_factor >= 1.0f) || !(max_y > 0.0f)) return GGNN_EINVAL;
   const int64_t nblk = (n_joint + 255) / 256;
   if (nblk >= INT32_MAX) return GGNN_EINVAL;
-  hipLaunchKernelGGL(noflux_boundary_kernel, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, rowptr_jg, col_jg,
-                     x_joint, n_joint, ldx_joint, domain_offset, domain_factor, max_y, x_grain, f_grain, joints_before);
+  hipLaunchKernelGGL(noflux_boundary_kernel<false>, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, rowptr_jg, col_jg,
+                     x_joint, n_joint, ldx_joint, domain_offset, domain_factor, max_y, x_grain, ldx_grain, f_grain,
+                     joints_before, (const int64_t*)nullptr, (const int64_t*)nullptr, 1);
   return launch_status();
 }
 
@@ -381,7 +438,7 @@ extern "C" int ggnn_detect_events_traj(const float* grain_area, const int32_t* l
   if (!grain_area || !live_grain || !flags || !counts || n_grain <= 0 || E < 0) return GGNN_EINVAL;
   if (E > 0 && (!edge_event || !edge_index_jj)) return GGNN_EINVAL;
   if (!traj_grain_off || !traj_joint_off || n_traj < 1 || n_traj > (1 << 29)) return GGNN_EINVAL;
-  if (skip_local_grain != -1) return GGNN_EINVAL;   // (no-flux unions: not yet)
+  if (skip_local_grain != -1) return GGNN_EINVAL;   // (no-flux unions keep their boundary grains out through live_grain)
   const int64_t nblk = (n_grain + E + 255) / 256;
   if (nblk >= INT32_MAX) return GGNN_EINVAL;
   const hipStream_t s = (hipStream_t)stream;

@@ -145,7 +145,8 @@ def run_sharded(n_traj: int, run_one: Callable[[int], torch.Tensor], rank: int, 
 
 def rollout_trajectories(rmodel, cmodel, graphs, span: int, n_steps: int, rank: int = 0,
                          world: int = 1, device="cuda", use_graph: bool = True,
-                         refresh_centres: bool = False, qoi=None, events=None):
+                         refresh_centres: bool = False, qoi=None, events=None, boundary: str = "periodic",
+                         max_y: float = 1.0, domain_factor: float = 1.0, domain_offsets=None):
     """BASELINE config 4: `graphs[t]` = (x, ei, ea) numpy dicts of independent trajectories with
     EQUAL node counts.  Rank r rolls out trajectories t = r (mod world) as ONE disjoint-union
     graph on its GPU (one set of launches for the whole shard), then all ranks all-gather the
@@ -159,7 +160,11 @@ def rollout_trajectories(rmodel, cmodel, graphs, span: int, n_steps: int, rank: 
     'joint' masks, default all ones]}: the shard's union runs n_steps of step_events() with events PER TRAJECTORY
     (GrainRollout.enable_events(traj_offsets=...)); a trajectory whose update is refused ends with the state of that
     moment, the others go on.  Every trajectory's row then also carries 'grain_live' [T, N_g], 'joint_live' [T, N_j],
-    'ended_at' [T] (-1: it ran to the end) and 'n_eliminated' [T], small integers as float32 in the same packed gather."""
+    'ended_at' [T] (-1: it ran to the end) and 'n_eliminated' [T], small integers as float32 in the same packed gather.
+    `boundary`: "periodic", or "noflux" -- every trajectory is a no-flux domain whose grain 0 is its boundary grain; the
+    shard's union is built with its trajectory offsets (GrainRollout(boundary="noflux", traj_offsets=...)), `max_y` and
+    `domain_factor` are the one box of all trajectories.  `domain_offsets`: per trajectory the [N_j, 2] offsets of
+    scale_feature_patchs, needed when domain_factor > 1 and the grain centres or the no-flux boundary use them."""
     from . import synthetic
     from .rollout import GrainRollout
 
@@ -167,10 +172,17 @@ def rollout_trajectories(rmodel, cmodel, graphs, span: int, n_steps: int, rank: 
     mine = shard_trajectories(len(graphs), rank, world)
     x, ei, ea, slices = synthetic.disjoint_union([graphs[t] for t in mine])
     X, EI, EA = synthetic.to_torch(x, ei, ea, device)
-    ro = GrainRollout(rmodel, cmodel, X, EI, EA, span, use_graph=use_graph, refresh_centres=refresh_centres)
-    grains = [s["grain"] for s in slices]
+    grains, joints = [s["grain"] for s in slices], [s["joint"] for s in slices]
+    offsets = {"grain": [lo for lo, _ in grains] + [grains[-1][1]], "joint": [lo for lo, _ in joints] + [joints[-1][1]]}
+    noflux = boundary == "noflux"
+    offset = None
+    if domain_offsets is not None:
+        offset = torch.from_numpy(np.ascontiguousarray(np.concatenate(
+            [np.asarray(domain_offsets[t], np.float32).reshape(-1, 2) for t in mine]))).to(device)
+    ro = GrainRollout(rmodel, cmodel, X, EI, EA, span, use_graph=use_graph, refresh_centres=refresh_centres,
+                      domain_factor=domain_factor, domain_offset=offset, boundary=boundary, max_y=max_y,
+                      **({"traj_offsets": offsets} if noflux else {}))
     if events is not None:
-        joints = [s["joint"] for s in slices]
         ones = lambda n: np.ones((n, 1), np.int64)
         masks = events.get("mask")
         if masks is None:
@@ -178,11 +190,10 @@ def rollout_trajectories(rmodel, cmodel, graphs, span: int, n_steps: int, rank: 
         else:
             mask = {k: np.concatenate([np.asarray(masks[t][k], np.int64).reshape(-1, 1) for t in mine]) for k in ("grain", "joint")}
         live0 = [int((mask["grain"][lo:hi] > 0).sum()) for lo, hi in grains]
-        ro.enable_events(mask, events["area_threshold"], events["edge_threshold"],
-                         traj_offsets={"grain": [lo for lo, _ in grains] + [grains[-1][1]],
-                                       "joint": [lo for lo, _ in joints] + [joints[-1][1]]})
+        # (a no-flux union has its offsets from the constructor)
+        ro.enable_events(mask, events["area_threshold"], events["edge_threshold"], traj_offsets=None if noflux else offsets)
     if qoi is not None:
-        ro.enable_qoi(**dict(qoi, traj_offsets=[lo for lo, _ in grains] + [grains[-1][1]]))
+        ro.enable_qoi(**dict(qoi, traj_offsets=None if noflux else offsets["grain"]))
     if events is None:
         ro.run(n_steps)
         local = {"joint_xy": torch.stack([X["joint"][lo:hi, :2] for lo, hi in (s["joint"] for s in slices)]),

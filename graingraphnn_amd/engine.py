@@ -23,11 +23,20 @@ JG = ("joint", "pull", "grain")
 NOFLUX_MASKS = {("grain", "push", "joint"): (0, -1), JG: (-1, 0), ("joint", "connect", "joint"): None}
 
 
+def noflux_unions(traj_grain_off):
+    """The ggnn_csr_union of every list of GraphCSR(boundary="noflux") -- the three edge types, then the full joint->grain
+    list -- for a disjoint union whose grains are split by `traj_grain_off` (int64 [n_traj + 1], device): NOFLUX_MASKS'
+    grain 0 then is every trajectory's LOCAL grain 0.  None without offsets."""
+    if traj_grain_off is None:
+        return None
+    return [(traj_grain_off, None), (None, traj_grain_off), None, None]
+
+
 class GraphCSR:
     """Destination-grouped neighbour lists of the three edge types of one topology."""
 
     def __init__(self, backend, edge_index_dict, n_nodes: Dict[str, int], trusted: bool = False, into=None, counts=None,
-                 boundary: str = "periodic"):
+                 boundary: str = "periodic", traj_grain_off=None):
         """trusted: the lists come from the library's own topology update (validated on the host, topology.py): the
         range check of the build -- a read-back, i.e. a host synchronisation -- is skipped.
         into = a backend.CsrInPlace: the tables are refilled IN PLACE (same device tensors, same addresses);
@@ -35,11 +44,16 @@ class GraphCSR:
         boundary = "noflux": `csr` holds the FORWARD graph (NOFLUX_MASKS; a masked table's E_dev is its kept-edge count)
         and `csr_full[JG]` the full joint->grain table (grain centres, boundary step), built in the same launches (`into`
         then has four lists); `edge_index` stays the full lists (the topology).  `count_dev[et]`: the device word with the
-        length of the full list edge_index[et] (or None)."""
+        length of the full list edge_index[et] (or None).  traj_grain_off (noflux): int64 [n_traj + 1] device offsets of
+        the grains of a disjoint union -- every trajectory's first grain is a boundary grain (noflux_unions; with `into`
+        the CsrInPlace carries them)."""
         self.csr = {}
         self.edge_index = {}
         self.n_nodes = dict(n_nodes)
         self.boundary = boundary
+        self.traj_grain_off = traj_grain_off
+        if traj_grain_off is not None and boundary != "noflux":
+            raise _lib.GGNNError("traj_grain_off belongs to boundary='noflux'")
         for et in EDGE_TYPES:
             if et not in edge_index_dict:
                 raise KeyError(f"edge_index_dict lacks edge type {et}")
@@ -55,7 +69,8 @@ class GraphCSR:
                     if masks[k] is None:
                         built[k].E_dev = self.count_dev[et]
             else:
-                built = backend.build_csr_batch(lists, check=not trusted, masks=masks)
+                built = backend.build_csr_batch(lists, check=not trusted, masks=masks, **(
+                    {} if traj_grain_off is None else {"unions": noflux_unions(traj_grain_off)}))
             self.csr = dict(zip(EDGE_TYPES, built[:3]))
             self.csr_full = {JG: built[3]}
             return
@@ -80,7 +95,8 @@ _graph_cache: Dict[tuple, GraphCSR] = {}
 _GRAPH_CACHE_MAX = 8
 
 
-def graph_for(backend, edge_index_dict, n_nodes, trusted: bool = False, boundary: str = "periodic") -> GraphCSR:
+def graph_for(backend, edge_index_dict, n_nodes, trusted: bool = False, boundary: str = "periodic",
+              traj_grain_off=None) -> GraphCSR:
     """CSR of `edge_index_dict`, rebuilt only when a tensor is replaced or modified in place
     (Cmodel.update swaps the tensors after a topological event, models.py:841-845)."""
     key = tuple((et, edge_index_dict[et].data_ptr(), edge_index_dict[et]._version,
@@ -88,9 +104,11 @@ def graph_for(backend, edge_index_dict, n_nodes, trusted: bool = False, boundary
     key = key + tuple(sorted(n_nodes.items()))
     if boundary != "periodic":
         key = key + (boundary,)
+    if traj_grain_off is not None:   # (a cached graph keeps its offsets tensor alive: the address names it)
+        key = key + ("traj", traj_grain_off.data_ptr())
     g = _graph_cache.get(key)
     if g is None:
-        g = GraphCSR(backend, edge_index_dict, n_nodes, trusted, boundary=boundary)
+        g = GraphCSR(backend, edge_index_dict, n_nodes, trusted, boundary=boundary, traj_grain_off=traj_grain_off)
         if len(_graph_cache) >= _GRAPH_CACHE_MAX:
             _graph_cache.pop(next(iter(_graph_cache)))
         _graph_cache[key] = g

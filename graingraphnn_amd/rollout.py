@@ -30,6 +30,29 @@ JG = ("joint", "pull", "grain")
 GJ = ("grain", "push", "joint")
 
 
+def resolve_traj_offsets(own, passed, what):
+    """The trajectory offsets an enable_* call works with on a no-flux rollout: `own` = the constructor's (grain, junction)
+    offsets or None, `passed` = the call's argument ({'grain', 'joint'} dict, or -- enable_qoi -- the grain offsets alone) or
+    None.  A no-flux union has ONE set of offsets, the constructor's (the forward graph and the boundary step are built from
+    them): passed ones must be equal.  Returns (grain offsets, junction offsets) or None."""
+    if own is None:
+        if passed is not None:
+            raise _lib.GGNNError(f"{what}(traj_offsets=...) with boundary='noflux': a noflux union takes its offsets at "
+                                 "construction, GrainRollout(..., boundary='noflux', traj_offsets=...) -- every trajectory has "
+                                 "a boundary grain of its own, which the forward graph and the boundary step must know")
+        return None
+    if passed is not None:
+        try:
+            same = (np.array_equal(np.asarray(passed["grain"], np.int64).reshape(-1), own[0])
+                    and np.array_equal(np.asarray(passed["joint"], np.int64).reshape(-1), own[1])) if isinstance(passed, dict) \
+                else np.array_equal(np.asarray(passed, np.int64).reshape(-1), own[0])
+        except (KeyError, TypeError, ValueError):
+            same = False
+        if not same:
+            raise _lib.GGNNError(f"{what}: traj_offsets differ from the ones this noflux rollout was built with")
+    return own
+
+
 class GrainRollout:
     JOINT_LAUNCH_MAX_JOINTS = 8000
 
@@ -37,7 +60,7 @@ class GrainRollout:
                  edge_attr_dict, span: int, use_graph: bool = False, concurrent: bool = True,
                  refresh_centres: bool = False,
                  domain_factor: float = 1.0, domain_offset: Optional[torch.Tensor] = None,
-                 joint_launches: Optional[bool] = None, boundary: str = "periodic", max_y: float = 1.0):
+                 joint_launches: Optional[bool] = None, boundary: str = "periodic", max_y: float = 1.0, traj_offsets=None):
         """refresh_centres: also recompute x_grain[:, :2] from the junction polygons every step,
         like the reference's traj.GNN_update + test.py:556-559 (default off = the static-geometry
         goldens).  domain_factor / domain_offset: `geometry_scaling` of test.py:310-312 when the
@@ -52,11 +75,24 @@ class GrainRollout:
         boundary: "periodic" (default) or "noflux" -- grain 0 is the boundary grain that wraps the domain (the reference's
         traj.BC == 'noflux', test.py:363-375, 418-422, 446-463): both forwards see the lists without grain 0's edges,
         grain 0 never takes part in events, and after every step's topology update the boundary step resets grain 0 and
-        pins the junctions to [0,1] x [0,max_y] ("No-flux boundary")."""
+        pins the junctions to [0,1] x [0,max_y] ("No-flux boundary").
+        traj_offsets (noflux only): {'grain': [n_traj + 1], 'joint': [n_traj + 1]} -- the graph is a disjoint union of
+        no-flux trajectories, trajectory t's boundary grain is its local grain 0 = global grain traj_offsets['grain'][t]
+        (DESIGN.md 8e).  max_y, domain_factor: one box for the whole union; domain_offset: the trajectories' concatenated.
+        enable_events / enable_qoi then use these offsets.  (Periodic unions pass their offsets to enable_events /
+        enable_qoi.)"""
         if boundary not in ("periodic", "noflux"):
             raise _lib.GGNNError(f"boundary must be 'periodic' or 'noflux', got {boundary!r}")
         self.boundary, self.max_y = boundary, float(max_y)
         self.noflux = boundary == "noflux"
+        self._traj = None                     # a no-flux union: its offsets (host and device) and boundary grains
+        if traj_offsets is not None:
+            if not self.noflux:
+                raise _lib.GGNNError("GrainRollout(traj_offsets=...) belongs to boundary='noflux'; a periodic union passes "
+                                     "its offsets to enable_events / enable_qoi")
+            from .topology import check_noflux_union, check_traj_offsets
+            og, oj = check_traj_offsets(traj_offsets, int(x_dict["grain"].shape[0]), int(x_dict["joint"].shape[0]))
+            self._traj = {"grain": og, "joint": oj, "boundary_grains": check_noflux_union(og, oj)}
         self.be = default_backend()
         self.rmodel, self.cmodel = rmodel, cmodel
         self.x = {nt: x_dict[nt] for nt in NODE_TYPES}  # mutated in place, like the reference
@@ -65,6 +101,8 @@ class GrainRollout:
             if not self.x[nt].is_contiguous():
                 raise _lib.GGNNError("x_dict tensors must be contiguous")
         dev = self.x["joint"].device
+        if self._traj is not None:
+            self._traj["dev"] = (torch.from_numpy(self._traj["grain"]).to(dev), torch.from_numpy(self._traj["joint"]).to(dev))
         self.n_nodes = {nt: self.x[nt].size(0) for nt in NODE_TYPES}
         self.pred = {}                        # this step's predictions (run_events: one of its slots' dicts)
         self.mask = None                      # enable_events()
@@ -167,7 +205,7 @@ class GrainRollout:
             self._cap = None   # (a caller's own topology, or one that grew: back to buffers of its own; the segment graphs go)
             self._drop_segment_graphs()
         self.edge_index = {et: edge_index_dict[et] for et in EDGE_TYPES}
-        self.graph = graph_for(self.be, self.edge_index, self.n_nodes, trusted, self.boundary)
+        self.graph = graph_for(self.be, self.edge_index, self.n_nodes, trusted, self.boundary, self._traj_grain_dev())
         if trusted and edge_attr_dict is None:
             return self._set_topology_buffers_from_one_allocation(dev)
         if edge_attr_dict is not None:
@@ -276,7 +314,7 @@ class GrainRollout:
         counts = {et: C["counts"][k:k + 1] for k, et in enumerate(EDGE_TYPES)}
         from .engine import GraphCSR
         self.graph = GraphCSR(self.be, self.edge_index, self.n_nodes, trusted=True, into=C["csr"], counts=counts,
-                              boundary=self.boundary)
+                              boundary=self.boundary, traj_grain_off=self._traj_grain_dev())
         buf, off = C["buf"], C["off"]
         cut = lambda name, n, shape=None: buf[off[name]:off[name] + n] if shape is None else buf[off[name]:off[name] + n].view(shape)
         rows = lambda et: E[et] + _lib.GGNN_UNIT_EDGES
@@ -327,9 +365,14 @@ class GrainRollout:
         shapes = [(cap[et], self.n_nodes[et[0]], self.n_nodes[et[-1]]) for et in EDGE_TYPES]
         if not self.noflux:
             return be.csr_in_place(shapes, dev)
-        from .engine import NOFLUX_MASKS
+        from .engine import NOFLUX_MASKS, noflux_unions
+        union = {} if self._traj is None else {"unions": noflux_unions(self._traj_grain_dev())}
         return be.csr_in_place(shapes + [(cap[JG], self.n_nodes["joint"], self.n_nodes["grain"])], dev,
-                               [NOFLUX_MASKS[et] for et in EDGE_TYPES] + [None])
+                               [NOFLUX_MASKS[et] for et in EDGE_TYPES] + [None], **union)
+
+    def _traj_grain_dev(self):
+        """A no-flux union's grain offsets on the device (every trajectory's first grain is a boundary grain), or None."""
+        return None if self._traj is None else self._traj["dev"][0]
 
     def _zero_records(self, *sets):
         """noflux: edge records of masked tables end before the list's length; what lies behind must be finite."""
@@ -339,10 +382,12 @@ class GrainRollout:
                     t.zero_()
 
     def _enqueue_boundary(self, joints_before=None):
-        """test.py:446-463 (noflux only): grain 0 reset, its junctions onto the walls, every junction into the domain."""
+        """test.py:446-463 (noflux only): grain 0 reset, its junctions onto the walls, every junction into the domain; a
+        union: every trajectory's boundary grain and its junctions, in the same launch."""
         if self.noflux:
+            union = {} if self._traj is None else {"traj_offsets": self._traj["dev"]}
             self.be.noflux_boundary(self.graph.csr_full[JG], self.x["joint"], self.x["grain"], self.domain_factor,
-                                    self.domain_offset, self.max_y, joints_before)
+                                    self.domain_offset, self.max_y, joints_before, **union)
 
     def _enqueue_centres(self, centres_before=None):
         """graph.update()'s region centres + test.py:556-559 (refresh_centres); noflux: from the full joint->grain table,
@@ -364,8 +409,10 @@ class GrainRollout:
         room for beyond layer 0 (default: the steps the frames allow, (frames - 1) // span); area0 [n_grain]: layer 0's
         areas when they are not the formula's (the reference keeps its rasterised pixel counts there, test.py:340);
         history=False keeps no volume_traj; traj_offsets: the first grain of every trajectory of a disjoint-union graph and
-        the total, [n_traj + 1] (default: one trajectory)."""
+        the total, [n_traj + 1] (default: one trajectory; a no-flux union: the constructor's, and nothing else)."""
         dev, ng = self.x["grain"].device, self.n_nodes["grain"]
+        if self._traj is not None:
+            traj_offsets = resolve_traj_offsets((self._traj["grain"], self._traj["joint"]), traj_offsets, "enable_qoi")[0]
         if frames is None:
             frames = int((final_height - ini_height) / 0.4) + 1   # test.py:191, 307
         if not (mesh_size > 0 and patch_size > 0 and frames > 1):
@@ -760,15 +807,22 @@ class GrainRollout:
         traj_offsets: None, or {'grain': [n_traj + 1], 'joint': [n_traj + 1]} -- the graph is a disjoint union of
         trajectories (node offsets rising from 0 to the node counts, as in enable_qoi) and the events are detected, applied
         and refused PER TRAJECTORY: a trajectory whose update is refused ends, the others go on
-        (trajectory_states)."""
-        if traj_offsets is not None and self.noflux:
-            raise _lib.GGNNError("enable_events(traj_offsets=...) with boundary='noflux' is not supported: the boundary step "
-                                 "knows one boundary grain")
+        (trajectory_states).  A no-flux union (constructor traj_offsets) uses the constructor's offsets: None here, or equal
+        ones; every trajectory's boundary grain stays out of its candidates."""
+        if self.noflux:   # (a no-flux union has the constructor's offsets and no others)
+            own = resolve_traj_offsets(None if self._traj is None else (self._traj["grain"], self._traj["joint"]), traj_offsets,
+                                       "enable_events")
+            traj_offsets = None if own is None else {"grain": own[0], "joint": own[1]}
         ens = None if traj_offsets is None else self._ensemble_sessions(traj_offsets)
         self.mask = {k: np.array(torch.as_tensor(mask[k]).cpu().numpy(), dtype=np.int64, copy=True).reshape(-1, 1)
                      for k in ("grain", "joint")}
         dev = self.x["joint"].device
         self._live_grain = torch.from_numpy(self.mask["grain"][:, 0].astype(np.int32)).to(dev)
+        # what the device-side count reads as its live mask.  A no-flux union: a second mask with every boundary grain's word
+        # at 0 (ggnn_detect_events_traj takes no grain to skip; the live mask itself keeps 1 there: the QoI reads it)
+        self._cand_grain = self._live_grain
+        if self._traj is not None:
+            self._cand_grain = torch.from_numpy(self._candidate_mask()).to(dev)
         self.area_threshold, self.edge_threshold = float(area_threshold), float(edge_threshold)
         # device-side trigger: slightly wider than the host's exact sigmoid(x) > threshold test,
         # so a borderline edge always reaches the host, which then decides exactly
@@ -793,6 +847,14 @@ class GrainRollout:
         og, oj = check_traj_offsets(traj_offsets, self.n_nodes["grain"], self.n_nodes["joint"])
         union_edge_segments(self.edge_index[GJ].cpu().numpy(), og, oj, "grain-junction list")
         return EnsembleSessions(self.edge_index[ET_JJ].cpu().numpy(), self.edge_index[JG].cpu().numpy(), og, oj)
+
+    def _candidate_mask(self, out=None):
+        """The live mask with the boundary grains' words at 0 (int32 [n_grain]; `out`: a pinned staging array)."""
+        cand = self.mask["grain"][:, 0].astype(np.int32) if out is None else out
+        if out is not None:
+            out[:] = self.mask["grain"][:, 0]
+        cand[self._traj["boundary_grains"]] = 0
+        return cand
 
     def _enable_ensemble(self, ens):
         """The device side of the per-trajectory layer: the offsets, the `ended` words and ONE buffer of 2 + 2 n_traj count
@@ -819,7 +881,7 @@ class GrainRollout:
         E["rewired"] += 1
         ended = E["ended_host"].numpy()
         res = ens.apply(N["xj"], N["yj"], N["yg"][:, 0], N["prob"][:n_e], N["area"], mg, mj, self._ev_host.numpy()[2:], ended,
-                        self.area_threshold, self.edge_threshold, N["lists"])
+                        self.area_threshold, self.edge_threshold, N["lists"], skip_local_grain=0 if self.noflux else None)
         for t, message in res["refused"].items():
             self._end_trajectory(t, message)
         if res["refused"]:
@@ -927,7 +989,7 @@ class GrainRollout:
                                   self.graph.edge_index[ET_JJ], self._logit_trigger, self._ev_flags, skip_grain=self._skip_grain())
         else:   # per trajectory: [2 + 2 n_traj] words, the totals over the running trajectories first
             E = self._ens
-            self.be.detect_events_traj(p["grain_area"], self._live_grain, self.area_threshold, p["edge_event"],
+            self.be.detect_events_traj(p["grain_area"], self._cand_grain, self.area_threshold, p["edge_event"],
                                        self.graph.edge_index[ET_JJ], self._logit_trigger, E["grain_off"], E["joint_off"],
                                        self._ev_flags[2:], self._ev_flags[:2], ended=E["ended"])
         self._ev_host.copy_(self._ev_flags, non_blocking=True)
@@ -1230,6 +1292,9 @@ class GrainRollout:
                          "lists": torch.empty(cap, dtype=torch.int64).pin_memory(),
                          "live": torch.empty(ng, dtype=torch.int32).pin_memory()}
         B["np"] = {k: B[k].numpy() for k in ("area", "prob", "xj", "yj", "yg", "lists", "live")}
+        if self._traj is not None:   # (the candidate mask of a no-flux union follows the live mask)
+            B["cand"] = torch.empty(ng, dtype=torch.int32).pin_memory()
+            B["np"]["cand"] = B["cand"].numpy()
         return B
 
     def _topology_session(self):
@@ -1323,6 +1388,9 @@ class GrainRollout:
         if len(events):
             B["np"]["live"][:] = self.mask["grain"][:, 0]
             self._live_grain.copy_(B["live"], non_blocking=True)
+            if self._traj is not None:
+                self._candidate_mask(B["np"]["cand"])
+                self._cand_grain.copy_(B["cand"], non_blocking=True)
         C = self._cap
         if C is not None and n_pp <= C["cap"][ET_JJ] and n_pq <= C["cap"][JG] and n_pq <= C["cap"][GJ]:
             jj, jg = C["lists"][ET_JJ][:2 * n_pp].view(2, n_pp), C["lists"][JG][:2 * n_pq].view(2, n_pq)

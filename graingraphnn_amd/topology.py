@@ -214,6 +214,21 @@ def check_traj_offsets(traj_offsets, n_grain: int, n_joint: int):
     return og, oj
 
 
+def check_noflux_union(grain_off, joint_off):
+    """A no-flux union's offsets (check_traj_offsets' arrays): every trajectory's local grain 0 is its boundary grain, so a
+    trajectory with junctions must own at least one grain (and one with grains has junctions: the boundary step reaches a
+    trajectory through its junctions); equal offsets on both sides are an empty trajectory.  GGNNError otherwise.  Returns
+    the boundary grains (global indices) of the trajectories that have nodes."""
+    ng, nj = np.diff(grain_off), np.diff(joint_off)
+    bad = np.flatnonzero((ng == 0) != (nj == 0))
+    if bad.size:
+        t = int(bad[0])
+        raise _lib.GGNNError(f"traj_offsets: trajectory {t} has {int(ng[t])} grains and {int(nj[t])} junctions -- with "
+                             "boundary='noflux' every non-empty trajectory owns at least one grain, its boundary grain, "
+                             "and the junctions on its walls")
+    return np.asarray(grain_off[:-1][ng > 0], np.int64)
+
+
 class EnsembleSessions:
     """One TopologySession per trajectory of a disjoint-union graph: the reference's `Cmodel.update` sweeps,
     sorts and asserts over the WHOLE lists it is given (models.py:712-757, 730), so a union's events must be applied
@@ -258,12 +273,15 @@ class EnsembleSessions:
 
     def apply(self, x_joint: np.ndarray, y_joint: np.ndarray, y_grain_area: np.ndarray, edge_prob: np.ndarray,
               grain_area: np.ndarray, mask_grain: np.ndarray, mask_joint: np.ndarray, counts, ended, area_threshold: float,
-              threshold: float, lists: Optional[np.ndarray] = None):
+              threshold: float, lists: Optional[np.ndarray] = None, skip_local_grain: Optional[int] = None):
         """One update of the union.  The arrays are the union's (x_joint [N_j, >= 8], y_joint [N_j, 2] fp32 C-contiguous,
         y_grain_area a float32 vector view [N_g] of the predicted area changes, edge_prob [n_pp] fp32, grain_area [N_g] the
         predicted areas, the int64 masks [N, 1] or [N]); every trajectory that has not `ended` and has a non-zero row of
         `counts` [n_traj, 2] gets its own update on its contiguous slices, in place: grain candidates = its live grains with
-        grain_area < area_threshold, smallest first (stable), as test.py:418-420 on that trajectory alone.  A TopologyError ends at that trajectory: its slices and its session stay untouched.
+        grain_area < area_threshold, smallest first (stable), as test.py:418-420 on that trajectory alone, without the
+        trajectory's grain `skip_local_grain` (local index; the no-flux boundary grain 0, dropped behind the sort as
+        test.py:421-422 does; None: nobody).  A TopologyError ends at that trajectory: its slices and its session stay
+        untouched.
         When a trajectory changed, the new union lists -- every trajectory's lists plus its node offsets, concatenated in
         trajectory order -- are written into `lists` (flat int64: [2, n_pp] then [2, n_pq]; default: a fresh array).
         Returns a dict: events (global grain ids: trajectory order, each trajectory's own order inside), switches
@@ -285,6 +303,8 @@ class EnsembleSessions:
             area = grain_area[g0:g1]
             ge = np.flatnonzero((mg[g0:g1] > 0) & (area < thr))
             ge = ge[np.argsort(area[ge], kind="stable")]
+            if skip_local_grain is not None:
+                ge = ge[ge != skip_local_grain]
             try:
                 ev, sw = self.sessions[t].apply(x_joint[j0:j1], y_joint[j0:j1], y_grain_area[g0:g1], edge_prob[seg_pp[t]:seg_pp[t + 1]], ge,
                                                 mg[g0:g1], mj[j0:j1], threshold)

@@ -102,6 +102,20 @@ typedef struct ggnn_csr_mask {
 } ggnn_csr_mask;
 int ggnn_build_csr_batch(const ggnn_csr_args* problems, const ggnn_csr_mask* masks /* [n_problems], or NULL: no list masked */,
                          int n_problems, ggnn_stream_t stream);
+/* Masked tables of a disjoint union of n_traj trajectories (a no-flux ensemble: every trajectory has a boundary grain of its
+ * own, its local grain 0).  Per list a ggnn_csr_union: src_off / dst_off = [n_traj + 1] int64 device offsets of the source /
+ * destination node type, rising from 0 to the node count (equal offsets: an empty trajectory), or NULL: that side is not
+ * split.  The list's skip_src / skip_dst then mean LOCAL indices on the sides that are split: an edge is left out when
+ * s - src_off[traj(s)] == skip_src or d - dst_off[traj(d)] == skip_dst, traj(v) = the last trajectory whose offset is <= v
+ * (with skip 0: the node is one of the offsets of a trajectory that has nodes).  Tables, slot order, perm into the FULL list
+ * and E_kept as above.  unions == NULL, or both pointers NULL: ggnn_build_csr_batch. */
+typedef struct ggnn_csr_union {
+  const int64_t* src_off;
+  const int64_t* dst_off;
+  int64_t n_traj;
+} ggnn_csr_union;
+int ggnn_build_csr_batch_traj(const ggnn_csr_args* problems, const ggnn_csr_mask* masks,
+                              const ggnn_csr_union* unions /* [n_problems], or NULL */, int n_problems, ggnn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Per-edge record in CSR order, computed once per forward and shared by every gate of the
@@ -627,7 +641,11 @@ int ggnn_detect_events_traj(const float* grain_area, const int32_t* live_grain, 
                             const int64_t* traj_joint_off /* [n_traj + 1], device */, int64_t n_traj,
                             const int32_t* ended /* NULL, or [n_traj] device words: non-zero = the trajectory takes part in
                                                     no events any more, its candidates are not counted */,
-                            int64_t skip_local_grain /* must be -1: no-flux unions are not supported yet */,
+                            int64_t skip_local_grain /* must be -1.  A no-flux union keeps its boundary grains (every
+                                                        trajectory's local grain 0) out of the count through live_grain: it
+                                                        passes a candidate mask, the live mask with those grains' words at 0
+                                                        (the live mask itself keeps 1 there: the QoI and the topology
+                                                        sessions read it) */,
                             int32_t* counts, int32_t* flags, int32_t* range_word, ggnn_stream_t stream);
 /* --- No-flux boundary (test.py:446-466, graph_datastruct.py:689-708 with traj.BC == 'noflux') ---
  * Grain 0 is the boundary grain that wraps the domain.
@@ -642,6 +660,18 @@ int ggnn_detect_events_traj(const float* grain_area, const int32_t* live_grain, 
 int ggnn_noflux_boundary(const int32_t* rowptr_jg, const int32_t* col_jg, float* x_joint, int64_t n_joint,
                          int64_t ldx_joint, const float* domain_offset, float domain_factor, float max_y,
                          float* x_grain, int64_t ldx_grain, int f_grain, float* joints_before, ggnn_stream_t stream);
+/* The boundary step for a disjoint union of n_traj trajectories, one launch of the same kernel: trajectory t owns the
+ * junctions [traj_joint_off[t], traj_joint_off[t + 1]) and the grains from traj_grain_off[t] on, its boundary grain is its
+ * first one, g0 = traj_grain_off[t].  Per trajectory with junctions: row g0 of x_grain reset as above, the junctions of row
+ * g0 of the FULL joint->grain CSR snapped to the nearest wall; every junction of the union clamped.  domain_factor, max_y:
+ * one box for the whole union; domain_offset: [n_joint, 2], the trajectories' concatenated.  The offsets ([n_traj + 1] int64,
+ * device) rise from 0 to the node counts; a trajectory with junctions must own at least one grain (equal offsets: an empty
+ * trajectory, skipped).  ggnn_noflux_boundary is the case of one trajectory. */
+int ggnn_noflux_boundary_traj(const int32_t* rowptr_jg, const int32_t* col_jg, float* x_joint, int64_t n_joint,
+                              int64_t ldx_joint, const float* domain_offset, float domain_factor, float max_y,
+                              float* x_grain, int64_t ldx_grain, int f_grain, float* joints_before,
+                              const int64_t* traj_grain_off, const int64_t* traj_joint_off, int64_t n_traj,
+                              ggnn_stream_t stream);
 /* --- Quantities of interest of a rollout (graph_trajectory.py:1042-1051 GNN_update "qoi", :221-242 volume('graph'),
  * :244-256 qoi) ---
  * Per trajectory t = grains [traj_offsets[t], traj_offsets[t+1]) of a disjoint-union graph, with F = domain_factor,
