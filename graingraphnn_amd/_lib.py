@@ -50,7 +50,7 @@ EXPORTED_SYMBOLS = (
     "ggnn_heads_classifier", "ggnn_step_update", "ggnn_grain_centres", "ggnn_detect_events", "ggnn_detect_events_traj", "ggnn_topology_update", "ggnn_topology_open", "ggnn_topology_apply",
     "ggnn_topology_counts", "ggnn_topology_export", "ggnn_topology_close", "ggnn_step_refresh",
     "ggnn_workspace_bytes",
-    "ggnn_qoi_accumulate", "ggnn_qoi_finalize",
+    "ggnn_qoi_accumulate", "ggnn_qoi_finalize", "ggnn_process_schedule",
 )
 
 
@@ -447,6 +447,9 @@ def _declare(lib):
     lib.ggnn_qoi_finalize.restype = c_int
     lib.ggnn_qoi_finalize.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, ctypes.c_double, c_void_p,
                                       c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.ggnn_process_schedule.restype = c_int
+    lib.ggnn_process_schedule.argtypes = [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p]
     lib.ggnn_workspace_bytes.restype = c_size_t
     lib.ggnn_workspace_bytes.argtypes = [c_int64, c_int64, c_int64]
 

@@ -1126,6 +1126,29 @@ class HipBackend:
         A.init = 1 if init else 0
         check(self.lib.ggnn_qoi_accumulate(ctypes.byref(A), _lib.current_stream()), "ggnn_qoi_accumulate")
 
+    def process_schedule(self, x_joint, table, traj_joint_off, step_in, step_out, sync_word):
+        """The (G, R) features of the step to come from a device-side table (include/ggnn.h, ggnn_process_schedule), one
+        launch: x_joint[:, 3:5] <- table[min(max(*step_in + 1, 0), n_rows - 1), trajectory of the junction], *step_out <-
+        *step_in + 1.  table: fp32 [n_rows, n_traj, 2]; traj_joint_off: int64 [n_traj + 1] on the device, or None (one
+        trajectory); step_in / step_out / sync_word: int32 device words (step_in and step_out may be the same)."""
+        _require_cuda(x_joint, table, traj_joint_off, step_in, step_out, sync_word)
+        _f32c(x_joint, "x_joint")
+        _f32c(table, "table")
+        if table.dim() != 3 or table.size(2) != 2 or table.size(0) < 1 or table.size(1) < 1:
+            raise _lib.GGNNError("table must be fp32 [n_rows, n_traj, 2]")
+        if traj_joint_off is None:
+            if table.size(1) != 1:
+                raise _lib.GGNNError("a table of several trajectories needs traj_joint_off")
+        elif traj_joint_off.dtype != torch.int64 or traj_joint_off.numel() != table.size(1) + 1 \
+                or not traj_joint_off.is_contiguous():
+            raise _lib.GGNNError("traj_joint_off must be a contiguous int64 [n_traj + 1]")
+        for w in (step_in, step_out, sync_word):
+            if w.dtype != torch.int32 or w.numel() < 1:
+                raise _lib.GGNNError("step_in / step_out / sync_word must be int32 words")
+        check(self.lib.ggnn_process_schedule(ptr(x_joint), x_joint.size(0), x_joint.stride(0), ptr(table), table.size(0),
+                                             table.size(1), ptr(traj_joint_off), ptr(step_in), ptr(step_out), ptr(sync_word),
+                                             _lib.current_stream()), "ggnn_process_schedule")
+
     def qoi_finalize(self, V0, T, e, traj_offsets, mesh_size, bin_edges=None):
         """(volume [n_grain], size [n_grain], d_mu [n_traj], d_std [n_traj], counts [n_traj, n_edges - 1] int32 or None) of
         ggnn_qoi_finalize; bin_edges: ascending fp32 [n_edges] on the device, or None."""

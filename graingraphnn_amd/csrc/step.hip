@@ -3,6 +3,7 @@
 //                       + z advance (test.py:401-402)
 //   ggnn_step_refresh = z clamp (test.py:405-407) + edge-length refresh (test.py:562-575)
 //   ggnn_noflux_boundary[_traj] = the no-flux boundary step (test.py:446-463), after the topology update
+//   ggnn_process_schedule = the (G, R) features of the step to come (test.py:376-379), row by a device-side counter
 //   ggnn_grain_centres = region centres of graph.update() (graph_datastruct.py:681-708) written
 //                       to x_grain[:, :2] (test.py:468-478, 556-559), between the two
 // Separate launches because each stage needs every node's updated coordinates.
@@ -296,6 +297,49 @@ __global__ __launch_bounds__(256) void noflux_boundary_kernel(
   }
 }
 
+// The process parameters of the step to come (test.py:376-379), from a table of feature values on the device: one thread per
+// junction, two 4-byte stores (columns 3 and 4; a row's column 3 is not 8-byte aligned for every ldx).  The table's row
+// follows a device-side counter, so that a captured graph replays with the counter where the replay before left it (the
+// mechanism of the QoI layer counter, qoi.hip): every block reads the counter at its top, and the last block to finish -- by
+// then every block has read it -- stores counter + 1, which may go to the same word.  A junction's trajectory is the last
+// offset <= the junction (bnd_traj_of); the offsets and the table's current row are staged in LDS while they fit
+// (SCH_LDS_TRAJ), read from global memory beyond that; `staged` depends on kernel arguments only, so the barrier behind the
+// staging is reached by every thread of every block or by none.
+constexpr int SCH_LDS_TRAJ = 512;   // 513 offsets of 8 bytes + 512 rows of 8 bytes: 8 KiB
+__global__ __launch_bounds__(256) void process_schedule_kernel(
+    float* __restrict__ x_joint, int64_t n_joint, int64_t ldxj, const float* __restrict__ table, int64_t n_rows, int n_traj,
+    const int64_t* __restrict__ traj_joint_off, const int32_t* step_in, int32_t* step_out, int32_t* sync_word) {
+  __shared__ int64_t s_off[SCH_LDS_TRAJ + 1];
+  __shared__ float s_row[2 * SCH_LDS_TRAJ];
+  const int32_t k = *step_in;
+  // the row of the step to come, inside the table for any counter: negative ones land on row 0, late ones on the last row
+  const int64_t r = min(max((int64_t)k + 1, (int64_t)0), n_rows - 1);
+  const float* row = table + r * (2 * (int64_t)n_traj);
+  const bool staged = traj_joint_off != nullptr && n_traj <= SCH_LDS_TRAJ;
+  if (staged) {
+    for (int i = threadIdx.x; i <= n_traj; i += 256) s_off[i] = traj_joint_off[i];
+    for (int i = threadIdx.x; i < 2 * n_traj; i += 256) s_row[i] = row[i];
+    __syncthreads();
+  }
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j < n_joint) {
+    const int t = traj_joint_off == nullptr ? 0 : bnd_traj_of(staged ? s_off : traj_joint_off, n_traj, j);
+    const float* v = staged ? s_row : row;
+    float* x = x_joint + j * ldxj;
+    x[3] = v[2 * t];
+    x[4] = v[2 * t + 1];
+  }
+  // the last block to get here has seen every other block read the counter
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    __threadfence();
+    if (atomicAdd(sync_word, 1) == (int32_t)gridDim.x - 1) {
+      *sync_word = 0;
+      *step_out = k < INT32_MAX ? k + 1 : k;
+    }
+  }
+}
+
 struct RefreshArgs {
   ggnn_refresh_edge et[3];
   int64_t e_off[4];  // prefix sums of E over the edge types
@@ -409,6 +453,20 @@ extern "C" int ggnn_noflux_boundary(const int32_t* rowptr_jg, const int32_t* col
   hipLaunchKernelGGL(noflux_boundary_kernel<false>, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, rowptr_jg, col_jg,
                      x_joint, n_joint, ldx_joint, domain_offset, domain_factor, max_y, x_grain, ldx_grain, f_grain,
                      joints_before, (const int64_t*)nullptr, (const int64_t*)nullptr, 1);
+  return launch_status();
+}
+
+extern "C" int ggnn_process_schedule(float* x_joint, int64_t n_joint, int64_t ldx_joint, const float* table, int64_t n_rows,
+                                     int64_t n_traj, const int64_t* traj_joint_off, const int32_t* step_in, int32_t* step_out,
+                                     int32_t* sync_word, ggnn_stream_t stream) {
+  using namespace ggnn;
+  if (!x_joint || !table || !step_in || !step_out || !sync_word) return GGNN_EINVAL;
+  if (n_joint <= 0 || ldx_joint < 5 || n_rows < 1 || n_traj < 1 || n_traj > (1 << 29)) return GGNN_EINVAL;
+  if (!traj_joint_off && n_traj != 1) return GGNN_EINVAL;
+  const int64_t nblk = (n_joint + 255) / 256;
+  if (nblk >= INT32_MAX) return GGNN_EINVAL;
+  hipLaunchKernelGGL(process_schedule_kernel, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, x_joint, n_joint,
+                     ldx_joint, table, n_rows, (int)n_traj, traj_joint_off, step_in, step_out, sync_word);
   return launch_status();
 }
 

@@ -146,7 +146,7 @@ def run_sharded(n_traj: int, run_one: Callable[[int], torch.Tensor], rank: int, 
 def rollout_trajectories(rmodel, cmodel, graphs, span: int, n_steps: int, rank: int = 0,
                          world: int = 1, device="cuda", use_graph: bool = True,
                          refresh_centres: bool = False, qoi=None, events=None, boundary: str = "periodic",
-                         max_y: float = 1.0, domain_factor: float = 1.0, domain_offsets=None):
+                         max_y: float = 1.0, domain_factor: float = 1.0, domain_offsets=None, schedule=None):
     """BASELINE config 4: `graphs[t]` = (x, ei, ea) numpy dicts of independent trajectories with
     EQUAL node counts.  Rank r rolls out trajectories t = r (mod world) as ONE disjoint-union
     graph on its GPU (one set of launches for the whole shard), then all ranks all-gather the
@@ -164,7 +164,10 @@ def rollout_trajectories(rmodel, cmodel, graphs, span: int, n_steps: int, rank: 
     `boundary`: "periodic", or "noflux" -- every trajectory is a no-flux domain whose grain 0 is its boundary grain; the
     shard's union is built with its trajectory offsets (GrainRollout(boundary="noflux", traj_offsets=...)), `max_y` and
     `domain_factor` are the one box of all trajectories.  `domain_offsets`: per trajectory the [N_j, 2] offsets of
-    scale_feature_patchs, needed when domain_factor > 1 and the grain centres or the no-flux boundary use them."""
+    scale_feature_patchs, needed when domain_factor > 1 and the grain centres or the no-flux boundary use them.
+    `schedule`: None, or the process parameters of every step per trajectory of the WHOLE ensemble, {'G': [T, n_rows],
+    'R': [T, n_rows]} or {'features': [T, n_rows, 2]} (GrainRollout.set_process_schedule): each rank takes the rows of its
+    shard, every trajectory follows its own (G, R) history on the device.  The returned keys are unchanged."""
     from . import synthetic
     from .rollout import GrainRollout
 
@@ -194,6 +197,12 @@ def rollout_trajectories(rmodel, cmodel, graphs, span: int, n_steps: int, rank: 
         ro.enable_events(mask, events["area_threshold"], events["edge_threshold"], traj_offsets=None if noflux else offsets)
     if qoi is not None:
         ro.enable_qoi(**dict(qoi, traj_offsets=None if noflux else offsets["grain"]))
+    if schedule is not None:
+        # [T, n_rows, ...] of the ensemble -> [n_rows, the shard's trajectories, ...]
+        take = lambda a: np.moveaxis(np.asarray(a)[mine], 0, 1)
+        if set(schedule) not in ({"G", "R"}, {"features"}):
+            raise ValueError("schedule must be {'G', 'R'} or {'features'}, one entry per trajectory")
+        ro.set_process_schedule(**{k: take(v) for k, v in schedule.items()}, traj_offsets=None if noflux else offsets)
     if events is None:
         ro.run(n_steps)
         local = {"joint_xy": torch.stack([X["joint"][lo:hi, :2] for lo, hi in (s["joint"] for s in slices)]),

@@ -253,3 +253,34 @@ def reference_sample(lxd: float = 40.0, seed: int = 0, G: float = 2.0, R: float 
     ea = {EDGE_TYPES[0]: gl, EDGE_TYPES[1]: gl.copy(), EDGE_TYPES[2]: np.array(jj_len, dtype=np.float32)[:, None]}
     x = {"grain": fg.astype(np.float32), "joint": fj.astype(np.float32)}
     return x, ei, ea
+
+
+def reference_gr_schedule(seed, freq, ini_height, final_height, delta_z):
+    """The (G, R) schedule of the reference's `--temporal` mode (graph_trajectory.py:129-155 GR_seq_from_time with
+    TemperatureProfile3DAnalytic.py:18-43 RandGR; test.py:346 calls it with freq = 2 ** (seed % 10) and delta_z =
+    train_delta_z * span): two random Fourier series in time, `freq` terms each -- amplitudes and phases drawn from the
+    legacy stream seeded with `seed`, G's amplitudes, G's phases, R's amplitudes, R's phases, term i damped by 1 / (i + 1) --
+    rescaled to G in [0.5, 10] K/um and R in [0.2, 2] m/s over 501 instants up to t_end = height / 0.2; the height reached
+    at every instant is the trapezoid integral of R, and both series are interpolated linearly (scipy's interp1d, as there)
+    at the mid-heights of the layers, delta_z * (0.5, 1.5, ...).  Returns (G_list, R_list), float64, one entry per layer:
+    row k is what GrainRollout.set_process_schedule(G, R) hands to step k.  The same operations in the same order through
+    the same libraries: pinned bit for bit by tests/golden/gr_schedule.npz (tests/golden/make_golden_gr_schedule.py)."""
+    from scipy.interpolate import interp1d
+    rs = np.random.RandomState(seed)
+    height = final_height - ini_height
+    t_end = height / 0.2
+    t = np.linspace(0, t_end, 501)
+    omega = np.arange(1, freq + 1) / t_end * math.pi / 2
+    g_amp, g_phase = rs.rand(len(omega)), rs.rand(len(omega)) * 2 * math.pi
+    r_amp, r_phase = rs.rand(len(omega)), rs.rand(len(omega)) * 2 * math.pi
+    G, R = np.zeros(len(t)), np.zeros(len(t))
+    for i in range(freq):
+        G += g_amp[i] * np.cos(omega[i] * t + g_phase[i]) / (i + 1)
+        R += r_amp[i] * np.sin(omega[i] * t + r_phase[i]) / (i + 1)
+    G = 0.5 + 9.5 * (G - np.min(G)) / (np.max(G) - np.min(G))
+    R = 0.2 + 1.8 * (R - np.min(R)) / (np.max(R) - np.min(R))
+    z = np.zeros(len(R))
+    z[1:] = 0.5 * np.cumsum(R[1:] + R[:-1]) * (t[1] - t[0])
+    layers = int(np.round(height / delta_z))
+    z_mid = delta_z * np.arange(0.5, layers)
+    return interp1d(z, G)(z_mid), interp1d(z, R)(z_mid)

@@ -53,6 +53,36 @@ def resolve_traj_offsets(own, passed, what):
     return own
 
 
+def process_schedule_table(G=None, R=None, features=None):
+    """The feature table of GrainRollout.set_process_schedule: (fp32 [n_rows, n_traj, 2], whether every trajectory shares
+    one column).  From G and R ([n_rows] or [n_rows, n_traj]): 1 - G / 10 and R / 2 computed in float64 and rounded to fp32
+    once -- the reference's assignment of a float64 scalar into a float32 tensor (test.py:378-379); or `features` ([n_rows, 2]
+    or [n_rows, n_traj, 2]) as they are."""
+    if (features is None) == (G is None and R is None) or (G is None) != (R is None):
+        raise _lib.GGNNError("set_process_schedule takes G and R, or features=, not both and not neither")
+    try:
+        if features is None:
+            g, r = np.asarray(G, np.float64), np.asarray(R, np.float64)
+            if g.shape != r.shape or g.ndim not in (1, 2):
+                raise _lib.GGNNError("G and R must have the same shape, [n_rows] or [n_rows, n_traj]")
+            table = np.stack(((1.0 - g / 10.0).astype(np.float32), (r / 2.0).astype(np.float32)), axis=-1)
+        else:
+            table = np.asarray(features)
+            if table.ndim not in (2, 3) or table.shape[-1] != 2:
+                raise _lib.GGNNError("features must be [n_rows, 2] or [n_rows, n_traj, 2]")
+            table = table.astype(np.float32)
+    except (TypeError, ValueError) as exc:
+        raise _lib.GGNNError(f"set_process_schedule: not a numeric array ({exc})") from exc
+    shared = table.ndim == 2
+    if shared:
+        table = table[:, None, :]
+    if table.shape[0] < 1 or table.shape[1] < 1:
+        raise _lib.GGNNError("a process schedule needs at least one row and one trajectory")
+    if not np.isfinite(table).all():
+        raise _lib.GGNNError("the process schedule must be finite")
+    return np.ascontiguousarray(table), shared
+
+
 class GrainRollout:
     JOINT_LAUNCH_MAX_JOINTS = 8000
 
@@ -117,6 +147,7 @@ class GrainRollout:
         self._xc_fresh = False
         self._graphs = None                   # run() / step() graphs per (steps, buffers): _replay
         self._qoi = None                      # enable_qoi(): the accumulator of grain volumes and its launch constants
+        self._sched = None                    # set_process_schedule(): the (G, R) table on the device and its counter word
         self._drop_segment_graphs()           # step_events()' segment graphs: _segment_graphs, _graph_fwd, _graph_ref
         self._set_topology(edge_index_dict, edge_attr_dict)
         self.span = span
@@ -161,9 +192,118 @@ class GrainRollout:
         of the step to come, written into the junction features (`x_joint[:, 3] = 1 - G / 10`, `x_joint[:, 4] = R / 2`)
         before the forwards.  The edge records of the next step carry the sources' features, so they are rebuilt: the
         in-place write bumps the tensor's version counter, which step() / run() check (`_ensure_edge_records`).  The
-        values themselves (graph_trajectory.py:129-175, GR_seq_from_time) are the caller's: call this between steps."""
+        values themselves (graph_trajectory.py:129-175, GR_seq_from_time) are the caller's: call this between steps.
+        (A whole schedule, on the device and inside run() / run_events(): set_process_schedule.)"""
+        if self._sched is not None:
+            raise _lib.GGNNError("a process schedule is set (set_process_schedule): the steps write the parameters themselves; "
+                                 "clear_process_schedule() first")
         self.x["joint"][:, 3] = 1.0 - float(G) / 10.0
         self.x["joint"][:, 4] = float(R) / 2.0
+
+    # -- the (G, R) schedule on the device (DESIGN.md 8f) -----------------------------------------------------------------
+    @torch.no_grad()
+    def set_process_schedule(self, G=None, R=None, *, features=None, traj_offsets=None):
+        """The reference's `--temporal` schedule (test.py:345-346, 376-379) as a table on the device: row r holds the
+        thermal gradient and the pulling speed of the r-th step from this call, and from now on the tail of every step writes
+        the row of the step to come into x_joint[:, 3:5] (one launch, ggnn_process_schedule, behind the boundary step, the
+        centres and the QoI launch and in front of the launch that builds the next step's edge records) -- in step(), run(),
+        step_events() and run_events(), eager and inside their hipGraphs: the row follows a counter word on the device.
+        Row 0 is written now (an in-place write: the edge records are rebuilt before the next step); past the last row the
+        last row holds, so after K steps x holds row min(K, n_rows - 1) (with n_rows = the number of steps: what the
+        reference leaves).  Calling it again restarts at row 0 (a table of the same shape on the same offsets goes into
+        the buffers of the one before: the captured graphs stay).
+        G, R: arrays [n_rows] (every trajectory the same) or [n_rows, n_traj]; the features 1 - G / 10 and R / 2 are computed
+        in float64 and rounded to fp32 once, as the reference's assignment does.  OR features: [n_rows, 2] or
+        [n_rows, n_traj, 2], the fp32 feature values themselves.  Values must be finite.
+        traj_offsets: for [.., n_traj] tables on a periodic union, {'joint': [n_traj + 1]} (or the {'grain', 'joint'} dict of
+        enable_events); a no-flux union uses its constructor's offsets (None here, or equal ones).
+        generator.reference_gr_schedule makes the reference's own (G, R) lists."""
+        table, shared = process_schedule_table(G, R, features)
+        off = self._schedule_offsets(traj_offsets)
+        if shared:
+            off = None   # one row for every junction: the launch needs no offsets
+        elif off is None:
+            if table.shape[1] != 1:
+                raise _lib.GGNNError(f"a schedule of {table.shape[1]} trajectories needs traj_offsets={{'joint': [...]}} "
+                                     "(a no-flux union: the constructor's)")
+        elif off.size != table.shape[1] + 1:
+            raise _lib.GGNNError(f"the schedule has {table.shape[1]} trajectories, the offsets {off.size - 1}")
+        if off is not None and off.size == 2:
+            off = None
+        dev = self.x["joint"].device
+        S = self._sched
+        if S is not None and S["table_host"].shape == table.shape and (
+                (off is None) == (S["offsets_host"] is None) and (off is None or np.array_equal(off, S["offsets_host"]))):
+            # the same launch on the same buffers (another history of an ensemble sweep): new values, counter back to 0,
+            # and every captured graph stays
+            S["table_host"] = table
+            S["table"].copy_(torch.from_numpy(table))
+            S["home"]["flat"].zero_()
+            S["at"] = None
+        else:
+            S = self._sched = {"name": "sched", "table_host": table, "table": torch.from_numpy(table).to(dev),
+                               "offsets_host": off, "offsets": None if off is None else torch.from_numpy(off).to(dev),
+                               "sync": torch.zeros(1, dtype=torch.int32, device=dev), "new": self._sched_state,
+                               "home": self._sched_state(), "ring": None, "entries": None, "launched": 0, "at": None}
+            self._schedule_changed()
+        # row 0, the step to come: an in-place write, seen by the version check of _ensure_edge_records
+        row0 = S["table"][0]
+        if off is not None:
+            counts = torch.from_numpy(np.diff(off)).to(dev)
+            row0 = torch.repeat_interleave(row0, counts, dim=0)
+        self.x["joint"][:, 3:5] = row0
+        self._einfo_fresh = False
+        self._x_written_outside()
+
+    def clear_process_schedule(self):
+        """No schedule any more: the steps make the launches they made before set_process_schedule, x keeps the parameters
+        it holds, and set_process_parameters works again."""
+        if self._sched is not None:
+            self._sched = None
+            self._schedule_changed()
+
+    def _schedule_changed(self):
+        """The launch list changed: every captured graph lacks (or has) the schedule's launch."""
+        self._graphs = None
+        self._drop_segment_graphs()
+        if self._spec is not None:
+            self._spec["graphs"], self._spec["captured"] = {}, None
+
+    def _schedule_offsets(self, passed):
+        """The junction offsets a schedule's trajectories are found with (int64 [n_traj + 1], host), or None: a no-flux
+        union's own (passed ones must be equal), else the call's ({'joint': [...]} or the full dict)."""
+        nj = self.n_nodes["joint"]
+        if self.noflux:
+            if self._traj is not None and isinstance(passed, dict) and "grain" not in passed:
+                passed = dict(passed, grain=self._traj["grain"])
+            own = resolve_traj_offsets(None if self._traj is None else (self._traj["grain"], self._traj["joint"]), passed,
+                                       "set_process_schedule")
+            return None if own is None else own[1]
+        if passed is None:
+            return None
+        try:
+            off = np.asarray(passed["joint"], dtype=np.int64).reshape(-1)
+        except (KeyError, TypeError, ValueError, IndexError) as exc:
+            raise _lib.GGNNError("set_process_schedule: traj_offsets must be {'joint': [n_traj + 1]}") from exc
+        if off.size < 2 or off[0] != 0 or off[-1] != nj or (np.diff(off) < 0).any():
+            raise _lib.GGNNError("traj_offsets['joint'] must rise from 0 to the number of junctions")
+        return off
+
+    def _sched_state(self):
+        """One counter word of the schedule (`flat`: what a state is copied by, as the QoI accumulator's)."""
+        return {"flat": torch.zeros(1, dtype=torch.int32, device=self.x["joint"].device)}
+
+    def _enqueue_schedule(self, slot=None):
+        """The parameters of the step to come (off unless set_process_schedule was called): counter and row on the rollout's
+        own word in place, or -- a ring `slot` of the speculative event loop -- from the word of the slot before to the
+        slot's own."""
+        S = self._sched
+        if S is None:
+            return
+        src = dst = S["home"]
+        if slot is not None:
+            src, dst = S["ring"][(slot - 1) % len(S["ring"])], S["ring"][slot]
+        self.be.process_schedule(self.x["joint"], S["table"], S["offsets"], src["flat"], dst["flat"], S["sync"])
 
     def _pack_weights(self):
         """Fused device weights of both models, and the parameter versions they were packed from."""
@@ -425,6 +565,7 @@ class GrainRollout:
         delta_h = self.span * (final_height - ini_height) / mesh_size / (frames - 1)
         f32 = dict(dtype=torch.float32, device=dev)
         Q = self._qoi = {
+            "name": "qoi", "new": self._qoi_state,
             "const": (self.domain_factor, patch_size / mesh_size + 1, delta_h), "mesh_size": float(mesh_size),
             "capacity": int(capacity), "offsets_host": off, "offsets": torch.from_numpy(off).to(dev),
             "V0": torch.empty(ng, **f32), "home": self._qoi_state(), "words": torch.zeros(2, dtype=torch.int32, device=dev),
@@ -464,37 +605,50 @@ class GrainRollout:
                                Q["const"], src, dst, Q["V0"], Q["words"][:1], Q["words"][1:], Q["history"], Q["capacity"],
                                Q["area_sum"], init=init, area0=area0)
 
-    def _qoi_home(self):
-        """Behind run_events the current accumulator is the last committed step's ring slot: back into the rollout's own."""
-        Q = self._qoi
-        if Q is not None and Q["at"] is not None:
-            self._qoi_take(Q["ring"][Q["at"]])
+    # -- what a step advances beside x: the QoI accumulator and the schedule's counter (run_events keeps them per slot) ----
+    def _carried(self):
+        """The device state a step advances beside x, each a dict with `home` (the rollout's own, advanced in place), `ring`
+        / `entries` / `launched` / `at` (run_events' copies, _carry_enter_block) and `new` (makes one state; a state is copied
+        through its `flat` tensor): the QoI accumulator (enable_qoi) and the schedule's counter word (set_process_schedule)."""
+        return [c for c in (self._qoi, self._sched) if c is not None]
 
-    def _qoi_take(self, state):
-        self._qoi["home"]["flat"].copy_(state["flat"])
-        self._qoi["at"] = None
+    @staticmethod
+    def _carry_home_one(c):
+        if c["at"] is not None:
+            c["home"]["flat"].copy_(c["ring"][c["at"]]["flat"])
+            c["at"] = None
 
-    def _qoi_enter_block(self, slots):
-        """Before a block of speculative steps: the slot before its first one holds the current accumulator, and a copy of
-        it is kept for the case that the block's first step is eventful (two full blocks in flight fill the ring: the last
-        step of the second one overwrites that slot).  Two copies alternate: at most two blocks are unchecked."""
-        Q = self._qoi
-        if Q is None:
-            return None
-        D = self._spec["D"]
-        if Q["ring"] is None or len(Q["ring"]) != D:
-            self._qoi_home()
-            Q["ring"], Q["entries"] = [self._qoi_state() for _ in range(D)], [self._qoi_state() for _ in range(2)]
-            self._spec["graphs"], self._spec["captured"] = {}, None
-        before = Q["ring"][(slots[0] - 1) % D]
-        if Q["at"] != (slots[0] - 1) % D:
-            self._qoi_home()
-            before["flat"].copy_(Q["home"]["flat"])
-        entry = Q["entries"][Q["launched"] & 1]
-        Q["launched"] += 1
-        entry["flat"].copy_(before["flat"])
-        Q["at"] = slots[-1]
-        return entry
+    def _carry_home(self):
+        """Behind run_events the current states are the last committed step's ring slot: back into the rollout's own."""
+        for c in self._carried():
+            self._carry_home_one(c)
+
+    def _carry_take(self, pick):
+        """The rollout's own states := `pick(c)` of every carried state c."""
+        for c in self._carried():
+            c["home"]["flat"].copy_(pick(c)["flat"])
+            c["at"] = None
+
+    def _carry_enter_block(self, slots):
+        """Before a block of speculative steps: the slot before its first one holds the current states, and a copy of
+        them is kept for the case that the block's first step is eventful (two full blocks in flight fill the ring: the last
+        step of the second one overwrites that slot).  Two copies alternate: at most two blocks are unchecked.  Returns the
+        copies by the states' names."""
+        D, entries = self._spec["D"], {}
+        for c in self._carried():
+            if c["ring"] is None or len(c["ring"]) != D:
+                self._carry_home_one(c)
+                c["ring"], c["entries"] = [c["new"]() for _ in range(D)], [c["new"]() for _ in range(2)]
+                self._spec["graphs"], self._spec["captured"] = {}, None
+            before = c["ring"][(slots[0] - 1) % D]
+            if c["at"] != (slots[0] - 1) % D:
+                self._carry_home_one(c)
+                before["flat"].copy_(c["home"]["flat"])
+            entry = entries[c["name"]] = c["entries"][c["launched"] & 1]
+            c["launched"] += 1
+            entry["flat"].copy_(before["flat"])
+            c["at"] = slots[-1]
+        return entries
 
     def qoi(self):
         """The quantities of interest up to the last step (one synchronisation).  For one trajectory: `volume` and `size`
@@ -508,7 +662,7 @@ class GrainRollout:
         Q = self._qoi
         if Q is None:
             raise _lib.GGNNError("call enable_qoi(...) first")
-        self._qoi_home()
+        self._carry_home()
         H = Q["home"]
         T, e, ended = H["T"], H["e"], []
         if self._ens is not None:
@@ -636,6 +790,7 @@ class GrainRollout:
         if self.refresh_centres:
             self._enqueue_centres(centres_before)
         self._enqueue_qoi(slot)
+        self._enqueue_schedule(slot)
         if headed_prev is not None:
             main.wait_event(headed_prev)   # the previous step's classifier has read the set this refresh writes
         be.step_refresh_prepare(x["joint"], x["grain"], self.zmax, zf,
@@ -746,6 +901,7 @@ class GrainRollout:
         if self.refresh_centres:
             self._enqueue_centres()
         self._enqueue_qoi()
+        self._enqueue_schedule()
         be.step_refresh(x["joint"], x["grain"], self.zmax, self.flags,
                         [(self.graph.edge_index[et], x[et[0]], x[et[-1]], ea[et], self.graph.count_dev[et]) for et in EDGE_TYPES])
 
@@ -979,7 +1135,7 @@ class GrainRollout:
         if self.mask is None:
             raise _lib.GGNNError("call enable_events(mask, ...) first")
         self.refresh_weights(sample=self.steps_done % 16 != 0)
-        self._qoi_home()
+        self._carry_home()
         self._einfo_fresh = False   # this mode prepares its edge records at the start of every step
         self._x_written_outside()
         self._run_segment("fwd")
@@ -1128,7 +1284,7 @@ class GrainRollout:
 
     def _spec_launch(self, n: int):
         """Enqueue `n` speculative steps from the current slot on; returns (their slots, the event behind them, the QoI
-        accumulator the block started from or None: _qoi_enter_block)."""
+        accumulator and the schedule counter the block started from: _carry_enter_block)."""
         S = self._spec
         slots = [(S["cur"] + i) % S["D"] for i in range(n)]
         if S["xs_valid"] != slots[0]:   # the first step's copy of x (later ones get theirs from the refresh before them)
@@ -1136,7 +1292,7 @@ class GrainRollout:
                 S["xs"][slots[0]][nt].copy_(self.x[nt])
         S["xs_valid"] = (slots[-1] + 1) % S["D"]
         self._xc_fresh = False
-        entry = self._qoi_enter_block(slots)
+        entry = self._carry_enter_block(slots)
         if self.use_graph and n > 1:
             g = S["graphs"].get((slots[0], n))
             if g is None:
@@ -1236,8 +1392,9 @@ class GrainRollout:
                 self._spec_adopt(slot)
                 # the void steps refreshed the edge sets past this point: lengths and records are recomputed from x below
                 self._einfo_fresh = False
-            if self._qoi is not None:   # the accumulator as the eventful step found it: its layer is computed again
-                self._qoi_take(self._qoi["ring"][slots[hit - 1]] if hit else entry)
+            # the accumulator and the schedule's counter as the eventful step found them: its layer is computed, its row of
+            # the step to come written again (the same row: the tail is idempotent there)
+            self._carry_take(lambda c: c["ring"][slots[hit - 1]] if hit else entry[c["name"]])
             keep_centres = self.x["grain"][:, :2].clone()
             self.x["grain"][:, :2].copy_(S["cen"][slot])     # the centres the events must see: before the refresh
             if self.noflux:   # ... and the junctions: before the boundary step
@@ -1245,8 +1402,7 @@ class GrainRollout:
                 self.x["joint"][:, :2].copy_(S["jb"][slot])
             def stands():   # the step stands as enqueued (its refresh ran on the unchanged topology)
                 self.x["grain"][:, :2].copy_(keep_centres)
-                if self._qoi is not None:
-                    self._qoi_take(self._qoi["ring"][slot])
+                self._carry_take(lambda c: c["ring"][slot])
                 if self.noflux:
                     self.x["joint"][:, :2].copy_(keep_joints)
                 if void:   # ... but its edge lengths were overwritten by the void steps: the same kernel on the same x
@@ -1417,7 +1573,7 @@ class GrainRollout:
         """Advance one rollout step; returns the prediction dict (tensors are reused)."""
         if self.steps_done % 16 == 0:
             self.refresh_weights()
-        self._qoi_home()
+        self._carry_home()
         if self._pipelined():
             self._ensure_edge_records()
         if self.use_graph:
@@ -1435,7 +1591,7 @@ class GrainRollout:
         """`n_steps` static-topology steps.  With hipGraph replay the bulk goes through a graph of
         RUN_UNROLL consecutive steps (same kernels, same order, same results as step() x n)."""
         self.refresh_weights()
-        self._qoi_home()
+        self._carry_home()
         if self.use_graph and n_steps >= self.RUN_UNROLL:
             if self._pipelined():
                 self._ensure_edge_records()

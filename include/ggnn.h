@@ -672,6 +672,26 @@ int ggnn_noflux_boundary_traj(const int32_t* rowptr_jg, const int32_t* col_jg, f
                               float* x_grain, int64_t ldx_grain, int f_grain, float* joints_before,
                               const int64_t* traj_grain_off, const int64_t* traj_joint_off, int64_t n_traj,
                               ggnn_stream_t stream);
+/* --- Process parameters on the device (the reference's --temporal mode, test.py:345-346, 376-379) ---
+ * ggnn_process_schedule = the thermal gradient and pulling speed features of the step to come, one launch at the tail of a
+ * step, in front of the launch that builds the next step's edge records.  For every junction j of trajectory t
+ *   x_joint[j, 3] = table[r, t, 0],  x_joint[j, 4] = table[r, t, 1],  r = min(max(*step_in + 1, 0), n_rows - 1),
+ * and the launch leaves *step_in + 1 in *step_out (INT32_MAX stays): row r belongs to the r-th step from a counter of 0, a
+ * captured graph replays with the counter where the replay before left it, past the last row the last row holds, and the
+ * table is never addressed outside [0, n_rows) for any counter value.
+ * table: [n_rows, n_traj, 2] fp32, device: FEATURE values (1 - G / 10 and R / 2, rounded to fp32 once by the host from
+ * float64: the reference's assignment of a float64 scalar into a float32 tensor).  The kernel only copies: bit for bit.
+ * traj_joint_off: [n_traj + 1] int64, device, rising from 0 to n_joint; trajectories may have any size or be empty; a
+ * junction belongs to the last trajectory whose offset is <= the junction.  NULL: one trajectory (n_traj must be 1).
+ * Nothing but columns 3 and 4 of rows [0, n_joint) is written (no padding column of ldx_joint > the feature count).
+ * step_in / step_out: int32 device words, the same word or different ones (the speculative event loop keeps one per ring
+ * slot): every block reads the counter before the last block to finish stores it.  sync_word: one zeroed int32 device
+ * word, left zero by every launch; not shared by launches that may run concurrently.  The results do not depend on the
+ * grid.  GGNN_EINVAL: a NULL required pointer, n_joint < 1, n_rows < 1, n_traj < 1, ldx_joint < 5, NULL offsets with
+ * n_traj != 1. */
+int ggnn_process_schedule(float* x_joint, int64_t n_joint, int64_t ldx_joint, const float* table, int64_t n_rows,
+                          int64_t n_traj, const int64_t* traj_joint_off, const int32_t* step_in, int32_t* step_out,
+                          int32_t* sync_word, ggnn_stream_t stream);
 /* --- Quantities of interest of a rollout (graph_trajectory.py:1042-1051 GNN_update "qoi", :221-242 volume('graph'),
  * :244-256 qoi) ---
  * Per trajectory t = grains [traj_offsets[t], traj_offsets[t+1]) of a disjoint-union graph, with F = domain_factor,
