@@ -29,6 +29,10 @@ GGNN_FLAG_QOI_OVERFLOW = 2
 GGNN_ADAM_CHUNK, GGNN_ADAM_MAX_TENSORS, GGNN_ADAM_MAX_GROUPS = 4096, 384, 8
 GGNN_ROWGEMM_MAX_PACK = 8
 GGNN_MSE_MAX_TERMS, GGNN_MSE_BLOCKS = 4, 64
+GGNN_METRIC_MAX_TERMS, GGNN_METRIC_MAX_THR, GGNN_METRIC_BLOCKS = 4, 16, 64
+GGNN_METRIC_F64_SLOTS, GGNN_METRIC_I64_SLOTS = 9, 49      # err[4] | norm[4] | loss;  TP[16] | FP[16] | FN[16] | batches
+GGNN_METRIC_WS_WORDS = GGNN_METRIC_BLOCKS * 56 + 1
+METRIC_CLASSIFIER, METRIC_REGRESSOR = 0, 1   # GGNN_METRIC_*
 MODE_LSTM, MODE_LSTM_H0, MODE_RAW = 0, 1, 2
 BC_PERIODIC, BC_NOFLUX = 0, 1   # GGNN_BC_*
 
@@ -51,6 +55,7 @@ EXPORTED_SYMBOLS = (
     "ggnn_topology_counts", "ggnn_topology_export", "ggnn_topology_close", "ggnn_step_refresh",
     "ggnn_workspace_bytes",
     "ggnn_qoi_accumulate", "ggnn_qoi_finalize", "ggnn_process_schedule",
+    "ggnn_metric_record",
 )
 
 
@@ -325,6 +330,20 @@ class QoiArgs(Structure):
     ]
 
 
+class MetricArgs(Structure):
+    """Mirror of `ggnn_metric_args`."""
+    _fields_ = [
+        ("pred", c_void_p * GGNN_METRIC_MAX_TERMS), ("target", c_void_p * GGNN_METRIC_MAX_TERMS),
+        ("mask", c_void_p * GGNN_METRIC_MAX_TERMS), ("n_rows", c_int64 * GGNN_METRIC_MAX_TERMS),
+        ("ld", c_int64 * GGNN_METRIC_MAX_TERMS), ("ld_mask", c_int64 * GGNN_METRIC_MAX_TERMS),
+        ("col", c_int32 * GGNN_METRIC_MAX_TERMS),
+        ("score", c_void_p), ("label", c_void_p), ("label_mask", c_void_p), ("n", c_int64), ("ld_label_mask", c_int64),
+        ("thr", c_float * GGNN_METRIC_MAX_THR),
+        ("loss", c_void_p), ("acc", c_void_p), ("workspace", c_void_p),
+        ("n_terms", c_int32), ("n_thr", c_int32), ("mode", c_int32), ("with_norm", c_int32),
+    ]
+
+
 _lib = None
 
 
@@ -447,6 +466,8 @@ def _declare(lib):
     lib.ggnn_qoi_finalize.restype = c_int
     lib.ggnn_qoi_finalize.argtypes = [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, ctypes.c_double, c_void_p,
                                       c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
+    lib.ggnn_metric_record.restype = c_int
+    lib.ggnn_metric_record.argtypes = [POINTER(MetricArgs), c_void_p]
     lib.ggnn_process_schedule.restype = c_int
     lib.ggnn_process_schedule.argtypes = [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p]

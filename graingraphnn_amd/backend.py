@@ -181,6 +181,7 @@ class HipBackend:
         self._range_flags = {}  # device -> int32 word the fp16 two-piece kernels report clamped activations in
         self._rowgemm_ws = {}   # (device, stream, bytes) -> weight-plane workspace of ggnn_rowgemm
         self._mse_ws = {}       # (device, stream) -> partial sums + arrival counter of ggnn_masked_mse
+        self._metric_ws = {}    # (device, stream) -> partial rows + arrival counter of ggnn_metric_record
         # encoder cell as ONE fused sweep + gate GEMM launch (ggnn_encoder_cell_batch; bf16x6 arithmetic
         # only).  GGNN_ENC=split keeps the sweep and the gate GEMM as separate launches (development).
         self.fused_encoder = (self.lib.ggnn_gemm_mode() == 1 and os.environ.get("GGNN_ENC", "") != "split")
@@ -956,6 +957,59 @@ class HipBackend:
         a.workspace, a.loss, a.scale, a.n_terms = ws.data_ptr(), loss.data_ptr(), scale, len(terms)
         self._launch(self.lib.ggnn_masked_mse, "ggnn_masked_mse", ctypes.byref(a), _lib.current_stream())
         return grads
+
+    def metric_record(self, acc, terms, with_norm, mode, score, label, label_mask, thresholds, loss=None):
+        """ggnn_metric_record: one validation batch into the accumulator `acc` (int64 [F64_SLOTS + I64_SLOTS] on the
+        device, graingraphnn_amd.metrics), one launch.  `terms` = [(pred, target, mask, col)]: float32 [n, c] with unit
+        column stride, mask one float32 per row ([n] or [n, 1]); `score` float32 [n], `label` int64 [n], `label_mask`
+        float32 per element (regressor mode) or None; `loss` a float32 device scalar or None."""
+        a = _lib.MetricArgs()
+        if len(terms) > _lib.GGNN_METRIC_MAX_TERMS or len(thresholds) > _lib.GGNN_METRIC_MAX_THR:
+            raise _lib.GGNNError("ggnn_metric_record: at most %d terms and %d thresholds"
+                                 % (_lib.GGNN_METRIC_MAX_TERMS, _lib.GGNN_METRIC_MAX_THR))
+        _require_cuda(acc, score, label, label_mask, loss)
+        if acc.dtype != torch.int64 or not acc.is_contiguous() \
+                or acc.numel() != _lib.GGNN_METRIC_F64_SLOTS + _lib.GGNN_METRIC_I64_SLOTS:
+            raise _lib.GGNNError("ggnn_metric_record: the accumulator is %d contiguous 8-byte words"
+                                 % (_lib.GGNN_METRIC_F64_SLOTS + _lib.GGNN_METRIC_I64_SLOTS))
+
+        def rows(m, n, what):   # one float32 per row: -> its row stride
+            if m.dtype != torch.float32 or m.dim() not in (1, 2) or m.size(0) != n or (n > 1 and m.stride(0) < 1):
+                raise _lib.GGNNError(f"ggnn_metric_record: {what} must hold one float32 per row")
+            return max(m.stride(0), 1)
+        for k, (p, y, m, col) in enumerate(terms):
+            _require_cuda(p, y, m)
+            for t in (p, y):
+                if t.dtype != torch.float32 or t.dim() != 2 or (t.numel() and t.size(1) > 1 and t.stride(1) != 1):
+                    raise _lib.GGNNError("ggnn_metric_record: pred and target must be float32 [n, c] with unit column stride")
+            n = p.size(0)
+            if y.shape != p.shape or not 0 <= col < p.size(1) or (n > 1 and (p.stride(0) != y.stride(0) or p.stride(0) < p.size(1))):
+                raise _lib.GGNNError("ggnn_metric_record: pred and target must agree in shape and row stride")
+            a.pred[k], a.target[k], a.mask[k] = p.data_ptr(), y.data_ptr(), m.data_ptr()
+            a.n_rows[k], a.ld[k], a.ld_mask[k], a.col[k] = n, max(p.stride(0), p.size(1)), rows(m, n, "mask"), col
+        n = score.numel()
+        if score.dtype != torch.float32 or not score.is_contiguous() or label.dtype != torch.int64 \
+                or not label.is_contiguous() or label.numel() != n:
+            raise _lib.GGNNError("ggnn_metric_record: score (float32) and label (int64) must be contiguous and of one length")
+        a.score, a.label, a.n = score.data_ptr(), label.data_ptr(), n
+        if label_mask is not None:
+            a.label_mask, a.ld_label_mask = label_mask.data_ptr(), rows(label_mask, n, "label_mask")
+        elif mode == _lib.METRIC_REGRESSOR:
+            raise _lib.GGNNError("ggnn_metric_record: regressor mode needs the row mask")
+        for j, t in enumerate(thresholds):
+            a.thr[j] = t
+        if loss is not None:
+            if loss.dtype != torch.float32 or loss.numel() != 1:
+                raise _lib.GGNNError("ggnn_metric_record: loss must be a float32 scalar on the device")
+            a.loss = loss.data_ptr()
+        # one workspace per (device, stream), as for ggnn_masked_mse: the arrival counter and the partial rows
+        key = (acc.device, torch.cuda.current_stream(acc.device).cuda_stream)
+        ws = self._metric_ws.get(key)
+        if ws is None:
+            ws = self._metric_ws[key] = torch.zeros(_lib.GGNN_METRIC_WS_WORDS, dtype=torch.int64, device=acc.device)
+        a.acc, a.workspace = acc.data_ptr(), ws.data_ptr()
+        a.n_terms, a.n_thr, a.mode, a.with_norm = len(terms), len(thresholds), mode, int(bool(with_norm))
+        self._launch(self.lib.ggnn_metric_record, "ggnn_metric_record", ctypes.byref(a), _lib.current_stream())
 
     # -- heads -------------------------------------------------------------------------
     def heads_regressor(self, h_joint, h_grain, x_grain, w, b, y_joint, y_grain, grain_area):

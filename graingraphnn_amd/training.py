@@ -588,6 +588,30 @@ def classifier_loss(y_dict, pred, pos_weight: float = 1.0):
     return torch.where(labelled, per_edge, torch.zeros_like(per_edge)).sum() / keep.sum()
 
 
+class LossMeter:
+    """The running mean of a loop's losses without a read-back per step: `add(loss)` is one device-side add into an fp64
+    scalar (the loop around `GraphedTrainStep` need not call `float(loss)`, which stalls the host on every step), `mean()`
+    one read-back.  `add` copies the value: the tensor a replayed step overwrites may be passed as it is."""
+
+    def __init__(self):
+        self.total, self.count = None, 0
+
+    @torch.no_grad()
+    def add(self, loss):
+        if self.total is None:
+            self.total = torch.zeros((), dtype=torch.float64, device=loss.device)
+        self.total += loss.detach().reshape(())
+        self.count += 1
+
+    def mean(self):
+        return float(self.total) / self.count if self.count else float("nan")
+
+    def reset(self):
+        if self.total is not None:
+            self.total.zero_()
+        self.count = 0
+
+
 class FusedAdam(torch.optim.Optimizer):
     """torch.optim.Adam (train.py:82-91: per-group learning rates, StepLR on top) with the update of ALL parameter tensors
     in ONE call (`ggnn_adam_step`: the update kernel + a one-workgroup launch that advances the step counts): the model has

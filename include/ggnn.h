@@ -1050,6 +1050,57 @@ typedef struct ggnn_mse_args {
 } ggnn_mse_args;
 int ggnn_masked_mse(const ggnn_mse_args* args, ggnn_stream_t stream);
 
+/* Validation metrics (metrics.py:23-72 feature_metric.record, :124-217 grain_class_acc / class_acc): ONE launch adds one
+ * validation batch to a device-resident accumulator; nothing is read back before the epoch's summary.
+ *   squared-error terms k < n_terms <= GGNN_METRIC_MAX_TERMS over n_rows[k] rows, m = mask[k][r ld_mask[k]]:
+ *       acc.f64[k]     += sum_r m (target[k][r ld[k] + col[k]] - pred[k][r ld[k] + col[k]])^2
+ *       acc.f64[4 + k] += sum_r m  target[k][r ld[k] + col[k]]^2                          (only with with_norm != 0)
+ *     fp32 inputs; the difference, the squares and the sums are fp64.  A row with m == 0 contributes EXACTLY 0 to both,
+ *     even where pred or target is not finite (the reference's 0 * inf is NaN there; classifier_loss makes the same choice).
+ *   one threshold term of n elements (score fp32, label int64 read as stored, optional row mask label_mask[i ld_label_mask]),
+ *     n_thr <= GGNN_METRIC_MAX_THR thresholds thr[] compared in fp32:
+ *       GGNN_METRIC_CLASSIFIER  counted: label > -1;     s = 1 / (1 + exp(-score)) in fp32;  positive: s > t;  negative: s <= t
+ *       GGNN_METRIC_REGRESSOR   counted: label_mask > 0; s = score;                          positive: s < t;  negative: s >= t
+ *       acc.i64[j] += #(label == 1, positive)   acc.i64[16 + j] += #(label == 0, positive)   acc.i64[32 + j] += #(label == 1, negative)
+ *     (a label that is neither 0 nor 1 counts nowhere)
+ *   loss != NULL: acc.f64[8] += (double)*loss (a DEVICE float) and acc.i64[48] += 1.
+ * acc: GGNN_METRIC_F64_SLOTS doubles followed by GGNN_METRIC_I64_SLOTS int64, one DEVICE allocation, zeroed by the caller
+ * when a sum starts.  workspace: GGNN_METRIC_WS_WORDS 8-byte words of DEVICE memory, zero before the first call (the call
+ * leaves its last word zero again); one per stream that may have a launch in flight.
+ * GGNN_METRIC_BLOCKS workgroups each walk a fixed share of the elements; their partial sums go through the workspace and the
+ * last workgroup to arrive (an integer ticket) adds them in index order INTO acc: no floating-point atomics, the same bits
+ * on every run, on any stream and from a replayed hipGraph (replays keep adding).
+ * GGNN_EINVAL without a launch: args / acc / workspace NULL, n_terms outside 0..4, n_thr outside 0..16, a negative count,
+ * a missing operand of a non-empty term, an unknown mode. */
+#define GGNN_METRIC_MAX_TERMS 4
+#define GGNN_METRIC_MAX_THR 16
+#define GGNN_METRIC_BLOCKS 64
+#define GGNN_METRIC_F64_SLOTS 9  /* err[4] | norm[4] | loss */
+#define GGNN_METRIC_I64_SLOTS 49 /* TP[16] | FP[16] | FN[16] | batches */
+#define GGNN_METRIC_WS_WORDS (GGNN_METRIC_BLOCKS * 56 + 1) /* per workgroup 8 doubles | 48 int64; + the arrival counter */
+#define GGNN_METRIC_CLASSIFIER 0
+#define GGNN_METRIC_REGRESSOR 1
+typedef struct ggnn_metric_args {
+  const float* pred[GGNN_METRIC_MAX_TERMS];
+  const float* target[GGNN_METRIC_MAX_TERMS];
+  const float* mask[GGNN_METRIC_MAX_TERMS];
+  int64_t n_rows[GGNN_METRIC_MAX_TERMS];
+  int64_t ld[GGNN_METRIC_MAX_TERMS];      /* row stride of pred and target, in floats */
+  int64_t ld_mask[GGNN_METRIC_MAX_TERMS]; /* row stride of mask */
+  int32_t col[GGNN_METRIC_MAX_TERMS];
+  const float* score;
+  const int64_t* label;
+  const float* label_mask; /* GGNN_METRIC_REGRESSOR only */
+  int64_t n;
+  int64_t ld_label_mask;
+  float thr[GGNN_METRIC_MAX_THR];
+  const float* loss; /* optional, DEVICE [1] */
+  void* acc;
+  void* workspace;
+  int32_t n_terms, n_thr, mode, with_norm;
+} ggnn_metric_args;
+int ggnn_metric_record(const ggnn_metric_args* args, ggnn_stream_t stream);
+
 /* Bytes of device scratch one model forward needs (projections + aggregates + h/c), so a
  * caller can size a single arena; the Python host allocates the same amounts as tensors. */
 size_t ggnn_workspace_bytes(int64_t n_grain, int64_t n_joint, int64_t E);
