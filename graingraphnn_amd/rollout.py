@@ -18,8 +18,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .backend import default_backend
-from .engine import (Workspace, _check_x, alloc_einfo, graph_for, prepare_edges, run_encoder_decoder,
+from .backend import _WordArena, default_backend
+from .engine import (Workspace, _check_x, graph_for, prepare_edges, run_encoder_decoder,
                      run_encoder_decoder_multi)
 from .modules import _param_version, _param_version_sample
 from .packing import EDGE_TYPES, NODE_TYPES, pack_classifier_heads, pack_regressor_heads
@@ -83,6 +83,50 @@ def process_schedule_table(G=None, R=None, features=None):
     return np.ascontiguousarray(table), shared
 
 
+class _EdgeSets:
+    """The per-edge buffers of a topology as views of ONE float32 allocation: two sets of edge lengths and two sets of edge
+    records per edge type -- the two-stream step reads one set while its refresh writes the other
+    (GrainRollout._enqueue_overlapped_step; GrainRollout._parity says which set is current) -- and the per-edge predictions
+    `edge_event` and `edge`.  Sized for a `capacity` per edge type; `cut(E)` gives the views for lists of E <= capacity
+    edges.  Every segment starts on a 16-byte boundary that does not depend on E: a topology that changes in place (the event
+    loop) is re-cut and no address moves; a topology with buffers of its own is the same arrangement with the capacity equal
+    to the size.
+    zero: the allocation starts as zeros; otherwise nothing is initialised -- for lists the event loop installs: the refresh
+    that follows an event writes every length, ggnn_edge_prepare / ggnn_step_refresh_prepare every record (zero padding
+    included) before anything reads them.  (noflux: the records of a masked table end before the list's length, and the
+    sweeps' clamps may read the rest as padding, which must be finite: always zeroed.)
+    The views share the allocation's version counter: an in-place Python write into any of them shows in `buf._version`
+    (GrainRollout._ensure_edge_records)."""
+
+    def __init__(self, capacity, device, zero: bool):
+        self.capacity = {et: int(capacity[et]) for et in EDGE_TYPES}
+        count = _WordArena()
+        self._segments(count)
+        self.buf = (torch.zeros if zero else torch.empty)(count.at, dtype=torch.float32, device=device)
+        self._lengths, self._records, self._edge_event, self._edge = self._segments(_WordArena(self.buf))
+
+    def _segments(self, arena):
+        """The segments in their one order, each for max(capacity, 1) edges; the records with the GGNN_UNIT_EDGES tail rows
+        that pad the last unit's reads."""
+        n = {et: max(c, 1) for et, c in self.capacity.items()}
+        lengths = [{et: arena.take(n[et]) for et in EDGE_TYPES} for _ in range(2)]
+        records = [{et: arena.take((self.capacity[et] + _lib.GGNN_UNIT_EDGES) * _lib.GGNN_EINFO_ROW) for et in EDGE_TYPES}
+                   for _ in range(2)]
+        return lengths, records, arena.take(n[ET_JJ]), arena.take(2 * n[ET_JJ])
+
+    def cut(self, E):
+        """-> ([lengths of set 0, of set 1]: {et: [E]}, [records of set 0, of set 1]: {et: [E + GGNN_UNIT_EDGES,
+        GGNN_EINFO_ROW]}, edge_event [E_jj], edge [E_jj, 2]) for the list sizes `E` ({et: int})."""
+        E = {et: int(E[et]) for et in EDGE_TYPES}
+        if any(E[et] > self.capacity[et] for et in EDGE_TYPES):
+            raise _lib.GGNNError(f"edge lists of {E} edges do not fit buffers of {self.capacity}")
+        rows = {et: E[et] + _lib.GGNN_UNIT_EDGES for et in EDGE_TYPES}
+        return ([{et: s[et][:E[et]] for et in EDGE_TYPES} for s in self._lengths],
+                [{et: s[et][:rows[et] * _lib.GGNN_EINFO_ROW].view(rows[et], _lib.GGNN_EINFO_ROW) for et in EDGE_TYPES}
+                 for s in self._records],
+                self._edge_event[:E[ET_JJ]], self._edge[:2 * E[ET_JJ]].view(E[ET_JJ], 2))
+
+
 class GrainRollout:
     JOINT_LAUNCH_MAX_JOINTS = 8000
 
@@ -135,6 +179,9 @@ class GrainRollout:
             self._traj["dev"] = (torch.from_numpy(self._traj["grain"]).to(dev), torch.from_numpy(self._traj["joint"]).to(dev))
         self.n_nodes = {nt: self.x[nt].size(0) for nt in NODE_TYPES}
         self.pred = {}                        # this step's predictions (run_events: one of its slots' dicts)
+        # which buffers self.pred holds: 0 = the rollout's own; 1 + k = those of run_events' ring slot k; -(1 + k) = slot k's
+        # per-node ones with the edge sets' own per-edge ones (a topology installed behind the slot's step: _cut_edge_sets)
+        self._pred_at = 0
         self.mask = None                      # enable_events()
         self._cap = None                      # the in-place topology of the event loop (_enter_capacity_mode)
         self._spec = None                     # run_events' ring of slots and its block graphs (_spec_state)
@@ -143,12 +190,15 @@ class GrainRollout:
         self._evb = None                      # pinned staging of the event round trip (_event_buffers)
         self._topo = None                     # (session, its jj list, its jg list, their versions): _topology_session
         self._ens = None                      # enable_events(traj_offsets=...): the per-trajectory event layer (_enable_ensemble)
-        self._xc = self._xc_other = None      # the classifier's two alternating copies of x (_overlap_buffers)
+        # which of the two sets of edge lengths / edge records (_EdgeSets) and of the classifier's two copies of x is
+        # current: an overlapped step reads set `_parity` and leaves the other one current
+        self._parity = 0
+        self._xcs = None                      # the classifier's two alternating copies of x (_overlap_buffers)
         self._xc_fresh = False
-        self._graphs = None                   # run() / step() graphs per (steps, buffers): _replay
+        self._graphs = None                   # run() / step() graphs per (steps, parity): _replay
         self._qoi = None                      # enable_qoi(): the accumulator of grain volumes and its launch constants
         self._sched = None                    # set_process_schedule(): the (G, R) table on the device and its counter word
-        self._drop_segment_graphs()           # step_events()' segment graphs: _segment_graphs, _graph_fwd, _graph_ref
+        self._invalidate_graphs(segments=True)   # step_events()' segment graphs: _segment_graphs, _graph_fwd, _graph_ref
         self._set_topology(edge_index_dict, edge_attr_dict)
         self.span = span
         # test.py:401-406 computes in fp32: z += fp32(span/121); clamp at fp32(120/121)
@@ -245,7 +295,8 @@ class GrainRollout:
                                "offsets_host": off, "offsets": None if off is None else torch.from_numpy(off).to(dev),
                                "sync": torch.zeros(1, dtype=torch.int32, device=dev), "new": self._sched_state,
                                "home": self._sched_state(), "ring": None, "entries": None, "launched": 0, "at": None}
-            self._schedule_changed()
+            # the launch list changed: every captured graph lacks (or has another) schedule launch
+            self._invalidate_graphs(static=True, segments=True, blocks=True)
         # row 0, the step to come: an in-place write, seen by the version check of _ensure_edge_records
         row0 = S["table"][0]
         if off is not None:
@@ -260,13 +311,23 @@ class GrainRollout:
         it holds, and set_process_parameters works again."""
         if self._sched is not None:
             self._sched = None
-            self._schedule_changed()
+            self._invalidate_graphs(static=True, segments=True, blocks=True)   # (every captured graph has the launch)
 
-    def _schedule_changed(self):
-        """The launch list changed: every captured graph lacks (or has) the schedule's launch."""
-        self._graphs = None
-        self._drop_segment_graphs()
-        if self._spec is not None:
+    def _invalidate_graphs(self, static=False, segments=False, blocks=False):
+        """Drop captured hipGraphs, by family: `static` = those of run() / step() (_graphs: _replay), `segments` = those of
+        step_events()' two segments (_segment_graphs, _graph_fwd, _graph_ref: _run_segment), `blocks` = those of run_events'
+        blocks (_spec["graphs"]: _spec_launch) -- the last two with the list sizes they were captured at.  A graph holds
+        the addresses of everything its launches read and write and the launch list of its moment, and its key (parity,
+        slot) names neither: whatever replaces a buffer a graph may hold, or changes the launches of a step, drops the
+        families that hold it here."""
+        if static:
+            self._graphs = None
+        if segments:
+            self._graph_fwd = self._graph_ref = None
+            self._segment_graphs = {}
+            if self._cap is not None:
+                self._cap["captured"] = None
+        if blocks and self._spec is not None:
             self._spec["graphs"], self._spec["captured"] = {}, None
 
     def _schedule_offsets(self, passed):
@@ -329,8 +390,7 @@ class GrainRollout:
                 return
         if force or self._wver != (_param_version(self.rmodel), _param_version(self.cmodel)):
             self._pack_weights()
-            self._graphs = None
-            self._drop_segment_graphs()
+            self._invalidate_graphs(static=True, segments=True)
             self._spec = None   # (run_events' captured blocks hold the old buffers' addresses too)
 
     def _set_topology(self, edge_index_dict, edge_attr_dict=None, lasting=True, trusted=False):
@@ -342,60 +402,44 @@ class GrainRollout:
         if self._cap is not None:
             if trusted and edge_attr_dict is None and all(edge_index_dict[et].size(1) <= self._cap["cap"][et] for et in EDGE_TYPES):
                 return self._install_topology_in_place(edge_index_dict)
-            self._cap = None   # (a caller's own topology, or one that grew: back to buffers of its own; the segment graphs go)
-            self._drop_segment_graphs()
+            self._cap = None   # (a caller's own topology, or one that grew: back to buffers of its own)
         self.edge_index = {et: edge_index_dict[et] for et in EDGE_TYPES}
         self.graph = graph_for(self.be, self.edge_index, self.n_nodes, trusted, self.boundary, self._traj_grain_dev())
-        if trusted and edge_attr_dict is None:
-            return self._set_topology_buffers_from_one_allocation(dev)
-        if edge_attr_dict is not None:
-            self.edge_attr = {et: edge_attr_dict[et].detach().clone().contiguous().view(-1).float()
-                              for et in EDGE_TYPES}
-        else:  # lengths are recomputed by the refresh that follows an event (every element: nothing to initialise)
-            self.edge_attr = {et: torch.empty(self.edge_index[et].size(1), device=dev) for et in EDGE_TYPES}
-        # second buffer of the two-stream step (_enqueue_overlapped_step): the refresh writes the lengths of step
-        # k + 1 while the classifier's head still reads those of step k
-        self._ea_other = {et: torch.empty_like(self.edge_attr[et]) for et in EDGE_TYPES}
-        self._einfo_fresh = False   # True: self.einfo already holds the records of the step to come
-        E = self.graph.edge_index[ET_JJ].size(1)
-        self.pred["edge_event"] = torch.empty(E, dtype=torch.float32, device=dev)
-        self.pred["edge"] = torch.empty(E, 2, dtype=torch.float32, device=dev)
-        self.einfo = alloc_einfo(self.graph, dev)
-        self._zero_records(self.einfo)
-        # second set of edge records (_enqueue_overlapped_step): made on first use (_overlap_buffers); the classifier's
-        # copies of x keep their buffers (the node sets never change) but no longer mirror x
-        self._einfo_other = None
-        self._x_written_outside()
-        self._graphs = None
-        self._seen = None
-
-    def _set_topology_buffers_from_one_allocation(self, dev):
-        """The per-edge buffers of a topology the event loop installs (every step, on the reference's trajectories): both
-        sets of edge lengths and edge records and the per-edge predictions as views of ONE allocation, nothing
-        initialised -- the refresh that follows an event writes every length, ggnn_edge_prepare / ggnn_step_refresh_prepare
-        every record (zero padding included) before anything reads them."""
+        # buffers of its own: edge sets whose capacity is the size.  Lists the event loop installs (every step, on the
+        # reference's trajectories) are written before they are read: nothing to initialise (_EdgeSets)
         E = {et: self.edge_index[et].size(1) for et in EDGE_TYPES}
-        r4 = lambda n: (n + 3) & ~3
-        rec = {et: (E[et] + _lib.GGNN_UNIT_EDGES) * _lib.GGNN_EINFO_ROW for et in EDGE_TYPES}
-        total = sum(2 * r4(E[et]) + 2 * r4(rec[et]) for et in EDGE_TYPES) + r4(E[ET_JJ]) + r4(2 * E[ET_JJ])
-        buf, o = torch.empty(total, dtype=torch.float32, device=dev), [0]
+        self._sets = _EdgeSets(E, dev, zero=self.noflux or not (trusted and edge_attr_dict is None))
+        self._cut_edge_sets(E)
+        if edge_attr_dict is not None:
+            for et in EDGE_TYPES:
+                self.edge_attr[et].copy_(edge_attr_dict[et].detach().reshape(-1))
+        # new CSR tables and new per-edge buffers: whatever was captured holds the old ones
+        self._invalidate_graphs(static=True, segments=True, blocks=True)
 
-        def take(n, shape=None):
-            v = buf[o[0]:o[0] + n]
-            o[0] += r4(n)
-            return v if shape is None else v.view(shape)
-        self.edge_attr = {et: take(E[et]) for et in EDGE_TYPES}
-        self._ea_other = {et: take(E[et]) for et in EDGE_TYPES}
-        shape = lambda et: (E[et] + _lib.GGNN_UNIT_EDGES, _lib.GGNN_EINFO_ROW)
-        self.einfo = {et: take(rec[et], shape(et)) for et in EDGE_TYPES}
-        self._einfo_other = {et: take(rec[et], shape(et)) for et in EDGE_TYPES}
-        self._zero_records(self.einfo, self._einfo_other)
-        self._einfo_fresh = False
-        self.pred["edge_event"] = take(E[ET_JJ])
-        self.pred["edge"] = take(2 * E[ET_JJ], (E[ET_JJ], 2))
+    def _cut_edge_sets(self, E):
+        """The views of the edge sets for lists of `E` edges (_EdgeSets.cut) become the rollout's per-edge tensors.  The
+        records are to be prepared and the version counters to be read again; the classifier's copies of x keep their
+        buffers (the node sets never change) but no longer mirror x."""
+        self._ea, self._recs, edge_event, edge = self._sets.cut(E)
+        if self._pred_at > 0:   # (a ring slot's dict, run_events: the slot keeps its own per-edge predictions)
+            self.pred, self._pred_at = dict(self.pred), -self._pred_at
+        self.pred["edge_event"], self.pred["edge"] = edge_event, edge
+        # which of the two sets is the current one follows the speculative loop's slot parity while its ring lives
+        # (run_events' graphs alternate the sets by slot: _spec_state); otherwise the first
+        self._parity = 0 if self._spec is None else self._spec["cur"] & 1
+        self._einfo_fresh = False   # True: self.einfo already holds the records of the step to come
         self._x_written_outside()
-        self._graphs = None
         self._seen = None
+
+    @property
+    def edge_attr(self):
+        """The current edge lengths, {edge type: [E]}: refreshed by every step, and the caller's to write in place."""
+        return self._ea[self._parity]
+
+    @property
+    def einfo(self):
+        """The current set of edge records, {edge type: [E + GGNN_UNIT_EDGES, GGNN_EINFO_ROW]}."""
+        return self._recs[self._parity]
 
     # -- a topology that changes IN PLACE (event mode) ---------------------------------------------------------------------
     def _enter_capacity_mode(self):
@@ -411,20 +455,11 @@ class GrainRollout:
             self._cap = None
             return
         cap = {et: int(self.edge_index[et].size(1)) for et in EDGE_TYPES}
-        r4 = lambda n: (n + 3) & ~3
-        rec = {et: (cap[et] + _lib.GGNN_UNIT_EDGES) * _lib.GGNN_EINFO_ROW for et in EDGE_TYPES}
-        off, at = {}, 0
-        for name, size in [(("ea", et), cap[et]) for et in EDGE_TYPES] + [(("ea2", et), cap[et]) for et in EDGE_TYPES] \
-                + [(("rec", et), rec[et]) for et in EDGE_TYPES] + [(("rec2", et), rec[et]) for et in EDGE_TYPES] \
-                + [("edge_event", cap[ET_JJ]), ("edge", 2 * cap[ET_JJ])]:
-            off[name] = at
-            at += r4(max(size, 1))
         old_ea = {et: self.edge_attr[et] for et in EDGE_TYPES}
         old_ei = {et: self.edge_index[et] for et in EDGE_TYPES}
+        self._sets = _EdgeSets(cap, dev, zero=self.noflux)
         self._cap = {
-            # (noflux: a masked table's records end before the capacity; the sweeps' clamps may read the rest as padding,
-            # which must be finite: zeros until a record is written there)
-            "cap": cap, "off": off, "buf": (torch.zeros if self.noflux else torch.empty)(at, dtype=torch.float32, device=dev),
+            "cap": cap,
             "lists": {et: torch.empty(2 * max(cap[et], 1), dtype=torch.int64, device=dev) for et in EDGE_TYPES},
             "csr": self._csr_in_place(be, cap, dev),
             "counts": torch.zeros(len(EDGE_TYPES), dtype=torch.int64, device=dev),
@@ -434,13 +469,13 @@ class GrainRollout:
         self._install_topology_in_place(old_ei)
         for et in EDGE_TYPES:
             self.edge_attr[et].copy_(old_ea[et])
-        self._drop_segment_graphs()
+        self._invalidate_graphs(segments=True, blocks=True)   # (what was captured holds the buffers of before)
 
     def _install_topology_in_place(self, edge_index_dict):
         """The lists of `edge_index_dict` (device tensors, or already views of the list buffers) become the topology: copied
         into the list buffers, their sizes into the device-side counts, the CSR tables rebuilt inside the arena, the per-edge
         tensors re-cut as views of the same allocations.  No address changes: the segment graphs stay."""
-        C, dev = self._cap, self.x["joint"].device
+        C = self._cap
         E = {et: int(edge_index_dict[et].size(1)) for et in EDGE_TYPES}
         self.edge_index = {}
         for k, et in enumerate(EDGE_TYPES):
@@ -455,31 +490,11 @@ class GrainRollout:
         from .engine import GraphCSR
         self.graph = GraphCSR(self.be, self.edge_index, self.n_nodes, trusted=True, into=C["csr"], counts=counts,
                               boundary=self.boundary, traj_grain_off=self._traj_grain_dev())
-        buf, off = C["buf"], C["off"]
-        cut = lambda name, n, shape=None: buf[off[name]:off[name] + n] if shape is None else buf[off[name]:off[name] + n].view(shape)
-        rows = lambda et: E[et] + _lib.GGNN_UNIT_EDGES
-        sets = [{et: cut(("ea", et), E[et]) for et in EDGE_TYPES}, {et: cut(("ea2", et), E[et]) for et in EDGE_TYPES}]
-        recs = [{et: cut(("rec", et), rows(et) * _lib.GGNN_EINFO_ROW, (rows(et), _lib.GGNN_EINFO_ROW)) for et in EDGE_TYPES},
-                {et: cut(("rec2", et), rows(et) * _lib.GGNN_EINFO_ROW, (rows(et), _lib.GGNN_EINFO_ROW)) for et in EDGE_TYPES}]
-        # which of the two sets is the current one follows the speculative loop's slot parity while its state lives
-        # (run_events' graphs alternate the sets by slot: _spec_state); step_events() alone stays on the first
-        S = self._spec
-        par = (S["cur"] & 1) if (S is not None and S["in_place"]) else 0
-        C["sets"], C["recs"] = sets, recs
-        self.edge_attr, self._ea_other = sets[par], sets[1 - par]
-        self.einfo, self._einfo_other = recs[par], recs[1 - par]
-        self._einfo_fresh = False
-        self.pred["edge_event"] = cut("edge_event", E[ET_JJ])
-        self.pred["edge"] = cut("edge", 2 * E[ET_JJ], (E[ET_JJ], 2))
-        self._x_written_outside()
-        self._graphs = None
-        self._seen = None
-        # a segment graph was captured for the sizes of ITS moment: it stays valid while nothing has grown since
-        if self._outgrown(C["captured"]):
-            self._drop_segment_graphs()
-            C["captured"] = None
-            if S is not None:
-                S["graphs"], S["captured"] = {}, None
+        self._cut_edge_sets(E)
+        # run() / step() graphs hold the sizes of their moment in their launches; a segment or block graph reads them from
+        # the device: it stays valid while nothing has grown since it was captured
+        grown = self._outgrown(C["captured"])
+        self._invalidate_graphs(static=True, segments=grown, blocks=grown)
 
     def _x_written_outside(self):
         """x was (or is about to be) advanced by something other than the overlapped two-stream step / the speculative
@@ -513,13 +528,6 @@ class GrainRollout:
     def _traj_grain_dev(self):
         """A no-flux union's grain offsets on the device (every trajectory's first grain is a boundary grain), or None."""
         return None if self._traj is None else self._traj["dev"][0]
-
-    def _zero_records(self, *sets):
-        """noflux: edge records of masked tables end before the list's length; what lies behind must be finite."""
-        if self.noflux:
-            for d in sets:
-                for t in d.values():
-                    t.zero_()
 
     def _enqueue_boundary(self, joints_before=None):
         """test.py:446-463 (noflux only): grain 0 reset, its junctions onto the walls, every junction into the domain; a
@@ -576,11 +584,7 @@ class GrainRollout:
             area0 = torch.as_tensor(area0).to(dev, torch.float32).contiguous().view(-1)
             if area0.numel() != ng:
                 raise _lib.GGNNError("area0 must have one entry per grain")
-        # graphs captured so far lack the launch
-        self._graphs = None
-        self._drop_segment_graphs()
-        if self._spec is not None:
-            self._spec["graphs"], self._spec["captured"] = {}, None
+        self._invalidate_graphs(static=True, segments=True, blocks=True)   # (graphs captured so far lack the launch)
         self._enqueue_qoi(init=True, area0=area0)
 
     def _qoi_state(self):
@@ -639,7 +643,7 @@ class GrainRollout:
             if c["ring"] is None or len(c["ring"]) != D:
                 self._carry_home_one(c)
                 c["ring"], c["entries"] = [c["new"]() for _ in range(D)], [c["new"]() for _ in range(2)]
-                self._spec["graphs"], self._spec["captured"] = {}, None
+                self._invalidate_graphs(blocks=True)   # (the blocks' launches advance the ring's states)
             before = c["ring"][(slots[0] - 1) % D]
             if c["at"] != (slots[0] - 1) % D:
                 self._carry_home_one(c)
@@ -725,26 +729,26 @@ class GrainRollout:
         self._x_written_outside()
 
     def _overlap_buffers(self):
-        """The second set of edge records and the classifier's two alternating copies of x (outside any capture:
-        _capture calls this first)."""
-        if self._pipelined():
-            if self._einfo_other is None:
-                self._einfo_other = alloc_einfo(self.graph, self.x["joint"].device)
-                self._zero_records(self._einfo_other)
-            if self._xc is None:
-                self._xc = {nt: torch.empty_like(self.x[nt]) for nt in NODE_TYPES}
-                self._xc_other = {nt: torch.empty_like(self.x[nt]) for nt in NODE_TYPES}
-                self._xc_fresh = False
+        """The classifier's two alternating copies of x, indexed like the edge sets (outside any capture: _capture calls
+        this first)."""
+        if self._pipelined() and self._xcs is None:
+            self._xcs = [{nt: torch.empty_like(self.x[nt]) for nt in NODE_TYPES} for _ in range(2)]
+            self._xc_fresh = False
 
-    def _enqueue_overlapped_step(self, ea, ea_next, einfo, einfo_next, xc, xc_next, p, zf, headed_prev, slot=None):
+    def _heads_classifier(self, h_joint, ea, p):
+        """The classifier's heads on the junction edges: `h_joint` and the lengths `ea` in, edge_event and edge of `p` out."""
+        self.be.heads_classifier(h_joint, self.graph.edge_index[ET_JJ], ea[ET_JJ], self.w_cls[0], self.w_cls[1], self._tmp,
+                                 p["edge_event"], p["edge"], E_dev=self.graph.csr[ET_JJ].E_dev)
+
+    def _enqueue_overlapped_step(self, par, xc, xc_next, p, zf, headed_prev, slot=None):
         """One static-topology step on two streams with the regressor's tail -- heads + Rmodel.update, boundary step, grain
         centres, z clamp + edge lengths + the NEXT step's edge records -- UNDER the classifier's forward, where the chip
         would otherwise run the last workgroups of one decoder cell alone (profiles/r6_step_timeline.txt).  The regressor's
         chain stays on the current stream: it carries every step-to-step dependency.  The classifier reads its own copy of x
         (`xc`), and the copies of x, the edge lengths and the edge records alternate between two sets: this step reads
-        `xc`, `ea`, `einfo`, its refresh writes `xc_next` (ggnn_step_refresh_prepare's mirror, a by-product of its pass over
-        the nodes), `ea_next` and `einfo_next`, so nothing the tail writes is read by the classifier's forward of the same
-        step.  Cross-stream edges:
+        `xc` and the lengths and records of set `par`, its refresh writes `xc_next` (ggnn_step_refresh_prepare's mirror, a
+        by-product of its pass over the nodes) and the lengths and records of the other set, so nothing the tail writes is
+        read by the classifier's forward of the same step.  Cross-stream edges:
           * the classifier waits for `ready`, recorded at the top of the step (its copy of x, the edge lengths and records
             are final);
           * the refresh, the first launch that writes into the set the previous step's classifier read, waits for that
@@ -757,6 +761,7 @@ class GrainRollout:
         (test_pipelined_two_stream_rollout_equals_the_single_stream_plan).  Returns (ready, updated or None, headed): the
         caller keeps them alive until the streams are joined and a capture has ended."""
         be, x, S = self.be, self.x, self._spec
+        ea, ea_next, einfo, einfo_next = self._ea[par], self._ea[1 - par], self._recs[par], self._recs[1 - par]
         main, st_c = torch.cuda.current_stream(), self._side[1]
         ready, headed = torch.cuda.Event(), torch.cuda.Event()
         updated = None if slot is None else torch.cuda.Event()
@@ -771,8 +776,7 @@ class GrainRollout:
                 st_c.wait_event(ready)
                 enc, dec = self.packed["C"]
                 h, _ = run_encoder_decoder(be, enc, dec, self.graph, self.ws["C"], xc, ea, einfo)
-                be.heads_classifier(h["joint"], self.graph.edge_index[ET_JJ], ea[ET_JJ], self.w_cls[0], self.w_cls[1],
-                                    self._tmp, p["edge_event"], p["edge"], E_dev=self.graph.csr[ET_JJ].E_dev)
+                self._heads_classifier(h["joint"], ea, p)
                 headed.record(st_c)
         finally:
             for name in ("R", "C"):
@@ -786,11 +790,7 @@ class GrainRollout:
             joints_before, centres_before = (S["jb"][slot] if self.noflux else None), S["cen"][slot]
             if not self.refresh_centres:   # (otherwise the snapshot rides with the launch that replaces the centres)
                 centres_before.copy_(x["grain"][:, :2])
-        self._enqueue_boundary(joints_before)
-        if self.refresh_centres:
-            self._enqueue_centres(centres_before)
-        self._enqueue_qoi(slot)
-        self._enqueue_schedule(slot)
+        self._enqueue_tail(slot, joints_before, centres_before)
         if headed_prev is not None:
             main.wait_event(headed_prev)   # the previous step's classifier has read the set this refresh writes
         be.step_refresh_prepare(x["joint"], x["grain"], self.zmax, zf,
@@ -799,18 +799,17 @@ class GrainRollout:
         return ready, updated, headed
 
     def _enqueue_steps_overlapped(self, n_steps: int):
-        """`n_steps` overlapped steps (_enqueue_overlapped_step) on the rollout's own buffers, the two sets swapped behind
+        """`n_steps` overlapped steps (_enqueue_overlapped_step) on the rollout's own buffers, the other set current behind
         every step, no join between the steps; the classifier's stream is joined behind the last one.  Needs self.einfo to
-        hold the records of the first step and self._xc to mirror x (step() / run() see to that: _ensure_edge_records)."""
+        hold the records of the first step and the current copy of x to mirror x (step() / run() see to that:
+        _ensure_edge_records)."""
         self._overlap_buffers()
         keep, headed = [], None
         for _ in range(n_steps):
-            keep.append(self._enqueue_overlapped_step(self.edge_attr, self._ea_other, self.einfo, self._einfo_other,
-                                                      self._xc, self._xc_other, self.pred, self.flags, headed))
+            par = self._parity
+            keep.append(self._enqueue_overlapped_step(par, self._xcs[par], self._xcs[1 - par], self.pred, self.flags, headed))
             headed = keep[-1][-1]
-            self.edge_attr, self._ea_other = self._ea_other, self.edge_attr
-            self.einfo, self._einfo_other = self._einfo_other, self.einfo
-            self._xc, self._xc_other = self._xc_other, self._xc
+            self._parity = 1 - par
         torch.cuda.current_stream().wait_stream(self._side[1])
         self._next_step_prepared()
         return keep
@@ -827,8 +826,7 @@ class GrainRollout:
         classifier's copy of x must equal x.  They are stale after construction, a topology change, an event-mode or
         single-stream step, and when the caller wrote into x / edge_attr (in-place Python writes bump the tensors' version
         counters; the kernels do not)."""
-        seen = tuple(t._version for t in self.x.values()) + tuple(sorted(
-            t._version for t in (*self.edge_attr.values(), *self._ea_other.values())))
+        seen = self._versions()
         if seen != self._seen:
             self._x_written_outside()
         if not self._einfo_fresh or seen != self._seen:
@@ -838,8 +836,27 @@ class GrainRollout:
         if mirror and not self._xc_fresh:
             self._overlap_buffers()
             for nt in NODE_TYPES:
-                self._xc[nt].copy_(self.x[nt])
+                self._xcs[self._parity][nt].copy_(self.x[nt])
             self._xc_fresh = True
+
+    def _versions(self):
+        """The version counters a caller's in-place write shows in: those of x and the one the views of the edge sets
+        share -- a write into either set of lengths (or into anything else in the allocation) counts.  The rollout's own
+        Python-side writes into the allocation bump it too: construction, which reads the counters anew (_cut_edge_sets),
+        and _move_lengths_over, which takes its own write out again."""
+        return tuple(t._version for t in self.x.values()) + (self._sets.buf._version,)
+
+    def _move_lengths_over(self, parity: int):
+        """Set `parity` becomes the current one with the lengths of the one that was (run_events' graphs alternate the sets
+        by slot parity; step() / step_events() in between may have left the other set current).  The records and the
+        classifier's copy of x do not follow."""
+        unwritten = self._seen == self._versions()
+        for et in EDGE_TYPES:
+            self._ea[parity][et].copy_(self.edge_attr[et])
+        if unwritten:   # (the copies bumped the allocation's counter; a caller's write from before still shows)
+            self._seen = self._versions()
+        self._parity = parity
+        self._einfo_fresh = self._xc_fresh = False
 
     def _enqueue_forward_update(self, joint=None):
         """test.py:382-402: both forwards, Rmodel.update, z advance.  `joint`: True = the regressor and the classifier in the
@@ -858,16 +875,14 @@ class GrainRollout:
         def classifier(x_read=None):
             enc, dec = self.packed["C"]
             h, _ = run_encoder_decoder(be, enc, dec, self.graph, self.ws["C"], x, ea, einfo, x_read)
-            be.heads_classifier(h["joint"], self.graph.edge_index[ET_JJ], ea[ET_JJ], self.w_cls[0],
-                                self.w_cls[1], self._tmp, p["edge_event"], p["edge"], E_dev=self.graph.csr[ET_JJ].E_dev)
+            self._heads_classifier(h["joint"], ea, p)
 
         if joint:
             run_encoder_decoder_multi(be, [(*self.packed["R"], self.ws["R"]), (*self.packed["C"], self.ws["C"])],
                                       self.graph, x, einfo)
             be.heads_regressor(self.ws["R"].h2["joint"], self.ws["R"].h2["grain"], x["grain"], self.w_reg[0],
                                self.w_reg[1], p["joint"], p["grain"], p["grain_area"])
-            be.heads_classifier(self.ws["C"].h2["joint"], self.graph.edge_index[ET_JJ], ea[ET_JJ], self.w_cls[0],
-                                self.w_cls[1], self._tmp, p["edge_event"], p["edge"], E_dev=self.graph.csr[ET_JJ].E_dev)
+            self._heads_classifier(self.ws["C"].h2["joint"], ea, p)
         elif self._side is None:
             regressor()
             classifier()
@@ -893,17 +908,28 @@ class GrainRollout:
             return
         be.step_update(x["joint"], x["grain"], p["joint"], p["grain"], self.dz, self.zmax, self.flags)
 
+    def _enqueue_tail(self, slot=None, joints_before=None, centres_before=None):
+        """What follows Rmodel.update in every plan, in front of the launch that refreshes the edge lengths: boundary step
+        (noflux), grain centres (refresh_centres), this step's QoI layer, the schedule's row of the step to come.  `slot`,
+        `joints_before`, `centres_before`: the speculative event loop's (_enqueue_overlapped_step)."""
+        self._enqueue_boundary(joints_before)
+        if self.refresh_centres:
+            self._enqueue_centres(centres_before)
+        self._enqueue_qoi(slot)
+        self._enqueue_schedule(slot)
+
+    def _refresh_edges(self, lists, count_dev=None):
+        """The edge list of a ggnn_step_refresh launch: the current lengths recomputed from x for `lists` ({edge type:
+        edge_index}); `count_dev`: {edge type: the device word with the list's length at run time, or None}."""
+        x, ea = self.x, self.edge_attr
+        return [(lists[et], x[et[0]], x[et[-1]], ea[et]) + (() if count_dev is None else (count_dev[et],)) for et in EDGE_TYPES]
+
     def _enqueue_refresh(self):
         """test.py:405-407, [446-463 noflux], 468-478 + 556-559, 562-575: z clamp, boundary step, grain centres, edge
         lengths (of the full lists)."""
-        be, x, ea = self.be, self.x, self.edge_attr
-        self._enqueue_boundary()
-        if self.refresh_centres:
-            self._enqueue_centres()
-        self._enqueue_qoi()
-        self._enqueue_schedule()
-        be.step_refresh(x["joint"], x["grain"], self.zmax, self.flags,
-                        [(self.graph.edge_index[et], x[et[0]], x[et[-1]], ea[et], self.graph.count_dev[et]) for et in EDGE_TYPES])
+        self._enqueue_tail()
+        self.be.step_refresh(self.x["joint"], self.x["grain"], self.zmax, self.flags,
+                             self._refresh_edges(self.graph.edge_index, self.graph.count_dev))
 
     @staticmethod
     def _captured(enqueue):
@@ -921,32 +947,26 @@ class GrainRollout:
         return g
 
     def _capture(self, n_steps: int = 1):
-        """Record `n_steps` steps into a hipGraph, leaving the rollout's buffers as they were.  An overlapped step swaps the
-        two sets of edge lengths / edge records / copies of x: a graph is only valid from the set it was captured on, so
-        graphs are kept per set (_replay), and an odd number of steps leaves the other set current after every replay."""
+        """Record `n_steps` steps into a hipGraph, leaving the rollout's buffers as they were.  An overlapped step leaves
+        the other set of edge lengths / edge records / copies of x current: a graph is only valid from the set it was
+        captured on, so graphs are kept per parity (_replay), and an odd number of steps flips it after every replay."""
         self._overlap_buffers()
-        state = (self.edge_attr, self._ea_other, self._einfo_fresh, self.einfo, self._einfo_other, self._xc,
-                 self._xc_other, self._xc_fresh)
+        state = (self._parity, self._einfo_fresh, self._xc_fresh)
         g = self._captured(lambda: self._enqueue_steps(n_steps))
-        (self.edge_attr, self._ea_other, self._einfo_fresh, self.einfo, self._einfo_other, self._xc, self._xc_other,
-         self._xc_fresh) = state
+        self._parity, self._einfo_fresh, self._xc_fresh = state
         return g
 
     def _replay(self, n_steps: int):
         """`n_steps` steps from the hipGraph captured for this step count and the current set of buffers."""
         if self._graphs is None:
             self._graphs = {}
-        key = (n_steps, self.edge_attr[ET_JJ].data_ptr(), self.einfo[ET_JJ].data_ptr(),
-               self._xc["joint"].data_ptr() if self._xc is not None else 0)
+        key = (n_steps, self._parity)
         g = self._graphs.get(key)
         if g is None:
             g = self._graphs[key] = self._capture(n_steps)
         g.replay()
         if self._pipelined():
-            if n_steps % 2:
-                self.edge_attr, self._ea_other = self._ea_other, self.edge_attr
-                self.einfo, self._einfo_other = self._einfo_other, self.einfo
-                self._xc, self._xc_other = self._xc_other, self._xc
+            self._parity ^= n_steps & 1
             self._next_step_prepared()
         else:
             self._einfo_fresh = False
@@ -986,9 +1006,8 @@ class GrainRollout:
         self._ev_flags = torch.zeros(2, dtype=torch.int32, device=dev)
         self._ev_host = torch.zeros(2, dtype=torch.int32).pin_memory()
         self._quiet_steps = 0
-        self._drop_segment_graphs()
-        if self._qoi is not None:   # (its launches read the live mask from now on)
-            self._graphs = None
+        # (a new live mask, which the QoI launches read from now on; the blocks go with the edge sets: _enter_capacity_mode)
+        self._invalidate_graphs(static=self._qoi is not None, segments=True)
         self.grain_events, self.switched = [], []
         self._enter_capacity_mode()
         self._ens = None
@@ -1012,6 +1031,14 @@ class GrainRollout:
         cand[self._traj["boundary_grains"]] = 0
         return cand
 
+    def _host_masks(self):
+        """The host masks (grain, joint) as the sessions patch them in place: contiguous int64 (a caller may have replaced
+        them by something else)."""
+        mg, mj = self.mask["grain"], self.mask["joint"]
+        if not (mg.dtype == np.int64 and mg.flags.c_contiguous and mj.dtype == np.int64 and mj.flags.c_contiguous):
+            mg, mj = self.mask["grain"], self.mask["joint"] = np.ascontiguousarray(mg, np.int64), np.ascontiguousarray(mj, np.int64)
+        return mg, mj
+
     def _enable_ensemble(self, ens):
         """The device side of the per-trajectory layer: the offsets, the `ended` words and ONE buffer of 2 + 2 n_traj count
         words (totals first: step_events reads them as it reads the two words of a single trajectory)."""
@@ -1031,9 +1058,7 @@ class GrainRollout:
         ens, n_e = E["sessions"], self.edge_index[ET_JJ].size(1)
         if ens.n_pp != n_e:
             raise _lib.GGNNError("the topology sessions and the rollout's junction edge list disagree")
-        mg, mj = self.mask["grain"], self.mask["joint"]
-        if not (mg.dtype == np.int64 and mg.flags.c_contiguous and mj.dtype == np.int64 and mj.flags.c_contiguous):
-            mg, mj = self.mask["grain"], self.mask["joint"] = np.ascontiguousarray(mg, np.int64), np.ascontiguousarray(mj, np.int64)
+        mg, mj = self._host_masks()
         E["rewired"] += 1
         ended = E["ended_host"].numpy()
         res = ens.apply(N["xj"], N["yj"], N["yg"][:, 0], N["prob"][:n_e], N["area"], mg, mj, self._ev_host.numpy()[2:], ended,
@@ -1088,11 +1113,6 @@ class GrainRollout:
         """The grain that never takes part in events: the no-flux boundary grain (test.py:421-422), or none."""
         return 0 if self.noflux else -1
 
-    def _drop_segment_graphs(self):
-        """The hipGraphs of step_events()' two segments, all variants (one per set of buffers they were captured on)."""
-        self._graph_fwd = self._graph_ref = None
-        self._segment_graphs = {}
-
     def _run_segment(self, which):
         """The two halves of a step, replayed from their own hipGraphs: on the in-place topology (_enter_capacity_mode) from the
         first step on and across events; otherwise once the topology has been quiet for two steps (an event then drops the
@@ -1102,13 +1122,9 @@ class GrainRollout:
         if self.use_graph and (self._quiet_steps >= 2 or in_place):
             # a segment graph holds the addresses of the buffers it reads and writes; run_events() leaves other ones current
             # (its slots' predictions, the other set of edge lengths / records): a graph per set.  The forwards read the edge
-            # lengths and records and write the predictions; the refresh writes the edge lengths
-            tables = self.graph.csr[ET_JJ].rowptr.data_ptr()
-            if which == "fwd":
-                key = (which, self.edge_attr[ET_JJ].data_ptr(), self.einfo[ET_JJ].data_ptr(), self.pred["joint"].data_ptr(),
-                       self.pred["edge_event"].data_ptr(), tables)
-            else:
-                key = (which, self.edge_attr[ET_JJ].data_ptr(), tables)
+            # lengths and records and write the predictions; the refresh writes the edge lengths.  (Everything else a
+            # segment holds is dropped with what replaces it: _invalidate_graphs)
+            key = (which, self._parity, self._pred_at) if which == "fwd" else (which, self._parity)
             g = self._segment_graphs.get(key)
             if g is None:
                 if in_place:   # valid for as long as no list is longer than now (_install_topology_in_place)
@@ -1185,56 +1201,36 @@ class GrainRollout:
         the step before, ggnn_step_refresh_prepare's mirror), the step's predictions, the grain centres as they were
         before the step's refresh, its z-clamp flag (test.py:405: written by the step's Rmodel.update, read by its
         refresh), its event counts and its own fp16-range word (device + pinned host: [grains, edges, range, -]) --
-        plus the two alternating sets of edge lengths / edge records (set = slot parity).  Graphs are captured per
-        (first slot, number of steps).  On the in-place topology (_enter_capacity_mode) the ring and the graphs survive events
-        (the views are re-cut); otherwise the per-edge half and the graphs are rebuilt after every topology change."""
-        S = self._spec
-        if S is not None and S["topology"] is self.graph and S["ea"][S["cur"] & 1] is self.edge_attr \
-                and S["einfo"][S["cur"] & 1] is self.einfo:
-            return S
-        self._overlap_buffers()
-        dev = self.x["joint"].device
+        the step of a slot reads the set of edge lengths / edge records of the slot's parity, so the rollout's parity follows
+        the current slot.  Graphs are captured per (first slot, number of steps).  On the in-place topology
+        (_enter_capacity_mode) the ring and the graphs survive events (the views are re-cut); otherwise the per-edge half and
+        the graphs are rebuilt after every topology change."""
+        S, dev = self._spec, self.x["joint"].device
         D = 2 * max(1, int(self.EVENTS_UNROLL))
-        per_edge = ("edge_event", "edge")   # the predictions that follow the junction edge list
-        C = self._cap
-        if C is not None:
-            # The topology lives in place (_enter_capacity_mode): the two sets of edge lengths / records are the SAME
-            # allocations before and after an event, the slots' per-edge predictions are cut from one allocation of the
-            # capacity, and the graphs of the blocks -- whose per-edge kernels read the number of edges from device memory --
-            # stay valid across events for as long as no list has grown: an event re-cuts the views, nothing else.
-            Ea = (C["cap"][ET_JJ] + 3) & ~3
-            if S is None or not S["in_place"] or S["D"] != D or S["flat"].numel() != 3 * D * Ea:
-                S = self._spec = {
-                    "in_place": True, "cur": 0, "D": D, "graphs": {}, "captured": None, "xs_valid": None,
-                    "flat": torch.empty(3 * D * Ea, dtype=torch.float32, device=dev), **self._spec_node_slots(D),
-                    "pred": [{k: torch.empty_like(v) for k, v in self.pred.items() if k not in per_edge} for _ in range(D)]}
+        if S is None or S["D"] != D:
+            # the per-node slots, the centre snapshots and the (pinned) count words: the node sets never change
+            per_edge = ("edge_event", "edge")   # the predictions that follow the junction edge list
+            S = self._spec = {
+                "cur": self._parity, "D": D, "graphs": {}, "captured": None, "xs_valid": None, "topology": None, "sets": None,
+                "flat": None, **self._spec_node_slots(D),
+                "pred": [{k: torch.empty_like(v) for k, v in self.pred.items() if k not in per_edge} for _ in range(D)]}
+            # (a segment graph captured while self.pred was a slot of the ring before holds that slot's predictions)
+            self._invalidate_graphs(segments=True)
+        if S["topology"] is not self.graph or S["sets"] is not self._sets:
+            # The slots' per-edge predictions are cut from one allocation of the edge sets' capacity.  While the topology
+            # lives in place (_enter_capacity_mode) the edge sets are the SAME allocations before and after an event, and the
+            # graphs of the blocks -- whose per-edge kernels read the number of edges from device memory -- stay valid
+            # across events for as long as no list has grown: an event re-cuts the views, nothing else.  Otherwise an event
+            # brings new edge sets (and has dropped the graphs with the old ones: _set_topology).
+            Ea = (self._sets.capacity[ET_JJ] + 3) & ~3                        # (16-byte aligned segments)
+            if S["sets"] is not self._sets:
+                S["flat"] = torch.empty(3 * D * Ea, dtype=torch.float32, device=dev)   # one allocation for all slots
             for slot, edge in zip(S["pred"], self._spec_edge_slots(S["flat"], D, Ea)):
                 slot.update(edge)
-            par = S["cur"] & 1
-            S["topology"], S["ea"], S["einfo"] = self.graph, C["sets"], C["recs"]
-            if self.edge_attr is not C["sets"][par]:   # (step_events() in between left the first set current: move over)
-                for et in EDGE_TYPES:
-                    C["sets"][par][et].copy_(self.edge_attr[et])
-                self._einfo_fresh = False
-            self.edge_attr, self._ea_other = C["sets"][par], C["sets"][1 - par]
-            self.einfo, self._einfo_other = C["recs"][par], C["recs"][1 - par]
-            if self._outgrown(S["captured"]):
-                S["graphs"], S["captured"] = {}, None
-            return S
-        if S is not None and S["D"] == D:
-            # a new topology (after an event): the per-node slots, the centre snapshots and the (pinned) count words stay --
-            # the node sets never change -- only the per-edge predictions follow the new edge list
-            keep = {k: S[k] for k in ("xs", "cen", "jb", "evf", "evh", "zf", "rw")}
-            Ea = (self.pred["edge_event"].numel() + 3) & ~3                    # (16-byte aligned segments)
-            flat = torch.empty(3 * D * Ea, dtype=torch.float32, device=dev)   # one allocation for all slots
-            pred = [{**slot, **edge} for slot, edge in zip(S["pred"], self._spec_edge_slots(flat, D, Ea))]
-        else:
-            keep = self._spec_node_slots(D)
-            pred = [{k: torch.empty_like(v) for k, v in self.pred.items()} for _ in range(D)]
-        S = self._spec = {
-            "in_place": False, "topology": self.graph, "cur": 0, "D": D,
-            "ea": [self.edge_attr, self._ea_other], "einfo": [self.einfo, self._einfo_other],
-            "pred": pred, "graphs": {}, "captured": None, "xs_valid": None, **keep}
+            S["in_place"], S["topology"], S["sets"] = self._cap is not None, self.graph, self._sets
+            self._invalidate_graphs(blocks=self._outgrown(S["captured"]))
+        if (S["cur"] & 1) != self._parity:   # (step() / step_events() in between left the other set current)
+            self._move_lengths_over(S["cur"] & 1)
         return S
 
     def _spec_node_slots(self, D: int):
@@ -1265,10 +1261,9 @@ class GrainRollout:
         main, st_d = torch.cuda.current_stream(), self._side[0]   # (the event counts on a stream of their own: neither
         keep, headed = [], None                                   #  model's chain waits for them)
         for slot in slots:
-            s, p = slot & 1, S["pred"][slot]
+            p = S["pred"][slot]
             ready, updated, headed = self._enqueue_overlapped_step(
-                S["ea"][s], S["ea"][1 - s], S["einfo"][s], S["einfo"][1 - s], S["xs"][slot], S["xs"][(slot + 1) % S["D"]],
-                p, S["zf"][slot], headed, slot)
+                slot & 1, S["xs"][slot], S["xs"][(slot + 1) % S["D"]], p, S["zf"][slot], headed, slot)
             keep.append((ready, updated, headed))
             with torch.cuda.stream(st_d):
                 st_d.wait_event(updated)   # grain_area of this step (and every cell of the regressor has reported its range)
@@ -1311,10 +1306,8 @@ class GrainRollout:
     def _spec_adopt(self, slot: int):
         """The rollout's current buffers := the state behind the step of `slot`."""
         S = self._spec
-        nxt = (slot + 1) & 1
-        self.pred = S["pred"][slot]
-        self.edge_attr, self._ea_other = S["ea"][nxt], S["ea"][1 - nxt]
-        self.einfo, self._einfo_other = S["einfo"][nxt], S["einfo"][1 - nxt]
+        self.pred, self._pred_at = S["pred"][slot], 1 + slot
+        self._parity = (slot + 1) & 1
         S["cur"] = (slot + 1) % S["D"]
 
     def run_events(self, n_steps: int):
@@ -1407,8 +1400,7 @@ class GrainRollout:
                     self.x["joint"][:, :2].copy_(keep_joints)
                 if void:   # ... but its edge lengths were overwritten by the void steps: the same kernel on the same x
                     self.be.step_refresh(self.x["joint"], self.x["grain"], self.zmax, self.flags,
-                                         [(self.graph.edge_index[et], self.x[et[0]], self.x[et[-1]], self.edge_attr[et])
-                                          for et in EDGE_TYPES])
+                                         self._refresh_edges(self.graph.edge_index))
             try:
                 events, switches = self._apply_events()
             except Exception:
@@ -1523,9 +1515,7 @@ class GrainRollout:
         E = self.edge_index[ET_JJ].size(1)
         if ses.n_pp != E:
             raise _lib.GGNNError("the topology session and the rollout's junction edge list disagree")
-        mg, mj = self.mask["grain"], self.mask["joint"]
-        if not (mg.dtype == np.int64 and mg.flags.c_contiguous and mj.dtype == np.int64 and mj.flags.c_contiguous):
-            mg, mj = self.mask["grain"], self.mask["joint"] = np.ascontiguousarray(mg, np.int64), np.ascontiguousarray(mj, np.int64)
+        mg, mj = self._host_masks()
         events, switches = ses.apply(N["xj"], N["yj"], N["yg"][:, 0], N["prob"][:E], ge, mg, mj, self.edge_threshold)
         if len(events) == 0 and len(switches) == 0:
             return None
@@ -1566,8 +1556,6 @@ class GrainRollout:
         if self._topo is not None and self._topo[1] is None:
             jj, jg = self.edge_index[ET_JJ], self.edge_index[JG]
             self._topo = (self._topo[0], jj, jg, (jj._version, jg._version))
-        if self._cap is None:   # (in place: the segment graphs stay)
-            self._drop_segment_graphs()
 
     def step(self):
         """Advance one rollout step; returns the prediction dict (tensors are reused)."""
@@ -1625,7 +1613,5 @@ class GrainRollout:
             # the step's fused refresh writes the lengths of the forward's edges (the masked tables' slots); grain 0's
             # edges of the full lists get theirs here -- the same kernel expression, z clamp off
             off = torch.zeros(2, dtype=torch.int32, device=self.x["joint"].device)
-            self.be.step_refresh(self.x["joint"], self.x["grain"], self.zmax, off,
-                                 [(self.edge_index[et], self.x[et[0]], self.x[et[-1]], self.edge_attr[et])
-                                  for et in EDGE_TYPES])
+            self.be.step_refresh(self.x["joint"], self.x["grain"], self.zmax, off, self._refresh_edges(self.edge_index))
         return {et: self.edge_attr[et].view(-1, 1) for et in EDGE_TYPES}

@@ -2208,13 +2208,15 @@ def test_fused_glue_launches_equal_the_separate_calls(clamp):
 
 
 @torch.no_grad()
+@pytest.mark.parametrize("written", ["x", "edge_attr"])
 @pytest.mark.parametrize("use_graph", [False, True])
-def test_pipelined_two_stream_rollout_equals_the_single_stream_plan(use_graph):
+def test_pipelined_two_stream_rollout_equals_the_single_stream_plan(use_graph, written):
     """The pipelined two-stream step (update, grain centres, refresh and the next edge records behind the
     regressor's heads, second edge_attr buffer, no join between the steps of a graph) is a re-ordering of the same
     launches: 23 steps on the folded 120 um fixture -- odd, so both edge_attr buffers end up current once, through
     4-step and single-step graphs -- must reproduce the single-stream plan bit for bit (x, edge_attr and every
-    prediction), also after the caller wrote into x between two runs (stale edge records)."""
+    prediction), also after the caller wrote into x, or in place into the junction edge lengths, between two runs (stale
+    edge records: the single-stream plan prepares them in every step, the pipelined one must notice the write)."""
     from graingraphnn_amd import GrainRollout
     x, ei, ea = load_graph("120")
     x, ea = {k: v.copy() for k, v in x.items()}, {k: v.copy() for k, v in ea.items()}
@@ -2228,7 +2230,10 @@ def test_pipelined_two_stream_rollout_equals_the_single_stream_plan(use_graph):
                           domain_offset=torch.from_numpy(off))
         assert ro._pipelined() == two_streams
         ro.run(10)
-        ro.x["joint"][:, 0] += 0.001              # the caller moves the junctions: the prepared records are stale
+        if written == "x":
+            ro.x["joint"][:, 0] += 0.001          # the caller moves the junctions: the prepared records are stale
+        else:
+            ro.edge_attr[JJ].mul_(1.25)           # ... or rescales the junction edge lengths in place
         ro.run(13)
         ros.append(ro)
     a, b = ros
@@ -2238,3 +2243,32 @@ def test_pipelined_two_stream_rollout_equals_the_single_stream_plan(use_graph):
         assert torch.equal(a.edge_attr[et], b.edge_attr[et]), et
     for k in a.pred:
         assert torch.equal(a.pred[k], b.pred[k]), k
+
+
+@torch.no_grad()
+@pytest.mark.parametrize("use_graph", [False, True])
+def test_pipelined_rollout_prepares_edge_records_only_after_a_write(use_graph, monkeypatch):
+    """The pipelined step gets its edge records from the refresh of the step before; a separate ggnn_edge_prepare (with a
+    new mirror of x) is due only when the caller wrote into x or edge_attr since -- seen through the tensors' version
+    counters.  The edge lengths, records and per-edge predictions are views of one allocation and share ONE counter:
+    the rollout's own steps must not look like a write (no prepare in step(), run(2), step()), and a real write must
+    still be seen (one prepare in the step behind it)."""
+    from graingraphnn_amd import GrainRollout
+    x, ei, ea = load_graph("40")
+    R, Cm = product_models(10020, 1.0, DEV)
+    ro = GrainRollout(R, Cm, tt(x, DEV), tt(ei, DEV), tt(ea, DEV), 6, use_graph=use_graph, joint_launches=False,
+                      concurrent=True)
+    assert ro._pipelined()
+    ro.run(3)
+    calls, prepare = [], ro.be.edge_prepare
+    monkeypatch.setattr(ro.be, "edge_prepare", lambda items: (calls.append(len(items)), prepare(items))[1])
+    ro.step()
+    ro.run(2)
+    ro.step()
+    print("ggnn_edge_prepare launches with nothing written:", len(calls))
+    assert len(calls) == 0
+    ro.x["joint"][:, 0] += 0.001
+    ro.step()
+    torch.cuda.synchronize()
+    print("ggnn_edge_prepare launches behind a write into x:", len(calls))
+    assert len(calls) == 1

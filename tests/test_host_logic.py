@@ -610,3 +610,43 @@ def test_sampled_parameter_versions_notice_what_changes_a_whole_model():
     with torch.no_grad():
         dict(R.named_parameters())[name].mul_(1.5)        # one tensor edited in place: the full walk's business
     assert _param_version(R) != full
+
+
+def test_edge_sets_layout():
+    """rollout._EdgeSets: both sets of edge lengths and edge records of every edge type and the two per-edge predictions
+    as views of ONE allocation.  Capacities with an empty list and sizes that are no multiple of four, cut at the
+    capacities, at smaller lists and at the capacities again: every view has its documented shape, starts on a 16-byte
+    boundary and overlaps no other view of its cut; no start moves with the list sizes; nothing reaches beyond the
+    allocation; lists above a capacity are refused."""
+    from graingraphnn_amd.rollout import ET_JJ, GJ, JG, _EdgeSets
+    U, ROW = _lib.GGNN_UNIT_EDGES, _lib.GGNN_EINFO_ROW
+    cap = {ET_JJ: 0, GJ: 1, JG: 5}
+    sets = _EdgeSets(cap, torch.device("cpu"), zero=False)
+    assert sets.buf.dtype == torch.float32 and sets.buf.dim() == 1 and sets.buf.data_ptr() % 16 == 0
+    starts = []
+    for E in (cap, {ET_JJ: 0, GJ: 0, JG: 3}, cap):
+        lengths, records, edge_event, edge = sets.cut(E)
+        assert len(lengths) == 2 and len(records) == 2
+        views = [edge_event, edge]
+        for s in range(2):
+            assert set(lengths[s]) == set(EDGE_TYPES) and set(records[s]) == set(EDGE_TYPES)
+            for et in EDGE_TYPES:
+                assert tuple(lengths[s][et].shape) == (E[et],), (s, et)
+                assert tuple(records[s][et].shape) == (E[et] + U, ROW), (s, et)
+                views += [lengths[s][et], records[s][et]]
+        assert tuple(edge_event.shape) == (E[ET_JJ],) and tuple(edge.shape) == (E[ET_JJ], 2)
+        spans = []
+        for v in views:
+            assert v.dtype == torch.float32 and v.is_contiguous()
+            assert v.untyped_storage().data_ptr() == sets.buf.untyped_storage().data_ptr()
+            assert (4 * v.storage_offset()) % 16 == 0
+            spans.append((v.storage_offset(), v.storage_offset() + v.numel()))
+        assert len({a for a, _ in spans}) == len(spans)                      # (an empty view has a place of its own, too)
+        ordered = sorted(spans)
+        assert all(b <= a2 for (_, b), (a2, _) in zip(ordered, ordered[1:]))
+        assert ordered[0][0] >= 0 and ordered[-1][1] <= sets.buf.numel()
+        starts.append([a for a, _ in spans])
+    assert starts[0] == starts[1] == starts[2]
+    for et in EDGE_TYPES:
+        with pytest.raises(_lib.GGNNError):
+            sets.cut({**cap, et: cap[et] + 1})
