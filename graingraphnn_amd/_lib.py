@@ -29,6 +29,7 @@ GGNN_FLAG_QOI_OVERFLOW = 2
 GGNN_ADAM_CHUNK, GGNN_ADAM_MAX_TENSORS, GGNN_ADAM_MAX_GROUPS = 4096, 384, 8
 GGNN_ROWGEMM_MAX_PACK = 8
 GGNN_MSE_MAX_TERMS, GGNN_MSE_BLOCKS = 4, 64
+GGNN_COLLATE_MAX_BATCH, GGNN_COLLATE_MAX_ROWS, GGNN_COLLATE_MAX_LISTS, GGNN_COLLATE_MAX_KINDS = 64, 12, 3, 5
 GGNN_METRIC_MAX_TERMS, GGNN_METRIC_MAX_THR, GGNN_METRIC_BLOCKS = 4, 16, 64
 GGNN_METRIC_F64_SLOTS, GGNN_METRIC_I64_SLOTS = 9, 49      # err[4] | norm[4] | loss;  TP[16] | FP[16] | FN[16] | batches
 GGNN_METRIC_WS_WORDS = GGNN_METRIC_BLOCKS * 56 + 1
@@ -56,6 +57,7 @@ EXPORTED_SYMBOLS = (
     "ggnn_workspace_bytes",
     "ggnn_qoi_accumulate", "ggnn_qoi_finalize", "ggnn_process_schedule",
     "ggnn_metric_record",
+    "ggnn_masked_mse_rows", "ggnn_collate_batch", "ggnn_reverse_slots",
 )
 
 
@@ -280,6 +282,41 @@ class MseArgs(Structure):
                 ("workspace", c_void_p), ("loss", c_void_p), ("scale", c_float), ("n_terms", c_int32)]
 
 
+class MseCounts(Structure):
+    """Mirror of `ggnn_mse_counts`."""
+    _fields_ = [("rows", c_void_p * GGNN_MSE_MAX_TERMS), ("row_elems", c_int64 * GGNN_MSE_MAX_TERMS)]
+
+
+class CollateRows(Structure):
+    """Mirror of `ggnn_collate_rows`."""
+    _fields_ = [("src", c_void_p), ("dst", c_void_p), ("cap", c_int64), ("words", c_int32), ("kind", c_int32),
+                ("pad_word", ctypes.c_uint32), ("meta", c_int32)]
+
+
+class CollateList(Structure):
+    """Mirror of `ggnn_collate_list`."""
+    _fields_ = [("src", c_void_p), ("dst", c_void_p), ("dst_flipped", c_void_p), ("ld_src", c_int64), ("cap", c_int64),
+                ("pad_src", c_int64), ("pad_dst", c_int64),
+                ("kind", c_int32), ("kind_src", c_int32), ("kind_dst", c_int32), ("reserved", c_int32)]
+
+
+class CollateArgs(Structure):
+    """Mirror of `ggnn_collate_args`."""
+    _fields_ = [("sample_off", c_void_p * GGNN_COLLATE_MAX_KINDS), ("batch_off", c_void_p * GGNN_COLLATE_MAX_KINDS),
+                ("count", c_void_p * GGNN_COLLATE_MAX_KINDS),
+                ("order", c_void_p), ("cursor_in", c_void_p), ("cursor_out", c_void_p), ("sync_word", c_void_p),
+                ("rows", CollateRows * GGNN_COLLATE_MAX_ROWS), ("lists", CollateList * GGNN_COLLATE_MAX_LISTS),
+                ("n_samples", c_int64),
+                ("n_batches", c_int32), ("batch_size", c_int32), ("n_kinds", c_int32), ("n_rows", c_int32),
+                ("n_lists", c_int32), ("reserved", c_int32)]
+
+
+class ReverseSlotsArgs(Structure):
+    """Mirror of `ggnn_reverse_slots_args`."""
+    _fields_ = [("perm", c_void_p), ("r_perm", c_void_p), ("r_slot", c_void_p), ("scratch", c_void_p),
+                ("E_kept", c_void_p), ("E", c_int64)]
+
+
 class AggregateBwdArgs(Structure):
     """Mirror of `ggnn_aggregate_bwd_args`."""
     _fields_ = [
@@ -423,6 +460,12 @@ def _declare(lib):
     lib.ggnn_sum_rows.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_void_p]
     lib.ggnn_masked_mse.restype = c_int
     lib.ggnn_masked_mse.argtypes = [POINTER(MseArgs), c_void_p]
+    lib.ggnn_masked_mse_rows.restype = c_int
+    lib.ggnn_masked_mse_rows.argtypes = [POINTER(MseArgs), POINTER(MseCounts), c_void_p]
+    lib.ggnn_collate_batch.restype = c_int
+    lib.ggnn_collate_batch.argtypes = [POINTER(CollateArgs), c_void_p]
+    lib.ggnn_reverse_slots.restype = c_int
+    lib.ggnn_reverse_slots.argtypes = [POINTER(ReverseSlotsArgs), c_int, c_void_p]
     lib.ggnn_pack_weights_batch.restype = c_int
     lib.ggnn_pack_weights_batch.argtypes = [POINTER(PackArgs), c_int, c_void_p]
     lib.ggnn_pack_weights_backward_batch.restype = c_int

@@ -925,10 +925,24 @@ class HipBackend:
         b.n_flat2, b.n_kq, b.inv_m, b.inv_kq_m = plan.n_flat2, plan.n_kq, plan.inv.size(1), plan.inv_kq.size(1)
         b.n_tail = g_flat.numel() - plan.n_flat
 
-    def masked_mse(self, terms, scale, loss, want_grad=True):
+    def masked_mse(self, terms, scale, loss, want_grad=True, rows=None):
         """ggnn_masked_mse: `terms` = [(pred, target, mask or None)], contiguous float32 CUDA tensors; mask has the shape
-        of pred or one entry per leading row of it.  Returns the gradients [g_pred] (None each with want_grad=False)."""
+        of pred or one entry per leading row of it.  Returns the gradients [g_pred] (None each with want_grad=False).
+        `rows`: per term None or an int64 [1] device tensor -- the number of real leading rows of a term whose tensors carry
+        pad rows behind them (mask 0 there): the term's mean is taken over them (ggnn_masked_mse_rows)."""
         a = _lib.MseArgs()
+        q = None
+        if rows is not None and any(r is not None for r in rows):
+            if len(rows) != len(terms):
+                raise _lib.GGNNError("ggnn_masked_mse_rows: one row count (or None) per term")
+            q = _lib.MseCounts()
+            for k, ((p, _, _), r) in enumerate(zip(terms, rows)):
+                if r is None:
+                    continue
+                _require_cuda(r)
+                if r.dtype != torch.int64 or r.numel() != 1 or p.dim() < 1 or p.size(0) < 1:
+                    raise _lib.GGNNError("ggnn_masked_mse_rows: a row count is an int64 [1] device tensor")
+                q.rows[k], q.row_elems[k] = r.data_ptr(), p.numel() // p.size(0)
         if not 1 <= len(terms) <= _lib.GGNN_MSE_MAX_TERMS:
             raise _lib.GGNNError("ggnn_masked_mse: 1..%d terms" % _lib.GGNN_MSE_MAX_TERMS)
         grads = []
@@ -955,8 +969,33 @@ class HipBackend:
         if ws is None:
             ws = self._mse_ws[key] = torch.zeros(_lib.GGNN_MSE_BLOCKS + 1, dtype=torch.float64, device=loss.device)
         a.workspace, a.loss, a.scale, a.n_terms = ws.data_ptr(), loss.data_ptr(), scale, len(terms)
-        self._launch(self.lib.ggnn_masked_mse, "ggnn_masked_mse", ctypes.byref(a), _lib.current_stream())
+        if q is None:
+            self._launch(self.lib.ggnn_masked_mse, "ggnn_masked_mse", ctypes.byref(a), _lib.current_stream())
+        else:
+            self._launch(self.lib.ggnn_masked_mse_rows, "ggnn_masked_mse_rows", ctypes.byref(a), ctypes.byref(q),
+                         _lib.current_stream())
         return grads
+
+    # -- device-resident mini-batches (batches.py) ---------------------------------------
+    def collate_batch(self, args):
+        """ggnn_collate_batch on a filled `_lib.CollateArgs` (batches.DeviceBatches keeps one: every address in it is fixed)."""
+        self._launch(self.lib.ggnn_collate_batch, "ggnn_collate_batch", ctypes.byref(args), _lib.current_stream())
+
+    def reverse_slots(self, items):
+        """ggnn_reverse_slots: items = [(csr, rcsr, r_slot_out [E] int32, scratch [E] int32)], the forward and the reverse
+        table of a list and the kept-slot word they share (csr.E_dev, None = all E slots)."""
+        arr = (_lib.ReverseSlotsArgs * len(items))()
+        for a, (csr, rcsr, r_slot, scratch) in zip(arr, items):
+            _require_cuda(csr.perm, rcsr.perm, r_slot, scratch, csr.E_dev)
+            E = csr.E
+            for t in (r_slot, scratch):
+                if t.dtype != torch.int32 or not t.is_contiguous() or t.numel() < E:
+                    raise _lib.GGNNError("ggnn_reverse_slots: r_slot and scratch are contiguous int32 [E] tensors")
+            if rcsr.E != E or csr.perm.numel() < E or rcsr.perm.numel() < E:
+                raise _lib.GGNNError("ggnn_reverse_slots: the two tables must be built from one list")
+            a.perm, a.r_perm, a.r_slot, a.scratch = csr.perm.data_ptr(), rcsr.perm.data_ptr(), r_slot.data_ptr(), scratch.data_ptr()
+            a.E_kept, a.E = ptr(csr.E_dev), E
+        self._launch(self.lib.ggnn_reverse_slots, "ggnn_reverse_slots", arr, len(items), _lib.current_stream())
 
     def metric_record(self, acc, terms, with_norm, mode, score, label, label_mask, thresholds, loss=None):
         """ggnn_metric_record: one validation batch into the accumulator `acc` (int64 [F64_SLOTS + I64_SLOTS] on the

@@ -67,7 +67,9 @@ __global__ __launch_bounds__(AD_THREADS) void adam_advance_kernel(const ggnn_ada
 // GGNN_MSE_BLOCKS workgroups, each over a fixed share of the elements; their partial sums (doubles) go through the
 // workspace and the last workgroup to arrive adds them in index order: the result does not depend on the arrival order.
 constexpr int MSE_THREADS = 256;
-__global__ __launch_bounds__(MSE_THREADS) void masked_mse_kernel(const ggnn_mse_args A) {
+// Q: ggnn_masked_mse_rows -- the mean's denominator of a term is a device word (rows x row_elems) where one is given: the
+// tensors then carry pad rows, which the walk over all n elements meets with mask 0.
+__global__ __launch_bounds__(MSE_THREADS) void masked_mse_kernel(const ggnn_mse_args A, const ggnn_mse_counts Q) {
   __shared__ double red[MSE_THREADS / 64];
   const int64_t gtid = (int64_t)blockIdx.x * MSE_THREADS + threadIdx.x, gstride = (int64_t)GGNN_MSE_BLOCKS * MSE_THREADS;
   double total = 0.0;
@@ -80,14 +82,15 @@ __global__ __launch_bounds__(MSE_THREADS) void masked_mse_kernel(const ggnn_mse_
     const float* __restrict__ m = A.mask[k];
     float* __restrict__ g = A.g_pred[k];
     const int64_t div = A.mask_div[k];
-    const float gs = 2.0f * A.scale / (float)n;
+    const int64_t nd = Q.rows[k] ? *Q.rows[k] * Q.row_elems[k] : n;   // (NULL: the mean over all n elements)
+    const float gs = nd > 0 ? 2.0f * A.scale / (float)nd : 0.f;
     float acc = 0.f;
     for (int64_t i = gtid; i < n; i += gstride) {
       const float d = p[i] - y[i], w = m ? m[div == 1 ? i : i / div] : 1.0f;
       acc = __builtin_fmaf(w * d, d, acc);
       if (g) g[i] = gs * w * d;
     }
-    total += (double)acc / (double)n;
+    if (nd > 0) total += (double)acc / (double)nd;
   }
   for (int o = 32; o > 0; o >>= 1) total += __shfl_down(total, o, 64);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = total;
@@ -245,15 +248,25 @@ extern "C" int ggnn_adam_step(const ggnn_adam_args* args, ggnn_stream_t stream) 
   return launch_status();
 }
 
-extern "C" int ggnn_masked_mse(const ggnn_mse_args* args, ggnn_stream_t stream) {
+extern "C" int ggnn_masked_mse_rows(const ggnn_mse_args* args, const ggnn_mse_counts* counts, ggnn_stream_t stream) {
   using namespace ggnn;
   if (!args || !args->loss || !args->workspace || args->n_terms < 1 || args->n_terms > GGNN_MSE_MAX_TERMS) return GGNN_EINVAL;
   for (int k = 0; k < args->n_terms; ++k) {
     if (args->n[k] < 0 || (args->n[k] > 0 && (!args->pred[k] || !args->target[k]))) return GGNN_EINVAL;
     if (args->mask[k] && args->mask_div[k] < 1) return GGNN_EINVAL;
   }
-  hipLaunchKernelGGL(masked_mse_kernel, dim3(GGNN_MSE_BLOCKS), dim3(MSE_THREADS), 0, (hipStream_t)stream, *args);
+  ggnn_mse_counts Q = {};
+  if (counts) {
+    Q = *counts;
+    for (int k = 0; k < args->n_terms; ++k)
+      if (Q.rows[k] && (Q.row_elems[k] < 1 || ((uintptr_t)Q.rows[k] & 7))) return GGNN_EINVAL;
+  }
+  hipLaunchKernelGGL(masked_mse_kernel, dim3(GGNN_MSE_BLOCKS), dim3(MSE_THREADS), 0, (hipStream_t)stream, *args, Q);
   return launch_status();
+}
+
+extern "C" int ggnn_masked_mse(const ggnn_mse_args* args, ggnn_stream_t stream) {
+  return ggnn_masked_mse_rows(args, nullptr, stream);
 }
 
 // ---- ggnn_train_input_rows: [x | 0 .. | 1 0 0 0], the data part of the weight gradients' B operands (include/ggnn.h) ----

@@ -93,12 +93,34 @@ class GraphCSR:
 
 _graph_cache: Dict[tuple, GraphCSR] = {}
 _GRAPH_CACHE_MAX = 8
+# graphs whose tables are refilled IN PLACE from list tensors that keep their addresses (batches.DeviceBatches): found by
+# those addresses -- a kernel's writes bump no _version, and a rebuild from the lists would read the pad edges back in
+_inplace_graphs: Dict[tuple, "weakref.ref"] = {}
+
+
+def register_inplace_graph(graph: GraphCSR):
+    """`graph_for` answers the list tensors of `graph` (the same tensor objects) with `graph` itself from now on, for as
+    long as the caller keeps it alive."""
+    import weakref
+    key = tuple(graph.edge_index[et].data_ptr() for et in EDGE_TYPES)
+
+    def drop(ref):   # (memory handed out again may already stand for a newer graph under this key)
+        if _inplace_graphs.get(key) is ref:
+            del _inplace_graphs[key]
+    _inplace_graphs[key] = weakref.ref(graph, drop)
+    return graph
 
 
 def graph_for(backend, edge_index_dict, n_nodes, trusted: bool = False, boundary: str = "periodic",
               traj_grain_off=None) -> GraphCSR:
     """CSR of `edge_index_dict`, rebuilt only when a tensor is replaced or modified in place
     (Cmodel.update swaps the tensors after a topological event, models.py:841-845)."""
+    if _inplace_graphs:   # the lists of a DeviceBatches: its tables are rebuilt in place by its next(), never from here
+        g = _inplace_graphs.get(tuple(edge_index_dict[et].data_ptr() for et in EDGE_TYPES if et in edge_index_dict))
+        g = None if g is None else g()
+        if g is not None and all(edge_index_dict[et] is g.edge_index[et] for et in EDGE_TYPES) \
+                and all(g.n_nodes[nt] == n for nt, n in n_nodes.items()) and boundary == "periodic":
+            return _pins.note(g)
     key = tuple((et, edge_index_dict[et].data_ptr(), edge_index_dict[et]._version,
                  tuple(edge_index_dict[et].shape)) for et in EDGE_TYPES if et in edge_index_dict)
     key = key + tuple(sorted(n_nodes.items()))

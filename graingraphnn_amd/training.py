@@ -73,6 +73,9 @@ _topo_cache: Dict[int, TrainTopology] = {}
 
 
 def train_topology(backend, graph) -> TrainTopology:
+    t = getattr(graph, "train_topology", None)   # a DeviceBatches' graph: its reverse tables are refilled in place beside it
+    if t is not None and t.graph is graph:
+        return _pins.note(t)
     t = _topo_cache.get(id(graph))
     if t is None or t.graph is not graph:
         if len(_topo_cache) >= 8:
@@ -533,12 +536,13 @@ class _MaskedMSE(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, scale, backend, n_terms, *tensors):
-        preds, ys, masks = tensors[:n_terms], tensors[n_terms:2 * n_terms], tensors[2 * n_terms:]
+        preds, ys, masks = tensors[:n_terms], tensors[n_terms:2 * n_terms], tensors[2 * n_terms:3 * n_terms]
+        rows = tensors[3 * n_terms:]   # (optional: the terms' real row counts, device words -- tensors with pad rows)
         c = lambda t: None if t is None else t.detach().to(torch.float32).contiguous()
         loss = torch.empty((), dtype=torch.float32, device=preds[0].device)
         grads = backend.masked_mse([(c(p), c(y), c(m)) for p, y, m in zip(preds, ys, masks)], scale, loss,
-                                   want_grad=any(ctx.needs_input_grad[3:3 + n_terms]))
-        ctx.n_terms = n_terms
+                                   want_grad=any(ctx.needs_input_grad[3:3 + n_terms]), **({"rows": rows} if rows else {}))
+        ctx.n_terms, ctx.n_rows = n_terms, len(rows)
         ctx.save_for_backward(*[g for g in grads if g is not None])
         return loss
 
@@ -551,15 +555,21 @@ class _MaskedMSE(torch.autograd.Function):
             scaled = torch._foreach_mul(list(grads), g_loss)
             out = [g if ctx.needs_input_grad[3 + k] else None for k, g in enumerate(scaled)]
         out += [None] * (ctx.n_terms - len(out))
-        return (None, None, None, *out, *([None] * (2 * ctx.n_terms)))
+        return (None, None, None, *out, *([None] * (2 * ctx.n_terms + ctx.n_rows)))
 
 
-def regressor_loss(y_dict, pred, mask):
+def regressor_loss(y_dict, pred, mask, rows=None):
     """train.py:31-37 (edge_len off): 100 * (mean(mask_j (y_j - p_j)^2) + mean(mask_g (y_g - p_g)^2)).  On the GPU one
     launch computes the loss and its gradient (`_MaskedMSE`); `regressor_loss_recorded` is the same expression as recorded
-    torch ops."""
+    torch ops.  `rows` = {'joint': int64 [1], 'grain': int64 [1]} device words: the tensors carry pad rows with mask 0
+    behind that many real ones (a `DeviceBatches` batch: pass its `.rows`), and the means are taken over the real rows."""
     pj, pg = pred["joint"], pred["grain"]
     mj, mg = mask["joint"], mask["grain"]
+    if rows is not None:
+        if not (pj.is_cuda and pj.dtype == torch.float32 and pg.dtype == torch.float32):
+            raise _lib.GGNNError("regressor_loss(rows=...): float32 predictions on the device (the fused loss kernel)")
+        return _MaskedMSE.apply(100.0, default_backend(), 2, pj, pg, y_dict["joint"], y_dict["grain"], mj, mg,
+                                rows["joint"], rows["grain"])
     fits = lambda m, p: m.shape == p.shape or (m.dim() >= 1 and m.numel() == p.size(0))   # elementwise or one per row
     if pj.is_cuda and pj.dtype == torch.float32 and pg.dtype == torch.float32 and fits(mj, pj) and fits(mg, pg) \
             and y_dict["joint"].shape == pj.shape and y_dict["grain"].shape == pg.shape \
@@ -790,15 +800,35 @@ class GraphedTrainStep:
     step (3.7 -> 2.3 ms at the 10k-grain graph, 2.2 -> 0.9 ms for four 40 um graphs; same update).  The .grad
     tensors are those of the captured step (its memory pool): valid after every call, replaced by none.  Warm-up
     (3 eager steps, which DO update the model) and capture (which only records) run on a side stream, PyTorch's
-    whole-network capture recipe."""
+    whole-network capture recipe.
 
-    def __init__(self, model, optimizer, loss_fn, x_dict, edge_index_dict, edge_attr, y_dict, autocast_dtype=None,
-                 warmup: int = 3):
+    Changing mini-batches (the reference's shuffled loop, train.py:365-366): pass a `DeviceBatches` instead of
+    tensors.  The captured step then begins with the collation of the batch at the device cursor and the in-place rebuild of
+    its tables, so one capture serves every batch of every epoch, across `DeviceDataset.set_order` too:
+
+        batches = DeviceBatches(DeviceDataset(samples, batch_size=4))
+        step = GraphedTrainStep(model, optimizer, lambda pred, b: regressor_loss(b.y_dict, pred, b.mask, rows=b.rows), batches)
+        batches.dataset.set_order(torch.randperm(n, generator=g))    # per epoch
+        loss = step.step()               # one graph launch, no host-to-device copy; also `step.loss`"""
+
+    def __init__(self, model, optimizer, loss_fn, x_dict, edge_index_dict=None, edge_attr=None, y_dict=None,
+                 autocast_dtype=None, warmup: int = 3):
         self.model, self.opt, self.loss_fn = model, optimizer, loss_fn
-        self.x = {k: v.detach().clone() for k, v in x_dict.items()}
-        self.ei = edge_index_dict
-        self.ea = {k: v.detach().clone() for k, v in edge_attr.items()}
-        self.y = {k: v.detach().clone() for k, v in y_dict.items()}
+        from .batches import DeviceBatches
+        self.batches = x_dict if isinstance(x_dict, DeviceBatches) else None
+        if self.batches is not None:
+            # Changing mini-batches: the captured step starts with the batch object's next() -- collation of the
+            # batch at the device cursor, the tables rebuilt in place -- and reads its buffers, whose addresses and shapes
+            # never change; `loss_fn(pred, batches)` takes the batch object.  The warm-up steps consume (and train on) the
+            # first `warmup` batches of the current order: call set_order() afterwards to start an epoch at its first batch.
+            if edge_index_dict is not None or edge_attr is not None or y_dict is not None:
+                raise ValueError("GraphedTrainStep(model, optimizer, loss_fn, batches): the batch object brings its own tensors")
+            self.x, self.ei, self.ea, self.y = x_dict.x_dict, x_dict.edge_index_dict, x_dict.edge_attr, x_dict
+        else:
+            self.x = {k: v.detach().clone() for k, v in x_dict.items()}
+            self.ei = edge_index_dict
+            self.ea = {k: v.detach().clone() for k, v in edge_attr.items()}
+            self.y = {k: v.detach().clone() for k, v in y_dict.items()}
         self.autocast_dtype = autocast_dtype
         if warmup < 1:
             raise ValueError("GraphedTrainStep needs at least one eager warm-up step before the capture")
@@ -819,7 +849,20 @@ class GraphedTrainStep:
         torch.cuda.current_stream().wait_stream(s)
         self._pins = list({id(o): o for o in self._pins}.values())
 
+    @property
+    def loss(self):
+        """The loss of the last step (a device tensor the next replay overwrites)."""
+        return self._loss
+
+    def step(self):
+        """One optimisation step on the next mini-batch of the batch object: one graph launch, no host-to-device copy."""
+        if self.batches is None:
+            raise ValueError("step() belongs to GraphedTrainStep(model, optimizer, loss_fn, batches); call the object with tensors")
+        return self()
+
     def _eager(self):
+        if self.batches is not None:
+            self.batches.next()   # (recorded, not run, inside the capture: the host's batch count stays where it is)
         with torch.autocast("cuda", dtype=self.autocast_dtype or torch.bfloat16, enabled=self.autocast_dtype is not None):
             loss = self.loss_fn(self.model(self.x, self.ei, self.ea), self.y)
         self.opt.zero_grad(set_to_none=True)   # (inside the capture the new .grad tensors come from the graph's pool)
@@ -833,7 +876,11 @@ class GraphedTrainStep:
     def __call__(self, x_dict=None, edge_attr=None, y_dict=None):
         """Copies the batch into the captured buffers (tensors that ARE the buffers are skipped), replays
         the step and returns the loss of that step (a tensor the next replay overwrites)."""
-        for dst, src in ((self.x, x_dict), (self.ea, edge_attr), (self.y, y_dict)):
+        if self.batches is not None:
+            if x_dict is not None or edge_attr is not None or y_dict is not None:
+                raise ValueError("a step over a batch object takes no tensors: the replay collates its next batch itself")
+            self.batches._advanced()
+        for dst, src in (() if self.batches is not None else ((self.x, x_dict), (self.ea, edge_attr), (self.y, y_dict))):
             for k, v in (src or {}).items():
                 if v is not dst[k]:
                     dst[k].copy_(v)
@@ -841,3 +888,6 @@ class GraphedTrainStep:
             self.opt.sync_hyperparams()
         self.graph.replay()
         return self._loss
+
+
+from .batches import DeviceBatches, DeviceDataset  # noqa: E402,F401  (training on device-resident mini-batches)

@@ -1049,6 +1049,84 @@ typedef struct ggnn_mse_args {
   int32_t n_terms;
 } ggnn_mse_args;
 int ggnn_masked_mse(const ggnn_mse_args* args, ggnn_stream_t stream);
+/* The same launch for terms whose tensors carry pad rows behind the real ones (a batch buffer of capacity shape,
+ * ggnn_collate_batch): the mean of term k is taken over *rows[k] * row_elems[k] elements, read at RUN time, where rows[k] is
+ * not NULL -- the sum still walks all n[k] elements, so the pad rows must add exact zeros (mask 0, finite operands).
+ * rows[k] NULL (or counts NULL) = n[k]: ggnn_masked_mse.  A count <= 0 makes the term and its gradient zero. */
+typedef struct ggnn_mse_counts {
+  const int64_t* rows[GGNN_MSE_MAX_TERMS]; /* DEVICE [1] each, or NULL */
+  int64_t row_elems[GGNN_MSE_MAX_TERMS];
+} ggnn_mse_counts;
+int ggnn_masked_mse_rows(const ggnn_mse_args* args, const ggnn_mse_counts* counts, ggnn_stream_t stream);
+
+/* Training on device-resident mini-batches.  The dataset lives in ARENAS: per array kind the rows of all samples
+ * one after another, per-sample offsets sample_off[kind][n_samples + 1]; a sample's edge indices are local to it.
+ * ggnn_collate_batch = the collation of train.py:365-366 (PyG DataLoader: node rows concatenated, edge indices offset by the
+ * node counts of the samples in front) in ONE launch: with b = *cursor_in modulo n_batches and the sample ids
+ * order[b * batch_size .. + batch_size) (-1 = an empty slot)
+ *   rows[j]   a row array of `words` 4-byte words per row (features, targets, masks, edge attributes, labels: any dtype of
+ *             4 or 8 bytes): dst holds the batch's rows from row 0, every word of the rows behind them is pad_word;
+ *   lists[j]  an edge list: dst [2][cap] = the samples' lists, sources shifted by the slot's first row of kind_src,
+ *             destinations by that of kind_dst; the edges behind them are (pad_src, pad_dst) -- two rows the caller keeps
+ *             free of real nodes and masks out of the tables (ggnn_csr_mask); dst_flipped (optional) the same list with the
+ *             two rows swapped (the list of the reverse table);
+ *   count[kind] = the batch's real rows / edges, batch_off[kind][batch_size + 1] = the first row / edge of every slot
+ *             (written by the array with meta = 1 of a node kind, by the list of an edge kind).
+ * The pad is rewritten by every call.  The grid depends on the capacities only; nothing is allocated, no floating-point or
+ * data atomics: an integer ticket (sync_word, zero before the first call and left zero) lets the last workgroup store
+ * *cursor_out = *cursor_in + 1, which may be the same word -- a replayed hipGraph moves on to the next batch by itself.
+ * The caller guarantees that every batch fits (capacities from the batch_size largest samples) and that the arenas hold
+ * what sample_off says; ids outside [0, n_samples) are empty slots.  GGNN_EINVAL without a launch: NULL operands, sizes
+ * outside their ranges, kinds outside [0, n_kinds). */
+#define GGNN_COLLATE_MAX_BATCH 64
+#define GGNN_COLLATE_MAX_ROWS 12
+#define GGNN_COLLATE_MAX_LISTS 3
+#define GGNN_COLLATE_MAX_KINDS 5
+typedef struct ggnn_collate_rows {
+  const uint32_t* src;
+  uint32_t* dst;
+  int64_t cap;       /* rows of dst */
+  int32_t words;     /* 1 .. 64 */
+  int32_t kind;
+  uint32_t pad_word;
+  int32_t meta;      /* 1: this array's launch share also writes count[kind] and batch_off[kind] */
+} ggnn_collate_rows;
+typedef struct ggnn_collate_list {
+  const int64_t* src;   /* [2][ld_src] */
+  int64_t* dst;         /* [2][cap] */
+  int64_t* dst_flipped; /* [2][cap] or NULL */
+  int64_t ld_src, cap;
+  int64_t pad_src, pad_dst;
+  int32_t kind, kind_src, kind_dst, reserved;
+} ggnn_collate_list;
+typedef struct ggnn_collate_args {
+  const int64_t* sample_off[GGNN_COLLATE_MAX_KINDS];
+  int64_t* batch_off[GGNN_COLLATE_MAX_KINDS];
+  int64_t* count[GGNN_COLLATE_MAX_KINDS];
+  const int32_t* order; /* [n_batches][batch_size] */
+  const int32_t* cursor_in;
+  int32_t* cursor_out;
+  int32_t* sync_word;
+  ggnn_collate_rows rows[GGNN_COLLATE_MAX_ROWS];
+  ggnn_collate_list lists[GGNN_COLLATE_MAX_LISTS];
+  int64_t n_samples;
+  int32_t n_batches, batch_size, n_kinds, n_rows, n_lists, reserved;
+} ggnn_collate_args;
+int ggnn_collate_batch(const ggnn_collate_args* args, ggnn_stream_t stream);
+
+/* r_slot[q] = the forward CSR slot of the edge in reverse (source-grouped) CSR slot q, for tables of which only the first
+ * *E_kept slots are filled (masked builds; E_kept NULL = E): perm / r_perm = the two tables' slot -> original edge maps
+ * ([E] int32, ggnn_csr_args.perm), scratch [E] int32; r_slot[q >= *E_kept] = 0.  Up to GGNN_COLLATE_MAX_LISTS lists per call,
+ * two launches, no read-back. */
+typedef struct ggnn_reverse_slots_args {
+  const int32_t* perm;
+  const int32_t* r_perm;
+  int32_t* r_slot;
+  int32_t* scratch;
+  const int64_t* E_kept; /* DEVICE [1] or NULL */
+  int64_t E;
+} ggnn_reverse_slots_args;
+int ggnn_reverse_slots(const ggnn_reverse_slots_args* lists, int n_lists, ggnn_stream_t stream);
 
 /* Validation metrics (metrics.py:23-72 feature_metric.record, :124-217 grain_class_acc / class_acc): ONE launch adds one
  * validation batch to a device-resident accumulator; nothing is read back before the epoch's summary.
