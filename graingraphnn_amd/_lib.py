@@ -45,7 +45,7 @@ EXPORTED_SYMBOLS = (
     "ggnn_period_gat_aggregate_batch", "ggnn_period_gat_aggregate_enc_batch", "ggnn_encoder_cell_batch",
     "ggnn_encoder_cell_values_batch",
     "ggnn_decoder_cell_batch",
-    "ggnn_aggregate_bwd_partials", "ggnn_period_gat_aggregate_backward",
+    "ggnn_aggregate_bwd_partials", "ggnn_period_gat_aggregate_backward", "ggnn_period_gat_aggregate_backward_inputs",
     "ggnn_lstm_epilogue_batch", "ggnn_heads_regressor", "ggnn_heads_regressor_update",
     "ggnn_step_refresh_prepare",
     "ggnn_lstm_train_forward_batch", "ggnn_lstm_train_backward_batch", "ggnn_train_input_rows", "ggnn_sum_rows_batch",
@@ -334,6 +334,15 @@ class AggregateBwdArgs(Structure):
     ]
 
 
+class AggregateBwdInputs(Structure):
+    """Mirror of `ggnn_aggregate_bwd_inputs` (the input-gradient extension passed beside `ggnn_aggregate_bwd_args`)."""
+    _fields_ = [
+        ("perm", c_void_p), ("edge_grad", c_void_p), ("g_x_src", c_void_p), ("g_x_dst", c_void_p), ("g_edge_attr", c_void_p),
+        ("ldgx_src", c_int64), ("ldgx_dst", c_int64),
+        ("f_src", c_int32), ("g_x_src_accumulate", c_int32), ("g_x_dst_accumulate", c_int32), ("reserved", c_int32),
+    ]
+
+
 class EpilogueArgs(Structure):
     """Mirror of `ggnn_epilogue_args`."""
     _fields_ = [
@@ -423,6 +432,8 @@ def _declare(lib):
     lib.ggnn_aggregate_bwd_partials.argtypes = [c_int64]
     lib.ggnn_period_gat_aggregate_backward.restype = c_int
     lib.ggnn_period_gat_aggregate_backward.argtypes = [POINTER(AggregateBwdArgs), c_void_p]
+    lib.ggnn_period_gat_aggregate_backward_inputs.restype = c_int
+    lib.ggnn_period_gat_aggregate_backward_inputs.argtypes = [POINTER(AggregateBwdArgs), POINTER(AggregateBwdInputs), c_void_p]
     lib.ggnn_lstm_epilogue_batch.restype = c_int
     lib.ggnn_lstm_epilogue_batch.argtypes = [POINTER(EpilogueArgs), c_int, c_void_p]
     lib.ggnn_heads_regressor.restype = c_int

@@ -547,7 +547,7 @@ class HipBackend:
 
     def aggregate_backward(self, csr, rcsr, r_slot, einfo, p_src, p_dst, h_src, ep, agg, g_agg,
                            v_off, u_off, u4_off, a_off, a_gstride, sc_off, n_gates, out_p_dst=None, out_p_src=None,
-                           ep_partial_out=None, g_h_into=None):
+                           ep_partial_out=None, g_h_into=None, inputs=None):
         """ggnn_period_gat_aggregate_backward (include/ggnn.h).  `rcsr`: CSR of the flipped
         edge_index (grouped by source), `r_slot` [E] int32: forward CSR slot of every reverse slot.
         Returns (g_p_dst, g_p_src, g_h_src or None, g_ep [n_gates, 3, 96]); the gradient tensors
@@ -555,7 +555,11 @@ class HipBackend:
         `ep_partial_out` [>= aggregate_bwd_partials(n_dst), n_gates, 3, 96]: the per-workgroup partial sums of g_ep go
         there and g_ep is returned as None -- the caller sums them (one reduction for the sweeps of a cell).
         `g_h_into` [n_src, 96]: an earlier sweep's g_h_src of the same source node type -- this sweep ADDS its own to it in
-        place (g_h_accumulate) and returns it."""
+        place (g_h_accumulate) and returns it.
+        `inputs` = (f_src, g_x_src [n_src, >= f_src], g_x_dst [n_dst, >= 3], g_edge_attr [edges of the list], src_accumulate,
+        dst_accumulate): the input gradients of ggnn_period_gat_aggregate_backward_inputs go into these float32 buffers
+        (columns 0..f_src-1 of the source rows, 0..2 of the destination rows, every kept edge's attribute; the flags add to
+        what the rows hold).  None: the entry point and the kernels without them."""
         _require_cuda(csr.rowptr, rcsr.rowptr, r_slot, einfo, p_src, p_dst, h_src, ep, agg, g_agg)
         dev = p_src.device
         E, G = csr.E, n_gates
@@ -599,6 +603,26 @@ class HipBackend:
         a.n_src, a.n_dst, a.E, a.n_partials = p_src.size(0), p_dst.size(0), E, n_part
         a.v_off, a.u_off, a.u4_off, a.a_off, a.a_gstride, a.sc_off, a.n_gates = (
             v_off, u_off, u4_off, a_off, a_gstride, sc_off, n_gates)
+        if inputs is not None:
+            f_src, g_x_src, g_x_dst, g_ea, acc_s, acc_d = inputs
+            _require_cuda(g_x_src, g_x_dst, g_ea, csr.perm)
+            for t, rows, cols, name in ((g_x_src, p_src.size(0), f_src, "g_x_src"), (g_x_dst, p_dst.size(0), 3, "g_x_dst")):
+                if t.dtype != torch.float32 or t.dim() != 2 or t.stride(1) != 1 or t.size(0) != rows or t.size(1) < cols:
+                    raise _lib.GGNNError(f"aggregate_backward: {name} must be float32 [{rows}, >= {cols}] with unit column stride")
+            if g_ea.dtype != torch.float32 or not g_ea.is_contiguous() or g_ea.numel() < E:
+                raise _lib.GGNNError("aggregate_backward: g_edge_attr must be a contiguous float32 tensor over the list's edges")
+            if E and int(csr.perm.numel()) < E:
+                raise _lib.GGNNError("aggregate_backward: the CSR's perm does not cover its slots")
+            x = _lib.AggregateBwdInputs()
+            edge_grad = torch.empty(max(E, 1), 16, **f32)
+            x.perm, x.edge_grad = csr.perm.data_ptr(), edge_grad.data_ptr()
+            ea_out = g_ea if g_ea.numel() else torch.empty(1, **f32)   # (a list without edges: nothing is written)
+            x.g_x_src, x.g_x_dst, x.g_edge_attr = g_x_src.data_ptr(), g_x_dst.data_ptr(), ea_out.data_ptr()
+            x.ldgx_src, x.ldgx_dst, x.f_src = g_x_src.stride(0), g_x_dst.stride(0), f_src
+            x.g_x_src_accumulate, x.g_x_dst_accumulate = int(bool(acc_s)), int(bool(acc_d))
+            self._launch(self.lib.ggnn_period_gat_aggregate_backward_inputs, "ggnn_period_gat_aggregate_backward_inputs",
+                         ctypes.byref(a), ctypes.byref(x), _lib.current_stream())
+            return g_p_dst, g_p_src, g_h_src, (ep_partial.sum(0) if ep_partial_out is None else None)
         self._launch(self.lib.ggnn_period_gat_aggregate_backward, "ggnn_period_gat_aggregate_backward", ctypes.byref(a),
                      _lib.current_stream())
         return g_p_dst, g_p_src, g_h_src, (ep_partial.sum(0) if ep_partial_out is None else None)
@@ -797,7 +821,7 @@ class HipBackend:
                 W[b] = w[b][:, :n_out]^T -- a gradient uses the transpose of the forward's weight), or 2-D for batch 1;
         `out` : [M, ldc] / [batch, M, ldc] float32 view with unit column stride: its first n_out columns are written
                 (returned as given: a [M, n] result must not come back as [1, M, n] -- autograd would sum_to_size it);
-        `c_in`: optional, same layout as out (may be out itself);
+        `c_in`: optional, same layout as out (another tensor: a ragged last row tile is produced twice, after its first store);
         `planes`: the weight planes of exactly this (w, K, n_out, batch, transposed, bf16) from `rowgemm_pack`."""
         g, _ = self._rowgemm_args(a, w, out, K, n_out, batch, c_in, transposed, bf16, planes)
         self._launch(self.lib.ggnn_rowgemm, "ggnn_rowgemm", ctypes.byref(g), _lib.current_stream())

@@ -23,6 +23,9 @@
 //   src pass  one wave per source row over the REVERSE (source-grouped) CSR: gathers the
 //             destination rows' g_out / u_h and the edge records, writes dV_j and dh_j.
 // Round 3: both passes take the edges in units of three with all loads of a unit in flight together.
+// Input gradients (ggnn_period_gat_aggregate_backward_inputs): a compile-time variant of the dst pass also
+// writes the gradient of every edge record and the destination rows' coordinates; a third launch gathers the records
+// to the source rows.  Without them the two passes are the kernels they were.
 #include "common.h"
 
 namespace ggnn {
@@ -61,8 +64,17 @@ __device__ __forceinline__ void st6(float* p, const float (&v)[6]) {
 // row of degree <= 3 -- every junction -- costs two memory round trips (hidden rows + tails, then values + records)
 // instead of six; the scores of such a row stay in registers between the two halves.  Rows of higher degree run the
 // same unit code twice (online max / sum, then the gradients).  Arithmetic and summation order of the first version.
-template <int G, bool HAS_H>
-__global__ __launch_bounds__(256) void aggregate_bwd_dst_kernel(const ggnn_aggregate_bwd_args A) {
+//
+// XG (input gradients): the pass also forms the gradient of every edge record -- 16 floats per CSR slot in the
+// u4 / x4 lane layout: g_x4[p, k] = sum_g ds u4[k], with g_r[p, 0..2] = sum_g sum_c alpha g_out [val > 0] W3[k, c] folded
+// into columns 0..2 and the direct attribute term sum_g alpha g_sae into column 13 -- summed over the wave's gate rows
+// with the source pass's shuffles, written by gate row 0 (one 64-byte store per edge) and, column 13, scattered to the
+// edge's place in the caller's attribute list through perm; minus the row's sum of columns 0..2 (the relocation is
+// x_src - x_dst + a piecewise constant shift) goes to the destination's coordinates once per row.  XG = false compiles
+// to the pass as it was.
+template <int G, bool HAS_H, bool XG>
+__global__ __launch_bounds__(256) void aggregate_bwd_dst_kernel(const ggnn_aggregate_bwd_args A,
+                                                                const ggnn_aggregate_bwd_inputs X) {
   const BwdLane L = bwd_lane<G>();
   const int64_t w = (int64_t)blockIdx.x * AB_WAVES + L.wave, n_w = (int64_t)gridDim.x * AB_WAVES;
   constexpr int U = GGNN_UNIT_EDGES;
@@ -130,8 +142,10 @@ __global__ __launch_bounds__(256) void aggregate_bwd_dst_kernel(const ggnn_aggre
     const float S = row_sum(dot) + gden * oden + gsae * osae;
     // ---- gradients, unit by unit (a single unit still has its hidden rows, tails and scores in registers) ----
     float du4 = 0.f, duh[6] = {};
+    [[maybe_unused]] float gxd = 0.f;   // XG: minus the row's sum of the relocation gradient (lanes 0..2)
     for (int p0 = beg; p0 < end; p0 += U) {
       float v[U][6], rec[U][4];
+      [[maybe_unused]] int pe[U];
       if (!one_unit) load_scores(p0);
 #pragma unroll
       for (int t = 0; t < U; ++t) {
@@ -139,6 +153,7 @@ __global__ __launch_bounds__(256) void aggregate_bwd_dst_kernel(const ggnn_aggre
         const float* r = A.einfo + (int64_t)p * GGNN_EINFO_ROW + 16;
         rec[t][0] = r[0], rec[t][1] = r[1], rec[t][2] = r[2], rec[t][3] = r[3];
         ld6(vsrc + jj[t] * A.ldp_src, v[t]);
+        if constexpr (XG) pe[t] = A.E > 0 ? X.perm[p] : 0;
       }
       if (!one_unit) {   // (scores again, without touching the softmax state)
 #pragma unroll
@@ -177,6 +192,30 @@ __global__ __launch_bounds__(256) void aggregate_bwd_dst_kernel(const ggnn_aggre
           A.edge_alpha[(int64_t)p * G + L.g] = alpha;
           A.edge_ds[(int64_t)p * G + L.g] = ds;
         }
+        if constexpr (XG) {
+          float gr0 = 0.f, gr1 = 0.f, gr2 = 0.f;
+#pragma unroll
+          for (int c = 0; c < 6; ++c) {
+            const float tt = alpha * gv[c];
+            gr0 += tt * wv[c][0], gr1 += tt * wv[c][1], gr2 += tt * wv[c][2];
+          }
+          gr0 = row_sum(gr0), gr1 = row_sum(gr1), gr2 = row_sum(gr2);
+          // (a gate row beyond G has u4 = g_out = g_sae = 0: it adds nothing)
+          float e = ds * u4 + (L.l16 == 0 ? gr0 : L.l16 == 1 ? gr1 : L.l16 == 2 ? gr2 : L.l16 == 13 ? alpha * gsae : 0.f);
+          e += __shfl_xor(e, 16, 64);
+          e += __shfl_xor(e, 32, 64);
+          if (live && L.g == 0) {
+            X.edge_grad[(int64_t)p * 16 + L.l16] = e;
+            if (L.l16 == 13) X.g_edge_attr[pe[t]] = e;
+          }
+          gxd -= e;   // (a slot behind the row's end has alpha = ds = 0)
+        }
+      }
+    }
+    if constexpr (XG) {
+      if (L.g == 0 && L.l16 < 3) {
+        float* o = X.g_x_dst + i * X.ldgx_dst + L.l16;
+        *o = X.g_x_dst_accumulate ? *o + gxd : gxd;
       }
     }
     if (L.active) {
@@ -275,6 +314,38 @@ __global__ __launch_bounds__(256) void aggregate_bwd_src_kernel(const ggnn_aggre
   }
 }
 
+// Source pass of the input gradients, a launch of its own so that the pass above stays the code it was (a
+// template variant of it re-associated the value gradient by an ulp): the records the destination pass wrote are gathered
+// over the REVERSE CSR through r_slot -- 16 lanes per source row, four rows per wave, the out-edges in units of three with
+// the unit's slot loads and then its record loads in flight together -- and summed in reverse-CSR order into columns
+// 0..f_src-1 of the source row (+1 on the coordinates, the features as they stand in x4).  No cross-lane operation: the
+// four rows of a wave may have different degrees.
+__global__ __launch_bounds__(256) void aggregate_bwd_src_inputs_kernel(const ggnn_aggregate_bwd_args A,
+                                                                       const ggnn_aggregate_bwd_inputs X) {
+  constexpr int U = GGNN_UNIT_EDGES;
+  const int l16 = threadIdx.x & 15;
+  const int64_t r0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) >> 4, n_r = (int64_t)gridDim.x * 16;
+  const int e_last = (int)max(A.E - 1, (int64_t)0);
+  for (int64_t j = r0; j < A.n_src; j += n_r) {
+    const int beg = A.r_rowptr[j], end = A.r_rowptr[j + 1];
+    float* o = X.g_x_src + j * X.ldgx_src + l16;
+    const bool own = l16 < X.f_src;
+    float gx = (X.g_x_src_accumulate && own) ? *o : 0.f;
+    float sum = 0.f;
+    for (int q0 = beg; q0 < end; q0 += U) {
+      int64_t pp[U];
+      float ge[U];
+#pragma unroll
+      for (int t = 0; t < U; ++t) pp[t] = A.E > 0 ? (int64_t)A.r_slot[min(q0 + t, e_last)] : 0;
+#pragma unroll
+      for (int t = 0; t < U; ++t) ge[t] = X.edge_grad[pp[t] * 16 + l16];
+#pragma unroll
+      for (int t = 0; t < U; ++t) sum += q0 + t < end ? ge[t] : 0.f;
+    }
+    if (own) *o = gx + sum;
+  }
+}
+
 }  // namespace ggnn
 
 // = workgroups of the destination pass: three per compute unit (the pass is a chain of dependent gathers per row and
@@ -284,10 +355,19 @@ extern "C" int64_t ggnn_aggregate_bwd_partials(int64_t n_dst) {
   return want < 768 ? (want > 0 ? want : 1) : 768;
 }
 
-extern "C" int ggnn_period_gat_aggregate_backward(const ggnn_aggregate_bwd_args* args, ggnn_stream_t stream) {
+// ext == nullptr: the sweep's backward as it was (the XG = false kernels)
+static int aggregate_backward_launch(const ggnn_aggregate_bwd_args* args, const ggnn_aggregate_bwd_inputs* ext,
+                                     ggnn_stream_t stream) {
   using namespace ggnn;
   if (!args) return GGNN_EINVAL;
   ggnn_aggregate_bwd_args A = *args;
+  ggnn_aggregate_bwd_inputs X = {};
+  if (ext) {
+    X = *ext;
+    if (!X.edge_grad || !X.g_x_src || !X.g_x_dst || !X.g_edge_attr || (A.E > 0 && !X.perm)) return GGNN_EINVAL;
+    if (X.f_src < 3 || X.f_src > 12 || X.ldgx_src < X.f_src || X.ldgx_dst < 3) return GGNN_EINVAL;
+    if ((X.g_x_src_accumulate | X.g_x_dst_accumulate) & ~1) return GGNN_EINVAL;
+  }
   if (!A.rowptr || !A.einfo || !A.p_src || !A.p_dst || !A.edge_params || !A.agg || !A.g_agg || !A.r_rowptr ||
       !A.edge_alpha || !A.edge_ds || !A.ep_partial || !A.g_p_dst || !A.g_p_src)
     return GGNN_EINVAL;
@@ -314,19 +394,36 @@ extern "C" int ggnn_period_gat_aggregate_backward(const ggnn_aggregate_bwd_args*
   const dim3 grid_d((unsigned)A.n_partials);
   const int64_t want_s = (A.n_src + AB_WAVES - 1) / AB_WAVES;
   const dim3 grid_s((unsigned)(want_s < 2048 ? want_s : 2048));
+#define GGNN_AB_LAUNCH2(G_, H_, X_)                                                                 \
+  do {                                                                                              \
+    hipLaunchKernelGGL((aggregate_bwd_dst_kernel<G_, H_, X_>), grid_d, dim3(256), 0, s, A, X);      \
+    hipLaunchKernelGGL((aggregate_bwd_src_kernel<G_, H_>), grid_s, dim3(256), 0, s, A);             \
+  } while (0)
 #define GGNN_AB_LAUNCH(G_)                                                                          \
   do {                                                                                              \
-    if (has_h) {                                                                                    \
-      hipLaunchKernelGGL((aggregate_bwd_dst_kernel<G_, true>), grid_d, dim3(256), 0, s, A);         \
-      hipLaunchKernelGGL((aggregate_bwd_src_kernel<G_, true>), grid_s, dim3(256), 0, s, A);         \
-    } else {                                                                                        \
-      hipLaunchKernelGGL((aggregate_bwd_dst_kernel<G_, false>), grid_d, dim3(256), 0, s, A);        \
-      hipLaunchKernelGGL((aggregate_bwd_src_kernel<G_, false>), grid_s, dim3(256), 0, s, A);        \
-    }                                                                                               \
+    if (has_h && ext) GGNN_AB_LAUNCH2(G_, true, true);                                              \
+    else if (has_h) GGNN_AB_LAUNCH2(G_, true, false);                                               \
+    else if (ext) GGNN_AB_LAUNCH2(G_, false, true);                                                 \
+    else GGNN_AB_LAUNCH2(G_, false, false);                                                         \
   } while (0)
   if (G == 4) GGNN_AB_LAUNCH(4);
   else if (G == 3) GGNN_AB_LAUNCH(3);
   else GGNN_AB_LAUNCH(1);
 #undef GGNN_AB_LAUNCH
+#undef GGNN_AB_LAUNCH2
+  if (ext) {
+    const int64_t want_x = (A.n_src + 15) / 16;
+    hipLaunchKernelGGL(aggregate_bwd_src_inputs_kernel, dim3((unsigned)(want_x < 2048 ? want_x : 2048)), dim3(256), 0, s, A, X);
+  }
   return launch_status();
+}
+
+extern "C" int ggnn_period_gat_aggregate_backward(const ggnn_aggregate_bwd_args* args, ggnn_stream_t stream) {
+  return aggregate_backward_launch(args, nullptr, stream);
+}
+
+extern "C" int ggnn_period_gat_aggregate_backward_inputs(const ggnn_aggregate_bwd_args* args,
+                                                         const ggnn_aggregate_bwd_inputs* inputs, ggnn_stream_t stream) {
+  if (!inputs) return GGNN_EINVAL;
+  return aggregate_backward_launch(args, inputs, stream);
 }

@@ -118,7 +118,7 @@ class GrainNN_regressor(_GrainNNBase):
     def forward(self, x_dict, edge_index_dict, edge_attr):
         """Inference (no autograd recording, or `.eval()`): the fused HIP path.  Inside a training
         loop (train.py:158-166) the differentiable path of `training.py`."""
-        if training.wants_autograd(self, x_dict):
+        if training.wants_autograd(self, x_dict, edge_attr):
             return training.regressor_forward(self, x_dict, edge_index_dict, edge_attr)
         return self._forward_inference(x_dict, edge_index_dict, edge_attr)
 
@@ -173,7 +173,7 @@ class GrainNN_classifier(_GrainNNBase):
         self._live_out = ("joint",)
 
     def forward(self, x_dict, edge_index_dict, edge_attr):
-        if training.wants_autograd(self, x_dict):
+        if training.wants_autograd(self, x_dict, edge_attr):
             return training.classifier_forward(self, x_dict, edge_index_dict, edge_attr)
         return self._forward_inference(x_dict, edge_index_dict, edge_attr)
 

@@ -19,6 +19,11 @@ and the module is in training mode, i.e. inside the reference's loop (train.py:1
     node-level backward: segment sums over the forward / reverse CSR in a fixed order, [n, 6] products; layer_size < 96:
     `_RowLinear` on the recorded pair matrix).
 
+The inputs are differentiable as well: a tensor of x_dict or edge_attr that requires grad sends the forward here
+in `.train()` and in `.eval()` (`wants_autograd`), and the backward fills its .grad -- the sweeps' backward with the edge
+records' gradient (`ggnn_period_gat_aggregate_backward_inputs`), a narrow `ggnn_rowgemm` for the projection's input columns,
+the heads' direct terms.  `unrolled_steps` differentiates a loss over K consecutive regressor steps.
+
 Under `torch.autocast(bfloat16)` (BASELINE config 5) the cells' dense products -- the decoder projection, the gate
 GEMM, its input gradient, the hidden-state gradient -- run in real bf16 arithmetic on the HIP kernels (operands rounded
 to bf16, ONE MFMA product per k-step instead of three or six, fp32 accumulate: GGNN_PRECISION_BF16), as do the recorded
@@ -145,12 +150,17 @@ class _PackedCell(torch.autograd.Function):
 
     Inputs (x_g, x_j, h_g, h_j, c_g, c_j, wp_g, wp_j, bp_g, bp_j, ep x 3, w2_g, w2_j) with the packed matrices as
     train_pack.packed_weights lays them out (wp [ncols, Fp + k2], w2 [G, 96, Kg]); h / c None = zero state
-    (encoder, 3 gates).  x carries no gradient (data).  `bf16`: the caller ran under bf16 autocast."""
+    (encoder, 3 gates).  `bf16`: the caller ran under bf16 autocast.  `ea_*`: the three edge attributes [E] the edge
+    records were made from -- not read by the forward (einfo holds them), they are the inputs whose gradient the backward
+    returns.  Input gradients (x_g, x_j, ea_*) are formed only when ctx.needs_input_grad asks for one of them:
+    the sweeps' backward then runs as ggnn_period_gat_aggregate_backward_inputs (the edge records' gradient routed to the
+    source / destination rows and through perm to the attributes) and one narrow ggnn_rowgemm per node type adds the dense
+    part gP Wp[:, :F]; otherwise the backward is launch for launch what it was."""
 
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, x_g, x_j, h_g, h_j, c_g, c_j, wp_g, wp_j, bp_g, bp_j, ep_gj, ep_jg, ep_jj, w2_g, w2_j,
-                backend, topo, einfo, layout, G, bf16=False, xs=None):
+                backend, topo, einfo, layout, G, bf16=False, xs=None, ea_gj=None, ea_jg=None, ea_jj=None):
         x = {"grain": x_g.contiguous(), "joint": x_j.contiguous()}
         sees_h = h_g is not None
         h = {"grain": h_g.contiguous() if sees_h else None, "joint": h_j.contiguous() if sees_h else None}
@@ -279,6 +289,20 @@ class _PackedCell(torch.autograd.Function):
             backend.rowgemm(g_z[nt], w2[nt], g_agg[nt].view(n, G, lay.Kg).transpose(0, 1), C, lay.Kg, batch=G,
                             transposed=True, bf16=bf16, planes=planes[k])                      # g_agg_g = g_z_g W2_g
         gh_src = {nt: None for nt in NODE_TYPES}
+        # input gradients: [n, 16] accumulators per node type (the sweeps add columns 0..F-1, the dense part
+        # goes on top), one attribute gradient per edge type
+        nig = tuple(ctx.needs_input_grad) + (False,) * 3   # (a caller that passed no edge attributes)
+        want_x = any(nig[k] for k in (0, 1, 22, 23, 24))
+        gx, g_ea = {nt: None for nt in NODE_TYPES}, {et: None for et in EDGE_TYPES}
+        if want_x:
+            # (views of ONE zero-filled buffer, every view 16-byte aligned: one fill instead of five)
+            sizes = [x[nt].size(0) * 16 for nt in NODE_TYPES] + [topo.graph.edge_index[et].size(1) for et in EDGE_TYPES]
+            offs = [0]
+            for n in sizes:
+                offs.append(offs[-1] + (n + 3) // 4 * 4)
+            flat = torch.zeros(offs[-1], **f32)
+            gx = {nt: flat[offs[k]:offs[k] + sizes[k]].view(-1, 16) for k, nt in enumerate(NODE_TYPES)}
+            g_ea = {et: flat[offs[2 + k]:offs[2 + k] + sizes[2 + k]] for k, et in enumerate(EDGE_TYPES)}
         # the per-workgroup partial sums of the three sweeps' edge-parameter gradients side by side: one reduction
         n_part = [backend.aggregate_bwd_partials(x[et[-1]].size(0)) for et in EDGE_TYPES]
         ep_part = (torch.empty if len(set(n_part)) == 1 else torch.zeros)(len(EDGE_TYPES), max(n_part), G, 3, C, **f32)
@@ -288,7 +312,8 @@ class _PackedCell(torch.autograd.Function):
                 topo.graph.csr[et], topo.rcsr[et], topo.r_slot[et], einfo[et], P[s], P[d], h[s], ep[et], agg[d],
                 g_agg[d], layout[s].v_off[et], layout[d].u_off.get(et, 0), layout[d].u4_off[et], layout[d].a_off[et],
                 layout[d].Kg, layout[d].sc_off[et], G, out_p_dst=gP[d], out_p_src=gP[s], ep_partial_out=ep_part[k],
-                g_h_into=gh_src[s])   # (the second sweep out of a node type adds to the first one's rows in place)
+                g_h_into=gh_src[s],   # (the second sweep out of a node type adds to the first one's rows in place)
+                **({"inputs": (layout[s].F, gx[s], gx[d], g_ea[et], True, True)} if want_x else {}))
             if g_h is not None:
                 gh_src[s] = g_h
         g_wp, g_bp, g_h, g_ep = {}, {}, {}, {}
@@ -324,19 +349,34 @@ class _PackedCell(torch.autograd.Function):
                     beside(hidden_state_gradient, "h")
                 else:
                     hidden_state_gradient()
+        if want_x:
+            # the dense part g_x += gP Wp[:, :F] (query-side u4 columns, value columns -- their coordinate columns are zero in
+            # Wp --, skip): a 16-wide ggnn_rowgemm on top of the sweeps' sums; under bf16 autocast it follows the hidden-state
+            # product (the decoder's), the encoder's stays fp32 like its projection
+            for nt in NODE_TYPES:
+                lay = layout[nt]
+                wx = torch.nn.functional.pad(wp[nt][:, :lay.F], (0, 16 - lay.F))                 # [ncols, 16]
+                # (a fresh output: a ragged last row tile is produced twice, so the product cannot add to c_in in place)
+                gx[nt] = backend.rowgemm(gP[nt], wx, torch.empty_like(gx[nt]), lay.ncols, 16, c_in=gx[nt], transposed=True,
+                                         bf16=bf16 and sees_h)
+            # (column views: autograd adds the two cells' and the heads' parts into a tensor of x's layout itself)
+            gx = {nt: gx[nt][:, :layout[nt].F] if nig[k] else None for k, nt in enumerate(NODE_TYPES)}
+            g_ea = {et: g_ea[et] if nig[22 + k] else None for k, et in enumerate(EDGE_TYPES)}
         if side is not None:
             main.wait_stream(side)
         if red:
             backend.sum_rows_batch(red)
-        return (None, None, g_h["grain"], g_h["joint"], g_c["grain"], g_c["joint"], g_wp["grain"], g_wp["joint"],
+        return (gx["grain"], gx["joint"], g_h["grain"], g_h["joint"], g_c["grain"], g_c["joint"], g_wp["grain"], g_wp["joint"],
                 g_bp["grain"], g_bp["joint"], g_ep[EDGE_TYPES[0]], g_ep[EDGE_TYPES[1]], g_ep[EDGE_TYPES[2]],
-                g_w2["grain"], g_w2["joint"], None, None, None, None, None, None, None)
+                g_w2["grain"], g_w2["joint"], None, None, None, None, None, None, None,
+                g_ea[EDGE_TYPES[0]], g_ea[EDGE_TYPES[1]], g_ea[EDGE_TYPES[2]])
 
 
-def cell_forward(cell, backend, topo, einfo, x, h, c, xs=None, packed=None):
+def cell_forward(cell, backend, topo, einfo, x, h, c, xs=None, packed=None, ea=None):
     """HeteroPGCLSTM.forward (heteropgclstm.py:101-183), differentiable, in the packed formulation: the packed
     weights are assembled from the parameters by recorded torch ops, the cell itself is _PackedCell.
     h, c: dicts or None (encoder: zero state; the forget gate multiplies c = 0 and is skipped).
+    ea: {edge type: [E] edge attribute} when input gradients are wanted (see _PackedCell), else None.
     (Measured and dropped, round 4: the decoder's packed weights assembled on a side stream beside the encoder cell -- a
     replayed hipGraph ran the two branches one after the other, with launch gaps between their small kernels.)"""
     gates = "ifco" if h is not None else "ico"
@@ -349,7 +389,7 @@ def cell_forward(cell, backend, topo, einfo, x, h, c, xs=None, packed=None):
         x["grain"], x["joint"], None if h is None else h["grain"], None if h is None else h["joint"],
         None if c is None else c["grain"], None if c is None else c["joint"], wp["grain"], wp["joint"], bp["grain"],
         bp["joint"], ep[EDGE_TYPES[0]], ep[EDGE_TYPES[1]], ep[EDGE_TYPES[2]], w2["grain"], w2["joint"], backend, topo,
-        einfo, layout, G, bf16, xs)
+        einfo, layout, G, bf16, xs, *([ea[et] for et in EDGE_TYPES] if ea is not None else []))
     return {"grain": hg, "joint": hj}, {"grain": cg, "joint": cj}
 
 
@@ -374,8 +414,14 @@ def encoder_decoder(model, x_dict, edge_index_dict, edge_attr):
     # both cells' packed weights by one autograd function: its launches (three forward, four backward) are shared
     with torch.autocast(x["joint"].device.type, enabled=False):   # weight-sized products stay fp32
         pk_enc, pk_dec = packed_weights_of([(enc, "ico", enc.in_channels_dict, False), (dec, "ifco", dec.in_channels_dict, True)])
-    h, c = cell_forward(enc, be, topo, einfo, x, None, None, xs, pk_enc)
-    h, c = cell_forward(dec, be, topo, einfo, x, h, c, xs, pk_dec)
+    # inputs that require grad go into the cells as they are (the edge records stay a no-grad launch: their backward is the
+    # scatter of ggnn_period_gat_aggregate_backward_inputs); everything else is data
+    xin = {nt: x_dict[nt] if x_dict[nt].requires_grad else x[nt] for nt in NODE_TYPES}
+    ea = None
+    if any(x_dict[nt].requires_grad for nt in NODE_TYPES) or any(edge_attr[et].requires_grad for et in EDGE_TYPES):
+        ea = {et: _edge_attr_1d(edge_attr[et]) for et in EDGE_TYPES}
+    h, c = cell_forward(enc, be, topo, einfo, xin, None, None, xs, pk_enc, ea)
+    h, c = cell_forward(dec, be, topo, einfo, xin, h, c, xs, pk_dec, ea)
     return h, graph
 
 
@@ -425,7 +471,7 @@ class _RegressorHeads(torch.autograd.Function):
         y_joint, y_grain, area = torch.empty(nj, 2, **f32), torch.empty(ng, 2, **f32), torch.empty(ng, **f32)
         backend.heads_regressor(h_joint, h_grain, x_grain, w, b, y_joint, y_grain, area)
         ctx.save_for_backward(h_joint, h_grain, w, y_joint, y_grain)
-        ctx.backend = backend
+        ctx.backend, ctx.x_shape = backend, x_grain.shape
         ctx.set_materialize_grads(False)
         return y_joint, y_grain, area
 
@@ -449,14 +495,19 @@ class _RegressorHeads(torch.autograd.Function):
         # adopted as .grad without a copy, where four strided slices cost four copies
         flat = torch.cat(rows)
         n = 2 * wd + 2
-        return ghj, ghg, None, flat[:2 * wd].view(2, wd), flat[2 * wd:n], flat[n:n + 2 * wd].view(2, wd), flat[n + 2 * wd:], None
+        g_x = None
+        if ctx.needs_input_grad[2] and g_area is not None:   # grain_area = tanh(.) / scaling + x_grain[:, 3]
+            g_x = torch.zeros(ctx.x_shape, dtype=torch.float32, device=h_grain.device)
+            g_x[:, 3] = g_area
+        return ghj, ghg, g_x, flat[:2 * wd].view(2, wd), flat[2 * wd:n], flat[n:n + 2 * wd].view(2, wd), flat[n + 2 * wd:], None
 
 
 def regressor_forward(model, x_dict, edge_index_dict, edge_attr):
     """GrainNN_regressor.forward (models.py:401-467) with autograd."""
     h, _ = encoder_decoder(model, x_dict, edge_index_dict, edge_attr)
     lin = model.linear
-    y_joint, y_grain, area = _RegressorHeads.apply(h["joint"], h["grain"], x_dict["grain"].detach().contiguous(),
+    xg = x_dict["grain"] if x_dict["grain"].requires_grad else x_dict["grain"].detach()
+    y_joint, y_grain, area = _RegressorHeads.apply(h["joint"], h["grain"], xg.contiguous(),
                                                    lin["joint"].weight, lin["joint"].bias, lin["grain"].weight,
                                                    lin["grain"].bias, default_backend())
     return {"grain": y_grain, "joint": y_joint, "grain_area": area}
@@ -474,6 +525,7 @@ class _ClassifierHeads(torch.autograd.Function):
     @staticmethod
     @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, h, ea, W, b, backend, topo):
+        ctx.ea_shape = ea.shape
         h, ea = h.contiguous(), ea.contiguous().view(-1)
         et = ("joint", "connect", "joint")
         ei = topo.graph.edge_index[et]
@@ -483,7 +535,7 @@ class _ClassifierHeads(torch.autograd.Function):
         f32 = dict(dtype=torch.float32, device=h.device)
         node_tmp, edge_event, edge = torch.empty(n, 8, **f32), torch.empty(E, **f32), torch.empty(E, 2, **f32)
         backend.heads_classifier(h, ei, ea, w_node, w_edge, node_tmp, edge_event, edge)
-        ctx.save_for_backward(h, ea, w_node, edge)
+        ctx.save_for_backward(h, ea, w_node, edge, w_edge)
         ctx.misc = (backend, topo)
         ctx.set_materialize_grads(False)
         return edge, edge_event
@@ -492,7 +544,7 @@ class _ClassifierHeads(torch.autograd.Function):
     @once_differentiable
     @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, g_edge, g_event):
-        h, ea, w_node, edge = ctx.saved_tensors
+        h, ea, w_node, edge, w_edge = ctx.saved_tensors
         backend, topo = ctx.misc
         et = ("joint", "connect", "joint")
         n, E = h.size(0), edge.size(0)
@@ -509,7 +561,10 @@ class _ClassifierHeads(torch.autograd.Function):
         g_h = g_tmp[:, :6] @ w_node
         g_w_node = backend.wgrad(g_tmp, h, n, 8, C, 8, C)[0][:6]              # [6, 96]
         g_W = torch.cat([g_w_node[:3], g_w_node[3:], (g_pre[:, :3] * ea.unsqueeze(1)).sum(0).unsqueeze(1)], 1)   # [3, 193]
-        return g_h, None, g_W, g_pre[:, :3].sum(0), None, None
+        g_ea = None
+        if ctx.needs_input_grad[1]:   # the pair's last column is the edge attribute: g_pre[:, :3] . W[:, 2 * 96]
+            g_ea = (g_pre[:, :3] * w_edge[:3]).sum(1).view(ctx.ea_shape)
+        return g_h, g_ea, g_W, g_pre[:, :3].sum(0), None, None
 
 
 def classifier_forward(model, x_dict, edge_index_dict, edge_attr):
@@ -761,18 +816,18 @@ class FusedAdam(torch.optim.Optimizer):
 _warned_eval_grad = False
 
 
-def wants_autograd(model, x_dict=None) -> bool:
-    """The differentiable path is taken in training mode with autograd recording (train.py:158-166).  In
-    `.eval()` mode the forward is the fused inference path and its outputs carry no grad_fn -- unlike the
-    reference, which is differentiable in either mode: asking for input gradients there is refused, and a
-    forward in eval mode with autograd recording warns once (wrap inference in torch.no_grad(), as test.py:240
-    does, or call model.train() to differentiate)."""
+def wants_autograd(model, x_dict=None, edge_attr=None) -> bool:
+    """The differentiable path is taken with autograd recording in training mode (train.py:158-166), and in either mode
+    when a tensor of x_dict or edge_attr requires grad: the reference is differentiable in `.train()` and in `.eval()`,
+    and a caller who marks an input asks for its gradient.  Under torch.no_grad() the forward is the fused
+    inference path.  In `.eval()` mode with recording and no input that requires grad it is the fused inference path too,
+    whose outputs carry no grad_fn: that warns once (wrap inference in torch.no_grad(), as test.py:240 does, or call
+    model.train() to differentiate)."""
     global _warned_eval_grad
     if not torch.is_grad_enabled():
         return False
-    if x_dict is not None and any(torch.is_tensor(v) and v.requires_grad for v in x_dict.values()):
-        raise NotImplementedError("gradients with respect to x_dict are not built (the reference's training "
-                                  "loop never asks for them, train.py:158-166): detach the inputs")
+    if any(torch.is_tensor(v) and v.requires_grad for d in (x_dict, edge_attr) if d is not None for v in d.values()):
+        return True
     if model.training:
         return any(p.requires_grad for p in model.parameters())
     if not _warned_eval_grad and any(p.requires_grad for p in model.parameters()):
@@ -782,6 +837,52 @@ def wants_autograd(model, x_dict=None) -> bool:
                       "inference path, whose outputs have no grad_fn; use torch.no_grad() for inference or "
                       "model.train() to differentiate", stacklevel=3)
     return False
+
+
+def edge_lengths(x_dict, edge_index_dict):
+    """test.py:562-575 as recorded ops: the min-image distance in the (x, y) plane between the end points of every edge,
+    {edge type: [E, 1]} -- the edge attribute of the next forward, differentiable in the node coordinates."""
+    out = {}
+    for et, index in edge_index_dict.items():
+        rel = x_dict[et[0]][index[0], :2] - x_dict[et[-1]][index[-1], :2]
+        rel = rel - (rel > 0.5).to(rel.dtype) + (rel < -0.5).to(rel.dtype)
+        out[et] = torch.sqrt(rel[:, 0] ** 2 + rel[:, 1] ** 2).view(-1, 1)
+    return out
+
+
+def unrolled_steps(rmodel, x_dict, edge_index_dict, n_steps, dz, z_max=None):
+    """`n_steps` consecutive regressor steps, out of place and differentiable end to end: the smallest consumer
+    of the input gradients -- a loss on step t reaches the parameters through every earlier step, and the inputs of step 0
+    (G and R are x_dict['joint'][:, 3:5]).  Static periodic topology, regressor only: no grain elimination, no neighbour
+    switching.  Per step:
+
+      * the edge lengths of the state (`edge_lengths`, test.py:562-575) and the forward `rmodel(x, edge_index_dict, ea)`;
+      * the non-melt branch of the reference's update (models.py:510-516) as recorded ops: junction (x, y) += dxy / scaling,
+        grain area += ds / scaling, grain excess volume = v, and the gradient features (joint 6:8, the grains' last column);
+      * z of both node types += dz, held at `z_max` once the first grain's z has passed it (test.py:401-407; default
+        1 - dz, i.e. train_frames / (train_frames + 1) for a span of one).
+
+    The grain centres (x_grain[:, :2]) are held fixed: their refresh is polygon geometry (test.py:556-559) and stays
+    outside the differentiated step.  Works with any model of the reference's call shape that has a `.scaling` dict --
+    the models of this package and the fp64 oracle alike.  Returns (predictions, states): the prediction dict of every
+    step and the state after it."""
+    z_max = 1.0 - dz if z_max is None else z_max
+    x = {nt: t for nt, t in x_dict.items()}
+    preds, states = [], []
+    for _ in range(n_steps):
+        pred = rmodel(x, edge_index_dict, edge_lengths(x, edge_index_dict))
+        dj, dg, dv = pred["joint"], pred["grain"][:, 0], pred["grain"][:, 1]
+        xj, xg = x["joint"], x["grain"]
+        zj, zg = xj[:, 2] + dz, xg[:, 2] + dz
+        over = zg[0] > z_max
+        zj, zg = torch.where(over, torch.full_like(zj, z_max), zj), torch.where(over, torch.full_like(zg, z_max), zg)
+        xj = torch.cat([xj[:, :2] + dj / rmodel.scaling["joint"], zj[:, None], xj[:, 3:6], dj, xj[:, 8:]], 1)
+        xg = torch.cat([xg[:, :2], zg[:, None], (xg[:, 3] + dg / rmodel.scaling["grain"])[:, None], dv[:, None], xg[:, 5:-1],
+                        dg[:, None]], 1)
+        x = {"joint": xj, "grain": xg}
+        preds.append(pred)
+        states.append(x)
+    return preds, states
 
 
 class GraphedTrainStep:

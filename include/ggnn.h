@@ -265,7 +265,8 @@ int ggnn_period_gat_aggregate_enc_batch(const ggnn_aggregate_enc_args* args, int
  *   g_p_src[j, v_off + g*96 ..]                                  (other columns untouched)
  *   g_h_src[j, 0..95]                                            (when h_src != NULL)
  *   ep_partial[w, g, k, c]: partial sums of d edge_params; the gradient is their sum over w.
- * The geometry (einfo) is data, not a parameter: no gradient.
+ * The geometry (einfo) carries no gradient through this entry point; ggnn_period_gat_aggregate_backward_inputs below
+ * adds the gradient of the edge records, i.e. of the node features and of the edge attribute they were made from.
  */
 typedef struct ggnn_aggregate_bwd_args {
   const int32_t* rowptr;   /* [n_dst + 1] destination-grouped CSR (ggnn_build_csr_batch) */
@@ -293,6 +294,34 @@ typedef struct ggnn_aggregate_bwd_args {
 } ggnn_aggregate_bwd_args;
 int64_t ggnn_aggregate_bwd_partials(int64_t n_dst); /* rows of ep_partial the call writes (one per workgroup of its destination pass) */
 int ggnn_period_gat_aggregate_backward(const ggnn_aggregate_bwd_args* args, ggnn_stream_t stream);
+
+/* The same backward with the gradients of the sweep's INPUTS: everything ggnn_period_gat_aggregate_backward
+ * writes, bit for bit, plus the gradient of the edge records einfo[p] = (x4 [16] | reloc [3] | a) mapped back through the
+ * record's column map (GGNN_EINFO_ROW above).  Per CSR slot p (edge j -> i), summed over the gates:
+ *   g_x4[p, k] = sum_g ds u4_i[k]                                     k = 0..15
+ *   g_r[p, k]  = sum_g sum_c alpha g_out_i[c] [val[c] > 0] W3_g[k, c]  k = 0..2
+ *   g_a[p]     = g_x4[p, 13] + sum_g alpha g_sae_i
+ * The min-image shift is piecewise constant, so with g_reloc = g_x4[p, 0..2] + g_r[p]:
+ *   g_x_src[j, 0..2] += g_reloc      g_x_dst[i, 0..2] -= g_reloc      g_x_src[j, 3..f_src-1] += g_x4[p, 3..f_src-1]
+ *   g_edge_attr[perm[p]] = g_a[p]    (perm is a permutation of the list's edges: every entry written once; entries of
+ *                                     edges a masked table leaves out are not written)
+ * Columns 12, 11 (f_src <= 11) and the padding of the record are constants.  Atomics-free and in a fixed order: the
+ * destination pass writes edge_grad and g_x_dst (one wave per row), a third launch gathers edge_grad over the reverse
+ * CSR (16 lanes per source row); the source pass is the one of ggnn_period_gat_aggregate_backward.  The *_accumulate
+ * flags add to what the buffer holds (a node type is the source and the destination of several sweeps of a cell: the
+ * calls of one stream are ordered); 0 writes columns 0..2 (dst) / 0..f_src-1 (src) of every row. */
+typedef struct ggnn_aggregate_bwd_inputs {
+  const int32_t* perm;   /* [E] edge id of every CSR slot in the caller's list (ggnn_build_csr_batch) */
+  float* edge_grad;      /* [max(E, 1), 16] scratch: gradient of the record's first 16 columns, g_r folded into 0..2, g_a at 13 */
+  float* g_x_src;        /* [n_src, ldgx_src] out */
+  float* g_x_dst;        /* [n_dst, ldgx_dst] out (may be g_x_src when the two node types are one) */
+  float* g_edge_attr;    /* [edges of the caller's list] out */
+  int64_t ldgx_src, ldgx_dst;
+  int32_t f_src;         /* 3 <= f_src <= 12, as ggnn_prepare_edge.f_src */
+  int32_t g_x_src_accumulate, g_x_dst_accumulate, reserved;
+} ggnn_aggregate_bwd_inputs;
+int ggnn_period_gat_aggregate_backward_inputs(const ggnn_aggregate_bwd_args* args, const ggnn_aggregate_bwd_inputs* inputs,
+                                              ggnn_stream_t stream);
 
 /* ------------------------------------------------------------------------------------
  * Gate GEMM + LSTM epilogue (arithmetic per ggnn_gemm_mode).  For every node and gate:
