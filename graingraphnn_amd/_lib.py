@@ -26,6 +26,7 @@ GGNN_OUT_BLOCK_MAJOR = 0x100
 GGNN_ETOPOLOGY = -3
 GGNN_FLAG_F16_RANGE = 1
 GGNN_FLAG_QOI_OVERFLOW = 2
+GGNN_FLAG_POLYGON_OVERFLOW = 4
 GGNN_ADAM_CHUNK, GGNN_ADAM_MAX_TENSORS, GGNN_ADAM_MAX_GROUPS = 4096, 384, 8
 GGNN_ROWGEMM_MAX_PACK = 8
 GGNN_MSE_MAX_TERMS, GGNN_MSE_BLOCKS = 4, 64
@@ -55,7 +56,7 @@ EXPORTED_SYMBOLS = (
     "ggnn_heads_classifier", "ggnn_step_update", "ggnn_grain_centres", "ggnn_detect_events", "ggnn_detect_events_traj", "ggnn_topology_update", "ggnn_topology_open", "ggnn_topology_apply",
     "ggnn_topology_counts", "ggnn_topology_export", "ggnn_topology_close", "ggnn_step_refresh",
     "ggnn_workspace_bytes",
-    "ggnn_qoi_accumulate", "ggnn_qoi_finalize", "ggnn_process_schedule",
+    "ggnn_qoi_accumulate", "ggnn_qoi_finalize", "ggnn_process_schedule", "ggnn_grain_polygons",
     "ggnn_metric_record",
     "ggnn_masked_mse_rows", "ggnn_collate_batch", "ggnn_reverse_slots",
 )
@@ -376,6 +377,19 @@ class QoiArgs(Structure):
     ]
 
 
+class PolygonArgs(Structure):
+    """Mirror of `ggnn_polygon_args`."""
+    _fields_ = [
+        ("rowptr", c_void_p), ("col", c_void_p), ("x_joint", c_void_p), ("domain_offset", c_void_p),
+        ("traj_grain_off", c_void_p), ("rowptr_out", c_void_p), ("joint_sorted", c_void_p), ("xy_sorted", c_void_p),
+        ("centre", c_void_p), ("area", c_void_p), ("layer_in", c_void_p), ("layer_out", c_void_p), ("sync_word", c_void_p),
+        ("flags", c_void_p),
+        ("n_joint", c_int64), ("ldx_joint", c_int64), ("n_grain", c_int64), ("E_cap", c_int64), ("n_traj", c_int64),
+        ("capacity", c_int64),
+        ("domain_factor", c_float), ("boundary", c_int32),
+    ]
+
+
 class MetricArgs(Structure):
     """Mirror of `ggnn_metric_args`."""
     _fields_ = [
@@ -522,6 +536,8 @@ def _declare(lib):
                                       c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]
     lib.ggnn_metric_record.restype = c_int
     lib.ggnn_metric_record.argtypes = [POINTER(MetricArgs), c_void_p]
+    lib.ggnn_grain_polygons.restype = c_int
+    lib.ggnn_grain_polygons.argtypes = [POINTER(PolygonArgs), c_void_p]
     lib.ggnn_process_schedule.restype = c_int
     lib.ggnn_process_schedule.argtypes = [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p]

@@ -1243,6 +1243,67 @@ class HipBackend:
         A.init = 1 if init else 0
         check(self.lib.ggnn_qoi_accumulate(ctypes.byref(A), _lib.current_stream()), "ggnn_qoi_accumulate")
 
+    def polygon_arena(self, n_grain, n_edges, capacity, device):
+        """The per-layer arrays ggnn_grain_polygons writes: `rowptr` int32 [capacity + 1, n_grain + 1], `joint_sorted` int32
+        [capacity + 1, E], `xy_sorted` fp32 [capacity + 1, E, 2], `centre` fp32 [capacity + 1, n_grain, 2], `area` fp32
+        [capacity + 1, n_grain].  Zeroed: what a shrunken table leaves unwritten behind its last entry reads as 0."""
+        L, i32, f32 = int(capacity) + 1, dict(dtype=torch.int32, device=device), dict(dtype=torch.float32, device=device)
+        return {"rowptr": torch.zeros(L, n_grain + 1, **i32), "joint_sorted": torch.zeros(L, n_edges, **i32),
+                "xy_sorted": torch.zeros(L, n_edges, 2, **f32), "centre": torch.zeros(L, n_grain, 2, **f32),
+                "area": torch.zeros(L, n_grain, **f32)}
+
+    def grain_polygons(self, csr_jg, x_joint, arena=None, domain_factor=1.0, domain_offset=None, boundary="periodic",
+                       traj_grain_off=None, layer_in=None, layer_out=None, sync_word=None, flags=None):
+        """One layer of the grains' junction polygons (include/ggnn.h, ggnn_grain_polygons), one launch; returns the arena.
+        csr_jg: the table grain_centres reads (the FULL one for boundary="noflux"); arena: a polygon_arena (None: one of a
+        single layer for this table, and the layer is written to its row 0); traj_grain_off: None or int64 [n_traj + 1] on
+        the device (noflux: every trajectory's first grain is reversed); layer_in / layer_out / sync_word / flags: int32
+        device words -- row *layer_in + 1 is written and left in *layer_out (layer_in None: row 0)."""
+        bc = _boundary_code(boundary)
+        n_grain = csr_jg.rowptr.numel() - 1
+        if arena is None:
+            arena = self.polygon_arena(n_grain, csr_jg.col.numel(), 0, x_joint.device)
+        _require_cuda(x_joint, csr_jg.rowptr, csr_jg.col, domain_offset, traj_grain_off, layer_in, layer_out, sync_word, flags,
+                      *arena.values())
+        L, E_cap = arena["joint_sorted"].shape
+        for name, dtype, shape in (("rowptr", torch.int32, (L, n_grain + 1)), ("joint_sorted", torch.int32, (L, E_cap)),
+                                   ("xy_sorted", torch.float32, (L, E_cap, 2)), ("centre", torch.float32, (L, n_grain, 2)),
+                                   ("area", torch.float32, (L, n_grain))):
+            t = arena[name]
+            if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+                raise _lib.GGNNError(f"arena[{name!r}] must be a contiguous {dtype} tensor of shape {shape}")
+        if L < 1 or n_grain < 1 or csr_jg.col.numel() < E_cap:
+            raise _lib.GGNNError("the arena has more entries per layer than the joint->grain table")
+        if csr_jg.rowptr.dtype != torch.int32 or csr_jg.col.dtype != torch.int32:
+            raise _lib.GGNNError("csr_jg must hold int32 tables")
+        if x_joint.dtype != torch.float32 or x_joint.dim() != 2 or x_joint.stride(1) != 1:
+            raise _lib.GGNNError("x_joint must be float32 [n_joint, >= 2] with unit column stride")
+        if domain_offset is not None:
+            _f32c(domain_offset, "domain_offset")
+            if tuple(domain_offset.shape) != (x_joint.size(0), 2):
+                raise _lib.GGNNError("domain_offset must be [n_joint, 2]")
+        elif domain_factor > 1:
+            raise _lib.GGNNError("domain_factor > 1 needs the domain_offset of scale_feature_patchs")
+        n_traj = 1
+        if traj_grain_off is not None:
+            if traj_grain_off.dtype != torch.int64 or traj_grain_off.numel() < 2 or not traj_grain_off.is_contiguous():
+                raise _lib.GGNNError("traj_grain_off must be a contiguous int64 [n_traj + 1]")
+            n_traj = traj_grain_off.numel() - 1
+        for w in (layer_in, layer_out, sync_word, flags):
+            if w is not None and (w.dtype != torch.int32 or w.numel() < 1):
+                raise _lib.GGNNError("layer_in / layer_out / sync_word / flags must be int32 words")
+        if layer_out is not None and (sync_word is None or flags is None):
+            raise _lib.GGNNError("layer_out needs sync_word and flags")
+        A = _lib.PolygonArgs()
+        A.rowptr, A.col, A.x_joint, A.domain_offset = ptr(csr_jg.rowptr), ptr(csr_jg.col), ptr(x_joint), ptr(domain_offset)
+        A.traj_grain_off, A.rowptr_out, A.joint_sorted = ptr(traj_grain_off), ptr(arena["rowptr"]), ptr(arena["joint_sorted"])
+        A.xy_sorted, A.centre, A.area = ptr(arena["xy_sorted"]), ptr(arena["centre"]), ptr(arena["area"])
+        A.layer_in, A.layer_out, A.sync_word, A.flags = ptr(layer_in), ptr(layer_out), ptr(sync_word), ptr(flags)
+        A.n_joint, A.ldx_joint, A.n_grain, A.E_cap = x_joint.size(0), x_joint.stride(0), n_grain, E_cap
+        A.n_traj, A.capacity, A.domain_factor, A.boundary = n_traj, L - 1, float(domain_factor), bc
+        check(self.lib.ggnn_grain_polygons(ctypes.byref(A), _lib.current_stream()), "ggnn_grain_polygons")
+        return arena
+
     def process_schedule(self, x_joint, table, traj_joint_off, step_in, step_out, sync_word):
         """The (G, R) features of the step to come from a device-side table (include/ggnn.h, ggnn_process_schedule), one
         launch: x_joint[:, 3:5] <- table[min(max(*step_in + 1, 0), n_rows - 1), trajectory of the junction], *step_out <-

@@ -146,7 +146,8 @@ def run_sharded(n_traj: int, run_one: Callable[[int], torch.Tensor], rank: int, 
 def rollout_trajectories(rmodel, cmodel, graphs, span: int, n_steps: int, rank: int = 0,
                          world: int = 1, device="cuda", use_graph: bool = True,
                          refresh_centres: bool = False, qoi=None, events=None, boundary: str = "periodic",
-                         max_y: float = 1.0, domain_factor: float = 1.0, domain_offsets=None, schedule=None):
+                         max_y: float = 1.0, domain_factor: float = 1.0, domain_offsets=None, schedule=None,
+                         polygons=False):
     """BASELINE config 4: `graphs[t]` = (x, ei, ea) numpy dicts of independent trajectories with
     EQUAL node counts.  Rank r rolls out trajectories t = r (mod world) as ONE disjoint-union
     graph on its GPU (one set of launches for the whole shard), then all ranks all-gather the
@@ -167,7 +168,11 @@ def rollout_trajectories(rmodel, cmodel, graphs, span: int, n_steps: int, rank: 
     scale_feature_patchs, needed when domain_factor > 1 and the grain centres or the no-flux boundary use them.
     `schedule`: None, or the process parameters of every step per trajectory of the WHOLE ensemble, {'G': [T, n_rows],
     'R': [T, n_rows]} or {'features': [T, n_rows, 2]} (GrainRollout.set_process_schedule): each rank takes the rows of its
-    shard, every trajectory follows its own (G, R) history on the device.  The returned keys are unchanged."""
+    shard, every trajectory follows its own (G, R) history on the device.  The returned keys are unchanged.
+    `polygons`: True (or the capacity in layers, default n_steps) records every layer's grain polygons on the device
+    (GrainRollout.enable_polygons).  The records stay on the rank that made them -- nothing of them is gathered: the result
+    gets 'polygons' = {'trajectories': the rank's own trajectory indices, 'last': per own trajectory the last layer's record
+    (GrainRollout.polygons(traj=i)), 'at': the rollout's polygons method, for the other layers}."""
     from . import synthetic
     from .rollout import GrainRollout
 
@@ -197,6 +202,8 @@ def rollout_trajectories(rmodel, cmodel, graphs, span: int, n_steps: int, rank: 
         ro.enable_events(mask, events["area_threshold"], events["edge_threshold"], traj_offsets=None if noflux else offsets)
     if qoi is not None:
         ro.enable_qoi(**dict(qoi, traj_offsets=None if noflux else offsets["grain"]))
+    if polygons:
+        ro.enable_polygons(capacity=n_steps if polygons is True else int(polygons), traj_offsets=None if noflux else offsets)
     if schedule is not None:
         # [T, n_rows, ...] of the ensemble -> [n_rows, the shard's trajectories, ...]
         take = lambda a: np.moveaxis(np.asarray(a)[mine], 0, 1)
@@ -235,4 +242,7 @@ def rollout_trajectories(rmodel, cmodel, graphs, span: int, n_steps: int, rank: 
     for k in ("ended_at", "n_eliminated"):
         if k in out:
             out[k] = out[k].reshape(len(graphs))
+    if polygons:
+        out["polygons"] = {"trajectories": list(mine), "last": [ro.polygons(traj=i) for i in range(len(mine))],
+                           "at": ro.polygons}
     return out

@@ -198,6 +198,7 @@ class GrainRollout:
         self._graphs = None                   # run() / step() graphs per (steps, parity): _replay
         self._qoi = None                      # enable_qoi(): the accumulator of grain volumes and its launch constants
         self._sched = None                    # set_process_schedule(): the (G, R) table on the device and its counter word
+        self._poly = None                     # enable_polygons(): the per-layer arena of grain polygons and its layer word
         self._invalidate_graphs(segments=True)   # step_events()' segment graphs: _segment_graphs, _graph_fwd, _graph_ref
         self._set_topology(edge_index_dict, edge_attr_dict)
         self.span = span
@@ -609,12 +610,136 @@ class GrainRollout:
                                Q["const"], src, dst, Q["V0"], Q["words"][:1], Q["words"][1:], Q["history"], Q["capacity"],
                                Q["area_sum"], init=init, area0=area0)
 
-    # -- what a step advances beside x: the QoI accumulator and the schedule's counter (run_events keeps them per slot) ----
+    # -- the layers' grain polygons (graph.update(), graph_datastruct.py:654-721) ---------------------------
+    def enable_polygons(self, capacity=None, traj_offsets=None):
+        """Record, from now on and on the device, every layer's grain polygons: what the reference's rollout leaves in
+        traj.regions / region_coors / region_center after traj.GNN_update (test.py:468-478) -- per grain the junctions of its
+        row of the joint->grain table, unwrapped, ordered counter-clockwise round their mean, with the mean and the shoelace
+        area.  One launch per step (ggnn_grain_polygons, include/ggnn.h) behind the boundary step and the centre refresh, in
+        step() / run() / step_events() / run_events() and inside their hipGraphs; the launch only reads the state.  Layer 0
+        -- the state as it is now -- is recorded at once.
+        capacity: the number of layers the arena has room for beyond layer 0 (default: enable_qoi's, when it was called
+        before; otherwise required).  The arena's rows have the size of the table as it is now: eliminations only shrink it.
+        traj_offsets: {'grain': [n_traj + 1], 'joint': [n_traj + 1]} of a disjoint-union graph, for polygons(traj=t)
+        (default: the constructor's of a no-flux union, or enable_events')."""
+        if capacity is None:
+            if self._qoi is None:
+                raise _lib.GGNNError("enable_polygons: capacity (the number of steps to record) is required unless enable_qoi "
+                                     "was called before")
+            capacity = self._qoi["capacity"]
+        if int(capacity) < 0:
+            raise _lib.GGNNError("enable_polygons: capacity must not be negative")
+        offsets = None
+        if self._traj is not None:
+            resolve_traj_offsets((self._traj["grain"], self._traj["joint"]), traj_offsets, "enable_polygons")
+        elif traj_offsets is not None:
+            from .topology import check_traj_offsets
+            offsets = check_traj_offsets(traj_offsets, self.n_nodes["grain"], self.n_nodes["joint"])
+        dev, ng = self.x["grain"].device, self.n_nodes["grain"]
+        self._poly = {
+            "name": "poly", "new": self._poly_state, "capacity": int(capacity), "offsets": offsets,
+            "arena": self.be.polygon_arena(ng, int(self.graph.edge_index[JG].size(1)), int(capacity), dev),
+            "home": self._poly_state(), "words": torch.zeros(2, dtype=torch.int32, device=dev),
+            "ring": None, "entries": None, "launched": 0, "at": None}
+        self._invalidate_graphs(static=True, segments=True, blocks=True)   # (graphs captured so far lack the launch)
+        self._enqueue_polygons(init=True)
+
+    def _poly_state(self):
+        """One counter word of the recorder: the layer written last (`flat`: what a state is copied by)."""
+        flat = torch.zeros(1, dtype=torch.int32, device=self.x["joint"].device)
+        return {"flat": flat, "layer": flat}
+
+    def _enqueue_polygons(self, slot=None, init=False):
+        """This step's layer of polygons (off unless enable_polygons was called): counted on the rollout's own word in
+        place, or -- a ring `slot` of the speculative event loop -- from the word of the slot before to the slot's own.
+        The arena is one: a voided step's row is written again by the step that stands."""
+        P = self._poly
+        if P is None:
+            return
+        if self.graph.edge_index[JG].size(1) > P["arena"]["joint_sorted"].size(1):
+            raise _lib.GGNNError("the joint->grain list has grown beyond the rows enable_polygons allocated: call it again")
+        src = dst = P["home"]
+        if slot is not None:
+            src, dst = P["ring"][(slot - 1) % len(P["ring"])], P["ring"][slot]
+        self.be.grain_polygons(self.graph.csr_full[JG], self.x["joint"], P["arena"], self.domain_factor, self.domain_offset,
+                               boundary=self.boundary, traj_grain_off=self._traj_grain_dev(),
+                               layer_in=None if init else src["layer"], layer_out=dst["layer"], sync_word=P["words"][:1],
+                               flags=P["words"][1:])
+
+    def _polygon_offsets(self):
+        """(grain offsets, junction offsets) of the union polygons(traj=t) slices, host int64, or None."""
+        if self._poly["offsets"] is not None:
+            return self._poly["offsets"]
+        if self._traj is not None:
+            return self._traj["grain"], self._traj["joint"]
+        if self._ens is not None:
+            ens = self._ens["sessions"]
+            return np.asarray(ens.grain_off, np.int64), np.asarray(ens.joint_off, np.int64)
+        return None
+
+    def polygons(self, layer=None, traj=None):
+        """The recorded polygons of one layer (one synchronisation): the last one, or `layer` = k (0 = the state
+        enable_polygons found).  Device tensors in the layout of the layer's joint->grain table: `rowptr` int32 [n + 1] (grain
+        g owns entries rowptr[g]:rowptr[g + 1]), `sides` [n], `joint_sorted` int32 [E] (the junctions counter-clockwise from
+        angle 0 round the centre; a no-flux boundary grain clockwise), `xy_sorted` fp32 [E, 2] (their unwrapped
+        coordinates), `centre` fp32 [n, 2] (unfolded), `area` fp32 [n] (shoelace, negative for a reversed grain); and
+        `layer`, `layers` (steps recorded).  traj=t (a union with known offsets): that trajectory's grains alone, rowptr
+        from 0 and junction ids local to the trajectory.  With enable_events(traj_offsets=...) `layers` is an array without
+        `traj`, and a trajectory that ended (trajectory_states) reports the layers up to its last completed step.  Raises
+        when a layer went beyond the capacity, or `layer` was not recorded."""
+        P = self._poly
+        if P is None:
+            raise _lib.GGNNError("call enable_polygons(...) first")
+        self._carry_home()
+        A, ng, cap = P["arena"], self.n_nodes["grain"], P["capacity"]
+        g0, g1, j0 = 0, ng, 0
+        if traj is not None:
+            off = self._polygon_offsets()
+            if off is None:
+                raise _lib.GGNNError("polygons(traj=...) needs the union's offsets: enable_polygons(traj_offsets=...)")
+            t = int(traj)
+            if not 0 <= t < len(off[0]) - 1:
+                raise _lib.GGNNError(f"no trajectory {traj}: the union has {len(off[0]) - 1}")
+            g0, g1, j0 = int(off[0][t]), int(off[0][t + 1]), int(off[1][t])
+        ended = []   # (trajectory, the layer word of its last completed step)
+        if self._ens is not None:
+            ended = [(t_, sn["poly_layer"]) for t_, sn in enumerate(self._ens["snapshot"])
+                     if sn is not None and sn.get("poly_layer") is not None]
+        count = next((w for t_, w in ended if traj is not None and t_ == int(traj)), P["home"]["layer"])
+        if layer is None:
+            row = A["rowptr"].index_select(0, count.long().clamp(0, cap))[0]
+        else:
+            if not 0 <= int(layer) <= cap:
+                raise _lib.GGNNError(f"layer {layer} is outside the arena's 0..{cap}")
+            row = A["rowptr"][int(layer)]
+        marks = row[torch.tensor([g0, g1, ng], device=row.device)]
+        words = torch.cat([P["home"]["layer"], P["words"][1:], count, marks] + [w for _, w in ended]).cpu().tolist()
+        if words[1] & _lib.GGNN_FLAG_POLYGON_OVERFLOW:
+            raise _lib.GGNNError(f"the polygon arena has room for {cap} layers, {words[0]} were recorded: "
+                                 "enable_polygons(capacity=...)")
+        layers = words[2]
+        k = layers if layer is None else int(layer)
+        if k > layers:
+            raise _lib.GGNNError(f"layer {k} has not been recorded: {layers} layers so far")
+        e0, e1 = words[3], words[4]
+        res = {"layer": k, "layers": layers, "rowptr": A["rowptr"][k, g0:g1 + 1] - e0,
+               "joint_sorted": A["joint_sorted"][k, e0:e1] - j0, "xy_sorted": A["xy_sorted"][k, e0:e1],
+               "centre": A["centre"][k, g0:g1], "area": A["area"][k, g0:g1]}
+        res["sides"] = res["rowptr"][1:] - res["rowptr"][:-1]
+        if self._ens is not None and traj is None:   # per trajectory of the event layer: an ended one stopped counting
+            per = np.full(self._ens["n_traj"], layers, dtype=np.int64)
+            for i, (t_, _) in enumerate(ended):
+                per[t_] = words[6 + i]
+            res["layers"] = per
+        return res
+
+    # -- what a step advances beside x: the QoI accumulator, the schedule's and the polygon recorder's counters -------------
     def _carried(self):
         """The device state a step advances beside x, each a dict with `home` (the rollout's own, advanced in place), `ring`
         / `entries` / `launched` / `at` (run_events' copies, _carry_enter_block) and `new` (makes one state; a state is copied
-        through its `flat` tensor): the QoI accumulator (enable_qoi) and the schedule's counter word (set_process_schedule)."""
-        return [c for c in (self._qoi, self._sched) if c is not None]
+        through its `flat` tensor): the QoI accumulator (enable_qoi), the schedule's counter word (set_process_schedule) and
+        the polygon recorder's layer word (enable_polygons)."""
+        return [c for c in (self._qoi, self._sched, self._poly) if c is not None]
 
     @staticmethod
     def _carry_home_one(c):
@@ -910,12 +1035,14 @@ class GrainRollout:
 
     def _enqueue_tail(self, slot=None, joints_before=None, centres_before=None):
         """What follows Rmodel.update in every plan, in front of the launch that refreshes the edge lengths: boundary step
-        (noflux), grain centres (refresh_centres), this step's QoI layer, the schedule's row of the step to come.  `slot`,
+        (noflux), grain centres (refresh_centres), this step's QoI layer and its layer of polygons, the schedule's row of the
+        step to come.  `slot`,
         `joints_before`, `centres_before`: the speculative event loop's (_enqueue_overlapped_step)."""
         self._enqueue_boundary(joints_before)
         if self.refresh_centres:
             self._enqueue_centres(centres_before)
         self._enqueue_qoi(slot)
+        self._enqueue_polygons(slot)
         self._enqueue_schedule(slot)
 
     def _refresh_edges(self, lists, count_dev=None):
@@ -1080,7 +1207,8 @@ class GrainRollout:
         g0, g1, j0, j1 = (int(v) for v in (ens.grain_off[t], ens.grain_off[t + 1], ens.joint_off[t], ens.joint_off[t + 1]))
         snap = {"x_joint": self.x["joint"][j0:j1].clone(), "x_grain": self.x["grain"][g0:g1].clone(),
                 "mask": {"grain": self.mask["grain"][g0:g1].copy(), "joint": self.mask["joint"][j0:j1].copy()},
-                "edge_index": ens.local_lists(t), "steps": self.steps_done, "qoi": None}
+                "edge_index": ens.local_lists(t), "steps": self.steps_done, "qoi": None,
+                "poly_layer": None if self._poly is None else self._poly["home"]["layer"].clone()}
         if self._qoi is not None:
             H = self._qoi["home"]
             snap["qoi"] = {"T": H["T"][g0:g1].clone(), "e": H["e"][g0:g1].clone(), "a": H["a"][g0:g1].clone(),

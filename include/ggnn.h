@@ -775,6 +775,57 @@ int ggnn_qoi_accumulate(const ggnn_qoi_args* args, ggnn_stream_t stream);
 int ggnn_qoi_finalize(const float* V0, const float* T, const float* e, int64_t n_grain, const int64_t* traj_offsets,
                       int64_t n_traj, double mesh_size, const float* bin_edges, int n_edges, float* volume, float* size,
                       float* d_mu, float* d_std, int32_t* hist, ggnn_stream_t stream);
+/* --- The grains' junction polygons of a rollout layer (graph.update(), graph_datastruct.py:654-721: `regions`,
+ * `region_coors`, `region_center`) ---
+ * ggnn_grain_polygons = ONE layer, one launch, behind the step's topology update, boundary step and centre refresh; it only
+ * reads the state.  Per grain g with row [p0, p1) of the joint->grain table (rowptr / col: the table ggnn_grain_centres reads,
+ * the FULL one for GGNN_BC_NOFLUX; read from device memory when the kernel runs, so a captured graph follows the events
+ * that rewrite the table in place; entries are clamped, nothing outside [0, E_cap) and [0, n_joint) is addressed):
+ *   unwrap : junction xy in the global frame ((x + domain_offset[j]) / domain_factor when domain_factor > 1); periodic: each
+ *            junction min-imaged to the previous moved one in the row's order (no-flux: no chaining); then +1 in a
+ *            coordinate where any vertex of the row is below -1e-12.  Exactly ggnn_grain_centres' coordinates.
+ *   centre : (the sum of the unwrapped coordinates in the row's order) / n, +1 where the vertices were shifted.  Unfolded:
+ *            frac(centre * domain_factor) belongs to x_grain, not to the polygon.
+ *   order  : ascending in the key of counterclock() (:100-116) -- the angle of d = v - centre in [0, 2 pi), then |d|, then
+ *            the position in the row.  The kernel compares (quadrant, q, |dx| + |dy|, position) with quadrant 0..3 counted
+ *            from dx > 0, dy >= 0 (d = 0: quadrant -1, first) and q = |dy| / (|dx| + |dy|) in quadrants 0 and 2, |dx| /
+ *            (|dx| + |dy|) in 1 and 3: the same order as the angle's wherever two angles differ by more than a few ulp, the
+ *            same 0 / 2 pi seam (the sign of dy), and only additions, comparisons and one correctly rounded division.
+ *            GGNN_BC_NOFLUX: the boundary grain's order is reversed (:715-716) -- grain 0, or with traj_grain_off the first
+ *            grain of every trajectory that has grains.
+ *   area   : half the sum of cross(d_i, d_next(i)) over the ordered polygon (negative for a reversed one).
+ * All of it in fp32, every operation that decides the order rounded on its own in one fixed sequence: the results do not
+ * depend on the grid or on the row's path through the kernel, bit for bit (the area's sum is a tree of fixed shape).
+ * A row of 0 or 1 junction is copied as it is, with area 0 and the centre at the junction (0 for an empty row).
+ * Outputs are rows of per-layer arrays in the table's own layout (sides of g = rowptr_out[g + 1] - rowptr_out[g]); layer
+ * k = *layer_in + 1 (NULL: k = 0) is read from device memory when the kernel runs and left in *layer_out (NULL: no counter),
+ * the same word or another one, advanced by the last block to finish through sync_word (one zeroed int32 device word,
+ * left zero, not shared by launches that may run concurrently).  A layer outside [0, capacity] writes nothing and ORs
+ * GGNN_FLAG_POLYGON_OVERFLOW into *flags.  Elements of joint_sorted / xy_sorted behind rowptr[n_grain] are not written.
+ * GGNN_EINVAL: a NULL required pointer, no such boundary, n_joint / n_grain < 1, ldx_joint < 2, E_cap or capacity outside
+ * [0, INT32_MAX), domain_factor < 1, traj_grain_off with n_traj < 1 (without: n_traj != 1), layer_out without sync_word /
+ * flags. */
+#define GGNN_FLAG_POLYGON_OVERFLOW 4  /* ggnn_grain_polygons: a layer beyond the arena's capacity */
+typedef struct ggnn_polygon_args {
+  const int32_t* rowptr;           /* [n_grain + 1] */
+  const int32_t* col;              /* [E_cap] junction of every table entry */
+  const float* x_joint;            /* [n_joint, ldx_joint >= 2] */
+  const float* domain_offset;      /* NULL (= 0) or [n_joint, 2] */
+  const int64_t* traj_grain_off;   /* NULL or [n_traj + 1], device: the trajectories' first grains (GGNN_BC_NOFLUX) */
+  int32_t* rowptr_out;             /* [capacity + 1, n_grain + 1]: row k = a copy of rowptr */
+  int32_t* joint_sorted;           /* [capacity + 1, E_cap] */
+  float* xy_sorted;                /* [capacity + 1, E_cap, 2] */
+  float* centre;                   /* [capacity + 1, n_grain, 2] */
+  float* area;                     /* [capacity + 1, n_grain] */
+  const int32_t* layer_in;         /* NULL (layer 0) or k - 1 */
+  int32_t* layer_out;              /* NULL or receives k */
+  int32_t* sync_word;
+  int32_t* flags;
+  int64_t n_joint, ldx_joint, n_grain, E_cap, n_traj, capacity;
+  float domain_factor;
+  int32_t boundary;                /* GGNN_BC_PERIODIC / GGNN_BC_NOFLUX */
+} ggnn_polygon_args;
+int ggnn_grain_polygons(const ggnn_polygon_args* args, ggnn_stream_t stream);
 /* The host-side topology update those counts trigger: one call of the reference's `Cmodel.update`
  * (models.py:612-842 with delete_grain_index :861-893, switching_edge_index :896-1051, point_in_triangle :1055-1070,
  * periodic_move :1103-1106), nucleation off.  HOST memory throughout, no stream: grains of `grain_event` (those below the
