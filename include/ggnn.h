@@ -595,6 +595,8 @@ int ggnn_heads_regressor_update(const float* h_joint, int64_t n_joint, const flo
  * (node_tmp [n_joint, 8] scratch) + a per-edge combine in the original COO order.
  *   w_node : [6][96] = lin1.w[0,0:96], lin1.w[1,0:96], lin2.w[0,0:96], lin1.w[0,96:192], lin1.w[1,96:192], lin2.w[0,96:192]
  *   w_edge : [6]     = lin1.w[0,192], lin1.w[1,192], lin2.w[0,192], lin1.b[0], lin1.b[1], lin2.b[0]
+ * An edge with an endpoint outside [0, n_joint) gets NaN in its own three outputs (edge_event[e], edge[e, 0:2]) and reads
+ * nothing; outputs behind *E_dev are not written.  (ggnn_step_refresh does the same with edge_attr[e].)
  */
 int ggnn_heads_classifier(const float* h_joint, int64_t n_joint, const int64_t* edge_index_jj, int64_t E,
                           const int64_t* E_dev /* NULL, or the number of edges read from device memory when the kernels run:

@@ -35,7 +35,7 @@ class TorchEmulatorBackend:
             rel = xs[col[:E], :3] - xd[row[:E], :3]
             reloc = torch.where(rel > 0.5, -1.0, torch.where(rel < -0.5, 1.0, 0.0)) + rel
             Fs = xs.size(1)
-            einfo[:E] = 0.0
+            einfo[:E + 3] = 0.0   # (the GGNN_UNIT_EDGES padding records behind the E edges are written too)
             einfo[:E, 0:3] = einfo[:E, 16:19] = reloc
             einfo[:E, 3:Fs] = xs[col[:E], 3:Fs]
             einfo[:E, 12] = 1.0
@@ -477,7 +477,8 @@ class TorchEmulatorBackend:
         x_grain[:, 2] += dz
         flags[1] = int(x_grain[0, 2] > torch.tensor(zmax, dtype=torch.float32))
 
-    def grain_centres(self, csr_jg, x_joint, x_grain, domain_factor=1.0, domain_offset=None, centres_before=None):
+    def grain_centres(self, csr_jg, x_joint, x_grain, domain_factor=1.0, domain_offset=None, centres_before=None,
+                      boundary="periodic"):
         if centres_before is not None:
             centres_before.copy_(x_grain[:, :2])
         rowptr, col = csr_jg.rowptr.tolist(), csr_jg.col.tolist()
@@ -492,6 +493,8 @@ class TorchEmulatorBackend:
             v = [xy[js[0]]]
             for j in js[1:]:
                 rel = xy[j] - v[-1]
+                if boundary == "noflux":   # (no min-image chaining: graph_datastruct.py:689-692)
+                    rel = torch.zeros_like(rel)
                 v.append(xy[j] + torch.where(rel > 0.5, -1.0, torch.where(rel < -0.5, 1.0, 0.0)))
             v = torch.stack(v)
             m = v.sum(0) / len(js) + (~(v > -1e-12).all(0)).float()
@@ -501,11 +504,14 @@ class TorchEmulatorBackend:
             x_grain[g, :2] = m
 
     def detect_events(self, grain_area, live_grain, area_threshold, edge_event, edge_index_jj,
-                      logit_threshold, flags, range_word=None, E_dev=None):
+                      logit_threshold, flags, range_word=None, E_dev=None, skip_grain=-1):
         if range_word is not None:
             flags[2] = int(range_word[0])
             range_word.zero_()
-        flags[0] = int(((live_grain > 0) & (grain_area < area_threshold)).sum())
+        counted = (live_grain > 0) & (grain_area < area_threshold)
+        if skip_grain >= 0:
+            counted[skip_grain] = False
+        flags[0] = int(counted.sum())
         flags[1] = int(((edge_event > logit_threshold) & (edge_index_jj[0] < edge_index_jj[1])).sum())
 
     def step_refresh(self, x_joint, x_grain, zmax, flags, edges):
