@@ -57,6 +57,7 @@ EXPORTED_SYMBOLS = (
     "ggnn_topology_counts", "ggnn_topology_export", "ggnn_topology_close", "ggnn_step_refresh",
     "ggnn_workspace_bytes",
     "ggnn_qoi_accumulate", "ggnn_qoi_finalize", "ggnn_process_schedule", "ggnn_grain_polygons",
+    "ggnn_polygons_rasterize", "ggnn_image_compare",
     "ggnn_metric_record",
     "ggnn_masked_mse_rows", "ggnn_collate_batch", "ggnn_reverse_slots",
 )
@@ -390,6 +391,16 @@ class PolygonArgs(Structure):
     ]
 
 
+class RasterArgs(Structure):
+    """Mirror of `ggnn_raster_args`."""
+    _fields_ = [
+        ("rowptr", c_void_p), ("xy_sorted", c_void_p), ("traj_grain_off", c_void_p), ("layers", c_void_p), ("image", c_void_p),
+        ("n_grain", c_int64), ("E_cap", c_int64), ("capacity", c_int64), ("n_traj", c_int64), ("grain_begin", c_int64),
+        ("grain_end", c_int64), ("n_layers", c_int64), ("nx", c_int64), ("ny", c_int64),
+        ("corner_grains", c_int32 * 4), ("with_corners", c_int32), ("boundary", c_int32),
+    ]
+
+
 class MetricArgs(Structure):
     """Mirror of `ggnn_metric_args`."""
     _fields_ = [
@@ -538,6 +549,10 @@ def _declare(lib):
     lib.ggnn_metric_record.argtypes = [POINTER(MetricArgs), c_void_p]
     lib.ggnn_grain_polygons.restype = c_int
     lib.ggnn_grain_polygons.argtypes = [POINTER(PolygonArgs), c_void_p]
+    lib.ggnn_polygons_rasterize.restype = c_int
+    lib.ggnn_polygons_rasterize.argtypes = [POINTER(RasterArgs), c_void_p]
+    lib.ggnn_image_compare.restype = c_int
+    lib.ggnn_image_compare.argtypes = [c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]
     lib.ggnn_process_schedule.restype = c_int
     lib.ggnn_process_schedule.argtypes = [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p]

@@ -1304,6 +1304,92 @@ class HipBackend:
         check(self.lib.ggnn_grain_polygons(ctypes.byref(A), _lib.current_stream()), "ggnn_grain_polygons")
         return arena
 
+    def rasterize_polygons(self, arena, size, layers=None, boundary="periodic", grains=None, traj_grain_off=None,
+                           corner_grains=None, out=None):
+        """The grain-ID images of arena rows (include/ggnn.h, ggnn_polygons_rasterize): int32 [L, ny, nx] (periodic: [L, nx,
+        nx]), pixel = the highest grain index + 1 among the polygons that hold it, 0 = uncovered; zeroed and filled by the
+        call.  arena: a polygon_arena as grain_polygons left it; size = (nx, ny); layers: the rows to draw (host integers;
+        None: all of them); grains = (g0, g1): that range alone, ids counted from g0; traj_grain_off: None or int64
+        [n_traj + 1] on the device (noflux: every trajectory's first grain is skipped); corner_grains: four ids for the
+        uncovered pixels of a no-flux image; out: the image to fill."""
+        bc = _boundary_code(boundary)
+        rowptr, xy = arena["rowptr"], arena["xy_sorted"]
+        _require_cuda(rowptr, xy, traj_grain_off, out)
+        if rowptr.dtype != torch.int32 or rowptr.dim() != 2 or rowptr.size(1) < 2 or not rowptr.is_contiguous():
+            raise _lib.GGNNError("arena['rowptr'] must be a contiguous int32 [layers, n_grain + 1]")
+        L_cap, n_grain = rowptr.size(0), rowptr.size(1) - 1
+        if xy.dtype != torch.float32 or xy.dim() != 3 or xy.size(0) != L_cap or xy.size(2) != 2 or not xy.is_contiguous():
+            raise _lib.GGNNError(f"arena['xy_sorted'] must be a contiguous float32 tensor of shape ({L_cap}, E, 2)")
+        try:
+            nx, ny = (int(v) for v in size)
+        except (TypeError, ValueError):
+            raise _lib.GGNNError("size must be (nx, ny)") from None
+        if not (0 < nx < 1 << 15 and 0 < ny < 1 << 15):
+            raise _lib.GGNNError(f"size must lie in 1 .. {(1 << 15) - 1} in both directions, got {(nx, ny)}")
+        rows = list(range(L_cap)) if layers is None else [int(k) for k in layers]
+        if not rows or any(not 0 <= k < L_cap for k in rows):
+            raise _lib.GGNNError(f"layers must name rows 0..{L_cap - 1} of the arena, at least one")
+        g0, g1 = (0, n_grain) if grains is None else (int(grains[0]), int(grains[1]))
+        if not 0 <= g0 <= g1 <= n_grain:
+            raise _lib.GGNNError(f"grains must be a range inside 0..{n_grain}")
+        n_traj = 1
+        if traj_grain_off is not None:
+            if traj_grain_off.dtype != torch.int64 or traj_grain_off.numel() < 2 or not traj_grain_off.is_contiguous():
+                raise _lib.GGNNError("traj_grain_off must be a contiguous int64 [n_traj + 1]")
+            n_traj = traj_grain_off.numel() - 1
+        if corner_grains is not None:
+            if bc != _lib.BC_NOFLUX:
+                raise _lib.GGNNError("corner_grains belong to a no-flux image")
+            corner_grains = [int(c) for c in corner_grains]
+            if len(corner_grains) != 4 or any(not -2 ** 31 <= c < 2 ** 31 for c in corner_grains):
+                raise _lib.GGNNError("corner_grains must be four int32 ids")
+        shape = (len(rows), nx, nx) if bc == _lib.BC_PERIODIC else (len(rows), ny, nx)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int32, device=rowptr.device)
+        elif out.dtype != torch.int32 or tuple(out.shape) != shape or not out.is_contiguous():
+            raise _lib.GGNNError(f"out must be a contiguous int32 tensor of shape {shape}")
+        A = _lib.RasterArgs()
+        host_rows = (ctypes.c_int32 * len(rows))(*rows)
+        A.rowptr, A.xy_sorted, A.traj_grain_off, A.image = ptr(rowptr), ptr(xy), ptr(traj_grain_off), ptr(out)
+        A.layers = ctypes.cast(host_rows, ctypes.c_void_p)
+        A.n_grain, A.E_cap, A.capacity, A.n_traj = n_grain, xy.size(1), L_cap - 1, n_traj
+        A.grain_begin, A.grain_end, A.n_layers, A.nx, A.ny = g0, g1, len(rows), nx, ny
+        if corner_grains is not None:
+            A.corner_grains, A.with_corners = (ctypes.c_int32 * 4)(*corner_grains), 1
+        A.boundary = bc
+        check(self.lib.ggnn_polygons_rasterize(ctypes.byref(A), _lib.current_stream()), "ggnn_polygons_rasterize")
+        return out
+
+    def image_compare(self, image, truth=None, n_grain=None, differing=None, counts=None):
+        """Differing pixels and per-id pixel counts of an int32 image (include/ggnn.h, ggnn_image_compare), one launch;
+        returns (differing, counts): int64 device tensors [1] (None without `truth`) and [n_grain + 1] (None without
+        `n_grain`), ADDED to the ones passed in (None: fresh zeroed ones).  truth: int32, the image's shape."""
+        _require_cuda(image, truth, differing, counts)
+        if image.dtype != torch.int32 or not image.is_contiguous() or image.numel() < 1:
+            raise _lib.GGNNError("image must be a contiguous int32 tensor with pixels")
+        if truth is not None and (truth.dtype != torch.int32 or truth.shape != image.shape or not truth.is_contiguous()):
+            raise _lib.GGNNError("truth must be a contiguous int32 tensor of the image's shape")
+        if truth is None and n_grain is None:
+            raise _lib.GGNNError("image_compare needs truth, n_grain or both")
+        if n_grain is not None and not 0 <= int(n_grain) < 2 ** 31 - 1:
+            raise _lib.GGNNError("n_grain must not be negative")
+        i64 = dict(dtype=torch.int64, device=image.device)
+        if truth is None:
+            differing = None
+        elif differing is None:
+            differing = torch.zeros(1, **i64)
+        elif differing.dtype != torch.int64 or differing.numel() != 1:
+            raise _lib.GGNNError("differing must be one int64 word")
+        if n_grain is None:
+            counts = None
+        elif counts is None:
+            counts = torch.zeros(int(n_grain) + 1, **i64)
+        elif counts.dtype != torch.int64 or counts.numel() != int(n_grain) + 1 or not counts.is_contiguous():
+            raise _lib.GGNNError("counts must be a contiguous int64 [n_grain + 1]")
+        check(self.lib.ggnn_image_compare(ptr(image), ptr(truth), image.numel(), 0 if n_grain is None else int(n_grain),
+                                          ptr(differing), ptr(counts), _lib.current_stream()), "ggnn_image_compare")
+        return differing, counts
+
     def process_schedule(self, x_joint, table, traj_joint_off, step_in, step_out, sync_word):
         """The (G, R) features of the step to come from a device-side table (include/ggnn.h, ggnn_process_schedule), one
         launch: x_joint[:, 3:5] <- table[min(max(*step_in + 1, 0), n_rows - 1), trajectory of the junction], *step_out <-

@@ -733,6 +733,57 @@ class GrainRollout:
             res["layers"] = per
         return res
 
+    # -- the layers' grain-ID images (plot_polygons, graph_datastruct.py:553-610) ------------------------------
+    def _raster_range(self, traj):
+        """(g0, g1) of polygons(traj=...)'s slice (which has checked `traj` already)."""
+        if traj is None:
+            return None
+        off = self._polygon_offsets()
+        return int(off[0][int(traj)]), int(off[0][int(traj) + 1])
+
+    def grain_image(self, size, layer=None, traj=None, corner_grains=None, out=None):
+        """The grain-ID image of one recorded layer, filled on the device from its polygons: what the reference's
+        traj.plot_polygons(size) leaves in `alpha_field` -- int32 [size[1], size[0]] (periodic: [size[0], size[0]]), indexed
+        [y, x], pixel = the highest grain index + 1 among the polygons that hold it (include/ggnn.h,
+        ggnn_polygons_rasterize: exact in integers), 0 = uncovered.  `layer` and `traj` as in polygons() (one
+        synchronisation, the same errors; traj=t: ids local to the trajectory).  A no-flux image skips the boundary
+        grain(s); corner_grains = (a, b, c, d) fills its uncovered pixels by quadrant.  On demand, on the current stream: the
+        step, its graphs and the carried state are not touched."""
+        k = self.polygons(layer, traj)["layer"]
+        img = self.be.rasterize_polygons(self._poly["arena"], size, [k], self.boundary, self._raster_range(traj),
+                                         self._traj_grain_dev(), corner_grains, None if out is None else out.unsqueeze(0))
+        return img[0] if out is None else out
+
+    def grain_images(self, size, layers=None, traj=None, corner_grains=None, out=None):
+        """grain_image of several layers from one launch: int32 [L, ny, nx] -- the reference's `alpha_field_list`.
+        layers: None = every layer recorded so far (of `traj`, where it ended early), or the layers to draw."""
+        recorded = int(np.max(self.polygons(None, traj)["layers"]))
+        if layers is None:
+            layers = range(recorded + 1)
+        layers = [int(k) for k in layers]
+        cap = self._poly["capacity"]
+        for k in layers:
+            if not 0 <= k <= cap:
+                raise _lib.GGNNError(f"layer {k} is outside the arena's 0..{cap}")
+            if k > recorded:
+                raise _lib.GGNNError(f"layer {k} has not been recorded: {recorded} layers so far")
+        return self.be.rasterize_polygons(self._poly["arena"], size, layers, self.boundary, self._raster_range(traj),
+                                          self._traj_grain_dev(), corner_grains, out)
+
+    def image_error(self, image, truth=None):
+        """An image against the phase-field map of its layer (compute_error_layer, graph_datastruct.py:346-348) and the
+        pixel count of every id (the initial areas, :287), one launch: {'rate': differing / pixels, 'differing': int,
+        'counts': int64 [n_grain + 1] on the device}; truth=None: the counts alone.  Integer atomics: exact."""
+        if self._poly is None:
+            raise _lib.GGNNError("call enable_polygons(...) first")
+        if truth is not None:
+            truth = torch.as_tensor(truth).to(device=image.device, dtype=torch.int32).contiguous()
+        differing, counts = self.be.image_compare(image, truth, self.n_nodes["grain"])
+        if truth is None:
+            return {"counts": counts}
+        differing = int(differing)
+        return {"rate": differing / image.numel(), "differing": differing, "counts": counts}
+
     # -- what a step advances beside x: the QoI accumulator, the schedule's and the polygon recorder's counters -------------
     def _carried(self):
         """The device state a step advances beside x, each a dict with `home` (the rollout's own, advanced in place), `ring`

@@ -828,6 +828,53 @@ typedef struct ggnn_polygon_args {
   int32_t boundary;                /* GGNN_BC_PERIODIC / GGNN_BC_NOFLUX */
 } ggnn_polygon_args;
 int ggnn_grain_polygons(const ggnn_polygon_args* args, ggnn_stream_t stream);
+/* --- The grain-ID image of recorded layers (plot_polygons, graph_datastruct.py:553-610: `alpha_field`) ---
+ * ggnn_polygons_rasterize = n_layers rows of ggnn_grain_polygons' arena filled into image [n_layers, ny, nx] int32 (periodic:
+ * [n_layers, nx, nx]), indexed [y][x]; the call zeroes the image itself, then ONE launch takes up to GGNN_RASTER_MAX_LAYERS
+ * layers (the layer is a grid dimension; more layers: one launch per such group).  On demand, on `stream`; it only reads
+ * the arena.  The rule is exact in integers (tests/rastercheck.py restates it):
+ *   vertices   : of polygon row [rowptr[g], rowptr[g + 1]) of xy_sorted, with s = nx for BOTH coordinates:
+ *                GGNN_BC_PERIODIC v = (int)(x * (float)s) -- one fp32 product, truncated toward zero; GGNN_BC_NOFLUX
+ *                v = (int)rintf(x * (float)s) -- half to even.  The product saturates at +-2^20 (NaN: -2^20).
+ *   membership : a lattice point belongs to a polygon when it lies on one of its edges, or has an odd number of crossings
+ *                under the half-open rule in y (edge a -> b with ya < yb counts on ya <= y < yb for points strictly left of
+ *                it): the closed set of the even-odd rule, decided by the sign of (x - xa)(yb - ya) - (y - ya)(xb - xa) in
+ *                int64.  The kernel takes it from the edge's crossing with the scanline, xc = xa + num / den with
+ *                num = (y - ya)(xb - xa), den = yb - ya > 0, rounded both ways: with q = num / den truncated toward zero
+ *                and r = num - q den, floor = q - (r < 0) and ceil = q + (r > 0) -- a negative numerator truncates
+ *                upward, so there the floor is corrected and the ceiling is not; x < xc <=> x < ceil, x = xc <=> ceil <=
+ *                x <= floor.  Rows of 0 or 1 junction draw nothing; a row of 2 draws the lattice points of its segment.
+ *   ownership  : image = max(grain index - grain_begin + 1) over the polygons that hold the point; 0 = uncovered.  A max:
+ *                the image does not depend on the grid or on the order of arrival.
+ *   periodic   : canvas [0, 2 nx)^2, points outside dropped, folded by mod nx with max (the four quadrants' np.max).
+ *   no-flux    : canvas [0, nx) x [0, ny), points outside dropped; the boundary grain is skipped (grain 0, or with
+ *                traj_grain_off the first grain of every trajectory that has grains); with_corners: an uncovered pixel takes
+ *                corner_grains[2 x / nx + 2 (2 y / ny)] (:602-605), otherwise it stays 0.
+ * Only grains [grain_begin, grain_end) are drawn (a trajectory of a union).  Table entries are clamped: nothing outside the
+ * arena rows and the image is addressed, whatever the tables hold.
+ * GGNN_EINVAL without a launch: args / rowptr / xy_sorted / image NULL, no such boundary, nx or ny outside [1, 2^15), n_grain
+ * < 1, E_cap or capacity outside [0, INT32_MAX), a grain range outside [0, n_grain], traj_grain_off with n_traj < 1 (without:
+ * n_traj != 1), n_layers < 1, a layer outside [0, capacity]. */
+#define GGNN_RASTER_MAX_LAYERS 256
+typedef struct ggnn_raster_args {
+  const int32_t* rowptr;           /* [capacity + 1, n_grain + 1], device: the arena's */
+  const float* xy_sorted;          /* [capacity + 1, E_cap, 2], device: the arena's */
+  const int64_t* traj_grain_off;   /* NULL or [n_traj + 1], device (GGNN_BC_NOFLUX) */
+  const int32_t* layers;           /* HOST [n_layers]: the arena rows to draw, or NULL: rows 0 .. n_layers - 1 */
+  int32_t* image;                  /* [n_layers, ny, nx] (periodic: [n_layers, nx, nx]), device */
+  int64_t n_grain, E_cap, capacity, n_traj, grain_begin, grain_end, n_layers, nx, ny;
+  int32_t corner_grains[4];
+  int32_t with_corners;
+  int32_t boundary;                /* GGNN_BC_PERIODIC / GGNN_BC_NOFLUX */
+} ggnn_raster_args;
+int ggnn_polygons_rasterize(const ggnn_raster_args* args, ggnn_stream_t stream);
+/* ggnn_image_compare = one launch over n_pixels int32 pixels: *differing += the pixels where image != truth (truth and
+ * differing both NULL: not compared), counts[id] += the pixels with that id for 0 <= id <= n_grain (counts NULL: not counted;
+ * other ids are not counted).  Both accumulate on what the caller left there, with 64-bit integer atomics: exact, and
+ * independent of the order.  GGNN_EINVAL without a launch: image NULL, n_pixels < 1, n_grain outside [0, INT32_MAX), truth
+ * without differing or the reverse, neither truth nor counts. */
+int ggnn_image_compare(const int32_t* image, const int32_t* truth, int64_t n_pixels, int64_t n_grain, uint64_t* differing,
+                       uint64_t* counts, ggnn_stream_t stream);
 /* The host-side topology update those counts trigger: one call of the reference's `Cmodel.update`
  * (models.py:612-842 with delete_grain_index :861-893, switching_edge_index :896-1051, point_in_triangle :1055-1070,
  * periodic_move :1103-1106), nucleation off.  HOST memory throughout, no stream: grains of `grain_event` (those below the

@@ -1,0 +1,489 @@
+"""The grain-ID image of recorded layers (ggnn_polygons_rasterize / ggnn_image_compare, GrainRollout.grain_image /
+grain_images / image_error) against the numpy restatement of tests/rastercheck.py, and the restatement against the reference's
+own `alpha_field` (tests/golden/make_golden_grain_image.py: plot_polygons through PIL 12.2).
+
+The contract.  KERNEL against RESTATEMENT: every pixel equal, on every shape below.  RESTATEMENT against the REFERENCE: PIL
+fills by its own scanline rule, so the two may differ on polygon boundaries and nowhere else -- at a differing pixel the
+reference's id is a grain whose closed integer polygon holds a lattice point within Chebyshev distance 1 of it, and the
+pixel lies within distance 1 of some polygon's boundary.  Measured here, the differing share of the five states is
+  init 0.012179   step1 0.012131   step3 0.011813   mass3 0.011163   noflux 0.010988
+and each is capped at its measured value plus a quarter (room for PIL's patch versions); the restated misclassification
+rate may differ from the reference's `error_layer` by the measured differing share at most (it cannot by more)."""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import rastercheck as rc
+from helpers import GOLDEN
+from graingraphnn_amd import _lib
+
+DEV = "cuda"
+TAGS = ("init", "step1", "step3", "mass3", "noflux")
+MEASURED_SHARE = {"init": 0.012179234345679898, "step1": 0.012131425771212068, "step3": 0.011812701941426529,
+                  "mass3": 0.011163302138238494, "noflux": 0.010988004031856447}
+# mass3: the eventful update leaves grain 96 a concave polygon whose junctions, ordered round their mean, wrap round the
+# triangle of grain 97; the reference's dict draws 96 after 97, so 66 pixels deep inside both are 97 there and 98 here.
+EXCLUDED_GRAINS = {tag: (97,) if tag == "mass3" else () for tag in TAGS}
+
+
+def npz(name):
+    return np.load(os.path.join(GOLDEN, name + ".npz"))
+
+
+def golden_image_case(tag):
+    """(rowptr, coors fp32, size, boundary, corner_grains, alpha_field, alpha_pde, error_layer) of a recorded state."""
+    P, I = npz("polygons_cfg1"), npz("grain_image_cfg1")
+    return (P[tag + "__rowptr"], P[tag + "__coors"].astype(np.float32), tuple(int(v) for v in I[tag + "__imagesize"]),
+            "noflux" if tag == "noflux" else "periodic", I["noflux__corner_grains"] if tag == "noflux" else None,
+            I[tag + "__alpha_field"].astype(np.int32), I[tag + "__alpha_pde"].astype(np.int32), float(I[tag + "__error_layer"]))
+
+
+_restated = {}
+
+
+def restated_golden(tag):
+    """The restatement's image of a golden state, computed once."""
+    if tag not in _restated:
+        rowptr, coors, size, bc, corners, _, _, _ = golden_image_case(tag)
+        img = rc.grain_image(rowptr, coors, size, bc, corner_grains=corners)
+        img.setflags(write=False)
+        _restated[tag] = img
+    return _restated[tag]
+
+
+def grow(m):
+    """3 x 3 dilation of a boolean window (what lies outside the window is False)."""
+    p = np.pad(m, 1)
+    out = np.zeros_like(m)
+    for dy in range(3):
+        for dx in range(3):
+            out |= p[dy:dy + m.shape[0], dx:dx + m.shape[1]]
+    return out
+
+
+def neighbourhoods(rowptr, coors, size, boundary, skip):
+    """Per grain (y0, x0, window) of the canvas points within Chebyshev distance 1 of its closed integer polygon, and the
+    canvas map of the points within distance 1 of any polygon's boundary."""
+    s = size[0]
+    width, height = (2 * s, 2 * s) if boundary == "periodic" else size
+    near, boundary_map = {}, np.zeros((height, width), bool)
+    for g in range(len(rowptr) - 1):
+        if g in skip or rowptr[g + 1] - rowptr[g] < 2:
+            continue
+        v = rc.vertex_pixels(coors[rowptr[g]:rowptr[g + 1]], s, boundary)
+        x0, x1 = max(int(v[:, 0].min()) - 2, 0), min(int(v[:, 0].max()) + 2, width - 1)
+        y0, y1 = max(int(v[:, 1].min()) - 2, 0), min(int(v[:, 1].max()) + 2, height - 1)
+        if x0 > x1 or y0 > y1:
+            continue
+        py, px = np.meshgrid(np.arange(y0, y1 + 1), np.arange(x0, x1 + 1), indexing="ij")
+        inside = rc.contains(v, px, py)
+        wide = grow(inside)
+        near[g] = (y0, x0, wide)
+        boundary_map[y0:y1 + 1, x0:x1 + 1] |= wide & grow(~inside)   # a member and a non-member within distance 1
+    return near, boundary_map
+
+
+# ---- CPU ---------------------------------------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("tag", TAGS)
+def test_restatement_against_the_reference_image(tag):
+    rowptr, coors, size, bc, corners, field, pde, error_layer = golden_image_case(tag)
+    img = restated_golden(tag)
+    assert img.shape == field.shape and img.dtype == np.int32
+    n_grain = len(rowptr) - 1
+    excluded = set(EXCLUDED_GRAINS[tag])
+    assert len(excluded) <= 0.01 * n_grain
+    differs = img != field
+    share = float(differs.mean())
+    differing, counts = rc.compare(img, pde, n_grain)
+    gap = abs(differing / img.size - error_layer)
+    print(f"{tag}: differing share {share:.6f} ({int(differs.sum())} pixels), |rate - error_layer| {gap:.6f}")
+    assert share <= 1.25 * MEASURED_SHARE[tag], (tag, share)
+    assert gap <= MEASURED_SHARE[tag], (tag, gap)
+    assert counts.sum() == img.size and np.array_equal(counts[1:], np.bincount(img.ravel(), minlength=n_grain + 1)[1:])
+    # the condition at every differing pixel
+    s = size[0]
+    near, boundary_map = neighbourhoods(rowptr, coors, size, bc, rc.boundary_grains(n_grain, bc))
+    images = [(a * s, b * s) for a in (0, 1) for b in (0, 1)] if bc == "periodic" else [(0, 0)]
+    bad = []
+    for y, x in zip(*np.nonzero(differs)):
+        ref = int(field[y, x]) - 1
+        if ref in excluded or int(img[y, x]) - 1 in excluded:
+            continue
+        at_boundary = any(boundary_map[y + oy, x + ox] for oy, ox in images)
+        held = False
+        if ref in near:
+            y0, x0, wide = near[ref]
+            held = any(0 <= y + oy - y0 < wide.shape[0] and 0 <= x + ox - x0 < wide.shape[1] and wide[y + oy - y0, x + ox - x0]
+                       for oy, ox in images)
+        elif corners is not None and int(img[y, x]) not in corners:
+            held = True   # the reference left the pixel uncovered (its corner fill): the boundary condition alone decides
+        if not (held and at_boundary):
+            bad.append((int(y), int(x), ref + 1, int(img[y, x])))
+    assert not bad, (tag, len(bad), bad[:10])
+
+
+def test_restatement_rule_on_small_shapes():
+    """The closed even-odd rule itself: boundary points belong, a segment is its lattice points, max id owns, the fold."""
+    sq = np.array([[1, 1], [4, 1], [4, 4], [1, 4]])
+    py, px = np.meshgrid(np.arange(6), np.arange(6), indexing="ij")
+    assert np.array_equal(rc.contains(sq, px, py), (px >= 1) & (px <= 4) & (py >= 1) & (py <= 4))
+    seg = np.array([[0, 0], [4, 2]])
+    assert sorted(zip(*np.nonzero(rc.contains(seg, px, py)))) == [(0, 0), (1, 2), (2, 4)]
+    bow = np.array([[0, 0], [4, 4], [4, 0], [0, 4]])                     # self-crossing: the crossing point is on two edges
+    m = rc.contains(bow, px, py)
+    assert m[2, 2] and m[1, 0] and m[1, 4] and not m[0, 2] and not m[4, 2] and m[3, 0]
+    s = 8
+    xy = (np.array([[1, 1], [5, 1], [5, 5], [1, 5], [5, 1], [9, 1], [9, 5], [5, 5]]) + 0.5) / s
+    img = rc.grain_image([0, 4, 8], xy.astype(np.float32), (s, s))
+    assert img.shape == (s, s) and img[3, 5] == 2 and img[3, 4] == 1 and img[3, 0] == 2 and img[3, 1] == 2 and img[0, 3] == 0
+    assert rc.vertex_pixels(np.array([[-0.01, 0.99]], np.float32), 37, "periodic").tolist() == [[0, 36]]
+    assert rc.vertex_pixels(np.array([[0.5 / 4, 1.5 / 4]], np.float32), 4, "noflux").tolist() == [[0, 2]]   # half to even
+    nf = rc.grain_image([0, 4, 8], xy.astype(np.float32), (s, 6), "noflux", corner_grains=(7, 8, 9, 10))
+    assert nf.shape == (6, s) and nf[3, 6] == 2 and nf[3, 2] == 9 and nf[0, 6] == 8 and nf[5, 0] == 9 and nf[0, 0] == 7
+
+
+def test_entry_points_validate_on_the_host():
+    lib = _lib.load()
+    assert lib.ggnn_version() == 26 == _lib.GGNN_ABI_VERSION
+    assert ctypes.sizeof(_lib.RasterArgs) == 5 * 8 + 9 * 8 + 6 * 4
+    assert lib.ggnn_polygons_rasterize(None, None) == -1
+    assert lib.ggnn_polygons_rasterize(ctypes.byref(_lib.RasterArgs()), None) == -1
+    buf = (ctypes.c_int32 * 64)()                 # (host memory: refused before anything would be launched)
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    rows = (ctypes.c_int32 * 2)(0, 3)
+
+    def args(**kw):
+        A = _lib.RasterArgs(p, p, None, ctypes.cast(rows, ctypes.c_void_p), p, 4, 9, 3, 1, 0, 4, 2, 8, 8)
+        for k, v in kw.items():
+            setattr(A, k, v)
+        return ctypes.byref(A)
+    for bad in (dict(boundary=7), dict(nx=0), dict(ny=-1), dict(nx=1 << 15), dict(ny=1 << 15), dict(rowptr=None),
+                dict(xy_sorted=None), dict(image=None), dict(n_grain=0), dict(E_cap=-1), dict(capacity=2), dict(capacity=-1),
+                dict(n_layers=0), dict(grain_end=5), dict(grain_begin=-1), dict(grain_begin=3, grain_end=2), dict(n_traj=2),
+                dict(traj_grain_off=p, n_traj=0), dict(layers=None, n_layers=5)):
+        assert lib.ggnn_polygons_rasterize(args(**bad), None) == -1, bad
+    for bad in ((None, p, 8, 3, p, p), (p, p, 0, 3, p, p), (p, p, 8, -1, p, p), (p, p, 8, 3, None, p), (p, None, 8, 3, p, p),
+                (p, None, 8, 3, None, None)):
+        assert lib.ggnn_image_compare(*bad, None) == -1, bad
+
+
+def test_rollout_refuses_images_before_polygons_are_enabled():
+    from graingraphnn_amd import GrainRollout
+    ro = object.__new__(GrainRollout)
+    ro._poly = None
+    for call in (lambda: ro.grain_image((8, 8)), lambda: ro.grain_images((8, 8)), lambda: ro.image_error(None, None)):
+        with pytest.raises(_lib.GGNNError, match="enable_polygons"):
+            call()
+
+
+# ---- GPU: the kernels alone, on arenas written by hand -------------------------------------------------------------------
+
+CANVAS = 74   # the shapes below are drawn for the periodic canvas of s = 37 and mapped onto other canvases
+
+
+def regular(n, cx, cy, r, phase=0.3):
+    a = 2 * np.pi * np.arange(n) / n + phase
+    return np.stack([cx + r * np.cos(a), cy + r * np.sin(a)], 1)
+
+
+SHAPES = [   # (the large ones first: where shapes overlap the higher id owns the pixel, and the four quadrants fold onto one)
+    [(3, 2), (20, 5), (8, 17)],                                        # 0  a triangle (the grain a no-flux image skips)
+    [(-3, 66), (74, 64), (74, 70), (-3, 69)],                          # 1  as wide as the canvas: more than one run of 64 pixels
+    [(22, 2), (34, 2), (34, 14), (28, 7), (22, 14), (25, 8)],          # 9  a concave hexagon
+    [(2, 20), (12, 20), (12, 26), (7, 26), (7, 31), (2, 31)],          # 10 horizontal and vertical edges
+    [],                                                                # 11 rows of 0, 1 and 2 junctions
+    [(10, 10)],                                                        # 12
+    [(1, 33), (12, 36)],                                               # 13
+    [(14, 20), (20, 20), (20, 28), (14, 28)],                          # 14 two sharing an edge ...
+    [(20, 20), (27, 20), (27, 28), (20, 28)],                          # 15
+    [(20, 28), (26, 34), (13, 35)],                                    # 16 ... and a third sharing a vertex with both
+    [(33, 10), (41, 12), (39, 19), (31, 16)],                          # 17 straddles x = s
+    [(33, 33), (42, 34), (40, 41), (34, 40)],                          # 18 straddles the corner (s, s)
+    [(70, 50), (74, 52), (74, 74), (66, 60)],                          # 19 vertices at exactly 2 s
+    [(-2, 40), (5, 38), (4, 47), (-1, 45)],                            # 20 slightly negative
+    [(30, 22), (36, 30), (30, 30), (36, 22)],                          # 21 self-crossing
+]
+REGULAR = [(15, 50, 12, 5), (16, 63, 14, 5.5), (17, 52, 30, 6), (63, 14, 56, 7), (64, 44, 58, 8.5), (65, 62, 44, 6.7),
+           (70, 30, 44, 9.3)]                                         # 2 .. 8: (junctions, centre, radius) of regular polygons
+N_ROWS = len(SHAPES) + len(REGULAR)
+UNDRAWN = (11 + 1, 12 + 1)                                             # the ids of the rows of 0 and 1 junction
+
+
+def shape_rows(size, boundary):
+    """The shapes as fp32 unit coordinates for an image of `size`: lattice vertices land where they are drawn."""
+    s = size[0]
+    width, height = (2 * s, 2 * s) if boundary == "periodic" else size
+    rows = []
+    for i, shape in enumerate(SHAPES):
+        if i == 2:
+            for n, cx, cy, r in REGULAR:
+                rows.append((regular(n, cx * width / CANVAS, cy * height / CANVAS, r * min(width, height) / CANVAS) / s)
+                            .astype(np.float32))
+        v = np.array([(x * width // CANVAS, y * height // CANVAS) for x, y in shape], np.int64).reshape(-1, 2)
+        # (truncation toward zero takes (v, v + 1) to v >= 0 and (v - 1, v) to v < 0; rounding takes v + 0.25 to v)
+        xy = ((np.where(v >= 0, v + 0.5, v - 0.5) if boundary == "periodic" else v + 0.25) / s).astype(np.float32)
+        assert np.array_equal(rc.vertex_pixels(xy, s, boundary), v)
+        rows.append(xy)
+    return rows
+
+
+def arena_of(layers, pad=3):
+    """Layers of polygon rows (every layer the same number of rows) in the arena's layout, on the device."""
+    n_grain = len(layers[0])
+    assert all(len(rows) == n_grain for rows in layers)
+    E = max(sum(len(r) for r in rows) for rows in layers) + pad
+    rowptr, xy = np.zeros((len(layers), n_grain + 1), np.int32), np.zeros((len(layers), E, 2), np.float32)
+    for k, rows in enumerate(layers):
+        rowptr[k, 1:] = np.cumsum([len(r) for r in rows])
+        if rowptr[k, -1]:
+            xy[k, :rowptr[k, -1]] = np.concatenate([np.asarray(r, np.float32).reshape(-1, 2) for r in rows])
+    return {"rowptr": torch.from_numpy(rowptr).to(DEV), "xy_sorted": torch.from_numpy(xy).to(DEV)}, rowptr, xy
+
+
+def backend():
+    from graingraphnn_amd.backend import default_backend
+    return default_backend()
+
+
+def assert_images_equal(got, want, what):
+    got = got.cpu().numpy()
+    assert got.dtype == np.int32 and got.shape == want.shape, (what, got.shape, want.shape)
+    bad = np.argwhere(got != want)
+    assert not len(bad), (what, len(bad), [(tuple(b), int(got[tuple(b)]), int(want[tuple(b)])) for b in bad[:8]])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("boundary,size", [("periodic", (37, 37)), ("noflux", (53, 29)), ("periodic", (1, 1)), ("noflux", (1, 1)),
+                                           ("periodic", (64, 64)), ("periodic", (65, 65)), ("noflux", (64, 9)), ("noflux", (65, 9))])
+def test_kernel_against_the_restatement_on_shapes(boundary, size):
+    """Every shape of the list at once (max id where they overlap), the image written over garbage; no-flux also with the
+    corner fill."""
+    rows = shape_rows(size, boundary)
+    arena, rowptr, xy = arena_of([rows])
+    be = backend()
+    shape = (1, size[0], size[0]) if boundary == "periodic" else (1, size[1], size[0])
+    out = torch.full(shape, -5, dtype=torch.int32, device=DEV)
+    got = be.rasterize_polygons(arena, size, None, boundary, out=out)
+    assert got is out
+    want = rc.grain_image(rowptr[0], xy[0], size, boundary)
+    assert_images_equal(got[0], want, (boundary, size))
+    ids = set(np.unique(want).tolist())
+    assert not ids & set(UNDRAWN) and (boundary == "periodic" or 1 not in ids)
+    if size in ((37, 37), (53, 29)):
+        assert ids == set(range(N_ROWS + 1)) - set(UNDRAWN) - ({1} if boundary == "noflux" else set()), ids
+    if boundary == "noflux":
+        corners = (3, 900, 1, 77)
+        got = be.rasterize_polygons(arena, size, [0], boundary, corner_grains=corners)
+        want = rc.grain_image(rowptr[0], xy[0], size, boundary, corner_grains=corners)
+        assert_images_equal(got[0], want, (boundary, size, "corners"))
+        differing, counts = be.image_compare(got, None, N_ROWS)
+        assert differing is None and np.array_equal(counts.cpu().numpy(), rc.compare(want, None, N_ROWS)[1])   # (900 is not counted)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("boundary,size", [("periodic", (37, 37)), ("noflux", (53, 29))])
+def test_kernel_batch_of_layers_with_their_own_tables(boundary, size):
+    """Three layers whose rows differ in length and place, drawn from one call in another order than the arena's."""
+    rows = shape_rows(size, boundary)
+    n = len(rows)
+    second = [rows[(g * 7 + 3) % n] for g in range(n)]
+    third = [rows[g] if g % 3 == 0 else rows[g][:0] for g in range(n)]
+    arena, rowptr, xy = arena_of([rows, second, third])
+    assert len({tuple(r) for r in rowptr.tolist()}) == 3
+    order = [2, 0, 1, 0]
+    got = backend().rasterize_polygons(arena, size, order, boundary)
+    assert got.shape[0] == 4
+    for i, k in enumerate(order):
+        assert_images_equal(got[i], rc.grain_image(rowptr[k], xy[k], size, boundary), (boundary, "layer", k))
+    assert not torch.equal(got[0], got[1]) and torch.equal(got[1], got[3])
+    allrows = backend().rasterize_polygons(arena, size, None, boundary)
+    assert torch.equal(allrows, got[[1, 2, 0]])
+
+
+@pytest.mark.gpu
+def test_kernel_noflux_union_skips_every_boundary_grain():
+    """Two trajectories in one arena: the first grain of each is skipped; grains=(g0, g1) draws one of them with local ids."""
+    size = (53, 29)
+    rows = shape_rows(size, "noflux")
+    off = np.array([0, 9, len(rows)], np.int64)
+    arena, rowptr, xy = arena_of([rows])
+    dev_off = torch.from_numpy(off).to(DEV)
+    be = backend()
+    whole = be.rasterize_polygons(arena, size, None, "noflux", traj_grain_off=dev_off)[0]
+    want = rc.grain_image(rowptr[0], xy[0], size, "noflux", traj_grain_off=off)
+    assert_images_equal(whole, want, "union")
+    assert 10 not in np.unique(want) and 1 not in np.unique(want) and 11 in np.unique(want)
+    assert 10 in np.unique(rc.grain_image(rowptr[0], xy[0], size, "noflux"))   # (a single trajectory draws grain 9)
+    for t in (0, 1):
+        grains = (int(off[t]), int(off[t + 1]))
+        got = be.rasterize_polygons(arena, size, None, "noflux", grains=grains, traj_grain_off=dev_off)[0]
+        want = rc.grain_image(rowptr[0], xy[0], size, "noflux", traj_grain_off=off, grains=grains)
+        assert_images_equal(got, want, ("traj", t))
+        assert want.max() <= grains[1] - grains[0] and want.max() > 1
+
+
+@pytest.mark.gpu
+def test_kernel_clamps_whatever_the_tables_hold():
+    """Row pointers outside the arena, coordinates that are huge, infinite or NaN: the image is the restatement's on the
+    clamped tables, and the guard words round the image stay."""
+    size = (37, 37)
+    rows = shape_rows(size, "periodic")[:8]
+    rows[1] = np.array([[0.2, 0.2], [3e9, 0.3], [0.4, np.inf], [np.nan, 0.9], [-1e30, -7.0]], np.float32)
+    arena, rowptr, xy = arena_of([rows], pad=0)
+    E = xy.shape[1]
+    wild = rowptr.copy()
+    wild[0, 3], wild[0, 6], wild[0, -1] = -4, E + 1000, 2 ** 31 - 1
+    arena["rowptr"] = torch.from_numpy(wild).to(DEV)
+    guarded = torch.full((37 * 37 + 128,), -9, dtype=torch.int32, device=DEV)
+    out = guarded[64:64 + 37 * 37].view(1, 37, 37)
+    backend().rasterize_polygons(arena, size, None, "periodic", out=out)
+    want = np.zeros((37, 37), np.int32)
+    for g in range(len(rows)):   # the kernel's rows: [max(r0, 0), max(r1, p0)) inside [0, E]
+        p0 = int(np.clip(wild[0, g], 0, E))
+        p1 = int(np.clip(max(int(wild[0, g + 1]), p0), 0, E))
+        one = rc.grain_image([0, p1 - p0], xy[0, p0:p1], size)
+        want = np.maximum(want, np.where(one > 0, g + 1, 0).astype(np.int32))
+    assert_images_equal(out[0], want, "clamped")
+    assert bool((guarded[:64] == -9).all()) and bool((guarded[64 + 37 * 37:] == -9).all())
+
+
+@pytest.mark.gpu
+def test_image_compare_counts_exactly():
+    rs = np.random.RandomState(5)
+    be = backend()
+    for n, n_grain in ((1, 3), (1023, 40), (257 * 129, 500), (5000, 12287), (5000, 12288)):   # (12288 ids: the last in LDS)
+        img = rs.randint(0, n_grain + 1, n).astype(np.int32)
+        img[n // 3:n // 2] = 2                                   # a long run
+        truth = np.where(rs.uniform(size=n) < 0.3, rs.randint(0, n_grain + 1, n), img).astype(np.int32)
+        d, c = be.image_compare(torch.from_numpy(img).to(DEV), torch.from_numpy(truth).to(DEV), n_grain)
+        assert int(d) == int((img != truth).sum()) and np.array_equal(c.cpu().numpy(), np.bincount(img, minlength=n_grain + 1))
+        d2, c2 = be.image_compare(torch.from_numpy(img).to(DEV), torch.from_numpy(truth).to(DEV), n_grain, d, c)   # accumulates
+        assert d2 is d and int(d) == 2 * int((img != truth).sum()) and int(c.sum()) == 2 * n
+        assert be.image_compare(torch.from_numpy(img).to(DEV), torch.from_numpy(truth).to(DEV))[1] is None
+
+
+# ---- GPU: rollouts -------------------------------------------------------------------------------------------------------
+
+def restated_layer(ro, size, layer=None, traj=None, corner_grains=None):
+    """The restatement on polygons()'s own record of the layer."""
+    p = ro.polygons(layer, traj)
+    off = None if ro._traj is None else np.asarray(ro._traj["grain"], np.int64)
+    if traj is not None and off is not None:   # a trajectory's slice: its first grain is its boundary grain
+        off = np.array([0, p["rowptr"].numel() - 1], np.int64)
+    return rc.grain_image(p["rowptr"].cpu().numpy(), p["xy_sorted"].cpu().numpy(), size, ro.boundary, traj_grain_off=off,
+                          corner_grains=corner_grains)
+
+
+def assert_error_matches_numpy(ro, img, pde, what):
+    e = ro.image_error(img, torch.from_numpy(pde).to(DEV))
+    host = img.cpu().numpy()
+    differing, counts = rc.compare(host, pde, ro.n_nodes["grain"])
+    assert e["differing"] == differing and e["rate"] == differing / host.size, what
+    assert e["counts"].dtype == torch.int64 and np.array_equal(e["counts"].cpu().numpy(), counts), what
+    only = ro.image_error(img)
+    assert set(only) == {"counts"} and torch.equal(only["counts"], e["counts"]), what
+
+
+@pytest.mark.gpu
+@torch.no_grad()
+def test_golden_states_through_the_rollout():
+    """grain_image of init / step1 / step3 (static steps), mass3 (the eventful step 3) and noflux (layer 0) equals the
+    restatement on the layer's own xy_sorted, and image_error against the reference's alpha_pde equals numpy's."""
+    from test_polygons import cfg1_rollout
+    I = npz("grain_image_cfg1")
+    size = tuple(int(v) for v in I["init__imagesize"])
+    ro, _ = cfg1_rollout(polygons=3)
+    images = {}
+    for layer in range(4):
+        if layer:
+            ro.step()
+        if layer == 2:
+            continue
+        tag = "init" if layer == 0 else f"step{layer}"
+        images[tag] = ro.grain_image(size)
+        assert images[tag].shape == (size[0], size[0]) and images[tag].dtype == torch.int32
+        assert_images_equal(images[tag], restated_layer(ro, size), tag)
+        assert_error_matches_numpy(ro, images[tag], I[tag + "__alpha_pde"].astype(np.int32), tag)
+    assert_images_equal(ro.grain_image(size, layer=0), images["init"].cpu().numpy(), "layer 0 again")
+    assert not torch.equal(images["init"], images["step3"])
+    # layer 0 is the reference's own structure: the image differs from its alpha_field on boundaries only
+    share = float((images["init"].cpu().numpy() != I["init__alpha_field"]).mean())
+    assert share <= 1.25 * MEASURED_SHARE["init"], share
+    with pytest.raises(_lib.GGNNError, match="not been recorded"):
+        cfg1_rollout(polygons=3)[0].grain_image(size, layer=2)
+    with pytest.raises(_lib.GGNNError, match="outside"):
+        ro.grain_images(size, layers=[0, 4])
+
+    mask = {"grain": np.ones((118, 1)), "joint": np.ones((236, 1))}
+    rm, _ = cfg1_rollout(use_graph=True, joint_launches=False, concurrent=True)
+    rm.enable_events(mask, 1e-4, 0.6)
+    for _ in range(3):
+        rm.step_events()
+    img = rm.grain_image(size)
+    assert_images_equal(img, restated_layer(rm, size), "mass3")
+    assert_error_matches_numpy(rm, img, I["mass3__alpha_pde"].astype(np.int32), "mass3")
+    assert int((img == 0).sum()) > 0   # (the eliminated grains leave uncovered pixels, as in the reference's image)
+
+    from test_noflux import fixture
+    from test_noflux_ensemble import F40, nf_graph, nf_rollout
+    d = fixture(F40)
+    corners = tuple(int(c) for c in I["noflux__corner_grains"])
+    rn, _, _ = nf_rollout(d, [nf_graph(d)], False, events=False, union=False)
+    rn.enable_polygons(capacity=0)
+    img = rn.grain_image(size, corner_grains=corners)
+    assert_images_equal(img, restated_layer(rn, size, corner_grains=corners), "noflux")
+    assert_error_matches_numpy(rn, img, I["noflux__alpha_pde"].astype(np.int32), "noflux")
+    assert img.shape == (size[1], size[0]) and int((img == 0).sum()) == 0 and int((img == 1).sum()) == 0
+    bare = rn.grain_image(size)
+    assert int((bare == 0).sum()) > 0 and torch.equal(bare[bare > 0], img[bare > 0])
+    # a union of two: each trajectory's image is its own rollout's, ids local
+    graphs = [nf_graph(d), nf_graph(d, 1000, 2e-3)]
+    ru, _, _ = nf_rollout(d, graphs, False, events=False)
+    ru.enable_polygons(capacity=0)
+    assert torch.equal(ru.grain_image(size, traj=0, corner_grains=corners), img)
+    second = ru.grain_image(size, traj=1)
+    assert_images_equal(second, restated_layer(ru, size, traj=1), "noflux union, trajectory 1")
+    both = ru.grain_image(size).cpu().numpy()
+    n0 = graphs[0][0]["grain"].shape[0]
+    assert_images_equal(ru.grain_image(size), restated_layer(ru, size), "noflux union")
+    assert both.max() > n0 and not (both == n0 + 1).any() and not (both == 1).any()
+
+
+@pytest.mark.gpu
+@torch.no_grad()
+def test_stack_from_a_graph_and_images_between_steps_change_nothing():
+    """grain_images of a 3-step run() from a hipGraph equals the grain_image calls layer by layer; a rollout whose images
+    were taken between its steps ends in the state of one that took none, bit for bit."""
+    from test_polygons import cfg1_rollout
+    size = (61, 61)
+    ro, X = cfg1_rollout(polygons=3, use_graph=True)
+    ro.RUN_UNROLL = 3
+    ro.run(3)
+    stack = ro.grain_images(size)
+    assert stack.shape == (4, 61, 61) and stack.dtype == torch.int32
+    for k in range(4):
+        one = ro.grain_image(size, layer=k)
+        assert torch.equal(stack[k], one), k
+        assert_images_equal(one, restated_layer(ro, size, layer=k), ("layer", k))
+    assert torch.equal(ro.grain_images(size, layers=[3, 1]), stack[[3, 1]])
+    out = torch.empty_like(stack)
+    assert ro.grain_images(size, out=out) is out and torch.equal(out, stack)
+    assert not torch.equal(stack[0], stack[3])
+    between, Xb = cfg1_rollout(polygons=3, use_graph=True)
+    for k in range(3):
+        between.step()
+        assert torch.equal(between.grain_image(size), stack[k + 1]), k
+        between.image_error(stack[k], stack[k + 1])
+    off, Xo = cfg1_rollout(polygons=None, use_graph=True)
+    off.RUN_UNROLL = 3
+    off.run(3)
+    for nt in X:
+        assert torch.equal(X[nt], Xo[nt]) and torch.equal(Xb[nt], Xo[nt]), nt
+    assert torch.equal(between.state()["joint_xy"], off.state()["joint_xy"])
+    assert between.polygons()["layers"] == 3
+    with pytest.raises(_lib.GGNNError, match="enable_polygons"):
+        off.grain_image(size)
