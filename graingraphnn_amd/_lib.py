@@ -27,6 +27,7 @@ GGNN_ETOPOLOGY = -3
 GGNN_FLAG_F16_RANGE = 1
 GGNN_FLAG_QOI_OVERFLOW = 2
 GGNN_FLAG_POLYGON_OVERFLOW = 4
+GGNN_INTERP_MAX_JOBS = 256
 GGNN_ADAM_CHUNK, GGNN_ADAM_MAX_TENSORS, GGNN_ADAM_MAX_GROUPS = 4096, 384, 8
 GGNN_ROWGEMM_MAX_PACK = 8
 GGNN_MSE_MAX_TERMS, GGNN_MSE_BLOCKS = 4, 64
@@ -57,6 +58,7 @@ EXPORTED_SYMBOLS = (
     "ggnn_topology_counts", "ggnn_topology_export", "ggnn_topology_close", "ggnn_step_refresh",
     "ggnn_workspace_bytes",
     "ggnn_qoi_accumulate", "ggnn_qoi_finalize", "ggnn_process_schedule", "ggnn_grain_polygons",
+    "ggnn_polygon_inputs", "ggnn_interp_polygons",
     "ggnn_polygons_rasterize", "ggnn_image_compare",
     "ggnn_metric_record",
     "ggnn_masked_mse_rows", "ggnn_collate_batch", "ggnn_reverse_slots",
@@ -391,6 +393,28 @@ class PolygonArgs(Structure):
     ]
 
 
+class PolygonInputsArgs(Structure):
+    """Mirror of `ggnn_polygon_inputs_args`."""
+    _fields_ = [
+        ("col", c_void_p), ("x_joint", c_void_p), ("domain_offset", c_void_p), ("col_out", c_void_p), ("joint_xy", c_void_p),
+        ("layer_in", c_void_p),
+        ("n_joint", c_int64), ("ldx_joint", c_int64), ("E_cap", c_int64), ("capacity", c_int64),
+        ("domain_factor", c_float),
+    ]
+
+
+class InterpArgs(Structure):
+    """Mirror of `ggnn_interp_args`."""
+    _fields_ = [
+        ("rowptr", c_void_p), ("col", c_void_p), ("joint_xy", c_void_p), ("traj_grain_off", c_void_p), ("job_layer", c_void_p),
+        ("job_coeff", c_void_p), ("work", c_void_p), ("rowptr_out", c_void_p), ("joint_sorted", c_void_p),
+        ("xy_sorted", c_void_p), ("centre", c_void_p), ("area", c_void_p),
+        ("n_joint", c_int64), ("n_grain", c_int64), ("E_cap", c_int64), ("capacity", c_int64), ("layers", c_int64),
+        ("n_traj", c_int64), ("n_jobs", c_int64),
+        ("max_y", c_float), ("boundary", c_int32),
+    ]
+
+
 class RasterArgs(Structure):
     """Mirror of `ggnn_raster_args`."""
     _fields_ = [
@@ -549,6 +573,10 @@ def _declare(lib):
     lib.ggnn_metric_record.argtypes = [POINTER(MetricArgs), c_void_p]
     lib.ggnn_grain_polygons.restype = c_int
     lib.ggnn_grain_polygons.argtypes = [POINTER(PolygonArgs), c_void_p]
+    lib.ggnn_polygon_inputs.restype = c_int
+    lib.ggnn_polygon_inputs.argtypes = [POINTER(PolygonInputsArgs), c_void_p]
+    lib.ggnn_interp_polygons.restype = c_int
+    lib.ggnn_interp_polygons.argtypes = [POINTER(InterpArgs), c_void_p]
     lib.ggnn_polygons_rasterize.restype = c_int
     lib.ggnn_polygons_rasterize.argtypes = [POINTER(RasterArgs), c_void_p]
     lib.ggnn_image_compare.restype = c_int

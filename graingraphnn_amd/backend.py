@@ -1304,6 +1304,106 @@ class HipBackend:
         check(self.lib.ggnn_grain_polygons(ctypes.byref(A), _lib.current_stream()), "ggnn_grain_polygons")
         return arena
 
+    def polygon_inputs_arena(self, n_joint, n_edges, capacity, device):
+        """The two per-layer arrays ggnn_polygon_inputs writes beside a polygon_arena: `col` int32 [capacity + 1, E] and
+        `joint_xy` fp32 [capacity + 1, n_joint, 2].  Zeroed."""
+        L = int(capacity) + 1
+        return {"col": torch.zeros(L, n_edges, dtype=torch.int32, device=device),
+                "joint_xy": torch.zeros(L, n_joint, 2, dtype=torch.float32, device=device)}
+
+    def polygon_inputs(self, csr_jg, x_joint, inputs, domain_factor=1.0, domain_offset=None, layer_in=None):
+        """What a layer's grain_polygons launch reads, kept for interp_polygons (include/ggnn.h, ggnn_polygon_inputs), one
+        launch in front of that launch: row *layer_in + 1 (None: row 0) of `inputs` (a polygon_inputs_arena) receives the
+        table's columns and the junctions in the global frame.  The word is not advanced."""
+        col_out, xy = inputs["col"], inputs["joint_xy"]
+        _require_cuda(x_joint, csr_jg.col, domain_offset, layer_in, col_out, xy)
+        if col_out.dtype != torch.int32 or col_out.dim() != 2 or not col_out.is_contiguous():
+            raise _lib.GGNNError("inputs['col'] must be a contiguous int32 [layers, E]")
+        L, E_cap = col_out.shape
+        n_joint = x_joint.size(0)
+        if xy.dtype != torch.float32 or tuple(xy.shape) != (L, n_joint, 2) or not xy.is_contiguous():
+            raise _lib.GGNNError(f"inputs['joint_xy'] must be a contiguous float32 tensor of shape ({L}, {n_joint}, 2)")
+        if L < 1 or csr_jg.col.dtype != torch.int32 or csr_jg.col.numel() < E_cap:
+            raise _lib.GGNNError("the inputs have more entries per layer than the joint->grain table")
+        if x_joint.dtype != torch.float32 or x_joint.dim() != 2 or x_joint.stride(1) != 1:
+            raise _lib.GGNNError("x_joint must be float32 [n_joint, >= 2] with unit column stride")
+        if domain_offset is not None:
+            _f32c(domain_offset, "domain_offset")
+            if tuple(domain_offset.shape) != (n_joint, 2):
+                raise _lib.GGNNError("domain_offset must be [n_joint, 2]")
+        elif domain_factor > 1:
+            raise _lib.GGNNError("domain_factor > 1 needs the domain_offset of scale_feature_patchs")
+        if layer_in is not None and (layer_in.dtype != torch.int32 or layer_in.numel() < 1):
+            raise _lib.GGNNError("layer_in must be an int32 word")
+        A = _lib.PolygonInputsArgs()
+        A.col, A.x_joint, A.domain_offset, A.col_out = ptr(csr_jg.col), ptr(x_joint), ptr(domain_offset), ptr(col_out)
+        A.joint_xy, A.layer_in = ptr(xy), ptr(layer_in)
+        A.n_joint, A.ldx_joint, A.E_cap, A.capacity, A.domain_factor = n_joint, x_joint.stride(0), E_cap, L - 1, float(domain_factor)
+        check(self.lib.ggnn_polygon_inputs(ctypes.byref(A), _lib.current_stream()), "ggnn_polygon_inputs")
+        return inputs
+
+    def interp_polygons(self, arena, inputs, jobs, layers, boundary="periodic", max_y=1.0, traj_grain_off=None, out=None):
+        """Polygon records of in-between layers (include/ggnn.h, ggnn_interp_polygons): jobs = [(layer L, coefficient c)],
+        each blended from rows L - 1 and L of `inputs` (a polygon_inputs_arena) with the table of the nearer layer
+        (`arena`'s rowptr, `inputs`' col).  layers: the number of layers recorded (1 <= L <= layers).  Returns a
+        polygon_arena of len(jobs) rows (`out`: the one to fill), which rasterize_polygons reads as it reads the recorder's;
+        two or three launches per GGNN_INTERP_MAX_JOBS jobs."""
+        bc = _boundary_code(boundary)
+        rowptr, col, xy = arena["rowptr"], inputs["col"], inputs["joint_xy"]
+        _require_cuda(rowptr, col, xy, traj_grain_off)
+        if rowptr.dtype != torch.int32 or rowptr.dim() != 2 or rowptr.size(1) < 2 or not rowptr.is_contiguous():
+            raise _lib.GGNNError("arena['rowptr'] must be a contiguous int32 [layers, n_grain + 1]")
+        L_cap, n_grain = rowptr.size(0), rowptr.size(1) - 1
+        if col.dtype != torch.int32 or col.dim() != 2 or col.size(0) != L_cap or not col.is_contiguous():
+            raise _lib.GGNNError(f"inputs['col'] must be a contiguous int32 [{L_cap}, E]")
+        if xy.dtype != torch.float32 or xy.dim() != 3 or xy.size(0) != L_cap or xy.size(1) < 1 or xy.size(2) != 2 \
+                or not xy.is_contiguous():
+            raise _lib.GGNNError(f"inputs['joint_xy'] must be a contiguous float32 [{L_cap}, n_joint, 2]")
+        E_cap, n_joint = col.size(1), xy.size(1)
+        try:
+            jobs = [(int(k), float(c)) for k, c in jobs]
+        except (TypeError, ValueError):
+            raise _lib.GGNNError("jobs must be (layer, coefficient) pairs") from None
+        layers = int(layers)
+        if not jobs:
+            raise _lib.GGNNError("interp_polygons needs at least one job")
+        if not 1 <= layers <= L_cap - 1:
+            raise _lib.GGNNError(f"{layers} recorded layers: an in-between layer needs two of the arena's {L_cap}")
+        for k, c in jobs:
+            if not 1 <= k <= layers:
+                raise _lib.GGNNError(f"a job's layer must lie in 1..{layers}, got {k}")
+            if not 0.0 <= c <= 1.0:
+                raise _lib.GGNNError(f"a job's coefficient must lie in [0, 1], got {c}")
+        n_traj = 1
+        if traj_grain_off is not None:
+            if traj_grain_off.dtype != torch.int64 or traj_grain_off.numel() < 2 or not traj_grain_off.is_contiguous():
+                raise _lib.GGNNError("traj_grain_off must be a contiguous int64 [n_traj + 1]")
+            n_traj = traj_grain_off.numel() - 1
+        dev = rowptr.device
+        if out is None:
+            out = self.polygon_arena(n_grain, E_cap, len(jobs) - 1, dev)
+        _require_cuda(*out.values())
+        for name, dtype, shape in (("rowptr", torch.int32, (len(jobs), n_grain + 1)), ("joint_sorted", torch.int32, (len(jobs), E_cap)),
+                                   ("xy_sorted", torch.float32, (len(jobs), E_cap, 2)), ("centre", torch.float32, (len(jobs), n_grain, 2)),
+                                   ("area", torch.float32, (len(jobs), n_grain))):
+            t = out[name]
+            if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+                raise _lib.GGNNError(f"out[{name!r}] must be a contiguous {dtype} tensor of shape {shape}")
+        work = torch.empty(min(len(jobs), _lib.GGNN_INTERP_MAX_JOBS), n_joint, 2, dtype=torch.float32, device=dev)
+        for first in range(0, len(jobs), _lib.GGNN_INTERP_MAX_JOBS):
+            part = jobs[first:first + _lib.GGNN_INTERP_MAX_JOBS]
+            host_layer = (ctypes.c_int32 * len(part))(*[k for k, _ in part])
+            host_coeff = (ctypes.c_double * len(part))(*[c for _, c in part])
+            A = _lib.InterpArgs()
+            A.rowptr, A.col, A.joint_xy, A.traj_grain_off, A.work = ptr(rowptr), ptr(col), ptr(xy), ptr(traj_grain_off), ptr(work)
+            A.job_layer, A.job_coeff = ctypes.cast(host_layer, ctypes.c_void_p), ctypes.cast(host_coeff, ctypes.c_void_p)
+            A.rowptr_out, A.joint_sorted = ptr(out["rowptr"][first:]), ptr(out["joint_sorted"][first:])
+            A.xy_sorted, A.centre, A.area = ptr(out["xy_sorted"][first:]), ptr(out["centre"][first:]), ptr(out["area"][first:])
+            A.n_joint, A.n_grain, A.E_cap, A.capacity, A.layers = n_joint, n_grain, E_cap, L_cap - 1, layers
+            A.n_traj, A.n_jobs, A.max_y, A.boundary = n_traj, len(part), float(max_y), bc
+            check(self.lib.ggnn_interp_polygons(ctypes.byref(A), _lib.current_stream()), "ggnn_interp_polygons")
+        return out
+
     def rasterize_polygons(self, arena, size, layers=None, boundary="periodic", grains=None, traj_grain_off=None,
                            corner_grains=None, out=None):
         """The grain-ID images of arena rows (include/ggnn.h, ggnn_polygons_rasterize): int32 [L, ny, nx] (periodic: [L, nx,

@@ -147,7 +147,7 @@ def rollout_trajectories(rmodel, cmodel, graphs, span: int, n_steps: int, rank: 
                          world: int = 1, device="cuda", use_graph: bool = True,
                          refresh_centres: bool = False, qoi=None, events=None, boundary: str = "periodic",
                          max_y: float = 1.0, domain_factor: float = 1.0, domain_offsets=None, schedule=None,
-                         polygons=False):
+                         polygons=False, positions=False):
     """BASELINE config 4: `graphs[t]` = (x, ei, ea) numpy dicts of independent trajectories with
     EQUAL node counts.  Rank r rolls out trajectories t = r (mod world) as ONE disjoint-union
     graph on its GPU (one set of launches for the whole shard), then all ranks all-gather the
@@ -172,7 +172,9 @@ def rollout_trajectories(rmodel, cmodel, graphs, span: int, n_steps: int, rank: 
     `polygons`: True (or the capacity in layers, default n_steps) records every layer's grain polygons on the device
     (GrainRollout.enable_polygons).  The records stay on the rank that made them -- nothing of them is gathered: the result
     gets 'polygons' = {'trajectories': the rank's own trajectory indices, 'last': per own trajectory the last layer's record
-    (GrainRollout.polygons(traj=i)), 'at': the rollout's polygons method, for the other layers}."""
+    (GrainRollout.polygons(traj=i)), 'at': the rollout's polygons method, for the other layers}.  `positions` (with
+    `polygons`): also keep every layer's table columns and junction positions (enable_polygons(positions=True)); the
+    result's 'polygons' gains 'interp' (GrainRollout.interp_polygons) and 'volume' (GrainRollout.grain_volume)."""
     from . import synthetic
     from .rollout import GrainRollout
 
@@ -203,7 +205,8 @@ def rollout_trajectories(rmodel, cmodel, graphs, span: int, n_steps: int, rank: 
     if qoi is not None:
         ro.enable_qoi(**dict(qoi, traj_offsets=None if noflux else offsets["grain"]))
     if polygons:
-        ro.enable_polygons(capacity=n_steps if polygons is True else int(polygons), traj_offsets=None if noflux else offsets)
+        ro.enable_polygons(capacity=n_steps if polygons is True else int(polygons), traj_offsets=None if noflux else offsets,
+                           positions=bool(positions))
     if schedule is not None:
         # [T, n_rows, ...] of the ensemble -> [n_rows, the shard's trajectories, ...]
         take = lambda a: np.moveaxis(np.asarray(a)[mine], 0, 1)
@@ -245,4 +248,6 @@ def rollout_trajectories(rmodel, cmodel, graphs, span: int, n_steps: int, rank: 
     if polygons:
         out["polygons"] = {"trajectories": list(mine), "last": [ro.polygons(traj=i) for i in range(len(mine))],
                            "at": ro.polygons}
+        if positions:
+            out["polygons"].update(interp=ro.interp_polygons, volume=ro.grain_volume)
     return out

@@ -611,7 +611,7 @@ class GrainRollout:
                                Q["area_sum"], init=init, area0=area0)
 
     # -- the layers' grain polygons (graph.update(), graph_datastruct.py:654-721) ---------------------------
-    def enable_polygons(self, capacity=None, traj_offsets=None):
+    def enable_polygons(self, capacity=None, traj_offsets=None, positions=False):
         """Record, from now on and on the device, every layer's grain polygons: what the reference's rollout leaves in
         traj.regions / region_coors / region_center after traj.GNN_update (test.py:468-478) -- per grain the junctions of its
         row of the joint->grain table, unwrapped, ordered counter-clockwise round their mean, with the mean and the shoelace
@@ -621,7 +621,11 @@ class GrainRollout:
         capacity: the number of layers the arena has room for beyond layer 0 (default: enable_qoi's, when it was called
         before; otherwise required).  The arena's rows have the size of the table as it is now: eliminations only shrink it.
         traj_offsets: {'grain': [n_traj + 1], 'joint': [n_traj + 1]} of a disjoint-union graph, for polygons(traj=t)
-        (default: the constructor's of a no-flux union, or enable_events')."""
+        (default: the constructor's of a no-flux union, or enable_events').
+        positions: also keep what every layer's launch read -- the table's columns and the junctions in the global frame
+        (ggnn_polygon_inputs, one more launch per step in front of the polygon launch) -- which interp_polygons and
+        grain_volume(interp_frames > 0) blend between layers.  Off: the step's launches are what they are
+        without it."""
         if capacity is None:
             if self._qoi is None:
                 raise _lib.GGNNError("enable_polygons: capacity (the number of steps to record) is required unless enable_qoi "
@@ -639,6 +643,8 @@ class GrainRollout:
         self._poly = {
             "name": "poly", "new": self._poly_state, "capacity": int(capacity), "offsets": offsets,
             "arena": self.be.polygon_arena(ng, int(self.graph.edge_index[JG].size(1)), int(capacity), dev),
+            "inputs": self.be.polygon_inputs_arena(self.n_nodes["joint"], int(self.graph.edge_index[JG].size(1)), int(capacity),
+                                                   dev) if positions else None,
             "home": self._poly_state(), "words": torch.zeros(2, dtype=torch.int32, device=dev),
             "ring": None, "entries": None, "launched": 0, "at": None}
         self._invalidate_graphs(static=True, segments=True, blocks=True)   # (graphs captured so far lack the launch)
@@ -661,6 +667,9 @@ class GrainRollout:
         src = dst = P["home"]
         if slot is not None:
             src, dst = P["ring"][(slot - 1) % len(P["ring"])], P["ring"][slot]
+        if P.get("inputs") is not None:   # (the same word, read before the polygon launch advances it)
+            self.be.polygon_inputs(self.graph.csr_full[JG], self.x["joint"], P["inputs"], self.domain_factor,
+                                   self.domain_offset, layer_in=None if init else src["layer"])
         self.be.grain_polygons(self.graph.csr_full[JG], self.x["joint"], P["arena"], self.domain_factor, self.domain_offset,
                                boundary=self.boundary, traj_grain_off=self._traj_grain_dev(),
                                layer_in=None if init else src["layer"], layer_out=dst["layer"], sync_word=P["words"][:1],
@@ -685,14 +694,16 @@ class GrainRollout:
         coordinates), `centre` fp32 [n, 2] (unfolded), `area` fp32 [n] (shoelace, negative for a reversed grain); and
         `layer`, `layers` (steps recorded).  traj=t (a union with known offsets): that trajectory's grains alone, rowptr
         from 0 and junction ids local to the trajectory.  With enable_events(traj_offsets=...) `layers` is an array without
-        `traj`, and a trajectory that ended (trajectory_states) reports the layers up to its last completed step.  Raises
+        `traj`, and a trajectory that ended (trajectory_states) reports the layers up to its last completed step.  With
+        enable_polygons(positions=True) also `col` int32 [E] (the table's columns as the layer's launch read them, local with
+        traj=t) and `joint_xy` fp32 [n_joint, 2] (the junctions in the global frame; traj=t: the trajectory's).  Raises
         when a layer went beyond the capacity, or `layer` was not recorded."""
         P = self._poly
         if P is None:
             raise _lib.GGNNError("call enable_polygons(...) first")
         self._carry_home()
         A, ng, cap = P["arena"], self.n_nodes["grain"], P["capacity"]
-        g0, g1, j0 = 0, ng, 0
+        g0, g1, j0, j1 = 0, ng, 0, self.n_nodes["joint"]
         if traj is not None:
             off = self._polygon_offsets()
             if off is None:
@@ -700,7 +711,7 @@ class GrainRollout:
             t = int(traj)
             if not 0 <= t < len(off[0]) - 1:
                 raise _lib.GGNNError(f"no trajectory {traj}: the union has {len(off[0]) - 1}")
-            g0, g1, j0 = int(off[0][t]), int(off[0][t + 1]), int(off[1][t])
+            g0, g1, j0, j1 = int(off[0][t]), int(off[0][t + 1]), int(off[1][t]), int(off[1][t + 1])
         ended = []   # (trajectory, the layer word of its last completed step)
         if self._ens is not None:
             ended = [(t_, sn["poly_layer"]) for t_, sn in enumerate(self._ens["snapshot"])
@@ -726,12 +737,97 @@ class GrainRollout:
                "joint_sorted": A["joint_sorted"][k, e0:e1] - j0, "xy_sorted": A["xy_sorted"][k, e0:e1],
                "centre": A["centre"][k, g0:g1], "area": A["area"][k, g0:g1]}
         res["sides"] = res["rowptr"][1:] - res["rowptr"][:-1]
+        if P.get("inputs") is not None:
+            res["col"], res["joint_xy"] = P["inputs"]["col"][k, e0:e1] - j0, P["inputs"]["joint_xy"][k, j0:j1]
         if self._ens is not None and traj is None:   # per trajectory of the event layer: an ended one stopped counting
             per = np.full(self._ens["n_traj"], layers, dtype=np.int64)
             for i, (t_, _) in enumerate(ended):
                 per[t_] = words[6 + i]
             res["layers"] = per
         return res
+
+    # -- in-between layers and the 3-D volume (test.py:494-528, pv_3Dview.py:150-192) ---------------------------
+    def _interp_arena(self, jobs, traj):
+        """The records of `jobs` = [(layer, coefficient)] as a polygon arena of len(jobs) rows (one synchronisation: the
+        layers recorded so far, of `traj` where it ended early)."""
+        recorded = int(np.max(self.polygons(None, traj)["layers"]))
+        P = self._poly
+        if P.get("inputs") is None:
+            raise _lib.GGNNError("in-between layers need the recorded positions: enable_polygons(..., positions=True)")
+        if recorded < 1:
+            raise _lib.GGNNError("an in-between layer needs two recorded layers: take a step first")
+        return self.be.interp_polygons(P["arena"], P["inputs"], jobs, recorded, self.boundary, self.max_y,
+                                       self._traj_grain_dev())
+
+    def interp_polygons(self, layer, coeff, traj=None):
+        """The polygon record of the in-between layer coeff * layer + (1 - coeff) * (layer - 1), as the reference's
+        --interp_frames builds it (test.py:494-528): junction positions blended, the topology of the nearer layer (`layer`'s
+        for coeff > 0.5), no-flux junctions of the boundary grain moved to the nearest wall and all clamped to the box; then
+        the rule of polygons() (include/ggnn.h, ggnn_interp_polygons).  Periodic positions are blended along the short way
+        across the walls and are not snapped.  Returns the dict polygons() returns (`layer`: the layer whose topology it
+        has; no `col` / `joint_xy`).  Needs enable_polygons(positions=True).  On demand, on the current stream."""
+        whole = self.polygons(None, traj)
+        arena = self._interp_arena([(layer, coeff)], traj)
+        top = int(layer) if float(coeff) > 0.5 else int(layer) - 1
+        g0, g1, j0 = 0, self.n_nodes["grain"], 0
+        if traj is not None:
+            off = self._polygon_offsets()
+            g0, g1, j0 = int(off[0][int(traj)]), int(off[0][int(traj) + 1]), int(off[1][int(traj)])
+        e0, e1 = (int(v) for v in arena["rowptr"][0, [g0, g1]].cpu())
+        res = {"layer": top, "layers": whole["layers"], "rowptr": arena["rowptr"][0, g0:g1 + 1] - e0,
+               "joint_sorted": arena["joint_sorted"][0, e0:e1] - j0, "xy_sorted": arena["xy_sorted"][0, e0:e1],
+               "centre": arena["centre"][0, g0:g1], "area": arena["area"][0, g0:g1]}
+        res["sides"] = res["rowptr"][1:] - res["rowptr"][:-1]
+        return res
+
+    def grain_volume(self, size, interp_frames=0, layers=None, traj=None, corner_grains=None, out=None):
+        """The 3-D grain-ID volume of the rollout, int32 [nz, ny, nx] on the device: the reference's `alpha_field_list`
+        stacked (pv_3Dview.py:150-192) -- layer 0, then for every later layer its `interp_frames` in-between images with
+        coefficient (1 + i) / (1 + interp_frames), i = 0 .., then the layer's own (test.py:494-528).  In C order this is
+        np.stack(alpha_field_list, axis=2).ravel(order='F'): vtkio.write_vtk needs no transpose.  layers: the recorded
+        layers to take (default: all; in-between frames lie between a layer and the recorded one before it).  One
+        interpolation call and one rasteriser launch per 256 images; interp_frames=0 is grain_images(size, layers)."""
+        k_in = int(interp_frames)
+        if k_in < 0:
+            raise _lib.GGNNError("interp_frames must not be negative")
+        if k_in == 0:
+            return self.grain_images(size, layers, traj, corner_grains, out)
+        if self._poly is not None and self._poly.get("inputs") is None:
+            raise _lib.GGNNError("in-between layers need the recorded positions: enable_polygons(..., positions=True)")
+        recorded = int(np.max(self.polygons(None, traj)["layers"]))
+        layers = list(range(recorded + 1)) if layers is None else [int(k) for k in layers]
+        for k in layers:
+            if not 0 <= k <= recorded:
+                raise _lib.GGNNError(f"layer {k} has not been recorded: {recorded} layers so far")
+        jobs, rows = [], []   # rows: (is a job, its index) in the volume's order
+        for k in layers:
+            if k > 0:
+                for i in range(k_in):
+                    rows.append((True, len(jobs)))
+                    jobs.append((k, (1 + i) / (1 + k_in)))
+            rows.append((False, k))
+        if not jobs:
+            return self.grain_images(size, layers, traj, corner_grains, out)
+        made, A = self._interp_arena(jobs, traj), self._poly["arena"]
+        # one arena for the rasteriser: the interpolated rows, then the recorded ones that are drawn
+        kept = sorted({k for is_job, k in rows if not is_job})
+        at = {k: len(jobs) + i for i, k in enumerate(kept)}
+        idx = torch.tensor(kept, device=A["rowptr"].device)
+        both = {name: torch.cat([made[name], A[name].index_select(0, idx)]) for name in ("rowptr", "xy_sorted")}
+        order = [i if is_job else at[i] for is_job, i in rows]
+        return self.be.rasterize_polygons(both, size, order, self.boundary, self._raster_range(traj), self._traj_grain_dev(),
+                                          corner_grains, out)
+
+    @staticmethod
+    def orientation_volume(volume, theta_z):
+        """Grain ids -> misorientation angles in degrees, float32 with the volume's shape: the reference's
+        theta_z[ids] / pi * 180 (pv_3Dview.py:150-192).  theta_z: [n_grain + 1] radians with entry 0 for uncovered pixels
+        (traj.theta_z).  The table is formed in float64 on the host and rounded once; one gather on the device."""
+        table = np.asarray(theta_z.detach().cpu().numpy() if torch.is_tensor(theta_z) else theta_z, np.float64).ravel()
+        table = torch.from_numpy((table / np.pi * 180).astype(np.float32)).to(volume.device)
+        if volume.numel() and not 0 <= int(volume.min()) <= int(volume.max()) < table.numel():
+            raise _lib.GGNNError(f"the volume holds ids outside theta_z's 0..{table.numel() - 1}")
+        return table[volume.long()]
 
     # -- the layers' grain-ID images (plot_polygons, graph_datastruct.py:553-610; DESIGN.md 8h) ------------------------------
     def _raster_range(self, traj):

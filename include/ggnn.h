@@ -828,6 +828,78 @@ typedef struct ggnn_polygon_args {
   int32_t boundary;                /* GGNN_BC_PERIODIC / GGNN_BC_NOFLUX */
 } ggnn_polygon_args;
 int ggnn_grain_polygons(const ggnn_polygon_args* args, ggnn_stream_t stream);
+/* ggnn_polygon_inputs = what a layer's ggnn_grain_polygons launch reads, kept beside its record so that two layers can be
+ * blended afterwards (ggnn_interp_polygons): one launch IN FRONT of that launch, on the same stream, writes row
+ * k = *layer_in + 1 (NULL: k = 0) -- the word the polygon launch reads; this launch does not advance it -- of
+ *   col_out  [capacity + 1, E_cap]      : col[0 .. E_cap) as it is (the polygon launch clamps what it reads, so do the readers),
+ *   joint_xy [capacity + 1, n_joint, 2] : the junctions in the global frame, the expression ggnn_grain_polygons unwraps from
+ *                                         ((x + domain_offset[j]) / domain_factor when domain_factor > 1).
+ * A layer outside [0, capacity] writes nothing (the polygon launch raises GGNN_FLAG_POLYGON_OVERFLOW).  Plain loads and
+ * stores.  GGNN_EINVAL: a NULL col / x_joint / col_out / joint_xy, n_joint < 1, ldx_joint < 2, E_cap or capacity outside
+ * [0, INT32_MAX), domain_factor < 1. */
+typedef struct ggnn_polygon_inputs_args {
+  const int32_t* col;              /* [>= E_cap] */
+  const float* x_joint;            /* [n_joint, ldx_joint >= 2] */
+  const float* domain_offset;      /* NULL (= 0) or [n_joint, 2] */
+  int32_t* col_out;                /* [capacity + 1, E_cap] */
+  float* joint_xy;                 /* [capacity + 1, n_joint, 2] */
+  const int32_t* layer_in;         /* NULL (layer 0) or k - 1 */
+  int64_t n_joint, ldx_joint, E_cap, capacity;
+  float domain_factor;
+} ggnn_polygon_inputs_args;
+int ggnn_polygon_inputs(const ggnn_polygon_inputs_args* args, ggnn_stream_t stream);
+/* --- In-between layers of a rollout (test.py:494-528, --interp_frames) ---
+ * ggnn_interp_polygons = n_jobs <= GGNN_INTERP_MAX_JOBS polygon records blended from recorded layers, the job a grid
+ * dimension; on demand, on `stream`; it only reads the recorder's arrays (rowptr of ggnn_grain_polygons, col_out / joint_xy
+ * of ggnn_polygon_inputs).  Job i = (layer L = job_layer[i] in [1, layers], coefficient c = job_coeff[i] in [0, 1]), HOST
+ * arrays; row i of the outputs -- the layout of ggnn_grain_polygons' five arrays with capacity + 1 = n_jobs, which
+ * ggnn_polygons_rasterize reads unchanged.  The rule (tests/interpcheck.py restates it), all of it in fp32, every operation
+ * rounded on its own:
+ *   topology : layer T = L where c > 0.5 (compared in double), else L - 1 (test.py:502-514); the job's rowptr and col are
+ *              layer T's recorded ones, O is the other layer of the two.
+ *   seam     : GGNN_BC_PERIODIC: per junction and coordinate layer O's value is brought to the minimum image of layer T's:
+ *              o += rel > 0.5 ? -1 : (rel < -0.5 ? 1 : 0) with rel = o - t.
+ *   blend    : v = fl(fl(c) * X_L) + fl(fl(1 - c) * X_{L-1}); 1 - c is formed in double and rounded once.
+ *   wrap     : GGNN_BC_PERIODIC: v -= floorf(v) where v is not in [0, 1) although layer T's coordinate is.  (Recorded
+ *              junctions are never wrapped and a few lie below 0; next to such a coordinate v stays where the blend put it,
+ *              so that the endpoints below hold for every recorded layer.)
+ *   no-flux  : GGNN_BC_NOFLUX, move_to_boundary and the clamps (test.py:58-70, 502-508): every junction of the boundary
+ *              grain's row of layer T's table (grain 0, or with traj_grain_off the first grain of every trajectory that has
+ *              grains) takes d = {x, 1 - x, y, max_y - y} of the UNCLAMPED blend, the FIRST minimum decides, and that
+ *              coordinate becomes 0, 1, 0 or max_y; every other coordinate of every junction is clamped to [0, 1] x
+ *              [0, max_y].  The positions are finished per junction in `work` before any row reads them, so a snapped
+ *              junction is seen snapped by every grain that holds it.  Periodic jobs neither snap nor clamp (there grain 0
+ *              is an ordinary grain).
+ *   rows     : ggnn_grain_polygons' rule on those positions with layer T's table, domain_factor 1: the same device code.
+ * (L, 1.0) reproduces layer L's record and (L, 0.0) layer L - 1's (joint_sorted, xy_sorted as numbers, centre): always
+ * (periodic), wherever the recorded junctions lie inside the box with the boundary grain's on the walls, as the step's
+ * boundary launch leaves them (no-flux).
+ * Launches: blend (one thread per junction and job), GGNN_BC_NOFLUX: snap (one block per trajectory and job; it forms the
+ * blend of its junctions again and overwrites the snapped coordinate), rows -- two or three, whatever n_jobs is.
+ * Table entries and layers are clamped: nothing outside the arrays is addressed, whatever they hold.
+ * GGNN_EINVAL without a launch: args or a pointer other than traj_grain_off NULL, no such boundary, n_joint / n_grain < 1,
+ * E_cap or capacity outside [0, INT32_MAX), layers outside [1, capacity], n_jobs outside [1, GGNN_INTERP_MAX_JOBS], a job with
+ * a layer outside [1, layers] or c outside [0, 1] (NaN included), GGNN_BC_NOFLUX without max_y > 0, traj_grain_off with
+ * n_traj < 1 (without: n_traj != 1). */
+#define GGNN_INTERP_MAX_JOBS 256
+typedef struct ggnn_interp_args {
+  const int32_t* rowptr;           /* [capacity + 1, n_grain + 1], device: the recorder's */
+  const int32_t* col;              /* [capacity + 1, E_cap], device: ggnn_polygon_inputs' col_out */
+  const float* joint_xy;           /* [capacity + 1, n_joint, 2], device: ggnn_polygon_inputs' */
+  const int64_t* traj_grain_off;   /* NULL or [n_traj + 1], device (GGNN_BC_NOFLUX) */
+  const int32_t* job_layer;        /* HOST [n_jobs] */
+  const double* job_coeff;         /* HOST [n_jobs] */
+  float* work;                     /* [n_jobs, n_joint, 2], device: the finished positions */
+  int32_t* rowptr_out;             /* [n_jobs, n_grain + 1] */
+  int32_t* joint_sorted;           /* [n_jobs, E_cap] */
+  float* xy_sorted;                /* [n_jobs, E_cap, 2] */
+  float* centre;                   /* [n_jobs, n_grain, 2] */
+  float* area;                     /* [n_jobs, n_grain] */
+  int64_t n_joint, n_grain, E_cap, capacity, layers, n_traj, n_jobs;
+  float max_y;
+  int32_t boundary;                /* GGNN_BC_PERIODIC / GGNN_BC_NOFLUX */
+} ggnn_interp_args;
+int ggnn_interp_polygons(const ggnn_interp_args* args, ggnn_stream_t stream);
 /* --- The grain-ID image of recorded layers (plot_polygons, graph_datastruct.py:553-610: `alpha_field`) ---
  * ggnn_polygons_rasterize = n_layers rows of ggnn_grain_polygons' arena filled into image [n_layers, ny, nx] int32 (periodic:
  * [n_layers, nx, nx]), indexed [y][x]; the call zeroes the image itself, then ONE launch takes up to GGNN_RASTER_MAX_LAYERS
