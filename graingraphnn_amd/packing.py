@@ -23,12 +23,18 @@ Layouts (C = 96, G = number of gates, F = features of the node type, Fp = roundu
 * edge parameters of an edge type, `EP [G][3][96]`: W_value[:, 0..2].
 * gate weight of node type T, `W2 [G][96][Ka]`, Ka = roundup4(98 * n_in):
       [lin_l2.weight of incoming edge type 0 | ... | (b_l2, w_edge) of type 0 | ...]
+  (training: zero columns up to the aggregate's gate stride Kg; a node type nothing flows into: [G][96][4] zeros)
+
+`assemble` below is the executable form of this layout for both paths: pack_cell runs it on the parameter values
+(inference), train_pack on the values with autograd and on index tensors (the tables of the device packer).
 """
 import math
 from dataclasses import dataclass, field
 from typing import Dict, List, Tuple
 
 import torch
+
+from ._lib import GGNNError
 
 C = 96
 NODE_TYPES = ("grain", "joint")
@@ -402,6 +408,90 @@ def padded_cell(cell, c: int):
     return out
 
 
+# The parameters of a PeriodConv that a cell's forward reads: (short name, Linear, weight / bias)
+_KINDS = (("wq", "lin_query", "weight"), ("bq", "lin_query", "bias"), ("wk", "lin_key", "weight"),
+          ("bk", "lin_key", "bias"), ("wv", "lin_value", "weight"), ("bv", "lin_value", "bias"),
+          ("ws", "lin_skip", "weight"), ("bs", "lin_skip", "bias"), ("wl", "lin_l2", "weight"),
+          ("bl", "lin_l2", "bias"), ("we", "lin_edge", "weight"))
+
+
+@torch.no_grad()
+def score_block(conv, F_src: int, F_dst: int, k2: int) -> torch.Tensor:
+    """Every key-free score coefficient of one PeriodConv, float64 [F_src + k2 + 2, F_dst + k2 + 1] (module docstring):
+    rows = the components of u (source features, then the k2 hidden channels), then s1, s2; columns = what they multiply
+    in the destination's [x | h], the last one the constant term.  k2 == 0 (encoder): both sides see the bare feature row.
+    Six separate products: the callers round each entry to fp32 once."""
+    scale = 1.0 / math.sqrt(C)  # periodGATconv.py:226
+    wq, bq = conv.lin_query.weight.detach().double(), conv.lin_query.bias.detach().double()
+    wk, bk = conv.lin_key.weight.detach().double(), conv.lin_key.bias.detach().double()
+    we = conv.lin_edge.weight.detach().double()[:, 0]
+    if not k2:
+        wq, wk = wq[:, :F_dst], wk[:, :F_src]
+    M, mb = (wk.t() @ wq) * scale, (wk.t() @ bq) * scale         # [Fs (+96), Fd (+96)], [Fs (+96)]
+    s1_w, s1_b = (bk @ wq) * scale, (bk @ bq) * scale
+    s2_w, s2_b = (we @ wq) * scale, (we @ bq) * scale
+    return torch.cat([torch.cat([M, s1_w.unsqueeze(0), s2_w.unsqueeze(0)]),
+                      torch.cat([mb, s1_b.view(1), s2_b.view(1)]).unsqueeze(1)], 1)
+
+
+def assemble(get, get_s, mr, zeros, sum_of, F, G, sees_h, live=NODE_TYPES, with_values=True,
+             w2_width=lambda lay: lay.Kg, edge_types=EDGE_TYPES):
+    """The layout, on values or on indices (so: only cat, slicing, reshape, transpose, unsqueeze and the caller's
+    zeros / sum_of).  get(et, kind): stacked parameters [G, *shape] (`_KINDS`) that are the single source of an entry;
+    get_s(et, kind) / get_s("b", nt): the same for the terms of a sum; mr(et): the score coefficients
+    [G, Fs + k2 + 2, Fd + k2 + 1] (score_block per gate); zeros(*shape); sum_of(list): elementwise sum, in list order
+    from 0 (HeteroConv aggr='sum').  live / with_values: see node_layout; w2_width(lay): columns of w2 (the defaults are
+    the training path's: everything live, the aggregate's gate stride).  Every block is laid at the row node_layout
+    names for it, or this raises.
+    -> (layout, {nt: W [ncols, Fp + k2]}, {nt: b [ncols]}, {et into a live type: ep [G, 3, 96]}, {nt: w2 [G, 96, width]})."""
+    k2 = C if sees_h else 0
+    layout, wp, bp, ep, w2 = {}, {}, {}, {}, {}
+    for nt in NODE_TYPES:
+        lay = node_layout(nt, F[nt], G, edge_types, nt in live, sees_h, with_values, tuple(live))
+        Fn, Fp, D = F[nt], lay.Fp, F[nt] + k2
+        blocks, at = [], 0                                           # rows of [W | b]: [n, D + 1]
+
+        def lay_at(off, what, block):
+            nonlocal at
+            if at != off:
+                raise GGNNError(f"packed layout of '{nt}': {what} at row {at}, node_layout says {off}")
+            if block is not None:
+                blocks.append(block)
+                at += block.size(0)
+        for et in lay.src_ets if with_values else ():                # value rows, relocation columns zeroed
+            wvr = get(et, "wv")[:, :, 3:D]
+            lay_at(lay.v_off[et], f"values of {et_key(et)}",
+                   torch.cat([zeros(G, C, 3), wvr, get(et, "bv").unsqueeze(-1)], 2).reshape(G * C, D + 1))
+        for et in lay.dst_ets if sees_h else ():                     # hidden-state part of u
+            Fs = F[et[0]]
+            lay_at(lay.u_off[et], f"u_h of {et_key(et)}", mr(et)[:, Fs:Fs + k2].reshape(G * C, D + 1))
+        skip = None                                                  # (a dead type: no rows at s_off)
+        if lay.live:                                                 # summed skip rows + gate bias
+            ws = sum_of([get_s(et, "ws")[:, :, :D] for et in lay.dst_ets])
+            bs = sum_of([get_s(et, "bs") for et in lay.dst_ets] + [get_s("b", nt)])
+            skip = torch.cat([ws, bs.unsqueeze(-1)], 2).reshape(G * C, D + 1)
+        lay_at(lay.s_off, "skip rows", skip)
+        for et in lay.dst_ets:                                       # u4 tails: feature part of u, s1, s2 rows
+            Fs, m = F[et[0]], mr(et)
+            tail = torch.cat([m[:, :Fs], zeros(G, 12 - Fs, D + 1), m[:, Fs + k2:Fs + k2 + 2], zeros(G, U4 - 14, D + 1)], 1)
+            lay_at(lay.u4_off[et], f"u4 of {et_key(et)}", tail.reshape(G * U4, D + 1))
+        pad = -at % C
+        lay_at(lay.ncols - pad, "zero rows up to a multiple of 96", zeros(pad, D + 1))
+        rows = torch.cat(blocks)
+        wp[nt] = torch.cat([rows[:, :Fn], zeros(lay.ncols, Fp - Fn), rows[:, Fn:D]], 1)   # ggnn_project_batch's input order
+        bp[nt] = rows[:, D]
+        layout[nt] = lay
+        n_in = len(lay.dst_ets)
+        w2[nt] = torch.cat([get(et, "wl") for et in lay.dst_ets]
+                           + [torch.cat([get(et, "bl").unsqueeze(-1), get(et, "we")], 2) for et in lay.dst_ets]
+                           + [zeros(G, C, w2_width(lay) - n_in * (C + 2))], 2)   # training: agg's pad columns meet zeros
+    for et in edge_types:
+        et = tuple(et)
+        if layout[et[-1]].live:                                      # relocation columns of lin_value
+            ep[et] = get(et, "wv")[:, :, :3].transpose(1, 2)          # [G, 3, 96]
+    return layout, wp, bp, ep, w2
+
+
 @torch.no_grad()
 def pack_cell(cell, in_channels: Dict[str, int], encoder: bool, edge_types=EDGE_TYPES,
               live=NODE_TYPES) -> PackedCell:
@@ -415,77 +505,29 @@ def pack_cell(cell, in_channels: Dict[str, int], encoder: bool, edge_types=EDGE_
     F_of = dict(in_channels)
     # encoder: the sweep forms the values from the edge records (no value columns in the projection)
     enc_mfma = encoder and all(F <= 11 for F in in_channels.values())
-    layout = {nt: node_layout(nt, in_channels[nt], G, edge_types, nt in live, not encoder, not enc_mfma, tuple(live))
-              for nt in NODE_TYPES}
-    wp, bp, w2, ep = {}, {}, {}, {}
+    attr = {kind: (lin, wb) for kind, lin, wb in _KINDS}
+    stacks, prod = {}, {}
 
-    def put(dst_w, dst_b, row0, F, Fp, weight, bias, zero_xyz=False):
-        """weight: [n, F + 96] in the reference's input order [x | h] -> n rows of the packed matrix
-        from row0 on (input order [x, pad to Fp | h]); bias is ADDED to the packed bias."""
-        w = weight.detach().to(dt)
-        n = w.size(0)
-        blk = dst_w[row0:row0 + n]
-        blk[:, :F] += w[:, :F]
-        if zero_xyz:
-            blk[:, :3] = 0.0
-        if k2:
-            blk[:, Fp:Fp + C] += w[:, F:F + C]
-        dst_b[row0:row0 + n] += bias.detach().to(dt)
+    def get(et, kind):   # [G, *shape]: the parameter of every gate; get("b", nt): the gate biases
+        if (et, kind) not in stacks:
+            if et == "b":
+                per_gate = [getattr(cell, "b_" + gate)[kind].view(-1) for gate in gates]
+            else:
+                lin, wb = attr[kind]
+                per_gate = [getattr(getattr(_conv(cell, gate, et), lin), wb) for gate in gates]
+            stacks[et, kind] = torch.stack([p.detach().to(dt) for p in per_gate])
+        return stacks[et, kind]
 
-    scale = 1.0 / math.sqrt(C)  # periodGATconv.py:226
-    for nt in NODE_TYPES:
-        lay = layout[nt]
-        F, Fp = lay.F, lay.Fp
-        W = torch.zeros(lay.ncols, Fp + k2, dtype=dt, device=dev)
-        B = torch.zeros(lay.ncols, dtype=dt, device=dev)
-        for et in lay.src_ets if not enc_mfma else ():
-            for g, gate in enumerate(gates):
-                conv = _conv(cell, gate, et)
-                put(W, B, lay.v_off[et] + g * C, F, Fp, conv.lin_value.weight, conv.lin_value.bias, True)
-        for et in lay.dst_ets:
-            Fs = F_of[et[0]]
-            for g, gate in enumerate(gates):
-                conv = _conv(cell, gate, et)
-                wq, bq = conv.lin_query.weight.detach().double(), conv.lin_query.bias.detach().double()
-                wk, bk = conv.lin_key.weight.detach().double(), conv.lin_key.bias.detach().double()
-                we = conv.lin_edge.weight.detach().double()[:, 0]
-                if not k2:  # encoder: both sides see the bare feature row
-                    wq, wk = wq[:, :F], wk[:, :Fs]
-                M, mb = (wk.t() @ wq) * scale, (wk.t() @ bq) * scale         # [Fs (+96), F (+96)], [Fs (+96)]
-                tail_w = torch.zeros(U4, wq.size(1), dtype=torch.float64, device=dev)
-                tail_b = torch.zeros(U4, dtype=torch.float64, device=dev)
-                tail_w[:Fs], tail_b[:Fs] = M[:Fs], mb[:Fs]
-                tail_w[12], tail_b[12] = (bk @ wq) * scale, (bk @ bq) * scale
-                tail_w[13], tail_b[13] = (we @ wq) * scale, (we @ bq) * scale
-                put(W, B, lay.u4_off[et] + g * U4, F, Fp, tail_w, tail_b)
-                if k2:
-                    put(W, B, lay.u_off[et] + g * C, F, Fp, M[Fs:], mb[Fs:])
-        for g, gate in enumerate(gates if lay.live else ()):
-            row0 = lay.s_off + g * C
-            for et in lay.dst_ets:  # HeteroConv sums the outputs -> sum the skip weights
-                conv = _conv(cell, gate, et)
-                put(W, B, row0, F, Fp, conv.lin_skip.weight, conv.lin_skip.bias)
-            B[row0:row0 + C] += getattr(cell, "b_" + gate)[nt].detach().to(dt).view(-1)
-        wp[nt], bp[nt] = W.contiguous(), B.contiguous()
+    def mr(et):   # the score coefficients: formed in float64, each rounded to fp32 once
+        if et not in prod:
+            prod[et] = torch.stack([score_block(_conv(cell, gate, et), F_of[et[0]], F_of[et[-1]], k2).to(dt)
+                                    for gate in gates])
+        return prod[et]
 
-        n_in = len(lay.dst_ets)
-        W2 = torch.zeros(G, C, max(lay.Ka, 4), dtype=dt, device=dev)
-        for d, et in enumerate(lay.dst_ets):
-            for g, gate in enumerate(gates):
-                conv = _conv(cell, gate, et)
-                W2[g, :, d * C:(d + 1) * C] = conv.lin_l2.weight.detach().to(dt)
-                W2[g, :, n_in * C + 2 * d] = conv.lin_l2.bias.detach().to(dt)
-                W2[g, :, n_in * C + 2 * d + 1] = conv.lin_edge.weight.detach().to(dt)[:, 0]
-        w2[nt] = W2.contiguous()
-
-    for et in edge_types:
-        et = tuple(et)
-        if not layout[et[-1]].live:
-            continue
-        E = torch.zeros(G, 3, C, dtype=dt, device=dev)
-        for g, gate in enumerate(gates):
-            E[g] = _conv(cell, gate, et).lin_value.weight.detach().to(dt)[:, 0:3].t()
-        ep[et] = E.contiguous()
+    layout, wp, bp, ep, w2 = assemble(get, get, mr, lambda *shape: torch.zeros(*shape, dtype=dt, device=dev), sum,
+                                      F_of, G, not encoder, live=tuple(live), with_values=not enc_mfma,
+                                      w2_width=lambda lay: max(lay.Ka, 4), edge_types=edge_types)
+    wp, bp, ep, w2 = ({k: t.contiguous() for k, t in d.items()} for d in (wp, bp, ep, w2))
     w2p = {nt: bf16_planes(t) for nt, t in w2.items()}
     wvf = {}
     if enc_mfma:
@@ -557,24 +599,14 @@ def pack_conv(conv, F_src: int, F_dst: int, k2: int):
 
     wp_src = pack(conv.lin_value.weight, F_src, True)
     bp_src = conv.lin_value.bias.detach().to(dt)
-    scale = 1.0 / math.sqrt(C)
-    wq, bq = conv.lin_query.weight.detach().double(), conv.lin_query.bias.detach().double()
-    wk, bk = conv.lin_key.weight.detach().double(), conv.lin_key.bias.detach().double()
-    we = conv.lin_edge.weight.detach().double()[:, 0]
-    if not k2:
-        wq, wk = wq[:, :F_dst], wk[:, :F_src]
-    M, mb = (wk.t() @ wq) * scale, (wk.t() @ bq) * scale
-    tail_w = torch.zeros(U4, wq.size(1), dtype=torch.float64, device=dev)
-    tail_b = torch.zeros(U4, dtype=torch.float64, device=dev)
-    tail_w[:F_src], tail_b[:F_src] = M[:F_src], mb[:F_src]
-    tail_w[12], tail_b[12] = (bk @ wq) * scale, (bk @ bq) * scale
-    tail_w[13], tail_b[13] = (we @ wq) * scale, (we @ bq) * scale
-    uh_w = M[F_src:] if k2 else torch.zeros(C, wq.size(1), dtype=torch.float64, device=dev)
-    uh_b = mb[F_src:] if k2 else torch.zeros(C, dtype=torch.float64, device=dev)
-    wp_dst = torch.cat([pack(uh_w, F_dst, False), pack(conv.lin_skip.weight, F_dst, False),
-                        pack(tail_w, F_dst, False),
+    m = score_block(conv, F_src, F_dst, k2)
+    uh = m[F_src:F_src + k2] if k2 else torch.zeros(C, m.size(1), dtype=torch.float64, device=dev)
+    tail = torch.zeros(U4, m.size(1), dtype=torch.float64, device=dev)
+    tail[:F_src], tail[12:14] = m[:F_src], m[F_src + k2:]
+    wp_dst = torch.cat([pack(uh[:, :-1], F_dst, False), pack(conv.lin_skip.weight, F_dst, False),
+                        pack(tail[:, :-1], F_dst, False),
                         torch.zeros(C - U4, roundup4(F_dst) + k2, dtype=dt, device=dev)])
-    bp_dst = torch.cat([uh_b.to(dt), conv.lin_skip.bias.detach().to(dt), tail_b.to(dt),
+    bp_dst = torch.cat([uh[:, -1].to(dt), conv.lin_skip.bias.detach().to(dt), tail[:, -1].to(dt),
                         torch.zeros(C - U4, dtype=dt, device=dev)])
     ep = conv.lin_value.weight.detach().to(dt)[:, 0:3].t().reshape(1, 3, C).contiguous()
     w2 = torch.zeros(1, C, 100, dtype=dt, device=dev)

@@ -12,8 +12,9 @@ entry of one of three small batched products, so the whole assembly is
 
 with index tables made once per cell configuration, and its backward is the same two gathers through the inverse
 tables plus 2 bmm (`_PackWeights`): ~15 launches each way where recorded torch ops needed ~120.  The tables are
-produced by running the readable definition of the layout (`assemble`) on index tensors; `packed_weights_ops` runs the
-same definition on the parameter values with autograd and is what tests compare the tables with.
+produced by running the one definition of the layout (`packing.assemble`, which also packs the inference path's
+weights) on index tensors; `packed_weights_ops` runs the same definition on the parameter values with autograd and is
+what tests compare the tables with.
 """
 import math
 from typing import Dict
@@ -23,12 +24,8 @@ import torch
 from . import _lib, _pins
 from torch.autograd.function import once_differentiable
 
-from .packing import C, EDGE_TYPES, NODE_TYPES, et_key, node_layout
+from .packing import C, EDGE_TYPES, NODE_TYPES, _KINDS, assemble, et_key
 
-_KINDS = (("wq", "lin_query", "weight"), ("bq", "lin_query", "bias"), ("wk", "lin_key", "weight"),
-          ("bk", "lin_key", "bias"), ("wv", "lin_value", "weight"), ("bv", "lin_value", "bias"),
-          ("ws", "lin_skip", "weight"), ("bs", "lin_skip", "bias"), ("wl", "lin_l2", "weight"),
-          ("bl", "lin_l2", "bias"), ("we", "lin_edge", "weight"))
 SCALE = 1.0 / math.sqrt(C)   # periodGATconv.py:226
 
 _zero_cache, _ones_cache = {}, {}
@@ -96,46 +93,6 @@ def kq_operands(get, F, k2, et):
     K = torch.cat([wk.transpose(1, 2), get(et, "bk").unsqueeze(1), get(et, "we").squeeze(-1).unsqueeze(1)], 1)
     Q = torch.cat([wq, get(et, "bq").unsqueeze(-1)], 2)
     return K, Q
-
-
-def assemble(get, get_s, mr, zeros, sum_of, F, G, sees_h):
-    """The layout, on values or on indices.  get(et, kind): stacked parameters [G, *shape] that are the single
-    source of an entry; get_s(et, kind) / get_s("b", nt): the same for the terms of a sum; mr(et): the product block
-    [G, Fs + k2 + 2, Fd + k2 + 1]; zeros(*shape); sum_of(list): elementwise sum (HeteroConv aggr='sum').
-    -> (layout, {nt: W [ncols, Fp + k2]}, {nt: b [ncols]}, {et: ep [G, 3, 96]}, {nt: w2 [G, 96, Kg]})."""
-    k2 = C if sees_h else 0
-    layout, wp, bp, ep, w2 = {}, {}, {}, {}, {}
-    for nt in NODE_TYPES:
-        lay = node_layout(nt, F[nt], G, EDGE_TYPES, True, sees_h, True)
-        Fn, Fp, D = F[nt], lay.Fp, F[nt] + k2
-        blocks = []                                                  # rows of [W | b]: [n, D + 1]
-        for et in lay.src_ets:                                       # value rows, relocation columns zeroed
-            wvr = get(et, "wv")[:, :, 3:D]
-            blocks.append(torch.cat([zeros(G, C, 3), wvr, get(et, "bv").unsqueeze(-1)], 2).reshape(G * C, D + 1))
-        if sees_h:
-            for et in lay.dst_ets:                                   # hidden-state part of u
-                Fs = F[et[0]]
-                blocks.append(mr(et)[:, Fs:Fs + k2].reshape(G * C, D + 1))
-        ws = sum_of([get_s(et, "ws")[:, :, :D] for et in lay.dst_ets])  # summed skip rows + gate bias
-        bs = sum_of([get_s(et, "bs") for et in lay.dst_ets] + [get_s("b", nt)])
-        blocks.append(torch.cat([ws, bs.unsqueeze(-1)], 2).reshape(G * C, D + 1))
-        for et in lay.dst_ets:                                       # u4 tails: feature part of u, s1, s2 rows
-            Fs, m = F[et[0]], mr(et)
-            tail = torch.cat([m[:, :Fs], zeros(G, 12 - Fs, D + 1), m[:, Fs + k2:Fs + k2 + 2], zeros(G, 2, D + 1)], 1)
-            blocks.append(tail.reshape(G * 16, D + 1))
-        n_rows = sum(b.size(0) for b in blocks)
-        blocks.append(zeros(lay.ncols - n_rows, D + 1))
-        rows = torch.cat(blocks)
-        wp[nt] = torch.cat([rows[:, :Fn], zeros(lay.ncols, Fp - Fn), rows[:, Fn:D]], 1)   # ggnn_project_batch's input order
-        bp[nt] = rows[:, D]
-        layout[nt] = lay
-        n_in = len(lay.dst_ets)
-        w2[nt] = torch.cat([get(et, "wl") for et in lay.dst_ets]
-                           + [torch.cat([get(et, "bl").unsqueeze(-1), get(et, "we")], 2) for et in lay.dst_ets]
-                           + [zeros(G, C, lay.Kg - n_in * (C + 2))], 2)   # [G, 96, Kg]: agg's pad columns meet zeros
-    for et in EDGE_TYPES:
-        ep[et] = get(et, "wv")[:, :, :3].transpose(1, 2)              # [G, 3, 96]
-    return layout, wp, bp, ep, w2
 
 
 def _outputs_in_order(wp, bp, ep, w2):
