@@ -1,0 +1,275 @@
+// The junction graph of a periodic grain-ID image: the inverse of raster.hip, and the way into a rollout for a structure
+// that exists as an image (an EBSD map, a phase-field cross-section) and not as the reference's junction tracks
+// (graph_trajectory.py:316-376 needs its solver's `node_region`).
+//   ggnn_image_junctions = windows, representatives, numbering, positions, triples, grain->joint columns, status
+//   ggnn_junction_links  = the joint->joint columns from the triples and the joint->grain table
+// The rule is exact in integers up to the one fp32 expression of a position (include/ggnn.h; tests/vectorcheck.py restates
+// it by brute force):
+//   window (y, x) = pixels TL (y, x), TR (y, x + 1), BL (y + 1, x), BR (y + 1, x + 1), periodic; raster index y nx + x
+//   keys          three distinct valid ids: that sorted triple; four: {TL, TR, BR} and {TL, BL, BR} (the TL-BR diagonal)
+//   junction      a (window, key) with no window of a smaller raster index at an offset |dy|, |dx| <= R carrying the key
+//   number        raster order of the window, ascending key within it
+// A block is a segment of GGNN_JUNCTION_SEGMENT windows of one image row, so block order then thread order IS raster order:
+// pass 1 counts the junctions of every block, one block scans the counts, pass 2 finds the same junctions again and writes
+// them at scan[block] + the thread's rank in the block.  Nothing is kept between the passes but the counts: candidate
+// windows are ~0.2 % of an image, their (2R + 1)^2 neighbourhood test reads the image through L2, and working it out
+// twice costs less than a list of candidates would.  The numbering does not depend on the grid because nothing in it does:
+// no atomics order anything (the three counters that use them are sums).
+// Every index is clamped as elsewhere: a pixel outside [1, n_grain] voids its windows, nothing is written at or beyond
+// joint_capacity, and ggnn_junction_links bounds every row and column it reads by the tables' sizes.
+#include <algorithm>
+
+#include "common.h"
+
+namespace ggnn {
+
+constexpr int VEC_BLOCK = GGNN_JUNCTION_SEGMENT;   // four waves, one window a thread
+constexpr int VEC_WAVES = VEC_BLOCK / 64;
+constexpr int VEC_SCAN_BLOCK = 1024;
+constexpr int VEC_MAX_RADIUS = 7;
+static_assert(VEC_BLOCK % 64 == 0, "whole waves");
+
+__device__ __forceinline__ void sort3(int32_t& a, int32_t& b, int32_t& c) {
+  const int32_t lo = min(a, min(b, c)), hi = max(a, max(b, c));
+  b = a ^ b ^ c ^ lo ^ hi;   // (the middle one: the other two cancel)
+  a = lo, c = hi;
+}
+
+__device__ __forceinline__ bool triple_less(const int32_t (&a)[3], const int32_t (&b)[3]) {
+  return a[0] != b[0] ? a[0] < b[0] : a[1] != b[1] ? a[1] < b[1] : a[2] < b[2];
+}
+
+// The keys of window (y, x), 0-based grains, ascending: -> how many (0, 1 or 2 = a quadruple).
+__device__ __forceinline__ int window_keys(const int32_t* __restrict__ image, int y, int x, int nx, int ny, int32_t n_grain,
+                                           int32_t (&k)[2][3], bool& tl_invalid) {
+  const int x1 = x + 1 == nx ? 0 : x + 1, y1 = y + 1 == ny ? 0 : y + 1;
+  const int32_t tl = image[(int64_t)y * nx + x], tr = image[(int64_t)y * nx + x1];
+  const int32_t bl = image[(int64_t)y1 * nx + x], br = image[(int64_t)y1 * nx + x1];
+  tl_invalid = tl < 1 || tl > n_grain;
+  if (tl == tr && tl == bl && tl == br) return 0;
+  if (tl_invalid || tr < 1 || tr > n_grain || bl < 1 || bl > n_grain || br < 1 || br > n_grain) return 0;
+  const bool e01 = tl == tr, e02 = tl == bl, e03 = tl == br, e12 = tr == bl, e13 = tr == br, e23 = bl == br;
+  const int equal = e01 + e02 + e03 + e12 + e13 + e23;   // 0: four distinct ids, 1: three, more: fewer
+  if (equal > 1) return 0;
+  if (equal == 1) {   // the three distinct ones: all but the second pixel of the equal pair
+    k[0][0] = tl - 1;
+    k[0][1] = (e01 ? bl : tr) - 1;
+    k[0][2] = (e01 || e02 || e12 ? br : bl) - 1;
+    sort3(k[0][0], k[0][1], k[0][2]);
+    return 1;
+  }
+  k[0][0] = tl - 1, k[0][1] = tr - 1, k[0][2] = br - 1;
+  k[1][0] = tl - 1, k[1][1] = bl - 1, k[1][2] = br - 1;
+  sort3(k[0][0], k[0][1], k[0][2]);
+  sort3(k[1][0], k[1][1], k[1][2]);
+  if (triple_less(k[1], k[0]))
+    for (int i = 0; i < 3; ++i) {
+      const int32_t t = k[0][i];
+      k[0][i] = k[1][i], k[1][i] = t;
+    }
+  return 2;
+}
+
+__device__ __forceinline__ bool window_carries(const int32_t* __restrict__ image, int y, int x, int nx, int ny, int32_t n_grain,
+                                               const int32_t (&key)[3]) {
+  int32_t k[2][3];
+  bool unused;
+  const int n = window_keys(image, y, x, nx, ny, n_grain, k, unused);
+  for (int i = 0; i < n; ++i)
+    if (k[i][0] == key[0] && k[i][1] == key[1] && k[i][2] == key[2]) return true;
+  return false;
+}
+
+// Is window (y, x) the representative of `key`; m, sx, sy = the carriers at offsets within R (itself included) and the sums
+// of their offsets.
+__device__ __forceinline__ bool window_represents(const int32_t* __restrict__ image, int y, int x, int nx, int ny, int32_t n_grain,
+                                                  int R, const int32_t (&key)[3], int& m, int& sx, int& sy) {
+  bool rep = true;
+  m = 1, sx = 0, sy = 0;
+  for (int dy = -R; dy <= R; ++dy) {
+    int yy = y + dy;
+    yy += yy < 0 ? ny : yy >= ny ? -ny : 0;   // (ny > 2 R: one step)
+    for (int dx = -R; dx <= R; ++dx) {
+      if (dy == 0 && dx == 0) continue;
+      int xx = x + dx;
+      xx += xx < 0 ? nx : xx >= nx ? -nx : 0;
+      if (!window_carries(image, yy, xx, nx, ny, n_grain, key)) continue;
+      if (yy < y || (yy == y && xx < x)) rep = false;   // a smaller raster index
+      ++m, sx += dx, sy += dy;
+    }
+  }
+  return rep;
+}
+
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
+#pragma unroll
+  for (int s = 32; s >= 1; s >>= 1) v += __shfl_xor(v, s);
+  return v;
+}
+
+// EMIT = false: block_count[b] = the junctions of block b, and the three window counters of the status.
+// EMIT = true : block_count holds the exclusive scan; the junctions are written.
+template <bool EMIT>
+__global__ __launch_bounds__(VEC_BLOCK) void image_junctions_kernel(const ggnn_junction_args A, int segments) {
+  __shared__ int wave_total[VEC_WAVES];
+  const int nx = (int)A.nx, ny = (int)A.ny, R = A.merge_radius;
+  const int32_t n_grain = (int32_t)A.n_grain;
+  const int y = blockIdx.x / segments, x = (blockIdx.x - y * segments) * VEC_BLOCK + threadIdx.x;
+  int32_t k[2][3];
+  int n_keys = 0, m[2] = {0, 0}, sx[2] = {0, 0}, sy[2] = {0, 0};
+  bool rep[2] = {false, false}, tl_invalid = false;
+  if (x < nx) {
+    n_keys = window_keys(A.image, y, x, nx, ny, n_grain, k, tl_invalid);
+    for (int i = 0; i < n_keys; ++i) rep[i] = window_represents(A.image, y, x, nx, ny, n_grain, R, k[i], m[i], sx[i], sy[i]);
+  }
+  const int mine = (rep[0] ? 1 : 0) + (rep[1] ? 1 : 0);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint64_t one = __ballot(mine >= 1), two = __ballot(mine == 2);
+  if (lane == 0) wave_total[wave] = __popcll(one) + __popcll(two);
+  __syncthreads();
+  if (!EMIT) {
+    if (threadIdx.x == 0) {
+      int total = 0;
+      for (int w = 0; w < VEC_WAVES; ++w) total += wave_total[w];
+      A.workspace[blockIdx.x] = total;
+    }
+    unsigned long long* status = (unsigned long long*)A.status;
+    const unsigned long long quads = wave_sum(n_keys == 2 ? 1 : 0), merged = wave_sum((unsigned long long)(n_keys - mine)),
+                             invalid = wave_sum(tl_invalid ? 1 : 0);
+    if (lane == 0) {
+      if (quads) atomicAdd(status + 1, quads);
+      if (merged) atomicAdd(status + 2, merged);
+      if (invalid) atomicAdd(status + 3, invalid);
+    }
+    return;
+  }
+  if (!mine) return;
+  const uint64_t below = lane ? ~0ull >> (64 - lane) : 0;
+  int64_t j = (int64_t)A.workspace[blockIdx.x] + __popcll(one & below) + __popcll(two & below);
+  for (int w = 0; w < wave; ++w) j += wave_total[w];
+  const int64_t ld = 3 * A.joint_capacity;
+  for (int i = 0; i < n_keys; ++i) {
+    if (!rep[i]) continue;
+    if (j >= 0 && j < A.joint_capacity) {
+      // x = ((float)xr + off + (float)Sx / (float)m) * pitch: the quotient, the sum of the first two, the sum, the product
+      const float qx = __fdiv_rn((float)sx[i], (float)m[i]), qy = __fdiv_rn((float)sy[i], (float)m[i]);
+      A.xy[2 * j] = __fmul_rn(__fadd_rn(__fadd_rn((float)x, A.offset), qx), A.pitch);
+      A.xy[2 * j + 1] = __fmul_rn(__fadd_rn(__fadd_rn((float)y, A.offset), qy), A.pitch);
+      for (int c = 0; c < 3; ++c) {
+        A.triples[3 * j + c] = k[i][c];
+        A.edge_gj[3 * j + c] = k[i][c];
+        A.edge_gj[ld + 3 * j + c] = j;
+      }
+    }
+    ++j;
+  }
+}
+
+// One block: the exclusive scan of the block counts in place, n_joint and overflow, and the grains that have pixels.
+__global__ __launch_bounds__(VEC_SCAN_BLOCK) void junction_scan_kernel(int32_t* __restrict__ count, int64_t n_blocks,
+                                                                       const uint64_t* __restrict__ pixel_counts, int64_t n_grain,
+                                                                       int64_t joint_capacity, int64_t* __restrict__ status) {
+  __shared__ long long part[VEC_SCAN_BLOCK];
+  __shared__ unsigned long long present;
+  const int t = threadIdx.x;
+  const int64_t per = (n_blocks + VEC_SCAN_BLOCK - 1) / VEC_SCAN_BLOCK;
+  const int64_t begin = min((int64_t)t * per, n_blocks), end = min(begin + per, n_blocks);
+  long long sum = 0;
+  for (int64_t i = begin; i < end; ++i) sum += count[i];
+  part[t] = sum;
+  if (t == 0) present = 0;
+  __syncthreads();
+  for (int s = 1; s < VEC_SCAN_BLOCK; s <<= 1) {   // inclusive scan of the threads' sums
+    const long long add = t >= s ? part[t - s] : 0;
+    __syncthreads();
+    part[t] += add;
+    __syncthreads();
+  }
+  long long at = part[t] - sum;
+  for (int64_t i = begin; i < end; ++i) {
+    const int32_t c = count[i];
+    count[i] = (int32_t)at;   // (at most 2 (2^15 - 1)^2 < 2^31 junctions)
+    at += c;
+  }
+  unsigned long long have = 0;
+  for (int64_t g = 1 + t; g <= n_grain; g += VEC_SCAN_BLOCK) have += pixel_counts[g] != 0 ? 1 : 0;
+  have = wave_sum(have);
+  if ((t & 63) == 0 && have) atomicAdd(&present, have);
+  __syncthreads();
+  if (t == 0) {
+    const long long total = part[VEC_SCAN_BLOCK - 1];
+    status[0] = total;
+    status[5] = (int64_t)present;
+    status[6] = total > joint_capacity ? 1 : 0;
+  }
+}
+
+// One thread a (junction, pair) slot: the one other junction of grain a's row whose triple holds grain b.
+__global__ __launch_bounds__(256) void junction_links_kernel(const ggnn_link_args A) {
+  const int64_t n = min(max(A.status[0], (int64_t)0), A.joint_capacity);
+  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  unsigned long long open = 0;
+  if (s < 3 * n) {
+    const int64_t j = s / 3;
+    const int k = (int)(s - 3 * j);
+    const int32_t a = A.triples[3 * j + (k == 2 ? 1 : 0)], b = A.triples[3 * j + (k == 0 ? 1 : 2)];
+    int found = 0;
+    int64_t partner = -1;
+    if (a >= 0 && a < A.n_grain) {
+      const int64_t p0 = min((int64_t)max(A.rowptr[a], 0), A.E_cap);
+      const int64_t p1 = min(max((int64_t)A.rowptr[a + 1], p0), A.E_cap);
+      for (int64_t p = p0; p < p1; ++p) {
+        const int64_t o = A.col[p];
+        if (o < 0 || o >= n || o == j) continue;
+        if (A.triples[3 * o] == b || A.triples[3 * o + 1] == b || A.triples[3 * o + 2] == b) ++found, partner = o;
+      }
+    }
+    A.edge_jj[s] = j;
+    A.edge_jj[3 * A.joint_capacity + s] = found == 1 ? partner : -1;
+    open = found == 1 ? 0 : 1;
+  }
+  open = wave_sum(open);
+  if ((threadIdx.x & 63) == 0 && open) atomicAdd((unsigned long long*)A.status + 4, open);
+}
+
+}  // namespace ggnn
+
+extern "C" int ggnn_image_junctions(const ggnn_junction_args* args, ggnn_stream_t stream) {
+  using namespace ggnn;
+  if (!args) return GGNN_EINVAL;
+  const ggnn_junction_args& A = *args;
+  if (!A.image || !A.pixel_counts || !A.xy || !A.triples || !A.edge_gj || !A.status || !A.workspace) return GGNN_EINVAL;
+  if (A.merge_radius < 0 || A.merge_radius > VEC_MAX_RADIUS) return GGNN_EINVAL;
+  if (A.nx <= 2 * A.merge_radius || A.ny <= 2 * A.merge_radius || A.nx >= (1 << 15) || A.ny >= (1 << 15)) return GGNN_EINVAL;
+  if (A.n_grain < 1 || A.n_grain >= INT32_MAX - 1) return GGNN_EINVAL;
+  if (A.joint_capacity < 1 || A.joint_capacity > INT32_MAX / 3) return GGNN_EINVAL;
+  if (!(A.pitch > 0.0f) || !(A.offset >= 0.0f) || A.pitch > 1.0f || A.offset > 1.0f) return GGNN_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(A.status) | reinterpret_cast<uintptr_t>(A.edge_gj) |
+       reinterpret_cast<uintptr_t>(A.pixel_counts)) & 7u)
+    return GGNN_EINVAL;
+  const int segments = (int)((A.nx + VEC_BLOCK - 1) / VEC_BLOCK);
+  const int64_t n_blocks = A.ny * segments;
+  if (A.workspace_bytes < (size_t)n_blocks * sizeof(int32_t)) return GGNN_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(A.status, 0, GGNN_JUNCTION_STATUS_WORDS * sizeof(int64_t), st) != hipSuccess) return GGNN_ELAUNCH;
+  hipLaunchKernelGGL(image_junctions_kernel<false>, dim3((unsigned)n_blocks), dim3(VEC_BLOCK), 0, st, A, segments);
+  hipLaunchKernelGGL(junction_scan_kernel, dim3(1), dim3(VEC_SCAN_BLOCK), 0, st, A.workspace, n_blocks, A.pixel_counts, A.n_grain,
+                     A.joint_capacity, A.status);
+  hipLaunchKernelGGL(image_junctions_kernel<true>, dim3((unsigned)n_blocks), dim3(VEC_BLOCK), 0, st, A, segments);
+  return launch_status();
+}
+
+extern "C" int ggnn_junction_links(const ggnn_link_args* args, ggnn_stream_t stream) {
+  using namespace ggnn;
+  if (!args) return GGNN_EINVAL;
+  const ggnn_link_args& A = *args;
+  if (!A.triples || !A.rowptr || !A.col || !A.edge_jj || !A.status) return GGNN_EINVAL;
+  if (A.n_grain < 1 || A.n_grain >= INT32_MAX - 1 || A.E_cap < 0 || A.E_cap >= INT32_MAX) return GGNN_EINVAL;
+  if (A.joint_capacity < 1 || A.joint_capacity > INT32_MAX / 3) return GGNN_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(A.status) | reinterpret_cast<uintptr_t>(A.edge_jj)) & 7u) return GGNN_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(A.status + 4, 0, sizeof(int64_t), st) != hipSuccess) return GGNN_ELAUNCH;
+  const int64_t blocks = (3 * A.joint_capacity + 255) / 256;
+  hipLaunchKernelGGL(junction_links_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A);
+  return launch_status();
+}

@@ -210,6 +210,20 @@ def raster_areas(region_coors, s):
     return dict(zip(ids.tolist(), counts.tolist()))
 
 
+def feature_rows(theta_x, theta_z, n_joint, G, R, span):
+    """The feature rows of a sample (graph_datastruct.py:980-1010), float64, without what the geometry fills in: grain
+    [n, 11] with cos / sin of the two angles in columns 5..8 and span / 120 in 9, joint [n_joint, 8] with 1 - G / 10, R / 2
+    and span / 120 in 3..5.  Columns 0..1 (position) of both and 3 (area) of the grains are left 0 for the caller; z and
+    the gradient columns are 0 in a first state.  Shared by reference_sample and vectorize.sample_from_image."""
+    theta_x, theta_z = np.asarray(theta_x, np.float64), np.asarray(theta_z, np.float64)
+    fg = np.zeros((len(theta_x), 11))
+    fg[:, 5], fg[:, 6], fg[:, 7], fg[:, 8] = np.cos(theta_x), np.sin(theta_x), np.cos(theta_z), np.sin(theta_z)
+    fg[:, 9] = span / 120
+    fj = np.zeros((n_joint, 8))
+    fj[:, 3], fj[:, 4], fj[:, 5] = 1 - G / 10, R / 2, span / 120
+    return fg, fj
+
+
 def reference_sample(lxd: float = 40.0, seed: int = 0, G: float = 2.0, R: float = 0.4, span: int = None,
                      grain_size: float = 4.0, noise: float = 0.01):
     """-> (x_dict, edge_index_dict, edge_attr) numpy dicts: the reference's `--mode=generate` sample of `seed`
@@ -228,16 +242,12 @@ def reference_sample(lxd: float = 40.0, seed: int = 0, G: float = 2.0, R: float 
         span = span_for(G, R)
 
     s_patch = int(np.round(PATCH / MESH)) + 1
-    fg = np.zeros((n_g, 11))
+    fg, fj = feature_rows(theta_x, theta_z, n_j, G, R, span)
     for grain, c in centre.items():
         fg[grain - 1, 0:2] = c
         fg[grain - 1, 3] = counts.get(grain, 0) / s_patch ** 2
-    fg[:, 5], fg[:, 6], fg[:, 7], fg[:, 8] = np.cos(theta_x), np.sin(theta_x), np.cos(theta_z), np.sin(theta_z)
-    fg[:, 9] = span / 120
-    fj = np.zeros((n_j, 8))
     for joint, c in vertices.items():
         fj[joint, 0:2] = c
-    fj[:, 3], fj[:, 4], fj[:, 5] = 1 - G / 10, R / 2, span / 120
 
     gj, gj_len = [], []
     for grains, joint in joint2vertex.items():

@@ -1,0 +1,153 @@
+"""Start a rollout from a grain-ID image: the junction graph of a periodic image, found on the device.
+
+`grain_image()` maps a layer's polygons to an image; this is the inverse.  A structure that exists as an image -- an EBSD
+map, a phase-field cross-section with one grain id per pixel -- becomes the `(x_dict, edge_index_dict, edge_attr)` that
+`GrainRollout` takes.  The reference has no such step (its graphs come from its generator or from its phase-field solver's
+junction tracks, graph_trajectory.py:316-376).  The rule is include/ggnn.h's (ggnn_image_junctions, ggnn_junction_links),
+restated in numpy by tests/vectorcheck.py: a junction is a 2 x 2 window of pixels with three distinct ids (four: two
+junctions, split along the TL-BR diagonal), windows that repeat a triple within `merge_radius` are one junction at their
+mean, junctions are numbered in raster order, and two junctions are linked when they share two grains.
+
+On the phase-field frame 0 of the reference's seed 10020 (tests/golden/grain_image_cfg1.npz) this gives the reference's
+own graph up to numbering: the same 236 triples, the same 354 junction pairs, every coordinate within half a pixel and
+the area feature bit for bit.
+
+Not covered: no-flux images (wall junctions need a contract of their own), unions of trajectories, stacks of frames, and
+resolving a quadruple from a history (the diagonal is fixed, and counted in the status)."""
+import ctypes
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+from .backend import default_backend
+from .synthetic import EDGE_TYPES
+
+STATUS_WORDS = ("n_joint", "n_quad_windows", "n_merged_windows", "n_invalid_pixels", "n_open_pairs", "n_present_grains",
+                "overflow")
+GRIDS = {"cells": lambda nx: (np.float32(1.0), np.float32(1.0) / np.float32(nx)),
+         "points": lambda nx: (np.float32(0.5), np.float32(1.0) / np.float32(nx - 1))}
+
+
+def status_is_valid(status):
+    """Euler's formula on the torus (two junctions a grain) and nothing dropped on the way."""
+    return (status["overflow"] == 0 and status["n_invalid_pixels"] == 0 and status["n_open_pairs"] == 0
+            and status["n_joint"] == 2 * status["n_present_grains"])
+
+
+def _vectorize(image, n_grain, grid, merge_radius, joint_capacity):
+    """Every launch, no read-back: -> dict of the capacity-sized device arrays, the pixel counts, the joint->grain table
+    and the status words."""
+    be = default_backend()
+    if not isinstance(image, torch.Tensor) or not image.is_cuda or image.dim() != 2:
+        raise _lib.GGNNError("image must be a [ny, nx] device tensor of grain ids (pixel p = grain p - 1)")
+    if image.dtype not in (torch.int16, torch.int32, torch.int64, torch.uint8):
+        raise _lib.GGNNError("image must hold integers")
+    if grid not in GRIDS:
+        raise _lib.GGNNError(f"grid must be 'cells' or 'points', got {grid!r}")
+    image = image.to(torch.int32).contiguous()
+    ny, nx = image.shape
+    if n_grain is None:
+        n_grain = int(image.max())   # (a read-back of its own: pass n_grain to avoid it)
+    n_grain, R = int(n_grain), int(merge_radius)
+    if n_grain < 1:
+        raise _lib.GGNNError("n_grain must be at least 1")
+    cap = 3 * n_grain + 16 if joint_capacity is None else int(joint_capacity)
+    dev = image.device
+    _, counts = be.image_compare(image, None, n_grain)
+    xy = torch.zeros(cap, 2, dtype=torch.float32, device=dev)
+    triples = torch.zeros(cap, 3, dtype=torch.int32, device=dev)
+    # The joint->grain table is built for the capacity, before n_joint is known on the host.  The columns the kernel does
+    # not write (junctions n_joint .. capacity) point spare grain rows of their own, n_grain + j, at junction j: the first
+    # n_grain rows hold the real junctions alone, and no row grows long (the table's build sorts a row serially).
+    slots = torch.arange(cap, dtype=torch.int64, device=dev).repeat_interleave(3)
+    gj = torch.stack([slots + n_grain, slots])
+    jj = torch.full((2, 3 * cap), -1, dtype=torch.int64, device=dev)
+    status = torch.zeros(_lib.GGNN_JUNCTION_STATUS_WORDS, dtype=torch.int64, device=dev)
+    words = ny * ((nx + _lib.GGNN_JUNCTION_SEGMENT - 1) // _lib.GGNN_JUNCTION_SEGMENT)
+    ws = torch.empty(max(words, 1), dtype=torch.int32, device=dev)
+    off, pitch = GRIDS[grid](nx)
+    A = _lib.JunctionArgs()
+    A.image, A.pixel_counts, A.xy, A.triples = _lib.ptr(image), _lib.ptr(counts), _lib.ptr(xy), _lib.ptr(triples)
+    A.edge_gj, A.status, A.workspace, A.workspace_bytes = _lib.ptr(gj), _lib.ptr(status), _lib.ptr(ws), 4 * ws.numel()
+    A.nx, A.ny, A.n_grain, A.joint_capacity = nx, ny, n_grain, cap
+    A.offset, A.pitch, A.merge_radius = float(off), float(pitch), R
+    _lib.check(be.lib.ggnn_image_junctions(ctypes.byref(A), _lib.current_stream()), "ggnn_image_junctions")
+    csr = be.build_csr_batch([(gj.flip(0).contiguous(), cap, n_grain + cap)], check=False)[0]
+    L = _lib.LinkArgs()
+    L.triples, L.rowptr, L.col, L.edge_jj, L.status = (_lib.ptr(triples), _lib.ptr(csr.rowptr), _lib.ptr(csr.col),
+                                                       _lib.ptr(jj), _lib.ptr(status))
+    L.n_grain, L.joint_capacity, L.E_cap = n_grain, cap, csr.col.numel()
+    _lib.check(be.lib.ggnn_junction_links(ctypes.byref(L), _lib.current_stream()), "ggnn_junction_links")
+    return {"xy": xy, "triples": triples, "gj": gj, "jj": jj, "status": status, "counts": counts, "csr": csr,
+            "n_grain": n_grain, "capacity": cap, "shape": (ny, nx),
+            "calls": (A, L, image, ws)}   # (the two calls' arguments and what they point to: tools/vectorize_cost.py)
+
+
+def graph_from_image(image, n_grain=None, grid="cells", merge_radius=2, joint_capacity=None, strict=True):
+    """The junction graph of a periodic grain-ID image.
+
+    image: integer [ny, nx] on the device, pixel p = grain p - 1 (what `grain_image` writes); n_grain: the number of grains
+    (None: the image's largest id, at the price of a read-back); grid: "cells" -- pixel (y, x) covers
+    [x / nx, (x + 1) / nx), the rasteriser's convention -- or "points" -- samples at x / (nx - 1), both ends included (the
+    phase-field data's 501 points); merge_radius: windows that carry a triple within this Chebyshev distance of one another
+    are one junction; joint_capacity: room for the junctions (default 3 n_grain + 16: a valid structure has 2 a grain).
+
+    -> (xy float32 [n_joint, 2], triples int32 [n_joint, 3] of 0-based grains, edge_index_dict of int64 [2, 3 n_joint] for the
+    three edge types, status dict).  Setup work: a dozen launches and ONE read-back, of the status.  strict: raise ValueError
+    naming the counters unless the structure is valid (status_is_valid); strict=False returns it as it is, with -1 as the
+    destination of every joint->joint column whose pair of grains has no partner, or more than one."""
+    return _graph(image, n_grain, grid, merge_radius, joint_capacity, strict)[:4]
+
+
+def _graph(image, n_grain, grid, merge_radius, joint_capacity, strict):
+    """graph_from_image, with the capacity-sized arrays behind its results as a fifth."""
+    v = _vectorize(image, n_grain, grid, merge_radius, joint_capacity)
+    status = dict(zip(STATUS_WORDS, v["status"].tolist()))
+    if strict and not status_is_valid(status):
+        raise ValueError(f"the image is not a valid periodic grain structure: {status} (valid: overflow, n_invalid_pixels "
+                         f"and n_open_pairs 0 and n_joint == 2 n_present_grains; joint_capacity {v['capacity']})")
+    n = min(status["n_joint"], v["capacity"])
+    gj = v["gj"][:, :3 * n].contiguous()
+    ei = {EDGE_TYPES[0]: gj, EDGE_TYPES[1]: gj.flip(0).contiguous(), EDGE_TYPES[2]: v["jj"][:, :3 * n].contiguous()}
+    return v["xy"][:n].contiguous(), v["triples"][:n].contiguous(), ei, status, v
+
+
+def sample_from_image(image, theta_x, theta_z, G, R, span=None, patch_pixels=None, **kw):
+    """A rollout's first state from a grain-ID image: device (x_dict, edge_index_dict, edge_attr) in the layout and dtypes of
+    `generator.reference_sample` (11 grain columns, 8 joint columns, global coordinates), as `GrainRollout` takes them.
+
+    theta_x, theta_z: the grains' orientation angles [n_grain] (host; their cos / sin are formed in float64 and rounded
+    once); G, R: the process parameters; span: the frame span (None: `synthetic.span_for(G, R)`); patch_pixels: the pixels
+    of one training-size patch, the area feature being fp32(count / patch_pixels) of a double quotient (None: nx ny).
+    Grain centres come from ggnn_grain_centres on the junctions found, edge lengths from the rollout's own edge refresh;
+    the gradient columns are 0.  Other keywords go to `graph_from_image`; an invalid structure always raises."""
+    from .generator import feature_rows
+    from .synthetic import span_for
+    theta_x, theta_z = np.asarray(theta_x, np.float64).ravel(), np.asarray(theta_z, np.float64).ravel()
+    n_grain = int(kw.pop("n_grain", None) or len(theta_x))
+    if len(theta_x) != n_grain or len(theta_z) != n_grain:
+        raise _lib.GGNNError("theta_x and theta_z must hold one angle per grain")
+    kw.pop("strict", None)
+    xy, _, ei, _, v = _graph(image, n_grain, kw.pop("grid", "cells"), kw.pop("merge_radius", 2),
+                             kw.pop("joint_capacity", None), True)
+    if kw:
+        raise TypeError(f"sample_from_image: unknown keywords {sorted(kw)}")
+    be, dev = default_backend(), xy.device
+    if span is None:
+        span = span_for(G, R)
+    ny, nx = v["shape"]
+    fg, fj = feature_rows(theta_x, theta_z, xy.size(0), G, R, span)
+    x_grain, x_joint = torch.from_numpy(fg.astype(np.float32)).to(dev), torch.from_numpy(fj.astype(np.float32)).to(dev)
+    x_joint[:, :2] = xy
+    x_grain[:, 3] = (v["counts"][1:].to(torch.float64) / float(patch_pixels or nx * ny)).to(torch.float32)
+    csr = v["csr"]
+    csr_jg = type(csr)(csr.rowptr[:n_grain + 1], csr.col, csr.perm, csr.row, csr.unit_ptr, csr.units, csr.E)
+    be.grain_centres(csr_jg, x_joint, x_grain)
+    ea = {et: torch.zeros(ei[et].size(1), 1, dtype=torch.float32, device=dev) for et in EDGE_TYPES}
+    x = {"grain": x_grain, "joint": x_joint}
+    flags = torch.zeros(2, dtype=torch.int32, device=dev)
+    be.step_refresh(x_joint, x_grain, math.inf, flags,
+                    [(ei[et], x[et[0]], x[et[2]], ea[et]) for et in EDGE_TYPES])
+    return x, ei, ea

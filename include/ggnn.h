@@ -947,6 +947,74 @@ int ggnn_polygons_rasterize(const ggnn_raster_args* args, ggnn_stream_t stream);
  * without differing or the reverse, neither truth nor counts. */
 int ggnn_image_compare(const int32_t* image, const int32_t* truth, int64_t n_pixels, int64_t n_grain, uint64_t* differing,
                        uint64_t* counts, ggnn_stream_t stream);
+/* ------------------------------------------------------------------------------------
+ * The junction graph of a grain-ID image: the inverse of ggnn_polygons_rasterize, the way into a rollout for a structure
+ * that exists as an image (an EBSD map, a phase-field cross-section).  The reference has no such step: its graphs come from
+ * its generator or from its phase-field solver's junction tracks (`node_region`, graph_trajectory.py:316-376).  On demand,
+ * on `stream`; setup work, not part of a step.  Periodic images only; no-flux images (wall junctions), unions, stacks of
+ * frames and resolving a quadruple from a history are not covered.
+ * ggnn_image_junctions = memset of the status + three launches (count per block, scan of the blocks, emit).  The rule is
+ * exact in integers up to the one fp32 expression of a position (tests/vectorcheck.py restates it):
+ *   image     : int32 [ny, nx], pixel p = grain p - 1 (as ggnn_polygons_rasterize writes), periodic in both directions
+ *   window    : (y, x) = the pixels TL (y, x), TR (y, x + 1), BL (y + 1, x), BR (y + 1, x + 1), indices mod ny / nx; its
+ *               raster index is y nx + x
+ *   keys      : a window with a pixel outside [1, n_grain] carries none; with three distinct ids it carries that sorted
+ *               triple; with four (a quadruple) the two triples {TL, TR, BR} and {TL, BL, BR} -- the TL-BR diagonal,
+ *               always, and counted; otherwise none.  Every pixel outside [1, n_grain] is counted once.
+ *   junctions : a window is the REPRESENTATIVE of a key it carries when no window of a smaller raster index at an offset
+ *               |dy|, |dx| <= merge_radius (the periodic minimum image; nx, ny > 2 merge_radius) carries the same key.
+ *               Every (representative, key) is one junction; junctions are numbered in raster order of the window and,
+ *               within a window, by ascending key.  A carried key that is not represented counts as merged.  The
+ *               numbering does not depend on the grid.
+ *   position  : with m = the windows at such offsets that carry the key, the representative (yr, xr) included, and
+ *               (Sx, Sy) = the sums of their offsets: x = ((float)xr + offset + (float)Sx / (float)m) * pitch, each
+ *               operation rounded to fp32 on its own in this order -- the quotient, (float)xr + offset, their sum, the
+ *               product; y likewise from yr and Sy.  offset = 1, pitch = 1 / nx restates the rasteriser's convention
+ *               (s = nx); offset = 0.5, pitch = 1 / (nx - 1) suits samples on a grid that includes both ends.  Positions
+ *               are not wrapped into [0, 1).
+ *   columns   : junction j with the 0-based grains g0 < g1 < g2: triples[j] = (g0, g1, g2); columns 3j .. 3j + 2 of the
+ *               grain->joint list edge_gj [2, 3 joint_capacity] (row 1 at edge_gj + 3 joint_capacity) = (g_k, j)
+ *   status    : int64 [GGNN_JUNCTION_STATUS_WORDS], zeroed by the call: n_joint, n_quad_windows, n_merged_windows,
+ *               n_invalid_pixels, n_open_pairs (ggnn_junction_links), n_present_grains (ids g with pixel_counts[g] != 0,
+ *               1 <= g <= n_grain), overflow (n_joint > joint_capacity).  Nothing is written at or beyond joint_capacity,
+ *               and nothing between n_joint and it.  The structure is VALID when overflow, n_invalid_pixels and
+ *               n_open_pairs are 0 and n_joint == 2 n_present_grains (Euler's formula on the torus).
+ * GGNN_EINVAL without a launch: args or a pointer NULL, status / edge_gj / pixel_counts not 8-byte aligned, merge_radius
+ * outside [0, 7], nx or ny outside (2 merge_radius, 2^15), n_grain outside [1, INT32_MAX - 1), joint_capacity outside
+ * [1, INT32_MAX / 3], offset outside [0, 1], pitch outside (0, 1], a workspace below ny ceil(nx / GGNN_JUNCTION_SEGMENT) words.
+ * ggnn_junction_links = one launch: column 3j + k of the joint->joint list edge_jj [2, 3 joint_capacity] = (j, partner) for
+ * the pairs (g0, g1), (g0, g2), (g1, g2) of junction j < min(n_joint, joint_capacity) in that order; the partner is the one
+ * OTHER junction below that bound whose triple holds both grains, found by walking the first grain's row of the
+ * joint->grain table (ggnn_build_csr_batch on the flipped edge_gj: no sort, no hash); -1 when there is none or more than
+ * one, and the slot is counted in status[4] (zeroed by the call; it reads status[0]).  Rows and columns are clamped to
+ * [0, E_cap] and [0, n_joint).  GGNN_EINVAL without a launch: args or a pointer NULL, status / edge_jj not 8-byte aligned,
+ * n_grain or joint_capacity as above, E_cap outside [0, INT32_MAX). */
+#define GGNN_JUNCTION_SEGMENT 256
+#define GGNN_JUNCTION_STATUS_WORDS 7
+typedef struct ggnn_junction_args {
+  const int32_t* image;          /* [ny, nx], device */
+  const uint64_t* pixel_counts;  /* [n_grain + 1], device: ggnn_image_compare's counts of the image */
+  float* xy;                     /* [joint_capacity, 2] out */
+  int32_t* triples;              /* [joint_capacity, 3] out */
+  int64_t* edge_gj;              /* [2, 3 joint_capacity] out */
+  int64_t* status;               /* [GGNN_JUNCTION_STATUS_WORDS] out */
+  int32_t* workspace;            /* ny * ceil(nx / GGNN_JUNCTION_SEGMENT) int32 words of device scratch */
+  size_t workspace_bytes;
+  int64_t nx, ny, n_grain, joint_capacity;
+  float offset, pitch;
+  int32_t merge_radius;
+  int32_t reserved;
+} ggnn_junction_args;
+int ggnn_image_junctions(const ggnn_junction_args* args, ggnn_stream_t stream);
+typedef struct ggnn_link_args {
+  const int32_t* triples;        /* [joint_capacity, 3], device: ggnn_image_junctions' */
+  const int32_t* rowptr;         /* [>= n_grain + 1]: the joint->grain table's row pointers */
+  const int32_t* col;            /* [E_cap]: its columns */
+  int64_t* edge_jj;              /* [2, 3 joint_capacity] out */
+  int64_t* status;               /* ggnn_image_junctions' status: word 0 is read, word 4 written */
+  int64_t n_grain, joint_capacity, E_cap;
+} ggnn_link_args;
+int ggnn_junction_links(const ggnn_link_args* args, ggnn_stream_t stream);
 /* The host-side topology update those counts trigger: one call of the reference's `Cmodel.update`
  * (models.py:612-842 with delete_grain_index :861-893, switching_edge_index :896-1051, point_in_triangle :1055-1070,
  * periodic_move :1103-1106), nucleation off.  HOST memory throughout, no stream: grains of `grain_event` (those below the
