@@ -432,7 +432,7 @@ class JunctionArgs(Structure):
         ("image", c_void_p), ("pixel_counts", c_void_p), ("xy", c_void_p), ("triples", c_void_p), ("edge_gj", c_void_p),
         ("status", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_size_t),
         ("nx", c_int64), ("ny", c_int64), ("n_grain", c_int64), ("joint_capacity", c_int64),
-        ("offset", c_float), ("pitch", c_float), ("merge_radius", c_int32), ("reserved", c_int32),
+        ("offset", c_float), ("pitch", c_float), ("merge_radius", c_int32), ("boundary", c_int32),
     ]
 
 

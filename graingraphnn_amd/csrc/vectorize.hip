@@ -1,5 +1,5 @@
-// The junction graph of a periodic grain-ID image: the inverse of raster.hip, and the way into a rollout for a structure
-// that exists as an image (an EBSD map, a phase-field cross-section) and not as the reference's junction tracks
+// The junction graph of a grain-ID image, periodic or with no-flux walls: the inverse of raster.hip, and the way into a
+// rollout for a structure that exists as an image (an EBSD map, a phase-field cross-section) and not as the reference's junction tracks
 // (graph_trajectory.py:316-376 needs its solver's `node_region`).
 //   ggnn_image_junctions = windows, representatives, numbering, positions, triples, grain->joint columns, status
 //   ggnn_junction_links  = the joint->joint columns from the triples and the joint->grain table
@@ -15,6 +15,9 @@
 // windows are ~0.2 % of an image, their (2R + 1)^2 neighbourhood test reads the image through L2, and working it out
 // twice costs less than a list of candidates would.  The numbering does not depend on the grid because nothing in it does:
 // no atomics order anything (the three counters that use them are sums).
+// GGNN_BC_NOFLUX is a compile-time mode of the same kernels (the periodic instantiation keeps its instruction stream): the
+// windows run from -1, a pixel outside the image reads as the boundary grain's id 1 -- resolved in registers, no padded copy
+// of the image is made --, offsets are clipped and not wrapped, and a junction of grain 0 gets its wall's coordinate exactly.
 // Every index is clamped as elsewhere: a pixel outside [1, n_grain] voids its windows, nothing is written at or beyond
 // joint_capacity, and ggnn_junction_links bounds every row and column it reads by the tables' sizes.
 #include <algorithm>
@@ -39,12 +42,25 @@ __device__ __forceinline__ bool triple_less(const int32_t (&a)[3], const int32_t
   return a[0] != b[0] ? a[0] < b[0] : a[1] != b[1] ? a[1] < b[1] : a[2] < b[2];
 }
 
+// Pixel (y, x) as the mode reads it.  Periodic: the image's own word (the caller has wrapped the indices).  No-flux: a pixel
+// outside the image is the boundary grain's id 1; inside, id 1 reads as 0, which every test below takes for an invalid pixel
+// (the boundary grain does not occur inside).  The load is from a clamped address and the choice a select: no lane branches
+// on where it stands, and nothing is read outside the image.
+template <int BC>
+__device__ __forceinline__ int32_t pixel_at(const int32_t* __restrict__ image, int y, int x, int nx, int ny) {
+  if (BC == GGNN_BC_PERIODIC) return image[(int64_t)y * nx + x];
+  const bool inside = (unsigned)y < (unsigned)ny && (unsigned)x < (unsigned)nx;
+  const int32_t v = image[(int64_t)min(max(y, 0), ny - 1) * nx + min(max(x, 0), nx - 1)];
+  return inside ? (v == 1 ? 0 : v) : 1;
+}
+
 // The keys of window (y, x), 0-based grains, ascending: -> how many (0, 1 or 2 = a quadruple).
+template <int BC>
 __device__ __forceinline__ int window_keys(const int32_t* __restrict__ image, int y, int x, int nx, int ny, int32_t n_grain,
                                            int32_t (&k)[2][3], bool& tl_invalid) {
-  const int x1 = x + 1 == nx ? 0 : x + 1, y1 = y + 1 == ny ? 0 : y + 1;
-  const int32_t tl = image[(int64_t)y * nx + x], tr = image[(int64_t)y * nx + x1];
-  const int32_t bl = image[(int64_t)y1 * nx + x], br = image[(int64_t)y1 * nx + x1];
+  const int x1 = BC == GGNN_BC_PERIODIC && x + 1 == nx ? 0 : x + 1, y1 = BC == GGNN_BC_PERIODIC && y + 1 == ny ? 0 : y + 1;
+  const int32_t tl = pixel_at<BC>(image, y, x, nx, ny), tr = pixel_at<BC>(image, y, x1, nx, ny);
+  const int32_t bl = pixel_at<BC>(image, y1, x, nx, ny), br = pixel_at<BC>(image, y1, x1, nx, ny);
   tl_invalid = tl < 1 || tl > n_grain;
   if (tl == tr && tl == bl && tl == br) return 0;
   if (tl_invalid || tr < 1 || tr > n_grain || bl < 1 || bl > n_grain || br < 1 || br > n_grain) return 0;
@@ -70,30 +86,38 @@ __device__ __forceinline__ int window_keys(const int32_t* __restrict__ image, in
   return 2;
 }
 
+template <int BC>
 __device__ __forceinline__ bool window_carries(const int32_t* __restrict__ image, int y, int x, int nx, int ny, int32_t n_grain,
                                                const int32_t (&key)[3]) {
   int32_t k[2][3];
   bool unused;
-  const int n = window_keys(image, y, x, nx, ny, n_grain, k, unused);
+  const int n = window_keys<BC>(image, y, x, nx, ny, n_grain, k, unused);
   for (int i = 0; i < n; ++i)
     if (k[i][0] == key[0] && k[i][1] == key[1] && k[i][2] == key[2]) return true;
   return false;
 }
 
 // Is window (y, x) the representative of `key`; m, sx, sy = the carriers at offsets within R (itself included) and the sums
-// of their offsets.
+// of their offsets.  Periodic: the offsets wrap.  No-flux: the window range [-1, ny - 1] x [-1, nx - 1] clips them.
+template <int BC>
 __device__ __forceinline__ bool window_represents(const int32_t* __restrict__ image, int y, int x, int nx, int ny, int32_t n_grain,
                                                   int R, const int32_t (&key)[3], int& m, int& sx, int& sy) {
   bool rep = true;
   m = 1, sx = 0, sy = 0;
   for (int dy = -R; dy <= R; ++dy) {
     int yy = y + dy;
-    yy += yy < 0 ? ny : yy >= ny ? -ny : 0;   // (ny > 2 R: one step)
+    if (BC == GGNN_BC_PERIODIC)
+      yy += yy < 0 ? ny : yy >= ny ? -ny : 0;   // (ny > 2 R: one step)
+    else if (yy < -1 || yy >= ny)
+      continue;
     for (int dx = -R; dx <= R; ++dx) {
       if (dy == 0 && dx == 0) continue;
       int xx = x + dx;
-      xx += xx < 0 ? nx : xx >= nx ? -nx : 0;
-      if (!window_carries(image, yy, xx, nx, ny, n_grain, key)) continue;
+      if (BC == GGNN_BC_PERIODIC)
+        xx += xx < 0 ? nx : xx >= nx ? -nx : 0;
+      else if (xx < -1 || xx >= nx)
+        continue;
+      if (!window_carries<BC>(image, yy, xx, nx, ny, n_grain, key)) continue;
       if (yy < y || (yy == y && xx < x)) rep = false;   // a smaller raster index
       ++m, sx += dx, sy += dy;
     }
@@ -109,18 +133,22 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
 
 // EMIT = false: block_count[b] = the junctions of block b, and the three window counters of the status.
 // EMIT = true : block_count holds the exclusive scan; the junctions are written.
-template <bool EMIT>
+// BC = GGNN_BC_NOFLUX: the grid is ny + 1 rows of segments of the nx + 1 windows of a row, and window (y, x) begins at -1.
+template <bool EMIT, int BC>
 __global__ __launch_bounds__(VEC_BLOCK) void image_junctions_kernel(const ggnn_junction_args A, int segments) {
   __shared__ int wave_total[VEC_WAVES];
+  constexpr int FIRST = BC == GGNN_BC_PERIODIC ? 0 : -1;
   const int nx = (int)A.nx, ny = (int)A.ny, R = A.merge_radius;
   const int32_t n_grain = (int32_t)A.n_grain;
-  const int y = blockIdx.x / segments, x = (blockIdx.x - y * segments) * VEC_BLOCK + threadIdx.x;
+  const int row = blockIdx.x / segments;
+  const int y = row + FIRST, x = (blockIdx.x - row * segments) * VEC_BLOCK + threadIdx.x + FIRST;
   int32_t k[2][3];
   int n_keys = 0, m[2] = {0, 0}, sx[2] = {0, 0}, sy[2] = {0, 0};
   bool rep[2] = {false, false}, tl_invalid = false;
   if (x < nx) {
-    n_keys = window_keys(A.image, y, x, nx, ny, n_grain, k, tl_invalid);
-    for (int i = 0; i < n_keys; ++i) rep[i] = window_represents(A.image, y, x, nx, ny, n_grain, R, k[i], m[i], sx[i], sy[i]);
+    n_keys = window_keys<BC>(A.image, y, x, nx, ny, n_grain, k, tl_invalid);
+    for (int i = 0; i < n_keys; ++i)
+      rep[i] = window_represents<BC>(A.image, y, x, nx, ny, n_grain, R, k[i], m[i], sx[i], sy[i]);
   }
   const int mine = (rep[0] ? 1 : 0) + (rep[1] ? 1 : 0);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -153,8 +181,16 @@ __global__ __launch_bounds__(VEC_BLOCK) void image_junctions_kernel(const ggnn_j
     if (j >= 0 && j < A.joint_capacity) {
       // x = ((float)xr + off + (float)Sx / (float)m) * pitch: the quotient, the sum of the first two, the sum, the product
       const float qx = __fdiv_rn((float)sx[i], (float)m[i]), qy = __fdiv_rn((float)sy[i], (float)m[i]);
-      A.xy[2 * j] = __fmul_rn(__fadd_rn(__fadd_rn((float)x, A.offset), qx), A.pitch);
-      A.xy[2 * j + 1] = __fmul_rn(__fadd_rn(__fadd_rn((float)y, A.offset), qy), A.pitch);
+      float px = __fmul_rn(__fadd_rn(__fadd_rn((float)x, A.offset), qx), A.pitch);
+      float py = __fmul_rn(__fadd_rn(__fadd_rn((float)y, A.offset), qy), A.pitch);
+      if (BC == GGNN_BC_NOFLUX && k[i][0] == 0) {   // a wall junction: the wall its window straddles sets the coordinate
+        const float two_off = __fmul_rn(2.0f, A.offset);
+        const float max_y = __fdiv_rn(__fadd_rn((float)(ny - 2), two_off), __fadd_rn((float)(nx - 2), two_off));
+        px = x == -1 ? 0.0f : x == nx - 1 ? 1.0f : fminf(fmaxf(px, 0.0f), 1.0f);
+        py = y == -1 ? 0.0f : y == ny - 1 ? max_y : fminf(fmaxf(py, 0.0f), max_y);
+      }
+      A.xy[2 * j] = px;
+      A.xy[2 * j + 1] = py;
       for (int c = 0; c < 3; ++c) {
         A.triples[3 * j + c] = k[i][c];
         A.edge_gj[3 * j + c] = k[i][c];
@@ -165,10 +201,12 @@ __global__ __launch_bounds__(VEC_BLOCK) void image_junctions_kernel(const ggnn_j
   }
 }
 
-// One block: the exclusive scan of the block counts in place, n_joint and overflow, and the grains that have pixels.
+// One block: the exclusive scan of the block counts in place, n_joint and overflow, and the grains that have pixels (ids
+// first_id .. n_grain: from 1, or from 2 for a no-flux image, whose id 1 is the boundary grain).
 __global__ __launch_bounds__(VEC_SCAN_BLOCK) void junction_scan_kernel(int32_t* __restrict__ count, int64_t n_blocks,
-                                                                       const uint64_t* __restrict__ pixel_counts, int64_t n_grain,
-                                                                       int64_t joint_capacity, int64_t* __restrict__ status) {
+                                                                       const uint64_t* __restrict__ pixel_counts, int64_t first_id,
+                                                                       int64_t n_grain, int64_t joint_capacity,
+                                                                       int64_t* __restrict__ status) {
   __shared__ long long part[VEC_SCAN_BLOCK];
   __shared__ unsigned long long present;
   const int t = threadIdx.x;
@@ -192,7 +230,7 @@ __global__ __launch_bounds__(VEC_SCAN_BLOCK) void junction_scan_kernel(int32_t* 
     at += c;
   }
   unsigned long long have = 0;
-  for (int64_t g = 1 + t; g <= n_grain; g += VEC_SCAN_BLOCK) have += pixel_counts[g] != 0 ? 1 : 0;
+  for (int64_t g = first_id + t; g <= n_grain; g += VEC_SCAN_BLOCK) have += pixel_counts[g] != 0 ? 1 : 0;
   have = wave_sum(have);
   if ((t & 63) == 0 && have) atomicAdd(&present, have);
   __syncthreads();
@@ -247,15 +285,20 @@ extern "C" int ggnn_image_junctions(const ggnn_junction_args* args, ggnn_stream_
   if ((reinterpret_cast<uintptr_t>(A.status) | reinterpret_cast<uintptr_t>(A.edge_gj) |
        reinterpret_cast<uintptr_t>(A.pixel_counts)) & 7u)
     return GGNN_EINVAL;
-  const int segments = (int)((A.nx + VEC_BLOCK - 1) / VEC_BLOCK);
-  const int64_t n_blocks = A.ny * segments;
+  if (A.boundary != GGNN_BC_PERIODIC && A.boundary != GGNN_BC_NOFLUX) return GGNN_EINVAL;
+  const bool periodic = A.boundary == GGNN_BC_PERIODIC;
+  const int64_t wx = periodic ? A.nx : A.nx + 1, wy = periodic ? A.ny : A.ny + 1;   // the windows of a row, the rows
+  const int segments = (int)((wx + VEC_BLOCK - 1) / VEC_BLOCK);
+  const int64_t n_blocks = wy * segments;
   if (A.workspace_bytes < (size_t)n_blocks * sizeof(int32_t)) return GGNN_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(A.status, 0, GGNN_JUNCTION_STATUS_WORDS * sizeof(int64_t), st) != hipSuccess) return GGNN_ELAUNCH;
-  hipLaunchKernelGGL(image_junctions_kernel<false>, dim3((unsigned)n_blocks), dim3(VEC_BLOCK), 0, st, A, segments);
-  hipLaunchKernelGGL(junction_scan_kernel, dim3(1), dim3(VEC_SCAN_BLOCK), 0, st, A.workspace, n_blocks, A.pixel_counts, A.n_grain,
-                     A.joint_capacity, A.status);
-  hipLaunchKernelGGL(image_junctions_kernel<true>, dim3((unsigned)n_blocks), dim3(VEC_BLOCK), 0, st, A, segments);
+  const auto count = periodic ? image_junctions_kernel<false, GGNN_BC_PERIODIC> : image_junctions_kernel<false, GGNN_BC_NOFLUX>;
+  const auto emit = periodic ? image_junctions_kernel<true, GGNN_BC_PERIODIC> : image_junctions_kernel<true, GGNN_BC_NOFLUX>;
+  hipLaunchKernelGGL(count, dim3((unsigned)n_blocks), dim3(VEC_BLOCK), 0, st, A, segments);
+  hipLaunchKernelGGL(junction_scan_kernel, dim3(1), dim3(VEC_SCAN_BLOCK), 0, st, A.workspace, n_blocks, A.pixel_counts,
+                     (int64_t)(periodic ? 1 : 2), A.n_grain, A.joint_capacity, A.status);
+  hipLaunchKernelGGL(emit, dim3((unsigned)n_blocks), dim3(VEC_BLOCK), 0, st, A, segments);
   return launch_status();
 }
 

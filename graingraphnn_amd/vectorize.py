@@ -1,4 +1,4 @@
-"""Start a rollout from a grain-ID image: the junction graph of a periodic image, found on the device.
+"""Start a rollout from a grain-ID image: the junction graph of a periodic or a no-flux image, found on the device.
 
 `grain_image()` maps a layer's polygons to an image; this is the inverse.  A structure that exists as an image -- an EBSD
 map, a phase-field cross-section with one grain id per pixel -- becomes the `(x_dict, edge_index_dict, edge_attr)` that
@@ -12,8 +12,14 @@ On the phase-field frame 0 of the reference's seed 10020 (tests/golden/grain_ima
 own graph up to numbering: the same 236 triples, the same 354 junction pairs, every coordinate within half a pixel and
 the area feature bit for bit.
 
-Not covered: no-flux images (wall junctions need a contract of their own), unions of trajectories, stacks of frames, and
-resolving a quadruple from a history (the diagonal is fixed, and counted in the status)."""
+`boundary="noflux"` takes an image with walls, non-square ones included: everything outside the image is grain 0, the
+boundary grain of the reference's no-flux graphs (id 1, which does not occur inside), so a junction lies on a wall exactly
+when its triple holds grain 0, wall junctions are linked along the walls through the pairs (0, a), their coordinate normal
+to the wall is exactly 0, 1 or `max_y`, and the four corner pixels come back as the `corner_grains` that `grain_image`
+fills the corners from (tests/vectorcheck_noflux.py restates the rule).
+
+Not covered: unions of trajectories, stacks of frames, and resolving a quadruple from a history (the diagonal is fixed,
+and counted in the status)."""
 import ctypes
 import math
 
@@ -30,16 +36,37 @@ GRIDS = {"cells": lambda nx: (np.float32(1.0), np.float32(1.0) / np.float32(nx))
          "points": lambda nx: (np.float32(0.5), np.float32(1.0) / np.float32(nx - 1))}
 
 
-def status_is_valid(status):
-    """Euler's formula on the torus (two junctions a grain) and nothing dropped on the way."""
+BOUNDARIES = {"periodic": _lib.BC_PERIODIC, "noflux": _lib.BC_NOFLUX}
+EULER = {"periodic": "n_joint == 2 n_present_grains", "noflux": "n_joint == 2 n_present_grains - 2"}
+
+
+def status_is_valid(status, boundary="periodic"):
+    """Euler's formula -- on the torus two junctions a grain; on the sphere, with the boundary grain as the outer face of a
+    no-flux image, two fewer -- and nothing dropped on the way."""
+    _check_boundary(boundary)
     return (status["overflow"] == 0 and status["n_invalid_pixels"] == 0 and status["n_open_pairs"] == 0
-            and status["n_joint"] == 2 * status["n_present_grains"])
+            and status["n_joint"] == 2 * status["n_present_grains"] - (2 if boundary == "noflux" else 0))
 
 
-def _vectorize(image, n_grain, grid, merge_radius, joint_capacity):
+def _check_boundary(boundary):
+    if boundary not in BOUNDARIES:
+        raise _lib.GGNNError(f"boundary must be 'periodic' or 'noflux', got {boundary!r}")
+
+
+def image_max_y(nx, ny, grid):
+    """The far y wall of a no-flux [ny, nx] image, the kernel's own fp32 expression: ny / nx for "cells",
+    (ny - 1) / (nx - 1) for "points", exactly 1 for a square image."""
+    f = np.float32
+    two_off = f(f(2) * GRIDS[grid](nx)[0])
+    return float(f(f(f(ny - 2) + two_off) / f(f(nx - 2) + two_off)))
+
+
+def _vectorize(image, n_grain, grid, merge_radius, joint_capacity, boundary="periodic"):
     """Every launch, no read-back: -> dict of the capacity-sized device arrays, the pixel counts, the joint->grain table
-    and the status words."""
+    and the status words (no-flux: the four corner pixels behind them, so that one read-back fetches both)."""
     be = default_backend()
+    _check_boundary(boundary)
+    noflux = boundary == "noflux"
     if not isinstance(image, torch.Tensor) or not image.is_cuda or image.dim() != 2:
         raise _lib.GGNNError("image must be a [ny, nx] device tensor of grain ids (pixel p = grain p - 1)")
     if image.dtype not in (torch.int16, torch.int32, torch.int64, torch.uint8):
@@ -64,15 +91,18 @@ def _vectorize(image, n_grain, grid, merge_radius, joint_capacity):
     slots = torch.arange(cap, dtype=torch.int64, device=dev).repeat_interleave(3)
     gj = torch.stack([slots + n_grain, slots])
     jj = torch.full((2, 3 * cap), -1, dtype=torch.int64, device=dev)
-    status = torch.zeros(_lib.GGNN_JUNCTION_STATUS_WORDS, dtype=torch.int64, device=dev)
-    words = ny * ((nx + _lib.GGNN_JUNCTION_SEGMENT - 1) // _lib.GGNN_JUNCTION_SEGMENT)
+    status = torch.zeros(_lib.GGNN_JUNCTION_STATUS_WORDS + (4 if noflux else 0), dtype=torch.int64, device=dev)
+    if noflux:   # the order of grain_image(corner_grains=)
+        status[_lib.GGNN_JUNCTION_STATUS_WORDS:] = torch.stack([image[0, 0], image[0, -1], image[-1, 0], image[-1, -1]])
+    wy, wx = (ny + 1, nx + 1) if noflux else (ny, nx)   # the rows of windows, the windows of a row
+    words = wy * ((wx + _lib.GGNN_JUNCTION_SEGMENT - 1) // _lib.GGNN_JUNCTION_SEGMENT)
     ws = torch.empty(max(words, 1), dtype=torch.int32, device=dev)
     off, pitch = GRIDS[grid](nx)
     A = _lib.JunctionArgs()
     A.image, A.pixel_counts, A.xy, A.triples = _lib.ptr(image), _lib.ptr(counts), _lib.ptr(xy), _lib.ptr(triples)
     A.edge_gj, A.status, A.workspace, A.workspace_bytes = _lib.ptr(gj), _lib.ptr(status), _lib.ptr(ws), 4 * ws.numel()
     A.nx, A.ny, A.n_grain, A.joint_capacity = nx, ny, n_grain, cap
-    A.offset, A.pitch, A.merge_radius = float(off), float(pitch), R
+    A.offset, A.pitch, A.merge_radius, A.boundary = float(off), float(pitch), R, BOUNDARIES[boundary]
     _lib.check(be.lib.ggnn_image_junctions(ctypes.byref(A), _lib.current_stream()), "ggnn_image_junctions")
     csr = be.build_csr_batch([(gj.flip(0).contiguous(), cap, n_grain + cap)], check=False)[0]
     L = _lib.LinkArgs()
@@ -81,12 +111,14 @@ def _vectorize(image, n_grain, grid, merge_radius, joint_capacity):
     L.n_grain, L.joint_capacity, L.E_cap = n_grain, cap, csr.col.numel()
     _lib.check(be.lib.ggnn_junction_links(ctypes.byref(L), _lib.current_stream()), "ggnn_junction_links")
     return {"xy": xy, "triples": triples, "gj": gj, "jj": jj, "status": status, "counts": counts, "csr": csr,
-            "n_grain": n_grain, "capacity": cap, "shape": (ny, nx),
+            "n_grain": n_grain, "capacity": cap, "shape": (ny, nx), "boundary": boundary,
+            "max_y": image_max_y(nx, ny, grid) if noflux else None,
             "calls": (A, L, image, ws)}   # (the two calls' arguments and what they point to: tools/vectorize_cost.py)
 
 
-def graph_from_image(image, n_grain=None, grid="cells", merge_radius=2, joint_capacity=None, strict=True):
-    """The junction graph of a periodic grain-ID image.
+def graph_from_image(image, n_grain=None, grid="cells", merge_radius=2, joint_capacity=None, strict=True,
+                     boundary="periodic"):
+    """The junction graph of a grain-ID image, periodic or (boundary="noflux") with walls.
 
     image: integer [ny, nx] on the device, pixel p = grain p - 1 (what `grain_image` writes); n_grain: the number of grains
     (None: the image's largest id, at the price of a read-back); grid: "cells" -- pixel (y, x) covers
@@ -97,17 +129,29 @@ def graph_from_image(image, n_grain=None, grid="cells", merge_radius=2, joint_ca
     -> (xy float32 [n_joint, 2], triples int32 [n_joint, 3] of 0-based grains, edge_index_dict of int64 [2, 3 n_joint] for the
     three edge types, status dict).  Setup work: a dozen launches and ONE read-back, of the status.  strict: raise ValueError
     naming the counters unless the structure is valid (status_is_valid); strict=False returns it as it is, with -1 as the
-    destination of every joint->joint column whose pair of grains has no partner, or more than one."""
-    return _graph(image, n_grain, grid, merge_radius, joint_capacity, strict)[:4]
+    destination of every joint->joint column whose pair of grains has no partner, or more than one.
+
+    boundary="noflux": the image is not periodic and may be non-square; everything outside it is grain 0, so the ids inside
+    are 2 .. n_grain (n_grain counts the boundary grain; id 1 inside is an invalid pixel), a valid structure has
+    2 n_present_grains - 2 junctions, and the junctions of grain 0 lie on the walls x = 0, x = 1, y = 0 and y = max_y.
+    -> (xy, triples, edge_index_dict, status, corner_grains, max_y): the four as above, the ids of the corner pixels [0, 0],
+    [0, nx - 1], [ny - 1, 0], [ny - 1, nx - 1] as `grain_image(corner_grains=)` takes them (they come with the status: still
+    one read-back), and the far y wall as a float that is exact in fp32, for `GrainRollout(boundary="noflux", max_y=)`."""
+    xy, triples, ei, status, v = _graph(image, n_grain, grid, merge_radius, joint_capacity, strict, boundary)
+    if boundary == "noflux":
+        return xy, triples, ei, status, v["corner_grains"], v["max_y"]
+    return xy, triples, ei, status
 
 
-def _graph(image, n_grain, grid, merge_radius, joint_capacity, strict):
-    """graph_from_image, with the capacity-sized arrays behind its results as a fifth."""
-    v = _vectorize(image, n_grain, grid, merge_radius, joint_capacity)
-    status = dict(zip(STATUS_WORDS, v["status"].tolist()))
-    if strict and not status_is_valid(status):
-        raise ValueError(f"the image is not a valid periodic grain structure: {status} (valid: overflow, n_invalid_pixels "
-                         f"and n_open_pairs 0 and n_joint == 2 n_present_grains; joint_capacity {v['capacity']})")
+def _graph(image, n_grain, grid, merge_radius, joint_capacity, strict, boundary="periodic"):
+    """graph_from_image's four, with the capacity-sized arrays behind its results as a fifth."""
+    v = _vectorize(image, n_grain, grid, merge_radius, joint_capacity, boundary)
+    words = v["status"].tolist()
+    status = dict(zip(STATUS_WORDS, words))
+    v["corner_grains"] = tuple(words[len(STATUS_WORDS):]) if boundary == "noflux" else None
+    if strict and not status_is_valid(status, boundary):
+        raise ValueError(f"the image is not a valid {boundary} grain structure: {status} (valid: overflow, n_invalid_pixels "
+                         f"and n_open_pairs 0 and {EULER[boundary]}; joint_capacity {v['capacity']})")
     n = min(status["n_joint"], v["capacity"])
     gj = v["gj"][:, :3 * n].contiguous()
     ei = {EDGE_TYPES[0]: gj, EDGE_TYPES[1]: gj.flip(0).contiguous(), EDGE_TYPES[2]: v["jj"][:, :3 * n].contiguous()}
@@ -122,7 +166,13 @@ def sample_from_image(image, theta_x, theta_z, G, R, span=None, patch_pixels=Non
     once); G, R: the process parameters; span: the frame span (None: `synthetic.span_for(G, R)`); patch_pixels: the pixels
     of one training-size patch, the area feature being fp32(count / patch_pixels) of a double quotient (None: nx ny).
     Grain centres come from ggnn_grain_centres on the junctions found, edge lengths from the rollout's own edge refresh;
-    the gradient columns are 0.  Other keywords go to `graph_from_image`; an invalid structure always raises."""
+    the gradient columns are 0.  Other keywords go to `graph_from_image`; an invalid structure always raises.
+
+    boundary="noflux": the angles count the boundary grain, theta[0], and the result is what
+    `GrainRollout(..., boundary="noflux", max_y=image_max_y(nx, ny, grid))` takes: the FULL edge lists, grain 0's edges
+    included (the rollout masks them itself); grain 0's row as the reference keeps it -- centre (0.5, 0.5), area 0, extraV 0 --
+    and every other centre from ggnn_grain_centres in its GGNN_BC_NOFLUX mode.  The rollout's boundary step finds this
+    state as it would leave it."""
     from .generator import feature_rows
     from .synthetic import span_for
     theta_x, theta_z = np.asarray(theta_x, np.float64).ravel(), np.asarray(theta_z, np.float64).ravel()
@@ -130,8 +180,9 @@ def sample_from_image(image, theta_x, theta_z, G, R, span=None, patch_pixels=Non
     if len(theta_x) != n_grain or len(theta_z) != n_grain:
         raise _lib.GGNNError("theta_x and theta_z must hold one angle per grain")
     kw.pop("strict", None)
+    boundary = kw.pop("boundary", "periodic")
     xy, _, ei, _, v = _graph(image, n_grain, kw.pop("grid", "cells"), kw.pop("merge_radius", 2),
-                             kw.pop("joint_capacity", None), True)
+                             kw.pop("joint_capacity", None), True, boundary)
     if kw:
         raise TypeError(f"sample_from_image: unknown keywords {sorted(kw)}")
     be, dev = default_backend(), xy.device
@@ -144,7 +195,11 @@ def sample_from_image(image, theta_x, theta_z, G, R, span=None, patch_pixels=Non
     x_grain[:, 3] = (v["counts"][1:].to(torch.float64) / float(patch_pixels or nx * ny)).to(torch.float32)
     csr = v["csr"]
     csr_jg = type(csr)(csr.rowptr[:n_grain + 1], csr.col, csr.perm, csr.row, csr.unit_ptr, csr.units, csr.E)
-    be.grain_centres(csr_jg, x_joint, x_grain)
+    be.grain_centres(csr_jg, x_joint, x_grain, boundary=boundary)
+    if boundary == "noflux":   # the boundary grain's row as ggnn_noflux_boundary resets it
+        x_grain[0, :2] = 0.5
+        x_grain[0, 3:5] = 0.0
+        x_grain[0, 10] = 0.0
     ea = {et: torch.zeros(ei[et].size(1), 1, dtype=torch.float32, device=dev) for et in EDGE_TYPES}
     x = {"grain": x_grain, "joint": x_joint}
     flags = torch.zeros(2, dtype=torch.int32, device=dev)

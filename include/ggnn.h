@@ -951,8 +951,8 @@ int ggnn_image_compare(const int32_t* image, const int32_t* truth, int64_t n_pix
  * The junction graph of a grain-ID image: the inverse of ggnn_polygons_rasterize, the way into a rollout for a structure
  * that exists as an image (an EBSD map, a phase-field cross-section).  The reference has no such step: its graphs come from
  * its generator or from its phase-field solver's junction tracks (`node_region`, graph_trajectory.py:316-376).  On demand,
- * on `stream`; setup work, not part of a step.  Periodic images only; no-flux images (wall junctions), unions, stacks of
- * frames and resolving a quadruple from a history are not covered.
+ * on `stream`; setup work, not part of a step.  Periodic images and images with no-flux walls (`boundary`, below); unions,
+ * stacks of frames and resolving a quadruple from a history are not covered.
  * ggnn_image_junctions = memset of the status + three launches (count per block, scan of the blocks, emit).  The rule is
  * exact in integers up to the one fp32 expression of a position (tests/vectorcheck.py restates it):
  *   image     : int32 [ny, nx], pixel p = grain p - 1 (as ggnn_polygons_rasterize writes), periodic in both directions
@@ -979,9 +979,34 @@ int ggnn_image_compare(const int32_t* image, const int32_t* truth, int64_t n_pix
  *               1 <= g <= n_grain), overflow (n_joint > joint_capacity).  Nothing is written at or beyond joint_capacity,
  *               and nothing between n_joint and it.  The structure is VALID when overflow, n_invalid_pixels and
  *               n_open_pairs are 0 and n_joint == 2 n_present_grains (Euler's formula on the torus).
+ * boundary = GGNN_BC_NOFLUX: the image has walls, and everything outside it is grain 0, the boundary grain that wraps the
+ * domain (its row of the joint->grain table holds every wall junction, as in the reference's no-flux graphs, where a junction
+ * lies on a wall exactly when its triple holds grain 0 and two wall junctions are linked exactly when they share (0, a)).
+ * The rule above with these changes (tests/vectorcheck_noflux.py restates it):
+ *   image     : not periodic.  Valid ids inside are [2, n_grain]: a pixel that is 1 or outside [1, n_grain] is counted in
+ *               n_invalid_pixels and voids its windows.
+ *   window    : (y, x) for y in [-1, ny - 1], x in [-1, nx - 1]; a pixel outside the image reads as id 1 (resolved in
+ *               registers: no padded copy of the image is made); raster index (y + 1)(nx + 1) + (x + 1).
+ *   keys      : as above.  A window on a wall holds two outside pixels and a corner window three, so neither holds four
+ *               ids, and a corner window {1, 1, 1, a} carries nothing: corners are not junctions in the reference, they
+ *               are its corner_grains.
+ *   junctions : as above with offsets (y' - y, x' - x) clipped by the window range, not wrapped; nx, ny > 2 merge_radius.
+ *   position  : the same expression (xr, yr may be -1); then for a junction whose triple holds grain 0 -- its
+ *               representative straddles a wall, since only such windows read an outside pixel -- the coordinate normal to
+ *               that wall is set exactly: xr == -1: x = 0.0f, xr == nx - 1: x = 1.0f, yr == -1: y = 0.0f, yr == ny - 1:
+ *               y = max_y = ((float)(ny - 2) + 2 offset) / ((float)(nx - 2) + 2 offset), each operation rounded to fp32
+ *               (ny / nx for offset 1, (ny - 1) / (nx - 1) for offset 0.5, exactly 1 for a square image); the coordinate no
+ *               wall has set is clamped to [0, 1] (x) or [0, max_y] (y), which acts next to a corner only, where the
+ *               carriers of one key lie on two walls.  Every junction then lies in [0, 1] x [0, max_y] with grain 0's on the
+ *               walls, so ggnn_noflux_boundary(max_y) leaves the positions as they are.
+ *   status    : n_present_grains counts the ids 2 .. n_grain; VALID: overflow, n_invalid_pixels and n_open_pairs 0 and
+ *               n_joint == 2 n_present_grains - 2 (Euler's formula on the sphere, grain 0 being the outer face).
+ * The grid is ny + 1 rows of ceil((nx + 1) / GGNN_JUNCTION_SEGMENT) segments, and the workspace holds one word a block.
  * GGNN_EINVAL without a launch: args or a pointer NULL, status / edge_gj / pixel_counts not 8-byte aligned, merge_radius
  * outside [0, 7], nx or ny outside (2 merge_radius, 2^15), n_grain outside [1, INT32_MAX - 1), joint_capacity outside
- * [1, INT32_MAX / 3], offset outside [0, 1], pitch outside (0, 1], a workspace below ny ceil(nx / GGNN_JUNCTION_SEGMENT) words.
+ * [1, INT32_MAX / 3], offset outside [0, 1], pitch outside (0, 1], boundary neither GGNN_BC_PERIODIC nor GGNN_BC_NOFLUX, a
+ * workspace below ny ceil(nx / GGNN_JUNCTION_SEGMENT) words (periodic) or (ny + 1) ceil((nx + 1) / GGNN_JUNCTION_SEGMENT)
+ * words (no-flux).
  * ggnn_junction_links = one launch: column 3j + k of the joint->joint list edge_jj [2, 3 joint_capacity] = (j, partner) for
  * the pairs (g0, g1), (g0, g2), (g1, g2) of junction j < min(n_joint, joint_capacity) in that order; the partner is the one
  * OTHER junction below that bound whose triple holds both grains, found by walking the first grain's row of the
@@ -998,12 +1023,12 @@ typedef struct ggnn_junction_args {
   int32_t* triples;              /* [joint_capacity, 3] out */
   int64_t* edge_gj;              /* [2, 3 joint_capacity] out */
   int64_t* status;               /* [GGNN_JUNCTION_STATUS_WORDS] out */
-  int32_t* workspace;            /* ny * ceil(nx / GGNN_JUNCTION_SEGMENT) int32 words of device scratch */
+  int32_t* workspace;            /* ny * ceil(nx / GGNN_JUNCTION_SEGMENT) int32 words of device scratch (no-flux: see above) */
   size_t workspace_bytes;
   int64_t nx, ny, n_grain, joint_capacity;
   float offset, pitch;
   int32_t merge_radius;
-  int32_t reserved;
+  int32_t boundary;              /* GGNN_BC_PERIODIC / GGNN_BC_NOFLUX */
 } ggnn_junction_args;
 int ggnn_image_junctions(const ggnn_junction_args* args, ggnn_stream_t stream);
 typedef struct ggnn_link_args {
