@@ -28,7 +28,7 @@ GGNN_FLAG_F16_RANGE = 1
 GGNN_FLAG_QOI_OVERFLOW = 2
 GGNN_FLAG_POLYGON_OVERFLOW = 4
 GGNN_INTERP_MAX_JOBS = 256
-GGNN_JUNCTION_SEGMENT, GGNN_JUNCTION_STATUS_WORDS = 256, 7
+GGNN_JUNCTION_SEGMENT, GGNN_JUNCTION_STATUS_WORDS, GGNN_JUNCTION_MAX_BLOCKS = 256, 7, 1 << 22
 GGNN_ADAM_CHUNK, GGNN_ADAM_MAX_TENSORS, GGNN_ADAM_MAX_GROUPS = 4096, 384, 8
 GGNN_ROWGEMM_MAX_PACK = 8
 GGNN_MSE_MAX_TERMS, GGNN_MSE_BLOCKS = 4, 64
@@ -61,6 +61,7 @@ EXPORTED_SYMBOLS = (
     "ggnn_qoi_accumulate", "ggnn_qoi_finalize", "ggnn_process_schedule", "ggnn_grain_polygons",
     "ggnn_polygon_inputs", "ggnn_interp_polygons",
     "ggnn_polygons_rasterize", "ggnn_image_compare", "ggnn_image_junctions", "ggnn_junction_links",
+    "ggnn_image_junctions_traj", "ggnn_junction_links_traj",
     "ggnn_metric_record",
     "ggnn_masked_mse_rows", "ggnn_collate_batch", "ggnn_reverse_slots",
 )
@@ -444,6 +445,24 @@ class LinkArgs(Structure):
     ]
 
 
+class JunctionTrajArgs(Structure):
+    """Mirror of `ggnn_junction_traj_args`."""
+    _fields_ = [
+        ("images", c_void_p), ("grain_off", c_void_p), ("pixel_counts", c_void_p), ("xy", c_void_p), ("triples", c_void_p),
+        ("edge_gj", c_void_p), ("status", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_size_t),
+        ("nx", c_int64), ("ny", c_int64), ("n_image", c_int64), ("n_grain", c_int64), ("joint_capacity", c_int64),
+        ("offset", c_float), ("pitch", c_float), ("merge_radius", c_int32), ("boundary", c_int32),
+    ]
+
+
+class LinkTrajArgs(Structure):
+    """Mirror of `ggnn_link_traj_args`."""
+    _fields_ = [
+        ("triples", c_void_p), ("rowptr", c_void_p), ("col", c_void_p), ("edge_jj", c_void_p), ("status", c_void_p),
+        ("n_grain", c_int64), ("joint_capacity", c_int64), ("E_cap", c_int64), ("n_image", c_int64),
+    ]
+
+
 class MetricArgs(Structure):
     """Mirror of `ggnn_metric_args`."""
     _fields_ = [
@@ -604,6 +623,10 @@ def _declare(lib):
     lib.ggnn_image_junctions.argtypes = [POINTER(JunctionArgs), c_void_p]
     lib.ggnn_junction_links.restype = c_int
     lib.ggnn_junction_links.argtypes = [POINTER(LinkArgs), c_void_p]
+    lib.ggnn_image_junctions_traj.restype = c_int
+    lib.ggnn_image_junctions_traj.argtypes = [POINTER(JunctionTrajArgs), c_void_p]
+    lib.ggnn_junction_links_traj.restype = c_int
+    lib.ggnn_junction_links_traj.argtypes = [POINTER(LinkTrajArgs), c_void_p]
     lib.ggnn_process_schedule.restype = c_int
     lib.ggnn_process_schedule.argtypes = [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p]

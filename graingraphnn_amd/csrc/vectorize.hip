@@ -270,6 +270,207 @@ __global__ __launch_bounds__(256) void junction_links_kernel(const ggnn_link_arg
   if ((threadIdx.x & 63) == 0 && open) atomicAdd((unsigned long long*)A.status + 4, open);
 }
 
+// ---- A stack of images into one union graph (ggnn_image_junctions_traj / ggnn_junction_links_traj) ---------------------------
+// The same rule per image, and the same three passes: the blocks are laid out image-major -- block = image * (rows *
+// segments) + row * segments + segment --, so block order is still the order of the numbering and the one scan block carries
+// over; it also writes joint_off[image] = the scan at the image's first block.  A block belongs to one image: its base
+// pointer, its grain range [grain_off[b], grain_off[b + 1]) (clamped to the union's n_grain; read from the device, never from
+// the host) and its status row are block-uniform, and the window tests above run on that image alone, so a wrap, a clipped
+// offset or an outside pixel never reaches a neighbouring image.  The count pass also counts the pixels per union grain
+// (every pixel is the TL pixel of exactly one window): a lane adds the length of its run of equal ids in the wave, so a row
+// inside a grain is one atomic and not 64.
+
+// The grains of image b: -> the first one, n = how many (0 when the offsets do not rise).
+__device__ __forceinline__ int64_t image_grains(const int64_t* __restrict__ grain_off, int64_t b, int64_t n_total, int32_t& n) {
+  const int64_t lo = min(max(grain_off[b], (int64_t)0), n_total), hi = min(max(grain_off[b + 1], lo), n_total);
+  n = (int32_t)(hi - lo);
+  return lo;
+}
+
+// The last entry of the rising off[0 .. n] that is <= v, below n.
+__device__ __forceinline__ int64_t segment_of(const int64_t* __restrict__ off, int64_t n, int64_t v) {
+  int64_t lo = 0, hi = n - 1;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi + 1) >> 1;
+    if (off[mid] <= v) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+template <bool EMIT, int BC>
+__global__ __launch_bounds__(VEC_BLOCK) void image_junctions_traj_kernel(const ggnn_junction_traj_args A, int segments, int rows) {
+  __shared__ int wave_total[VEC_WAVES];
+  constexpr int FIRST = BC == GGNN_BC_PERIODIC ? 0 : -1;
+  const int nx = (int)A.nx, ny = (int)A.ny, R = A.merge_radius;
+  const int per_image = rows * segments;
+  const int b = blockIdx.x / per_image, in_image = blockIdx.x - b * per_image;
+  if (b >= A.n_image) return;
+  int32_t n_grain;
+  const int64_t g0 = image_grains(A.grain_off, b, A.n_grain, n_grain);
+  const int32_t* __restrict__ image = A.images + (int64_t)b * ny * nx;
+  const int row = in_image / segments;
+  const int y = row + FIRST, x = (in_image - row * segments) * VEC_BLOCK + threadIdx.x + FIRST;
+  int32_t k[2][3];
+  int n_keys = 0, m[2] = {0, 0}, sx[2] = {0, 0}, sy[2] = {0, 0};
+  bool rep[2] = {false, false}, tl_invalid = false;
+  if (x < nx) {
+    n_keys = window_keys<BC>(image, y, x, nx, ny, n_grain, k, tl_invalid);
+    for (int i = 0; i < n_keys; ++i) rep[i] = window_represents<BC>(image, y, x, nx, ny, n_grain, R, k[i], m[i], sx[i], sy[i]);
+  }
+  const int mine = (rep[0] ? 1 : 0) + (rep[1] ? 1 : 0);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const uint64_t one = __ballot(mine >= 1), two = __ballot(mine == 2);
+  if (lane == 0) wave_total[wave] = __popcll(one) + __popcll(two);
+  __syncthreads();
+  if (!EMIT) {
+    if (threadIdx.x == 0) {
+      int total = 0;
+      for (int w = 0; w < VEC_WAVES; ++w) total += wave_total[w];
+      A.workspace[blockIdx.x] = total;
+    }
+    unsigned long long* status = (unsigned long long*)A.status + (int64_t)b * GGNN_JUNCTION_STATUS_WORDS;
+    const unsigned long long quads = wave_sum(n_keys == 2 ? 1 : 0), merged = wave_sum((unsigned long long)(n_keys - mine)),
+                             invalid = wave_sum(tl_invalid ? 1 : 0);
+    if (lane == 0) {
+      if (quads) atomicAdd(status + 1, quads);
+      if (merged) atomicAdd(status + 2, merged);
+      if (invalid) atomicAdd(status + 3, invalid);
+    }
+    // the pixel counts: the image's own word of the TL pixel (id 1 of a no-flux image included: the counts are a histogram)
+    int32_t id = 0;
+    if (x < nx && x >= 0 && y >= 0) {
+      id = image[(int64_t)y * nx + x];
+      id = id >= 1 && id <= n_grain ? id : 0;
+    }
+    const int32_t before = __shfl_up(id, 1);
+    const bool head = lane == 0 || id != before;
+    const uint64_t heads = __ballot(head);
+    if (head && id) {
+      const uint64_t above = lane == 63 ? 0 : heads >> (lane + 1);
+      const int run = above ? __ffsll((unsigned long long)above) : 64 - lane;
+      atomicAdd((unsigned long long*)A.pixel_counts + g0 + id - 1, (unsigned long long)run);
+    }
+    return;
+  }
+  if (!mine) return;
+  const uint64_t below = lane ? ~0ull >> (64 - lane) : 0;
+  int64_t j = (int64_t)A.workspace[blockIdx.x] + __popcll(one & below) + __popcll(two & below);
+  for (int w = 0; w < wave; ++w) j += wave_total[w];
+  const int64_t ld = 3 * A.joint_capacity;
+  for (int i = 0; i < n_keys; ++i) {
+    if (!rep[i]) continue;
+    if (j >= 0 && j < A.joint_capacity) {
+      // the position and the wall snap: image_junctions_kernel's expressions, operation for operation
+      const float qx = __fdiv_rn((float)sx[i], (float)m[i]), qy = __fdiv_rn((float)sy[i], (float)m[i]);
+      float px = __fmul_rn(__fadd_rn(__fadd_rn((float)x, A.offset), qx), A.pitch);
+      float py = __fmul_rn(__fadd_rn(__fadd_rn((float)y, A.offset), qy), A.pitch);
+      if (BC == GGNN_BC_NOFLUX && k[i][0] == 0) {
+        const float two_off = __fmul_rn(2.0f, A.offset);
+        const float max_y = __fdiv_rn(__fadd_rn((float)(ny - 2), two_off), __fadd_rn((float)(nx - 2), two_off));
+        px = x == -1 ? 0.0f : x == nx - 1 ? 1.0f : fminf(fmaxf(px, 0.0f), 1.0f);
+        py = y == -1 ? 0.0f : y == ny - 1 ? max_y : fminf(fmaxf(py, 0.0f), max_y);
+      }
+      A.xy[2 * j] = px;
+      A.xy[2 * j + 1] = py;
+      for (int c = 0; c < 3; ++c) {
+        const int64_t g = g0 + k[i][c];   // (below the union's n_grain < 2^31)
+        A.triples[3 * j + c] = (int32_t)g;
+        A.edge_gj[3 * j + c] = g;
+        A.edge_gj[ld + 3 * j + c] = j;
+      }
+    }
+    ++j;
+  }
+}
+
+// One block: the exclusive scan of the block counts in place; per image joint_off (behind the status rows), n_joint, overflow
+// and the grains that have pixels (local ids from first_local: 0, or 1 for a no-flux image, whose local grain 0 is the
+// boundary grain).  The images' present grains are summed in LDS for the first VEC_SCAN_BLOCK images, in memory beyond.
+__global__ __launch_bounds__(VEC_SCAN_BLOCK) void junction_scan_traj_kernel(int32_t* __restrict__ count, int64_t n_blocks,
+                                                                            int64_t per_image,
+                                                                            const uint64_t* __restrict__ pixel_counts,
+                                                                            const int64_t* __restrict__ grain_off,
+                                                                            int64_t first_local, int64_t n_grain, int64_t n_image,
+                                                                            int64_t joint_capacity, int64_t* __restrict__ status) {
+  __shared__ long long part[VEC_SCAN_BLOCK];
+  __shared__ unsigned int present[VEC_SCAN_BLOCK];
+  const int t = threadIdx.x;
+  const int64_t per = (n_blocks + VEC_SCAN_BLOCK - 1) / VEC_SCAN_BLOCK;
+  const int64_t begin = min((int64_t)t * per, n_blocks), end = min(begin + per, n_blocks);
+  long long sum = 0;
+  for (int64_t i = begin; i < end; ++i) sum += count[i];
+  part[t] = sum;
+  present[t] = 0;
+  __syncthreads();
+  for (int s = 1; s < VEC_SCAN_BLOCK; s <<= 1) {   // inclusive scan of the threads' sums
+    const long long add = t >= s ? part[t - s] : 0;
+    __syncthreads();
+    part[t] += add;
+    __syncthreads();
+  }
+  long long at = part[t] - sum;
+  for (int64_t i = begin; i < end; ++i) {
+    const int32_t c = count[i];
+    count[i] = (int32_t)at;   // (at most 512 junctions a block, at most 2^22 blocks)
+    at += c;
+  }
+  for (int64_t g = t; g < n_grain; g += VEC_SCAN_BLOCK) {
+    if (pixel_counts[g] == 0) continue;
+    const int64_t b = segment_of(grain_off, n_image, g);
+    int32_t n;
+    const int64_t g0 = image_grains(grain_off, b, n_grain, n);
+    if (g < g0 + first_local || g >= g0 + n) continue;
+    if (b < VEC_SCAN_BLOCK)
+      atomicAdd(&present[b], 1u);
+    else
+      atomicAdd((unsigned long long*)status + b * GGNN_JUNCTION_STATUS_WORDS + 5, 1ull);
+  }
+  __syncthreads();   // (the scan in `count` and the LDS sums, for every thread of the block)
+  const long long total = part[VEC_SCAN_BLOCK - 1];
+  int64_t* joint_off = status + n_image * GGNN_JUNCTION_STATUS_WORDS;
+  for (int64_t b = t; b < n_image; b += VEC_SCAN_BLOCK) {
+    const long long lo = count[b * per_image], hi = b + 1 < n_image ? (long long)count[(b + 1) * per_image] : total;
+    int64_t* s = status + b * GGNN_JUNCTION_STATUS_WORDS;
+    joint_off[b] = lo;
+    s[0] = hi - lo;
+    if (b < VEC_SCAN_BLOCK) s[5] = present[b];
+    s[6] = hi > joint_capacity ? 1 : 0;
+  }
+  if (t == 0) joint_off[n_image] = total;
+}
+
+__global__ __launch_bounds__(256) void zero_open_pairs_kernel(int64_t* __restrict__ status, int64_t n_image) {
+  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b < n_image) status[b * GGNN_JUNCTION_STATUS_WORDS + 4] = 0;
+}
+
+// junction_links_kernel on the union: triples and rows hold union grains, a pair's partner lies in its grain's row and so in
+// its image; an open slot is counted in the status row of the image that joint_off puts the junction in.
+__global__ __launch_bounds__(256) void junction_links_traj_kernel(const ggnn_link_traj_args A) {
+  const int64_t* joint_off = A.status + A.n_image * GGNN_JUNCTION_STATUS_WORDS;
+  const int64_t n = min(max(joint_off[A.n_image], (int64_t)0), A.joint_capacity);
+  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= 3 * n) return;
+  const int64_t j = s / 3;
+  const int k = (int)(s - 3 * j);
+  const int32_t a = A.triples[3 * j + (k == 2 ? 1 : 0)], b = A.triples[3 * j + (k == 0 ? 1 : 2)];
+  int found = 0;
+  int64_t partner = -1;
+  if (a >= 0 && a < A.n_grain) {
+    const int64_t p0 = min((int64_t)max(A.rowptr[a], 0), A.E_cap);
+    const int64_t p1 = min(max((int64_t)A.rowptr[a + 1], p0), A.E_cap);
+    for (int64_t p = p0; p < p1; ++p) {
+      const int64_t o = A.col[p];
+      if (o < 0 || o >= n || o == j) continue;
+      if (A.triples[3 * o] == b || A.triples[3 * o + 1] == b || A.triples[3 * o + 2] == b) ++found, partner = o;
+    }
+  }
+  A.edge_jj[s] = j;
+  A.edge_jj[3 * A.joint_capacity + s] = found == 1 ? partner : -1;
+  if (found != 1)   // (rare: none in a valid structure)
+    atomicAdd((unsigned long long*)A.status + segment_of(joint_off, A.n_image, j) * GGNN_JUNCTION_STATUS_WORDS + 4, 1ull);
+}
+
 }  // namespace ggnn
 
 extern "C" int ggnn_image_junctions(const ggnn_junction_args* args, ggnn_stream_t stream) {
@@ -314,5 +515,56 @@ extern "C" int ggnn_junction_links(const ggnn_link_args* args, ggnn_stream_t str
   if (hipMemsetAsync(A.status + 4, 0, sizeof(int64_t), st) != hipSuccess) return GGNN_ELAUNCH;
   const int64_t blocks = (3 * A.joint_capacity + 255) / 256;
   hipLaunchKernelGGL(junction_links_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A);
+  return launch_status();
+}
+
+extern "C" int ggnn_image_junctions_traj(const ggnn_junction_traj_args* args, ggnn_stream_t stream) {
+  using namespace ggnn;
+  if (!args) return GGNN_EINVAL;
+  const ggnn_junction_traj_args& A = *args;
+  if (!A.images || !A.grain_off || !A.pixel_counts || !A.xy || !A.triples || !A.edge_gj || !A.status || !A.workspace)
+    return GGNN_EINVAL;
+  if (A.merge_radius < 0 || A.merge_radius > VEC_MAX_RADIUS) return GGNN_EINVAL;
+  if (A.nx <= 2 * A.merge_radius || A.ny <= 2 * A.merge_radius || A.nx >= (1 << 15) || A.ny >= (1 << 15)) return GGNN_EINVAL;
+  if (A.n_image < 1 || A.n_image > GGNN_JUNCTION_MAX_BLOCKS) return GGNN_EINVAL;
+  if (A.n_grain < 1 || A.n_grain >= INT32_MAX - 1) return GGNN_EINVAL;
+  if (A.joint_capacity < 1 || A.joint_capacity > INT32_MAX / 3) return GGNN_EINVAL;
+  if (!(A.pitch > 0.0f) || !(A.offset >= 0.0f) || A.pitch > 1.0f || A.offset > 1.0f) return GGNN_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(A.status) | reinterpret_cast<uintptr_t>(A.edge_gj) |
+       reinterpret_cast<uintptr_t>(A.pixel_counts) | reinterpret_cast<uintptr_t>(A.grain_off)) & 7u)
+    return GGNN_EINVAL;
+  if (A.boundary != GGNN_BC_PERIODIC && A.boundary != GGNN_BC_NOFLUX) return GGNN_EINVAL;
+  const bool periodic = A.boundary == GGNN_BC_PERIODIC;
+  const int64_t wx = periodic ? A.nx : A.nx + 1, wy = periodic ? A.ny : A.ny + 1;   // the windows of a row, the rows
+  const int segments = (int)((wx + VEC_BLOCK - 1) / VEC_BLOCK);
+  const int64_t per_image = wy * segments, n_blocks = A.n_image * per_image;          // (< 2^22 2^22: no overflow)
+  if (n_blocks > GGNN_JUNCTION_MAX_BLOCKS) return GGNN_EINVAL;
+  if (A.workspace_bytes < (size_t)n_blocks * sizeof(int32_t)) return GGNN_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(A.status, 0, (size_t)A.n_image * GGNN_JUNCTION_STATUS_WORDS * sizeof(int64_t), st) != hipSuccess)
+    return GGNN_ELAUNCH;
+  if (hipMemsetAsync(A.pixel_counts, 0, (size_t)A.n_grain * sizeof(uint64_t), st) != hipSuccess) return GGNN_ELAUNCH;
+  const auto count = periodic ? image_junctions_traj_kernel<false, GGNN_BC_PERIODIC> : image_junctions_traj_kernel<false, GGNN_BC_NOFLUX>;
+  const auto emit = periodic ? image_junctions_traj_kernel<true, GGNN_BC_PERIODIC> : image_junctions_traj_kernel<true, GGNN_BC_NOFLUX>;
+  hipLaunchKernelGGL(count, dim3((unsigned)n_blocks), dim3(VEC_BLOCK), 0, st, A, segments, (int)wy);
+  hipLaunchKernelGGL(junction_scan_traj_kernel, dim3(1), dim3(VEC_SCAN_BLOCK), 0, st, A.workspace, n_blocks, per_image,
+                     A.pixel_counts, A.grain_off, (int64_t)(periodic ? 0 : 1), A.n_grain, A.n_image, A.joint_capacity, A.status);
+  hipLaunchKernelGGL(emit, dim3((unsigned)n_blocks), dim3(VEC_BLOCK), 0, st, A, segments, (int)wy);
+  return launch_status();
+}
+
+extern "C" int ggnn_junction_links_traj(const ggnn_link_traj_args* args, ggnn_stream_t stream) {
+  using namespace ggnn;
+  if (!args) return GGNN_EINVAL;
+  const ggnn_link_traj_args& A = *args;
+  if (!A.triples || !A.rowptr || !A.col || !A.edge_jj || !A.status) return GGNN_EINVAL;
+  if (A.n_grain < 1 || A.n_grain >= INT32_MAX - 1 || A.E_cap < 0 || A.E_cap >= INT32_MAX) return GGNN_EINVAL;
+  if (A.joint_capacity < 1 || A.joint_capacity > INT32_MAX / 3) return GGNN_EINVAL;
+  if (A.n_image < 1 || A.n_image > GGNN_JUNCTION_MAX_BLOCKS) return GGNN_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(A.status) | reinterpret_cast<uintptr_t>(A.edge_jj)) & 7u) return GGNN_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(zero_open_pairs_kernel, dim3((unsigned)((A.n_image + 255) / 256)), dim3(256), 0, st, A.status, A.n_image);
+  const int64_t blocks = (3 * A.joint_capacity + 255) / 256;
+  hipLaunchKernelGGL(junction_links_traj_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A);
   return launch_status();
 }

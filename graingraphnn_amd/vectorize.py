@@ -18,8 +18,14 @@ when its triple holds grain 0, wall junctions are linked along the walls through
 to the wall is exactly 0, 1 or `max_y`, and the four corner pixels come back as the `corner_grains` that `grain_image`
 fills the corners from (tests/vectorcheck_noflux.py restates the rule).
 
-Not covered: unions of trajectories, stacks of frames, and resolving a quadruple from a history (the diagonal is fixed,
-and counted in the status)."""
+A STACK of equal-shaped images becomes one disjoint union in one go (`graphs_from_images`, `samples_from_images`;
+ggnn_image_junctions_traj, ggnn_junction_links_traj; tests/vectorcheck_union.py): the rule per image, grains and
+junctions numbered image after image, a status per image, and the trajectory offsets that `GrainRollout(traj_offsets=)`,
+`enable_events`, `enable_qoi` and `enable_polygons` take.  The launches do not depend on the number of images and there is
+one read-back.  The frames of a recorded sequence go the same way, each vectorised on its own.
+
+Not covered: stacks of mixed image shapes, tracking junctions between frames, and resolving a quadruple from a history (the
+diagonal is fixed, and counted in the status)."""
 import ctypes
 import math
 
@@ -206,3 +212,212 @@ def sample_from_image(image, theta_x, theta_z, G, R, span=None, patch_pixels=Non
     be.step_refresh(x_joint, x_grain, math.inf, flags,
                     [(ei[et], x[et[0]], x[et[2]], ea[et]) for et in EDGE_TYPES])
     return x, ei, ea
+
+
+# ---- a stack of images into one union ------------------------------------------------------------------------------------
+
+def _stack(images):
+    """[B, ny, nx] int32, contiguous, on the device, from a tensor or a list of equal-shaped [ny, nx] tensors."""
+    if isinstance(images, (list, tuple)):
+        if not images or any(not isinstance(i, torch.Tensor) or i.dim() != 2 or i.shape != images[0].shape for i in images):
+            raise _lib.GGNNError("images must be equal-shaped [ny, nx] device tensors (one shape a stack)")
+        images = torch.stack(list(images))
+    if not isinstance(images, torch.Tensor) or not images.is_cuda or images.dim() != 3 or images.size(0) < 1:
+        raise _lib.GGNNError("images must be a [B, ny, nx] device tensor of grain ids, or a list of [ny, nx] device tensors")
+    if images.dtype not in (torch.int16, torch.int32, torch.int64, torch.uint8):
+        raise _lib.GGNNError("images must hold integers")
+    return images.to(torch.int32).contiguous()
+
+
+def grain_offsets(n_grains, device):
+    """The union's grain offsets of per-image grain counts: (host list [B + 1], int64 device tensor)."""
+    n_grains = [int(n) for n in n_grains]
+    if not n_grains or min(n_grains) < 1:
+        raise _lib.GGNNError("n_grains must hold one count of at least 1 per image")
+    off = np.concatenate([[0], np.cumsum(n_grains, dtype=np.int64)]).astype(np.int64)
+    return off.tolist(), torch.from_numpy(off).to(device)
+
+
+def _vectorize_union(images, n_grains, grid, merge_radius, joint_capacity, boundary="periodic", grain_off=None):
+    """`_vectorize` for a stack: every launch, no read-back.  images: what `_stack` returns; grain_off: what `grain_offsets`
+    returns (None: formed here, an upload -- pass it to a stream capture).  The status tensor holds the B status rows, behind
+    them joint_off [B + 1] and, for no-flux, the 4 B corner pixels: one read-back fetches them all."""
+    be = default_backend()
+    _check_boundary(boundary)
+    noflux = boundary == "noflux"
+    if grid not in GRIDS:
+        raise _lib.GGNNError(f"grid must be 'cells' or 'points', got {grid!r}")
+    B, ny, nx = images.shape
+    dev = images.device
+    if len(n_grains) != B:
+        raise _lib.GGNNError("n_grains must hold one count per image")
+    off_host, off_dev = grain_offsets(n_grains, dev) if grain_off is None else grain_off
+    n_total, R = off_host[-1], int(merge_radius)
+    cap = 3 * n_total + 16 * B if joint_capacity is None else int(joint_capacity)
+    counts = torch.empty(n_total, dtype=torch.int64, device=dev)       # (zeroed by the call)
+    xy = torch.zeros(cap, 2, dtype=torch.float32, device=dev)
+    triples = torch.zeros(cap, 3, dtype=torch.int32, device=dev)
+    slots = torch.arange(cap, dtype=torch.int64, device=dev).repeat_interleave(3)   # (spare rows: see _vectorize)
+    gj = torch.stack([slots + n_total, slots])
+    jj = torch.full((2, 3 * cap), -1, dtype=torch.int64, device=dev)
+    W = _lib.GGNN_JUNCTION_STATUS_WORDS
+    status = torch.zeros(B * W + B + 1 + (4 * B if noflux else 0), dtype=torch.int64, device=dev)
+    if noflux:   # per image, the order of grain_image(corner_grains=)
+        status[B * W + B + 1:] = torch.stack([images[:, 0, 0], images[:, 0, -1], images[:, -1, 0], images[:, -1, -1]], 1).reshape(-1)
+    wy, wx = (ny + 1, nx + 1) if noflux else (ny, nx)
+    words = B * wy * ((wx + _lib.GGNN_JUNCTION_SEGMENT - 1) // _lib.GGNN_JUNCTION_SEGMENT)
+    ws = torch.empty(words, dtype=torch.int32, device=dev)
+    off, pitch = GRIDS[grid](nx)
+    A = _lib.JunctionTrajArgs()
+    A.images, A.grain_off, A.pixel_counts, A.xy = _lib.ptr(images), _lib.ptr(off_dev), _lib.ptr(counts), _lib.ptr(xy)
+    A.triples, A.edge_gj, A.status, A.workspace, A.workspace_bytes = (_lib.ptr(triples), _lib.ptr(gj), _lib.ptr(status),
+                                                                      _lib.ptr(ws), 4 * ws.numel())
+    A.nx, A.ny, A.n_image, A.n_grain, A.joint_capacity = nx, ny, B, n_total, cap
+    A.offset, A.pitch, A.merge_radius, A.boundary = float(off), float(pitch), R, BOUNDARIES[boundary]
+    _lib.check(be.lib.ggnn_image_junctions_traj(ctypes.byref(A), _lib.current_stream()), "ggnn_image_junctions_traj")
+    csr = be.build_csr_batch([(gj.flip(0).contiguous(), cap, n_total + cap)], check=False)[0]
+    L = _lib.LinkTrajArgs()
+    L.triples, L.rowptr, L.col, L.edge_jj, L.status = (_lib.ptr(triples), _lib.ptr(csr.rowptr), _lib.ptr(csr.col),
+                                                       _lib.ptr(jj), _lib.ptr(status))
+    L.n_grain, L.joint_capacity, L.E_cap, L.n_image = n_total, cap, csr.col.numel(), B
+    _lib.check(be.lib.ggnn_junction_links_traj(ctypes.byref(L), _lib.current_stream()), "ggnn_junction_links_traj")
+    return {"xy": xy, "triples": triples, "gj": gj, "jj": jj, "status": status, "counts": counts, "csr": csr,
+            "n_grain": n_total, "n_image": B, "grain_off": off_host, "grain_off_dev": off_dev, "capacity": cap,
+            "shape": (ny, nx), "boundary": boundary, "max_y": image_max_y(nx, ny, grid) if noflux else None,
+            "calls": (A, L, images, ws)}
+
+
+def _graphs(images, n_grains, grid, merge_radius, joint_capacity, strict, boundary="periodic"):
+    """graphs_from_images' dict, with the capacity-sized arrays behind it as a second result."""
+    _check_boundary(boundary)
+    images = _stack(images)
+    if n_grains is None:
+        n_grains = images.amax(dim=(1, 2)).tolist()   # (a read-back of its own: pass n_grains to avoid it)
+    v = _vectorize_union(images, n_grains, grid, merge_radius, joint_capacity, boundary)
+    words = v["status"].tolist()                      # the one read-back
+    B, W, cap = v["n_image"], len(STATUS_WORDS), v["capacity"]
+    status = [dict(zip(STATUS_WORDS, words[b * W:(b + 1) * W])) for b in range(B)]
+    joint_off = [min(o, cap) for o in words[B * W:B * W + B + 1]]
+    corners = None
+    if boundary == "noflux":
+        corners = [tuple(words[B * W + B + 1 + 4 * b:B * W + B + 5 + 4 * b]) for b in range(B)]
+    v["corner_grains"] = corners
+    bad = [b for b in range(B) if not status_is_valid(status[b], boundary)]
+    if strict and bad:
+        raise ValueError(f"{len(bad)} of {B} images are not valid {boundary} grain structures: "
+                         + "; ".join(f"image {b}: {status[b]}" for b in bad)
+                         + f" (valid: overflow, n_invalid_pixels and n_open_pairs 0 and {EULER[boundary]}; joint_capacity {cap} "
+                           "for the union)")
+    n = joint_off[-1]
+    gj = v["gj"][:, :3 * n].contiguous()
+    ei = {EDGE_TYPES[0]: gj, EDGE_TYPES[1]: gj.flip(0).contiguous(), EDGE_TYPES[2]: v["jj"][:, :3 * n].contiguous()}
+    out = {"xy": v["xy"][:n].contiguous(), "triples": v["triples"][:n].contiguous(), "edge_index_dict": ei, "status": status,
+           "traj_offsets": {"grain": list(v["grain_off"]), "joint": joint_off}}
+    if boundary == "noflux":
+        out["corner_grains"], out["max_y"] = corners, v["max_y"]
+    return out, v
+
+
+def graphs_from_images(images, n_grains=None, grid="cells", merge_radius=2, joint_capacity=None, strict=True,
+                       boundary="periodic"):
+    """The junction graphs of a stack of grain-ID images as ONE disjoint union: `graph_from_image`'s rule per image, in a
+    number of launches that does not depend on the number of images, with one read-back.
+
+    images: integer [B, ny, nx] on the device, or a list of B equal-shaped [ny, nx] device tensors (one shape a stack: the
+    project keeps one box per union); n_grains: the B grain counts (None: each image's largest id, at the price of a
+    read-back); grid, merge_radius, boundary: as in `graph_from_image`, the same for every image; joint_capacity: room for
+    the junctions of the whole union (default 3 sum(n_grains) + 16 B).
+
+    -> dict: `xy` float32 [n_joint, 2], `triples` int32 [n_joint, 3] and `edge_index_dict` (int64 [2, 3 n_joint] per edge
+    type) of the union -- image b's grains are traj_offsets["grain"][b] .. and its junctions traj_offsets["joint"][b] ..,
+    numbered within the image as `graph_from_image` numbers them --, `status`: a list of B dicts,
+    `traj_offsets` = {"grain": [B + 1], "joint": [B + 1]} (host lists, as GrainRollout, enable_events, enable_qoi and
+    enable_polygons take them); boundary="noflux": also `corner_grains`, a list of B 4-tuples, and `max_y`.
+    `union_member(result, t)` is image t's own graph.
+
+    strict: raise ValueError naming every invalid image and its counters (status_is_valid per image); strict=False returns
+    what was found, with -1 as the destination of a joint->joint column whose pair has no partner or more than one."""
+    return _graphs(images, n_grains, grid, merge_radius, joint_capacity, strict, boundary)[0]
+
+
+def union_member(result, t):
+    """Trajectory t of `graphs_from_images`' result with local indices, in the shape of `graph_from_image`'s return value:
+    (xy, triples, edge_index_dict, status), for no-flux with (corner_grains, max_y) behind them."""
+    og, oj = result["traj_offsets"]["grain"], result["traj_offsets"]["joint"]
+    if not 0 <= t < len(og) - 1:
+        raise _lib.GGNNError(f"the union has {len(og) - 1} trajectories, got {t}")
+    g0, j0, j1 = og[t], oj[t], oj[t + 1]
+    ei = result["edge_index_dict"]
+    gj = ei[EDGE_TYPES[0]][:, 3 * j0:3 * j1].clone()
+    gj[0] -= g0
+    gj[1] -= j0
+    jj = ei[EDGE_TYPES[2]][:, 3 * j0:3 * j1].clone()
+    jj[0] -= j0
+    jj[1] = torch.where(jj[1] >= 0, jj[1] - j0, jj[1])
+    own = {EDGE_TYPES[0]: gj, EDGE_TYPES[1]: gj.flip(0).contiguous(), EDGE_TYPES[2]: jj}
+    out = (result["xy"][j0:j1].contiguous(), result["triples"][j0:j1] - g0, own, result["status"][t])
+    if "corner_grains" in result:
+        out += (result["corner_grains"][t], result["max_y"])
+    return out
+
+
+def samples_from_images(images, theta_x, theta_z, G, R, span=None, patch_pixels=None, **kw):
+    """A union rollout's first state from a stack of grain-ID images: device (x_dict, edge_index_dict, edge_attr,
+    traj_offsets), every trajectory's rows being `sample_from_image`'s of its image, bit for bit.
+
+    theta_x, theta_z: lists of B arrays, one angle per grain of the image (their lengths are the grain counts); G, R: scalars
+    or length-B sequences, the per-trajectory process columns; span: one value for the union (None: `span_for(G_b, R_b)`,
+    which must agree across the images); patch_pixels: as in `sample_from_image`.  The area column comes from the
+    per-image pixel counts of the vectorisation, grain centres and edge lengths from one ggnn_grain_centres and one edge
+    refresh on the union.  Other keywords go to `graphs_from_images`; an invalid structure always raises.
+
+    boundary="noflux": what `GrainRollout(..., boundary="noflux", traj_offsets=traj_offsets, max_y=image_max_y(nx, ny, grid))`
+    takes; the row of every trajectory's boundary grain is reset as `sample_from_image` resets grain 0's."""
+    from .generator import feature_rows
+    from .synthetic import span_for
+    tx = [np.asarray(t, np.float64).ravel() for t in theta_x]
+    tz = [np.asarray(t, np.float64).ravel() for t in theta_z]
+    B = len(tx)
+    if B < 1 or len(tz) != B or any(len(a) != len(b) for a, b in zip(tx, tz)):
+        raise _lib.GGNNError("theta_x and theta_z must be lists of one array per image, one angle per grain")
+    n_grains = kw.pop("n_grains", None) or [len(t) for t in tx]
+    if [int(n) for n in n_grains] != [len(t) for t in tx]:
+        raise _lib.GGNNError("theta_x and theta_z must hold one angle per grain")
+    try:
+        Gs = [float(g) for g in np.broadcast_to(np.asarray(G, np.float64), (B,))]
+        Rs = [float(r) for r in np.broadcast_to(np.asarray(R, np.float64), (B,))]
+    except ValueError as exc:
+        raise _lib.GGNNError("G and R must be scalars or hold one value per image") from exc
+    if span is None:
+        spans = sorted({span_for(g, r) for g, r in zip(Gs, Rs)})
+        if len(spans) != 1:
+            raise _lib.GGNNError(f"the images' (G, R) give the frame spans {spans}: a union has one, pass span=")
+        span = spans[0]
+    kw.pop("strict", None)
+    boundary = kw.pop("boundary", "periodic")
+    res, v = _graphs(images, n_grains, kw.pop("grid", "cells"), kw.pop("merge_radius", 2), kw.pop("joint_capacity", None),
+                     True, boundary)
+    if kw:
+        raise TypeError(f"samples_from_images: unknown keywords {sorted(kw)}")
+    be, xy, ei = default_backend(), res["xy"], res["edge_index_dict"]
+    dev, oj = xy.device, res["traj_offsets"]["joint"]
+    ny, nx = v["shape"]
+    rows = [feature_rows(tx[b], tz[b], oj[b + 1] - oj[b], Gs[b], Rs[b], span) for b in range(B)]
+    x_grain = torch.from_numpy(np.concatenate([fg for fg, _ in rows]).astype(np.float32)).to(dev)
+    x_joint = torch.from_numpy(np.concatenate([fj for _, fj in rows]).astype(np.float32)).to(dev)
+    x_joint[:, :2] = xy
+    x_grain[:, 3] = (v["counts"].to(torch.float64) / float(patch_pixels or nx * ny)).to(torch.float32)
+    csr, n_total = v["csr"], v["n_grain"]
+    csr_jg = type(csr)(csr.rowptr[:n_total + 1], csr.col, csr.perm, csr.row, csr.unit_ptr, csr.units, csr.E)
+    be.grain_centres(csr_jg, x_joint, x_grain, boundary=boundary)
+    if boundary == "noflux":   # every trajectory's boundary grain as ggnn_noflux_boundary_traj resets it
+        first = v["grain_off_dev"][:-1]
+        x_grain[first, :2] = 0.5
+        x_grain[first, 3:5] = 0.0
+        x_grain[first, 10] = 0.0
+    ea = {et: torch.zeros(ei[et].size(1), 1, dtype=torch.float32, device=dev) for et in EDGE_TYPES}
+    x = {"grain": x_grain, "joint": x_joint}
+    flags = torch.zeros(2, dtype=torch.int32, device=dev)
+    be.step_refresh(x_joint, x_grain, math.inf, flags,
+                    [(ei[et], x[et[0]], x[et[2]], ea[et]) for et in EDGE_TYPES])
+    return x, ei, ea, res["traj_offsets"]

@@ -951,8 +951,10 @@ int ggnn_image_compare(const int32_t* image, const int32_t* truth, int64_t n_pix
  * The junction graph of a grain-ID image: the inverse of ggnn_polygons_rasterize, the way into a rollout for a structure
  * that exists as an image (an EBSD map, a phase-field cross-section).  The reference has no such step: its graphs come from
  * its generator or from its phase-field solver's junction tracks (`node_region`, graph_trajectory.py:316-376).  On demand,
- * on `stream`; setup work, not part of a step.  Periodic images and images with no-flux walls (`boundary`, below); unions,
- * stacks of frames and resolving a quadruple from a history are not covered.
+ * on `stream`; setup work, not part of a step.  Periodic images and images with no-flux walls (`boundary`, below); a stack
+ * of equal-shaped images -- the trajectories of a union, or the frames of a sequence, each on its own -- goes through the
+ * _traj forms further down.  Stacks of mixed shapes, tracking junctions between frames and resolving a quadruple from a
+ * history are not covered.
  * ggnn_image_junctions = memset of the status + three launches (count per block, scan of the blocks, emit).  The rule is
  * exact in integers up to the one fp32 expression of a position (tests/vectorcheck.py restates it):
  *   image     : int32 [ny, nx], pixel p = grain p - 1 (as ggnn_polygons_rasterize writes), periodic in both directions
@@ -1040,6 +1042,61 @@ typedef struct ggnn_link_args {
   int64_t n_grain, joint_capacity, E_cap;
 } ggnn_link_args;
 int ggnn_junction_links(const ggnn_link_args* args, ggnn_stream_t stream);
+/* The same for a STACK of images, into the disjoint union of their graphs: images int32 [n_image, ny, nx] (one shape a
+ * stack), image b holding the union's grains grain_off[b] .. grain_off[b + 1] - 1, pixel p of image b = union grain
+ * grain_off[b] + p - 1.  The rule is the one above applied per image, for both boundaries: windows, keys, the TL-BR diagonal,
+ * representatives within merge_radius, the fp32 position expression in its order, the wall snap and max_y -- with n_grain =
+ * grain_off[b + 1] - grain_off[b], read on the device.  A periodic wrap, a clipped no-flux offset and a no-flux outside pixel
+ * stay inside their image; indices into the stack are 64-bit.
+ *   numbering : junctions image after image, raster order (then ascending key) within an image: the blocks are laid out
+ *               image-major, (image, row, segment), so block order is union order and one scan block serves, as above.
+ *               triples and row 0 of edge_gj hold UNION grains, row 1 of edge_gj and both rows of edge_jj union junctions.
+ *   status    : int64 [n_image, GGNN_JUNCTION_STATUS_WORDS], zeroed by the call: the seven words above per image --
+ *               n_present_grains counts that image's ids, n_invalid_pixels judges a pixel by its own image's grain count,
+ *               n_open_pairs goes to the image of the junction, overflow is 1 for every image whose last junction lies
+ *               beyond joint_capacity (the capacity is the union's) -- and DIRECTLY BEHIND them joint_off int64
+ *               [n_image + 1], written by the scan: image b's junctions are joint_off[b] .. joint_off[b + 1] - 1 and
+ *               joint_off[n_image] is the union's n_joint (not clamped to the capacity).  One read-back fetches both.
+ *   counts    : pixel_counts uint64 [n_grain] (n_grain = the union's), zeroed and filled by the count pass: the pixels of
+ *               union grain g = the pixels of its image with the id g - grain_off[b] + 1, exact; ids outside the image's range
+ *               are not counted.  No launch per image, and none beside the three.
+ *   grain_off : device memory, so not validated but clamped: every offset to [0, n_grain], an image's end to its begin at
+ *               least.  An image with no grain carries nothing: all its pixels are invalid.
+ * Nothing is written at or beyond joint_capacity, and nothing between the union's n_joint and it.  The launches -- two
+ * memsets, count, scan, emit -- do not depend on n_image.  The grid is n_image * rows * segments blocks (rows and segments as
+ * above for the boundary), at most GGNN_JUNCTION_MAX_BLOCKS: a block holds at most 512 junctions, so the int32 scan cannot
+ * overflow.  GGNN_EINVAL without a launch: as ggnn_image_junctions (n_grain is the union's; grain_off too must be 8-byte
+ * aligned), n_image < 1, a grid beyond GGNN_JUNCTION_MAX_BLOCKS, a workspace below one word a block.
+ * ggnn_junction_links_traj = two launches: word 4 of every status row zeroed, then ggnn_junction_links' search on the union
+ * (rowptr / col: the union's joint->grain table; a pair's partner lies in its first grain's row and so in its own image);
+ * an open slot is counted in the row of the image that joint_off puts its junction in.  It reads joint_off behind the status
+ * rows.  GGNN_EINVAL without a launch: as ggnn_junction_links, and n_image outside [1, GGNN_JUNCTION_MAX_BLOCKS]. */
+#define GGNN_JUNCTION_MAX_BLOCKS (1 << 22)
+typedef struct ggnn_junction_traj_args {
+  const int32_t* images;         /* [n_image, ny, nx], device */
+  const int64_t* grain_off;      /* [n_image + 1], device, rising from 0 */
+  uint64_t* pixel_counts;        /* [n_grain] out */
+  float* xy;                     /* [joint_capacity, 2] out */
+  int32_t* triples;              /* [joint_capacity, 3] out */
+  int64_t* edge_gj;              /* [2, 3 joint_capacity] out */
+  int64_t* status;               /* [n_image * GGNN_JUNCTION_STATUS_WORDS + n_image + 1] out: the status rows, then joint_off */
+  int32_t* workspace;            /* one int32 word a block of device scratch */
+  size_t workspace_bytes;
+  int64_t nx, ny, n_image, n_grain, joint_capacity;   /* n_grain, joint_capacity: the union's */
+  float offset, pitch;
+  int32_t merge_radius;
+  int32_t boundary;              /* GGNN_BC_PERIODIC / GGNN_BC_NOFLUX */
+} ggnn_junction_traj_args;
+int ggnn_image_junctions_traj(const ggnn_junction_traj_args* args, ggnn_stream_t stream);
+typedef struct ggnn_link_traj_args {
+  const int32_t* triples;        /* [joint_capacity, 3], device: ggnn_image_junctions_traj's */
+  const int32_t* rowptr;         /* [>= n_grain + 1]: the union's joint->grain table's row pointers */
+  const int32_t* col;            /* [E_cap]: its columns */
+  int64_t* edge_jj;              /* [2, 3 joint_capacity] out */
+  int64_t* status;               /* ggnn_image_junctions_traj's: joint_off is read, word 4 of every row written */
+  int64_t n_grain, joint_capacity, E_cap, n_image;
+} ggnn_link_traj_args;
+int ggnn_junction_links_traj(const ggnn_link_traj_args* args, ggnn_stream_t stream);
 /* The host-side topology update those counts trigger: one call of the reference's `Cmodel.update`
  * (models.py:612-842 with delete_grain_index :861-893, switching_edge_index :896-1051, point_in_triangle :1055-1070,
  * periodic_move :1103-1106), nucleation off.  HOST memory throughout, no stream: grains of `grain_event` (those below the

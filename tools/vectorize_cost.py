@@ -10,7 +10,20 @@ timed by events per call, median of the rounds after three warm-up rounds.
 boundary grain) and the image read with walls.  The benchmark's generator makes periodic structures only, so the grains the
 seams cut touch two walls and the status reports their open pairs; the work -- the windows, the wall junctions in grain 0's
 row of the table, the links that walk it -- is that of a no-flux structure of this size.
-    python tools/vectorize_cost.py [--rounds 50] [--size 4096] [--boundary periodic|noflux]"""
+    python tools/vectorize_cost.py [--rounds 50] [--size 4096] [--boundary periodic|noflux]
+--union B times the union path at about bench.py's cfg4 shape instead (cfg4 has 118 grains a trajectory): B images of
+--size x --size (128 when not given) with 121 grains each -- Voronoi cells of a jittered brick lattice, made on the device from --seed; candidates that are no valid
+structure (an edge below a pixel) are dropped --, and prints
+  loop       B x sample_from_image, the results to the host, synthetic.disjoint_union, the union uploaded again: the only
+             route before samples_from_images
+  union      one samples_from_images
+  calls x B  B x (ggnn_image_compare + ggnn_image_junctions + ggnn_junction_links) on prepared arguments
+  calls      ggnn_image_junctions_traj + ggnn_junction_links_traj on prepared arguments
+loop and union by the host clock around work that ends in a synchronise (both hold host work), the calls by events; median of
+the rounds after three warm-up rounds, the arms alternating within a round.  The kernel launches of one loop and of one
+union call are counted by torch.profiler in a pass of their own after the timing, which also lists the device time of
+every kernel of the two union calls (the count, scan and emit passes by name).
+    python tools/vectorize_cost.py --union 64 [--rounds 20] [--boundary periodic]"""
 import argparse
 import ctypes
 import os
@@ -22,10 +35,16 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=50)
-    ap.add_argument("--size", type=int, default=4096)
+    ap.add_argument("--size", type=int, default=None, help="image side (default: 4096, with --union 128)")
     ap.add_argument("--boundary", choices=("periodic", "noflux"), default="periodic")
+    ap.add_argument("--union", type=int, default=0, metavar="B")
+    ap.add_argument("--seed", type=int, default=0)
     a = ap.parse_args()
     sys.path[:0] = [os.path.dirname(HERE)]
+    if a.size is None:
+        a.size = 128 if a.union else 4096
+    if a.union:
+        return union_cost(a)
     import numpy as np
     import torch
     import bench
@@ -66,6 +85,138 @@ def main():
         for name, t in times.items():
             t = np.array(t)
             print(f"{name:9s} us/call by events: median {np.median(t):8.1f}  min {t.min():8.1f}  max {t.max():8.1f}", flush=True)
+        print(f"# torch {torch.__version__}, {torch.cuda.get_device_name()}", flush=True)
+
+
+def lattice_images(B, size, seed, device, cells=11):
+    """[B, size, size] int32 periodic Voronoi images of cells x cells seeds on a jittered brick lattice (every other row
+    shifted by half a cell): ids 1 .. cells^2, nearest seed under the torus metric."""
+    import torch
+    gen = torch.Generator(device="cpu").manual_seed(seed)
+    iy, ix = torch.meshgrid(torch.arange(cells), torch.arange(cells), indexing="ij")
+    sx = (ix + 0.5 * (iy % 2) + 0.25).reshape(-1) / cells
+    sy = (iy + 0.25).reshape(-1) / cells
+    jitter = (torch.rand(B, 2, cells * cells, generator=gen) - 0.5) * (0.3 / cells)
+    px = ((torch.arange(size, dtype=torch.float32) + 0.5) / size).to(device)
+    out = []
+    for b in range(B):
+        x, y = (sx + jitter[b, 0]).to(device), (sy + jitter[b, 1]).to(device)
+        dx = (px[None, :, None] - x[None, None, :]).abs()
+        dy = (px[:, None, None] - y[None, None, :]).abs()
+        dx, dy = torch.minimum(dx, 1 - dx), torch.minimum(dy, 1 - dy)
+        out.append((dx * dx + dy * dy).argmin(dim=2).to(torch.int32) + 1)
+    return torch.stack(out)
+
+
+def union_cost(a):
+    import time
+    import numpy as np
+    import torch
+    from graingraphnn_amd import _lib, synthetic
+    from graingraphnn_amd import vectorize as vz
+    from graingraphnn_amd.backend import default_backend
+    from graingraphnn_amd.synthetic import EDGE_TYPES
+    if a.boundary != "periodic":
+        raise SystemExit("--union times periodic stacks")
+    B, size = a.union, a.size
+    dev = torch.device("cuda", 0)
+    lib, be = _lib.load(), default_backend()
+    with torch.no_grad():
+        candidates = lattice_images(B + B // 2 + 8, size, a.seed, dev)
+        n_grain = int(candidates.max())
+        status = vz.graphs_from_images(candidates, [n_grain] * len(candidates), strict=False)["status"]
+        valid = [i for i, s in enumerate(status) if vz.status_is_valid(s)]
+        print(f"# {len(valid)} of {len(candidates)} candidate images are valid structures", flush=True)
+        if len(valid) < B:
+            raise SystemExit("too few valid images: try another --seed")
+        images = candidates[valid[:B]].contiguous()
+        n_grains = [n_grain] * B
+        rs = np.random.RandomState(a.seed)
+        theta_x = [rs.uniform(0, np.pi / 2, n_grain) for _ in range(B)]
+        theta_z = [rs.uniform(0, np.pi / 2, n_grain) for _ in range(B)]
+        G, R, span = 2.0, 0.4, 6
+
+        def loop():
+            parts = []
+            for b in range(B):
+                x, ei, ea = vz.sample_from_image(images[b], theta_x[b], theta_z[b], G, R, span=span)
+                parts.append(tuple({k: v.cpu().numpy() for k, v in d.items()} for d in (x, ei, ea)))
+            x, ei, ea, _ = synthetic.disjoint_union(parts)
+            out = tuple({k: torch.from_numpy(v).to(dev) for k, v in d.items()} for d in (x, ei, ea))
+            torch.cuda.synchronize()
+            return out
+
+        def union():
+            out = vz.samples_from_images(images, theta_x, theta_z, G, R, span=span)
+            torch.cuda.synchronize()
+            return out
+
+        X, EI, EA = loop()
+        UX, UEI, UEA, off = union()
+        same = all(torch.equal(X[k], UX[k]) for k in X) and all(torch.equal(EI[et], UEI[et]) and torch.equal(EA[et], UEA[et])
+                                                                 for et in EDGE_TYPES)
+        print(f"# {B} images {size} x {size}, {n_grain} grains each, {off['joint'][-1]} junctions; the union equals the loop's "
+              f"disjoint union bit for bit: {same}", flush=True)
+        singles = [vz._vectorize(images[b], n_grain, "cells", 2, None) for b in range(B)]
+        whole = vz._vectorize_union(images, n_grains, "cells", 2, None)
+        torch.cuda.synchronize()
+
+        def calls_single():
+            for b, v in enumerate(singles):
+                A, L, _, _ = v["calls"]
+                v["counts"].zero_()
+                be.image_compare(images[b], None, n_grain, None, v["counts"])
+                _lib.check(lib.ggnn_image_junctions(ctypes.byref(A), _lib.current_stream()), "junctions")
+                _lib.check(lib.ggnn_junction_links(ctypes.byref(L), _lib.current_stream()), "links")
+
+        def calls_union():
+            A, L, _, _ = whole["calls"]
+            _lib.check(lib.ggnn_image_junctions_traj(ctypes.byref(A), _lib.current_stream()), "junctions_traj")
+            _lib.check(lib.ggnn_junction_links_traj(ctypes.byref(L), _lib.current_stream()), "links_traj")
+
+        def by_events(call):
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            call()
+            t1.record()
+            t1.synchronize()
+            return t0.elapsed_time(t1) * 1e3
+
+        def by_clock(call):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            call()
+            return (time.perf_counter() - t0) * 1e6
+
+        arms = {"loop": lambda: by_clock(loop), "union": lambda: by_clock(union),
+                f"calls x {B}": lambda: by_events(calls_single), "calls": lambda: by_events(calls_union)}
+        times = {k: [] for k in arms}
+        for rnd in range(a.rounds + 3):
+            for name, arm in arms.items():
+                t = arm()
+                if rnd >= 3:
+                    times[name].append(t)
+        for name, t in times.items():
+            t = np.array(t)
+            print(f"{name:10s} us: median {np.median(t):10.1f}  min {t.min():10.1f}  max {t.max():10.1f}", flush=True)
+        print(f"# loop / union = {np.median(times['loop']) / np.median(times['union']):.1f}, calls x {B} / calls = "
+              f"{np.median(times['calls x %d' % B]) / np.median(times['calls']):.1f}", flush=True)
+        try:
+            from torch.profiler import ProfilerActivity, profile
+            for name, call in (("loop", loop), ("union", union), (f"calls x {B}", calls_single), ("calls", calls_union)):
+                with profile(activities=[ProfilerActivity.CUDA]) as prof:
+                    call()
+                    torch.cuda.synchronize()
+                n = sum(1 for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA)
+                print(f"{name:10s} device activities (kernels, memsets, copies) in one pass: {n}", flush=True)
+                if name == "calls":
+                    for k in sorted(prof.key_averages(), key=lambda k: k.key):
+                        t = getattr(k, "device_time_total", None)
+                        t = getattr(k, "cuda_time_total", 0.0) if t is None else t
+                        if t:
+                            print(f"    {k.count:3d} x {k.key[:110]}: {t:.1f} us by the tracer", flush=True)
+        except Exception as exc:   # (a build of torch without the tracer)
+            print(f"# launches not counted: {type(exc).__name__}: {exc}", flush=True)
         print(f"# torch {torch.__version__}, {torch.cuda.get_device_name()}", flush=True)
 
 
