@@ -61,7 +61,7 @@ EXPORTED_SYMBOLS = (
     "ggnn_qoi_accumulate", "ggnn_qoi_finalize", "ggnn_process_schedule", "ggnn_grain_polygons",
     "ggnn_polygon_inputs", "ggnn_interp_polygons",
     "ggnn_polygons_rasterize", "ggnn_image_compare", "ggnn_image_junctions", "ggnn_junction_links",
-    "ggnn_image_junctions_traj", "ggnn_junction_links_traj",
+    "ggnn_image_junctions_traj", "ggnn_junction_links_traj", "ggnn_track_junctions", "ggnn_track_targets",
     "ggnn_metric_record",
     "ggnn_masked_mse_rows", "ggnn_collate_batch", "ggnn_reverse_slots",
 )
@@ -463,6 +463,30 @@ class LinkTrajArgs(Structure):
     ]
 
 
+class TrackArgs(Structure):
+    """Mirror of `ggnn_track_args`."""
+    _fields_ = [
+        ("triples", c_void_p), ("rowptr", c_void_p), ("col", c_void_p), ("grain_off", c_void_p), ("status", c_void_p),
+        ("next_joint", c_void_p), ("prev_joint", c_void_p), ("counters", c_void_p),
+        ("n_grain", c_int64), ("joint_capacity", c_int64), ("E_cap", c_int64), ("n_frame", c_int64),
+        ("boundary", c_int32), ("reserved", c_int32),
+    ]
+
+
+class TrackTargetsArgs(Structure):
+    """Mirror of `ggnn_track_targets_args`."""
+    _fields_ = [
+        ("triples", c_void_p), ("rowptr", c_void_p), ("col", c_void_p), ("edge_jj", c_void_p), ("xy", c_void_p),
+        ("pixel_counts", c_void_p), ("extra_volume", c_void_p), ("grain_off", c_void_p), ("status", c_void_p),
+        ("next_joint", c_void_p), ("prev_joint", c_void_p),
+        ("y_joint", c_void_p), ("mask_joint", c_void_p), ("hist_joint", c_void_p), ("edge_label", c_void_p),
+        ("y_grain", c_void_p), ("mask_grain", c_void_p), ("grain_event", c_void_p), ("hist_grain", c_void_p),
+        ("counters", c_void_p), ("patch_pixels", ctypes.c_double),
+        ("n_grain", c_int64), ("joint_capacity", c_int64), ("E_cap", c_int64), ("n_frame", c_int64),
+        ("boundary", c_int32), ("reserved", c_int32),
+    ]
+
+
 class MetricArgs(Structure):
     """Mirror of `ggnn_metric_args`."""
     _fields_ = [
@@ -627,6 +651,10 @@ def _declare(lib):
     lib.ggnn_image_junctions_traj.argtypes = [POINTER(JunctionTrajArgs), c_void_p]
     lib.ggnn_junction_links_traj.restype = c_int
     lib.ggnn_junction_links_traj.argtypes = [POINTER(LinkTrajArgs), c_void_p]
+    lib.ggnn_track_junctions.restype = c_int
+    lib.ggnn_track_junctions.argtypes = [POINTER(TrackArgs), c_void_p]
+    lib.ggnn_track_targets.restype = c_int
+    lib.ggnn_track_targets.argtypes = [POINTER(TrackTargetsArgs), c_void_p]
     lib.ggnn_process_schedule.restype = c_int
     lib.ggnn_process_schedule.argtypes = [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p]

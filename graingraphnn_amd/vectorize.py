@@ -24,8 +24,15 @@ junctions numbered image after image, a status per image, and the trajectory off
 `enable_events`, `enable_qoi` and `enable_polygons` take.  The launches do not depend on the number of images and there is
 one read-back.  The frames of a recorded sequence go the same way, each vectorised on its own.
 
-Not covered: stacks of mixed image shapes, tracking junctions between frames, and resolving a quadruple from a history (the
-diagonal is fixed, and counted in the status)."""
+A recorded SEQUENCE of images with stable grain ids becomes a training set (`frames_to_samples`, `track_frames`;
+ggnn_track_junctions, ggnn_track_targets; tests/trackcheck.py): junctions of consecutive valid frames are matched
+by their grain triple -- the reference's own mask rule, form_gradient:884-889 --, and the node targets, masks, grain events,
+edge labels and history columns of `training.DeviceDataset`'s samples are derived from the match on the device, what the
+reference gets from its junction tracker (graph_trajectory.py:283-846) and form_gradient (graph_datastruct.py:851-1011).
+
+Not covered: stacks of mixed image shapes, resolving a quadruple from a history (the diagonal is fixed, and counted in the
+status), the reference's `edge` length target (its edge_len head is disabled in every shipped configuration) and its
+`elim_list` scaling of shrinking grains (commented out in the reference)."""
 import ctypes
 import math
 
@@ -238,10 +245,11 @@ def grain_offsets(n_grains, device):
     return off.tolist(), torch.from_numpy(off).to(device)
 
 
-def _vectorize_union(images, n_grains, grid, merge_radius, joint_capacity, boundary="periodic", grain_off=None):
+def _vectorize_union(images, n_grains, grid, merge_radius, joint_capacity, boundary="periodic", grain_off=None, extra_words=0):
     """`_vectorize` for a stack: every launch, no read-back.  images: what `_stack` returns; grain_off: what `grain_offsets`
     returns (None: formed here, an upload -- pass it to a stream capture).  The status tensor holds the B status rows, behind
-    them joint_off [B + 1] and, for no-flux, the 4 B corner pixels: one read-back fetches them all."""
+    them joint_off [B + 1] and, for no-flux, the 4 B corner pixels: one read-back fetches them all (extra_words: zeroed room
+    behind those, for the counters of a caller that wants them in the same read-back)."""
     be = default_backend()
     _check_boundary(boundary)
     noflux = boundary == "noflux"
@@ -261,9 +269,9 @@ def _vectorize_union(images, n_grains, grid, merge_radius, joint_capacity, bound
     gj = torch.stack([slots + n_total, slots])
     jj = torch.full((2, 3 * cap), -1, dtype=torch.int64, device=dev)
     W = _lib.GGNN_JUNCTION_STATUS_WORDS
-    status = torch.zeros(B * W + B + 1 + (4 * B if noflux else 0), dtype=torch.int64, device=dev)
+    status = torch.zeros(B * W + B + 1 + (4 * B if noflux else 0) + extra_words, dtype=torch.int64, device=dev)
     if noflux:   # per image, the order of grain_image(corner_grains=)
-        status[B * W + B + 1:] = torch.stack([images[:, 0, 0], images[:, 0, -1], images[:, -1, 0], images[:, -1, -1]], 1).reshape(-1)
+        status[B * W + B + 1:B * W + 5 * B + 1] = torch.stack([images[:, 0, 0], images[:, 0, -1], images[:, -1, 0], images[:, -1, -1]], 1).reshape(-1)
     wy, wx = (ny + 1, nx + 1) if noflux else (ny, nx)
     words = B * wy * ((wx + _lib.GGNN_JUNCTION_SEGMENT - 1) // _lib.GGNN_JUNCTION_SEGMENT)
     ws = torch.empty(words, dtype=torch.int32, device=dev)
@@ -294,7 +302,12 @@ def _graphs(images, n_grains, grid, merge_radius, joint_capacity, strict, bounda
     if n_grains is None:
         n_grains = images.amax(dim=(1, 2)).tolist()   # (a read-back of its own: pass n_grains to avoid it)
     v = _vectorize_union(images, n_grains, grid, merge_radius, joint_capacity, boundary)
-    words = v["status"].tolist()                      # the one read-back
+    return _graphs_of(v, v["status"].tolist(), strict)   # the one read-back
+
+
+def _graphs_of(v, words, strict):
+    """`_graphs`' two results from the arrays of `_vectorize_union` and the words of its status, read back."""
+    boundary = v["boundary"]
     B, W, cap = v["n_image"], len(STATUS_WORDS), v["capacity"]
     status = [dict(zip(STATUS_WORDS, words[b * W:(b + 1) * W])) for b in range(B)]
     joint_off = [min(o, cap) for o in words[B * W:B * W + B + 1]]
@@ -373,7 +386,6 @@ def samples_from_images(images, theta_x, theta_z, G, R, span=None, patch_pixels=
 
     boundary="noflux": what `GrainRollout(..., boundary="noflux", traj_offsets=traj_offsets, max_y=image_max_y(nx, ny, grid))`
     takes; the row of every trajectory's boundary grain is reset as `sample_from_image` resets grain 0's."""
-    from .generator import feature_rows
     from .synthetic import span_for
     tx = [np.asarray(t, np.float64).ravel() for t in theta_x]
     tz = [np.asarray(t, np.float64).ravel() for t in theta_z]
@@ -399,6 +411,15 @@ def samples_from_images(images, theta_x, theta_z, G, R, span=None, patch_pixels=
                      True, boundary)
     if kw:
         raise TypeError(f"samples_from_images: unknown keywords {sorted(kw)}")
+    x, ei, ea = _union_state(res, v, tx, tz, Gs, Rs, span, patch_pixels)
+    return x, ei, ea, res["traj_offsets"]
+
+
+def _union_state(res, v, tx, tz, Gs, Rs, span, patch_pixels):
+    """samples_from_images' (x_dict, edge_index_dict, edge_attr) of a vectorised union.  A joint->joint column without a
+    destination (strict=False: an invalid image's) is measured as a loop on its source, length 0."""
+    from .generator import feature_rows
+    B, boundary = v["n_image"], v["boundary"]
     be, xy, ei = default_backend(), res["xy"], res["edge_index_dict"]
     dev, oj = xy.device, res["traj_offsets"]["joint"]
     ny, nx = v["shape"]
@@ -418,6 +439,161 @@ def samples_from_images(images, theta_x, theta_z, G, R, span=None, patch_pixels=
     ea = {et: torch.zeros(ei[et].size(1), 1, dtype=torch.float32, device=dev) for et in EDGE_TYPES}
     x = {"grain": x_grain, "joint": x_joint}
     flags = torch.zeros(2, dtype=torch.int32, device=dev)
+    measured = dict(ei)
+    if not all(status_is_valid(s, boundary) for s in res["status"]):
+        jj = ei[EDGE_TYPES[2]]
+        measured[EDGE_TYPES[2]] = torch.stack([jj[0], torch.where(jj[1] >= 0, jj[1], jj[0])])
     be.step_refresh(x_joint, x_grain, math.inf, flags,
-                    [(ei[et], x[et[0]], x[et[2]], ea[et]) for et in EDGE_TYPES])
-    return x, ei, ea, res["traj_offsets"]
+                    [(measured[et], x[et[0]], x[et[2]], ea[et]) for et in EDGE_TYPES])
+    return x, ei, ea
+
+
+# ---- a recorded sequence into training samples ---------------------------------------------------------------------------
+
+PAIR_COUNTERS = ("n_matched", "n_ambiguous", "n_label0", "n_label1", "n_unlabelled", "n_eliminated")
+
+
+def _track(frames, n_grain, grid, merge_radius, joint_capacity, boundary, extra_volume=None, patch_pixels=None, targets=True):
+    """Every launch of a tracked sequence, no read-back: `_vectorize_union`'s dict with the frames as its images, plus
+    next_joint / prev_joint and, with `targets`, the capacity-sized target arrays.  The counters of ggnn_track_junctions
+    [T, 2] and of ggnn_track_targets [T, 4] lie behind the union's status words, at v["counter_words"]."""
+    be = default_backend()
+    frames = _stack(frames)
+    T, ny, nx = frames.shape
+    n_grain = int(n_grain)
+    if T < 2:
+        raise _lib.GGNNError("a sequence needs at least two frames")
+    v = _vectorize_union(frames, [n_grain] * T, grid, merge_radius, joint_capacity, boundary, extra_words=6 * T)
+    dev, cap, n_total, csr, status = frames.device, v["capacity"], v["n_grain"], v["csr"], v["status"]
+    v["counter_words"] = status.numel() - 6 * T
+    counters = status[v["counter_words"]:]
+    v["next_joint"] = torch.full((cap,), -1, dtype=torch.int64, device=dev)
+    v["prev_joint"] = torch.full((cap,), -1, dtype=torch.int64, device=dev)
+    K = _lib.TrackArgs()
+    K.triples, K.rowptr, K.col, K.grain_off, K.status = (_lib.ptr(v["triples"]), _lib.ptr(csr.rowptr), _lib.ptr(csr.col),
+                                                         _lib.ptr(v["grain_off_dev"]), _lib.ptr(status))
+    K.next_joint, K.prev_joint, K.counters = _lib.ptr(v["next_joint"]), _lib.ptr(v["prev_joint"]), _lib.ptr(counters)
+    K.n_grain, K.joint_capacity, K.E_cap, K.n_frame, K.boundary = n_total, cap, csr.col.numel(), T, BOUNDARIES[boundary]
+    _lib.check(be.lib.ggnn_track_junctions(ctypes.byref(K), _lib.current_stream()), "ggnn_track_junctions")
+    v["track_calls"] = (K, None)
+    if not targets:
+        return v
+    if extra_volume is not None:
+        extra_volume = torch.as_tensor(extra_volume).to(device=dev, dtype=torch.float64).contiguous()
+        if extra_volume.shape != (T, n_grain):
+            raise _lib.GGNNError("extra_volume must be [T, n_grain]")
+    f32 = dict(dtype=torch.float32, device=dev)
+    out = {"y_joint": torch.zeros(cap, 2, **f32), "mask_joint": torch.zeros(cap, **f32), "hist_joint": torch.zeros(cap, 2, **f32),
+           "edge_label": torch.full((3 * cap,), -1, dtype=torch.int64, device=dev),
+           "y_grain": torch.zeros(n_total, 2, **f32), "mask_grain": torch.zeros(n_total, **f32),
+           "grain_event": torch.zeros(n_total, dtype=torch.int64, device=dev), "hist_grain": torch.zeros(n_total, 2, **f32)}
+    G = _lib.TrackTargetsArgs()
+    G.triples, G.rowptr, G.col, G.edge_jj, G.xy = K.triples, K.rowptr, K.col, _lib.ptr(v["jj"]), _lib.ptr(v["xy"])
+    G.pixel_counts, G.extra_volume = _lib.ptr(v["counts"]), (None if extra_volume is None else _lib.ptr(extra_volume))
+    G.grain_off, G.status, G.next_joint, G.prev_joint = K.grain_off, K.status, K.next_joint, K.prev_joint
+    for name, t in out.items():
+        setattr(G, name, _lib.ptr(t))
+    G.counters, G.patch_pixels = _lib.ptr(counters[2 * T:]), float(patch_pixels or nx * ny)
+    G.n_grain, G.joint_capacity, G.E_cap, G.n_frame, G.boundary = n_total, cap, csr.col.numel(), T, BOUNDARIES[boundary]
+    _lib.check(be.lib.ggnn_track_targets(ctypes.byref(G), _lib.current_stream()), "ggnn_track_targets")
+    v.update(out)
+    v["track_calls"] = (K, G, extra_volume)   # (the two calls' arguments and what they point to: tools/vectorize_cost.py)
+    return v
+
+
+def track_frames(frames, n_grain, grid="cells", merge_radius=2, joint_capacity=None, boundary="periodic"):
+    """The frame-to-frame correspondence of a recorded sequence of grain-ID images (ggnn_track_junctions; tests/trackcheck.py
+    restates the rule): -> (`graphs_from_images(frames, [n_grain] * T, strict=False)`'s dict, next_joint, prev_joint).
+
+    frames: int [T, ny, nx] on the device or a list of T equal-shaped device images, T >= 2, with grain ids that are stable
+    across the frames (pixel p = grain p - 1 in every frame; an eliminated grain no longer occurs).  next_joint int64
+    [n_joint]: the union index of the junction of the following frame that carries the same grain triple -- when that triple
+    occurs exactly once in both frames, and both frames are valid structures (status_is_valid, judged on the device) --, or
+    -1; prev_joint: the same towards the preceding frame, the inverse map.  One read-back, of the status."""
+    v = _track(frames, n_grain, grid, merge_radius, joint_capacity, boundary, targets=False)
+    res, _ = _graphs_of(v, v["status"].tolist(), False)   # the one read-back
+    n = res["traj_offsets"]["joint"][-1]
+    return res, v["next_joint"][:n].contiguous(), v["prev_joint"][:n].contiguous()
+
+
+def frames_to_samples(frames, theta_x, theta_z, G, R, span=None, patch_pixels=None, extra_volume=None, z=None, grid="cells",
+                      merge_radius=2, joint_capacity=None, boundary="periodic"):
+    """A training set from a recorded sequence of grain-ID images -- a phase-field run, a serial-section series, the
+    `grain_images()` of a rollout --: -> (samples, report), one sample per pair of consecutive VALID frames (t, t + 1), each the
+    (x, edge_index, edge_attr, y, mask) of device tensors with local indices that `training.DeviceDataset` takes.  What the
+    reference gets from its junction tracker (graph_trajectory.py:283-846) and form_gradient (graph_datastruct.py:851-1011).
+
+    frames: as in `track_frames`; theta_x, theta_z: one angle per grain (n_grain = their length, the same in every frame;
+    boundary="noflux": they count the boundary grain, grain 0); G, R: scalars or one value per frame; span, patch_pixels: as in
+    `samples_from_images`; extra_volume: float [T, n_grain], the reference's extraV_frames[:, frame] / s**3, a solver output
+    that the frames do not hold (None: zeros); z: [T], the z feature of every row of a frame (None: 0).
+
+    x, edge_index, edge_attr of sample t are frame t's rows of `samples_from_images(frames, ...)` bit for bit (the frames are
+    vectorised with strict=False: an invalid frame is skipped with its pairs, not raised), except the history columns:
+    x_grain[:, 4] = fp32(20 extra_volume[t]), and, when the pair (t - 1, t) was emitted too, x_grain[:, 10] = the area change
+    and x_joint[:, 6:8] = the displacement since frame t - 1 in the targets' scaling (0 for a first sample, after a skipped
+    pair and for a junction without a predecessor; the row of a grain without pixels in frame t keeps only its orientation, span
+    and process columns).  y = {"grain": [n_grain, 2] (20 x the change of the area feature; 20 x
+    extra_volume[t + 1]), "joint": [n_joint_t, 2] (5 x the displacement to the matched junction; periodic: its minimum
+    image), "edge_event": int64 [3 n_joint_t] (0: the link persists, 1: a neighbour switch, -1: unlabelled), "grain_event":
+    int64 [n_grain] (1: the grain has pixels in frame t and none in t + 1)}; mask = {"grain": [n_grain, 1], "joint":
+    [n_joint_t, 1]} float32 (a grain with pixels in frame t; a matched junction).  include/ggnn.h states the rule in full.
+
+    report = {"status": per frame, "pairs": [(t, t + 1)] emitted, "skipped": [(t, t + 1, reason)], "counts": per emitted pair
+    a dict of n_matched, n_ambiguous, n_label0, n_label1, n_unlabelled, n_eliminated}.  Everything is found on the device
+    (ggnn_track_junctions, ggnn_track_targets) in a number of launches that does not depend on T, with ONE read-back: the
+    union's status words and the counters behind them.  Cutting the union into samples is a slice per pair."""
+    from .synthetic import span_for
+    tx, tz = np.asarray(theta_x, np.float64).ravel(), np.asarray(theta_z, np.float64).ravel()
+    n_grain = len(tx)
+    if n_grain < 1 or len(tz) != n_grain:
+        raise _lib.GGNNError("theta_x and theta_z must hold one angle per grain")
+    _check_boundary(boundary)
+    frames = _stack(frames)
+    T = frames.size(0)
+    try:
+        Gs = [float(g) for g in np.broadcast_to(np.asarray(G, np.float64), (T,))]
+        Rs = [float(r) for r in np.broadcast_to(np.asarray(R, np.float64), (T,))]
+        zs = None if z is None else [float(a) for a in np.broadcast_to(np.asarray(z, np.float64), (T,))]
+    except ValueError as exc:
+        raise _lib.GGNNError("G, R and z must be scalars or hold one value per frame") from exc
+    if span is None:
+        spans = sorted({span_for(g, r) for g, r in zip(Gs, Rs)})
+        if len(spans) != 1:
+            raise _lib.GGNNError(f"the frames' (G, R) give the frame spans {spans}: a sequence has one, pass span=")
+        span = spans[0]
+    v = _track(frames, n_grain, grid, merge_radius, joint_capacity, boundary, extra_volume, patch_pixels)
+    words = v["status"].tolist()                      # the one read-back
+    res, _ = _graphs_of(v, words, False)
+    x, ei, ea = _union_state(res, v, [tx] * T, [tz] * T, Gs, Rs, span, patch_pixels)
+    oj, n = res["traj_offsets"]["joint"], res["traj_offsets"]["joint"][-1]
+    valid = [status_is_valid(s, boundary) for s in res["status"]]
+    x["grain"][:, 4] = v["hist_grain"][:, 1]
+    x["grain"][:, 10] = v["hist_grain"][:, 0]
+    x["joint"][:, 6:8] = v["hist_joint"][:n]
+    if zs is not None:
+        for t in range(T):
+            x["grain"][t * n_grain:(t + 1) * n_grain, 2] = zs[t]
+            x["joint"][oj[t]:oj[t + 1], 2] = zs[t]
+    c0 = v["counter_words"]
+    report = {"status": res["status"], "pairs": [], "skipped": [], "counts": []}
+    samples = []
+    for t in range(T - 1):
+        if not (valid[t] and valid[t + 1]):
+            bad = [u for u in (t, t + 1) if not valid[u]]
+            report["skipped"].append((t, t + 1, "; ".join(f"frame {u} is not a valid {boundary} structure: {res['status'][u]}"
+                                                          for u in bad)))
+            continue
+        g0, g1, j0, j1 = t * n_grain, (t + 1) * n_grain, oj[t], oj[t + 1]
+        own = union_member(res, t)[2]
+        sx = {"grain": x["grain"][g0:g1].clone(), "joint": x["joint"][j0:j1].clone()}
+        sea = {EDGE_TYPES[0]: ea[EDGE_TYPES[0]][3 * j0:3 * j1].clone(), EDGE_TYPES[1]: ea[EDGE_TYPES[1]][3 * j0:3 * j1].clone(),
+               EDGE_TYPES[2]: ea[EDGE_TYPES[2]][3 * j0:3 * j1].clone()}
+        y = {"grain": v["y_grain"][g0:g1].clone(), "joint": v["y_joint"][j0:j1].clone(),
+             "edge_event": v["edge_label"][3 * j0:3 * j1].clone(), "grain_event": v["grain_event"][g0:g1].clone()}
+        mask = {"grain": v["mask_grain"][g0:g1].reshape(-1, 1).clone(), "joint": v["mask_joint"][j0:j1].reshape(-1, 1).clone()}
+        samples.append((sx, own, sea, y, mask))
+        report["pairs"].append((t, t + 1))
+        a, b = words[c0 + 2 * t:c0 + 2 * t + 2], words[c0 + 2 * T + 4 * t:c0 + 2 * T + 4 * t + 4]
+        report["counts"].append(dict(zip(PAIR_COUNTERS, a + b)))
+    return samples, report

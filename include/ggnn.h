@@ -953,8 +953,8 @@ int ggnn_image_compare(const int32_t* image, const int32_t* truth, int64_t n_pix
  * its generator or from its phase-field solver's junction tracks (`node_region`, graph_trajectory.py:316-376).  On demand,
  * on `stream`; setup work, not part of a step.  Periodic images and images with no-flux walls (`boundary`, below); a stack
  * of equal-shaped images -- the trajectories of a union, or the frames of a sequence, each on its own -- goes through the
- * _traj forms further down.  Stacks of mixed shapes, tracking junctions between frames and resolving a quadruple from a
- * history are not covered.
+ * _traj forms further down; the frames of a sequence are matched to one another by ggnn_track_junctions below.  Stacks of
+ * mixed shapes and resolving a quadruple from a history are not covered.
  * ggnn_image_junctions = memset of the status + three launches (count per block, scan of the blocks, emit).  The rule is
  * exact in integers up to the one fp32 expression of a position (tests/vectorcheck.py restates it):
  *   image     : int32 [ny, nx], pixel p = grain p - 1 (as ggnn_polygons_rasterize writes), periodic in both directions
@@ -1097,6 +1097,85 @@ typedef struct ggnn_link_traj_args {
   int64_t n_grain, joint_capacity, E_cap, n_image;
 } ggnn_link_traj_args;
 int ggnn_junction_links_traj(const ggnn_link_traj_args* args, ggnn_stream_t stream);
+/* ------------------------------------------------------------------------------------
+ * Training targets from a recorded SEQUENCE of grain-ID images: the n_frame images of one union above are the frames of a
+ * sequence in which a grain keeps its id (local grain g of every frame is the same grain; an eliminated grain no longer
+ * occurs), and the two calls derive from the union's arrays what the reference's junction tracker (graph_trajectory.py:283-846)
+ * and GrainHeterograph.form_gradient (graph_datastruct.py:851-1011) derive from its phase-field solver's output.  Setup work,
+ * on `stream`, nothing through the host; tests/trackcheck.py restates the rule.
+ *   frames    : frame t is VALID when its status row is (overflow, n_invalid_pixels, n_open_pairs 0 and Euler's formula for
+ *               `boundary`), judged on the device; the PAIR (t, t + 1) is emitted when both frames are valid.
+ *   match     : a junction's LOCAL triple is its triple minus its frame's grain_off.  Junction j of frame t matches junction
+ *               k of frame t + 1 when the pair is emitted, their local triples are equal and that triple occurs exactly once
+ *               in frame t and exactly once in frame t + 1: next_joint[j] = k, prev_joint[k] = j (union indices), otherwise
+ *               -1.  A junction of frame t whose triple occurs more than once in frame t or in frame t + 1 is AMBIGUOUS.
+ * ggnn_track_junctions = a memset of its counters + one launch, a thread a junction j < min(n_joint, joint_capacity): it walks
+ * the joint->grain row of the triple's first grain in its own, the next and the previous frame and counts equal triples.
+ * counters int64 [n_frame, 2], zeroed by the call: n_matched, n_ambiguous of the pair (t, t + 1), counted at frame t.
+ * ggnn_track_targets = a memset of its counters + two launches (a thread a joint->joint column; a thread a union grain):
+ *   y_joint   : matched j -> k: fp32(5.0 * d), d = (double)xy[k] - (double)xy[j] per coordinate, for GGNN_BC_PERIODIC the
+ *               minimum image (d > 0.5: d - 1; d < -0.5: d + 1); mask_joint = 1.  Unmatched: y 0, mask 0.
+ *   hist_joint: the same expression from prev_joint[j] to j (x_joint columns 6, 7 of the reference), 0 without one.
+ *   edge_label: per column s = 3 j + k of edge_jj, u = j, v its destination, in a frame whose pair is emitted: 0 when u and
+ *               v are both matched and next_joint[u], next_joint[v] are linked in frame t + 1 (one is the destination of a
+ *               column of the other); 1 (a neighbour switch) when both are unmatched and, with u = {a, b, c}, v = {a, b, d},
+ *               the triples {a, c, d} and {b, c, d} each occur exactly once in frame t + 1 and those two junctions are linked;
+ *               -1 (unlabelled) otherwise, and for every column of a frame whose pair is not emitted.
+ *   y_grain   : with c, c' the pixel counts of the grain in frames t, t + 1: [0] = fp32(20.0 * ((double)c' / patch_pixels -
+ *               (double)c / patch_pixels)), [1] = fp32(20.0 * extra_volume[grain in t + 1]) (0 when extra_volume is NULL);
+ *               mask_grain = 1 where c != 0 (never for local grain 0 of GGNN_BC_NOFLUX, the boundary grain); grain_event = 1
+ *               where the mask is 1 and c' == 0.  All 0 in a frame whose pair is not emitted.
+ *   hist_grain: [0] = the area expression from frame t - 1 to t when the pair (t - 1, t) is emitted, else 0 (x_grain column
+ *               10); [1] = fp32(20.0 * extra_volume[grain]) (x_grain column 4); both 0 for a grain without pixels in frame t
+ *               and for a no-flux boundary grain.
+ *   counters  : int64 [n_frame, 4], zeroed by the call: the directed columns labelled 0, 1, -1 and the grain events of the
+ *               pair (t, t + 1), counted at frame t (frames without an emitted pair count nothing).
+ * The counters are integer atomics (sums); no result is ordered by one, so a replay gives the same bits.  Nothing is read or
+ * written at or beyond joint_capacity, rows and columns of the table are clamped as in ggnn_junction_links, grain offsets to
+ * [0, n_grain].  GGNN_EINVAL without a launch: args or a pointer NULL (extra_volume may be), a 64-bit array not 8-byte
+ * aligned, n_grain, joint_capacity, E_cap as in ggnn_junction_links, n_frame outside [2, GGNN_JUNCTION_MAX_BLOCKS], boundary
+ * neither GGNN_BC_PERIODIC nor GGNN_BC_NOFLUX, patch_pixels below 1. */
+typedef struct ggnn_track_args {
+  const int32_t* triples;        /* [joint_capacity, 3], device: ggnn_image_junctions_traj's */
+  const int32_t* rowptr;         /* [>= n_grain + 1]: the union's joint->grain table's row pointers */
+  const int32_t* col;            /* [E_cap]: its columns */
+  const int64_t* grain_off;      /* [n_frame + 1], device */
+  const int64_t* status;         /* [n_frame * GGNN_JUNCTION_STATUS_WORDS + n_frame + 1]: the status rows, then joint_off */
+  int64_t* next_joint;           /* [joint_capacity] out */
+  int64_t* prev_joint;           /* [joint_capacity] out */
+  int64_t* counters;             /* [n_frame, 2] out */
+  int64_t n_grain, joint_capacity, E_cap, n_frame;
+  int32_t boundary;              /* GGNN_BC_PERIODIC / GGNN_BC_NOFLUX */
+  int32_t reserved;
+} ggnn_track_args;
+int ggnn_track_junctions(const ggnn_track_args* args, ggnn_stream_t stream);
+typedef struct ggnn_track_targets_args {
+  const int32_t* triples;        /* as above */
+  const int32_t* rowptr;
+  const int32_t* col;
+  const int64_t* edge_jj;        /* [2, 3 joint_capacity]: ggnn_junction_links_traj's */
+  const float* xy;               /* [joint_capacity, 2] */
+  const uint64_t* pixel_counts;  /* [n_grain] */
+  const double* extra_volume;    /* [n_grain] in union order, or NULL */
+  const int64_t* grain_off;
+  const int64_t* status;
+  const int64_t* next_joint;     /* ggnn_track_junctions' */
+  const int64_t* prev_joint;
+  float* y_joint;                /* [joint_capacity, 2] out */
+  float* mask_joint;             /* [joint_capacity] out */
+  float* hist_joint;             /* [joint_capacity, 2] out */
+  int64_t* edge_label;           /* [3 joint_capacity] out */
+  float* y_grain;                /* [n_grain, 2] out */
+  float* mask_grain;             /* [n_grain] out */
+  int64_t* grain_event;          /* [n_grain] out */
+  float* hist_grain;             /* [n_grain, 2] out */
+  int64_t* counters;             /* [n_frame, 4] out */
+  double patch_pixels;
+  int64_t n_grain, joint_capacity, E_cap, n_frame;
+  int32_t boundary;
+  int32_t reserved;
+} ggnn_track_targets_args;
+int ggnn_track_targets(const ggnn_track_targets_args* args, ggnn_stream_t stream);
 /* The host-side topology update those counts trigger: one call of the reference's `Cmodel.update`
  * (models.py:612-842 with delete_grain_index :861-893, switching_edge_index :896-1051, point_in_triangle :1055-1070,
  * periodic_move :1103-1106), nucleation off.  HOST memory throughout, no stream: grains of `grain_event` (those below the

@@ -1,0 +1,678 @@
+"""Training samples from a recorded sequence of grain-ID images (ggnn_track_junctions / ggnn_track_targets,
+vectorize.track_frames / frames_to_samples) against the restatement of tests/trackcheck.py, bit for bit, on the recorded
+phase-field sequence of tests/golden/pf_frames_cfg1.npz and on small crafted sequences.
+
+The crafted sequences are drawn from bricks (periodic) and bands (no-flux); what each was made for is checked on the CPU
+restatement first (test_the_sequences_show_what_they_were_made_for), then the device must give the restatement's bits.
+
+Ambiguous triples.  A VALID periodic structure cannot repeat a triple: two junctions with the triple {a, b, c} whose three
+pairs are closed are joined by the three boundaries a|b, a|c, b|c alone, which is a sphere of three faces, not a torus.  The
+three-id brick tiling of a small torus repeats its one triple and leaves every pair open: its frames are invalid and its pairs
+skipped (checked).  The no-flux image of two halves is that sphere -- boundary grain, left, right, the triple at the top and at
+the bottom wall -- and is valid: both copies stay unmatched and are counted in n_ambiguous."""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import test_vectorize as tv
+import test_vectorize_noflux as tn
+import trackcheck as tc
+import vectorcheck_union as vu
+from helpers import ROOT
+from graingraphnn_amd import _lib
+from graingraphnn_amd import vectorize as vz
+from graingraphnn_amd.synthetic import EDGE_TYPES
+
+DEV = "cuda"
+GJ, JG, JJ = EDGE_TYPES
+W = 7
+SHAPES = [("periodic", 32, 32), ("periodic", 24, 40), ("noflux", 32, 32), ("noflux", 24, 40)]
+
+_cache = {}
+
+
+def cached(key, make):
+    if key not in _cache:
+        _cache[key] = make()
+    return _cache[key]
+
+
+# ---- sequences ---------------------------------------------------------------------------------------------------------------
+
+def plain(boundary, ny, nx, shift=0, lower=0):
+    """Four rows of four bricks (periodic, 16 grains) or three bands of three (no-flux, 10 grains with the boundary grain); the
+    first cut of the second row at `shift` more, the last cut of the last row at `lower` more."""
+    if boundary == "periodic":
+        ry, cx = ny // 4, nx // 4
+        even, odd = [0, cx, 2 * cx, 3 * cx], [cx // 2 + k * cx for k in range(4)]
+        return tv.bricks(ny, nx, [0, ry, 2 * ry, 3 * ry], [even, [odd[0] + shift] + odd[1:], even, odd[:3] + [odd[3] + lower]])
+    b = ny // 3
+    return tn.bands(ny, nx, [0, b, 2 * b, ny], [[nx // 3, 2 * nx // 3], [nx // 6 + shift, nx // 2], [nx // 3 + 3, 2 * nx // 3 + lower + 3]])
+
+
+def drifting(boundary, ny, nx, T=3):
+    """T valid frames whose junctions move a pixel or two a frame."""
+    made = [plain(boundary, ny, nx, shift=t % 3, lower=-(t % 2)) for t in range(T)]
+    return [m[0] for m in made], made[0][1]
+
+
+def switching(boundary, ny, nx):
+    """Two frames with ONE neighbour switch: a cut of one row and a cut of the row under it, three pixels apart, change sides, so
+    the short boundary between the bricks A (above) and B (below) gives way to one between C (above left) and D (below right):
+    {A, B, C}, {A, B, D} -> {A, C, D}, {B, C, D}."""
+    if boundary == "periodic":
+        ry, cx = ny // 4, nx // 4
+        even, odd = [0, cx, 2 * cx, 3 * cx], [cx // 2 + k * cx for k in range(4)]
+        rows = [0, ry, 2 * ry, 3 * ry]
+        before, n = tv.bricks(ny, nx, rows, [even, odd, [0, odd[0] + 3, 2 * cx, 3 * cx], odd])
+        after, _ = tv.bricks(ny, nx, rows, [even, [odd[0] + 3] + odd[1:], [0, odd[0], 2 * cx, 3 * cx], odd])
+        return [before, after], n
+    b = ny // 3
+    before, n = tn.bands(ny, nx, [0, b, 2 * b, ny], [[nx // 3, 2 * nx // 3], [nx // 3 + 3, 2 * nx // 3 + 6], [nx // 2]])
+    after, _ = tn.bands(ny, nx, [0, b, 2 * b, ny], [[nx // 3 + 3, 2 * nx // 3], [nx // 3, 2 * nx // 3 + 6], [nx // 2]])
+    return [before, after], n
+
+
+def eliminating(boundary, ny, nx):
+    """Two frames: a small grain on a T junction, three-sided, and the same structure without it."""
+    after, n = plain(boundary, ny, nx)
+    before = after.copy()
+    if boundary == "periodic":
+        y, x = ny // 4, nx // 8          # the first cut of the second row meets the first row
+    else:
+        y, x = ny // 3, nx // 3          # the first cut of the first band meets the second band
+    before[y - 2:y + 2, x - 2:x + 2] = n + 1
+    return [before, after], n + 1
+
+
+def crossing(ny, nx):
+    """Two periodic frames, the second the first rolled by three pixels in x and, in a square image, two in y: the junctions at
+    the image's edges cross the periodic walls.  (The period is 1 in both coordinates, as everywhere in the project: a
+    non-square periodic image has no wrap in y that the minimum image could see.)"""
+    image, n = plain("periodic", ny, nx)
+    return [image, np.roll(np.roll(image, 3, 1), 2 if ny == nx else 0, 0)], n
+
+
+def three_ids(n=12):
+    """The three-id brick tiling of an n x n torus (n a multiple of 6, bricks n / 3 wide and high, a row shifted by half a
+    brick and by one id): every junction carries the triple (0, 1, 2)."""
+    b = n // 3
+    image = np.zeros((n, n), np.int32)
+    for r in range(3):
+        for x in range(n):
+            image[r * b:(r + 1) * b, x] = 1 + (((x - r * (b // 2)) % n) // b + r) % 3
+    return [image, np.roll(image, 1, 1)], 3
+
+
+def two_halves(ny, nx):
+    """Two no-flux frames of a left and a right grain, the cut one pixel further in the second: the triple (0, 1, 2) at the top
+    and at the bottom wall."""
+    return [tn.bands(ny, nx, [0, ny], [[nx // 2 + t]])[0] for t in range(2)], 3
+
+
+def one_grain(boundary, ny, nx):
+    return np.ones((ny, nx), np.int32) if boundary == "periodic" else np.full((ny, nx), 2, np.int32)
+
+
+def with_a_gap(boundary, ny, nx):
+    """Six frames, the fourth no valid structure (periodic: one grain; no-flux, where one grain in a box is valid: a pixel
+    without a grain): the pairs (0, 1), (1, 2) and (4, 5) are emitted."""
+    frames, n = drifting(boundary, ny, nx, T=5)
+    broken = one_grain(boundary, ny, nx)
+    if boundary == "noflux":
+        broken = frames[2].copy()
+        broken[ny // 2, nx // 2] = 0
+    return frames[:3] + [broken] + frames[3:], n
+
+
+def block_stack(extra):
+    """A periodic stack of 7 plain 32 x 32 frames (32 junctions each) and an eighth with 31, 32 or 33: 255, 256 and 257 junctions
+    in the union, one below, at and above a block of 256 threads.  31: one junction voided by an invalid pixel; 33: a pixel of a
+    third brick on a boundary next to a junction."""
+    frames, n = drifting("periodic", 32, 32, T=8)
+    last = frames[7].copy()
+    if extra == -1:
+        last[8, 0] = 0
+    elif extra == 1:
+        last[3, 8] = last[8, 4]
+    frames[7] = last
+    return frames, n
+
+
+def restate(key, frames, n_grain, boundary, **kw):
+    def make():
+        u = vu.vectorize(frames, [n_grain] * len(frames), boundary=boundary, grid=kw.get("grid", "cells"),
+                         joint_capacity=kw.get("joint_capacity"))
+        return u, tc.track(u, n_grain, boundary, patch_pixels=kw.get("patch_pixels"), extra_volume=kw.get("extra_volume"),
+                           shape=frames[0].shape)
+    return cached((key, boundary, frames[0].shape, tuple(sorted((k, v if np.isscalar(v) or v is None else id(v)) for k, v in kw.items()))), make)
+
+
+# ---- CPU ---------------------------------------------------------------------------------------------------------------------
+
+def hand_union(triples, jj, xy, counts, n_grain, T):
+    """A union written by hand: T frames of len(triples[t]) junctions with local triples, joint->joint destinations local."""
+    off = np.cumsum([0] + [len(t) for t in triples])
+    status = [{"n_joint": len(t), "n_quad_windows": 0, "n_merged_windows": 0, "n_invalid_pixels": 0, "n_open_pairs": 0,
+               "n_present_grains": len(t) // 2, "overflow": 0} for t in triples]
+    tr = np.concatenate([np.asarray(t, np.int32) + f * n_grain for f, t in enumerate(triples)])
+    n = len(tr)
+    dst = np.concatenate([np.asarray(j, np.int64).reshape(-1) + off[f] for f, j in enumerate(jj)])
+    return {"triples": tr, "jj": np.stack([np.repeat(np.arange(n), 3), dst]), "xy": np.asarray(xy, np.float32).reshape(n, 2),
+            "counts": np.asarray(counts, np.int64).reshape(-1), "status": status, "joint_off": off.tolist(),
+            "grain_off": [f * n_grain for f in range(T + 1)]}
+
+
+# The tetrahedron of the grains 0 .. 3 (the restatement judges validity from the status alone, which hand_union writes as valid)
+TETRA = [(0, 1, 2), (0, 1, 3), (0, 2, 3), (1, 2, 3)]
+# destinations per junction for the pairs (g0, g1), (g0, g2), (g1, g2)
+TETRA_JJ = [[1, 2, 3], [0, 2, 3], [0, 1, 3], [0, 1, 2]]
+
+
+def test_restatement_on_four_junctions_by_hand():
+    """Every label outcome on four junctions.  Frame 0: the tetrahedron of grains 0..3.  Frame 1: the same (label 0, all
+    matched).  Then a frame in which grain 3 gave way to grain 4 in two junctions: those two are unmatched, the link between
+    two matched ones keeps 0, a half-matched link is -1, and the link between the two unmatched ones, {0, 1, 3} and
+    {0, 2, 3}, is 1 by the rule: {0, 1, 2} and {1, 2, 3} each occur once in the next frame and are linked there.  Then a switch by hand: u = {0, 1, 2}, v = {0, 1, 3} become {0, 2, 3} and {1, 2, 3}."""
+    xy = np.zeros((8, 2), np.float32)
+    xy[:4, 0], xy[4:, 0] = [0.1, 0.3, 0.5, 0.95], [0.12, 0.3, 0.5, 0.02]
+    u = hand_union([TETRA, TETRA], [TETRA_JJ, TETRA_JJ], xy, [[4, 4, 4, 4, 0], [5, 3, 4, 4, 0]], 5, 2)
+    r = tc.track(u, 5, "periodic", patch_pixels=16)
+    assert r["next"].tolist() == [4, 5, 6, 7, -1, -1, -1, -1] and r["prev"].tolist() == [-1] * 4 + [0, 1, 2, 3]
+    assert r["edge_label"].tolist() == [0] * 12 + [-1] * 12
+    assert r["counts"][0] == {"n_matched": 4, "n_ambiguous": 0, "n_label0": 12, "n_label1": 0, "n_unlabelled": 0, "n_eliminated": 0}
+    f = np.float32
+    assert r["y_joint"][:, 0].tolist() == [f(5.0 * (np.float64(f(0.12)) - np.float64(f(0.1)))), 0, 0,
+                                           f(5.0 * (np.float64(f(0.02)) - np.float64(f(0.95)) + 1.0)), 0, 0, 0, 0]
+    assert r["hist_joint"][4:, 0].tolist() == r["y_joint"][:4, 0].tolist() and r["mask_joint"].tolist() == [1] * 4 + [0] * 4
+    assert r["y_grain"][:5, 0].tolist() == [f(20.0 * (5 / 16 - 4 / 16)), f(20.0 * (3 / 16 - 4 / 16)), 0, 0, 0]
+    assert r["mask_grain"].tolist() == [1, 1, 1, 1, 0] + [0] * 5 and r["hist_grain"][5:, 0].tolist() == r["y_grain"][:5, 0].tolist()
+    # grain 3 replaced by grain 4 in junctions 1 and 2 of the next frame; grain 3 is eliminated
+    changed = [(0, 1, 2), (0, 1, 4), (0, 2, 4), (1, 2, 3)]
+    u = hand_union([TETRA, changed], [TETRA_JJ, TETRA_JJ], xy, [[4, 4, 4, 4, 0], [4, 4, 4, 0, 4]], 5, 2)
+    r = tc.track(u, 5, "periodic", patch_pixels=16)
+    assert r["next"].tolist() == [4, -1, -1, 7, -1, -1, -1, -1]
+    #        junction 0: ->1 half, ->2 half, ->3 both      1: ->0 half, ->2 switch, ->3 half     2: likewise      3: ->0, half, half
+    assert r["edge_label"][:12].tolist() == [-1, -1, 0, -1, 1, -1, -1, 1, -1, 0, -1, -1]
+    assert r["grain_event"].tolist() == [0, 0, 0, 1, 0] + [0] * 5 and r["counts"][0]["n_eliminated"] == 1
+    # the switch: u = junction 0 = {0, 1, 2}, v = junction 1 = {0, 1, 3}; the next frame holds {0, 2, 3} and {1, 2, 3}, linked
+    switched = [(0, 2, 3), (1, 2, 3), (0, 2, 3), (1, 2, 3)]
+    first = [(0, 1, 2), (0, 1, 3), (0, 2, 3), (1, 2, 3)]
+    u = hand_union([first, switched[:2] + [(0, 1, 4), (2, 3, 4)]], [TETRA_JJ, [[1, 1, 1], [0, 0, 0], [3, 3, 3], [2, 2, 2]]], xy,
+                   [[4, 4, 4, 4, 0], [4, 4, 4, 4, 4]], 5, 2)
+    r = tc.track(u, 5, "periodic", patch_pixels=16)
+    assert r["next"].tolist() == [-1, -1, 4, 5, -1, -1, -1, -1]
+    assert r["edge_label"][:6].tolist() == [1, -1, -1, 1, -1, -1] and r["edge_label"][6:12].tolist() == [-1, -1, 0, -1, -1, 0]
+    # an ambiguous triple: two copies in the next frame
+    u = hand_union([TETRA, [TETRA[0], TETRA[0], TETRA[2], TETRA[3]]], [TETRA_JJ, TETRA_JJ], xy, [[4, 4, 4, 4, 0]] * 2, 5, 2)
+    r = tc.track(u, 5, "periodic", patch_pixels=16)
+    assert r["next"].tolist() == [-1, -1, 6, 7, -1, -1, -1, -1] and r["counts"][0]["n_ambiguous"] == 1
+    # an invalid frame: nothing is matched, labelled or counted
+    u["status"][1]["n_open_pairs"] = 1
+    r = tc.track(u, 5, "periodic", patch_pixels=16)
+    assert r["pairs"] == [] and (r["next"] == -1).all() and (r["edge_label"] == -1).all() and not r["mask_grain"].any()
+    assert all(v == 0 for v in r["counts"][0].values())
+
+
+@pytest.mark.parametrize("boundary,ny,nx", SHAPES)
+def test_the_sequences_show_what_they_were_made_for(boundary, ny, nx):
+    noflux = boundary == "noflux"
+    frames, n = drifting(boundary, ny, nx)
+    u, r = restate("drift", frames, n, boundary)
+    assert r["valid"] == [True] * 3 and all(c["n_matched"] == u["status"][0]["n_joint"] for c in r["counts"][:2])
+    assert all(c["n_unlabelled"] == c["n_label1"] == 0 for c in r["counts"]) and np.abs(r["y_joint"]).max() > 0
+    assert np.abs(r["hist_joint"][r["joint_off"][1]:]).max() > 0 and np.abs(r["hist_grain"][n:, 0]).max() > 0
+    frames, n = switching(boundary, ny, nx)
+    u, r = restate("switch", frames, n, boundary)
+    c = r["counts"][0]
+    assert r["valid"] == [True, True], u["status"]
+    assert (c["n_label1"], c["n_unlabelled"], c["n_matched"]) == (2, 8, u["status"][0]["n_joint"] - 2), c
+    assert c["n_label0"] == 3 * u["status"][0]["n_joint"] - 10 and c["n_ambiguous"] == 0
+    frames, n = eliminating(boundary, ny, nx)
+    u, r = restate("elim", frames, n, boundary)
+    c = r["counts"][0]
+    assert r["valid"] == [True, True], u["status"]
+    assert u["status"][0]["n_joint"] == u["status"][1]["n_joint"] + 2 and c["n_eliminated"] == 1 and r["grain_event"][n - 1] == 1
+    assert c["n_matched"] == u["status"][0]["n_joint"] - 3 and c["n_label1"] == 0 and c["n_unlabelled"] == 12, c
+    frames, n = with_a_gap(boundary, ny, nx)
+    u, r = restate("gap", frames, n, boundary)
+    assert r["pairs"] == [(0, 1), (1, 2), (4, 5)]
+    o = r["joint_off"]
+    assert np.abs(r["hist_joint"][o[1]:o[3]]).max() > 0 and not r["hist_joint"][o[3]:o[5]].any() and not r["hist_grain"][3 * n:5 * n, 0].any()
+    assert not r["y_joint"][o[2]:o[4]].any() and (r["edge_label"][3 * o[2]:3 * o[4]] == -1).all()
+    if noflux:
+        frames, n = two_halves(ny, nx)
+        u, r = restate("halves", frames, n, boundary)
+        assert r["valid"] == [True, True] and r["counts"][0]["n_ambiguous"] == 2 and r["counts"][0]["n_matched"] == 0
+        assert (r["next"] == -1).all() and r["mask_grain"].tolist() == [0, 1, 1, 0, 0, 0]
+    else:
+        frames, n = crossing(ny, nx)
+        u, r = restate("cross", frames, n, boundary)
+        raw = u["xy"][r["next"][:r["joint_off"][1]]].astype(np.float64) - u["xy"][:r["joint_off"][1]].astype(np.float64)
+        assert r["counts"][0]["n_matched"] == 32 and (np.abs(raw) > 0.5).any(1).sum() >= 4 and np.abs(r["y_joint"]).max() < 0.75
+        frames, n = three_ids()
+        u, r = restate("three", frames, n, boundary)
+        assert len({tuple(t) for t in u["triples"][:r["joint_off"][1]]}) == 1 and r["joint_off"][1] > 1      # duplicates
+        assert r["valid"] == [False, False] and r["pairs"] == [] and u["status"][0]["n_open_pairs"] > 0
+
+
+@pytest.mark.parametrize("extra,total", [(-1, 255), (0, 256), (1, 257)])
+def test_the_block_stacks_hold_what_they_say(extra, total):
+    frames, n = block_stack(extra)
+    u, r = restate(("block", extra), frames, n, "periodic")
+    assert u["joint_off"][-1] == total and r["valid"][:7] == [True] * 7 and r["valid"][7] == (extra == 0)
+
+
+def golden():
+    return cached("golden", lambda: dict(np.load(os.path.join(ROOT, "tests", "golden", "pf_frames_cfg1.npz"))))
+
+
+def golden_restated():
+    d = golden()
+    frames = list(d["frames"].astype(np.int32))
+    return restate("pf", frames, 118, "periodic", grid="points", patch_pixels=501 * 501, extra_volume=d["extra_volume"])
+
+
+TABLE = [(234, 236, 698, 2, 8, set()), (234, 236, 698, 2, 8, set()), (226, 236, 658, 10, 40, set()),
+         (206, 236, 568, 26, 114, {51}), (188, 234, 506, 22, 174, {1, 2, 6, 39, 53, 100})]
+WRAPPED = [1, 2, 1, 0, 2]
+
+
+def test_restatement_on_the_recorded_sequence():
+    d = golden()
+    assert d["frames"].shape == (7, 501, 501) and d["frames"].dtype == np.int8 and d["frame_ids"].tolist() == list(range(0, 37, 6))
+    u, r = golden_restated()
+    assert r["valid"] == [True] * 6 + [False] and u["status"][6]["n_open_pairs"] == 4 and r["pairs"] == [(t, t + 1) for t in range(5)]
+    for t, (matched, n_joint, l0, l1, lu, gone) in enumerate(TABLE):
+        c = r["counts"][t]
+        assert (c["n_matched"], u["status"][t]["n_joint"], c["n_label0"], c["n_label1"], c["n_unlabelled"]) == (matched, n_joint, l0, l1, lu)
+        assert c["n_ambiguous"] == 0 and c["n_eliminated"] == len(gone)
+        recorded = {int(g) for f, g in zip(d["event_frame"], d["event_grain"]) if 6 * t + 1 <= f <= 6 * t + 6}
+        assert set((np.nonzero(r["grain_event"][118 * t:118 * (t + 1)])[0] + 1).tolist()) == recorded == gone
+        j0, j1 = r["joint_off"][t], r["joint_off"][t + 1]
+        m = np.arange(j0, j1)[r["next"][j0:j1] >= 0]
+        raw = u["xy"][r["next"][m]].astype(np.float64) - u["xy"][m].astype(np.float64)
+        assert int((np.abs(raw) > 0.5).any(1).sum()) == WRAPPED[t] and np.abs(r["y_joint"][j0:j1]).max() < 0.2
+        assert len({tuple(x) for x in u["triples"][j0:j1]}) == j1 - j0
+
+
+def assert_equals_form_gradient(t, y, mask, what):
+    """Sample t's targets against what the reference's own form_gradient made of the two states (the golden of
+    make_golden_frames.py), after the cast to fp32; the rows whose raw difference exceeds 0.5 excepted, where the rule departs
+    from the reference on purpose -- at most 2 a pair."""
+    d = golden()
+    key = f"fg{t}__"
+    wrapped = d[key + "wrapped"]
+    assert len(wrapped) == WRAPPED[t] <= 2
+    keep = np.ones(len(d[key + "mask_joint"]), bool)
+    keep[wrapped] = False
+    same(y["grain"], d[key + "y_grain"].astype(np.float32), (what, t, "grain"))
+    mine = bits(y["joint"]).view(np.float32)      # (by value: the reference's mask * target leaves -0.0 in an unmatched row)
+    assert mine.dtype == np.float32 and np.array_equal(mine[keep], d[key + "y_joint"].astype(np.float32)[keep]), (what, t, "joint")
+    same(bits(mask["joint"]).view(np.float32).reshape(-1).astype(np.int64), d[key + "mask_joint"], (what, t, "mask"))
+    same(y["grain_event"], d[key + "grain_event"], (what, t, "grain_event"))
+
+
+def test_restatement_equals_the_reference_form_gradient():
+    u, r = golden_restated()
+    for t in range(5):
+        y, mask, _ = tc.cut(r, 118, t)
+        assert_equals_form_gradient(t, y, mask, "restatement")
+
+
+def test_entry_points_validate_on_the_host():
+    lib = _lib.load()
+    assert {"ggnn_track_junctions", "ggnn_track_targets"} <= set(_lib.EXPORTED_SYMBOLS)
+    assert lib.ggnn_track_junctions(None, None) == -1 and lib.ggnn_track_targets(None, None) == -1
+    buf = (ctypes.c_int64 * 64)()
+    p = ctypes.cast(buf, ctypes.c_void_p).value
+
+    def junctions(**kw):
+        A = _lib.TrackArgs(p, p, p, p, p, p, p, p, 16, 8, 24, 3, 0, 0)
+        for k, v in kw.items():
+            setattr(A, k, v)
+        return lib.ggnn_track_junctions(ctypes.byref(A), None)
+
+    def targets(**kw):
+        A = _lib.TrackTargetsArgs(*([p] * 20), 64.0, 16, 8, 24, 3, 0, 0)
+        for k, v in kw.items():
+            setattr(A, k, v)
+        return lib.ggnn_track_targets(ctypes.byref(A), None)
+    for call in (junctions, targets):
+        for bad in (dict(n_frame=1), dict(n_frame=(1 << 22) + 1), dict(n_grain=0), dict(joint_capacity=0), dict(E_cap=-1),
+                    dict(boundary=2), dict(triples=None), dict(status=None), dict(next_joint=None), dict(counters=p + 4),
+                    dict(grain_off=p + 4), dict(prev_joint=p + 4)):
+            assert call(**bad) == -1, (call.__name__, bad)
+    for bad in (dict(patch_pixels=0.5), dict(patch_pixels=float("nan")), dict(xy=None), dict(edge_label=p + 4), dict(hist_grain=None),
+                dict(extra_volume=p + 4)):
+        assert targets(**bad) == -1, bad
+    assert ctypes.sizeof(_lib.TrackArgs) == 8 * 8 + 4 * 8 + 2 * 4 and ctypes.sizeof(_lib.TrackTargetsArgs) == 20 * 8 + 8 + 4 * 8 + 2 * 4
+    # the mirrors hold the header's fields in the header's order; the ABI version is as it was
+    import re
+    src = open(os.path.join(ROOT, "include", "ggnn.h")).read()
+    assert re.search(r"#define GGNN_ABI_VERSION 26\b", src) and _lib.GGNN_ABI_VERSION == 26
+    for struct, mirror in (("ggnn_track_args", _lib.TrackArgs), ("ggnn_track_targets_args", _lib.TrackTargetsArgs)):
+        body = re.search(r"typedef struct " + struct + r" \{(.*?)\} " + struct + ";", src, re.S).group(1)
+        names = re.findall(r"(\w+)\s*[,;]", re.sub(r"/\*.*?\*/", "", body, flags=re.S))
+        assert names == [f[0] for f in mirror._fields_], (struct, names)
+
+
+# ---- GPU ---------------------------------------------------------------------------------------------------------------------
+
+def to_dev(frames):
+    return torch.from_numpy(np.stack(frames).astype(np.int32)).to(DEV)
+
+
+def bits(a):
+    a = a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    return a.view(np.uint32) if a.dtype == np.float32 else a
+
+
+def same(got, want, what):
+    got, want = bits(got), bits(want)
+    assert got.dtype == want.dtype and got.shape == want.shape and np.array_equal(got, want), what
+
+
+UNION_ARRAYS = (("next_joint", "next", 1), ("prev_joint", "prev", 1), ("y_joint", "y_joint", 1), ("hist_joint", "hist_joint", 1),
+                ("mask_joint", "mask_joint", 1), ("edge_label", "edge_label", 3))
+
+
+def check_sequence(key, frames, n_grain, boundary, **kw):
+    """The device's arrays of the whole union, its samples and its report against the restatement, bit for bit; the
+    x / edge_index / edge_attr of every sample against samples_from_images of the valid frames.  -> (samples, report, r)."""
+    u, r = restate(key, frames, n_grain, boundary, **kw)
+    T, n = len(frames), len(u["triples"])
+    dev = to_dev(frames)
+    grid, cap = kw.get("grid", "cells"), kw.get("joint_capacity")
+    v = vz._track(dev, n_grain, grid, 2, cap, boundary, kw.get("extra_volume"), kw.get("patch_pixels"))
+    for mine, theirs, per in UNION_ARRAYS:
+        same(v[mine][:per * n], r[theirs], (key, mine))
+    for k in ("y_grain", "hist_grain", "mask_grain", "grain_event"):
+        same(v[k], r[k], (key, k))
+    res, nxt, prv = vz.track_frames(dev, n_grain, grid=grid, joint_capacity=cap, boundary=boundary)
+    same(nxt, r["next"], key), same(prv, r["prev"], key)
+    assert res["status"] == u["status"] and res["traj_offsets"]["joint"] == r["joint_off"]
+    rs = np.random.RandomState(5)
+    tx, tz = rs.uniform(0, 1.5, n_grain), rs.uniform(0, 1.5, n_grain)
+    z = [0.25 * t for t in range(T)]
+    samples, report = vz.frames_to_samples(dev, tx, tz, 2.0, 0.4, z=z, grid=grid, joint_capacity=cap, boundary=boundary,
+                                           patch_pixels=kw.get("patch_pixels"), extra_volume=kw.get("extra_volume"))
+    assert report["pairs"] == r["pairs"] and report["status"] == u["status"]
+    assert [s[:2] for s in report["skipped"]] == [(t, t + 1) for t in range(T - 1) if (t, t + 1) not in r["pairs"]]
+    assert report["counts"] == [r["counts"][t] for t, _ in r["pairs"]]
+    good = [t for t in range(T) if r["valid"][t]]
+    if good:
+        X, EI, EA, off = vz.samples_from_images(dev[good], [tx] * len(good), [tz] * len(good), 2.0, 0.4, grid=grid, boundary=boundary,
+                                                patch_pixels=kw.get("patch_pixels"))
+    for (t, _), (x, ei, ea, y, mask) in zip(r["pairs"], samples):
+        wy, wm, (h_area, h_extra, h_joint) = tc.cut(r, n_grain, t)
+        for k in wy:
+            same(y[k], wy[k], (key, t, "y", k))
+        for k in wm:
+            same(mask[k], wm[k], (key, t, "mask", k))
+        b = good.index(t)
+        g0, j0, j1 = off["grain"][b], off["joint"][b], off["joint"][b + 1]
+        xg, xj = X["grain"][g0:g0 + n_grain].clone(), X["joint"][j0:j1].clone()
+        xg[:, 2], xj[:, 2] = z[t], z[t]
+        xg[:, 10], xg[:, 4], xj[:, 6:8] = torch.from_numpy(h_area).to(DEV), torch.from_numpy(h_extra).to(DEV), torch.from_numpy(h_joint).to(DEV)
+        same(x["grain"], xg, (key, t, "x_grain")), same(x["joint"], xj, (key, t, "x_joint"))
+        for et, shift in ((GJ, (g0, j0)), (JG, (j0, g0)), (JJ, (j0, j0))):
+            own = EI[et][:, 3 * j0:3 * j1] - torch.tensor(shift, device=DEV).reshape(2, 1)
+            same(ei[et], own, (key, t, et)), same(ea[et], EA[et][3 * j0:3 * j1], (key, t, et, "attr"))
+            assert ei[et].is_contiguous() and (ei[et].numel() == 0 or int(ei[et].min()) >= 0)
+    return samples, report, r
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("boundary,ny,nx", SHAPES)
+def test_small_sequences_equal_the_restatement(boundary, ny, nx):
+    for name, make in (("drift", drifting), ("switch", switching), ("elim", eliminating), ("gap", with_a_gap)):
+        frames, n = make(boundary, ny, nx)
+        samples, report, r = check_sequence(name, frames, n, boundary)
+        assert len(samples) == len(r["pairs"]) >= 1
+    frames, n = drifting(boundary, ny, nx, T=2)          # T = 2, with extra volumes, on the points grid
+    ev = np.random.RandomState(3).uniform(0, 1e-3, (2, n))
+    check_sequence("two", frames, n, boundary, grid="points", extra_volume=ev, patch_pixels=100)
+    if boundary == "noflux":
+        frames, n = two_halves(ny, nx)
+        samples, report, r = check_sequence("halves", frames, n, boundary)
+        assert report["counts"][0]["n_ambiguous"] == 2 and not samples[0][4]["joint"].any()
+    else:
+        frames, n = crossing(ny, nx)
+        samples, _, _ = check_sequence("cross", frames, n, boundary)
+        assert float(samples[0][3]["joint"].abs().max()) < 0.75
+        frames, n = three_ids()
+        samples, report, _ = check_sequence("three", frames, n, boundary)
+        assert samples == [] and len(report["skipped"]) == 1
+
+
+@pytest.mark.gpu
+def test_the_switch_and_the_elimination_are_labelled_as_drawn():
+    frames, n = switching("periodic", 32, 32)
+    (x, ei, ea, y, mask), = vz.frames_to_samples(to_dev(frames), np.zeros(n), np.zeros(n), 2.0, 0.4)[0]
+    lab, jj = y["edge_event"].cpu().numpy(), ei[JJ].cpu().numpy()
+    u, v = jj[:, lab == 1]
+    assert sorted(u.tolist()) == sorted(v.tolist()) and len(u) == 2 and u[0] == v[1]            # both directions of one link
+    around = (np.isin(jj[0], u) | np.isin(jj[1], u)) & (lab != 1)
+    assert around.sum() == 8 and (lab[around] == -1).all() and (lab[~around & (lab != 1)] == 0).all()
+    assert mask["joint"].cpu().numpy().reshape(-1).tolist() == [0.0 if j in u else 1.0 for j in range(len(lab) // 3)]
+    frames, n = eliminating("noflux", 24, 40)
+    (x, ei, ea, y, mask), = vz.frames_to_samples(to_dev(frames), np.zeros(n), np.zeros(n), 2.0, 0.4, boundary="noflux")[0]
+    assert y["grain_event"].tolist() == [0] * (n - 1) + [1] and mask["grain"].reshape(-1).tolist() == [0.0] + [1.0] * (n - 1)
+    assert int((mask["joint"] == 0).sum()) == 3 and float(y["grain"][n - 1, 0]) == float(np.float32(20.0 * (0.0 - 16 / 960)))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("boundary", ("periodic", "noflux"))
+def test_a_one_grain_frame_in_the_middle(boundary):
+    """Periodic: one grain is no valid torus (0 junctions, 2 expected), both pairs that touch it are skipped.  No-flux: one grain
+    in a box IS valid (0 = 2 * 1 - 2 junctions), so both pairs are emitted, with nothing matched and a sample without junctions."""
+    frames, n = drifting(boundary, 32, 32, T=2)
+    frames = [frames[0], one_grain(boundary, 32, 32), frames[1]]
+    samples, report, r = check_sequence("middle", frames, n, boundary)
+    if boundary == "periodic":
+        assert samples == [] and [s[:2] for s in report["skipped"]] == [(0, 1), (1, 2)] and "frame 1" in report["skipped"][0][2]
+    else:
+        assert report["skipped"] == [] and [c["n_matched"] for c in report["counts"]] == [0, 0]
+        assert samples[1][0]["joint"].shape == (0, 8) and samples[1][3]["edge_event"].numel() == 0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("extra", (-1, 0, 1))
+def test_unions_around_a_block_of_threads(extra):
+    frames, n = block_stack(extra)
+    samples, report, r = check_sequence(("block", extra), frames, n, "periodic")
+    assert len(samples) == (7 if extra == 0 else 6)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("boundary,nx", [("periodic", 255), ("noflux", 256), ("noflux", 257)])
+def test_strips_across_the_segment_edge(boundary, nx):
+    image, n = tn.strip(nx)
+    if boundary == "periodic":
+        frames = [image, np.roll(image, 1, 1)]
+    else:
+        moved = image.copy()
+        moved[0:4, 100:102] = image[0, 99]
+        frames = [image, moved]
+    check_sequence(("strip", nx), frames, n, boundary)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("boundary,ny,nx", [("periodic", 32, 32), ("noflux", 24, 40)])
+def test_the_capacity_ends_inside_frame_one(boundary, ny, nx):
+    """Frame 1 overflows, so it and frame 2 are invalid and every pair is skipped; the two entry points on guarded arrays -- at
+    that capacity and at one beyond the union's n_joint -- write nothing at or beyond min(n_joint, joint_capacity), and nothing
+    outside their arrays."""
+    frames, n_grain = drifting(boundary, ny, nx)
+    full, _ = restate("drift", frames, n_grain, boundary)
+    cap = full["joint_off"][1] + 5
+    u, r = restate("cut", frames, n_grain, boundary, joint_capacity=cap)
+    assert [s["overflow"] for s in u["status"]] == [0, 1, 1] and r["pairs"] == []
+    samples, report, _ = check_sequence("cut", frames, n_grain, boundary, joint_capacity=cap)
+    assert samples == [] and len(report["skipped"]) == 2
+    # the two entry points on guarded arrays: that capacity, and one LARGER than what the union holds, so that [n_joint, capacity)
+    # is there to be left alone
+    for key, cap in (("cut", cap), ("roomy", full["joint_off"][3] + 9)):
+        n, T, n_total = min(cap, full["joint_off"][3]), 3, 3 * n_grain
+        u, r = restate(key, frames, n_grain, boundary, joint_capacity=cap)
+        v = vz._track(to_dev(frames), n_grain, "cells", 2, cap, boundary, targets=False)
+        K = v["track_calls"][0]
+        lib, G = _lib.load(), 16
+        i64 = lambda m: torch.full((m + 2 * G,), -7, dtype=torch.int64, device=DEV)
+        f32 = lambda m: torch.full((m + 2 * G,), -7.0, dtype=torch.float32, device=DEV)
+        out = {"next_joint": i64(cap), "prev_joint": i64(cap), "y_joint": f32(2 * cap), "mask_joint": f32(cap), "hist_joint": f32(2 * cap),
+               "edge_label": i64(3 * cap), "y_grain": f32(2 * n_total), "mask_grain": f32(n_total), "grain_event": i64(n_total),
+               "hist_grain": f32(2 * n_total), "c2": i64(2 * T), "c4": i64(4 * T)}
+        at = lambda k: out[k].data_ptr() + G * out[k].element_size()
+        K.next_joint, K.prev_joint, K.counters = at("next_joint"), at("prev_joint"), at("c2")
+        _lib.check(lib.ggnn_track_junctions(ctypes.byref(K), _lib.current_stream()), "ggnn_track_junctions")
+        A = _lib.TrackTargetsArgs()
+        A.triples, A.rowptr, A.col, A.grain_off, A.status = K.triples, K.rowptr, K.col, K.grain_off, K.status
+        A.edge_jj, A.xy, A.pixel_counts, A.extra_volume = v["jj"].data_ptr(), v["xy"].data_ptr(), v["counts"].data_ptr(), None
+        A.next_joint, A.prev_joint, A.counters, A.patch_pixels = K.next_joint, K.prev_joint, at("c4"), float(ny * nx)
+        for k in ("y_joint", "mask_joint", "hist_joint", "edge_label", "y_grain", "mask_grain", "grain_event", "hist_grain"):
+            setattr(A, k, at(k))
+        A.n_grain, A.joint_capacity, A.E_cap, A.n_frame, A.boundary = K.n_grain, K.joint_capacity, K.E_cap, K.n_frame, K.boundary
+        _lib.check(lib.ggnn_track_targets(ctypes.byref(A), _lib.current_stream()), "ggnn_track_targets")
+        torch.cuda.synchronize()
+        for k, t in out.items():
+            assert bool((t[:G] == -7).all()) and bool((t[-G:] == -7).all()), k
+        for mine, theirs, per in UNION_ARRAYS:
+            per = per * (2 if mine in ("y_joint", "hist_joint") else 1)
+            body = out[mine][G:-G]
+            same(body[:per * n], np.ascontiguousarray(r[theirs]).reshape(-1), mine)
+            assert bool((body[per * n:] == -7).all()), mine                           # between n_joint and the capacity too
+        for k in ("y_grain", "hist_grain", "mask_grain", "grain_event"):
+            same(out[k][G:-G], np.ascontiguousarray(r[k]).reshape(-1), k)
+        want = [[r["counts"][t][c] for c in tc.COUNTERS] for t in range(T)]
+        assert out["c2"][G:-G].reshape(T, 2).tolist() == [w[:2] for w in want] and out["c4"][G:-G].reshape(T, 4).tolist() == [w[2:] for w in want]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("boundary", ("periodic", "noflux"))
+def test_captured_graph_of_the_two_calls_gives_the_same_bits(boundary):
+    frames, n = with_a_gap(boundary, 24, 40)
+    ev = np.random.RandomState(1).uniform(0, 1e-3, (6, n))
+    eager = vz._track(to_dev(frames), n, "cells", 2, None, boundary, ev, None)
+    held = vz._track(to_dev(frames), n, "cells", 2, None, boundary, ev, None)             # (also the warm-up of the capture)
+    K, A = held["track_calls"][:2]
+    lib = _lib.load()
+    keys = ("next_joint", "prev_joint", "y_joint", "mask_joint", "hist_joint", "edge_label", "y_grain", "mask_grain", "grain_event",
+            "hist_grain")
+    torch.cuda.synchronize()
+    for k in keys:
+        held[k].fill_(-3)
+    held["status"][held["counter_words"]:] = -3
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        _lib.check(lib.ggnn_track_junctions(ctypes.byref(K), _lib.current_stream()), "ggnn_track_junctions")
+        _lib.check(lib.ggnn_track_targets(ctypes.byref(A), _lib.current_stream()), "ggnn_track_targets")
+    n_joint = int(eager["status"][6 * W + 6])
+    for _ in range(2):
+        graph.replay()
+        torch.cuda.synchronize()
+        for k in keys:
+            per = held[k].numel() // held["capacity"] if "joint" in k or k == "edge_label" else None
+            a, b = (held[k], eager[k]) if per is None else (held[k].reshape(-1)[:per * n_joint], eager[k].reshape(-1)[:per * n_joint])
+            assert torch.equal(a, b), k
+        assert torch.equal(held["status"], eager["status"])
+
+
+# ---- the recorded sequence -----------------------------------------------------------------------------------------------
+
+def recorded_samples():
+    def make():
+        d = golden()
+        return vz.frames_to_samples(torch.from_numpy(d["frames"].astype(np.int32)).to(DEV), d["theta_x"], d["theta_z"], float(d["G"]),
+                                    float(d["R"]), patch_pixels=501 * 501, extra_volume=d["extra_volume"], grid="points")
+    return cached("recorded", make)
+
+
+@pytest.mark.gpu
+def test_the_recorded_sequence():
+    d = golden()
+    u, r = golden_restated()
+    samples, report = recorded_samples()
+    assert report["pairs"] == [(t, t + 1) for t in range(5)] and len(samples) == 5
+    assert [s[:2] for s in report["skipped"]] == [(5, 6)] and report["status"][6]["n_open_pairs"] == 4
+    assert not vz.status_is_valid(report["status"][6]) and all(vz.status_is_valid(s) for s in report["status"][:6])
+    for t, (matched, n_joint, l0, l1, lu, gone) in enumerate(TABLE):
+        c = report["counts"][t]
+        x, ei, ea, y, mask = samples[t]
+        print(t, c)
+        assert (c["n_matched"], c["n_label0"], c["n_label1"], c["n_unlabelled"], c["n_ambiguous"]) == (matched, l0, l1, lu, 0)
+        assert x["joint"].shape == (n_joint, 8) and int(mask["joint"].sum()) == matched
+        lab = y["edge_event"]
+        assert (int((lab == 0).sum()), int((lab == 1).sum()), int((lab == -1).sum())) == (l0, l1, lu)
+        recorded = {int(g) for f, g in zip(d["event_frame"], d["event_grain"]) if 6 * t + 1 <= f <= 6 * t + 6}
+        assert set((torch.nonzero(y["grain_event"]).reshape(-1) + 1).tolist()) == recorded and c["n_eliminated"] == len(recorded)
+        wy, wm, (h_area, h_extra, h_joint) = tc.cut(r, 118, t)
+        for k in wy:
+            same(y[k], wy[k], (t, "y", k))
+        for k in wm:
+            same(mask[k], wm[k], (t, "mask", k))
+        same(x["grain"][:, 10], h_area, t), same(x["grain"][:, 4], h_extra, t), same(x["joint"][:, 6:8].contiguous(), h_joint, t)
+        assert_equals_form_gradient(t, y, mask, "device")
+        # the minimum image is visible
+        m = (mask["joint"].reshape(-1) > 0).cpu().numpy()
+        j0 = r["joint_off"][t]
+        raw = u["xy"][r["next"][j0:j0 + n_joint][m]].astype(np.float64) - u["xy"][j0:j0 + n_joint][m].astype(np.float64)
+        assert int((np.abs(raw) > 0.5).any(1).sum()) == WRAPPED[t]
+        print(t, "largest |y_joint|", float(y["joint"].abs().max()))
+        assert float(y["joint"].abs().max()) < 0.2
+        absent = (x["grain"][:, 3] == 0).cpu().numpy()
+        assert absent.sum() == 118 - report["status"][t]["n_present_grains"] and not x["grain"][absent][:, [0, 1, 2, 3, 4, 10]].any()
+    # x, edge_index, edge_attr: frame t's rows of samples_from_images on the six valid frames
+    dev = torch.from_numpy(d["frames"][:6].astype(np.int32)).to(DEV)
+    X, EI, EA, off = vz.samples_from_images(dev, [d["theta_x"]] * 6, [d["theta_z"]] * 6, float(d["G"]), float(d["R"]),
+                                            patch_pixels=501 * 501, grid="points")
+    for t, (x, ei, ea, y, mask) in enumerate(samples):
+        g0, j0, j1 = off["grain"][t], off["joint"][t], off["joint"][t + 1]
+        keep_g, keep_j = [0, 1, 2, 3, 5, 6, 7, 8, 9], [0, 1, 2, 3, 4, 5]
+        same(x["grain"][:, keep_g].contiguous(), X["grain"][g0:g0 + 118][:, keep_g].contiguous(), t)
+        same(x["joint"][:, keep_j].contiguous(), X["joint"][j0:j1][:, keep_j].contiguous(), t)
+        for et, shift in ((GJ, (g0, j0)), (JG, (j0, g0)), (JJ, (j0, j0))):
+            same(ei[et], EI[et][:, 3 * j0:3 * j1] - torch.tensor(shift, device=DEV).reshape(2, 1), (t, et))
+            same(ea[et], EA[et][3 * j0:3 * j1], (t, et))
+
+
+@pytest.mark.gpu
+def test_recorded_samples_through_the_device_dataset_and_one_loss_each():
+    """DeviceDataset(samples, 2) and one collated batch: the real rows' y, mask and labels are the samples' own; then one
+    regressor loss and one classifier loss on seeded models in training mode, finite and bit-equal to the same losses on the
+    restatement's targets."""
+    from helpers import product_models
+    from graingraphnn_amd import training
+    samples, report = recorded_samples()
+    u, r = golden_restated()
+    restated = []
+    for t, (x, ei, ea, y, mask) in enumerate(samples):
+        wy, wm, _ = tc.cut(r, 118, t)
+        restated.append((x, ei, ea, {k: torch.from_numpy(np.ascontiguousarray(a)).to(DEV) for k, a in wy.items()},
+                         {k: torch.from_numpy(np.ascontiguousarray(a)).to(DEV) for k, a in wm.items()}))
+    R, Cm = product_models(10020, 1.0, DEV)
+    R.train(), Cm.train()
+    losses = []
+    for them in (samples, restated):
+        ds = training.DeviceDataset(them, 2)
+        db = training.DeviceBatches(ds)
+        ds.set_order(np.arange(5))
+        db.next()
+        for i, sl in zip(ds.batch_ids(0), ds.slices(0)):
+            x, ei, ea, y, mask = them[i]
+            for nt in ("grain", "joint"):
+                a, b = sl[nt]
+                same(db.y_dict[nt][a:b], y[nt], (i, nt)), same(db.mask[nt][a:b].reshape(-1, 1), mask[nt], (i, nt))
+            a, b = sl[JJ]
+            same(db.y_dict["edge_event"][a:b], y["edge_event"], i)
+            a, b = sl["grain"]
+            same(db.y_dict["grain_event"][a:b], y["grain_event"], i)
+        lr = training.regressor_loss(db.y_dict, R(db.x_dict, db.edge_index_dict, db.edge_attr), db.mask, rows=db.rows)
+        lc = training.classifier_loss(db.y_dict, Cm(db.x_dict, db.edge_index_dict, db.edge_attr), 1.0)
+        assert bool(torch.isfinite(lr)) and bool(torch.isfinite(lc)) and float(lr.detach()) > 0 and float(lc.detach()) > 0
+        losses.append((lr.detach().clone(), lc.detach().clone()))
+    assert torch.equal(losses[0][0], losses[1][0]) and torch.equal(losses[0][1], losses[1][1])

@@ -23,7 +23,16 @@ loop and union by the host clock around work that ends in a synchronise (both ho
 the rounds after three warm-up rounds, the arms alternating within a round.  The kernel launches of one loop and of one
 union call are counted by torch.profiler in a pass of their own after the timing, which also lists the device time of
 every kernel of the two union calls (the count, scan and emit passes by name).
-    python tools/vectorize_cost.py --union 64 [--rounds 20] [--boundary periodic]"""
+    python tools/vectorize_cost.py --union 64 [--rounds 20] [--boundary periodic]
+--track T times the way from a recorded sequence to training samples (vectorize.frames_to_samples): T frames of --size x --size
+(128 when not given) with 121 grains, the Voronoi cells of lattice seeds that drift from frame to frame, and prints
+  host       the only route before it: graphs_from_images(strict=False), the union's arrays read back, the matcher and the
+             targets of the restatement (tests/trackcheck.py) on the host
+  samples    one frames_to_samples
+  calls      ggnn_track_junctions + ggnn_track_targets on prepared arguments
+host and samples by the host clock around work that ends in a synchronise, the calls by events; the same protocol as --union.
+The device activities of one frames_to_samples and of the two calls are counted at T = 8 and at T: they must not differ.
+    python tools/vectorize_cost.py --track 64 [--rounds 20]"""
 import argparse
 import ctypes
 import os
@@ -38,11 +47,14 @@ def main():
     ap.add_argument("--size", type=int, default=None, help="image side (default: 4096, with --union 128)")
     ap.add_argument("--boundary", choices=("periodic", "noflux"), default="periodic")
     ap.add_argument("--union", type=int, default=0, metavar="B")
+    ap.add_argument("--track", type=int, default=0, metavar="T")
     ap.add_argument("--seed", type=int, default=0)
     a = ap.parse_args()
     sys.path[:0] = [os.path.dirname(HERE)]
     if a.size is None:
-        a.size = 128 if a.union else 4096
+        a.size = 128 if a.union or a.track else 4096
+    if a.track:
+        return track_cost(a)
     if a.union:
         return union_cost(a)
     import numpy as np
@@ -215,6 +227,123 @@ def union_cost(a):
                         t = getattr(k, "cuda_time_total", 0.0) if t is None else t
                         if t:
                             print(f"    {k.count:3d} x {k.key[:110]}: {t:.1f} us by the tracer", flush=True)
+        except Exception as exc:   # (a build of torch without the tracer)
+            print(f"# launches not counted: {type(exc).__name__}: {exc}", flush=True)
+        print(f"# torch {torch.__version__}, {torch.cuda.get_device_name()}", flush=True)
+
+
+def lattice_frames(T, size, seed, device, cells=11):
+    """[T, size, size] int32: `lattice_images`' Voronoi image of one set of seeds that drift by a fraction of a pixel a frame."""
+    import torch
+    gen = torch.Generator(device="cpu").manual_seed(seed)
+    iy, ix = torch.meshgrid(torch.arange(cells), torch.arange(cells), indexing="ij")
+    sx = (ix + 0.5 * (iy % 2) + 0.25).reshape(-1) / cells + (torch.rand(cells * cells, generator=gen) - 0.5) * (0.3 / cells)
+    sy = (iy + 0.25).reshape(-1) / cells + (torch.rand(cells * cells, generator=gen) - 0.5) * (0.3 / cells)
+    vx, vy = ((torch.rand(2, cells * cells, generator=gen) - 0.5) * (0.6 / size))
+    px = ((torch.arange(size, dtype=torch.float32) + 0.5) / size).to(device)
+    out = []
+    for t in range(T):
+        x, y = (sx + t * vx).to(device), (sy + t * vy).to(device)
+        dx = (px[None, :, None] - x[None, None, :]).abs()
+        dy = (px[:, None, None] - y[None, None, :]).abs()
+        dx, dy = torch.minimum(dx, 1 - dx), torch.minimum(dy, 1 - dy)
+        out.append((dx * dx + dy * dy).argmin(dim=2).to(torch.int32) + 1)
+    return torch.stack(out)
+
+
+def track_cost(a):
+    import time
+    import numpy as np
+    import torch
+    sys.path[:0] = [os.path.join(os.path.dirname(HERE), "tests")]
+    import trackcheck as tc
+    from graingraphnn_amd import _lib
+    from graingraphnn_amd import vectorize as vz
+    from graingraphnn_amd.synthetic import EDGE_TYPES
+    if a.boundary != "periodic":
+        raise SystemExit("--track times periodic sequences")
+    T, size = a.track, a.size
+    dev = torch.device("cuda", 0)
+    lib = _lib.load()
+    with torch.no_grad():
+        frames = lattice_frames(T, size, a.seed, dev)
+        n_grain = int(frames.max())
+        rs = np.random.RandomState(a.seed)
+        theta_x, theta_z = rs.uniform(0, np.pi / 2, n_grain), rs.uniform(0, np.pi / 2, n_grain)
+        G, R, span = 2.0, 0.4, 6
+
+        def host(frames=frames):
+            res = vz.graphs_from_images(frames, [n_grain] * len(frames), strict=False)
+            counts = torch.stack([torch.bincount(f.reshape(-1).long(), minlength=n_grain + 1)[1:] for f in frames]).reshape(-1)
+            u = {"xy": res["xy"].cpu().numpy(), "triples": res["triples"].cpu().numpy(),
+                 "jj": res["edge_index_dict"][EDGE_TYPES[2]].cpu().numpy(), "counts": counts.cpu().numpy(), "status": res["status"],
+                 "joint_off": res["traj_offsets"]["joint"]}
+            return tc.track(u, n_grain, "periodic", shape=(size, size))
+
+        def samples(frames=frames):
+            out = vz.frames_to_samples(frames, theta_x, theta_z, G, R, span=span)
+            torch.cuda.synchronize()
+            return out
+
+        r = host()
+        got, report = samples()
+        same = report["pairs"] == r["pairs"] and report["counts"] == [r["counts"][t] for t, _ in r["pairs"]] and all(
+            np.array_equal(s[3]["joint"].cpu().numpy(), tc.cut(r, n_grain, t)[0]["joint"])
+            and np.array_equal(s[3]["edge_event"].cpu().numpy(), tc.cut(r, n_grain, t)[0]["edge_event"])
+            for (t, _), s in zip(r["pairs"], got))
+        total = {k: sum(c[k] for c in report["counts"]) for k in vz.PAIR_COUNTERS}
+        print(f"# {T} frames {size} x {size}, {n_grain} grains, {sum(s['n_joint'] for s in report['status'])} junctions, "
+              f"{len(report['pairs'])} pairs emitted, {len(report['skipped'])} skipped; totals {total}; the samples equal the host "
+              f"route's: {same}", flush=True)
+        whole = {n: vz._track(frames[:n], n_grain, "cells", 2, None, "periodic") for n in sorted({min(8, T), T})}
+        torch.cuda.synchronize()
+
+        def calls(n=T):
+            K, A = whole[n]["track_calls"][:2]
+            _lib.check(lib.ggnn_track_junctions(ctypes.byref(K), _lib.current_stream()), "track_junctions")
+            _lib.check(lib.ggnn_track_targets(ctypes.byref(A), _lib.current_stream()), "track_targets")
+
+        def by_events(call):
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            call()
+            t1.record()
+            t1.synchronize()
+            return t0.elapsed_time(t1) * 1e3
+
+        def by_clock(call):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            call()
+            return (time.perf_counter() - t0) * 1e6
+
+        arms = {"host": lambda: by_clock(host), "samples": lambda: by_clock(samples), "calls": lambda: by_events(calls)}
+        times = {k: [] for k in arms}
+        for rnd in range(a.rounds + 3):
+            for name, arm in arms.items():
+                t = arm()
+                if rnd >= 3:
+                    times[name].append(t)
+        for name, t in times.items():
+            t = np.array(t)
+            print(f"{name:10s} us: median {np.median(t):10.1f}  min {t.min():10.1f}  max {t.max():10.1f}", flush=True)
+        print(f"# host / samples = {np.median(times['host']) / np.median(times['samples']):.1f}", flush=True)
+        try:
+            from torch.profiler import ProfilerActivity, profile
+            for n in sorted(whole):
+                for name, call in (("vectorise + track", lambda: vz._track(frames[:n], n_grain, "cells", 2, None, "periodic")),
+                                   ("calls", lambda: calls(n))):
+                    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+                        call()
+                        torch.cuda.synchronize()
+                    k = sum(1 for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA)
+                    print(f"T = {n:3d}  {name:18s} device activities (kernels, memsets, copies) in one pass: {k}", flush=True)
+                    if name == "calls" and n == T:
+                        for e in sorted(prof.key_averages(), key=lambda e: e.key):
+                            t = getattr(e, "device_time_total", None)
+                            t = getattr(e, "cuda_time_total", 0.0) if t is None else t
+                            if t:
+                                print(f"    {e.count:3d} x {e.key[:110]}: {t:.1f} us by the tracer", flush=True)
         except Exception as exc:   # (a build of torch without the tracer)
             print(f"# launches not counted: {type(exc).__name__}: {exc}", flush=True)
         print(f"# torch {torch.__version__}, {torch.cuda.get_device_name()}", flush=True)
