@@ -29,6 +29,7 @@ GGNN_FLAG_QOI_OVERFLOW = 2
 GGNN_FLAG_POLYGON_OVERFLOW = 4
 GGNN_INTERP_MAX_JOBS = 256
 GGNN_JUNCTION_SEGMENT, GGNN_JUNCTION_STATUS_WORDS, GGNN_JUNCTION_MAX_BLOCKS = 256, 7, 1 << 22
+GGNN_TRACE_COUNTERS = 3
 GGNN_ADAM_CHUNK, GGNN_ADAM_MAX_TENSORS, GGNN_ADAM_MAX_GROUPS = 4096, 384, 8
 GGNN_ROWGEMM_MAX_PACK = 8
 GGNN_MSE_MAX_TERMS, GGNN_MSE_BLOCKS = 4, 64
@@ -62,6 +63,7 @@ EXPORTED_SYMBOLS = (
     "ggnn_polygon_inputs", "ggnn_interp_polygons",
     "ggnn_polygons_rasterize", "ggnn_image_compare", "ggnn_image_junctions", "ggnn_junction_links",
     "ggnn_image_junctions_traj", "ggnn_junction_links_traj", "ggnn_track_junctions", "ggnn_track_targets",
+    "ggnn_image_junction_windows_traj", "ggnn_junction_links_trace_traj",
     "ggnn_metric_record",
     "ggnn_masked_mse_rows", "ggnn_collate_batch", "ggnn_reverse_slots",
 )
@@ -463,6 +465,16 @@ class LinkTrajArgs(Structure):
     ]
 
 
+class LinkTraceArgs(Structure):
+    """Mirror of `ggnn_link_trace_args`."""
+    _fields_ = [
+        ("images", c_void_p), ("grain_off", c_void_p), ("triples", c_void_p), ("rep", c_void_p), ("rowptr", c_void_p),
+        ("col", c_void_p), ("edge_jj", c_void_p), ("status", c_void_p), ("counters", c_void_p),
+        ("nx", c_int64), ("ny", c_int64), ("n_image", c_int64), ("n_grain", c_int64), ("joint_capacity", c_int64),
+        ("E_cap", c_int64), ("max_trace", c_int64), ("merge_radius", c_int32), ("boundary", c_int32),
+    ]
+
+
 class TrackArgs(Structure):
     """Mirror of `ggnn_track_args`."""
     _fields_ = [
@@ -651,6 +663,10 @@ def _declare(lib):
     lib.ggnn_image_junctions_traj.argtypes = [POINTER(JunctionTrajArgs), c_void_p]
     lib.ggnn_junction_links_traj.restype = c_int
     lib.ggnn_junction_links_traj.argtypes = [POINTER(LinkTrajArgs), c_void_p]
+    lib.ggnn_image_junction_windows_traj.restype = c_int
+    lib.ggnn_image_junction_windows_traj.argtypes = [POINTER(JunctionTrajArgs), c_void_p, c_void_p]
+    lib.ggnn_junction_links_trace_traj.restype = c_int
+    lib.ggnn_junction_links_trace_traj.argtypes = [POINTER(LinkTraceArgs), c_void_p]
     lib.ggnn_track_junctions.restype = c_int
     lib.ggnn_track_junctions.argtypes = [POINTER(TrackArgs), c_void_p]
     lib.ggnn_track_targets.restype = c_int

@@ -3,6 +3,7 @@
 // (graph_trajectory.py:316-376 needs its solver's `node_region`).
 //   ggnn_image_junctions = windows, representatives, numbering, positions, triples, grain->joint columns, status
 //   ggnn_junction_links  = the joint->joint columns from the triples and the joint->grain table
+//   ggnn_junction_links_trace_traj = the columns that rule leaves open because two grains meet twice, by following the boundary
 // The rule is exact in integers up to the one fp32 expression of a position (include/ggnn.h; tests/vectorcheck.py restates
 // it by brute force):
 //   window (y, x) = pixels TL (y, x), TR (y, x + 1), BL (y + 1, x), BR (y + 1, x + 1), periodic; raster index y nx + x
@@ -298,7 +299,8 @@ __device__ __forceinline__ int64_t segment_of(const int64_t* __restrict__ off, i
 }
 
 template <bool EMIT, int BC>
-__global__ __launch_bounds__(VEC_BLOCK) void image_junctions_traj_kernel(const ggnn_junction_traj_args A, int segments, int rows) {
+__global__ __launch_bounds__(VEC_BLOCK) void image_junctions_traj_kernel(const ggnn_junction_traj_args A, int segments, int rows,
+                                                                         int32_t* __restrict__ rep_out) {
   __shared__ int wave_total[VEC_WAVES];
   constexpr int FIRST = BC == GGNN_BC_PERIODIC ? 0 : -1;
   const int nx = (int)A.nx, ny = (int)A.ny, R = A.merge_radius;
@@ -378,6 +380,8 @@ __global__ __launch_bounds__(VEC_BLOCK) void image_junctions_traj_kernel(const g
         A.edge_gj[3 * j + c] = g;
         A.edge_gj[ld + 3 * j + c] = j;
       }
+      // (ggnn_image_junction_windows_traj: the representative's raster index within its image, below 2^30)
+      if (rep_out) rep_out[j] = BC == GGNN_BC_PERIODIC ? y * nx + x : (y + 1) * (nx + 1) + (x + 1);
     }
     ++j;
   }
@@ -471,6 +475,217 @@ __global__ __launch_bounds__(256) void junction_links_traj_kernel(const ggnn_lin
     atomicAdd((unsigned long long*)A.status + segment_of(joint_off, A.n_image, j) * GGNN_JUNCTION_STATUS_WORDS + 4, 1ull);
 }
 
+// ---- Linking by tracing boundaries (ggnn_junction_links_trace_traj; tests/tracecheck.py restates the rule) ------------------
+// The columns junction_links_traj_kernel left open -- a pair of grains held by more than one other junction: a lens on a
+// boundary, a band from wall to wall -- are linked by following the a | b boundary through the image, pixel edge by pixel
+// edge, from the junction to the one at the other end.  A thread takes a column and returns at once unless it is open; the
+// open ones are a handful an image and each is a chain of dependent reads that L2 serves, so there is no compaction and no
+// tile: the few lanes that walk do so alone, and a wave without an open column is done after one load.  Every loop is
+// bounded: the neighbourhoods by (2R + 1)^2, a row of the table by E_cap, the walk by max_trace.  A thread writes its own
+// column only and reads no other's, so the reverse column is found by its own thread, which walks the same chain backwards.
+constexpr int TRACE_TRACED = 0, TRACE_FAILED = 1, TRACE_OVERFLOW = 2;
+// The three large helpers stay OUT OF LINE.  Inlined into one body (some 7000 instructions, exits worked out at two places
+// inside the walk) the periodic instantiation spilled over a hundred scalar registers into vector lanes across its nested
+// divergent loops and, at -O3 on gfx950, failed every walk along a horizontal stretch of boundary, while the same source links
+// them on the host (plain and under the address, undefined-behaviour and memory sanitizers), at -O1, and out of line.  As
+// calls the kernel is a fifth of the size, and the path is a rare one (tests/test_trace_links.py walks both directions).
+#define TRACE_FN __device__ __attribute__((noinline))
+
+struct trace_image {             // the image of a column, as its thread sees it
+  const int32_t* image;          // [ny, nx]
+  const int32_t* triples;        // the union's
+  const int32_t* rep;
+  const int32_t* rowptr;
+  const int32_t* col;
+  int64_t g0, n_total;           // the image's first union grain; the union's grains
+  int64_t j_lo, j_hi;            // the image's junctions that were kept
+  int64_t E_cap;
+  int32_t n_grain;               // the image's
+  int nx, ny, R;
+};
+
+// The window of raster index r -> is it one.
+template <int BC>
+__device__ bool trace_window(const trace_image& I, int32_t r, int& y, int& x) {
+  const int w = BC == GGNN_BC_PERIODIC ? I.nx : I.nx + 1, h = BC == GGNN_BC_PERIODIC ? I.ny : I.ny + 1;
+  if (r < 0 || (int64_t)r >= (int64_t)w * h) return false;
+  y = r / w, x = r - y * w;
+  if (BC == GGNN_BC_NOFLUX) --y, --x;
+  return true;
+}
+
+template <int BC>
+__device__ __forceinline__ bool trace_in_range(const trace_image& I, int y, int x) {
+  return BC == GGNN_BC_PERIODIC ? (unsigned)y < (unsigned)I.ny && (unsigned)x < (unsigned)I.nx
+                                : y >= -1 && y < I.ny && x >= -1 && x < I.nx;
+}
+
+// Does (yb, xb) lie at an offset within R of (ya, xa): the minimum image, or the plain difference between walls.
+template <int BC>
+__device__ __forceinline__ bool trace_near(const trace_image& I, int ya, int xa, int yb, int xb) {
+  int dy = yb - ya, dx = xb - xa;
+  if (BC == GGNN_BC_PERIODIC) {
+    dy += dy < 0 ? I.ny : 0, dx += dx < 0 ? I.nx : 0;
+    return (dy <= I.R || dy >= I.ny - I.R) && (dx <= I.R || dx >= I.nx - I.R);
+  }
+  return dy >= -I.R && dy <= I.R && dx >= -I.R && dx <= I.R;
+}
+
+// The vertex across crack d (UP, DOWN, LEFT, RIGHT) of (y, x): wrapped on the torus, as it is between walls (the caller
+// tests the range before it reads there).
+template <int BC>
+__device__ __forceinline__ void trace_step(const trace_image& I, int y, int x, int d, int& y2, int& x2) {
+  y2 = y + (d == 0 ? -1 : d == 1 ? 1 : 0), x2 = x + (d == 2 ? -1 : d == 3 ? 1 : 0);
+  if (BC == GGNN_BC_PERIODIC) {
+    y2 += y2 < 0 ? I.ny : y2 >= I.ny ? -I.ny : 0;
+    x2 += x2 < 0 ? I.nx : x2 >= I.nx ? -I.nx : 0;
+  }
+}
+
+// The four pixels TL, TR, BL, BR of an in-range window, and its a | b cracks as a mask of UP, DOWN, LEFT, RIGHT.
+template <int BC>
+__device__ int trace_cracks(const trace_image& I, int y, int x, int32_t ia, int32_t ib, int32_t (&px)[4]) {
+  const int x1 = BC == GGNN_BC_PERIODIC && x + 1 == I.nx ? 0 : x + 1, y1 = BC == GGNN_BC_PERIODIC && y + 1 == I.ny ? 0 : y + 1;
+  px[0] = pixel_at<BC>(I.image, y, x, I.nx, I.ny), px[1] = pixel_at<BC>(I.image, y, x1, I.nx, I.ny);
+  px[2] = pixel_at<BC>(I.image, y1, x, I.nx, I.ny), px[3] = pixel_at<BC>(I.image, y1, x1, I.nx, I.ny);
+  const auto ab = [&](int p, int q) { return (px[p] == ia && px[q] == ib) || (px[p] == ib && px[q] == ia); };
+  return (ab(0, 1) ? 1 : 0) | (ab(2, 3) ? 2 : 0) | (ab(0, 2) ? 4 : 0) | (ab(1, 3) ? 8 : 0);
+}
+
+// The junction that owns the carrier (y, x) of the local key: the smallest kept one of the image with that triple whose
+// representative lies within R, found in the joint->grain row of the key's last grain (never a no-flux boundary grain, whose
+// row holds every wall junction); -1: nobody.
+template <int BC>
+TRACE_FN int64_t trace_owner(const trace_image& I, int y, int x, const int32_t (&key)[3]) {
+  const int64_t g = I.g0 + key[2];
+  if (g < 0 || g >= I.n_total) return -1;
+  const int64_t p0 = min((int64_t)max(I.rowptr[g], 0), I.E_cap);
+  const int64_t p1 = min(max((int64_t)I.rowptr[g + 1], p0), I.E_cap);
+  int64_t best = -1;
+  for (int64_t p = p0; p < p1; ++p) {
+    const int64_t o = I.col[p];
+    if (o < I.j_lo || o >= I.j_hi || (best >= 0 && o > best)) continue;
+    if (I.triples[3 * o] != I.g0 + key[0] || I.triples[3 * o + 1] != I.g0 + key[1] || I.triples[3 * o + 2] != g) continue;
+    int ry, rx;
+    if (!trace_window<BC>(I, I.rep[o], ry, rx) || !trace_near<BC>(I, ry, rx, y, x)) continue;
+    best = o;
+  }
+  return best;
+}
+
+template <int BC>
+__device__ bool trace_owned(const trace_image& I, int64_t j, const int32_t (&key)[3], int y, int x) {
+  return trace_in_range<BC>(I, y, x) && window_carries<BC>(I.image, y, x, I.nx, I.ny, I.n_grain, key) &&
+         trace_owner<BC>(I, y, x, key) == j;
+}
+
+// The exits of junction j (local key) for the ids ia, ib -> how many, the last one as the vertex reached and the crack taken;
+// n_diag, (qy, qx): the quadruple windows owned by j whose TL and BR are the two ids, and the last of them.
+template <int BC>
+TRACE_FN int trace_exits(const trace_image& I, int64_t j, const int32_t (&key)[3], int32_t ia, int32_t ib, int& ey, int& ex,
+                           int& ed, int& n_diag, int& qy, int& qx) {
+  int n = 0, ry, rx;
+  n_diag = 0;
+  if (!trace_window<BC>(I, I.rep[j], ry, rx)) return 0;
+  for (int dy = -I.R; dy <= I.R; ++dy)
+    for (int dx = -I.R; dx <= I.R; ++dx) {
+      int y = ry + dy, x = rx + dx;
+      if (BC == GGNN_BC_PERIODIC) {
+        y += y < 0 ? I.ny : y >= I.ny ? -I.ny : 0;
+        x += x < 0 ? I.nx : x >= I.nx ? -I.nx : 0;
+      }
+      if (!trace_owned<BC>(I, j, key, y, x)) continue;
+      int32_t px[4];
+      const int cracks = trace_cracks<BC>(I, y, x, ia, ib, px);
+      const bool quad = px[0] != px[1] && px[0] != px[2] && px[0] != px[3] && px[1] != px[2] && px[1] != px[3] && px[2] != px[3];
+      if (quad && ((px[0] == ia && px[3] == ib) || (px[0] == ib && px[3] == ia))) ++n_diag, qy = y, qx = x;
+      for (int d = 0; d < 4; ++d) {
+        if (!(cracks >> d & 1)) continue;
+        int y2, x2;
+        trace_step<BC>(I, y, x, d, y2, x2);
+        if (!trace_owned<BC>(I, j, key, y2, x2)) ++n, ey = y2, ex = x2, ed = d;
+      }
+    }
+  return n;
+}
+
+// The partner of junction j (local key) for its local grains a, b -> TRACE_*; o: the partner when traced.
+template <int BC>
+TRACE_FN int trace_partner(const trace_image& I, int64_t j, const int32_t (&key)[3], int32_t a, int32_t b, int64_t max_trace,
+                             int64_t& o) {
+  const int32_t ia = a + 1, ib = b + 1;
+  int y = 0, x = 0, d = 0, n_diag, qy = 0, qx = 0;
+  const int n_exit = trace_exits<BC>(I, j, key, ia, ib, y, x, d, n_diag, qy, qx);
+  int32_t k[2][3];
+  bool unused;
+  if (n_diag) {   // the diagonal of a quadruple window: its two junctions, when each has this one diagonal
+    if (n_diag != 1) return TRACE_FAILED;
+    if (window_keys<BC>(I.image, qy, qx, I.nx, I.ny, I.n_grain, k, unused) != 2) return TRACE_FAILED;
+    const int other = k[0][0] == key[0] && k[0][1] == key[1] && k[0][2] == key[2] ? 1 : 0;
+    o = trace_owner<BC>(I, qy, qx, k[other]);
+    if (o < 0 || o == j) return TRACE_FAILED;
+    int ty, tx, td, their_diag, ry = 0, rx = 0;
+    trace_exits<BC>(I, o, k[other], ia, ib, ty, tx, td, their_diag, ry, rx);
+    return their_diag == 1 && ry == qy && rx == qx ? TRACE_TRACED : TRACE_FAILED;
+  }
+  if (n_exit != 1) return TRACE_FAILED;
+  int arrived = d ^ 1;   // (UP <-> DOWN, LEFT <-> RIGHT)
+  for (int64_t steps = 1;; ++steps) {
+    if (steps > max_trace) return TRACE_OVERFLOW;
+    if (!trace_in_range<BC>(I, y, x)) return TRACE_FAILED;
+    const int n_keys = window_keys<BC>(I.image, y, x, I.nx, I.ny, I.n_grain, k, unused);
+    for (int i = 0; i < n_keys; ++i) {
+      const bool has_a = k[i][0] == a || k[i][1] == a || k[i][2] == a, has_b = k[i][0] == b || k[i][1] == b || k[i][2] == b;
+      if (!(has_a && has_b)) continue;
+      o = trace_owner<BC>(I, y, x, k[i]);   // the junction at the other end
+      if (o < 0 || o == j) return TRACE_FAILED;
+      int ty, tx, td, their_diag, ry, rx;
+      const int theirs = trace_exits<BC>(I, o, k[i], ia, ib, ty, tx, td, their_diag, ry, rx);
+      return their_diag == 0 && theirs == 1 ? TRACE_TRACED : TRACE_FAILED;
+    }
+    int32_t px[4];
+    const int cracks = trace_cracks<BC>(I, y, x, ia, ib, px);
+    if (__popc(cracks) != 2 || !(cracks >> arrived & 1)) return TRACE_FAILED;   // (one: a dead end; four: [a b; b a])
+    d = __ffs(cracks & ~(1 << arrived)) - 1;
+    int y2, x2;
+    trace_step<BC>(I, y, x, d, y2, x2);
+    y = y2, x = x2, arrived = d ^ 1;
+  }
+}
+
+template <int BC>
+__global__ __launch_bounds__(256) void junction_trace_kernel(const ggnn_link_trace_args A) {
+  const int64_t* joint_off = A.status + A.n_image * GGNN_JUNCTION_STATUS_WORDS;
+  const int64_t n = min(max(joint_off[A.n_image], (int64_t)0), A.joint_capacity);
+  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (s >= 3 * n) return;
+  int64_t* slot = A.edge_jj + 3 * A.joint_capacity + s;
+  if (*slot != -1) return;   // (every column of a structure without open pairs)
+  const int64_t j = s / 3;
+  const int c = (int)(s - 3 * j);
+  const int64_t b = segment_of(joint_off, A.n_image, j);
+  trace_image I;
+  I.g0 = image_grains(A.grain_off, b, A.n_grain, I.n_grain);
+  I.image = A.images + b * A.ny * A.nx;
+  I.triples = A.triples, I.rep = A.rep, I.rowptr = A.rowptr, I.col = A.col;
+  I.n_total = A.n_grain, I.E_cap = A.E_cap;
+  I.j_lo = min(max(joint_off[b], (int64_t)0), n), I.j_hi = min(max(joint_off[b + 1], I.j_lo), n);
+  I.nx = (int)A.nx, I.ny = (int)A.ny, I.R = A.merge_radius;
+  int32_t key[3];
+  bool inside = true;
+  for (int i = 0; i < 3; ++i) {
+    const int64_t g = (int64_t)A.triples[3 * j + i] - I.g0;
+    inside = inside && g >= 0 && g < I.n_grain;
+    key[i] = (int32_t)g;
+  }
+  int64_t o = -1;
+  const int what = inside ? trace_partner<BC>(I, j, key, key[c == 2 ? 1 : 0], key[c == 0 ? 1 : 2], A.max_trace, o) : TRACE_FAILED;
+  atomicAdd((unsigned long long*)A.counters + GGNN_TRACE_COUNTERS * b + what, 1ull);
+  if (what != TRACE_TRACED) return;
+  *slot = o;
+  atomicAdd((unsigned long long*)A.status + b * GGNN_JUNCTION_STATUS_WORDS + 4, ~0ull);   // one open pair fewer
+}
+
 }  // namespace ggnn
 
 extern "C" int ggnn_image_junctions(const ggnn_junction_args* args, ggnn_stream_t stream) {
@@ -518,7 +733,8 @@ extern "C" int ggnn_junction_links(const ggnn_link_args* args, ggnn_stream_t str
   return launch_status();
 }
 
-extern "C" int ggnn_image_junctions_traj(const ggnn_junction_traj_args* args, ggnn_stream_t stream) {
+// ggnn_image_junctions_traj (rep NULL) and ggnn_image_junction_windows_traj: the same checks, the same launches.
+static int image_junctions_traj(const ggnn_junction_traj_args* args, int32_t* rep, ggnn_stream_t stream) {
   using namespace ggnn;
   if (!args) return GGNN_EINVAL;
   const ggnn_junction_traj_args& A = *args;
@@ -546,11 +762,20 @@ extern "C" int ggnn_image_junctions_traj(const ggnn_junction_traj_args* args, gg
   if (hipMemsetAsync(A.pixel_counts, 0, (size_t)A.n_grain * sizeof(uint64_t), st) != hipSuccess) return GGNN_ELAUNCH;
   const auto count = periodic ? image_junctions_traj_kernel<false, GGNN_BC_PERIODIC> : image_junctions_traj_kernel<false, GGNN_BC_NOFLUX>;
   const auto emit = periodic ? image_junctions_traj_kernel<true, GGNN_BC_PERIODIC> : image_junctions_traj_kernel<true, GGNN_BC_NOFLUX>;
-  hipLaunchKernelGGL(count, dim3((unsigned)n_blocks), dim3(VEC_BLOCK), 0, st, A, segments, (int)wy);
+  hipLaunchKernelGGL(count, dim3((unsigned)n_blocks), dim3(VEC_BLOCK), 0, st, A, segments, (int)wy, (int32_t*)nullptr);
   hipLaunchKernelGGL(junction_scan_traj_kernel, dim3(1), dim3(VEC_SCAN_BLOCK), 0, st, A.workspace, n_blocks, per_image,
                      A.pixel_counts, A.grain_off, (int64_t)(periodic ? 0 : 1), A.n_grain, A.n_image, A.joint_capacity, A.status);
-  hipLaunchKernelGGL(emit, dim3((unsigned)n_blocks), dim3(VEC_BLOCK), 0, st, A, segments, (int)wy);
+  hipLaunchKernelGGL(emit, dim3((unsigned)n_blocks), dim3(VEC_BLOCK), 0, st, A, segments, (int)wy, rep);
   return launch_status();
+}
+
+extern "C" int ggnn_image_junctions_traj(const ggnn_junction_traj_args* args, ggnn_stream_t stream) {
+  return image_junctions_traj(args, nullptr, stream);
+}
+
+extern "C" int ggnn_image_junction_windows_traj(const ggnn_junction_traj_args* args, int32_t* rep, ggnn_stream_t stream) {
+  if (!rep) return GGNN_EINVAL;
+  return image_junctions_traj(args, rep, stream);
 }
 
 extern "C" int ggnn_junction_links_traj(const ggnn_link_traj_args* args, ggnn_stream_t stream) {
@@ -566,5 +791,33 @@ extern "C" int ggnn_junction_links_traj(const ggnn_link_traj_args* args, ggnn_st
   hipLaunchKernelGGL(zero_open_pairs_kernel, dim3((unsigned)((A.n_image + 255) / 256)), dim3(256), 0, st, A.status, A.n_image);
   const int64_t blocks = (3 * A.joint_capacity + 255) / 256;
   hipLaunchKernelGGL(junction_links_traj_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A);
+  return launch_status();
+}
+
+extern "C" int ggnn_junction_links_trace_traj(const ggnn_link_trace_args* args, ggnn_stream_t stream) {
+  using namespace ggnn;
+  if (!args) return GGNN_EINVAL;
+  const ggnn_link_trace_args& A = *args;
+  if (!A.images || !A.grain_off || !A.triples || !A.rep || !A.rowptr || !A.col || !A.edge_jj || !A.status || !A.counters)
+    return GGNN_EINVAL;
+  if (A.n_grain < 1 || A.n_grain >= INT32_MAX - 1 || A.E_cap < 0 || A.E_cap >= INT32_MAX) return GGNN_EINVAL;
+  if (A.joint_capacity < 1 || A.joint_capacity > INT32_MAX / 3) return GGNN_EINVAL;
+  if (A.n_image < 1 || A.n_image > GGNN_JUNCTION_MAX_BLOCKS) return GGNN_EINVAL;
+  if (A.merge_radius < 0 || A.merge_radius > VEC_MAX_RADIUS) return GGNN_EINVAL;
+  if (A.nx <= 2 * A.merge_radius || A.ny <= 2 * A.merge_radius || A.nx >= (1 << 15) || A.ny >= (1 << 15)) return GGNN_EINVAL;
+  if (A.boundary != GGNN_BC_PERIODIC && A.boundary != GGNN_BC_NOFLUX) return GGNN_EINVAL;
+  if (A.max_trace < 1) return GGNN_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(A.status) | reinterpret_cast<uintptr_t>(A.edge_jj) | reinterpret_cast<uintptr_t>(A.counters) |
+       reinterpret_cast<uintptr_t>(A.grain_off)) & 7u)
+    return GGNN_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(A.images) | reinterpret_cast<uintptr_t>(A.triples) | reinterpret_cast<uintptr_t>(A.rep) |
+       reinterpret_cast<uintptr_t>(A.rowptr) | reinterpret_cast<uintptr_t>(A.col)) & 3u)
+    return GGNN_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(A.counters, 0, (size_t)A.n_image * GGNN_TRACE_COUNTERS * sizeof(int64_t), st) != hipSuccess)
+    return GGNN_ELAUNCH;
+  const int64_t blocks = (3 * A.joint_capacity + 255) / 256;
+  const auto trace = A.boundary == GGNN_BC_PERIODIC ? junction_trace_kernel<GGNN_BC_PERIODIC> : junction_trace_kernel<GGNN_BC_NOFLUX>;
+  hipLaunchKernelGGL(trace, dim3((unsigned)blocks), dim3(256), 0, st, A);
   return launch_status();
 }

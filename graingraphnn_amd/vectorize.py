@@ -30,6 +30,11 @@ by their grain triple -- the reference's own mask rule, form_gradient:884-889 --
 edge labels and history columns of `training.DeviceDataset`'s samples are derived from the match on the device, what the
 reference gets from its junction tracker (graph_trajectory.py:283-846) and form_gradient (graph_datastruct.py:851-1011).
 
+`links="trace"` adds a second linking rule to all of these (ggnn_image_junction_windows_traj, ggnn_junction_links_trace_traj;
+tests/tracecheck.py): a pair of grains that more than one other junction holds -- two grains that share two separate
+stretches of boundary: a lens on a boundary, a band from wall to wall -- is linked by following the boundary through the image,
+on the device and exact in integers; the default `links="unique"` is the rule above, launch for launch.
+
 Not covered: stacks of mixed image shapes, resolving a quadruple from a history (the diagonal is fixed, and counted in the
 status), the reference's `edge` length target (its edge_len head is disabled in every shipped configuration) and its
 `elim_list` scaling of shrinking grains (commented out in the reference)."""
@@ -50,6 +55,8 @@ GRIDS = {"cells": lambda nx: (np.float32(1.0), np.float32(1.0) / np.float32(nx))
 
 
 BOUNDARIES = {"periodic": _lib.BC_PERIODIC, "noflux": _lib.BC_NOFLUX}
+LINKS = ("unique", "trace")
+TRACE_COUNTERS = ("n_traced", "n_trace_failed", "n_trace_overflow")
 EULER = {"periodic": "n_joint == 2 n_present_grains", "noflux": "n_joint == 2 n_present_grains - 2"}
 
 
@@ -64,6 +71,18 @@ def status_is_valid(status, boundary="periodic"):
 def _check_boundary(boundary):
     if boundary not in BOUNDARIES:
         raise _lib.GGNNError(f"boundary must be 'periodic' or 'noflux', got {boundary!r}")
+
+
+def _check_links(links, max_trace, nx, ny):
+    """-> max_trace as the trace call takes it (None: 4 (nx + ny)), or None for links="unique"."""
+    if links not in LINKS:
+        raise ValueError(f"links must be 'unique' or 'trace', got {links!r}")
+    if links == "unique":
+        return None
+    max_trace = 4 * (nx + ny) if max_trace is None else int(max_trace)
+    if max_trace < 1:
+        raise ValueError(f"max_trace must be at least 1, got {max_trace}")
+    return max_trace
 
 
 def image_max_y(nx, ny, grid):
@@ -130,7 +149,7 @@ def _vectorize(image, n_grain, grid, merge_radius, joint_capacity, boundary="per
 
 
 def graph_from_image(image, n_grain=None, grid="cells", merge_radius=2, joint_capacity=None, strict=True,
-                     boundary="periodic"):
+                     boundary="periodic", links="unique", max_trace=None):
     """The junction graph of a grain-ID image, periodic or (boundary="noflux") with walls.
 
     image: integer [ny, nx] on the device, pixel p = grain p - 1 (what `grain_image` writes); n_grain: the number of grains
@@ -149,19 +168,42 @@ def graph_from_image(image, n_grain=None, grid="cells", merge_radius=2, joint_ca
     2 n_present_grains - 2 junctions, and the junctions of grain 0 lie on the walls x = 0, x = 1, y = 0 and y = max_y.
     -> (xy, triples, edge_index_dict, status, corner_grains, max_y): the four as above, the ids of the corner pixels [0, 0],
     [0, nx - 1], [ny - 1, 0], [ny - 1, nx - 1] as `grain_image(corner_grains=)` takes them (they come with the status: still
-    one read-back), and the far y wall as a float that is exact in fp32, for `GrainRollout(boundary="noflux", max_y=)`."""
-    xy, triples, ei, status, v = _graph(image, n_grain, grid, merge_radius, joint_capacity, strict, boundary)
+    one read-back), and the far y wall as a float that is exact in fp32, for `GrainRollout(boundary="noflux", max_y=)`.
+
+    links="unique" (the default) is the rule above: a pair of grains that MORE than one other junction holds stays open, and
+    the structure is invalid -- which is what two grains look like that share two separate stretches of boundary: a lens on a
+    boundary, a band from wall to wall.  links="trace" links those columns too, by following the boundary through the image
+    from the junction to the one at its other end (ggnn_junction_links_trace_traj; tests/tracecheck.py), on the
+    device and exact in integers; max_trace bounds a walk (None: 4 (nx + ny) vertices).  The image goes through the one-image
+    union, which equals this path bit for bit; a structure without open pairs comes out as with "unique".  The status gains
+    n_traced, n_trace_failed and n_trace_overflow (directed columns), n_open_pairs is what is still open, and strict judges
+    that.  Still one read-back.  Any other value raises ValueError."""
+    xy, triples, ei, status, v = _graph(image, n_grain, grid, merge_radius, joint_capacity, strict, boundary, links, max_trace)
     if boundary == "noflux":
         return xy, triples, ei, status, v["corner_grains"], v["max_y"]
     return xy, triples, ei, status
 
 
-def _graph(image, n_grain, grid, merge_radius, joint_capacity, strict, boundary="periodic"):
+def _graph(image, n_grain, grid, merge_radius, joint_capacity, strict, boundary="periodic", links="unique", max_trace=None):
     """graph_from_image's four, with the capacity-sized arrays behind its results as a fifth."""
-    v = _vectorize(image, n_grain, grid, merge_radius, joint_capacity, boundary)
-    words = v["status"].tolist()
-    status = dict(zip(STATUS_WORDS, words))
-    v["corner_grains"] = tuple(words[len(STATUS_WORDS):]) if boundary == "noflux" else None
+    _check_links(links, max_trace, 1, 1)
+    if links == "unique":
+        v = _vectorize(image, n_grain, grid, merge_radius, joint_capacity, boundary)
+        words = v["status"].tolist()
+        status = dict(zip(STATUS_WORDS, words))
+        v["corner_grains"] = tuple(words[len(STATUS_WORDS):]) if boundary == "noflux" else None
+    else:   # the one-image union: the same bits, and the trace call exists for unions alone
+        _check_boundary(boundary)
+        if not isinstance(image, torch.Tensor) or not image.is_cuda or image.dim() != 2:
+            raise _lib.GGNNError("image must be a [ny, nx] device tensor of grain ids (pixel p = grain p - 1)")
+        _check_links(links, max_trace, image.size(1), image.size(0))
+        if n_grain is None:
+            n_grain = int(image.max())   # (a read-back of its own: pass n_grain to avoid it)
+        v = _vectorize_union(_stack(image[None]), [int(n_grain)], grid, merge_radius, joint_capacity, boundary, links=links,
+                             max_trace=max_trace)
+        res, _ = _graphs_of(v, v["status"].tolist(), False)   # the one read-back
+        status = res["status"][0]
+        v["corner_grains"] = res["corner_grains"][0] if boundary == "noflux" else None
     if strict and not status_is_valid(status, boundary):
         raise ValueError(f"the image is not a valid {boundary} grain structure: {status} (valid: overflow, n_invalid_pixels "
                          f"and n_open_pairs 0 and {EULER[boundary]}; joint_capacity {v['capacity']})")
@@ -179,7 +221,9 @@ def sample_from_image(image, theta_x, theta_z, G, R, span=None, patch_pixels=Non
     once); G, R: the process parameters; span: the frame span (None: `synthetic.span_for(G, R)`); patch_pixels: the pixels
     of one training-size patch, the area feature being fp32(count / patch_pixels) of a double quotient (None: nx ny).
     Grain centres come from ggnn_grain_centres on the junctions found, edge lengths from the rollout's own edge refresh;
-    the gradient columns are 0.  Other keywords go to `graph_from_image`; an invalid structure always raises.
+    the gradient columns are 0.  Other keywords go to `graph_from_image` (links="trace" among them: a grain with two sides, a
+    lens, and the doubled joint->joint column between its two junctions are plain list entries); an invalid structure always
+    raises.
 
     boundary="noflux": the angles count the boundary grain, theta[0], and the result is what
     `GrainRollout(..., boundary="noflux", max_y=image_max_y(nx, ny, grid))` takes: the FULL edge lists, grain 0's edges
@@ -195,7 +239,7 @@ def sample_from_image(image, theta_x, theta_z, G, R, span=None, patch_pixels=Non
     kw.pop("strict", None)
     boundary = kw.pop("boundary", "periodic")
     xy, _, ei, _, v = _graph(image, n_grain, kw.pop("grid", "cells"), kw.pop("merge_radius", 2),
-                             kw.pop("joint_capacity", None), True, boundary)
+                             kw.pop("joint_capacity", None), True, boundary, kw.pop("links", "unique"), kw.pop("max_trace", None))
     if kw:
         raise TypeError(f"sample_from_image: unknown keywords {sorted(kw)}")
     be, dev = default_backend(), xy.device
@@ -205,7 +249,8 @@ def sample_from_image(image, theta_x, theta_z, G, R, span=None, patch_pixels=Non
     fg, fj = feature_rows(theta_x, theta_z, xy.size(0), G, R, span)
     x_grain, x_joint = torch.from_numpy(fg.astype(np.float32)).to(dev), torch.from_numpy(fj.astype(np.float32)).to(dev)
     x_joint[:, :2] = xy
-    x_grain[:, 3] = (v["counts"][1:].to(torch.float64) / float(patch_pixels or nx * ny)).to(torch.float32)
+    counts = v["counts"] if "n_image" in v else v["counts"][1:]   # (the one-image union of links="trace" counts grains, not ids)
+    x_grain[:, 3] = (counts.to(torch.float64) / float(patch_pixels or nx * ny)).to(torch.float32)
     csr = v["csr"]
     csr_jg = type(csr)(csr.rowptr[:n_grain + 1], csr.col, csr.perm, csr.row, csr.unit_ptr, csr.units, csr.E)
     be.grain_centres(csr_jg, x_joint, x_grain, boundary=boundary)
@@ -245,17 +290,22 @@ def grain_offsets(n_grains, device):
     return off.tolist(), torch.from_numpy(off).to(device)
 
 
-def _vectorize_union(images, n_grains, grid, merge_radius, joint_capacity, boundary="periodic", grain_off=None, extra_words=0):
+def _vectorize_union(images, n_grains, grid, merge_radius, joint_capacity, boundary="periodic", grain_off=None, extra_words=0,
+                     links="unique", max_trace=None):
     """`_vectorize` for a stack: every launch, no read-back.  images: what `_stack` returns; grain_off: what `grain_offsets`
     returns (None: formed here, an upload -- pass it to a stream capture).  The status tensor holds the B status rows, behind
     them joint_off [B + 1] and, for no-flux, the 4 B corner pixels: one read-back fetches them all (extra_words: zeroed room
-    behind those, for the counters of a caller that wants them in the same read-back)."""
+    behind those, for the counters of a caller that wants them in the same read-back).  links="trace": the vectorisation also
+    writes `rep`, ggnn_junction_links_trace_traj follows the links call, and its 3 B counters lie behind the corner pixels, at
+    v["trace_words"] (None for "unique", whose launches and words are what they were)."""
     be = default_backend()
     _check_boundary(boundary)
     noflux = boundary == "noflux"
     if grid not in GRIDS:
         raise _lib.GGNNError(f"grid must be 'cells' or 'points', got {grid!r}")
     B, ny, nx = images.shape
+    max_trace = _check_links(links, max_trace, nx, ny)
+    trace = links == "trace"
     dev = images.device
     if len(n_grains) != B:
         raise _lib.GGNNError("n_grains must hold one count per image")
@@ -269,7 +319,9 @@ def _vectorize_union(images, n_grains, grid, merge_radius, joint_capacity, bound
     gj = torch.stack([slots + n_total, slots])
     jj = torch.full((2, 3 * cap), -1, dtype=torch.int64, device=dev)
     W = _lib.GGNN_JUNCTION_STATUS_WORDS
-    status = torch.zeros(B * W + B + 1 + (4 * B if noflux else 0) + extra_words, dtype=torch.int64, device=dev)
+    trace_words = B * W + B + 1 + (4 * B if noflux else 0) if trace else None
+    status = torch.zeros(B * W + B + 1 + (4 * B if noflux else 0) + (_lib.GGNN_TRACE_COUNTERS * B if trace else 0) + extra_words,
+                         dtype=torch.int64, device=dev)
     if noflux:   # per image, the order of grain_image(corner_grains=)
         status[B * W + B + 1:B * W + 5 * B + 1] = torch.stack([images[:, 0, 0], images[:, 0, -1], images[:, -1, 0], images[:, -1, -1]], 1).reshape(-1)
     wy, wx = (ny + 1, nx + 1) if noflux else (ny, nx)
@@ -282,26 +334,42 @@ def _vectorize_union(images, n_grains, grid, merge_radius, joint_capacity, bound
                                                                       _lib.ptr(ws), 4 * ws.numel())
     A.nx, A.ny, A.n_image, A.n_grain, A.joint_capacity = nx, ny, B, n_total, cap
     A.offset, A.pitch, A.merge_radius, A.boundary = float(off), float(pitch), R, BOUNDARIES[boundary]
-    _lib.check(be.lib.ggnn_image_junctions_traj(ctypes.byref(A), _lib.current_stream()), "ggnn_image_junctions_traj")
+    rep = None
+    if trace:
+        rep = torch.zeros(cap, dtype=torch.int32, device=dev)
+        _lib.check(be.lib.ggnn_image_junction_windows_traj(ctypes.byref(A), _lib.ptr(rep), _lib.current_stream()),
+                   "ggnn_image_junction_windows_traj")
+    else:
+        _lib.check(be.lib.ggnn_image_junctions_traj(ctypes.byref(A), _lib.current_stream()), "ggnn_image_junctions_traj")
     csr = be.build_csr_batch([(gj.flip(0).contiguous(), cap, n_total + cap)], check=False)[0]
     L = _lib.LinkTrajArgs()
     L.triples, L.rowptr, L.col, L.edge_jj, L.status = (_lib.ptr(triples), _lib.ptr(csr.rowptr), _lib.ptr(csr.col),
                                                        _lib.ptr(jj), _lib.ptr(status))
     L.n_grain, L.joint_capacity, L.E_cap, L.n_image = n_total, cap, csr.col.numel(), B
     _lib.check(be.lib.ggnn_junction_links_traj(ctypes.byref(L), _lib.current_stream()), "ggnn_junction_links_traj")
+    T = None
+    if trace:
+        T = _lib.LinkTraceArgs()
+        T.images, T.grain_off, T.triples, T.rep, T.rowptr, T.col = A.images, A.grain_off, L.triples, _lib.ptr(rep), L.rowptr, L.col
+        T.edge_jj, T.status, T.counters = L.edge_jj, L.status, _lib.ptr(status[trace_words:])
+        T.nx, T.ny, T.n_image, T.n_grain, T.joint_capacity, T.E_cap = nx, ny, B, n_total, cap, L.E_cap
+        T.max_trace, T.merge_radius, T.boundary = max_trace, R, BOUNDARIES[boundary]
+        _lib.check(be.lib.ggnn_junction_links_trace_traj(ctypes.byref(T), _lib.current_stream()), "ggnn_junction_links_trace_traj")
     return {"xy": xy, "triples": triples, "gj": gj, "jj": jj, "status": status, "counts": counts, "csr": csr,
             "n_grain": n_total, "n_image": B, "grain_off": off_host, "grain_off_dev": off_dev, "capacity": cap,
             "shape": (ny, nx), "boundary": boundary, "max_y": image_max_y(nx, ny, grid) if noflux else None,
+            "rep": rep, "trace_words": trace_words, "trace_call": T,
             "calls": (A, L, images, ws)}
 
 
-def _graphs(images, n_grains, grid, merge_radius, joint_capacity, strict, boundary="periodic"):
+def _graphs(images, n_grains, grid, merge_radius, joint_capacity, strict, boundary="periodic", links="unique", max_trace=None):
     """graphs_from_images' dict, with the capacity-sized arrays behind it as a second result."""
     _check_boundary(boundary)
+    _check_links(links, max_trace, 1, 1)
     images = _stack(images)
     if n_grains is None:
         n_grains = images.amax(dim=(1, 2)).tolist()   # (a read-back of its own: pass n_grains to avoid it)
-    v = _vectorize_union(images, n_grains, grid, merge_radius, joint_capacity, boundary)
+    v = _vectorize_union(images, n_grains, grid, merge_radius, joint_capacity, boundary, links=links, max_trace=max_trace)
     return _graphs_of(v, v["status"].tolist(), strict)   # the one read-back
 
 
@@ -310,6 +378,10 @@ def _graphs_of(v, words, strict):
     boundary = v["boundary"]
     B, W, cap = v["n_image"], len(STATUS_WORDS), v["capacity"]
     status = [dict(zip(STATUS_WORDS, words[b * W:(b + 1) * W])) for b in range(B)]
+    if v.get("trace_words") is not None:   # links="trace": the three counters of every image
+        t0, C = v["trace_words"], len(TRACE_COUNTERS)
+        for b in range(B):
+            status[b].update(zip(TRACE_COUNTERS, words[t0 + C * b:t0 + C * (b + 1)]))
     joint_off = [min(o, cap) for o in words[B * W:B * W + B + 1]]
     corners = None
     if boundary == "noflux":
@@ -332,7 +404,7 @@ def _graphs_of(v, words, strict):
 
 
 def graphs_from_images(images, n_grains=None, grid="cells", merge_radius=2, joint_capacity=None, strict=True,
-                       boundary="periodic"):
+                       boundary="periodic", links="unique", max_trace=None):
     """The junction graphs of a stack of grain-ID images as ONE disjoint union: `graph_from_image`'s rule per image, in a
     number of launches that does not depend on the number of images, with one read-back.
 
@@ -349,8 +421,12 @@ def graphs_from_images(images, n_grains=None, grid="cells", merge_radius=2, join
     `union_member(result, t)` is image t's own graph.
 
     strict: raise ValueError naming every invalid image and its counters (status_is_valid per image); strict=False returns
-    what was found, with -1 as the destination of a joint->joint column whose pair has no partner or more than one."""
-    return _graphs(images, n_grains, grid, merge_radius, joint_capacity, strict, boundary)[0]
+    what was found, with -1 as the destination of a joint->joint column whose pair has no partner or more than one.
+
+    links="trace", max_trace: as in `graph_from_image`, per image: every status dict gains n_traced, n_trace_failed and
+    n_trace_overflow, and its n_open_pairs is what is still open after tracing.  One more launch and one memset, whatever the
+    number of images or of open pairs; still one read-back."""
+    return _graphs(images, n_grains, grid, merge_radius, joint_capacity, strict, boundary, links, max_trace)[0]
 
 
 def union_member(result, t):
@@ -408,7 +484,7 @@ def samples_from_images(images, theta_x, theta_z, G, R, span=None, patch_pixels=
     kw.pop("strict", None)
     boundary = kw.pop("boundary", "periodic")
     res, v = _graphs(images, n_grains, kw.pop("grid", "cells"), kw.pop("merge_radius", 2), kw.pop("joint_capacity", None),
-                     True, boundary)
+                     True, boundary, kw.pop("links", "unique"), kw.pop("max_trace", None))
     if kw:
         raise TypeError(f"samples_from_images: unknown keywords {sorted(kw)}")
     x, ei, ea = _union_state(res, v, tx, tz, Gs, Rs, span, patch_pixels)
@@ -453,17 +529,20 @@ def _union_state(res, v, tx, tz, Gs, Rs, span, patch_pixels):
 PAIR_COUNTERS = ("n_matched", "n_ambiguous", "n_label0", "n_label1", "n_unlabelled", "n_eliminated")
 
 
-def _track(frames, n_grain, grid, merge_radius, joint_capacity, boundary, extra_volume=None, patch_pixels=None, targets=True):
+def _track(frames, n_grain, grid, merge_radius, joint_capacity, boundary, extra_volume=None, patch_pixels=None, targets=True,
+           links="unique", max_trace=None):
     """Every launch of a tracked sequence, no read-back: `_vectorize_union`'s dict with the frames as its images, plus
     next_joint / prev_joint and, with `targets`, the capacity-sized target arrays.  The counters of ggnn_track_junctions
     [T, 2] and of ggnn_track_targets [T, 4] lie behind the union's status words, at v["counter_words"]."""
     be = default_backend()
+    _check_links(links, max_trace, 1, 1)
     frames = _stack(frames)
     T, ny, nx = frames.shape
     n_grain = int(n_grain)
     if T < 2:
         raise _lib.GGNNError("a sequence needs at least two frames")
-    v = _vectorize_union(frames, [n_grain] * T, grid, merge_radius, joint_capacity, boundary, extra_words=6 * T)
+    v = _vectorize_union(frames, [n_grain] * T, grid, merge_radius, joint_capacity, boundary, extra_words=6 * T, links=links,
+                         max_trace=max_trace)
     dev, cap, n_total, csr, status = frames.device, v["capacity"], v["n_grain"], v["csr"], v["status"]
     v["counter_words"] = status.numel() - 6 * T
     counters = status[v["counter_words"]:]
@@ -501,7 +580,8 @@ def _track(frames, n_grain, grid, merge_radius, joint_capacity, boundary, extra_
     return v
 
 
-def track_frames(frames, n_grain, grid="cells", merge_radius=2, joint_capacity=None, boundary="periodic"):
+def track_frames(frames, n_grain, grid="cells", merge_radius=2, joint_capacity=None, boundary="periodic", links="unique",
+                 max_trace=None):
     """The frame-to-frame correspondence of a recorded sequence of grain-ID images (ggnn_track_junctions; tests/trackcheck.py
     restates the rule): -> (`graphs_from_images(frames, [n_grain] * T, strict=False)`'s dict, next_joint, prev_joint).
 
@@ -509,15 +589,20 @@ def track_frames(frames, n_grain, grid="cells", merge_radius=2, joint_capacity=N
     across the frames (pixel p = grain p - 1 in every frame; an eliminated grain no longer occurs).  next_joint int64
     [n_joint]: the union index of the junction of the following frame that carries the same grain triple -- when that triple
     occurs exactly once in both frames, and both frames are valid structures (status_is_valid, judged on the device) --, or
-    -1; prev_joint: the same towards the preceding frame, the inverse map.  One read-back, of the status."""
-    v = _track(frames, n_grain, grid, merge_radius, joint_capacity, boundary, targets=False)
+    -1; prev_joint: the same towards the preceding frame, the inverse map.  One read-back, of the status.
+
+    links="trace", max_trace: as in `graphs_from_images`; the frames are traced before they are judged, so a frame with a lens
+    or a wall-to-wall band is valid and its pairs are tracked.  The tracker itself is the same: the two junctions of a lens
+    share a triple, so they are counted in n_ambiguous and stay unmatched (mask 0), and the links around them are labelled by
+    the rule above."""
+    v = _track(frames, n_grain, grid, merge_radius, joint_capacity, boundary, targets=False, links=links, max_trace=max_trace)
     res, _ = _graphs_of(v, v["status"].tolist(), False)   # the one read-back
     n = res["traj_offsets"]["joint"][-1]
     return res, v["next_joint"][:n].contiguous(), v["prev_joint"][:n].contiguous()
 
 
 def frames_to_samples(frames, theta_x, theta_z, G, R, span=None, patch_pixels=None, extra_volume=None, z=None, grid="cells",
-                      merge_radius=2, joint_capacity=None, boundary="periodic"):
+                      merge_radius=2, joint_capacity=None, boundary="periodic", links="unique", max_trace=None):
     """A training set from a recorded sequence of grain-ID images -- a phase-field run, a serial-section series, the
     `grain_images()` of a rollout --: -> (samples, report), one sample per pair of consecutive VALID frames (t, t + 1), each the
     (x, edge_index, edge_attr, y, mask) of device tensors with local indices that `training.DeviceDataset` takes.  What the
@@ -542,13 +627,20 @@ def frames_to_samples(frames, theta_x, theta_z, G, R, span=None, patch_pixels=No
     report = {"status": per frame, "pairs": [(t, t + 1)] emitted, "skipped": [(t, t + 1, reason)], "counts": per emitted pair
     a dict of n_matched, n_ambiguous, n_label0, n_label1, n_unlabelled, n_eliminated}.  Everything is found on the device
     (ggnn_track_junctions, ggnn_track_targets) in a number of launches that does not depend on T, with ONE read-back: the
-    union's status words and the counters behind them.  Cutting the union into samples is a slice per pair."""
+    union's status words and the counters behind them.  Cutting the union into samples is a slice per pair.
+
+    links="trace", max_trace: as in `graphs_from_images`: the frames are traced on the device before the tracker judges them, so
+    the frame in which a grain is a lens on a boundary, one frame before it vanishes, is valid and keeps its two pairs -- the
+    ones that carry the classifier's positive labels; report["status"] carries n_traced, n_trace_failed and n_trace_overflow
+    per frame.  The tracker itself is the same: the two junctions of a lens share a triple, so they are counted in n_ambiguous
+    and stay unmatched (mask 0), and the links around them are labelled by the rule above."""
     from .synthetic import span_for
     tx, tz = np.asarray(theta_x, np.float64).ravel(), np.asarray(theta_z, np.float64).ravel()
     n_grain = len(tx)
     if n_grain < 1 or len(tz) != n_grain:
         raise _lib.GGNNError("theta_x and theta_z must hold one angle per grain")
     _check_boundary(boundary)
+    _check_links(links, max_trace, 1, 1)
     frames = _stack(frames)
     T = frames.size(0)
     try:
@@ -562,7 +654,8 @@ def frames_to_samples(frames, theta_x, theta_z, G, R, span=None, patch_pixels=No
         if len(spans) != 1:
             raise _lib.GGNNError(f"the frames' (G, R) give the frame spans {spans}: a sequence has one, pass span=")
         span = spans[0]
-    v = _track(frames, n_grain, grid, merge_radius, joint_capacity, boundary, extra_volume, patch_pixels)
+    v = _track(frames, n_grain, grid, merge_radius, joint_capacity, boundary, extra_volume, patch_pixels, links=links,
+               max_trace=max_trace)
     words = v["status"].tolist()                      # the one read-back
     res, _ = _graphs_of(v, words, False)
     x, ei, ea = _union_state(res, v, [tx] * T, [tz] * T, Gs, Rs, span, patch_pixels)

@@ -1097,6 +1097,66 @@ typedef struct ggnn_link_traj_args {
   int64_t n_grain, joint_capacity, E_cap, n_image;
 } ggnn_link_traj_args;
 int ggnn_junction_links_traj(const ggnn_link_traj_args* args, ggnn_stream_t stream);
+/* Linking by TRACING BOUNDARIES: a second linking rule for the columns the rule above leaves open because MORE than one other
+ * junction holds the pair -- two grains that share two separate stretches of boundary: a lens on a boundary one frame before
+ * it vanishes, a band that reaches from wall to wall.  Such a structure is legal (three-fold junctions, Euler's formula holds);
+ * the boundary in the image says which two junctions each stretch joins.  Per image of a union, both boundaries, exact in
+ * integers; tests/tracecheck.py restates the rule.  A structure without open pairs is left as it is, bit for bit.
+ * ggnn_image_junction_windows_traj = ggnn_image_junctions_traj -- the same checks, launches and results -- with one more
+ * output: rep int32 [joint_capacity], rep[j] = the raster index of junction j's representative window within its image (y nx +
+ * x, no-flux (y + 1)(nx + 1) + (x + 1)); nothing at or beyond joint_capacity or n_joint.  GGNN_EINVAL also for rep NULL.
+ * ggnn_junction_links_trace_traj, after ggnn_junction_links_traj = a memset of its counters + one launch, a thread a
+ * joint->joint column of a junction j < min(n_joint, joint_capacity); a column that is not -1 returns at once.
+ *   vertex    : a window (y, x) of the junction rule, with its range, its periodic wrap and its outside-reads-as-id-1 convention
+ *   cracks    : of a vertex: UP between TL and TR to (y - 1, x), DOWN between BL and BR to (y + 1, x), LEFT between TL and BL to
+ *               (y, x - 1), RIGHT between TR and BR to (y, x + 1); an a | b crack has the ids of grains a and b as its two pixels
+ *   owner     : a window W that carries key k is owned by the junction of smallest index (below the bound above, in W's image)
+ *               that has triple k and whose representative lies at an offset within merge_radius of W -- wrapped for periodic,
+ *               plain for no-flux --, found by walking the joint->grain row of the key's last grain and comparing triple and
+ *               rep (no sort, no hash).  A carrier that no junction owns belongs to nobody (carriers that chain-merge).
+ *   owned by j: the windows at offsets within merge_radius of rep[j] that carry j's triple and whose owner for it is j
+ *   exits     : for j and its pair (a, b): the a | b cracks from a vertex owned by j to a vertex not owned by j
+ *   diagonals : for j and (a, b): the quadruple windows owned by j whose TL and BR are a and b
+ *   walk      : j has no diagonal and exactly one exit: follow it.  At every vertex reached: if the window carries a key that
+ *               holds both a and b, stop -- its owner is o.  Otherwise the vertex must have exactly two a | b cracks, the one
+ *               arrived by and one more: leave by the other.  The walk FAILS at a vertex with another number of them (four is
+ *               the two-id checkerboard window [a b; b a]) and at a carrier nobody owns; it OVERFLOWS when more than max_trace
+ *               vertices would be reached.
+ *   accept    : partner(j, pair) = o only if o too has no diagonal and exactly one exit for (a, b) (worked out by the same
+ *               thread): that exit is the crack arrived by, so the thread of o's column reaches j by the reversed walk of the
+ *               same length -- the result is symmetric, and a thread writes its own column only.
+ *   quadruple : j has exactly one diagonal W for (a, b): o = the owner of W's other key, and partner(j, pair) = o when o too has
+ *               exactly one diagonal for (a, b) and it is W.  There is no crack to follow.  Several diagonals fail.
+ *   counters  : int64 [n_image, GGNN_TRACE_COUNTERS], zeroed by the call: n_traced, n_trace_failed (no exit or several, a failed
+ *               walk, a refused partner), n_trace_overflow -- directed columns, counted at the image of the junction; every open
+ *               column is counted in exactly one.  Status word 4 (n_open_pairs) of the image loses one per traced column and so
+ *               becomes what is still open: the validity tests read it unchanged.  Integer sums; no result is ordered by one,
+ *               so a replay gives the same bits.
+ * Pixel reads wrap or clip inside their image with 64-bit indices; nothing is read or written at or beyond joint_capacity; rows
+ * and columns of the table are clamped as in ggnn_junction_links, grain offsets as above, a rep outside its image's windows
+ * owns nothing; (2 merge_radius + 1)^2, E_cap and max_trace bound every loop.  GGNN_EINVAL without a launch: args or a pointer
+ * NULL, a 64-bit array not 8-byte aligned or a 32-bit one not 4-byte aligned, n_grain, joint_capacity, E_cap, n_image as in
+ * ggnn_junction_links_traj, nx, ny, merge_radius, boundary as in ggnn_image_junctions_traj, max_trace < 1.
+ * Not covered: matching the two junctions of a lens between frames (they share a triple: ggnn_track_junctions counts them as
+ * ambiguous and leaves them unmatched), structures that fail Euler's formula (a sub-pixel edge that loses a junction). */
+#define GGNN_TRACE_COUNTERS 3
+int ggnn_image_junction_windows_traj(const ggnn_junction_traj_args* args, int32_t* rep, ggnn_stream_t stream);
+typedef struct ggnn_link_trace_args {
+  const int32_t* images;         /* [n_image, ny, nx], device: ggnn_image_junction_windows_traj's */
+  const int64_t* grain_off;      /* [n_image + 1], device */
+  const int32_t* triples;        /* [joint_capacity, 3] */
+  const int32_t* rep;            /* [joint_capacity]: ggnn_image_junction_windows_traj's */
+  const int32_t* rowptr;         /* [>= n_grain + 1]: the union's joint->grain table's row pointers */
+  const int32_t* col;            /* [E_cap]: its columns */
+  int64_t* edge_jj;              /* [2, 3 joint_capacity]: ggnn_junction_links_traj's; the open columns of row 1 are written */
+  int64_t* status;               /* the status rows, then joint_off: joint_off is read, word 4 of the rows updated */
+  int64_t* counters;             /* [n_image, GGNN_TRACE_COUNTERS] out */
+  int64_t nx, ny, n_image, n_grain, joint_capacity, E_cap;
+  int64_t max_trace;             /* the vertices a walk may reach, at least 1 (the Python layer's default: 4 (nx + ny)) */
+  int32_t merge_radius;
+  int32_t boundary;              /* GGNN_BC_PERIODIC / GGNN_BC_NOFLUX */
+} ggnn_link_trace_args;
+int ggnn_junction_links_trace_traj(const ggnn_link_trace_args* args, ggnn_stream_t stream);
 /* ------------------------------------------------------------------------------------
  * Training targets from a recorded SEQUENCE of grain-ID images: the n_frame images of one union above are the frames of a
  * sequence in which a grain keeps its id (local grain g of every frame is the same grain; an eliminated grain no longer

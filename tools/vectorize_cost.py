@@ -32,7 +32,13 @@ every kernel of the two union calls (the count, scan and emit passes by name).
   calls      ggnn_track_junctions + ggnn_track_targets on prepared arguments
 host and samples by the host clock around work that ends in a synchronise, the calls by events; the same protocol as --union.
 The device activities of one frames_to_samples and of the two calls are counted at T = 8 and at T: they must not differ.
-    python tools/vectorize_cost.py --track 64 [--rounds 20]"""
+    python tools/vectorize_cost.py --track 64 [--rounds 20]
+--trace adds linking by tracing boundaries (links="trace", ggnn_junction_links_trace_traj).  On the 4 096 x 4 096 image, read as a
+one-image union: ggnn_junction_links_traj and the trace call behind it on prepared arguments, by events -- the image is valid,
+so every thread of the trace call reads its column and returns.  With --track T: frames_to_samples with links="unique" and with
+links="trace" alternating, the pairs each emits, and what the frames that are still invalid fail by.
+    python tools/vectorize_cost.py --trace [--rounds 50]
+    python tools/vectorize_cost.py --track 64 --trace [--rounds 20]"""
 import argparse
 import ctypes
 import os
@@ -49,6 +55,7 @@ def main():
     ap.add_argument("--union", type=int, default=0, metavar="B")
     ap.add_argument("--track", type=int, default=0, metavar="T")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--trace", action="store_true", help="the links=\"trace\" arms")
     a = ap.parse_args()
     sys.path[:0] = [os.path.dirname(HERE)]
     if a.size is None:
@@ -97,7 +104,39 @@ def main():
         for name, t in times.items():
             t = np.array(t)
             print(f"{name:9s} us/call by events: median {np.median(t):8.1f}  min {t.min():8.1f}  max {t.max():8.1f}", flush=True)
+        if a.trace:
+            trace_call_cost(a, image, n_grain)
         print(f"# torch {torch.__version__}, {torch.cuda.get_device_name()}", flush=True)
+
+
+def trace_call_cost(a, image, n_grain):
+    """ggnn_junction_links_traj and ggnn_junction_links_trace_traj on the image as a one-image union, by events."""
+    import numpy as np
+    import torch
+    from graingraphnn_amd import _lib
+    from graingraphnn_amd import vectorize as vz
+    lib = _lib.load()
+    v = vz._vectorize_union(vz._stack(image[None]), [n_grain], "cells", 2, None, a.boundary, links="trace")
+    res, _ = vz._graphs_of(v, v["status"].tolist(), False)
+    print(f"# one-image union, links=\"trace\": status {res['status'][0]}, valid {vz.status_is_valid(res['status'][0], a.boundary)}",
+          flush=True)
+    L, T = v["calls"][1], v["trace_call"]
+    arms = {"links_traj": lambda: _lib.check(lib.ggnn_junction_links_traj(ctypes.byref(L), _lib.current_stream()), "links_traj"),
+            "trace_traj": lambda: _lib.check(lib.ggnn_junction_links_trace_traj(ctypes.byref(T), _lib.current_stream()), "trace_traj")}
+    times = {k: [] for k in arms}
+    for rnd in range(a.rounds + 3):
+        for name, call in arms.items():
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            call()
+            t1.record()
+            t1.synchronize()
+            if rnd >= 3:
+                times[name].append(t0.elapsed_time(t1) * 1e3)
+    for name, t in times.items():
+        t = np.array(t)
+        print(f"{name:10s} us/call by events: median {np.median(t):8.1f}  min {t.min():8.1f}  max {t.max():8.1f}", flush=True)
+    print(f"# trace_traj / links_traj = {np.median(times['trace_traj']) / np.median(times['links_traj']):.2f}", flush=True)
 
 
 def lattice_images(B, size, seed, device, cells=11):
@@ -280,8 +319,8 @@ def track_cost(a):
                  "joint_off": res["traj_offsets"]["joint"]}
             return tc.track(u, n_grain, "periodic", shape=(size, size))
 
-        def samples(frames=frames):
-            out = vz.frames_to_samples(frames, theta_x, theta_z, G, R, span=span)
+        def samples(frames=frames, links="unique"):
+            out = vz.frames_to_samples(frames, theta_x, theta_z, G, R, span=span, links=links)
             torch.cuda.synchronize()
             return out
 
@@ -318,6 +357,16 @@ def track_cost(a):
             return (time.perf_counter() - t0) * 1e6
 
         arms = {"host": lambda: by_clock(host), "samples": lambda: by_clock(samples), "calls": lambda: by_events(calls)}
+        if a.trace:
+            _, traced = samples(links="trace")
+            still = [s for s in traced["status"] if not vz.status_is_valid(s)]
+            euler = sum(1 for s in still if s["n_joint"] != 2 * s["n_present_grains"])
+            print(f"# links=\"trace\": {len(traced['pairs'])} pairs emitted, {len(traced['skipped'])} skipped (links=\"unique\": "
+                  f"{len(report['pairs'])} and {len(report['skipped'])}); {sum(s['n_traced'] for s in traced['status'])} columns traced "
+                  f"in {sum(1 for s in traced['status'] if s['n_traced'])} frames; {len(still)} frames still invalid, {euler} of them "
+                  f"by Euler's formula, with {sum(s['n_trace_failed'] for s in still)} failed and "
+                  f"{sum(s['n_trace_overflow'] for s in still)} overflowed columns", flush=True)
+            arms["samples, trace"] = lambda: by_clock(lambda: samples(links="trace"))
         times = {k: [] for k in arms}
         for rnd in range(a.rounds + 3):
             for name, arm in arms.items():
