@@ -30,6 +30,7 @@ GGNN_FLAG_POLYGON_OVERFLOW = 4
 GGNN_INTERP_MAX_JOBS = 256
 GGNN_JUNCTION_SEGMENT, GGNN_JUNCTION_STATUS_WORDS, GGNN_JUNCTION_MAX_BLOCKS = 256, 7, 1 << 22
 GGNN_TRACE_COUNTERS = 3
+GGNN_LABEL_TILE_X, GGNN_LABEL_TILE_Y, GGNN_LABEL_STATUS_WORDS, GGNN_LABEL_MAX_SWEEPS = 64, 16, 9, 1024
 GGNN_ADAM_CHUNK, GGNN_ADAM_MAX_TENSORS, GGNN_ADAM_MAX_GROUPS = 4096, 384, 8
 GGNN_ROWGEMM_MAX_PACK = 8
 GGNN_MSE_MAX_TERMS, GGNN_MSE_BLOCKS = 4, 64
@@ -64,6 +65,7 @@ EXPORTED_SYMBOLS = (
     "ggnn_polygons_rasterize", "ggnn_image_compare", "ggnn_image_junctions", "ggnn_junction_links",
     "ggnn_image_junctions_traj", "ggnn_junction_links_traj", "ggnn_track_junctions", "ggnn_track_targets",
     "ggnn_image_junction_windows_traj", "ggnn_junction_links_trace_traj",
+    "ggnn_label_workspace_bytes", "ggnn_label_grains",
     "ggnn_metric_record",
     "ggnn_masked_mse_rows", "ggnn_collate_batch", "ggnn_reverse_slots",
 )
@@ -499,6 +501,16 @@ class TrackTargetsArgs(Structure):
     ]
 
 
+class LabelArgs(Structure):
+    """Mirror of `ggnn_label_args`."""
+    _fields_ = [
+        ("ids", c_void_p), ("angles", c_void_p), ("valid", c_void_p), ("image", c_void_p), ("mean_angles", c_void_p),
+        ("status", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_size_t),
+        ("nx", c_int64), ("ny", c_int64), ("grain_capacity", c_int64), ("min_pixels", c_int64),
+        ("tol", c_float), ("K", c_int32), ("max_sweeps", c_int32), ("boundary", c_int32),
+    ]
+
+
 class MetricArgs(Structure):
     """Mirror of `ggnn_metric_args`."""
     _fields_ = [
@@ -671,6 +683,10 @@ def _declare(lib):
     lib.ggnn_track_junctions.argtypes = [POINTER(TrackArgs), c_void_p]
     lib.ggnn_track_targets.restype = c_int
     lib.ggnn_track_targets.argtypes = [POINTER(TrackTargetsArgs), c_void_p]
+    lib.ggnn_label_workspace_bytes.restype = c_size_t
+    lib.ggnn_label_workspace_bytes.argtypes = [c_int64, c_int64, c_int32]
+    lib.ggnn_label_grains.restype = c_int
+    lib.ggnn_label_grains.argtypes = [POINTER(LabelArgs), c_void_p]
     lib.ggnn_process_schedule.restype = c_int
     lib.ggnn_process_schedule.argtypes = [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p]

@@ -35,9 +35,19 @@ tests/tracecheck.py): a pair of grains that more than one other junct
 stretches of boundary: a lens on a boundary, a band from wall to wall -- is linked by following the boundary through the image,
 on the device and exact in integers; the default `links="unique"` is the rule above, launch for launch.
 
+A MEASURED map is not a grain-ID image: it carries orientations per pixel, non-indexed points and speckle.  `label_grains`
+(ggnn_label_grains; tests/labelcheck.py) is the stage before all of the above: connected components of an
+orientation map (two neighbours are linked when every angle differs by at most `tol`) or of a noisy id image, periodic or with
+walls, specks and non-indexed pixels dissolved into their neighbours by majority, grains numbered in raster order, and the
+per-grain mean angles as exact fixed-point sums -- on the device, exact in integers.  `sample_from_orientations` chains it
+with `sample_from_image`.  One wrong pixel on a boundary no longer drops a frame: it is repaired before the vectoriser,
+whose own contract -- an invalid structure is reported, not repaired -- stands.
+
 Not covered: stacks of mixed image shapes, resolving a quadruple from a history (the diagonal is fixed, and counted in the
 status), the reference's `edge` length target (its edge_len head is disabled in every shipped configuration) and its
-`elim_list` scaling of shrinking grains (commented out in the reference)."""
+`elim_list` scaling of shrinking grains (commented out in the reference); for the labelling: stacks of maps in one launch, ids
+that are consistent across the frames of a sequence, symmetry-reduced misorientation, 8-connectivity, Euler-angle triples
+with crystal symmetry."""
 import ctypes
 import math
 
@@ -690,3 +700,115 @@ def frames_to_samples(frames, theta_x, theta_z, G, R, span=None, patch_pixels=No
         a, b = words[c0 + 2 * t:c0 + 2 * t + 2], words[c0 + 2 * T + 4 * t:c0 + 2 * T + 4 * t + 4]
         report["counts"].append(dict(zip(PAIR_COUNTERS, a + b)))
     return samples, report
+
+
+# ---- a measured map into a grain-ID image --------------------------------------------------------------------------------
+
+LABEL_STATUS_WORDS = ("n_components", "n_specks", "n_speck_pixels", "n_invalid_in", "n_grains", "n_sweeps", "n_unfilled",
+                      "overflow", "n_bound_hits")
+
+
+def _label(ids, angles, tol, valid, min_pixels, max_sweeps, boundary, grain_capacity):
+    """Every launch of `label_grains`, no read-back: -> dict of the image, the capacity-sized means (None with ids), the
+    status words on the device, and the call's arguments with what they point to (tools/vectorize_cost.py)."""
+    be = default_backend()
+    _check_boundary(boundary)
+    if (ids is None) == (angles is None):
+        raise _lib.GGNNError("exactly one of ids and angles must be given")
+    src = ids if angles is None else angles
+    if not isinstance(src, torch.Tensor) or not src.is_cuda:
+        raise _lib.GGNNError("ids / angles must be device tensors")
+    if angles is None:
+        if ids.dim() != 2 or ids.dtype not in (torch.int16, torch.int32, torch.int64, torch.uint8, torch.int8):
+            raise _lib.GGNNError("ids must be an integer [ny, nx] device tensor")
+        ids = ids.to(torch.int32).contiguous()
+        K, (ny, nx) = 0, ids.shape
+    else:
+        if tol is None:
+            raise _lib.GGNNError("angles need tol, the largest difference per channel that still links two neighbours")
+        if angles.dim() != 3 or not 1 <= angles.size(0) <= 4 or angles.dtype != torch.float32:
+            raise _lib.GGNNError("angles must be a float32 [K, ny, nx] device tensor with 1 <= K <= 4")
+        angles = angles.contiguous()
+        K, ny, nx = angles.shape
+    if nx < 3 or ny < 3:
+        raise _lib.GGNNError("the image must have at least 3 x 3 pixels")
+    dev = src.device
+    if valid is not None:
+        if not isinstance(valid, torch.Tensor) or not valid.is_cuda or valid.shape != (ny, nx):
+            raise _lib.GGNNError("valid must be a [ny, nx] device mask")
+        valid = (valid != 0).to(torch.uint8).contiguous()
+    min_pixels, max_sweeps = int(min_pixels), int(max_sweeps)
+    if min_pixels < 1:
+        raise _lib.GGNNError("min_pixels must be at least 1")
+    if not 0 <= max_sweeps <= _lib.GGNN_LABEL_MAX_SWEEPS:
+        raise _lib.GGNNError(f"max_sweeps must lie in [0, {_lib.GGNN_LABEL_MAX_SWEEPS}]")
+    cap = ny * nx // min_pixels + 2 if grain_capacity is None else int(grain_capacity)
+    if cap < 1:
+        raise _lib.GGNNError("grain_capacity must be at least 1")
+    image = torch.empty(ny, nx, dtype=torch.int32, device=dev)
+    means = torch.zeros(K, cap, dtype=torch.float32, device=dev) if K else None
+    status = torch.empty(_lib.GGNN_LABEL_STATUS_WORDS, dtype=torch.int64, device=dev)   # (zeroed by the call)
+    ws = torch.empty(be.lib.ggnn_label_workspace_bytes(nx, ny, K), dtype=torch.uint8, device=dev)
+    A = _lib.LabelArgs()
+    A.ids, A.angles, A.valid, A.image, A.mean_angles = _lib.ptr(ids), _lib.ptr(angles), _lib.ptr(valid), _lib.ptr(image), _lib.ptr(means)
+    A.status, A.workspace, A.workspace_bytes = _lib.ptr(status), _lib.ptr(ws), ws.numel()
+    A.nx, A.ny, A.grain_capacity, A.min_pixels = nx, ny, cap, min_pixels
+    A.tol, A.K, A.max_sweeps, A.boundary = (0.0 if tol is None else float(np.float32(tol))), K, max_sweeps, BOUNDARIES[boundary]
+    _lib.check(be.lib.ggnn_label_grains(ctypes.byref(A), _lib.current_stream()), "ggnn_label_grains")
+    return {"image": image, "means": means, "status": status, "capacity": cap, "boundary": boundary,
+            "calls": (A, ids, angles, valid, ws)}
+
+
+def label_grains(ids=None, angles=None, tol=None, valid=None, min_pixels=1, max_sweeps=64, boundary="periodic",
+                 grain_capacity=None):
+    """Segment a measured map into a grain-ID image on the device (ggnn_label_grains; include/ggnn.h states the rule,
+    tests/labelcheck.py restates it): connected components of the pixel-to-pixel links, specks and non-indexed
+    pixels dissolved into their neighbours, canonical numbering, per-grain mean angles.
+
+    Exactly one of ids -- integer [ny, nx] on the device, a pixel is valid when id >= 1, two 4-neighbours are linked when their
+    ids are equal -- and angles -- float32 [K, ny, nx] on the device, 1 <= K <= 4 (K = 2: theta_x, theta_z in radians), a pixel
+    is valid when every channel is finite with |a| <= 8, two 4-neighbours are linked when |a_k - b_k| <= tol in every channel
+    (tol is required; the pixel-to-pixel misorientation criterion, not transitive).  valid: an optional [ny, nx] device mask,
+    0 = non-indexed.  min_pixels: a component with fewer pixels is a speck; specks and invalid pixels are dissolved into the
+    neighbouring grains by majority in at most max_sweeps Jacobi sweeps (1: nothing valid is cleaned up).  boundary: "periodic"
+    (neighbours wrap; ids from 1) or "noflux" (walls; ids from 2, id 1 being the boundary grain of `graph_from_image`).
+    grain_capacity: room of the per-grain rows (default ny nx // min_pixels + 2, which cannot overflow).
+
+    -> (image int32 [ny, nx], n_grain, mean_angles float32 [K, n_grain] or None with ids, status dict): grains numbered in raster
+    order of their first pixel, 0 = a pixel no sweep reached (`graph_from_image` counts it in n_invalid_pixels); the means run
+    over the pixels of the original components only.  status: n_components, n_specks, n_speck_pixels, n_invalid_in, n_grains,
+    n_sweeps, n_unfilled, overflow (more grains than grain_capacity: the image is complete, the means hold the first rows).
+    Device tensors in, device tensors out, ONE read-back (the status); 9 + 2 max_sweeps launches whatever the image holds.
+
+    Not covered: stacks of maps in one launch, ids that are consistent across the frames of a sequence (`frames_to_samples`
+    needs them), symmetry-reduced misorientation (reduce the angles to a fundamental zone first), 8-connectivity, Euler-angle
+    triples with crystal symmetry."""
+    v = _label(ids, angles, tol, valid, min_pixels, max_sweeps, boundary, grain_capacity)
+    status = dict(zip(LABEL_STATUS_WORDS, v["status"].tolist()))   # the one read-back
+    if status["n_bound_hits"]:
+        raise _lib.GGNNError(f"ggnn_label_grains: {status['n_bound_hits']} threads reached the bound of a parent walk: {status}")
+    n_grain = status["n_grains"] + (1 if boundary == "noflux" else 0)
+    means = None if v["means"] is None else v["means"][:, :min(n_grain, v["capacity"])].contiguous()
+    return v["image"], n_grain, means, status
+
+
+def sample_from_orientations(theta_x_map, theta_z_map, G, R, tol, min_pixels=1, **kw):
+    """A rollout's first state from an orientation map: `label_grains` on the two angle maps ([ny, nx] float32 on the device,
+    radians), the per-grain mean angles read back, and `sample_from_image` on the labelled image with everything it takes
+    (span, patch_pixels, grid, merge_radius, boundary, links, ...); valid, max_sweeps and grain_capacity go to `label_grains`.
+
+    -> (x_dict, edge_index_dict, edge_attr, image, status): the first three are bit for bit what
+    `sample_from_image(image, theta_x, theta_z, ...)` gives on the returned image and the labelling's mean angles (no-flux: row
+    0, the boundary grain's, is 0); status is the labelling's, with the means under "theta_x" and "theta_z" (host float32).  A
+    map whose labelled image is no valid structure raises, as `sample_from_image` does."""
+    if not isinstance(theta_x_map, torch.Tensor) or not isinstance(theta_z_map, torch.Tensor) or theta_x_map.shape != theta_z_map.shape:
+        raise _lib.GGNNError("theta_x_map and theta_z_map must be equal-shaped [ny, nx] device tensors")
+    boundary = kw.get("boundary", "periodic")
+    label_kw = {k: kw.pop(k) for k in ("valid", "max_sweeps", "grain_capacity") if k in kw}
+    angles = torch.stack([theta_x_map.to(torch.float32), theta_z_map.to(torch.float32)])
+    image, n_grain, means, status = label_grains(angles=angles, tol=tol, min_pixels=min_pixels, boundary=boundary, **label_kw)
+    if status["overflow"]:
+        raise ValueError(f"the map has more grains than grain_capacity: {status}")
+    theta = means.cpu().numpy()
+    x, ei, ea = sample_from_image(image, theta[0], theta[1], G, R, n_grain=n_grain, **kw)
+    return x, ei, ea, image, dict(status, theta_x=theta[0], theta_z=theta[1])

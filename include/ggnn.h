@@ -1236,6 +1236,78 @@ typedef struct ggnn_track_targets_args {
   int32_t reserved;
 } ggnn_track_targets_args;
 int ggnn_track_targets(const ggnn_track_targets_args* args, ggnn_stream_t stream);
+/* ------------------------------------------------------------------------------------
+ * The way in from a MEASURED map: an orientation map (an EBSD scan: angles per pixel, non-indexed points, speckle) or a noisy
+ * id image becomes the grain-ID image and the per-grain angles that the calls above take.  Setup work, on `stream`, nothing
+ * through the host, exact in integers; tests/labelcheck.py restates the rule.  One image a call.
+ *   input     : one image [ny, nx], nx, ny >= 3, `boundary` GGNN_BC_PERIODIC or GGNN_BC_NOFLUX, in one of two forms.
+ *               ids: int32; a pixel is VALID when id >= 1 and the optional byte mask `valid` is non-zero there; two
+ *               4-neighbours are LINKED when both are valid and their ids are equal.
+ *               angles: float32 [K, ny, nx], 1 <= K <= 4 (the model's case: K = 2, theta_x and theta_z in radians); a pixel
+ *               is valid when every channel is finite with |a| <= 8 and the mask allows it; two 4-neighbours are linked when
+ *               both are valid and fabsf(a_k - b_k) <= tol for every k -- one fp32 subtraction a channel, symmetric by IEEE.
+ *               Linking is not transitive in the angle: it is the usual pixel-to-pixel misorientation criterion.
+ *               Neighbours wrap under GGNN_BC_PERIODIC and do not exist beyond a wall under GGNN_BC_NOFLUX.  The raster
+ *               index of a pixel is y nx + x.
+ *   components: the classes of the valid pixels under the links.  A component's ROOT is its smallest raster index, its size
+ *               its pixel count.
+ *   cleanup   : a component of fewer than min_pixels pixels is a SPECK (min_pixels >= 1; 1: no valid pixel is cleaned up).
+ *               Speck pixels and invalid pixels are OPEN, all others CLOSED, carrying their root.  Jacobi sweeps: sweep s
+ *               reads the state after sweep s - 1; every open pixel collects the roots of the closed ones among its four
+ *               neighbour positions (left, right, up, down, by the boundary rule above); if there is any it takes the root
+ *               that occurs most often among them, a tie going to the smaller root, and is closed from the next sweep on.
+ *               The sweeps end after max_sweeps, or after one that assigned nothing.  Pixels still open are UNFILLED and are
+ *               written 0 (ggnn_image_junctions counts them in n_invalid_pixels).  Components grow and never merge, so
+ *               roots are stable.
+ *   numbering : the components closed before the first sweep are the grains, ranked by ascending root.  Periodic: pixel =
+ *               rank + 1, n_grain = their number.  No-flux: pixel = rank + 2, n_grain = their number + 1: grain 0 (id 1) is
+ *               the boundary grain and does not occur inside, as ggnn_image_junctions requires.
+ *   means     : (K > 0) per grain and channel over the pixels of the ORIGINAL component (absorbed pixels carry noise and do
+ *               not count): q = __float2ll_rn(__fmul_rn(a, 16777216.0f)), S = the int64 sum of q, n = the original size,
+ *               mean = (float)((double)S / (double)n / 16777216.0).  |a| <= 8 and fewer than 2^30 pixels: S fits 2^57, the
+ *               sum is exact and independent of the order.  mean_angles is [K, grain_capacity], row g of channel k at
+ *               k grain_capacity + g; no-flux: row 0 is 0.  Rows from n_grain on are not written.
+ *   status    : int64 [GGNN_LABEL_STATUS_WORDS], zeroed by the call: n_components (before the cleanup), n_specks,
+ *               n_speck_pixels, n_invalid_in, n_grains (the closed components: n_grain without the boundary grain),
+ *               n_sweeps (sweeps that assigned something), n_unfilled, overflow (n_grain > grain_capacity: the image is
+ *               still complete, the per-grain rows hold the first grain_capacity grains), n_bound_hits (must be 0: a
+ *               thread that followed parents beyond the bound derived from the image size counted itself and left).
+ * ggnn_label_grains = two memsets and 9 + 2 max_sweeps launches, whatever the image holds: links (a byte a pixel), tiles (a
+ * workgroup a GGNN_LABEL_TILE_X x GGNN_LABEL_TILE_Y tile: union-find on labels in LDS, tile-local roots, counts and angle sums),
+ * seams (linked pairs across tile edges and the wrap: atomicMin on the larger root's parent, retried from the new roots),
+ * flatten, classify (closed / open, the list of open pixels, the counters), per sweep decide + commit (a sweep after one that
+ * assigned nothing returns on a device word), the rank as block sums, scan of the sums and add (with the means), the image.
+ * No kernel waits on another workgroup; every loop over parents is bounded.  Nothing outside the image, the workspace, the
+ * status and grain_capacity rows of mean_angles is addressed, whatever the inputs hold.
+ * GGNN_EINVAL without a launch: args, image, status or workspace NULL, both or neither of ids / angles, nx or ny outside
+ * [3, 2^15), with angles K outside [1, 4], mean_angles NULL or tol not >= 0, with ids K != 0, min_pixels < 1, max_sweeps
+ * outside [0, GGNN_LABEL_MAX_SWEEPS], grain_capacity outside [1, INT32_MAX), an unknown boundary, status or workspace not
+ * 8-byte aligned, a 32-bit array not 4-byte aligned, a workspace below ggnn_label_workspace_bytes(nx, ny, K) (which is 0 for
+ * sizes the call refuses).
+ * Not covered: stacks of maps in one launch, ids that are consistent across the frames of a sequence, symmetry-reduced
+ * misorientation (reduce the angles to a fundamental zone first: a grain that straddles the wrap of an angle comes out as two),
+ * 8-connectivity, full Euler-angle triples with crystal symmetry. */
+#define GGNN_LABEL_TILE_X 64
+#define GGNN_LABEL_TILE_Y 16
+#define GGNN_LABEL_STATUS_WORDS 9
+#define GGNN_LABEL_MAX_SWEEPS 1024
+typedef struct ggnn_label_args {
+  const int32_t* ids;            /* [ny, nx], device, or NULL */
+  const float* angles;           /* [K, ny, nx], device, or NULL: exactly one of the two */
+  const uint8_t* valid;          /* [ny, nx] bytes, device, or NULL: every pixel allowed */
+  int32_t* image;                /* [ny, nx] out */
+  float* mean_angles;            /* [K, grain_capacity] out (NULL with ids) */
+  int64_t* status;               /* [GGNN_LABEL_STATUS_WORDS] out */
+  void* workspace;               /* ggnn_label_workspace_bytes(nx, ny, K) of device scratch */
+  size_t workspace_bytes;
+  int64_t nx, ny, grain_capacity, min_pixels;
+  float tol;
+  int32_t K;                     /* channels of angles; 0 with ids */
+  int32_t max_sweeps;
+  int32_t boundary;              /* GGNN_BC_PERIODIC / GGNN_BC_NOFLUX */
+} ggnn_label_args;
+size_t ggnn_label_workspace_bytes(int64_t nx, int64_t ny, int32_t K);
+int ggnn_label_grains(const ggnn_label_args* args, ggnn_stream_t stream);
 /* The host-side topology update those counts trigger: one call of the reference's `Cmodel.update`
  * (models.py:612-842 with delete_grain_index :861-893, switching_edge_index :896-1051, point_in_triangle :1055-1070,
  * periodic_move :1103-1106), nucleation off.  HOST memory throughout, no stream: grains of `grain_event` (those below the

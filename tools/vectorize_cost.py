@@ -38,7 +38,20 @@ one-image union: ggnn_junction_links_traj and the trace call behind it on prepar
 so every thread of the trace call reads its column and returns.  With --track T: frames_to_samples with links="unique" and with
 links="trace" alternating, the pairs each emits, and what the frames that are still invalid fail by.
     python tools/vectorize_cost.py --trace [--rounds 50]
-    python tools/vectorize_cost.py --track 64 --trace [--rounds 20]"""
+    python tools/vectorize_cost.py --track 64 --trace [--rounds 20]
+--label times the stage before all of these, segmenting a measured map (vectorize.label_grains, ggnn_label_grains), in angles mode
+with K = 2 on two maps: frame 0 of tests/golden/pf_frames_cfg1.npz (501 x 501, 118 grains, as it is) and a --size x --size periodic
+Voronoi map of size^2 / 8192 cells with 1 % of the pixels non-indexed or wrong (half each) and min_pixels = 8; and prints
+  call       ggnn_label_grains on prepared arguments, by events
+  label      one label_grains with its read-back, by the host clock
+  host       the only route before it, by the host clock: the map read back, the links in numpy, scipy's connected components of
+             the link graph (which takes the wrap and the tolerance as they are; scipy.ndimage.label takes one id a call, and the
+             wrong pixels spread every id's bounding box over the whole map), the restatement's numbering and cleanup sweeps
+             (tests/labelcheck.py), the image uploaded.  --host-rounds bounds its rounds (it takes seconds on the large map).
+The arms alternate within a round; median of the rounds after three warm-up rounds.  Then the device activities of one call
+for both maps (they must not differ: the launches do not depend on the content), the traffic floor of every launch (the bytes
+it must move / 8 TB/s), and, where the tracer is there, the device time of every kernel.
+    python tools/vectorize_cost.py --label [--rounds 20] [--size 4096] [--host-rounds 2] [--no-host]"""
 import argparse
 import ctypes
 import os
@@ -56,10 +69,15 @@ def main():
     ap.add_argument("--track", type=int, default=0, metavar="T")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--trace", action="store_true", help="the links=\"trace\" arms")
+    ap.add_argument("--label", action="store_true", help="the cost of label_grains")
+    ap.add_argument("--host-rounds", type=int, default=2, help="--label: timed rounds of the host route on the large map")
+    ap.add_argument("--no-host", action="store_true", help="--label: leave the host route out (a profiler's run)")
     a = ap.parse_args()
     sys.path[:0] = [os.path.dirname(HERE)]
     if a.size is None:
         a.size = 128 if a.union or a.track else 4096
+    if a.label:
+        return label_cost(a)
     if a.track:
         return track_cost(a)
     if a.union:
@@ -396,6 +414,148 @@ def track_cost(a):
         except Exception as exc:   # (a build of torch without the tracer)
             print(f"# launches not counted: {type(exc).__name__}: {exc}", flush=True)
         print(f"# torch {torch.__version__}, {torch.cuda.get_device_name()}", flush=True)
+
+
+def label_floor(nx, ny, K, status, max_sweeps):
+    """[(launch, bytes it must move)] of one ggnn_label_grains: every array a pass reads or writes once, gathers of neighbours
+    and roots counted as hits; the sweeps move the open pixels' words only."""
+    N, n_open = nx * ny, status["n_invalid_in"] + status["n_speck_pixels"]
+    seams = ny * -(-nx // 64) + nx * -(-ny // 16)
+    out = [("links", N * (4 * K + 1)), ("tiles", N * (1 + 4 * K + 4)), ("seams", seams * 9), ("flatten", N * (1 + 4 + 4)),
+           ("classify", N * (1 + 4 + 4) + 4 * n_open)]
+    out += [(f"sweep {s}", n_open * (4 + 4 + 4) + n_open * (4 + 4 + 4)) for s in range(min(status["n_sweeps"] + 1, max_sweeps))]
+    out += [("rank sums", 4 * N), ("rank scan", 8 * -(-N // 1024)), ("rank add", 4 * N), ("image", N * (4 + 4))]
+    return out
+
+
+def label_cost(a):
+    import time
+    import numpy as np
+    import torch
+    from scipy.sparse import coo_matrix
+    from scipy.sparse.csgraph import connected_components
+    sys.path[:0] = [os.path.join(os.path.dirname(HERE), "tests")]
+    import labelcheck as lc
+    from graingraphnn_amd import _lib
+    from graingraphnn_amd import vectorize as vz
+    dev = torch.device("cuda", 0)
+    lib = _lib.load()
+    d = np.load(os.path.join(os.path.dirname(HERE), "tests", "golden", "pf_frames_cfg1.npz"))
+    frame = d["frames"][0].astype(np.int64)
+    theta = np.stack([d["theta_x"], d["theta_z"]]).astype(np.float32)
+    maps = {"golden 501 x 501": (np.ascontiguousarray(theta[:, frame - 1]), 1e-3, 1)}
+    rs = np.random.RandomState(a.seed)
+    n = max(4, a.size * a.size // 8192)
+    seeds = torch.from_numpy(rs.uniform(0, a.size, (n, 2)).astype(np.float32)).to(dev)   # nearest seed on the torus, in slabs of rows
+    px = torch.arange(a.size, dtype=torch.float32, device=dev) + 0.5
+    slabs = []
+    for y0 in range(0, a.size, 16):
+        dy = (px[y0:y0 + 16, None] - seeds[None, :, 0]).abs()
+        dx = (px[:, None] - seeds[None, :, 1]).abs()
+        dy, dx = torch.minimum(dy, a.size - dy), torch.minimum(dx, a.size - dx)
+        slabs.append((dy[:, None, :] ** 2 + dx[None, :, :] ** 2).argmin(2))
+    ids = torch.cat(slabs).cpu().numpy() + 1
+    del slabs
+    th = np.stack([np.linspace(0.05, 1.5, n)[rs.permutation(n)], np.linspace(1.5, 0.05, n)[rs.permutation(n)]]).astype(np.float32)
+    m = rs.rand(a.size, a.size)
+    ids[m < 0.005] = 0
+    wrong = (m >= 0.005) & (m < 0.01)
+    ids[wrong] = rs.randint(1, n + 1, int(wrong.sum()))
+    big = np.ascontiguousarray(th[:, np.maximum(ids, 1) - 1])
+    big[:, ids == 0] = np.nan
+    maps[f"voronoi {a.size} x {a.size}, {n} cells, 1 % noise"] = (big, 0.5 * 1.45 / n, 8)
+
+    def host_route(angles_dev, tol, min_pixels):
+        ang = angles_dev.cpu().numpy()
+        ny, nx = ang.shape[1:]
+        ok = lc.validity(None, ang, None)
+        right, down = lc.links(None, ang, tol, ok, True)
+        idx = np.arange(ny * nx, dtype=np.int64).reshape(ny, nx)
+        src = np.concatenate([idx[right], idx[down]])
+        dst = np.concatenate([np.roll(idx, -1, 1)[right], np.roll(idx, -1, 0)[down]])
+        _, comp = connected_components(coo_matrix((np.ones(len(src), np.int8), (src, dst)), shape=(ny * nx, ny * nx)), directed=False)
+        first = np.full(comp.max() + 1, ny * nx, np.int64)
+        np.minimum.at(first, comp, idx.reshape(-1))
+        root = first[comp]
+        okf = ok.reshape(-1)
+        size = np.bincount(root[okf], minlength=ny * nx)
+        closed = okf & (size[root] >= min_pixels)
+        state = np.where(closed, root, -1).reshape(ny, nx)
+        for _ in range(64):
+            state, assigned = lc.sweep(state, True)
+            if not assigned:
+                break
+        roots = np.unique(root[closed])
+        rank = np.zeros(ny * nx + 1, np.int32)
+        rank[roots] = np.arange(1, len(roots) + 1)
+        image = torch.from_numpy(rank[state.reshape(-1)].reshape(ny, nx)).to(dev)
+        torch.cuda.synchronize()
+        return image, len(roots)
+
+    def by_events(call):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        call()
+        t1.record()
+        t1.synchronize()
+        return t0.elapsed_time(t1) * 1e3
+
+    def by_clock(call):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        call()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e6
+
+    activities = {}
+    for name, (angles, tol, mp) in maps.items():
+        ang = torch.from_numpy(angles).to(dev)
+        K, ny, nx = ang.shape
+        image, n_grain, means, status = vz.label_grains(angles=ang, tol=tol, min_pixels=mp)
+        v = vz._label(None, ang, tol, None, mp, 64, "periodic", None)
+        A = v["calls"][0]
+        print(f"# {name}: {n_grain} grains, status {status}, workspace {lib.ggnn_label_workspace_bytes(nx, ny, K) / 1e6:.1f} MB", flush=True)
+        if not a.no_host:
+            h_image, h_n = host_route(ang, tol, mp)
+            print(f"# the host route gives the same image: {bool(torch.equal(h_image, image))} ({h_n} grains)", flush=True)
+        large = nx * ny > 1 << 20
+        arms = {"call": lambda: by_events(lambda: _lib.check(lib.ggnn_label_grains(ctypes.byref(A), _lib.current_stream()), "label")),
+                "label": lambda: by_clock(lambda: vz.label_grains(angles=ang, tol=tol, min_pixels=mp)),
+                "host": lambda: by_clock(lambda: host_route(ang, tol, mp))}
+        if a.no_host:
+            del arms["host"]
+        times = {k: [] for k in arms}
+        for rnd in range(a.rounds + 3):
+            for arm, call in arms.items():
+                if arm == "host" and large and not 3 <= rnd < 3 + a.host_rounds:
+                    continue
+                t = call()
+                if rnd >= 3:
+                    times[arm].append(t)
+        for arm, t in times.items():
+            t = np.array(t)
+            print(f"{arm:6s} us ({len(t)} rounds): median {np.median(t):12.1f}  min {t.min():12.1f}  max {t.max():12.1f}", flush=True)
+        if not a.no_host:
+            print(f"# host / label = {np.median(times['host']) / np.median(times['label']):.1f}", flush=True)
+        floor = label_floor(nx, ny, K, status, 64)
+        total = sum(b for _, b in floor)
+        print("# traffic floor at 8 TB/s: " + ", ".join(f"{k} {b / 8e6:.2f} us" for k, b in floor) + f"; all {total / 8e6:.1f} us "
+              f"({total / 1e6:.1f} MB); call / floor = {np.median(times['call']) / (total / 8e6):.1f}", flush=True)
+        try:
+            from torch.profiler import ProfilerActivity, profile
+            with profile(activities=[ProfilerActivity.CUDA]) as prof:
+                _lib.check(lib.ggnn_label_grains(ctypes.byref(A), _lib.current_stream()), "label")
+                torch.cuda.synchronize()
+            activities[name] = sum(1 for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA)
+            print(f"device activities (kernels, memsets) of one call: {activities[name]}", flush=True)
+            for e in sorted(prof.key_averages(), key=lambda e: e.key):
+                t = getattr(e, "device_time_total", None)
+                t = getattr(e, "cuda_time_total", 0.0) if t is None else t
+                if t:
+                    print(f"    {e.count:3d} x {e.key[:100]}: {t:.1f} us by the tracer", flush=True)
+        except Exception as exc:   # (a build of torch without the tracer)
+            print(f"# launches not counted: {type(exc).__name__}: {exc}", flush=True)
+    print(f"# device activities per map: {activities}; torch {torch.__version__}, {torch.cuda.get_device_name()}", flush=True)
 
 
 if __name__ == "__main__":
