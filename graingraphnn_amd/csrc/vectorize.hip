@@ -19,6 +19,17 @@
 // GGNN_BC_NOFLUX is a compile-time mode of the same kernels (the periodic instantiation keeps its instruction stream): the
 // windows run from -1, a pixel outside the image reads as the boundary grain's id 1 -- resolved in registers, no padded copy
 // of the image is made --, offsets are clipped and not wrapped, and a junction of grain 0 gets its wall's coordinate exactly.
+// STACK is a compile-time mode in the same way (ggnn_image_junctions_traj / ggnn_junction_links_traj: a stack of images into
+// one union graph; the single-image instantiation keeps its instruction stream): the same rule per image and the same three
+// passes, with the blocks laid out image-major -- block = image * (rows * segments) + row * segments + segment --, so block
+// order is still the order of the numbering and the one scan block carries over; it also writes joint_off[image] = the scan at
+// the image's first block.  A block belongs to one image: its base pointer, its grain range [grain_off[b], grain_off[b + 1])
+// (clamped to the union's n_grain; read from the device, never from the host) and its status row are block-uniform, and the
+// window tests run on that image alone, so a wrap, a clipped offset or an outside pixel never reaches a neighbouring image.
+// The stack's count pass also counts the pixels per union grain (every pixel is the TL pixel of exactly one window): a lane
+// adds the length of its run of equal ids in the wave, so a row inside a grain is one atomic and not 64.  A single image is
+// the stack of one with the image's own ids: no grain_off and no joint_off exist for it, and every read or write of either
+// stands in code that STACK = false compiles out.
 // Every index is clamped as elsewhere: a pixel outside [1, n_grain] voids its windows, nothing is written at or beyond
 // joint_capacity, and ggnn_junction_links bounds every row and column it reads by the tables' sizes.
 #include <algorithm>
@@ -132,154 +143,23 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v) {
   return v;
 }
 
-// EMIT = false: block_count[b] = the junctions of block b, and the three window counters of the status.
-// EMIT = true : block_count holds the exclusive scan; the junctions are written.
-// BC = GGNN_BC_NOFLUX: the grid is ny + 1 rows of segments of the nx + 1 windows of a row, and window (y, x) begins at -1.
-template <bool EMIT, int BC>
-__global__ __launch_bounds__(VEC_BLOCK) void image_junctions_kernel(const ggnn_junction_args A, int segments) {
-  __shared__ int wave_total[VEC_WAVES];
-  constexpr int FIRST = BC == GGNN_BC_PERIODIC ? 0 : -1;
-  const int nx = (int)A.nx, ny = (int)A.ny, R = A.merge_radius;
-  const int32_t n_grain = (int32_t)A.n_grain;
-  const int row = blockIdx.x / segments;
-  const int y = row + FIRST, x = (blockIdx.x - row * segments) * VEC_BLOCK + threadIdx.x + FIRST;
-  int32_t k[2][3];
-  int n_keys = 0, m[2] = {0, 0}, sx[2] = {0, 0}, sy[2] = {0, 0};
-  bool rep[2] = {false, false}, tl_invalid = false;
-  if (x < nx) {
-    n_keys = window_keys<BC>(A.image, y, x, nx, ny, n_grain, k, tl_invalid);
-    for (int i = 0; i < n_keys; ++i)
-      rep[i] = window_represents<BC>(A.image, y, x, nx, ny, n_grain, R, k[i], m[i], sx[i], sy[i]);
-  }
-  const int mine = (rep[0] ? 1 : 0) + (rep[1] ? 1 : 0);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const uint64_t one = __ballot(mine >= 1), two = __ballot(mine == 2);
-  if (lane == 0) wave_total[wave] = __popcll(one) + __popcll(two);
-  __syncthreads();
-  if (!EMIT) {
-    if (threadIdx.x == 0) {
-      int total = 0;
-      for (int w = 0; w < VEC_WAVES; ++w) total += wave_total[w];
-      A.workspace[blockIdx.x] = total;
-    }
-    unsigned long long* status = (unsigned long long*)A.status;
-    const unsigned long long quads = wave_sum(n_keys == 2 ? 1 : 0), merged = wave_sum((unsigned long long)(n_keys - mine)),
-                             invalid = wave_sum(tl_invalid ? 1 : 0);
-    if (lane == 0) {
-      if (quads) atomicAdd(status + 1, quads);
-      if (merged) atomicAdd(status + 2, merged);
-      if (invalid) atomicAdd(status + 3, invalid);
-    }
-    return;
-  }
-  if (!mine) return;
-  const uint64_t below = lane ? ~0ull >> (64 - lane) : 0;
-  int64_t j = (int64_t)A.workspace[blockIdx.x] + __popcll(one & below) + __popcll(two & below);
-  for (int w = 0; w < wave; ++w) j += wave_total[w];
-  const int64_t ld = 3 * A.joint_capacity;
-  for (int i = 0; i < n_keys; ++i) {
-    if (!rep[i]) continue;
-    if (j >= 0 && j < A.joint_capacity) {
-      // x = ((float)xr + off + (float)Sx / (float)m) * pitch: the quotient, the sum of the first two, the sum, the product
-      const float qx = __fdiv_rn((float)sx[i], (float)m[i]), qy = __fdiv_rn((float)sy[i], (float)m[i]);
-      float px = __fmul_rn(__fadd_rn(__fadd_rn((float)x, A.offset), qx), A.pitch);
-      float py = __fmul_rn(__fadd_rn(__fadd_rn((float)y, A.offset), qy), A.pitch);
-      if (BC == GGNN_BC_NOFLUX && k[i][0] == 0) {   // a wall junction: the wall its window straddles sets the coordinate
-        const float two_off = __fmul_rn(2.0f, A.offset);
-        const float max_y = __fdiv_rn(__fadd_rn((float)(ny - 2), two_off), __fadd_rn((float)(nx - 2), two_off));
-        px = x == -1 ? 0.0f : x == nx - 1 ? 1.0f : fminf(fmaxf(px, 0.0f), 1.0f);
-        py = y == -1 ? 0.0f : y == ny - 1 ? max_y : fminf(fmaxf(py, 0.0f), max_y);
-      }
-      A.xy[2 * j] = px;
-      A.xy[2 * j + 1] = py;
-      for (int c = 0; c < 3; ++c) {
-        A.triples[3 * j + c] = k[i][c];
-        A.edge_gj[3 * j + c] = k[i][c];
-        A.edge_gj[ld + 3 * j + c] = j;
-      }
-    }
-    ++j;
-  }
-}
-
-// One block: the exclusive scan of the block counts in place, n_joint and overflow, and the grains that have pixels (ids
-// first_id .. n_grain: from 1, or from 2 for a no-flux image, whose id 1 is the boundary grain).
-__global__ __launch_bounds__(VEC_SCAN_BLOCK) void junction_scan_kernel(int32_t* __restrict__ count, int64_t n_blocks,
-                                                                       const uint64_t* __restrict__ pixel_counts, int64_t first_id,
-                                                                       int64_t n_grain, int64_t joint_capacity,
-                                                                       int64_t* __restrict__ status) {
-  __shared__ long long part[VEC_SCAN_BLOCK];
-  __shared__ unsigned long long present;
-  const int t = threadIdx.x;
-  const int64_t per = (n_blocks + VEC_SCAN_BLOCK - 1) / VEC_SCAN_BLOCK;
-  const int64_t begin = min((int64_t)t * per, n_blocks), end = min(begin + per, n_blocks);
-  long long sum = 0;
-  for (int64_t i = begin; i < end; ++i) sum += count[i];
-  part[t] = sum;
-  if (t == 0) present = 0;
-  __syncthreads();
-  for (int s = 1; s < VEC_SCAN_BLOCK; s <<= 1) {   // inclusive scan of the threads' sums
-    const long long add = t >= s ? part[t - s] : 0;
-    __syncthreads();
-    part[t] += add;
-    __syncthreads();
-  }
-  long long at = part[t] - sum;
-  for (int64_t i = begin; i < end; ++i) {
-    const int32_t c = count[i];
-    count[i] = (int32_t)at;   // (at most 2 (2^15 - 1)^2 < 2^31 junctions)
-    at += c;
-  }
-  unsigned long long have = 0;
-  for (int64_t g = first_id + t; g <= n_grain; g += VEC_SCAN_BLOCK) have += pixel_counts[g] != 0 ? 1 : 0;
-  have = wave_sum(have);
-  if ((t & 63) == 0 && have) atomicAdd(&present, have);
-  __syncthreads();
-  if (t == 0) {
-    const long long total = part[VEC_SCAN_BLOCK - 1];
-    status[0] = total;
-    status[5] = (int64_t)present;
-    status[6] = total > joint_capacity ? 1 : 0;
-  }
-}
-
-// One thread a (junction, pair) slot: the one other junction of grain a's row whose triple holds grain b.
-__global__ __launch_bounds__(256) void junction_links_kernel(const ggnn_link_args A) {
-  const int64_t n = min(max(A.status[0], (int64_t)0), A.joint_capacity);
-  const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  unsigned long long open = 0;
-  if (s < 3 * n) {
-    const int64_t j = s / 3;
-    const int k = (int)(s - 3 * j);
-    const int32_t a = A.triples[3 * j + (k == 2 ? 1 : 0)], b = A.triples[3 * j + (k == 0 ? 1 : 2)];
-    int found = 0;
-    int64_t partner = -1;
-    if (a >= 0 && a < A.n_grain) {
-      const int64_t p0 = min((int64_t)max(A.rowptr[a], 0), A.E_cap);
-      const int64_t p1 = min(max((int64_t)A.rowptr[a + 1], p0), A.E_cap);
-      for (int64_t p = p0; p < p1; ++p) {
-        const int64_t o = A.col[p];
-        if (o < 0 || o >= n || o == j) continue;
-        if (A.triples[3 * o] == b || A.triples[3 * o + 1] == b || A.triples[3 * o + 2] == b) ++found, partner = o;
-      }
-    }
-    A.edge_jj[s] = j;
-    A.edge_jj[3 * A.joint_capacity + s] = found == 1 ? partner : -1;
-    open = found == 1 ? 0 : 1;
-  }
-  open = wave_sum(open);
-  if ((threadIdx.x & 63) == 0 && open) atomicAdd((unsigned long long*)A.status + 4, open);
-}
-
-// ---- A stack of images into one union graph (ggnn_image_junctions_traj / ggnn_junction_links_traj) ---------------------------
-// The same rule per image, and the same three passes: the blocks are laid out image-major -- block = image * (rows *
-// segments) + row * segments + segment --, so block order is still the order of the numbering and the one scan block carries
-// over; it also writes joint_off[image] = the scan at the image's first block.  A block belongs to one image: its base
-// pointer, its grain range [grain_off[b], grain_off[b + 1]) (clamped to the union's n_grain; read from the device, never from
-// the host) and its status row are block-uniform, and the window tests above run on that image alone, so a wrap, a clipped
-// offset or an outside pixel never reaches a neighbouring image.  The count pass also counts the pixels per union grain
-// (every pixel is the TL pixel of exactly one window): a lane adds the length of its run of equal ids in the wave, so a row
-// inside a grain is one atomic and not 64.
+// What the kernels of both junction entry points take, filled from the public structs.  A single image: n_image 1, no
+// grain_off, no rep, pixel_counts = the caller's histogram by id (read); a stack: pixel_counts by union grain (written).
+struct junction_kargs {
+  const int32_t* images;         // [n_image, ny, nx]
+  const int64_t* grain_off;      // [n_image + 1], STACK alone
+  uint64_t* pixel_counts;
+  float* xy;
+  int32_t* triples;
+  int64_t* edge_gj;
+  int64_t* status;               // the caller's: n_image rows, and for STACK joint_off [n_image + 1] behind them
+  int32_t* workspace;            // a word a block
+  int32_t* rep;                  // ggnn_image_junction_windows_traj's, or null
+  int64_t nx, ny, n_image, n_grain, joint_capacity;
+  float offset, pitch;
+  int32_t merge_radius;
+  int32_t segments, rows;        // the blocks of a row of windows, the rows of windows of an image
+};
 
 // The grains of image b: -> the first one, n = how many (0 when the offsets do not rise).
 __device__ __forceinline__ int64_t image_grains(const int64_t* __restrict__ grain_off, int64_t b, int64_t n_total, int32_t& n) {
@@ -298,18 +178,28 @@ __device__ __forceinline__ int64_t segment_of(const int64_t* __restrict__ off, i
   return lo;
 }
 
-template <bool EMIT, int BC>
-__global__ __launch_bounds__(VEC_BLOCK) void image_junctions_traj_kernel(const ggnn_junction_traj_args A, int segments, int rows,
-                                                                         int32_t* __restrict__ rep_out) {
+// EMIT = false: block_count[b] = the junctions of block b, the three window counters of the status and, for a stack, the
+//               pixel counts.
+// EMIT = true : block_count holds the exclusive scan; the junctions are written.
+// BC = GGNN_BC_NOFLUX: the grid is ny + 1 rows of segments of the nx + 1 windows of a row, and window (y, x) begins at -1.
+// STACK = false: the image is the one image, its grains are 0 .. n_grain - 1 and its status row is the one row.
+template <bool EMIT, int BC, bool STACK>
+__global__ __launch_bounds__(VEC_BLOCK) void image_junctions_kernel(const junction_kargs A) {
   __shared__ int wave_total[VEC_WAVES];
   constexpr int FIRST = BC == GGNN_BC_PERIODIC ? 0 : -1;
-  const int nx = (int)A.nx, ny = (int)A.ny, R = A.merge_radius;
-  const int per_image = rows * segments;
-  const int b = blockIdx.x / per_image, in_image = blockIdx.x - b * per_image;
-  if (b >= A.n_image) return;
-  int32_t n_grain;
-  const int64_t g0 = image_grains(A.grain_off, b, A.n_grain, n_grain);
-  const int32_t* __restrict__ image = A.images + (int64_t)b * ny * nx;
+  const int nx = (int)A.nx, ny = (int)A.ny, R = A.merge_radius, segments = A.segments;
+  int b = 0;
+  unsigned in_image = blockIdx.x;
+  int32_t n_grain = (int32_t)A.n_grain;
+  int64_t g0 = 0;
+  const int32_t* __restrict__ image = A.images;
+  if (STACK) {   // (block-uniform)
+    const int per_image = A.rows * segments;
+    b = blockIdx.x / per_image, in_image = blockIdx.x - b * per_image;
+    if (b >= A.n_image) return;
+    g0 = image_grains(A.grain_off, b, A.n_grain, n_grain);
+    image += (int64_t)b * ny * nx;
+  }
   const int row = in_image / segments;
   const int y = row + FIRST, x = (in_image - row * segments) * VEC_BLOCK + threadIdx.x + FIRST;
   int32_t k[2][3];
@@ -338,19 +228,21 @@ __global__ __launch_bounds__(VEC_BLOCK) void image_junctions_traj_kernel(const g
       if (merged) atomicAdd(status + 2, merged);
       if (invalid) atomicAdd(status + 3, invalid);
     }
-    // the pixel counts: the image's own word of the TL pixel (id 1 of a no-flux image included: the counts are a histogram)
-    int32_t id = 0;
-    if (x < nx && x >= 0 && y >= 0) {
-      id = image[(int64_t)y * nx + x];
-      id = id >= 1 && id <= n_grain ? id : 0;
-    }
-    const int32_t before = __shfl_up(id, 1);
-    const bool head = lane == 0 || id != before;
-    const uint64_t heads = __ballot(head);
-    if (head && id) {
-      const uint64_t above = lane == 63 ? 0 : heads >> (lane + 1);
-      const int run = above ? __ffsll((unsigned long long)above) : 64 - lane;
-      atomicAdd((unsigned long long*)A.pixel_counts + g0 + id - 1, (unsigned long long)run);
+    if (STACK) {
+      // the pixel counts: the image's own word of the TL pixel (id 1 of a no-flux image included: the counts are a histogram)
+      int32_t id = 0;
+      if (x < nx && x >= 0 && y >= 0) {
+        id = image[(int64_t)y * nx + x];
+        id = id >= 1 && id <= n_grain ? id : 0;
+      }
+      const int32_t before = __shfl_up(id, 1);
+      const bool head = lane == 0 || id != before;
+      const uint64_t heads = __ballot(head);
+      if (head && id) {
+        const uint64_t above = lane == 63 ? 0 : heads >> (lane + 1);
+        const int run = above ? __ffsll((unsigned long long)above) : 64 - lane;
+        atomicAdd((unsigned long long*)A.pixel_counts + g0 + id - 1, (unsigned long long)run);
+      }
     }
     return;
   }
@@ -362,11 +254,11 @@ __global__ __launch_bounds__(VEC_BLOCK) void image_junctions_traj_kernel(const g
   for (int i = 0; i < n_keys; ++i) {
     if (!rep[i]) continue;
     if (j >= 0 && j < A.joint_capacity) {
-      // the position and the wall snap: image_junctions_kernel's expressions, operation for operation
+      // x = ((float)xr + off + (float)Sx / (float)m) * pitch: the quotient, the sum of the first two, the sum, the product
       const float qx = __fdiv_rn((float)sx[i], (float)m[i]), qy = __fdiv_rn((float)sy[i], (float)m[i]);
       float px = __fmul_rn(__fadd_rn(__fadd_rn((float)x, A.offset), qx), A.pitch);
       float py = __fmul_rn(__fadd_rn(__fadd_rn((float)y, A.offset), qy), A.pitch);
-      if (BC == GGNN_BC_NOFLUX && k[i][0] == 0) {
+      if (BC == GGNN_BC_NOFLUX && k[i][0] == 0) {   // a wall junction: the wall its window straddles sets the coordinate
         const float two_off = __fmul_rn(2.0f, A.offset);
         const float max_y = __fdiv_rn(__fadd_rn((float)(ny - 2), two_off), __fadd_rn((float)(nx - 2), two_off));
         px = x == -1 ? 0.0f : x == nx - 1 ? 1.0f : fminf(fmaxf(px, 0.0f), 1.0f);
@@ -381,30 +273,31 @@ __global__ __launch_bounds__(VEC_BLOCK) void image_junctions_traj_kernel(const g
         A.edge_gj[ld + 3 * j + c] = j;
       }
       // (ggnn_image_junction_windows_traj: the representative's raster index within its image, below 2^30)
-      if (rep_out) rep_out[j] = BC == GGNN_BC_PERIODIC ? y * nx + x : (y + 1) * (nx + 1) + (x + 1);
+      if (STACK && A.rep) A.rep[j] = BC == GGNN_BC_PERIODIC ? y * nx + x : (y + 1) * (nx + 1) + (x + 1);
     }
     ++j;
   }
 }
 
-// One block: the exclusive scan of the block counts in place; per image joint_off (behind the status rows), n_joint, overflow
-// and the grains that have pixels (local ids from first_local: 0, or 1 for a no-flux image, whose local grain 0 is the
-// boundary grain).  The images' present grains are summed in LDS for the first VEC_SCAN_BLOCK images, in memory beyond.
-__global__ __launch_bounds__(VEC_SCAN_BLOCK) void junction_scan_traj_kernel(int32_t* __restrict__ count, int64_t n_blocks,
-                                                                            int64_t per_image,
-                                                                            const uint64_t* __restrict__ pixel_counts,
-                                                                            const int64_t* __restrict__ grain_off,
-                                                                            int64_t first_local, int64_t n_grain, int64_t n_image,
-                                                                            int64_t joint_capacity, int64_t* __restrict__ status) {
+// One block: the exclusive scan of the block counts in place; per image n_joint, overflow and the grains that have pixels
+// (local grains from first_local: 0, or 1 for a no-flux image, whose local grain 0 is the boundary grain) and, for a stack,
+// joint_off behind the status rows.  A stack's present grains are summed in LDS for the first VEC_SCAN_BLOCK images, in
+// memory beyond; a single image's are the ids first_local + 1 .. n_grain of its histogram, summed by wave.
+template <bool STACK>
+__global__ __launch_bounds__(VEC_SCAN_BLOCK) void junction_scan_kernel(const junction_kargs A, int64_t first_local) {
   __shared__ long long part[VEC_SCAN_BLOCK];
-  __shared__ unsigned int present[VEC_SCAN_BLOCK];
+  __shared__ unsigned int present[STACK ? VEC_SCAN_BLOCK : 1];
+  int32_t* __restrict__ count = A.workspace;
+  int64_t* __restrict__ status = A.status;
+  const int64_t n_image = STACK ? A.n_image : 1, per_image = (int64_t)A.rows * A.segments, n_blocks = n_image * per_image;
+  const int64_t n_grain = A.n_grain, joint_capacity = A.joint_capacity;
   const int t = threadIdx.x;
   const int64_t per = (n_blocks + VEC_SCAN_BLOCK - 1) / VEC_SCAN_BLOCK;
   const int64_t begin = min((int64_t)t * per, n_blocks), end = min(begin + per, n_blocks);
   long long sum = 0;
   for (int64_t i = begin; i < end; ++i) sum += count[i];
   part[t] = sum;
-  present[t] = 0;
+  if (STACK || t == 0) present[STACK ? t : 0] = 0;
   __syncthreads();
   for (int s = 1; s < VEC_SCAN_BLOCK; s <<= 1) {   // inclusive scan of the threads' sums
     const long long add = t >= s ? part[t - s] : 0;
@@ -418,29 +311,38 @@ __global__ __launch_bounds__(VEC_SCAN_BLOCK) void junction_scan_traj_kernel(int3
     count[i] = (int32_t)at;   // (at most 512 junctions a block, at most 2^22 blocks)
     at += c;
   }
-  for (int64_t g = t; g < n_grain; g += VEC_SCAN_BLOCK) {
-    if (pixel_counts[g] == 0) continue;
-    const int64_t b = segment_of(grain_off, n_image, g);
-    int32_t n;
-    const int64_t g0 = image_grains(grain_off, b, n_grain, n);
-    if (g < g0 + first_local || g >= g0 + n) continue;
-    if (b < VEC_SCAN_BLOCK)
-      atomicAdd(&present[b], 1u);
-    else
-      atomicAdd((unsigned long long*)status + b * GGNN_JUNCTION_STATUS_WORDS + 5, 1ull);
+  if (STACK) {
+    const uint64_t* __restrict__ pixel_counts = A.pixel_counts;
+    for (int64_t g = t; g < n_grain; g += VEC_SCAN_BLOCK) {
+      if (pixel_counts[g] == 0) continue;
+      const int64_t b = segment_of(A.grain_off, n_image, g);
+      int32_t n;
+      const int64_t g0 = image_grains(A.grain_off, b, n_grain, n);
+      if (g < g0 + first_local || g >= g0 + n) continue;
+      if (b < VEC_SCAN_BLOCK)
+        atomicAdd(&present[b], 1u);
+      else
+        atomicAdd((unsigned long long*)status + b * GGNN_JUNCTION_STATUS_WORDS + 5, 1ull);
+    }
+  } else {
+    const uint64_t* __restrict__ by_id = A.pixel_counts + 1;
+    unsigned long long have = 0;
+    for (int64_t g = first_local + t; g < n_grain; g += VEC_SCAN_BLOCK) have += by_id[g] != 0 ? 1 : 0;
+    have = wave_sum(have);   // (below n_grain < 2^31)
+    if ((t & 63) == 0 && have) atomicAdd(&present[0], (unsigned int)have);
   }
   __syncthreads();   // (the scan in `count` and the LDS sums, for every thread of the block)
   const long long total = part[VEC_SCAN_BLOCK - 1];
-  int64_t* joint_off = status + n_image * GGNN_JUNCTION_STATUS_WORDS;
+  int64_t* joint_off = status + n_image * GGNN_JUNCTION_STATUS_WORDS;   // (STACK alone: a single image's status ends here)
   for (int64_t b = t; b < n_image; b += VEC_SCAN_BLOCK) {
     const long long lo = count[b * per_image], hi = b + 1 < n_image ? (long long)count[(b + 1) * per_image] : total;
     int64_t* s = status + b * GGNN_JUNCTION_STATUS_WORDS;
-    joint_off[b] = lo;
+    if (STACK) joint_off[b] = lo;
     s[0] = hi - lo;
     if (b < VEC_SCAN_BLOCK) s[5] = present[b];
     s[6] = hi > joint_capacity ? 1 : 0;
   }
-  if (t == 0) joint_off[n_image] = total;
+  if (STACK && t == 0) joint_off[n_image] = total;
 }
 
 __global__ __launch_bounds__(256) void zero_open_pairs_kernel(int64_t* __restrict__ status, int64_t n_image) {
@@ -448,11 +350,14 @@ __global__ __launch_bounds__(256) void zero_open_pairs_kernel(int64_t* __restric
   if (b < n_image) status[b * GGNN_JUNCTION_STATUS_WORDS + 4] = 0;
 }
 
-// junction_links_kernel on the union: triples and rows hold union grains, a pair's partner lies in its grain's row and so in
-// its image; an open slot is counted in the status row of the image that joint_off puts the junction in.
-__global__ __launch_bounds__(256) void junction_links_traj_kernel(const ggnn_link_traj_args A) {
-  const int64_t* joint_off = A.status + A.n_image * GGNN_JUNCTION_STATUS_WORDS;
-  const int64_t n = min(max(joint_off[A.n_image], (int64_t)0), A.joint_capacity);
+// One thread a (junction, pair) slot: the one other junction of grain a's row whose triple holds grain b.  On a union the
+// triples and rows hold union grains, a pair's partner lies in its grain's row and so in its image.  An open slot is counted
+// in word 4 of its image's status row: the one row, or the row of the image that joint_off puts the junction in.  (The
+// arguments are the union's for both: ggnn_junction_links fills them with n_image 1.)
+template <bool STACK>
+__global__ __launch_bounds__(256) void junction_links_kernel(const ggnn_link_traj_args A) {
+  const int64_t* joint_off = A.status + A.n_image * GGNN_JUNCTION_STATUS_WORDS;   // (STACK alone)
+  const int64_t n = min(max(STACK ? joint_off[A.n_image] : A.status[0], (int64_t)0), A.joint_capacity);
   const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= 3 * n) return;
   const int64_t j = s / 3;
@@ -472,11 +377,12 @@ __global__ __launch_bounds__(256) void junction_links_traj_kernel(const ggnn_lin
   A.edge_jj[s] = j;
   A.edge_jj[3 * A.joint_capacity + s] = found == 1 ? partner : -1;
   if (found != 1)   // (rare: none in a valid structure)
-    atomicAdd((unsigned long long*)A.status + segment_of(joint_off, A.n_image, j) * GGNN_JUNCTION_STATUS_WORDS + 4, 1ull);
+    atomicAdd((unsigned long long*)A.status + (STACK ? segment_of(joint_off, A.n_image, j) : 0) * GGNN_JUNCTION_STATUS_WORDS + 4,
+              1ull);
 }
 
 // ---- Linking by tracing boundaries (ggnn_junction_links_trace_traj; tests/tracecheck.py restates the rule) ------------------
-// The columns junction_links_traj_kernel left open -- a pair of grains held by more than one other junction: a lens on a
+// The columns junction_links_kernel<true> left open -- a pair of grains held by more than one other junction: a lens on a
 // boundary, a band from wall to wall -- are linked by following the a | b boundary through the image, pixel edge by pixel
 // edge, from the junction to the one at the other end.  A thread takes a column and returns at once unless it is open; the
 // open ones are a handful an image and each is a chain of dependent reads that L2 serves, so there is no compaction and no
@@ -688,49 +594,54 @@ __global__ __launch_bounds__(256) void junction_trace_kernel(const ggnn_link_tra
 
 }  // namespace ggnn
 
+// The checks the junction entry points share, on the kernel arguments they filled: -> the blocks of the grid, with
+// K.segments and K.rows set, or 0: invalid.  (A single image, n_image 1, has at most 2^15 2^7 = GGNN_JUNCTION_MAX_BLOCKS.)
+static int64_t junction_blocks(ggnn::junction_kargs& K, size_t workspace_bytes, int32_t boundary) {
+  using namespace ggnn;
+  if (!K.images || !K.pixel_counts || !K.xy || !K.triples || !K.edge_gj || !K.status || !K.workspace) return 0;
+  if (K.merge_radius < 0 || K.merge_radius > VEC_MAX_RADIUS) return 0;
+  if (K.nx <= 2 * K.merge_radius || K.ny <= 2 * K.merge_radius || K.nx >= (1 << 15) || K.ny >= (1 << 15)) return 0;
+  if (K.n_image < 1 || K.n_image > GGNN_JUNCTION_MAX_BLOCKS) return 0;
+  if (K.n_grain < 1 || K.n_grain >= INT32_MAX - 1) return 0;
+  if (K.joint_capacity < 1 || K.joint_capacity > INT32_MAX / 3) return 0;
+  if (!(K.pitch > 0.0f) || !(K.offset >= 0.0f) || K.pitch > 1.0f || K.offset > 1.0f) return 0;
+  if ((reinterpret_cast<uintptr_t>(K.status) | reinterpret_cast<uintptr_t>(K.edge_gj) |
+       reinterpret_cast<uintptr_t>(K.pixel_counts)) & 7u)
+    return 0;
+  if (boundary != GGNN_BC_PERIODIC && boundary != GGNN_BC_NOFLUX) return 0;
+  const bool periodic = boundary == GGNN_BC_PERIODIC;
+  const int64_t wx = periodic ? K.nx : K.nx + 1, wy = periodic ? K.ny : K.ny + 1;   // the windows of a row, the rows
+  K.segments = (int32_t)((wx + VEC_BLOCK - 1) / VEC_BLOCK), K.rows = (int32_t)wy;
+  const int64_t n_blocks = K.n_image * wy * K.segments;                             // (< 2^22 2^22: no overflow)
+  if (n_blocks > GGNN_JUNCTION_MAX_BLOCKS) return 0;
+  if (workspace_bytes < (size_t)n_blocks * sizeof(int32_t)) return 0;
+  return n_blocks;
+}
+
+// Count, scan, emit.
+template <bool STACK>
+static int launch_junctions(const ggnn::junction_kargs& K, int64_t n_blocks, int32_t boundary, hipStream_t st) {
+  using namespace ggnn;
+  const bool periodic = boundary == GGNN_BC_PERIODIC;
+  const auto count = periodic ? image_junctions_kernel<false, GGNN_BC_PERIODIC, STACK> : image_junctions_kernel<false, GGNN_BC_NOFLUX, STACK>;
+  const auto emit = periodic ? image_junctions_kernel<true, GGNN_BC_PERIODIC, STACK> : image_junctions_kernel<true, GGNN_BC_NOFLUX, STACK>;
+  hipLaunchKernelGGL(count, dim3((unsigned)n_blocks), dim3(VEC_BLOCK), 0, st, K);
+  hipLaunchKernelGGL(junction_scan_kernel<STACK>, dim3(1), dim3(VEC_SCAN_BLOCK), 0, st, K, (int64_t)(periodic ? 0 : 1));
+  hipLaunchKernelGGL(emit, dim3((unsigned)n_blocks), dim3(VEC_BLOCK), 0, st, K);
+  return launch_status();
+}
+
 extern "C" int ggnn_image_junctions(const ggnn_junction_args* args, ggnn_stream_t stream) {
   using namespace ggnn;
   if (!args) return GGNN_EINVAL;
   const ggnn_junction_args& A = *args;
-  if (!A.image || !A.pixel_counts || !A.xy || !A.triples || !A.edge_gj || !A.status || !A.workspace) return GGNN_EINVAL;
-  if (A.merge_radius < 0 || A.merge_radius > VEC_MAX_RADIUS) return GGNN_EINVAL;
-  if (A.nx <= 2 * A.merge_radius || A.ny <= 2 * A.merge_radius || A.nx >= (1 << 15) || A.ny >= (1 << 15)) return GGNN_EINVAL;
-  if (A.n_grain < 1 || A.n_grain >= INT32_MAX - 1) return GGNN_EINVAL;
-  if (A.joint_capacity < 1 || A.joint_capacity > INT32_MAX / 3) return GGNN_EINVAL;
-  if (!(A.pitch > 0.0f) || !(A.offset >= 0.0f) || A.pitch > 1.0f || A.offset > 1.0f) return GGNN_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(A.status) | reinterpret_cast<uintptr_t>(A.edge_gj) |
-       reinterpret_cast<uintptr_t>(A.pixel_counts)) & 7u)
-    return GGNN_EINVAL;
-  if (A.boundary != GGNN_BC_PERIODIC && A.boundary != GGNN_BC_NOFLUX) return GGNN_EINVAL;
-  const bool periodic = A.boundary == GGNN_BC_PERIODIC;
-  const int64_t wx = periodic ? A.nx : A.nx + 1, wy = periodic ? A.ny : A.ny + 1;   // the windows of a row, the rows
-  const int segments = (int)((wx + VEC_BLOCK - 1) / VEC_BLOCK);
-  const int64_t n_blocks = wy * segments;
-  if (A.workspace_bytes < (size_t)n_blocks * sizeof(int32_t)) return GGNN_EINVAL;
+  junction_kargs K{A.image, nullptr, const_cast<uint64_t*>(A.pixel_counts), A.xy, A.triples, A.edge_gj, A.status, A.workspace,
+                   nullptr, A.nx, A.ny, 1, A.n_grain, A.joint_capacity, A.offset, A.pitch, A.merge_radius, 0, 0};
+  const int64_t n_blocks = junction_blocks(K, A.workspace_bytes, A.boundary);
+  if (!n_blocks) return GGNN_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(A.status, 0, GGNN_JUNCTION_STATUS_WORDS * sizeof(int64_t), st) != hipSuccess) return GGNN_ELAUNCH;
-  const auto count = periodic ? image_junctions_kernel<false, GGNN_BC_PERIODIC> : image_junctions_kernel<false, GGNN_BC_NOFLUX>;
-  const auto emit = periodic ? image_junctions_kernel<true, GGNN_BC_PERIODIC> : image_junctions_kernel<true, GGNN_BC_NOFLUX>;
-  hipLaunchKernelGGL(count, dim3((unsigned)n_blocks), dim3(VEC_BLOCK), 0, st, A, segments);
-  hipLaunchKernelGGL(junction_scan_kernel, dim3(1), dim3(VEC_SCAN_BLOCK), 0, st, A.workspace, n_blocks, A.pixel_counts,
-                     (int64_t)(periodic ? 1 : 2), A.n_grain, A.joint_capacity, A.status);
-  hipLaunchKernelGGL(emit, dim3((unsigned)n_blocks), dim3(VEC_BLOCK), 0, st, A, segments);
-  return launch_status();
-}
-
-extern "C" int ggnn_junction_links(const ggnn_link_args* args, ggnn_stream_t stream) {
-  using namespace ggnn;
-  if (!args) return GGNN_EINVAL;
-  const ggnn_link_args& A = *args;
-  if (!A.triples || !A.rowptr || !A.col || !A.edge_jj || !A.status) return GGNN_EINVAL;
-  if (A.n_grain < 1 || A.n_grain >= INT32_MAX - 1 || A.E_cap < 0 || A.E_cap >= INT32_MAX) return GGNN_EINVAL;
-  if (A.joint_capacity < 1 || A.joint_capacity > INT32_MAX / 3) return GGNN_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(A.status) | reinterpret_cast<uintptr_t>(A.edge_jj)) & 7u) return GGNN_EINVAL;
-  hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(A.status + 4, 0, sizeof(int64_t), st) != hipSuccess) return GGNN_ELAUNCH;
-  const int64_t blocks = (3 * A.joint_capacity + 255) / 256;
-  hipLaunchKernelGGL(junction_links_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A);
-  return launch_status();
+  return launch_junctions<false>(K, n_blocks, A.boundary, st);
 }
 
 // ggnn_image_junctions_traj (rep NULL) and ggnn_image_junction_windows_traj: the same checks, the same launches.
@@ -738,35 +649,16 @@ static int image_junctions_traj(const ggnn_junction_traj_args* args, int32_t* re
   using namespace ggnn;
   if (!args) return GGNN_EINVAL;
   const ggnn_junction_traj_args& A = *args;
-  if (!A.images || !A.grain_off || !A.pixel_counts || !A.xy || !A.triples || !A.edge_gj || !A.status || !A.workspace)
-    return GGNN_EINVAL;
-  if (A.merge_radius < 0 || A.merge_radius > VEC_MAX_RADIUS) return GGNN_EINVAL;
-  if (A.nx <= 2 * A.merge_radius || A.ny <= 2 * A.merge_radius || A.nx >= (1 << 15) || A.ny >= (1 << 15)) return GGNN_EINVAL;
-  if (A.n_image < 1 || A.n_image > GGNN_JUNCTION_MAX_BLOCKS) return GGNN_EINVAL;
-  if (A.n_grain < 1 || A.n_grain >= INT32_MAX - 1) return GGNN_EINVAL;
-  if (A.joint_capacity < 1 || A.joint_capacity > INT32_MAX / 3) return GGNN_EINVAL;
-  if (!(A.pitch > 0.0f) || !(A.offset >= 0.0f) || A.pitch > 1.0f || A.offset > 1.0f) return GGNN_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(A.status) | reinterpret_cast<uintptr_t>(A.edge_gj) |
-       reinterpret_cast<uintptr_t>(A.pixel_counts) | reinterpret_cast<uintptr_t>(A.grain_off)) & 7u)
-    return GGNN_EINVAL;
-  if (A.boundary != GGNN_BC_PERIODIC && A.boundary != GGNN_BC_NOFLUX) return GGNN_EINVAL;
-  const bool periodic = A.boundary == GGNN_BC_PERIODIC;
-  const int64_t wx = periodic ? A.nx : A.nx + 1, wy = periodic ? A.ny : A.ny + 1;   // the windows of a row, the rows
-  const int segments = (int)((wx + VEC_BLOCK - 1) / VEC_BLOCK);
-  const int64_t per_image = wy * segments, n_blocks = A.n_image * per_image;          // (< 2^22 2^22: no overflow)
-  if (n_blocks > GGNN_JUNCTION_MAX_BLOCKS) return GGNN_EINVAL;
-  if (A.workspace_bytes < (size_t)n_blocks * sizeof(int32_t)) return GGNN_EINVAL;
+  if (!A.grain_off || (reinterpret_cast<uintptr_t>(A.grain_off) & 7u)) return GGNN_EINVAL;
+  junction_kargs K{A.images, A.grain_off, A.pixel_counts, A.xy, A.triples, A.edge_gj, A.status, A.workspace,
+                   rep, A.nx, A.ny, A.n_image, A.n_grain, A.joint_capacity, A.offset, A.pitch, A.merge_radius, 0, 0};
+  const int64_t n_blocks = junction_blocks(K, A.workspace_bytes, A.boundary);
+  if (!n_blocks) return GGNN_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(A.status, 0, (size_t)A.n_image * GGNN_JUNCTION_STATUS_WORDS * sizeof(int64_t), st) != hipSuccess)
     return GGNN_ELAUNCH;
   if (hipMemsetAsync(A.pixel_counts, 0, (size_t)A.n_grain * sizeof(uint64_t), st) != hipSuccess) return GGNN_ELAUNCH;
-  const auto count = periodic ? image_junctions_traj_kernel<false, GGNN_BC_PERIODIC> : image_junctions_traj_kernel<false, GGNN_BC_NOFLUX>;
-  const auto emit = periodic ? image_junctions_traj_kernel<true, GGNN_BC_PERIODIC> : image_junctions_traj_kernel<true, GGNN_BC_NOFLUX>;
-  hipLaunchKernelGGL(count, dim3((unsigned)n_blocks), dim3(VEC_BLOCK), 0, st, A, segments, (int)wy, (int32_t*)nullptr);
-  hipLaunchKernelGGL(junction_scan_traj_kernel, dim3(1), dim3(VEC_SCAN_BLOCK), 0, st, A.workspace, n_blocks, per_image,
-                     A.pixel_counts, A.grain_off, (int64_t)(periodic ? 0 : 1), A.n_grain, A.n_image, A.joint_capacity, A.status);
-  hipLaunchKernelGGL(emit, dim3((unsigned)n_blocks), dim3(VEC_BLOCK), 0, st, A, segments, (int)wy, rep);
-  return launch_status();
+  return launch_junctions<true>(K, n_blocks, A.boundary, st);
 }
 
 extern "C" int ggnn_image_junctions_traj(const ggnn_junction_traj_args* args, ggnn_stream_t stream) {
@@ -778,19 +670,37 @@ extern "C" int ggnn_image_junction_windows_traj(const ggnn_junction_traj_args* a
   return image_junctions_traj(args, rep, stream);
 }
 
+// The checks the two links entry points share (n_image: 1 for a single image).
+static bool links_valid(const ggnn_link_traj_args& K) {
+  if (!K.triples || !K.rowptr || !K.col || !K.edge_jj || !K.status) return false;
+  if (K.n_grain < 1 || K.n_grain >= INT32_MAX - 1 || K.E_cap < 0 || K.E_cap >= INT32_MAX) return false;
+  if (K.joint_capacity < 1 || K.joint_capacity > INT32_MAX / 3) return false;
+  if (K.n_image < 1 || K.n_image > GGNN_JUNCTION_MAX_BLOCKS) return false;
+  return !((reinterpret_cast<uintptr_t>(K.status) | reinterpret_cast<uintptr_t>(K.edge_jj)) & 7u);
+}
+
+extern "C" int ggnn_junction_links(const ggnn_link_args* args, ggnn_stream_t stream) {
+  using namespace ggnn;
+  if (!args) return GGNN_EINVAL;
+  const ggnn_link_args& A = *args;
+  const ggnn_link_traj_args K{A.triples, A.rowptr, A.col, A.edge_jj, A.status, A.n_grain, A.joint_capacity, A.E_cap, 1};
+  if (!links_valid(K)) return GGNN_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(A.status + 4, 0, sizeof(int64_t), st) != hipSuccess) return GGNN_ELAUNCH;
+  const int64_t blocks = (3 * A.joint_capacity + 255) / 256;
+  hipLaunchKernelGGL(junction_links_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, K);
+  return launch_status();
+}
+
 extern "C" int ggnn_junction_links_traj(const ggnn_link_traj_args* args, ggnn_stream_t stream) {
   using namespace ggnn;
   if (!args) return GGNN_EINVAL;
   const ggnn_link_traj_args& A = *args;
-  if (!A.triples || !A.rowptr || !A.col || !A.edge_jj || !A.status) return GGNN_EINVAL;
-  if (A.n_grain < 1 || A.n_grain >= INT32_MAX - 1 || A.E_cap < 0 || A.E_cap >= INT32_MAX) return GGNN_EINVAL;
-  if (A.joint_capacity < 1 || A.joint_capacity > INT32_MAX / 3) return GGNN_EINVAL;
-  if (A.n_image < 1 || A.n_image > GGNN_JUNCTION_MAX_BLOCKS) return GGNN_EINVAL;
-  if ((reinterpret_cast<uintptr_t>(A.status) | reinterpret_cast<uintptr_t>(A.edge_jj)) & 7u) return GGNN_EINVAL;
+  if (!links_valid(A)) return GGNN_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(zero_open_pairs_kernel, dim3((unsigned)((A.n_image + 255) / 256)), dim3(256), 0, st, A.status, A.n_image);
   const int64_t blocks = (3 * A.joint_capacity + 255) / 256;
-  hipLaunchKernelGGL(junction_links_traj_kernel, dim3((unsigned)blocks), dim3(256), 0, st, A);
+  hipLaunchKernelGGL(junction_links_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, A);
   return launch_status();
 }
 

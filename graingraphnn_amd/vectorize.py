@@ -103,28 +103,21 @@ def image_max_y(nx, ny, grid):
     return float(f(f(f(ny - 2) + two_off) / f(f(nx - 2) + two_off)))
 
 
-def _vectorize(image, n_grain, grid, merge_radius, joint_capacity, boundary="periodic"):
-    """Every launch, no read-back: -> dict of the capacity-sized device arrays, the pixel counts, the joint->grain table
-    and the status words (no-flux: the four corner pixels behind them, so that one read-back fetches both)."""
-    be = default_backend()
-    _check_boundary(boundary)
-    noflux = boundary == "noflux"
-    if not isinstance(image, torch.Tensor) or not image.is_cuda or image.dim() != 2:
-        raise _lib.GGNNError("image must be a [ny, nx] device tensor of grain ids (pixel p = grain p - 1)")
-    if image.dtype not in (torch.int16, torch.int32, torch.int64, torch.uint8):
-        raise _lib.GGNNError("image must hold integers")
-    if grid not in GRIDS:
-        raise _lib.GGNNError(f"grid must be 'cells' or 'points', got {grid!r}")
-    image = image.to(torch.int32).contiguous()
-    ny, nx = image.shape
-    if n_grain is None:
-        n_grain = int(image.max())   # (a read-back of its own: pass n_grain to avoid it)
-    n_grain, R = int(n_grain), int(merge_radius)
-    if n_grain < 1:
-        raise _lib.GGNNError("n_grain must be at least 1")
-    cap = 3 * n_grain + 16 if joint_capacity is None else int(joint_capacity)
-    dev = image.device
-    _, counts = be.image_compare(image, None, n_grain)
+IMAGE_2D = "image must be a [ny, nx] device tensor of grain ids (pixel p = grain p - 1)"
+
+
+def _image_tensor(t, dim, shape_text, noun="image"):
+    """An image (dim 2) or a stack (dim 3) as the calls take it: on the device, integer -> int32, contiguous."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dim() != dim:
+        raise _lib.GGNNError(shape_text)
+    if t.dtype not in (torch.int16, torch.int32, torch.int64, torch.uint8):
+        raise _lib.GGNNError(f"{noun} must hold integers")
+    return t.to(torch.int32).contiguous()
+
+
+def _arrays(dev, n_grain, cap, n_image, ny, nx, noflux, status_words):
+    """What both vectorisations write into, for `cap` junctions of `n_grain` grains in `n_image` [ny, nx] images:
+    -> xy, triples, gj, jj, the zeroed status tensor of `status_words` words and the workspace."""
     xy = torch.zeros(cap, 2, dtype=torch.float32, device=dev)
     triples = torch.zeros(cap, 3, dtype=torch.int32, device=dev)
     # The joint->grain table is built for the capacity, before n_joint is known on the host.  The columns the kernel does
@@ -133,12 +126,34 @@ def _vectorize(image, n_grain, grid, merge_radius, joint_capacity, boundary="per
     slots = torch.arange(cap, dtype=torch.int64, device=dev).repeat_interleave(3)
     gj = torch.stack([slots + n_grain, slots])
     jj = torch.full((2, 3 * cap), -1, dtype=torch.int64, device=dev)
-    status = torch.zeros(_lib.GGNN_JUNCTION_STATUS_WORDS + (4 if noflux else 0), dtype=torch.int64, device=dev)
-    if noflux:   # the order of grain_image(corner_grains=)
-        status[_lib.GGNN_JUNCTION_STATUS_WORDS:] = torch.stack([image[0, 0], image[0, -1], image[-1, 0], image[-1, -1]])
+    status = torch.zeros(status_words, dtype=torch.int64, device=dev)
     wy, wx = (ny + 1, nx + 1) if noflux else (ny, nx)   # the rows of windows, the windows of a row
-    words = wy * ((wx + _lib.GGNN_JUNCTION_SEGMENT - 1) // _lib.GGNN_JUNCTION_SEGMENT)
+    words = n_image * wy * ((wx + _lib.GGNN_JUNCTION_SEGMENT - 1) // _lib.GGNN_JUNCTION_SEGMENT)
     ws = torch.empty(max(words, 1), dtype=torch.int32, device=dev)
+    return xy, triples, gj, jj, status, ws
+
+
+def _vectorize(image, n_grain, grid, merge_radius, joint_capacity, boundary="periodic"):
+    """Every launch, no read-back: -> dict of the capacity-sized device arrays, the pixel counts, the joint->grain table
+    and the status words (no-flux: the four corner pixels behind them, so that one read-back fetches both)."""
+    be = default_backend()
+    _check_boundary(boundary)
+    noflux = boundary == "noflux"
+    image = _image_tensor(image, 2, IMAGE_2D)
+    if grid not in GRIDS:
+        raise _lib.GGNNError(f"grid must be 'cells' or 'points', got {grid!r}")
+    ny, nx = image.shape
+    if n_grain is None:
+        n_grain = int(image.max())   # (a read-back of its own: pass n_grain to avoid it)
+    n_grain, R = int(n_grain), int(merge_radius)
+    if n_grain < 1:
+        raise _lib.GGNNError("n_grain must be at least 1")
+    cap = 3 * n_grain + 16 if joint_capacity is None else int(joint_capacity)
+    _, counts = be.image_compare(image, None, n_grain)
+    W = _lib.GGNN_JUNCTION_STATUS_WORDS
+    xy, triples, gj, jj, status, ws = _arrays(image.device, n_grain, cap, 1, ny, nx, noflux, W + (4 if noflux else 0))
+    if noflux:   # the order of grain_image(corner_grains=)
+        status[W:] = torch.stack([image[0, 0], image[0, -1], image[-1, 0], image[-1, -1]])
     off, pitch = GRIDS[grid](nx)
     A = _lib.JunctionArgs()
     A.image, A.pixel_counts, A.xy, A.triples = _lib.ptr(image), _lib.ptr(counts), _lib.ptr(xy), _lib.ptr(triples)
@@ -202,10 +217,10 @@ def _graph(image, n_grain, grid, merge_radius, joint_capacity, strict, boundary=
         words = v["status"].tolist()
         status = dict(zip(STATUS_WORDS, words))
         v["corner_grains"] = tuple(words[len(STATUS_WORDS):]) if boundary == "noflux" else None
+        v["grain_counts"] = v["counts"][1:]   # (ggnn_image_compare's histogram is by id, from 0; a union's is by grain)
     else:   # the one-image union: the same bits, and the trace call exists for unions alone
         _check_boundary(boundary)
-        if not isinstance(image, torch.Tensor) or not image.is_cuda or image.dim() != 2:
-            raise _lib.GGNNError("image must be a [ny, nx] device tensor of grain ids (pixel p = grain p - 1)")
+        image = _image_tensor(image, 2, IMAGE_2D, "images")
         _check_links(links, max_trace, image.size(1), image.size(0))
         if n_grain is None:
             n_grain = int(image.max())   # (a read-back of its own: pass n_grain to avoid it)
@@ -214,13 +229,18 @@ def _graph(image, n_grain, grid, merge_radius, joint_capacity, strict, boundary=
         res, _ = _graphs_of(v, v["status"].tolist(), False)   # the one read-back
         status = res["status"][0]
         v["corner_grains"] = res["corner_grains"][0] if boundary == "noflux" else None
+        v["grain_counts"] = v["counts"]
     if strict and not status_is_valid(status, boundary):
         raise ValueError(f"the image is not a valid {boundary} grain structure: {status} (valid: overflow, n_invalid_pixels "
                          f"and n_open_pairs 0 and {EULER[boundary]}; joint_capacity {v['capacity']})")
-    n = min(status["n_joint"], v["capacity"])
+    return (*_cut(v, min(status["n_joint"], v["capacity"])), status, v)
+
+
+def _cut(v, n):
+    """The first n junctions of the capacity-sized arrays: -> xy [n, 2], triples [n, 3], the three edge lists [2, 3 n]."""
     gj = v["gj"][:, :3 * n].contiguous()
     ei = {EDGE_TYPES[0]: gj, EDGE_TYPES[1]: gj.flip(0).contiguous(), EDGE_TYPES[2]: v["jj"][:, :3 * n].contiguous()}
-    return v["xy"][:n].contiguous(), v["triples"][:n].contiguous(), ei, status, v
+    return v["xy"][:n].contiguous(), v["triples"][:n].contiguous(), ei
 
 
 def sample_from_image(image, theta_x, theta_z, G, R, span=None, patch_pixels=None, **kw):
@@ -240,7 +260,6 @@ def sample_from_image(image, theta_x, theta_z, G, R, span=None, patch_pixels=Non
     included (the rollout masks them itself); grain 0's row as the reference keeps it -- centre (0.5, 0.5), area 0, extraV 0 --
     and every other centre from ggnn_grain_centres in its GGNN_BC_NOFLUX mode.  The rollout's boundary step finds this
     state as it would leave it."""
-    from .generator import feature_rows
     from .synthetic import span_for
     theta_x, theta_z = np.asarray(theta_x, np.float64).ravel(), np.asarray(theta_z, np.float64).ravel()
     n_grain = int(kw.pop("n_grain", None) or len(theta_x))
@@ -252,28 +271,10 @@ def sample_from_image(image, theta_x, theta_z, G, R, span=None, patch_pixels=Non
                              kw.pop("joint_capacity", None), True, boundary, kw.pop("links", "unique"), kw.pop("max_trace", None))
     if kw:
         raise TypeError(f"sample_from_image: unknown keywords {sorted(kw)}")
-    be, dev = default_backend(), xy.device
     if span is None:
         span = span_for(G, R)
-    ny, nx = v["shape"]
-    fg, fj = feature_rows(theta_x, theta_z, xy.size(0), G, R, span)
-    x_grain, x_joint = torch.from_numpy(fg.astype(np.float32)).to(dev), torch.from_numpy(fj.astype(np.float32)).to(dev)
-    x_joint[:, :2] = xy
-    counts = v["counts"] if "n_image" in v else v["counts"][1:]   # (the one-image union of links="trace" counts grains, not ids)
-    x_grain[:, 3] = (counts.to(torch.float64) / float(patch_pixels or nx * ny)).to(torch.float32)
-    csr = v["csr"]
-    csr_jg = type(csr)(csr.rowptr[:n_grain + 1], csr.col, csr.perm, csr.row, csr.unit_ptr, csr.units, csr.E)
-    be.grain_centres(csr_jg, x_joint, x_grain, boundary=boundary)
-    if boundary == "noflux":   # the boundary grain's row as ggnn_noflux_boundary resets it
-        x_grain[0, :2] = 0.5
-        x_grain[0, 3:5] = 0.0
-        x_grain[0, 10] = 0.0
-    ea = {et: torch.zeros(ei[et].size(1), 1, dtype=torch.float32, device=dev) for et in EDGE_TYPES}
-    x = {"grain": x_grain, "joint": x_joint}
-    flags = torch.zeros(2, dtype=torch.int32, device=dev)
-    be.step_refresh(x_joint, x_grain, math.inf, flags,
-                    [(ei[et], x[et[0]], x[et[2]], ea[et]) for et in EDGE_TYPES])
-    return x, ei, ea
+    # the union of one trajectory: its boundary grain is grain 0, and strict has judged it valid
+    return _union_state(xy, ei, [0, xy.size(0)], v, v["grain_counts"], 0, True, [theta_x], [theta_z], [G], [R], span, patch_pixels)
 
 
 # ---- a stack of images into one union ------------------------------------------------------------------------------------
@@ -284,11 +285,10 @@ def _stack(images):
         if not images or any(not isinstance(i, torch.Tensor) or i.dim() != 2 or i.shape != images[0].shape for i in images):
             raise _lib.GGNNError("images must be equal-shaped [ny, nx] device tensors (one shape a stack)")
         images = torch.stack(list(images))
-    if not isinstance(images, torch.Tensor) or not images.is_cuda or images.dim() != 3 or images.size(0) < 1:
-        raise _lib.GGNNError("images must be a [B, ny, nx] device tensor of grain ids, or a list of [ny, nx] device tensors")
-    if images.dtype not in (torch.int16, torch.int32, torch.int64, torch.uint8):
-        raise _lib.GGNNError("images must hold integers")
-    return images.to(torch.int32).contiguous()
+    shape_text = "images must be a [B, ny, nx] device tensor of grain ids, or a list of [ny, nx] device tensors"
+    if isinstance(images, torch.Tensor) and images.dim() == 3 and images.size(0) < 1:
+        raise _lib.GGNNError(shape_text)
+    return _image_tensor(images, 3, shape_text, "images")
 
 
 def grain_offsets(n_grains, device):
@@ -323,20 +323,12 @@ def _vectorize_union(images, n_grains, grid, merge_radius, joint_capacity, bound
     n_total, R = off_host[-1], int(merge_radius)
     cap = 3 * n_total + 16 * B if joint_capacity is None else int(joint_capacity)
     counts = torch.empty(n_total, dtype=torch.int64, device=dev)       # (zeroed by the call)
-    xy = torch.zeros(cap, 2, dtype=torch.float32, device=dev)
-    triples = torch.zeros(cap, 3, dtype=torch.int32, device=dev)
-    slots = torch.arange(cap, dtype=torch.int64, device=dev).repeat_interleave(3)   # (spare rows: see _vectorize)
-    gj = torch.stack([slots + n_total, slots])
-    jj = torch.full((2, 3 * cap), -1, dtype=torch.int64, device=dev)
     W = _lib.GGNN_JUNCTION_STATUS_WORDS
     trace_words = B * W + B + 1 + (4 * B if noflux else 0) if trace else None
-    status = torch.zeros(B * W + B + 1 + (4 * B if noflux else 0) + (_lib.GGNN_TRACE_COUNTERS * B if trace else 0) + extra_words,
-                         dtype=torch.int64, device=dev)
+    xy, triples, gj, jj, status, ws = _arrays(dev, n_total, cap, B, ny, nx, noflux, B * W + B + 1 + (4 * B if noflux else 0)
+                                              + (_lib.GGNN_TRACE_COUNTERS * B if trace else 0) + extra_words)
     if noflux:   # per image, the order of grain_image(corner_grains=)
         status[B * W + B + 1:B * W + 5 * B + 1] = torch.stack([images[:, 0, 0], images[:, 0, -1], images[:, -1, 0], images[:, -1, -1]], 1).reshape(-1)
-    wy, wx = (ny + 1, nx + 1) if noflux else (ny, nx)
-    words = B * wy * ((wx + _lib.GGNN_JUNCTION_SEGMENT - 1) // _lib.GGNN_JUNCTION_SEGMENT)
-    ws = torch.empty(words, dtype=torch.int32, device=dev)
     off, pitch = GRIDS[grid](nx)
     A = _lib.JunctionTrajArgs()
     A.images, A.grain_off, A.pixel_counts, A.xy = _lib.ptr(images), _lib.ptr(off_dev), _lib.ptr(counts), _lib.ptr(xy)
@@ -403,10 +395,8 @@ def _graphs_of(v, words, strict):
                          + "; ".join(f"image {b}: {status[b]}" for b in bad)
                          + f" (valid: overflow, n_invalid_pixels and n_open_pairs 0 and {EULER[boundary]}; joint_capacity {cap} "
                            "for the union)")
-    n = joint_off[-1]
-    gj = v["gj"][:, :3 * n].contiguous()
-    ei = {EDGE_TYPES[0]: gj, EDGE_TYPES[1]: gj.flip(0).contiguous(), EDGE_TYPES[2]: v["jj"][:, :3 * n].contiguous()}
-    out = {"xy": v["xy"][:n].contiguous(), "triples": v["triples"][:n].contiguous(), "edge_index_dict": ei, "status": status,
+    xy, triples, ei = _cut(v, joint_off[-1])
+    out = {"xy": xy, "triples": triples, "edge_index_dict": ei, "status": status,
            "traj_offsets": {"grain": list(v["grain_off"]), "joint": joint_off}}
     if boundary == "noflux":
         out["corner_grains"], out["max_y"] = corners, v["max_y"]
@@ -472,7 +462,6 @@ def samples_from_images(images, theta_x, theta_z, G, R, span=None, patch_pixels=
 
     boundary="noflux": what `GrainRollout(..., boundary="noflux", traj_offsets=traj_offsets, max_y=image_max_y(nx, ny, grid))`
     takes; the row of every trajectory's boundary grain is reset as `sample_from_image` resets grain 0's."""
-    from .synthetic import span_for
     tx = [np.asarray(t, np.float64).ravel() for t in theta_x]
     tz = [np.asarray(t, np.float64).ravel() for t in theta_z]
     B = len(tx)
@@ -481,44 +470,54 @@ def samples_from_images(images, theta_x, theta_z, G, R, span=None, patch_pixels=
     n_grains = kw.pop("n_grains", None) or [len(t) for t in tx]
     if [int(n) for n in n_grains] != [len(t) for t in tx]:
         raise _lib.GGNNError("theta_x and theta_z must hold one angle per grain")
-    try:
-        Gs = [float(g) for g in np.broadcast_to(np.asarray(G, np.float64), (B,))]
-        Rs = [float(r) for r in np.broadcast_to(np.asarray(R, np.float64), (B,))]
-    except ValueError as exc:
-        raise _lib.GGNNError("G and R must be scalars or hold one value per image") from exc
-    if span is None:
-        spans = sorted({span_for(g, r) for g, r in zip(Gs, Rs)})
-        if len(spans) != 1:
-            raise _lib.GGNNError(f"the images' (G, R) give the frame spans {spans}: a union has one, pass span=")
-        span = spans[0]
+    Gs, Rs, _, span = _process_columns(B, G, R, None, span, "G and R", "image", "union")
     kw.pop("strict", None)
     boundary = kw.pop("boundary", "periodic")
     res, v = _graphs(images, n_grains, kw.pop("grid", "cells"), kw.pop("merge_radius", 2), kw.pop("joint_capacity", None),
                      True, boundary, kw.pop("links", "unique"), kw.pop("max_trace", None))
     if kw:
         raise TypeError(f"samples_from_images: unknown keywords {sorted(kw)}")
-    x, ei, ea = _union_state(res, v, tx, tz, Gs, Rs, span, patch_pixels)
+    x, ei, ea = _union_state(res["xy"], res["edge_index_dict"], res["traj_offsets"]["joint"], v, v["counts"],
+                             v["grain_off_dev"][:-1], True, tx, tz, Gs, Rs, span, patch_pixels)   # (strict has judged it valid)
     return x, ei, ea, res["traj_offsets"]
 
 
-def _union_state(res, v, tx, tz, Gs, Rs, span, patch_pixels):
-    """samples_from_images' (x_dict, edge_index_dict, edge_attr) of a vectorised union.  A joint->joint column without a
-    destination (strict=False: an invalid image's) is measured as a loop on its source, length 0."""
+def _process_columns(n, G, R, z, span, names, noun, whole):
+    """The process columns of n images (or frames: `noun`) of one union (or sequence: `whole`): -> G, R and z (or None) as n
+    floats each, and the one frame span (None: `span_for(G_b, R_b)`, which must agree)."""
+    from .synthetic import span_for
+
+    def column(c):
+        return [float(a) for a in np.broadcast_to(np.asarray(c, np.float64), (n,))]
+    try:
+        Gs, Rs, zs = column(G), column(R), (None if z is None else column(z))
+    except ValueError as exc:
+        raise _lib.GGNNError(f"{names} must be scalars or hold one value per {noun}") from exc
+    if span is None:
+        spans = sorted({span_for(g, r) for g, r in zip(Gs, Rs)})
+        if len(spans) != 1:
+            raise _lib.GGNNError(f"the {noun}s' (G, R) give the frame spans {spans}: a {whole} has one, pass span=")
+        span = spans[0]
+    return Gs, Rs, zs, span
+
+
+def _union_state(xy, ei, joint_off, v, counts, first, valid, tx, tz, Gs, Rs, span, patch_pixels):
+    """samples_from_images' (x_dict, edge_index_dict, edge_attr) of a vectorised union: its junctions xy, its edge lists and
+    joint offsets; of v its shape, boundary, grains and joint->grain table; counts: the pixels per union grain; first: the
+    index of every trajectory's first grain (its boundary grain when there are walls).  Not `valid`: a joint->joint column
+    without a destination (strict=False: an invalid image's) is measured as a loop on its source, length 0."""
     from .generator import feature_rows
-    B, boundary = v["n_image"], v["boundary"]
-    be, xy, ei = default_backend(), res["xy"], res["edge_index_dict"]
-    dev, oj = xy.device, res["traj_offsets"]["joint"]
+    be, dev, boundary = default_backend(), xy.device, v["boundary"]
     ny, nx = v["shape"]
-    rows = [feature_rows(tx[b], tz[b], oj[b + 1] - oj[b], Gs[b], Rs[b], span) for b in range(B)]
+    rows = [feature_rows(tx[b], tz[b], joint_off[b + 1] - joint_off[b], Gs[b], Rs[b], span) for b in range(len(tx))]
     x_grain = torch.from_numpy(np.concatenate([fg for fg, _ in rows]).astype(np.float32)).to(dev)
     x_joint = torch.from_numpy(np.concatenate([fj for _, fj in rows]).astype(np.float32)).to(dev)
     x_joint[:, :2] = xy
-    x_grain[:, 3] = (v["counts"].to(torch.float64) / float(patch_pixels or nx * ny)).to(torch.float32)
+    x_grain[:, 3] = (counts.to(torch.float64) / float(patch_pixels or nx * ny)).to(torch.float32)
     csr, n_total = v["csr"], v["n_grain"]
     csr_jg = type(csr)(csr.rowptr[:n_total + 1], csr.col, csr.perm, csr.row, csr.unit_ptr, csr.units, csr.E)
     be.grain_centres(csr_jg, x_joint, x_grain, boundary=boundary)
-    if boundary == "noflux":   # every trajectory's boundary grain as ggnn_noflux_boundary_traj resets it
-        first = v["grain_off_dev"][:-1]
+    if boundary == "noflux":   # every trajectory's boundary grain as ggnn_noflux_boundary(_traj) resets it
         x_grain[first, :2] = 0.5
         x_grain[first, 3:5] = 0.0
         x_grain[first, 10] = 0.0
@@ -526,7 +525,7 @@ def _union_state(res, v, tx, tz, Gs, Rs, span, patch_pixels):
     x = {"grain": x_grain, "joint": x_joint}
     flags = torch.zeros(2, dtype=torch.int32, device=dev)
     measured = dict(ei)
-    if not all(status_is_valid(s, boundary) for s in res["status"]):
+    if not valid:
         jj = ei[EDGE_TYPES[2]]
         measured[EDGE_TYPES[2]] = torch.stack([jj[0], torch.where(jj[1] >= 0, jj[1], jj[0])])
     be.step_refresh(x_joint, x_grain, math.inf, flags,
@@ -644,7 +643,6 @@ def frames_to_samples(frames, theta_x, theta_z, G, R, span=None, patch_pixels=No
     ones that carry the classifier's positive labels; report["status"] carries n_traced, n_trace_failed and n_trace_overflow
     per frame.  The tracker itself is the same: the two junctions of a lens share a triple, so they are counted in n_ambiguous
     and stay unmatched (mask 0), and the links around them are labelled by the rule above."""
-    from .synthetic import span_for
     tx, tz = np.asarray(theta_x, np.float64).ravel(), np.asarray(theta_z, np.float64).ravel()
     n_grain = len(tx)
     if n_grain < 1 or len(tz) != n_grain:
@@ -653,24 +651,15 @@ def frames_to_samples(frames, theta_x, theta_z, G, R, span=None, patch_pixels=No
     _check_links(links, max_trace, 1, 1)
     frames = _stack(frames)
     T = frames.size(0)
-    try:
-        Gs = [float(g) for g in np.broadcast_to(np.asarray(G, np.float64), (T,))]
-        Rs = [float(r) for r in np.broadcast_to(np.asarray(R, np.float64), (T,))]
-        zs = None if z is None else [float(a) for a in np.broadcast_to(np.asarray(z, np.float64), (T,))]
-    except ValueError as exc:
-        raise _lib.GGNNError("G, R and z must be scalars or hold one value per frame") from exc
-    if span is None:
-        spans = sorted({span_for(g, r) for g, r in zip(Gs, Rs)})
-        if len(spans) != 1:
-            raise _lib.GGNNError(f"the frames' (G, R) give the frame spans {spans}: a sequence has one, pass span=")
-        span = spans[0]
+    Gs, Rs, zs, span = _process_columns(T, G, R, z, span, "G, R and z", "frame", "sequence")
     v = _track(frames, n_grain, grid, merge_radius, joint_capacity, boundary, extra_volume, patch_pixels, links=links,
                max_trace=max_trace)
     words = v["status"].tolist()                      # the one read-back
     res, _ = _graphs_of(v, words, False)
-    x, ei, ea = _union_state(res, v, [tx] * T, [tz] * T, Gs, Rs, span, patch_pixels)
     oj, n = res["traj_offsets"]["joint"], res["traj_offsets"]["joint"][-1]
     valid = [status_is_valid(s, boundary) for s in res["status"]]
+    x, ei, ea = _union_state(res["xy"], res["edge_index_dict"], oj, v, v["counts"], v["grain_off_dev"][:-1], all(valid),
+                             [tx] * T, [tz] * T, Gs, Rs, span, patch_pixels)
     x["grain"][:, 4] = v["hist_grain"][:, 1]
     x["grain"][:, 10] = v["hist_grain"][:, 0]
     x["joint"][:, 6:8] = v["hist_joint"][:n]

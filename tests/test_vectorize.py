@@ -337,7 +337,9 @@ def test_kernels_against_the_restatement_on_hand_made_images(name):
 
 @pytest.mark.gpu
 def test_nothing_is_written_beyond_the_capacity_or_the_junctions():
-    """The entry point itself on guarded arrays: capacity one short of the 32 junctions, then four to spare."""
+    """The two entry points themselves on guarded arrays: capacity one short of the 32 junctions, then four to spare.  The
+    links and scan kernels share their code with the stack form, which writes joint_off behind the status rows: the four
+    words behind the one row keep their guard through both calls."""
     image, n_grain, _, _ = case("plain")
     lib, dev_image = _lib.load(), torch.from_numpy(image).to(DEV)
     from graingraphnn_amd.backend import default_backend
@@ -361,6 +363,19 @@ def test_nothing_is_written_beyond_the_capacity_or_the_junctions():
         rows = gj[:6 * cap].view(2, 3 * cap)
         assert np.array_equal(rows[:, :3 * n].cpu().numpy(), v["gj"])
         assert bool((rows[:, 3 * n:] == -7).all()) and bool((gj[6 * cap:] == -7).all())
+        # ggnn_junction_links on the same guarded status, the table built as _vectorize builds it (spare rows past n)
+        slots = torch.arange(cap, dtype=torch.int64, device=DEV).repeat_interleave(3)
+        table = torch.stack([slots + n_grain, slots])
+        table[:, :3 * n] = rows[:, :3 * n]
+        csr = default_backend().build_csr_batch([(table.flip(0).contiguous(), cap, n_grain + cap)], check=False)[0]
+        jj = torch.full((6 * cap + 16,), -7, dtype=torch.int64, device=DEV)
+        L = _lib.LinkArgs(triples.data_ptr(), csr.rowptr.data_ptr(), csr.col.data_ptr(), jj.data_ptr(), status.data_ptr(),
+                          n_grain, cap, csr.col.numel())
+        _lib.check(lib.ggnn_junction_links(ctypes.byref(L), _lib.current_stream()), "ggnn_junction_links")
+        assert dict(zip(vc.STATUS, status[:7].tolist())) == v["status"] and bool((status[7:] == -7).all())
+        cols = jj[:6 * cap].view(2, 3 * cap)
+        assert np.array_equal(cols[:, :3 * n].cpu().numpy(), v["jj"])
+        assert bool((cols[:, 3 * n:] == -7).all()) and bool((jj[6 * cap:] == -7).all())
 
 
 @pytest.mark.gpu

@@ -517,7 +517,8 @@ def test_kernels_on_rasters_of_noflux_40(size):
 
 @pytest.mark.gpu
 def test_nothing_is_written_beyond_the_capacity_or_the_junctions():
-    """The entry point itself on guarded arrays: capacity one short of the 10 junctions (overflow set), then four to spare."""
+    """The two entry points themselves on guarded arrays: capacity one short of the 10 junctions (overflow set), then four to
+    spare; the four words behind the one status row keep their guard through both calls."""
     image, n_grain = walls_image(24, 40)
     lib, dev_image = _lib.load(), torch.from_numpy(image).to(DEV)
     from graingraphnn_amd.backend import default_backend
@@ -542,6 +543,19 @@ def test_nothing_is_written_beyond_the_capacity_or_the_junctions():
         rows = gj[:6 * cap].view(2, 3 * cap)
         assert np.array_equal(rows[:, :3 * n].cpu().numpy(), v["gj"])
         assert bool((rows[:, 3 * n:] == -7).all()) and bool((gj[6 * cap:] == -7).all())
+        # ggnn_junction_links on the same guarded status, the table built as _vectorize builds it (spare rows past n)
+        slots = torch.arange(cap, dtype=torch.int64, device=DEV).repeat_interleave(3)
+        table = torch.stack([slots + n_grain, slots])
+        table[:, :3 * n] = rows[:, :3 * n]
+        csr = default_backend().build_csr_batch([(table.flip(0).contiguous(), cap, n_grain + cap)], check=False)[0]
+        jj = torch.full((6 * cap + 16,), -7, dtype=torch.int64, device=DEV)
+        L = _lib.LinkArgs(triples.data_ptr(), csr.rowptr.data_ptr(), csr.col.data_ptr(), jj.data_ptr(), status.data_ptr(),
+                          n_grain, cap, csr.col.numel())
+        _lib.check(lib.ggnn_junction_links(ctypes.byref(L), _lib.current_stream()), "ggnn_junction_links")
+        assert dict(zip(vn.STATUS, status[:7].tolist())) == v["status"] and bool((status[7:] == -7).all())
+        cols = jj[:6 * cap].view(2, 3 * cap)
+        assert np.array_equal(cols[:, :3 * n].cpu().numpy(), v["jj"])
+        assert bool((cols[:, 3 * n:] == -7).all()) and bool((jj[6 * cap:] == -7).all())
         A.workspace_bytes = 4 * 24                                                  # enough for the periodic grid only
         assert lib.ggnn_image_junctions(ctypes.byref(A), _lib.current_stream()) == -1
 

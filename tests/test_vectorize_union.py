@@ -315,6 +315,12 @@ def test_every_trajectory_equals_the_single_image_call(boundary, ny, nx):
     # B = 1
     for t in range(3):
         check_members(images[t:t + 1], n_grains[t:t + 1], boundary)
+        # ... and at the entry points: the one-image union's words and counts are the single call's
+        one = vz._vectorize_union(dev[t:t + 1], n_grains[t:t + 1], "cells", 2, None, boundary)
+        own = vz._vectorize(dev[t], n_grains[t], "cells", 2, None, boundary)
+        words, seven = one["status"].tolist(), own["status"][:7].tolist()
+        assert words[:7] == seven and words[7:9] == [0, seven[0]], (boundary, t, words, seven)     # the row, then joint_off
+        assert own["counts"].numel() == n_grains[t] + 1 and torch.equal(one["counts"], own["counts"][1:]), (boundary, t)
     if boundary == "noflux":   # all three are valid: strict passes
         assert vz.graphs_from_images(dev, n_grains, boundary=boundary)["status"] == res["status"]
 
