@@ -118,12 +118,8 @@ def _csr_unions(unions, n):
     arr, keep = (_lib.CsrUnion * n)(), []
     for a, u in zip(arr, unions):
         offs = [t for t in (u or ()) if t is not None]
-        for t in offs:
-            if t.dtype != torch.int64 or t.dim() != 1 or t.numel() < 2 or not t.is_contiguous() or not t.is_cuda \
-                    or t.numel() != offs[0].numel():
-                raise _lib.GGNNError("union offsets must be contiguous int64 [n_traj + 1] device tensors of one length")
         if offs:
-            a.src_off, a.dst_off, a.n_traj = ptr(u[0]), ptr(u[1]), offs[0].numel() - 1
+            a.src_off, a.dst_off, a.n_traj = ptr(u[0]), ptr(u[1]), _offsets(offs, "union offsets")
             keep += offs
     return arr, tuple(keep)
 
@@ -148,6 +144,16 @@ def _f32c(t, name):
     if t.dtype != torch.float32 or not t.is_contiguous():
         raise _lib.GGNNError(f"{name} must be a contiguous float32 tensor")
     return t
+
+
+def _offsets(tensors, name, entries=None):
+    """The offsets of a disjoint union (csrc/segments.h): contiguous int64 [n_traj + 1] device tensors, n_traj >= 1, all of
+    one length -- of `entries` where the caller knows how many there must be; -> n_traj."""
+    want = tensors[0].numel() if entries is None else entries
+    for t in tensors:
+        if not t.is_cuda or t.dtype != torch.int64 or t.dim() != 1 or not t.is_contiguous() or t.numel() < 2 or t.numel() != want:
+            raise _lib.GGNNError(f"{name} must be contiguous int64 [n_traj + 1] on the device, of one length")
+    return want - 1
 
 
 def _check_einfo(einfo, E):
@@ -1190,14 +1196,11 @@ class HipBackend:
             raise _lib.GGNNError("domain_factor > 1 needs the domain_offset of scale_feature_patchs")
         if traj_offsets is not None:
             og, oj = traj_offsets
-            for off in (og, oj):
-                if off.dtype != torch.int64 or off.dim() != 1 or off.numel() != og.numel() or og.numel() < 2 \
-                        or not off.is_contiguous():
-                    raise _lib.GGNNError("traj_offsets must be two contiguous int64 [n_traj + 1] tensors")
+            n_traj = _offsets((og, oj), "traj_offsets")
             check(self.lib.ggnn_noflux_boundary_traj(ptr(csr_jg.rowptr), ptr(csr_jg.col), ptr(x_joint), x_joint.size(0),
                                                      x_joint.stride(0), ptr(domain_offset), float(domain_factor),
                                                      float(max_y), ptr(x_grain), x_grain.stride(0), x_grain.size(1),
-                                                     ptr(joints_before), ptr(og), ptr(oj), og.numel() - 1,
+                                                     ptr(joints_before), ptr(og), ptr(oj), n_traj,
                                                      _lib.current_stream()), "ggnn_noflux_boundary_traj")
             return
         check(self.lib.ggnn_noflux_boundary(ptr(csr_jg.rowptr), ptr(csr_jg.col), ptr(x_joint), x_joint.size(0),
@@ -1220,8 +1223,7 @@ class HipBackend:
                 _f32c(t, name)
                 if t.numel() != n:
                     raise _lib.GGNNError(f"{name} must have one element per grain")
-        if traj_offsets.dtype != torch.int64 or traj_offsets.numel() < 2 or not traj_offsets.is_contiguous():
-            raise _lib.GGNNError("traj_offsets must be a contiguous int64 [n_traj + 1]")
+        n_traj = _offsets((traj_offsets,), "traj_offsets")
         if live_grain is not None and (live_grain.dtype != torch.int32 or live_grain.numel() != n):
             raise _lib.GGNNError("live_grain must be int32 [n_grain]")
         for w in (state_in["layer"], state_out["layer"], sync_word, flags):
@@ -1231,14 +1233,14 @@ class HipBackend:
             _f32c(history, "history")
             if history.numel() != (int(capacity) + 1) * n:
                 raise _lib.GGNNError("history must be [capacity + 1, n_grain]")
-        if area_sum is not None and (area_sum.dtype != torch.float32 or area_sum.numel() != traj_offsets.numel() - 1):
+        if area_sum is not None and (area_sum.dtype != torch.float32 or area_sum.numel() != n_traj):
             raise _lib.GGNNError("area_sum must be fp32 [n_traj]")
         A = _lib.QoiArgs()
         A.x_grain, A.live_grain, A.traj_offsets, A.area0 = ptr(x_grain), ptr(live_grain), ptr(traj_offsets), ptr(area0)
         A.a_prev, A.T_in, A.layer_in = ptr(state_in["a"]), ptr(state_in["T"]), ptr(state_in["layer"])
         A.a_cur, A.T_out, A.e_cur, A.layer_out = ptr(state_out["a"]), ptr(state_out["T"]), ptr(state_out["e"]), ptr(state_out["layer"])
         A.V0, A.history, A.area_sum, A.sync_word, A.flags = ptr(V0), ptr(history), ptr(area_sum), ptr(sync_word), ptr(flags)
-        A.ldx_grain, A.n_grain, A.n_traj, A.capacity = x_grain.stride(0), n, traj_offsets.numel() - 1, int(capacity)
+        A.ldx_grain, A.n_grain, A.n_traj, A.capacity = x_grain.stride(0), n, n_traj, int(capacity)
         A.domain_factor, A.s, A.delta_h = (float(c) for c in const)
         A.init = 1 if init else 0
         check(self.lib.ggnn_qoi_accumulate(ctypes.byref(A), _lib.current_stream()), "ggnn_qoi_accumulate")
@@ -1284,11 +1286,7 @@ class HipBackend:
                 raise _lib.GGNNError("domain_offset must be [n_joint, 2]")
         elif domain_factor > 1:
             raise _lib.GGNNError("domain_factor > 1 needs the domain_offset of scale_feature_patchs")
-        n_traj = 1
-        if traj_grain_off is not None:
-            if traj_grain_off.dtype != torch.int64 or traj_grain_off.numel() < 2 or not traj_grain_off.is_contiguous():
-                raise _lib.GGNNError("traj_grain_off must be a contiguous int64 [n_traj + 1]")
-            n_traj = traj_grain_off.numel() - 1
+        n_traj = 1 if traj_grain_off is None else _offsets((traj_grain_off,), "traj_grain_off")
         for w in (layer_in, layer_out, sync_word, flags):
             if w is not None and (w.dtype != torch.int32 or w.numel() < 1):
                 raise _lib.GGNNError("layer_in / layer_out / sync_word / flags must be int32 words")
@@ -1374,11 +1372,7 @@ class HipBackend:
                 raise _lib.GGNNError(f"a job's layer must lie in 1..{layers}, got {k}")
             if not 0.0 <= c <= 1.0:
                 raise _lib.GGNNError(f"a job's coefficient must lie in [0, 1], got {c}")
-        n_traj = 1
-        if traj_grain_off is not None:
-            if traj_grain_off.dtype != torch.int64 or traj_grain_off.numel() < 2 or not traj_grain_off.is_contiguous():
-                raise _lib.GGNNError("traj_grain_off must be a contiguous int64 [n_traj + 1]")
-            n_traj = traj_grain_off.numel() - 1
+        n_traj = 1 if traj_grain_off is None else _offsets((traj_grain_off,), "traj_grain_off")
         dev = rowptr.device
         if out is None:
             out = self.polygon_arena(n_grain, E_cap, len(jobs) - 1, dev)
@@ -1432,11 +1426,7 @@ class HipBackend:
         g0, g1 = (0, n_grain) if grains is None else (int(grains[0]), int(grains[1]))
         if not 0 <= g0 <= g1 <= n_grain:
             raise _lib.GGNNError(f"grains must be a range inside 0..{n_grain}")
-        n_traj = 1
-        if traj_grain_off is not None:
-            if traj_grain_off.dtype != torch.int64 or traj_grain_off.numel() < 2 or not traj_grain_off.is_contiguous():
-                raise _lib.GGNNError("traj_grain_off must be a contiguous int64 [n_traj + 1]")
-            n_traj = traj_grain_off.numel() - 1
+        n_traj = 1 if traj_grain_off is None else _offsets((traj_grain_off,), "traj_grain_off")
         if corner_grains is not None:
             if bc != _lib.BC_NOFLUX:
                 raise _lib.GGNNError("corner_grains belong to a no-flux image")
@@ -1503,9 +1493,8 @@ class HipBackend:
         if traj_joint_off is None:
             if table.size(1) != 1:
                 raise _lib.GGNNError("a table of several trajectories needs traj_joint_off")
-        elif traj_joint_off.dtype != torch.int64 or traj_joint_off.numel() != table.size(1) + 1 \
-                or not traj_joint_off.is_contiguous():
-            raise _lib.GGNNError("traj_joint_off must be a contiguous int64 [n_traj + 1]")
+        else:
+            _offsets((traj_joint_off,), "traj_joint_off", table.size(1) + 1)
         for w in (step_in, step_out, sync_word):
             if w.dtype != torch.int32 or w.numel() < 1:
                 raise _lib.GGNNError("step_in / step_out / sync_word must be int32 words")
@@ -1517,13 +1506,11 @@ class HipBackend:
         """(volume [n_grain], size [n_grain], d_mu [n_traj], d_std [n_traj], counts [n_traj, n_edges - 1] int32 or None) of
         ggnn_qoi_finalize; bin_edges: ascending fp32 [n_edges] on the device, or None."""
         _require_cuda(V0, T, e, traj_offsets, bin_edges)
-        n, n_traj = V0.numel(), traj_offsets.numel() - 1
+        n, n_traj = V0.numel(), _offsets((traj_offsets,), "traj_offsets")
         for t, name in ((V0, "V0"), (T, "T"), (e, "e")):
             _f32c(t, name)
             if t.numel() != n:
                 raise _lib.GGNNError(f"{name} must have one element per grain")
-        if traj_offsets.dtype != torch.int64 or n_traj < 1 or not traj_offsets.is_contiguous():
-            raise _lib.GGNNError("traj_offsets must be a contiguous int64 [n_traj + 1]")
         dev = V0.device
         volume, size = torch.empty(n, device=dev), torch.empty(n, device=dev)
         d_mu, d_std = torch.empty(n_traj, device=dev), torch.empty(n_traj, device=dev)
@@ -1560,10 +1547,7 @@ class HipBackend:
         totals; ended: int32 [n_traj] or None, a non-zero word keeps a trajectory's candidates out of both."""
         _require_cuda(grain_area, live_grain, edge_event, edge_index_jj, traj_grain_off, traj_joint_off, counts, flags, ended,
                       range_word, E_dev)
-        n_traj = traj_grain_off.numel() - 1
-        for off in (traj_grain_off, traj_joint_off):
-            if off.dtype != torch.int64 or off.numel() != n_traj + 1 or n_traj < 1 or not off.is_contiguous():
-                raise _lib.GGNNError("traj_grain_off / traj_joint_off must be contiguous int64 [n_traj + 1]")
+        n_traj = _offsets((traj_grain_off, traj_joint_off), "traj_grain_off / traj_joint_off")
         if live_grain.dtype != torch.int32 or flags.dtype != torch.int32 or flags.numel() < (2 if range_word is None else 3):
             raise _lib.GGNNError("live_grain / flags must be int32 (flags: two words, three with a range word)")
         if counts.dtype != torch.int32 or counts.numel() != 2 * n_traj or not counts.is_contiguous():

@@ -5,6 +5,7 @@
 //   ggnn_reverse_slots  = the forward CSR slot of every reverse (source-grouped) CSR slot of tables that keep only the
 //                         first E_kept slots (masked builds: the pad edges of such a batch are in no table).
 #include "common.h"
+#include "segments.h"
 
 namespace ggnn {
 
@@ -14,17 +15,6 @@ constexpr int CO_MAX_JOBS = GGNN_COLLATE_MAX_ROWS + GGNN_COLLATE_MAX_LISTS;
 struct CollatePlan {
   int blk_off[CO_MAX_JOBS + 1];   // first workgroup of every job: the row arrays, then the lists
 };
-
-// the slot whose rows hold item r: the last k with pre[k] <= r (r < pre[B]; slots of empty samples have equal bounds)
-__device__ __forceinline__ int co_slot(const int64_t* pre, int B, int64_t r) {
-  int lo = 0, hi = B;
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (pre[mid] <= r) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
 
 // Every workgroup reads the cursor, the batch's sample ids and the sizes of those samples for the (at most three) kinds its
 // job follows, and lays the batch's prefix sums into LDS: at most 3 x 64 loads of 8 bytes per workgroup, from tables that
@@ -72,7 +62,7 @@ __global__ __launch_bounds__(CO_THREADS) void collate_batch_kernel(const ggnn_co
       if (i >= n_all) break;
       uint32_t v = R.pad_word;
       if (i < n_real) {
-        const int k = co_slot(s_pre[0], B, i / R.words);
+        const int k = seg_of(s_pre[0], B, i / R.words);   // the slot whose rows hold the item (i < n_real: inside the batch)
         v = R.src[s_base[0][k] * R.words + (i - s_pre[0][k] * R.words)];
       }
       R.dst[i] = v;
@@ -89,7 +79,7 @@ __global__ __launch_bounds__(CO_THREADS) void collate_batch_kernel(const ggnn_co
       if (e >= L.cap) break;
       int64_t s = L.pad_src, d = L.pad_dst;   // a pad edge: the two reserved rows, which the masked tables skip
       if (e < n_real) {
-        const int k = co_slot(s_pre[0], B, e);
+        const int k = seg_of(s_pre[0], B, e);
         const int64_t at = s_base[0][k] + (e - s_pre[0][k]);
         s = L.src[at] + s_pre[1][k];
         d = L.src[L.ld_src + at] + s_pre[2][k];

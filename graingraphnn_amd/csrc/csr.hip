@@ -4,6 +4,7 @@
 // used at periodGATconv.py:174-175.  Deterministic: inside a row the slots are ordered by
 // original edge id, whatever order the atomics happened to land in.
 #include "common.h"
+#include "segments.h"
 
 namespace ggnn {
 
@@ -20,23 +21,12 @@ struct CsrBatch {
   ggnn_csr_mask m[CSR_MAX_BATCH];   // (all -1 / NULL without masks)
   ggnn_csr_union u[CSR_MAX_BATCH];  // (all NULL for ggnn_build_csr_batch: skip_src / skip_dst are global indices)
 };
-// a node's index inside its trajectory of a disjoint union: off [n_traj + 1] rises from 0 to the node count, the node
-// belongs to the last trajectory whose offset is <= node (equal offsets are empty trajectories).  At most a few hundred
-// offsets, searched once per masked edge and topological event: read from global memory (they stay in the caches).
-__device__ __forceinline__ int64_t csr_local(const int64_t* __restrict__ off, int64_t n_traj, int64_t node) {
-  int64_t lo = 0, hi = n_traj;
-  while (hi - lo > 1) {
-    const int64_t mid = lo + ((hi - lo) >> 1);
-    if (off[mid] <= node) lo = mid;
-    else hi = mid;
-  }
-  return node - off[lo];
-}
 // an edge of a masked list (ggnn_csr_mask) that the tables leave out; with a union (ggnn_csr_union) the skipped index is
-// the node's LOCAL one on the sides that are split
+// the node's LOCAL one on the sides that are split (seg_local: at most a few hundred offsets, searched once per masked edge
+// and topological event, read from global memory -- they stay in the caches)
 __device__ __forceinline__ bool csr_skipped(const ggnn_csr_mask& M, const ggnn_csr_union& U, int64_t s, int64_t d) {
-  if (M.skip_src >= 0 && (U.src_off ? csr_local(U.src_off, U.n_traj, s) : s) == M.skip_src) return true;
-  return M.skip_dst >= 0 && (U.dst_off ? csr_local(U.dst_off, U.n_traj, d) : d) == M.skip_dst;
+  if (M.skip_src >= 0 && (U.src_off ? seg_local(U.src_off, (int)U.n_traj, s) : s) == M.skip_src) return true;
+  return M.skip_dst >= 0 && (U.dst_off ? seg_local(U.dst_off, (int)U.n_traj, d) : d) == M.skip_dst;
 }
 __device__ __forceinline__ int32_t* csr_counts(const ggnn_csr_args& P) { return reinterpret_cast<int32_t*>(P.workspace); }
 __device__ __forceinline__ int32_t* csr_cursor(const ggnn_csr_args& P) { return csr_counts(P) + P.n_dst + 1; }
@@ -185,8 +175,8 @@ extern "C" int ggnn_build_csr_batch_traj(const ggnn_csr_args* problems, const gg
     B.m[k] = ggnn_csr_mask{-1, -1, nullptr};
     B.u[k] = ggnn_csr_union{nullptr, nullptr, 0};
     if (k >= n_problems) continue;
-    if (unions && (unions[k].src_off || unions[k].dst_off)) {
-      if (unions[k].n_traj < 1 || unions[k].n_traj > (1 << 29)) return GGNN_EINVAL;
+    if (const int64_t* off = !unions ? nullptr : unions[k].src_off ? unions[k].src_off : unions[k].dst_off) {   // a split list
+      if (!seg_union_ok(off, unions[k].n_traj, false)) return GGNN_EINVAL;
       B.u[k] = unions[k];
     }
     if (masks) {

@@ -130,7 +130,7 @@ extern "C" int ggnn_interp_polygons(const ggnn_interp_args* args, ggnn_stream_t 
   if (A.capacity < 0 || A.capacity >= INT32_MAX || A.layers < 1 || A.layers > A.capacity) return GGNN_EINVAL;
   if (A.n_jobs < 1 || A.n_jobs > GGNN_INTERP_MAX_JOBS) return GGNN_EINVAL;
   if (A.boundary == GGNN_BC_NOFLUX && !(A.max_y > 0.0f)) return GGNN_EINVAL;
-  if (A.traj_grain_off ? A.n_traj < 1 || A.n_traj > (1 << 29) : A.n_traj != 1) return GGNN_EINVAL;
+  if (!seg_union_ok(A.traj_grain_off, A.n_traj, true)) return GGNN_EINVAL;
   InterpJobs J = {};
   for (int64_t i = 0; i < A.n_jobs; ++i) {
     const double c = A.job_coeff[i];

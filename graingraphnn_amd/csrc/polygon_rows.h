@@ -4,6 +4,7 @@
 // and the two row paths.
 #pragma once
 #include "common.h"
+#include "segments.h"
 
 namespace ggnn {
 
@@ -161,17 +162,6 @@ __device__ void poly_row_wave(const PolyIn& I, const PolyOut& O, int64_t g, int 
   }
 }
 
-// Is `g` the first grain of a trajectory that has grains (the no-flux boundary grain of its trajectory)?
-__device__ __forceinline__ bool poly_boundary_grain(const int64_t* __restrict__ off, int64_t n_traj, int64_t g) {
-  if (off == nullptr) return g == 0;
-  int64_t a = 0, z = n_traj;   // the last t in [0, n_traj] with off[t] <= g (off[0] = 0)
-  while (a < z) {
-    const int64_t m = (a + z + 1) >> 1;
-    if (off[m] <= g) a = m; else z = m - 1;
-  }
-  return a < n_traj && off[a] == g;
-}
-
 // The grains of one block, POLY_GRAINS of them from blockIdx.x * POLY_GRAINS: their rows of (rowptr, I.col) into O, and a
 // copy of rowptr into rowptr_out.  Every thread of the block must call it.
 template <bool PERIODIC>
@@ -190,7 +180,7 @@ __device__ __forceinline__ void poly_block_rows(const PolyIn& I, const PolyOut& 
       rowptr_out[g] = r0;
       if (g == n_grain - 1) rowptr_out[g + 1] = r1;
     }
-    if (!PERIODIC) reversed = poly_boundary_grain(traj_grain_off, n_traj, g);   // graph_datastruct.py:715-716
+    if (!PERIODIC) reversed = seg_is_first(traj_grain_off, (int)n_traj, g);   // a boundary grain, graph_datastruct.py:715-716
     if (n <= 1 && l == 0) poly_short_row(I, O, g, p0, n);
   }
   // -- rows of 2..16 junctions: lane l of the group holds vertex l ------------------------------------------------------

@@ -94,7 +94,7 @@ extern "C" int ggnn_grain_polygons(const ggnn_polygon_args* args, ggnn_stream_t 
     return GGNN_EINVAL;
   if (A.n_joint <= 0 || A.n_grain <= 0 || A.ldx_joint < 2 || A.E_cap < 0 || A.E_cap >= INT32_MAX) return GGNN_EINVAL;
   if (!(A.domain_factor >= 1.0f) || A.capacity < 0 || A.capacity >= INT32_MAX) return GGNN_EINVAL;
-  if (A.traj_grain_off ? A.n_traj < 1 || A.n_traj > (1 << 29) : A.n_traj != 1) return GGNN_EINVAL;
+  if (!seg_union_ok(A.traj_grain_off, A.n_traj, true)) return GGNN_EINVAL;
   if (A.layer_out && (!A.sync_word || !A.flags)) return GGNN_EINVAL;
   const int64_t nblk = (A.n_grain + POLY_GRAINS - 1) / POLY_GRAINS;
   if (nblk >= INT32_MAX) return GGNN_EINVAL;

@@ -39,6 +39,7 @@ __device__ __forceinline__ double block_sum_d(double v, double* s_red) {
 // The trajectory and the 256-grain chunk of it that block `b` works on: chunks are counted from each trajectory's first
 // grain, trajectory after trajectory.  Returns false for a block behind the last chunk (the launch is sized by an upper
 // bound).  Offsets outside [0, n_grain] are clamped: nothing is ever addressed outside the arrays.
+// (A walk over the trajectories' chunk counts, not segments.h's "which segment holds node v".)
 __device__ __forceinline__ bool qoi_block_range(const int64_t* __restrict__ off, int64_t n_traj, int64_t n_grain, int64_t b,
                                                 int64_t& traj, int64_t& lo, int64_t& n, int64_t& chunk) {
   for (int64_t t = 0; t < n_traj; ++t) {

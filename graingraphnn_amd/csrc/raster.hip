@@ -34,6 +34,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "segments.h"
 
 namespace ggnn {
 
@@ -99,17 +100,6 @@ __device__ __forceinline__ RasterEdge raster_edge(bool have, int x0, int y0, int
   return E;
 }
 
-// Is `g` the first grain of a trajectory that has grains?  (polygons.hip's search, on the same table)
-__device__ __forceinline__ bool raster_boundary_grain(const int64_t* __restrict__ off, int64_t n_traj, int64_t g) {
-  if (off == nullptr) return g == 0;
-  int64_t a = 0, z = n_traj;
-  while (a < z) {
-    const int64_t m = (a + z + 1) >> 1;
-    if (off[m] <= g) a = m; else z = m - 1;
-  }
-  return a < n_traj && off[a] == g;
-}
-
 template <bool PERIODIC>
 __global__ __launch_bounds__(RASTER_BLOCK) void polygons_rasterize_kernel(const ggnn_raster_args A, const RasterLayers layers,
                                                                           int first) {
@@ -117,7 +107,7 @@ __global__ __launch_bounds__(RASTER_BLOCK) void polygons_rasterize_kernel(const 
   // one polygon per wave: everything below that does not name `lane` or `x` is wave-uniform, and said to be so
   const int64_t g = A.grain_begin + (int64_t)blockIdx.x * RASTER_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (g >= A.grain_end) return;
-  if (!PERIODIC && raster_boundary_grain(A.traj_grain_off, A.n_traj, g)) return;
+  if (!PERIODIC && seg_is_first(A.traj_grain_off, (int)A.n_traj, g)) return;   // (a trajectory's boundary grain is not drawn)
   const int64_t k = min((int64_t)max(layers.at[blockIdx.y], 0), A.capacity);
   const int32_t* __restrict__ rowptr = A.rowptr + k * (A.n_grain + 1);
   const float* __restrict__ xy = A.xy_sorted + 2 * k * A.E_cap;
@@ -300,7 +290,7 @@ extern "C" int ggnn_polygons_rasterize(const ggnn_raster_args* args, ggnn_stream
   if (A.nx <= 0 || A.ny <= 0 || A.nx >= (1 << 15) || A.ny >= (1 << 15)) return GGNN_EINVAL;
   if (A.n_grain <= 0 || A.E_cap < 0 || A.E_cap >= INT32_MAX || A.capacity < 0 || A.capacity >= INT32_MAX) return GGNN_EINVAL;
   if (A.grain_begin < 0 || A.grain_end < A.grain_begin || A.grain_end > A.n_grain) return GGNN_EINVAL;
-  if (A.traj_grain_off ? A.n_traj < 1 || A.n_traj > (1 << 29) : A.n_traj != 1) return GGNN_EINVAL;
+  if (!seg_union_ok(A.traj_grain_off, A.n_traj, true)) return GGNN_EINVAL;
   if (A.n_layers <= 0 || A.n_layers >= INT32_MAX) return GGNN_EINVAL;
   for (int64_t l = 0; l < A.n_layers; ++l) {
     const int64_t k = A.layers ? (int64_t)A.layers[l] : l;

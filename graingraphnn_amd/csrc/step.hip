@@ -8,6 +8,7 @@
 //                       to x_grain[:, :2] (test.py:468-478, 556-559), between the two
 // Separate launches because each stage needs every node's updated coordinates.
 #include "common.h"
+#include "segments.h"
 
 namespace ggnn {
 
@@ -101,96 +102,91 @@ __global__ __launch_bounds__(256) void grain_centres_kernel(
   }
 }
 
-// Counts the events the host-side topology update would act on (test.py:418, models.py:624-626):
-// flags[0] += #live grains with grain_area < area_threshold, flags[1] += #directed junction edges
-// (src < dst) with edge_event > logit_threshold.  One pass over 10k + 60k values; the rollout reads
-// the two words back once per step and only touches the host path when one is non-zero.
-__global__ __launch_bounds__(256) void detect_events_kernel(
-    const float* __restrict__ grain_area, const int32_t* __restrict__ live_grain, int64_t n_grain,
-    float area_threshold, const float* __restrict__ edge_event, const int64_t* __restrict__ ei_jj,
-    int64_t E_cap, const int64_t* __restrict__ E_dev, float logit_threshold, int32_t* __restrict__ flags,
-    int32_t* __restrict__ range_word, int64_t skip_grain) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t E = E_dev ? *E_dev : E_cap;   // (E_dev: include/ggnn.h, ggnn_prepare_edge)
-  // (the caller's fp16-range word travels with the counts and starts its next use clean: one thread moves it)
-  if (range_word != nullptr && t == 0) flags[2] = atomicExch(range_word, 0);
-  bool g = false, e = false;
-  if (t < n_grain) g = t != skip_grain && live_grain[t] > 0 && grain_area[t] < area_threshold;
-  else if (t - n_grain < E) {
-    const int64_t k = t - n_grain;
-    e = edge_event[k] > logit_threshold && ei_jj[k] < ei_jj[E + k];
-  }
-  const int ng = __popcll(__ballot(g)), ne = __popcll(__ballot(e));
-  if ((threadIdx.x & 63) == 0) {
-    if (ng) atomicAdd(&flags[0], ng);
-    if (ne) atomicAdd(&flags[1], ne);
-  }
-}
+// What the kernel of both detection entry points takes, filled from their arguments.
+struct detect_kargs {
+  const float* __restrict__ grain_area;
+  const int32_t* __restrict__ live_grain;
+  const float* __restrict__ edge_event;
+  const int64_t* __restrict__ ei_jj;
+  const int64_t* __restrict__ E_dev;
+  int32_t* __restrict__ flags;
+  int32_t* __restrict__ range_word;
+  int64_t n_grain, E_cap;
+  float area_threshold, logit_threshold;
+  int64_t skip_grain;                           // UNION = false alone
+  const int64_t* __restrict__ traj_grain_off;   // UNION = true alone, from here on
+  const int64_t* __restrict__ traj_joint_off;
+  const int32_t* __restrict__ ended;
+  int32_t* __restrict__ counts;
+  int n_traj;
+};
 
-// ggnn_detect_events for a disjoint union of trajectories: the same candidates, counted per trajectory.  A grain
+// Counts the events the host-side topology update would act on (test.py:418, models.py:624-626): the live grains with
+// grain_area < area_threshold and the directed junction edges (src < dst) with edge_event > logit_threshold.  One pass over
+// 10k + 60k values; the rollout reads the words back once per step and only touches the host path when one is non-zero.
+// UNION = false: flags[0] += the grains (skip_grain left out), flags[1] += the edges, a ballot and an atomic a wave each.
+// UNION = true, a disjoint union of trajectories: the same candidates, counted per trajectory as well.  A grain
 // belongs to the trajectory whose range of traj_grain_off holds it, a junction edge to the trajectory of its source junction;
 // the boundaries fall anywhere inside a wave.  Candidates are rare: a block without one leaves at once; one with candidates
 // stages the offsets in LDS while they fit (DET_LDS_TRAJ) and only its candidate lanes search them.  A wave's candidates of
 // one (trajectory, kind) go out as one pair of integer atomics: exact and order-free.
 constexpr int DET_LDS_TRAJ = 511;   // 2 x 512 offsets of 8 bytes: 8 KiB
-__global__ __launch_bounds__(256) void detect_events_traj_kernel(
-    const float* __restrict__ grain_area, const int32_t* __restrict__ live_grain, int64_t n_grain,
-    float area_threshold, const float* __restrict__ edge_event, const int64_t* __restrict__ ei_jj,
-    int64_t E_cap, const int64_t* __restrict__ E_dev, float logit_threshold,
-    const int64_t* __restrict__ traj_grain_off, const int64_t* __restrict__ traj_joint_off, int n_traj,
-    const int32_t* __restrict__ ended, int32_t* __restrict__ counts, int32_t* __restrict__ flags,
-    int32_t* __restrict__ range_word) {
-  __shared__ int64_t s_off[2][DET_LDS_TRAJ + 1];
+template <bool UNION>
+__global__ __launch_bounds__(256) void detect_events_kernel(const detect_kargs A) {
   const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  const int64_t E = E_dev ? *E_dev : E_cap;
-  if (range_word != nullptr && t == 0) flags[2] = atomicExch(range_word, 0);
+  const int64_t E = A.E_dev ? *A.E_dev : A.E_cap;   // (E_dev: include/ggnn.h, ggnn_prepare_edge)
+  // (the caller's fp16-range word travels with the counts and starts its next use clean: one thread moves it)
+  if (A.range_word != nullptr && t == 0) A.flags[2] = atomicExch(A.range_word, 0);
   bool cand = false;
   int kind = 0;       // 0: grain, 1: junction edge
   int64_t node = 0;   // the grain, or the edge's source junction
-  if (t < n_grain) {
-    cand = live_grain[t] > 0 && grain_area[t] < area_threshold;
+  if (t < A.n_grain) {
+    cand = (UNION || t != A.skip_grain) && A.live_grain[t] > 0 && A.grain_area[t] < A.area_threshold;
     node = t;
-  } else if (t - n_grain < E) {
-    const int64_t k = t - n_grain;
-    node = ei_jj[k];
-    cand = edge_event[k] > logit_threshold && node < ei_jj[E + k];
+  } else if (t - A.n_grain < E) {
+    const int64_t k = t - A.n_grain;
     kind = 1;
-  }
-  if (!__syncthreads_or(cand)) return;   // (uniform over the block: nobody waits at the barrier below)
-  const bool staged = n_traj <= DET_LDS_TRAJ;
-  if (staged) {
-    for (int i = threadIdx.x; i <= n_traj; i += 256) {
-      s_off[0][i] = traj_grain_off[i];
-      s_off[1][i] = traj_joint_off[i];
+    if (A.edge_event[k] > A.logit_threshold) {
+      node = A.ei_jj[k];
+      cand = node < A.ei_jj[E + k];
     }
-    __syncthreads();
   }
-  int key = 0;   // 2 x trajectory + kind: the candidate's word of counts [n_traj, 2]
-  if (cand) {
-    // the last trajectory whose offset is <= node (offsets rise from 0; equal ones are empty trajectories): any node lands
-    // inside [0, n_traj)
-    const int64_t* off = staged ? s_off[kind] : (kind ? traj_joint_off : traj_grain_off);
-    int lo = 0, hi = n_traj;
-    while (hi - lo > 1) {
-      const int mid = lo + ((hi - lo) >> 1);
-      if (off[mid] <= node) lo = mid;
-      else hi = mid;
+  if constexpr (!UNION) {
+    const int ng = __popcll(__ballot(cand && kind == 0)), ne = __popcll(__ballot(cand && kind == 1));
+    if ((threadIdx.x & 63) == 0) {
+      if (ng) atomicAdd(&A.flags[0], ng);
+      if (ne) atomicAdd(&A.flags[1], ne);
     }
-    if (ended != nullptr && ended[lo] != 0) cand = false;
-    key = 2 * lo + kind;
-  }
-  const int lane = threadIdx.x & 63;
-  unsigned long long todo = __ballot(cand);
-  while (todo) {   // (wave-uniform)
-    const int lead = __ffsll(todo) - 1;
-    const int lead_key = __shfl(key, lead);
-    const unsigned long long same = __ballot(cand && key == lead_key);
-    if (lane == lead) {
-      const int n = __popcll(same);
-      atomicAdd(&counts[lead_key], n);
-      atomicAdd(&flags[lead_key & 1], n);
+  } else {
+    __shared__ int64_t s_off[2][DET_LDS_TRAJ + 1];
+    if (!__syncthreads_or(cand)) return;   // (uniform over the block: nobody waits at the barrier below)
+    const bool staged = A.n_traj <= DET_LDS_TRAJ;
+    if (staged) {
+      for (int i = threadIdx.x; i <= A.n_traj; i += 256) {
+        s_off[0][i] = A.traj_grain_off[i];
+        s_off[1][i] = A.traj_joint_off[i];
+      }
+      __syncthreads();
     }
-    todo &= ~same;
+    int key = 0;   // 2 x trajectory + kind: the candidate's word of counts [n_traj, 2]
+    if (cand) {
+      const int tr = seg_of(staged ? s_off[kind] : (kind ? A.traj_joint_off : A.traj_grain_off), A.n_traj, node);
+      if (A.ended != nullptr && A.ended[tr] != 0) cand = false;
+      key = 2 * tr + kind;
+    }
+    const int lane = threadIdx.x & 63;
+    unsigned long long todo = __ballot(cand);
+    while (todo) {   // (wave-uniform)
+      const int lead = __ffsll(todo) - 1;
+      const int lead_key = __shfl(key, lead);
+      const unsigned long long same = __ballot(cand && key == lead_key);
+      if (lane == lead) {
+        const int n = __popcll(same);
+        atomicAdd(&A.counts[lead_key], n);
+        atomicAdd(&A.flags[lead_key & 1], n);
+      }
+      todo &= ~same;
+    }
   }
 }
 
@@ -206,16 +202,6 @@ __global__ __launch_bounds__(256) void detect_events_traj_kernel(
 // of its own trajectory's row.  UNION = false compiles the same body without the walk: the single rollout's launch costs
 // what it cost before unions.
 constexpr int BND_CHUNK = 1024;
-// the last trajectory whose offset is <= node (offsets rise from 0; equal ones are empty trajectories)
-__device__ __forceinline__ int bnd_traj_of(const int64_t* __restrict__ off, int n_traj, int64_t node) {
-  int lo = 0, hi = n_traj;
-  while (hi - lo > 1) {
-    const int mid = lo + ((hi - lo) >> 1);
-    if (off[mid] <= node) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
 template <bool UNION>
 __global__ __launch_bounds__(256) void noflux_boundary_kernel(
     const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col, float* __restrict__ x_joint, int64_t n_joint,
@@ -239,8 +225,8 @@ __global__ __launch_bounds__(256) void noflux_boundary_kernel(
   // the trajectories of the block's first and last junction (block-uniform)
   int tr = 0, tr_last = 0;
   if (UNION) {
-    tr = bnd_traj_of(traj_joint_off, n_traj, first);
-    tr_last = bnd_traj_of(traj_joint_off, n_traj, min(first + 255, n_joint - 1));
+    tr = seg_of(traj_joint_off, n_traj, first);
+    tr_last = seg_of(traj_joint_off, n_traj, min(first + 255, n_joint - 1));
   }
   bool bound = false;
   for (; tr <= tr_last; ++tr) {
@@ -302,7 +288,7 @@ __global__ __launch_bounds__(256) void noflux_boundary_kernel(
 // follows a device-side counter, so that a captured graph replays with the counter where the replay before left it (the
 // mechanism of the QoI layer counter, qoi.hip): every block reads the counter at its top, and the last block to finish -- by
 // then every block has read it -- stores counter + 1, which may go to the same word.  A junction's trajectory is the last
-// offset <= the junction (bnd_traj_of); the offsets and the table's current row are staged in LDS while they fit
+// offset <= the junction (seg_of, segments.h); the offsets and the table's current row are staged in LDS while they fit
 // (SCH_LDS_TRAJ), read from global memory beyond that; `staged` depends on kernel arguments only, so the barrier behind the
 // staging is reached by every thread of every block or by none.
 constexpr int SCH_LDS_TRAJ = 512;   // 513 offsets of 8 bytes + 512 rows of 8 bytes: 8 KiB
@@ -323,7 +309,7 @@ __global__ __launch_bounds__(256) void process_schedule_kernel(
   }
   const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (j < n_joint) {
-    const int t = traj_joint_off == nullptr ? 0 : bnd_traj_of(staged ? s_off : traj_joint_off, n_traj, j);
+    const int t = traj_joint_off == nullptr ? 0 : seg_of(staged ? s_off : traj_joint_off, n_traj, j);
     const float* v = staged ? s_row : row;
     float* x = x_joint + j * ldxj;
     x[3] = v[2 * t];
@@ -386,6 +372,37 @@ __global__ __launch_bounds__(256) void step_refresh_kernel(
   T.edge_attr[e] = sqrtf(r[0] * r[0] + r[1] * r[1]);  // test.py:572
 }
 
+// ggnn_noflux_boundary (traj_joint_off NULL, n_traj 1) and ggnn_noflux_boundary_traj, which has checked its union arguments.
+static int launch_noflux_boundary(const int32_t* rowptr_jg, const int32_t* col_jg, float* x_joint, int64_t n_joint,
+                                  int64_t ldx_joint, const float* domain_offset, float domain_factor, float max_y,
+                                  float* x_grain, int64_t ldx_grain, int f_grain, float* joints_before,
+                                  const int64_t* traj_grain_off, const int64_t* traj_joint_off, int n_traj, hipStream_t stream) {
+  if (!rowptr_jg || !col_jg || !x_joint || !x_grain || n_joint <= 0) return GGNN_EINVAL;
+  if (ldx_joint < 2 || f_grain < 6 || ldx_grain < f_grain) return GGNN_EINVAL;
+  if (!(domain_factor >= 1.0f) || !(max_y > 0.0f)) return GGNN_EINVAL;
+  const int64_t nblk = (n_joint + 255) / 256;
+  if (nblk >= INT32_MAX) return GGNN_EINVAL;
+  hipLaunchKernelGGL(traj_joint_off ? noflux_boundary_kernel<true> : noflux_boundary_kernel<false>, dim3((unsigned)nblk),
+                     dim3(256), 0, stream, rowptr_jg, col_jg, x_joint, n_joint, ldx_joint, domain_offset, domain_factor, max_y,
+                     x_grain, ldx_grain, f_grain, joints_before, traj_grain_off, traj_joint_off, n_traj);
+  return launch_status();
+}
+
+// Both detection entry points: the checks they share, the grid, the memsets of flags and -- a union -- of counts, the launch.
+static int launch_detect_events(const detect_kargs& A, bool is_union, hipStream_t stream) {
+  if (!A.grain_area || !A.live_grain || !A.flags || A.n_grain <= 0 || A.E_cap < 0) return GGNN_EINVAL;
+  if (A.E_cap > 0 && (!A.edge_event || !A.ei_jj)) return GGNN_EINVAL;
+  const int64_t nblk = (A.n_grain + A.E_cap + 255) / 256;
+  if (nblk >= INT32_MAX) return GGNN_EINVAL;
+  const size_t n_flags = A.range_word ? 3 : 2, n_counts = is_union ? 2 * (size_t)A.n_traj : 0;
+  const bool one = is_union && A.counts == A.flags + n_flags;   // one buffer, the totals first: one memset
+  if (hipMemsetAsync(A.flags, 0, (n_flags + (one ? n_counts : 0)) * sizeof(int32_t), stream) != hipSuccess) return GGNN_ELAUNCH;
+  if (is_union && !one && hipMemsetAsync(A.counts, 0, n_counts * sizeof(int32_t), stream) != hipSuccess) return GGNN_ELAUNCH;
+  hipLaunchKernelGGL(is_union ? detect_events_kernel<true> : detect_events_kernel<false>, dim3((unsigned)nblk), dim3(256), 0,
+                     stream, A);
+  return launch_status();
+}
+
 }  // namespace ggnn
 
 extern "C" int ggnn_step_update(float* x_joint, int64_t n_joint, int64_t ldx_joint, float* x_grain,
@@ -426,17 +443,10 @@ extern "C" int ggnn_noflux_boundary_traj(const int32_t* rowptr_jg, const int32_t
                                          float* x_grain, int64_t ldx_grain, int f_grain, float* joints_before,
                                          const int64_t* traj_grain_off, const int64_t* traj_joint_off, int64_t n_traj,
                                          ggnn_stream_t stream) {
-  using namespace ggnn;
-  if (!rowptr_jg || !col_jg || !x_joint || !x_grain || n_joint <= 0) return GGNN_EINVAL;
-  if (ldx_joint < 2 || f_grain < 6 || ldx_grain < f_grain) return GGNN_EINVAL;
-  if (!(domain_factor >= 1.0f) || !(max_y > 0.0f)) return GGNN_EINVAL;
-  if (!traj_grain_off || !traj_joint_off || n_traj < 1 || n_traj > (1 << 29)) return GGNN_EINVAL;
-  const int64_t nblk = (n_joint + 255) / 256;
-  if (nblk >= INT32_MAX) return GGNN_EINVAL;
-  hipLaunchKernelGGL(noflux_boundary_kernel<true>, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, rowptr_jg, col_jg,
-                     x_joint, n_joint, ldx_joint, domain_offset, domain_factor, max_y, x_grain, ldx_grain, f_grain,
-                     joints_before, traj_grain_off, traj_joint_off, (int)n_traj);
-  return launch_status();
+  if (!ggnn::seg_union_ok(traj_grain_off, n_traj, false) || !traj_joint_off) return GGNN_EINVAL;
+  return ggnn::launch_noflux_boundary(rowptr_jg, col_jg, x_joint, n_joint, ldx_joint, domain_offset, domain_factor, max_y, x_grain,
+                                      ldx_grain, f_grain, joints_before, traj_grain_off, traj_joint_off, (int)n_traj,
+                                      (hipStream_t)stream);
 }
 
 // (one rollout = the one-trajectory case of the kernel: every junction, boundary grain 0)
@@ -444,16 +454,8 @@ extern "C" int ggnn_noflux_boundary(const int32_t* rowptr_jg, const int32_t* col
                                     int64_t ldx_joint, const float* domain_offset, float domain_factor, float max_y,
                                     float* x_grain, int64_t ldx_grain, int f_grain, float* joints_before,
                                     ggnn_stream_t stream) {
-  using namespace ggnn;
-  if (!rowptr_jg || !col_jg || !x_joint || !x_grain || n_joint <= 0) return GGNN_EINVAL;
-  if (ldx_joint < 2 || f_grain < 6 || ldx_grain < f_grain) return GGNN_EINVAL;
-  if (!(domain_factor >= 1.0f) || !(max_y > 0.0f)) return GGNN_EINVAL;
-  const int64_t nblk = (n_joint + 255) / 256;
-  if (nblk >= INT32_MAX) return GGNN_EINVAL;
-  hipLaunchKernelGGL(noflux_boundary_kernel<false>, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, rowptr_jg, col_jg,
-                     x_joint, n_joint, ldx_joint, domain_offset, domain_factor, max_y, x_grain, ldx_grain, f_grain,
-                     joints_before, (const int64_t*)nullptr, (const int64_t*)nullptr, 1);
-  return launch_status();
+  return ggnn::launch_noflux_boundary(rowptr_jg, col_jg, x_joint, n_joint, ldx_joint, domain_offset, domain_factor, max_y, x_grain,
+                                      ldx_grain, f_grain, joints_before, nullptr, nullptr, 1, (hipStream_t)stream);
 }
 
 extern "C" int ggnn_process_schedule(float* x_joint, int64_t n_joint, int64_t ldx_joint, const float* table, int64_t n_rows,
@@ -461,8 +463,7 @@ extern "C" int ggnn_process_schedule(float* x_joint, int64_t n_joint, int64_t ld
                                      int32_t* sync_word, ggnn_stream_t stream) {
   using namespace ggnn;
   if (!x_joint || !table || !step_in || !step_out || !sync_word) return GGNN_EINVAL;
-  if (n_joint <= 0 || ldx_joint < 5 || n_rows < 1 || n_traj < 1 || n_traj > (1 << 29)) return GGNN_EINVAL;
-  if (!traj_joint_off && n_traj != 1) return GGNN_EINVAL;
+  if (n_joint <= 0 || ldx_joint < 5 || n_rows < 1 || !seg_union_ok(traj_joint_off, n_traj, true)) return GGNN_EINVAL;
   const int64_t nblk = (n_joint + 255) / 256;
   if (nblk >= INT32_MAX) return GGNN_EINVAL;
   hipLaunchKernelGGL(process_schedule_kernel, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream, x_joint, n_joint,
@@ -474,16 +475,9 @@ extern "C" int ggnn_detect_events(const float* grain_area, const int32_t* live_g
                                   float area_threshold, const float* edge_event, const int64_t* edge_index_jj,
                                   int64_t E, const int64_t* E_dev, float logit_threshold, int32_t* flags,
                                   int32_t* range_word, int64_t skip_grain, ggnn_stream_t stream) {
-  using namespace ggnn;
-  if (!grain_area || !live_grain || !flags || n_grain <= 0 || E < 0) return GGNN_EINVAL;
-  if (E > 0 && (!edge_event || !edge_index_jj)) return GGNN_EINVAL;
-  const int64_t nblk = (n_grain + E + 255) / 256;
-  if (nblk >= INT32_MAX) return GGNN_EINVAL;
-  if (hipMemsetAsync(flags, 0, (range_word ? 3 : 2) * sizeof(int32_t), (hipStream_t)stream) != hipSuccess) return GGNN_ELAUNCH;
-  hipLaunchKernelGGL(detect_events_kernel, dim3((unsigned)nblk), dim3(256), 0, (hipStream_t)stream,
-                     grain_area, live_grain, n_grain, area_threshold, edge_event, edge_index_jj, E, E_dev,
-                     logit_threshold, flags, range_word, skip_grain);
-  return launch_status();
+  const ggnn::detect_kargs A = {grain_area, live_grain, edge_event, edge_index_jj, E_dev, flags, range_word, n_grain, E,
+                                area_threshold, logit_threshold, skip_grain, nullptr, nullptr, nullptr, nullptr, 1};
+  return ggnn::launch_detect_events(A, false, (hipStream_t)stream);
 }
 
 extern "C" int ggnn_detect_events_traj(const float* grain_area, const int32_t* live_grain, int64_t n_grain,
@@ -492,25 +486,11 @@ extern "C" int ggnn_detect_events_traj(const float* grain_area, const int32_t* l
                                        const int64_t* traj_grain_off, const int64_t* traj_joint_off, int64_t n_traj,
                                        const int32_t* ended, int64_t skip_local_grain, int32_t* counts, int32_t* flags,
                                        int32_t* range_word, ggnn_stream_t stream) {
-  using namespace ggnn;
-  if (!grain_area || !live_grain || !flags || !counts || n_grain <= 0 || E < 0) return GGNN_EINVAL;
-  if (E > 0 && (!edge_event || !edge_index_jj)) return GGNN_EINVAL;
-  if (!traj_grain_off || !traj_joint_off || n_traj < 1 || n_traj > (1 << 29)) return GGNN_EINVAL;
+  if (!counts || !ggnn::seg_union_ok(traj_grain_off, n_traj, false) || !traj_joint_off) return GGNN_EINVAL;
   if (skip_local_grain != -1) return GGNN_EINVAL;   // (no-flux unions keep their boundary grains out through live_grain)
-  const int64_t nblk = (n_grain + E + 255) / 256;
-  if (nblk >= INT32_MAX) return GGNN_EINVAL;
-  const hipStream_t s = (hipStream_t)stream;
-  const size_t n_flags = range_word ? 3 : 2, n_counts = 2 * (size_t)n_traj;
-  if (counts == flags + n_flags) {   // one buffer, the totals first: one memset
-    if (hipMemsetAsync(flags, 0, (n_flags + n_counts) * sizeof(int32_t), s) != hipSuccess) return GGNN_ELAUNCH;
-  } else {
-    if (hipMemsetAsync(flags, 0, n_flags * sizeof(int32_t), s) != hipSuccess) return GGNN_ELAUNCH;
-    if (hipMemsetAsync(counts, 0, n_counts * sizeof(int32_t), s) != hipSuccess) return GGNN_ELAUNCH;
-  }
-  hipLaunchKernelGGL(detect_events_traj_kernel, dim3((unsigned)nblk), dim3(256), 0, s, grain_area, live_grain, n_grain,
-                     area_threshold, edge_event, edge_index_jj, E, E_dev, logit_threshold, traj_grain_off, traj_joint_off,
-                     (int)n_traj, ended, counts, flags, range_word);
-  return launch_status();
+  const ggnn::detect_kargs A = {grain_area, live_grain, edge_event, edge_index_jj, E_dev, flags, range_word, n_grain, E,
+                                area_threshold, logit_threshold, -1, traj_grain_off, traj_joint_off, ended, counts, (int)n_traj};
+  return ggnn::launch_detect_events(A, true, (hipStream_t)stream);
 }
 
 extern "C" int ggnn_step_refresh(float* x_joint, int64_t n_joint, int64_t ldx_joint,

@@ -11,6 +11,7 @@
 // Every index is clamped as in vectorize.hip: rows to [0, E_cap], columns to [0, n_joint), grain offsets to [0, n_grain],
 // nothing is read or written at or beyond joint_capacity; indices into the union are 64-bit.
 #include "common.h"
+#include "segments.h"
 
 namespace ggnn {
 
@@ -27,16 +28,6 @@ struct TrackTables {
   int64_t n_grain, n_joint, E_cap, n_frame;
   int32_t boundary;
 };
-
-// The last entry of the rising off[0 .. n] that is <= v, below n.
-__device__ __forceinline__ int64_t frame_of(const int64_t* __restrict__ off, int64_t n, int64_t v) {
-  int64_t lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= v) lo = mid; else hi = mid - 1;
-  }
-  return lo;
-}
 
 // The grains of frame t: -> the first one, n = how many (0 when the offsets do not rise).
 __device__ __forceinline__ int64_t frame_grains(const TrackTables& T, int64_t t, int64_t& n) {
@@ -125,7 +116,7 @@ __global__ __launch_bounds__(TRK_BLOCK) void track_junctions_kernel(const ggnn_t
   int64_t t = 0;
   bool matched = false, ambiguous = false;
   if (live) {
-    t = frame_of(joint_off, A.n_frame, j);
+    t = seg_of(joint_off, (int)A.n_frame, j);
     const int64_t a = T.triples[3 * j], b = T.triples[3 * j + 1], c = T.triples[3 * j + 2];
     int64_t at;
     const int own = find_triple(T, a, b, c, at);
@@ -174,7 +165,7 @@ __global__ __launch_bounds__(TRK_BLOCK) void track_joint_targets_kernel(const gg
   if (live) {
     const int64_t j = s / 3;
     const int k = (int)(s - 3 * j);
-    t = frame_of(joint_off, A.n_frame, j);
+    t = seg_of(joint_off, (int)A.n_frame, j);
     const int64_t nu = A.next_joint[j];
     if (k == 0) {
       const int64_t pu = A.prev_joint[j];
@@ -231,7 +222,7 @@ __global__ __launch_bounds__(TRK_BLOCK) void track_grain_targets_kernel(const gg
   int64_t t = 0;
   bool gone = false;
   if (live) {
-    t = frame_of(A.grain_off, A.n_frame, g);
+    t = seg_of(A.grain_off, (int)A.n_frame, g);
     int64_t n_own, n_next = 0, n_prev = 0;
     const int64_t g0 = frame_grains(T, t, n_own), l = g - g0;
     const bool inside = l >= 0 && l < n_own;   // (false only for offsets that do not cover the union)

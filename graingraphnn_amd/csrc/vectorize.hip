@@ -35,6 +35,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "segments.h"
 
 namespace ggnn {
 
@@ -165,16 +166,6 @@ struct junction_kargs {
 __device__ __forceinline__ int64_t image_grains(const int64_t* __restrict__ grain_off, int64_t b, int64_t n_total, int32_t& n) {
   const int64_t lo = min(max(grain_off[b], (int64_t)0), n_total), hi = min(max(grain_off[b + 1], lo), n_total);
   n = (int32_t)(hi - lo);
-  return lo;
-}
-
-// The last entry of the rising off[0 .. n] that is <= v, below n.
-__device__ __forceinline__ int64_t segment_of(const int64_t* __restrict__ off, int64_t n, int64_t v) {
-  int64_t lo = 0, hi = n - 1;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi + 1) >> 1;
-    if (off[mid] <= v) lo = mid; else hi = mid - 1;
-  }
   return lo;
 }
 
@@ -315,7 +306,7 @@ __global__ __launch_bounds__(VEC_SCAN_BLOCK) void junction_scan_kernel(const jun
     const uint64_t* __restrict__ pixel_counts = A.pixel_counts;
     for (int64_t g = t; g < n_grain; g += VEC_SCAN_BLOCK) {
       if (pixel_counts[g] == 0) continue;
-      const int64_t b = segment_of(A.grain_off, n_image, g);
+      const int64_t b = seg_of(A.grain_off, (int)n_image, g);
       int32_t n;
       const int64_t g0 = image_grains(A.grain_off, b, n_grain, n);
       if (g < g0 + first_local || g >= g0 + n) continue;
@@ -377,7 +368,7 @@ __global__ __launch_bounds__(256) void junction_links_kernel(const ggnn_link_tra
   A.edge_jj[s] = j;
   A.edge_jj[3 * A.joint_capacity + s] = found == 1 ? partner : -1;
   if (found != 1)   // (rare: none in a valid structure)
-    atomicAdd((unsigned long long*)A.status + (STACK ? segment_of(joint_off, A.n_image, j) : 0) * GGNN_JUNCTION_STATUS_WORDS + 4,
+    atomicAdd((unsigned long long*)A.status + (STACK ? seg_of(joint_off, (int)A.n_image, j) : 0) * GGNN_JUNCTION_STATUS_WORDS + 4,
               1ull);
 }
 
@@ -569,7 +560,7 @@ __global__ __launch_bounds__(256) void junction_trace_kernel(const ggnn_link_tra
   if (*slot != -1) return;   // (every column of a structure without open pairs)
   const int64_t j = s / 3;
   const int c = (int)(s - 3 * j);
-  const int64_t b = segment_of(joint_off, A.n_image, j);
+  const int64_t b = seg_of(joint_off, (int)A.n_image, j);
   trace_image I;
   I.g0 = image_grains(A.grain_off, b, A.n_grain, I.n_grain);
   I.image = A.images + b * A.ny * A.nx;

@@ -327,6 +327,22 @@ def test_kernel_noflux_union_skips_every_boundary_grain():
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("off", [(0, N_ROWS), (0, 0, 2, 2, 3, 6, N_ROWS, N_ROWS), (0, 1, 2, 3, N_ROWS)])
+def test_kernel_noflux_union_at_the_edges_of_the_offsets(off):
+    """A union of one trajectory; empty trajectories first, in the middle and last; trajectories of one to three grains: the
+    first grain of every trajectory that has grains is skipped, and no other."""
+    size = (53, 29)
+    arena, rowptr, xy = arena_of([shape_rows(size, "noflux")])
+    dev_off = torch.tensor(off, dtype=torch.int64, device=DEV)
+    got = backend().rasterize_polygons(arena, size, None, "noflux", traj_grain_off=dev_off)[0]
+    want = rc.grain_image(rowptr[0], xy[0], size, "noflux", traj_grain_off=off)
+    assert_images_equal(got, want, off)
+    ids = set(np.unique(want).tolist())
+    first = {a + 1 for a, b in zip(off[:-1], off[1:]) if b > a}
+    assert not ids & first and ids == set(range(N_ROWS + 1)) - set(UNDRAWN) - first, (off, ids)
+
+
+@pytest.mark.gpu
 def test_kernel_clamps_whatever_the_tables_hold():
     """Row pointers outside the arena, coordinates that are huge, infinite or NaN: the image is the restatement's on the
     clamped tables, and the guard words round the image stay."""

@@ -198,6 +198,27 @@ def test_masked_union_tables_equal_the_tables_of_the_filtered_lists():
     _check_masked_union(be, got[1], jg2, nj, ng, bnd, 1)
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("sizes", [[3], [0, 2, 0, 1, 3, 0], [2, 1, 0, 0, 2]])
+def test_masked_union_tables_at_the_edges_of_the_offsets(sizes):
+    """Trajectories of 0 to 3 grains -- a union of one, empty ones first, in the middle and last, a grain on every offset: the
+    edges left out are those of the first grain of every trajectory that has grains, on the source and on the destination side."""
+    from graingraphnn_amd.backend import default_backend
+    be = default_backend()
+    og = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    ng, nj = int(og[-1]), 5
+    first = og[:-1][np.diff(og) > 0]
+    rs = np.random.RandomState(len(sizes))
+    gj = np.stack([np.repeat(np.arange(ng), 3), rs.randint(0, nj, 3 * ng)]).astype(np.int64)   # (every grain has edges)
+    jg = np.ascontiguousarray(gj[::-1])
+    dev = lambda a: torch.from_numpy(a).to(DEV)
+    og_dev = dev(og)
+    built = be.build_csr_batch([(dev(gj), ng, nj), (dev(jg), nj, ng)], masks=[(0, -1), (-1, 0)],
+                               unions=[(og_dev, None), (None, og_dev)])
+    _check_masked_union(be, built[0], gj, ng, nj, first, 0)
+    _check_masked_union(be, built[1], jg, nj, ng, first, 1)
+
+
 # ---- GPU: the boundary step of a union --------------------------------------------------------------------------------------
 
 def _fixture_part(d, seed, spread=0.03):

@@ -481,6 +481,18 @@ def test_a_one_grain_frame_in_the_middle(boundary):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("boundary", ("periodic", "noflux"))
+@pytest.mark.parametrize("at", (0, 2))
+def test_a_one_grain_frame_first_or_last(boundary, at):
+    """The frame without junctions at either end of the sequence: joint_off begins, or ends, with two equal offsets."""
+    frames, n = drifting(boundary, 32, 32, T=2)
+    frames.insert(at, one_grain(boundary, 32, 32))
+    samples, report, r = check_sequence(("end", at), frames, n, boundary)
+    assert r["joint_off"][at] == r["joint_off"][at + 1] and r["joint_off"][3] > 0
+    assert len(samples) == (1 if boundary == "periodic" else 2)
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("extra", (-1, 0, 1))
 def test_unions_around_a_block_of_threads(extra):
     frames, n = block_stack(extra)

@@ -191,6 +191,37 @@ def test_collation_equals_the_restatement_bit_for_bit_over_two_epochs():
     assert int(ds.sync_word) == 0
 
 
+def _tiny_samples():
+    """Four samples of 0 to 3 nodes a type: sample 1 is empty, sample 3 has nodes and no edge."""
+    rs = np.random.RandomState(11)
+    out = []
+    for ng, nj, ne in ((2, 3, 3), (0, 0, 0), (3, 1, 2), (1, 2, 0)):
+        n = {"grain": ng, "joint": nj}
+        x = {"grain": rs.rand(ng, 11).astype(np.float32), "joint": rs.rand(nj, 8).astype(np.float32)}
+        ei = {et: np.stack([rs.randint(0, max(n[et[0]], 1), ne), rs.randint(0, max(n[et[-1]], 1), ne)]).astype(np.int64)
+              for et in EDGE_TYPES}
+        ea = {et: rs.rand(ne, 1).astype(np.float32) for et in EDGE_TYPES}
+        y = {nt: rs.rand(n[nt], 2).astype(np.float32) for nt in NODE_TYPES}
+        y["edge_event"], y["grain_event"] = rs.randint(-1, 2, ne).astype(np.int64), rs.randint(0, 2, ng).astype(np.int64)
+        mask = {nt: rs.randint(0, 2, (n[nt], 1)).astype(np.float32) for nt in NODE_TYPES}
+        out.append({"x": x, "edge_index": ei, "edge_attr": ea, "y": y, "mask": mask})
+    return out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("batch_size, perm", [(4, [0, 1, 2, 3]), (4, [1, 3, 0, 2]), (1, [2, 1, 0, 3]), (3, [3, 1, 2, 0])])
+def test_collation_of_tiny_samples_at_the_edges_of_the_slots(batch_size, perm):
+    """Slots of 0 to 3 rows: an empty sample first, in the middle and last, a batch of one slot, and every row and edge that
+    stands exactly on a slot's first offset -- against the same restatement."""
+    S = _tiny_samples()
+    ds = training.DeviceDataset(S, batch_size)
+    db = training.DeviceBatches(ds)
+    ds.set_order(perm)
+    for b in range(ds.n_batches):
+        db.next()
+        _assert_batch_equals_restatement(db, S, perm[b * batch_size:(b + 1) * batch_size], (batch_size, perm, b))
+
+
 def _union_on_device(S, ids):
     x, ei, ea, y, mask, _ = bc.union(S, ids)
     return tt(x, "cuda"), tt(ei, "cuda"), tt(ea, "cuda"), tt(y, "cuda"), tt(mask, "cuda")

@@ -368,6 +368,19 @@ def test_a_one_grain_image_between_two_real_ones(boundary):
     assert_equals_restatement(res, restated("one grain", images, n_grains, boundary), boundary)
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("boundary", BOUNDARIES)
+@pytest.mark.parametrize("at", [0, 2])
+def test_a_one_grain_image_first_or_last(boundary, at):
+    """The image without junctions at either end of the stack: joint_off begins, or ends, with two equal offsets."""
+    images, n_grains = stack_of(boundary, 24, 40)
+    images[at], n_grains[at] = one_grain(boundary, 24, 40)
+    res = check_members(images, n_grains, boundary)
+    oj = res["traj_offsets"]["joint"]
+    assert oj[at] == oj[at + 1] and oj[3] > 0
+    assert_equals_restatement(res, restated(("one grain", at), images, n_grains, boundary), (boundary, at))
+
+
 def guarded_call(images, n_grains, boundary, cap):
     """The entry points themselves on guarded arrays -> (xy, triples, gj, jj, status, counts, ws) with 16 guard words of -7
     behind each, n_blocks."""

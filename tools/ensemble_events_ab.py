@@ -96,10 +96,10 @@ def main():
             E, p, be = ro._ens, ro.pred, ro.be
             flags = torch.zeros(2, dtype=torch.int32, device=dev)
             calls = {
-                "ggnn_detect_events (detect_events_kernel)": lambda: be.detect_events(
+                "ggnn_detect_events (detect_events_kernel<false>)": lambda: be.detect_events(
                     p["grain_area"], ro._live_grain, ro.area_threshold, p["edge_event"], ro.graph.edge_index[("joint", "connect", "joint")],
                     ro._logit_trigger, flags),
-                "ggnn_detect_events_traj (detect_events_traj_kernel)": lambda: be.detect_events_traj(
+                "ggnn_detect_events_traj (detect_events_kernel<true>)": lambda: be.detect_events_traj(
                     p["grain_area"], ro._live_grain, ro.area_threshold, p["edge_event"], ro.graph.edge_index[("joint", "connect", "joint")],
                     ro._logit_trigger, E["grain_off"], E["joint_off"], ro._ev_flags[2:], ro._ev_flags[:2], ended=E["ended"])}
             n = 500
