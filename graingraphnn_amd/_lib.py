@@ -31,6 +31,7 @@ GGNN_INTERP_MAX_JOBS = 256
 GGNN_JUNCTION_SEGMENT, GGNN_JUNCTION_STATUS_WORDS, GGNN_JUNCTION_MAX_BLOCKS = 256, 7, 1 << 22
 GGNN_TRACE_COUNTERS = 3
 GGNN_LABEL_TILE_X, GGNN_LABEL_TILE_Y, GGNN_LABEL_STATUS_WORDS, GGNN_LABEL_MAX_SWEEPS = 64, 16, 9, 1024
+GGNN_LINK_SLOTS, GGNN_LINK_RUN, GGNN_LINK_FRAME_WORDS, GGNN_LINK_GLOBAL_WORDS = 16, 4, 6, 2
 GGNN_ADAM_CHUNK, GGNN_ADAM_MAX_TENSORS, GGNN_ADAM_MAX_GROUPS = 4096, 384, 8
 GGNN_ROWGEMM_MAX_PACK = 8
 GGNN_MSE_MAX_TERMS, GGNN_MSE_BLOCKS = 4, 64
@@ -65,7 +66,7 @@ EXPORTED_SYMBOLS = (
     "ggnn_polygons_rasterize", "ggnn_image_compare", "ggnn_image_junctions", "ggnn_junction_links",
     "ggnn_image_junctions_traj", "ggnn_junction_links_traj", "ggnn_track_junctions", "ggnn_track_targets",
     "ggnn_image_junction_windows_traj", "ggnn_junction_links_trace_traj",
-    "ggnn_label_workspace_bytes", "ggnn_label_grains",
+    "ggnn_label_workspace_bytes", "ggnn_label_grains", "ggnn_link_workspace_bytes", "ggnn_link_labels",
     "ggnn_metric_record",
     "ggnn_masked_mse_rows", "ggnn_collate_batch", "ggnn_reverse_slots",
 )
@@ -511,6 +512,18 @@ class LabelArgs(Structure):
     ]
 
 
+class LinkLabelsArgs(Structure):
+    """Mirror of `ggnn_link_labels_args` (`LinkArgs` is the junction linking's)."""
+    _fields_ = [
+        ("labels", c_void_p), ("n_local", c_void_p), ("means", c_void_p), ("frames_out", c_void_p), ("gid", c_void_p),
+        ("pred", c_void_p), ("first_frame", c_void_p), ("last_frame", c_void_p), ("theta", c_void_p), ("status", c_void_p),
+        ("workspace", c_void_p), ("workspace_bytes", c_size_t),
+        ("T", c_int64), ("nx", c_int64), ("ny", c_int64), ("local_capacity", c_int64), ("global_capacity", c_int64),
+        ("min_overlap", c_int64),
+        ("match_tol", c_float), ("use_match_tol", c_int32), ("K", c_int32), ("boundary", c_int32),
+    ]
+
+
 class MetricArgs(Structure):
     """Mirror of `ggnn_metric_args`."""
     _fields_ = [
@@ -687,6 +700,10 @@ def _declare(lib):
     lib.ggnn_label_workspace_bytes.argtypes = [c_int64, c_int64, c_int32]
     lib.ggnn_label_grains.restype = c_int
     lib.ggnn_label_grains.argtypes = [POINTER(LabelArgs), c_void_p]
+    lib.ggnn_link_workspace_bytes.restype = c_size_t
+    lib.ggnn_link_workspace_bytes.argtypes = [c_int64, c_int64, c_int32]
+    lib.ggnn_link_labels.restype = c_int
+    lib.ggnn_link_labels.argtypes = [POINTER(LinkLabelsArgs), c_void_p]
     lib.ggnn_process_schedule.restype = c_int
     lib.ggnn_process_schedule.argtypes = [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p]

@@ -45,9 +45,15 @@ whose own contract -- an invalid structure is reported, not repaired -- stands.
 
 Not covered: stacks of mixed image shapes, resolving a quadruple from a history (the diagonal is fixed, and counted in the
 status), the reference's `edge` length target (its edge_len head is disabled in every shipped configuration) and its
-`elim_list` scaling of shrinking grains (commented out in the reference); for the labelling: stacks of maps in one launch, ids
-that are consistent across the frames of a sequence, symmetry-reduced misorientation, 8-connectivity, Euler-angle triples
-with crystal symmetry."""
+`elim_list` scaling of shrinking grains (commented out in the reference); for the labelling: stacks of maps in one launch,
+symmetry-reduced misorientation, 8-connectivity, Euler-angle triples with crystal symmetry; for the linking: merging grains, a
+grain that reappears keeping its id, matching across more than one frame back, crystal symmetry in the gate.
+
+A SEQUENCE of measured maps gets ids that persist from frame to frame (`link_labels`, `label_sequence`,
+`samples_from_orientation_sequence`; ggnn_link_labels; tests/linkcheck.py): every frame is labelled on its own, the
+grains of consecutive frames are linked by their pixel overlap on the device -- votes in integers, the predecessor with the
+most shared pixels, one keeper per predecessor, fresh ids for the rest --, and the relabelled stack is what `frames_to_samples`
+takes: a series of measured maps becomes a training set without the host."""
 import ctypes
 import math
 
@@ -769,9 +775,9 @@ def label_grains(ids=None, angles=None, tol=None, valid=None, min_pixels=1, max_
     n_sweeps, n_unfilled, overflow (more grains than grain_capacity: the image is complete, the means hold the first rows).
     Device tensors in, device tensors out, ONE read-back (the status); 9 + 2 max_sweeps launches whatever the image holds.
 
-    Not covered: stacks of maps in one launch, ids that are consistent across the frames of a sequence (`frames_to_samples`
-    needs them), symmetry-reduced misorientation (reduce the angles to a fundamental zone first), 8-connectivity, Euler-angle
-    triples with crystal symmetry."""
+    Not covered: stacks of maps in one launch (`label_sequence` labels a sequence frame by frame and gives its grains the ids
+    that persist across the frames, which `frames_to_samples` needs), symmetry-reduced misorientation (reduce the angles to a
+    fundamental zone first), 8-connectivity, Euler-angle triples with crystal symmetry."""
     v = _label(ids, angles, tol, valid, min_pixels, max_sweeps, boundary, grain_capacity)
     status = dict(zip(LABEL_STATUS_WORDS, v["status"].tolist()))   # the one read-back
     if status["n_bound_hits"]:
@@ -801,3 +807,212 @@ def sample_from_orientations(theta_x_map, theta_z_map, G, R, tol, min_pixels=1, 
     theta = means.cpu().numpy()
     x, ei, ea = sample_from_image(image, theta[0], theta[1], G, R, n_grain=n_grain, **kw)
     return x, ei, ea, image, dict(status, theta_x=theta[0], theta_z=theta[1])
+
+
+# ---- ids that persist across a sequence of labelled maps --------------------------------------------------------------------
+
+LINK_FRAME_WORDS = ("n_local", "n_matched", "n_fresh", "n_split", "n_gone", "n_vote_overflow")
+LINK_MAX_DEFAULT_CAPACITY = 65536   # the default room per frame: a frame's slot table takes 128 bytes a row
+
+
+def _link(labels, n_local, means, match_tol, min_overlap, boundary, local_capacity, global_capacity):
+    """Every launch of `link_labels`, no read-back: -> dict of the relabelled frames, gid, pred, first_frame, last_frame, theta
+    (None without means), the status words on the device, and the call's arguments with what they point to
+    (tools/vectorize_cost.py).  labels int32 [T, ny, nx], n_local int64 [T], means float32 [T, K, local_capacity] or None: all
+    contiguous, on one device."""
+    be = default_backend()
+    T, ny, nx = labels.shape
+    K, dev = (0 if means is None else means.size(1)), labels.device
+    frames = torch.empty_like(labels)
+    gid = torch.empty(T, local_capacity, dtype=torch.int32, device=dev)
+    pred = torch.empty(T, local_capacity, dtype=torch.int32, device=dev)
+    first_frame = torch.empty(global_capacity, dtype=torch.int32, device=dev)
+    last_frame = torch.empty(global_capacity, dtype=torch.int32, device=dev)
+    theta = torch.empty(K, global_capacity, dtype=torch.float32, device=dev) if K else None
+    status = torch.empty(_lib.GGNN_LINK_FRAME_WORDS * T + _lib.GGNN_LINK_GLOBAL_WORDS, dtype=torch.int64, device=dev)   # (zeroed by the call)
+    need = be.lib.ggnn_link_workspace_bytes(T, local_capacity, K)
+    if need == 0:
+        raise _lib.GGNNError(f"ggnn_link_labels takes no stack of {T} frames with room for {local_capacity} grains each")
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    A = _lib.LinkLabelsArgs()
+    A.labels, A.n_local, A.means, A.frames_out, A.gid, A.pred = (_lib.ptr(labels), _lib.ptr(n_local), _lib.ptr(means), _lib.ptr(frames),
+                                                                  _lib.ptr(gid), _lib.ptr(pred))
+    A.first_frame, A.last_frame, A.theta, A.status = _lib.ptr(first_frame), _lib.ptr(last_frame), _lib.ptr(theta), _lib.ptr(status)
+    A.workspace, A.workspace_bytes = _lib.ptr(ws), need
+    A.T, A.nx, A.ny, A.local_capacity, A.global_capacity, A.min_overlap = T, nx, ny, local_capacity, global_capacity, min_overlap
+    A.match_tol, A.use_match_tol = (0.0 if match_tol is None else float(np.float32(match_tol))), int(match_tol is not None)
+    A.K, A.boundary = K, BOUNDARIES[boundary]
+    _lib.check(be.lib.ggnn_link_labels(ctypes.byref(A), _lib.current_stream()), "ggnn_link_labels")
+    return {"frames": frames, "gid": gid, "pred": pred, "first_frame": first_frame, "last_frame": last_frame, "theta": theta,
+            "status": status, "boundary": boundary, "calls": (A, labels, n_local, means, ws)}
+
+
+def _link_checked(labels, n_local, means, match_tol, min_overlap, boundary, local_capacity, global_capacity):
+    """`_link` behind the checks that `link_labels` and `label_sequence` share: -> its dict."""
+    _check_boundary(boundary)
+    labels = _image_tensor(labels, 3, "labels must be a [T, ny, nx] device tensor of labelled frames", "labels")
+    T, ny, nx = labels.shape
+    if T < 1 or nx < 3 or ny < 3:
+        raise _lib.GGNNError("labels must hold at least one frame of at least 3 x 3 pixels")
+    if isinstance(n_local, torch.Tensor):
+        if not n_local.is_cuda or n_local.numel() != T:
+            raise _lib.GGNNError("n_local must be a device tensor or a host list of one count per frame")
+        n_local = n_local.reshape(-1).to(torch.int64).contiguous()
+        most = None
+    else:
+        host = [int(n) for n in n_local]
+        if len(host) != T:
+            raise _lib.GGNNError("n_local must be a device tensor or a host list of one count per frame")
+        most = max(max(host), 1)
+        n_local = torch.tensor(host, dtype=torch.int64, device=labels.device)
+    if means is not None:
+        if not isinstance(means, torch.Tensor) or not means.is_cuda or means.dim() != 3 or means.size(0) != T or means.dtype != torch.float32:
+            raise _lib.GGNNError("means must be a float32 [T, K, local_capacity] device tensor")
+        if not 0 <= means.size(1) <= 4:
+            raise _lib.GGNNError("means must hold at most 4 channels")
+        if local_capacity is not None and int(local_capacity) != means.size(2):
+            raise _lib.GGNNError("local_capacity must be the row length of means")
+        local_capacity = means.size(2)
+        means = means.contiguous() if means.size(1) else None
+    if match_tol is not None and (means is None or not float(match_tol) >= 0):
+        raise _lib.GGNNError("match_tol needs means and must be >= 0")
+    if int(min_overlap) < 1:
+        raise _lib.GGNNError("min_overlap must be at least 1")
+    if local_capacity is None:
+        local_capacity = most if most is not None else min(ny * nx, LINK_MAX_DEFAULT_CAPACITY)
+    local_capacity = int(local_capacity)
+    global_capacity = local_capacity * min(T, 2) if global_capacity is None else int(global_capacity)
+    if local_capacity < 1 or global_capacity < 1:
+        raise _lib.GGNNError("local_capacity and global_capacity must be at least 1")
+    return _link(labels, n_local, means, match_tol, int(min_overlap), boundary, local_capacity, global_capacity)
+
+
+def _link_report(v, words):
+    """The status words of a link call as the report of `link_labels`, and its results cut to what the sequence holds; raises on
+    a dropped vote and on an overflow."""
+    T = v["frames"].size(0)
+    W = _lib.GGNN_LINK_FRAME_WORDS
+    per_frame = [dict(zip(LINK_FRAME_WORDS, words[W * t:W * t + W])) for t in range(T)]
+    n_global, overflow = words[W * T], words[W * T + 1]
+    dropped = sum(s["n_vote_overflow"] for s in per_frame)
+    if dropped:
+        raise _lib.GGNNError(f"ggnn_link_labels: {dropped} votes found the {_lib.GGNN_LINK_SLOTS} slots of their grain taken (a grain "
+                             f"overlaps more grains of the frame before: the frames are too far apart): {per_frame}")
+    if overflow:
+        raise _lib.GGNNError(f"ggnn_link_labels: overflow {overflow} (ids beyond the local capacity, or {n_global} global grains "
+                             f"beyond the global capacity {v['first_frame'].numel()}): {per_frame}")
+    noflux = v["boundary"] == "noflux"
+    n_grain = n_global + (1 if noflux else 0)
+    theta = v["theta"]
+    if theta is not None:
+        theta = theta[:, :n_global]
+        if noflux:                                         # row 0: the boundary grain's, as label_grains writes it
+            theta = torch.cat([torch.zeros(theta.size(0), 1, dtype=theta.dtype, device=theta.device), theta], 1)
+        theta = theta.contiguous()
+    report = {"frames": per_frame, "n_global": n_global, "gid": v["gid"], "pred": v["pred"],
+              "first_frame": v["first_frame"][:n_global].contiguous(), "last_frame": v["last_frame"][:n_global].contiguous()}
+    return v["frames"], n_grain, theta, report
+
+
+def link_labels(labels, n_local, means=None, match_tol=None, min_overlap=1, boundary="periodic", local_capacity=None,
+                global_capacity=None):
+    """Give the grains of a stack of labelled frames ids that persist from frame to frame, on the device (ggnn_link_labels;
+    include/ggnn.h states the rule, tests/linkcheck.py restates it): the grains of consecutive frames are linked by
+    their pixel overlap and the whole stack is renumbered, which is what `frames_to_samples` needs and what labelling each frame
+    on its own does not give.
+
+    labels: integer [T, ny, nx] on the device, every frame labelled on its own whatever its numbering, as `label_grains` writes
+    it: local ids first .. first + n_local[t] - 1, first = 1 ("periodic") or 2 ("noflux": id 1 is the boundary grain and stays 1),
+    0 = unfilled (it never votes and stays 0).  n_local: a device tensor or a host list of T counts.  means: float32
+    [T, K, local_capacity] on the device, 0 <= K <= 4, row b - first of frame t the mean of local grain b; with match_tol the
+    predecessor must also lie within match_tol of the grain in every channel (one fp32 subtraction each).  min_overlap: the
+    fewest shared pixels that make a candidate.  local_capacity: rows per frame (default: the row length of means, the largest
+    of a host n_local, else min(ny nx, 65536)); global_capacity: rows of the per-grain results (default min(T, 2)
+    local_capacity).
+
+    The rule: a grain's predecessor is the grain of the frame before that shares the most pixels with it (a tie: the smaller
+    id); when several grains claim one predecessor the one that shares the most keeps it (a tie: the smaller id) and the others
+    are FRESH; frame 0 keeps its ids, fresh grains are numbered after them by frame and then by local id.  A grain pinched in two
+    keeps its id on the larger part.  A grain that is absent from one frame and present in the next comes back fresh.
+
+    -> (frames int32 [T, ny, nx], n_grain, theta float32 [K, n_grain] or None, report): theta is every grain's mean in its first
+    frame (no-flux: row 0, the boundary grain's, is 0); report = {"frames": per frame a dict of n_local, n_matched, n_fresh,
+    n_split, n_gone, n_vote_overflow; "n_global"; "gid", "pred": int32 [T, local_capacity] device tensors, row b - first;
+    "first_frame", "last_frame": int32 [n_global] device tensors, row g - first}.  Device tensors in, device tensors out, ONE
+    read-back (the status); five launches whatever T and whatever the frames hold.  Raises when a vote was dropped (a grain that
+    overlaps more than 16 grains of the frame before) and on an overflow of either capacity."""
+    v = _link_checked(labels, n_local, means, match_tol, min_overlap, boundary, local_capacity, global_capacity)
+    return _link_report(v, v["status"].tolist())           # the one read-back
+
+
+def label_sequence(ids=None, angles=None, tol=None, valid=None, min_pixels=1, max_sweeps=64, boundary="periodic", match_tol=None,
+                   min_overlap=1, grain_capacity=None):
+    """A sequence of measured maps -- in-situ EBSD, serial sections, a phase-field run exported as orientations -- into grain-ID
+    images whose ids persist: `label_grains`' launches once per frame on the current stream, then `link_labels`' on the stack,
+    with nothing read back in between (every frame's number of grains goes from the labelling's status to the linking on the
+    device) and ONE read-back at the end, of the T label status rows and the link status together.
+
+    Exactly one of ids -- integer [T, ny, nx] -- and angles -- float32 [T, K, ny, nx] with tol --, on the device; valid: an
+    optional [T, ny, nx] mask; min_pixels, max_sweeps, boundary: as in `label_grains`; match_tol (angles only), min_overlap: as in
+    `link_labels`, the means being the labelling's.  grain_capacity: room per frame (default min(ny nx // min_pixels + 2, 65536)).
+
+    -> (frames, n_grain, theta, report) as `link_labels` gives them; report["label"] is the per-frame `label_grains` status.
+    Raises on n_bound_hits, as `label_grains` does, and on an overflow of a frame's labelling.  The labelling launches grow with
+    T (stacked labelling in one launch is not covered); the linking launches do not."""
+    _check_boundary(boundary)
+    if (ids is None) == (angles is None):
+        raise _lib.GGNNError("exactly one of ids and angles must be given")
+    src = ids if angles is None else angles
+    if not isinstance(src, torch.Tensor) or not src.is_cuda or src.dim() != (3 if angles is None else 4) or src.size(0) < 1:
+        raise _lib.GGNNError("ids must be a [T, ny, nx], angles a [T, K, ny, nx] device tensor")
+    T, (ny, nx) = src.size(0), src.shape[-2:]
+    if valid is not None and (not isinstance(valid, torch.Tensor) or valid.shape != (T, ny, nx)):
+        raise _lib.GGNNError("valid must be a [T, ny, nx] device mask")
+    noflux = boundary == "noflux"
+    cap = min(ny * nx // max(int(min_pixels), 1) + 2, LINK_MAX_DEFAULT_CAPACITY) if grain_capacity is None else int(grain_capacity)
+    if cap < (2 if noflux else 1):
+        raise _lib.GGNNError("grain_capacity must hold at least one grain")
+    per_frame = [_label(None if ids is None else ids[t], None if angles is None else angles[t], tol, None if valid is None else valid[t],
+                        min_pixels, max_sweeps, boundary, cap) for t in range(T)]
+    labels = torch.stack([v["image"] for v in per_frame])
+    label_status = torch.stack([v["status"] for v in per_frame])
+    n_local = label_status[:, LABEL_STATUS_WORDS.index("n_grains")].contiguous()
+    means = None
+    if angles is not None:
+        means = torch.stack([v["means"] for v in per_frame])
+        if noflux:                                         # (row 0 is the boundary grain's: local grain b is row b - 2 from here on)
+            means = means[:, :, 1:].contiguous()
+    v = _link_checked(labels, n_local, means, match_tol, min_overlap, boundary, cap - 1 if noflux else cap, None)
+    words = torch.cat([label_status.reshape(-1), v["status"]]).tolist()   # the one read-back
+    n = len(LABEL_STATUS_WORDS)
+    label_report = [dict(zip(LABEL_STATUS_WORDS, words[n * t:n * t + n])) for t in range(T)]
+    for t, s in enumerate(label_report):
+        if s["n_bound_hits"]:
+            raise _lib.GGNNError(f"ggnn_label_grains: frame {t}: {s['n_bound_hits']} threads reached the bound of a parent walk: {s}")
+        if s["overflow"]:
+            raise _lib.GGNNError(f"frame {t} has more grains than grain_capacity {cap}: {s}")
+    frames, n_grain, theta, report = _link_report(v, words[n * T:])
+    report["label"] = label_report
+    return frames, n_grain, theta, report
+
+
+def samples_from_orientation_sequence(theta_x_maps, theta_z_maps, G, R, tol, min_pixels=1, **kw):
+    """A training set from a recorded sequence of orientation maps: `label_sequence` on the two stacks of angle maps
+    ([T, ny, nx] float32 on the device, radians), the per-grain angles of every grain's first frame read back, and
+    `frames_to_samples` on the relabelled frames with everything it takes (span, patch_pixels, extra_volume, z, grid,
+    merge_radius, joint_capacity, boundary, links, max_trace); valid, max_sweeps, match_tol, min_overlap and grain_capacity go to
+    `label_sequence`.
+
+    -> (samples, report, frames): samples and report as `frames_to_samples` gives them on the returned frames; report["sequence"]
+    is `label_sequence`'s report, with the angles under "theta_x" and "theta_z" (host float32)."""
+    if (not isinstance(theta_x_maps, torch.Tensor) or not isinstance(theta_z_maps, torch.Tensor) or theta_x_maps.dim() != 3
+            or theta_x_maps.shape != theta_z_maps.shape):
+        raise _lib.GGNNError("theta_x_maps and theta_z_maps must be equal-shaped [T, ny, nx] device tensors")
+    seq_kw = {k: kw.pop(k) for k in ("valid", "max_sweeps", "match_tol", "min_overlap", "grain_capacity") if k in kw}
+    angles = torch.stack([theta_x_maps.to(torch.float32), theta_z_maps.to(torch.float32)], 1)
+    frames, n_grain, theta, sequence = label_sequence(angles=angles, tol=tol, min_pixels=min_pixels, boundary=kw.get("boundary", "periodic"),
+                                                      **seq_kw)
+    angles_host = theta.cpu().numpy()
+    samples, report = frames_to_samples(frames, angles_host[0], angles_host[1], G, R, **kw)
+    report["sequence"] = dict(sequence, theta_x=angles_host[0], theta_z=angles_host[1])
+    return samples, report, frames

@@ -1284,9 +1284,9 @@ int ggnn_track_targets(const ggnn_track_targets_args* args, ggnn_stream_t stream
  * outside [0, GGNN_LABEL_MAX_SWEEPS], grain_capacity outside [1, INT32_MAX), an unknown boundary, status or workspace not
  * 8-byte aligned, a 32-bit array not 4-byte aligned, a workspace below ggnn_label_workspace_bytes(nx, ny, K) (which is 0 for
  * sizes the call refuses).
- * Not covered: stacks of maps in one launch, ids that are consistent across the frames of a sequence, symmetry-reduced
- * misorientation (reduce the angles to a fundamental zone first: a grain that straddles the wrap of an angle comes out as two),
- * 8-connectivity, full Euler-angle triples with crystal symmetry. */
+ * Not covered: stacks of maps in one launch (a sequence is labelled frame by frame; ggnn_link_labels below then gives its
+ * grains ids that persist across the frames), symmetry-reduced misorientation (reduce the angles to a fundamental zone first: a
+ * grain that straddles the wrap of an angle comes out as two), 8-connectivity, full Euler-angle triples with crystal symmetry. */
 #define GGNN_LABEL_TILE_X 64
 #define GGNN_LABEL_TILE_Y 16
 #define GGNN_LABEL_STATUS_WORDS 9
@@ -1308,6 +1308,94 @@ typedef struct ggnn_label_args {
 } ggnn_label_args;
 size_t ggnn_label_workspace_bytes(int64_t nx, int64_t ny, int32_t K);
 int ggnn_label_grains(const ggnn_label_args* args, ggnn_stream_t stream);
+/* ------------------------------------------------------------------------------------
+ * Grain ids that PERSIST across a sequence of labelled maps: ggnn_label_grains numbers every frame by the raster order of its
+ * grains' first pixels, so the numbering changes as soon as a boundary moves or a grain vanishes, and ggnn_track_targets needs
+ * the same grain to carry the same id in every frame.  This call links the grains of consecutive frames by their pixel
+ * overlap and renumbers the whole stack, on `stream`, nothing through the host, exact in integers; tests/linkcheck.py restates
+ * the rule.
+ *   input     : labels int32 [T, ny, nx], T >= 1, frame t as ggnn_label_grains writes it (or any labelling with the same id
+ *               ranges).  first = 1 (GGNN_BC_PERIODIC) or 2 (GGNN_BC_NOFLUX: id 1 is the boundary grain and maps to itself).
+ *               n_local int64 [T] ON THE DEVICE (word 4 of a labelling's status: no read-back between the two calls); L_t =
+ *               n_local[t] clamped to [0, local_capacity].  The local grains of frame t are the ids first .. first + L_t - 1.
+ *               Pixel 0 is unfilled: it never votes and stays 0.  Every other id outside these (negative, or at or beyond
+ *               first + L_t, so anything at or beyond first + local_capacity) is treated as 0 and counted in `overflow`, a
+ *               pixel each; a frame with n_local[t] outside [0, local_capacity] counts once more.
+ *               means (optional, K > 0) float32 [T, K, local_capacity]: row b - first of frame t and channel k, at
+ *               (t K + k) local_capacity + b - first, is the mean of local grain b.
+ *   votes     : for t >= 1 and every pixel p, a = labels[t-1][p], b = labels[t][p]; when both are local grains of their
+ *               frames, vote(t, b, a) += 1.  Integers: exact whatever the order.
+ *   candidates: grain a of frame t - 1 is ELIGIBLE for grain b of frame t when vote(t, b, a) >= min_overlap (>= 1) and, when
+ *               the gate is on (use_match_tol, K > 0), fabsf(mean[t][k][b] - mean[t-1][k][a]) <= match_tol in every channel --
+ *               one fp32 subtraction each, the form of ggnn_label_grains' tol (a NaN fails it).
+ *   pred      : pred(t, b) = the eligible a with the most votes, a tie going to the smaller a; -1 when there is none, and in
+ *               frame 0.
+ *   claims    : among the b of frame t with pred(t, b) = a, the one with the largest vote(t, b, a) keeps it, a tie going to the
+ *               smaller b; every other claimant gets pred = -1 and counts in n_split.  A grain of frame t - 1 that nobody keeps
+ *               counts in n_gone of frame t.
+ *   global ids: gid(0, b) = b; gid(t, b) = gid(t-1, pred(t, b)) when pred >= 0; otherwise the grain is FRESH: fresh grains are
+ *               numbered from first + L_0 on, by ascending frame and then ascending local id.  n_global = L_0 + the number of
+ *               fresh grains (no-flux: the sequence has n_global + 1 grains, as ggnn_label_grains counts).  A grain pinched in
+ *               two keeps its id on the larger part; nothing merges ids; a grain that is absent from one frame and present in
+ *               the next comes back FRESH, under a new id; only frame t - 1 is looked at.
+ *   outputs   : frames_out int32 [T, ny, nx]: gid(t, labels[t][p]), 0 -> 0, no-flux 1 -> 1 (must not alias labels).
+ *               gid, pred int32 [T, local_capacity], row b - first; rows from L_t on: 0 and -1.
+ *               first_frame, last_frame int32 [global_capacity], row g - first of global grain g: the first frame that holds
+ *               it and the last of the unbroken run that does; theta (K > 0) float32 [K, global_capacity]: the grain's mean
+ *               in its first frame, copied, not recomputed.  Rows from n_global on: -1, -1 and 0.
+ *               n_global > global_capacity adds 1 to `overflow`: the images are still complete, the per-grain rows hold the
+ *               first global_capacity grains.
+ *   status    : int64 [GGNN_LINK_FRAME_WORDS T + GGNN_LINK_GLOBAL_WORDS], zeroed by the call.  Per frame t, at
+ *               GGNN_LINK_FRAME_WORDS t: n_local (L_t), n_matched, n_fresh (the split ones included; 0 in frame 0), n_split,
+ *               n_gone, n_vote_overflow; then n_global and overflow.
+ * ggnn_link_labels = at most six memsets and five launches (three with T = 1: there is no pair to vote on), whatever T > 1
+ * and whatever the images hold:
+ *   votes     every (frame t >= 1, local grain) owns GGNN_LINK_SLOTS slots of (key a, count) in the workspace.  A thread takes
+ *             GGNN_LINK_RUN consecutive pixels of a row, merges equal consecutive (b, a) pairs and spends one probe of at most
+ *             GGNN_LINK_SLOTS slots a distinct pair: atomicCAS on the key, atomicAdd on the count.  A vote that finds
+ *             GGNN_LINK_SLOTS other keys is dropped and its pixels are counted in n_vote_overflow of its frame: the results are
+ *             defined only when that word is 0 in every frame (a grain that overlaps more than GGNN_LINK_SLOTS grains of the
+ *             frame before: the frames are too far apart).
+ *   match     a thread per (t, b): the slots, the gates, the argmax; a 64-bit atomicMax of (vote << 32) | (0xFFFFFFFF - b) on
+ *             the claim word of (t - 1, a): the winner does not depend on the order.
+ *   resolve   a thread per (t, b) keeps pred only if the claim word names it; n_split, n_gone; the unused rows.
+ *   compose   one workgroup walks t = 0 .. T - 1 over grain rows, a block scan over the fresh flags in chunks; n_global.
+ *   relabel   a thread per pixel.
+ * No kernel waits on another workgroup; every loop is bounded by T, local_capacity and the pixels; nothing outside the named
+ * arrays is addressed, whatever the inputs hold; counters are integer atomics and no result is ordered by one; the call can
+ * be captured, and a replay gives the same bits.
+ * GGNN_EINVAL without a launch: args, labels, n_local, frames_out, gid, pred, first_frame, last_frame, status or workspace
+ * NULL, T < 1, nx or ny outside [3, 2^15), local_capacity or global_capacity outside [1, INT32_MAX), T local_capacity beyond
+ * 2^36, K outside [0, 4], with K > 0 means or theta NULL, min_overlap < 1, use_match_tol with K = 0 or with match_tol not
+ * >= 0, an unknown boundary, n_local, status or workspace not 8-byte aligned, a 32-bit array not 4-byte aligned, a workspace
+ * below ggnn_link_workspace_bytes(T, local_capacity, K) (which is 0 for sizes the call refuses).
+ * Not covered: merging grains (two grains that become one: the smaller one is gone), a grain that reappears keeping its id,
+ * matching across more than one frame back, crystal symmetry in the gate, labelling the stack in one launch. */
+#define GGNN_LINK_SLOTS 16
+#define GGNN_LINK_RUN 4
+#define GGNN_LINK_FRAME_WORDS 6
+#define GGNN_LINK_GLOBAL_WORDS 2
+typedef struct ggnn_link_labels_args {
+  const int32_t* labels;         /* [T, ny, nx], device */
+  const int64_t* n_local;        /* [T], device */
+  const float* means;            /* [T, K, local_capacity], device, or NULL with K = 0 */
+  int32_t* frames_out;           /* [T, ny, nx] out */
+  int32_t* gid;                  /* [T, local_capacity] out */
+  int32_t* pred;                 /* [T, local_capacity] out */
+  int32_t* first_frame;          /* [global_capacity] out */
+  int32_t* last_frame;           /* [global_capacity] out */
+  float* theta;                  /* [K, global_capacity] out (NULL with K = 0) */
+  int64_t* status;               /* [GGNN_LINK_FRAME_WORDS T + GGNN_LINK_GLOBAL_WORDS] out */
+  void* workspace;               /* ggnn_link_workspace_bytes(T, local_capacity, K) of device scratch */
+  size_t workspace_bytes;
+  int64_t T, nx, ny, local_capacity, global_capacity, min_overlap;
+  float match_tol;
+  int32_t use_match_tol;         /* 0: overlap alone */
+  int32_t K;                     /* channels of means */
+  int32_t boundary;              /* GGNN_BC_PERIODIC / GGNN_BC_NOFLUX */
+} ggnn_link_labels_args;
+size_t ggnn_link_workspace_bytes(int64_t T, int64_t local_capacity, int32_t K);
+int ggnn_link_labels(const ggnn_link_labels_args* args, ggnn_stream_t stream);
 /* The host-side topology update those counts trigger: one call of the reference's `Cmodel.update`
  * (models.py:612-842 with delete_grain_index :861-893, switching_edge_index :896-1051, point_in_triangle :1055-1070,
  * periodic_move :1103-1106), nucleation off.  HOST memory throughout, no stream: grains of `grain_event` (those below the

@@ -51,7 +51,19 @@ Voronoi map of size^2 / 8192 cells with 1 % of the pixels non-indexed or wrong (
 The arms alternate within a round; median of the rounds after three warm-up rounds.  Then the device activities of one call
 for both maps (they must not differ: the launches do not depend on the content), the traffic floor of every launch (the bytes
 it must move / 8 TB/s), and, where the tracer is there, the device time of every kernel.
-    python tools/vectorize_cost.py --label [--rounds 20] [--size 4096] [--host-rounds 2] [--no-host]"""
+    python tools/vectorize_cost.py --label [--rounds 20] [--size 4096] [--host-rounds 2] [--no-host]
+--link times giving the grains of a labelled sequence ids that persist (vectorize.link_labels / label_sequence, ggnn_link_labels),
+in ids mode on two sequences: the seven recorded frames of tests/golden/pf_frames_cfg1.npz (501 x 501, 118 grains falling to
+100) and --track's drift sequence of 64 frames of --size x --size (128 when not given) with 121 grains; and prints
+  call       ggnn_link_labels on prepared arguments (the stack labelled frame by frame on the device before), by events
+  link       one link_labels on that stack with its read-back, by the host clock
+  host       the only route before it, by the host clock: the labelled stack read back, the votes as one numpy bincount a pair
+             of frames and the matcher of the restatement (tests/linkcheck.py), the relabelled stack uploaded
+  sequence   one label_sequence, the labelling of every frame included, by the host clock
+The arms alternate within a round; median of the rounds after three warm-up rounds.  Then the device activities of one call
+at T = 2 and at T (they must not differ).  --no-host leaves the host arm out (a profiler's run: per-launch times come from
+rocprofv3 --kernel-trace --stats around this tool).
+    python tools/vectorize_cost.py --link [--rounds 20] [--size 128] [--no-host]"""
 import argparse
 import ctypes
 import os
@@ -70,12 +82,15 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--trace", action="store_true", help="the links=\"trace\" arms")
     ap.add_argument("--label", action="store_true", help="the cost of label_grains")
+    ap.add_argument("--link", action="store_true", help="the cost of link_labels and label_sequence")
     ap.add_argument("--host-rounds", type=int, default=2, help="--label: timed rounds of the host route on the large map")
     ap.add_argument("--no-host", action="store_true", help="--label: leave the host route out (a profiler's run)")
     a = ap.parse_args()
     sys.path[:0] = [os.path.dirname(HERE)]
     if a.size is None:
-        a.size = 128 if a.union or a.track else 4096
+        a.size = 128 if a.union or a.track or a.link else 4096
+    if a.link:
+        return link_cost(a)
     if a.label:
         return label_cost(a)
     if a.track:
@@ -414,6 +429,96 @@ def track_cost(a):
         except Exception as exc:   # (a build of torch without the tracer)
             print(f"# launches not counted: {type(exc).__name__}: {exc}", flush=True)
         print(f"# torch {torch.__version__}, {torch.cuda.get_device_name()}", flush=True)
+
+
+def link_cost(a):
+    import time
+    import numpy as np
+    import torch
+    sys.path[:0] = [os.path.join(os.path.dirname(HERE), "tests")]
+    import linkcheck as lk
+    from graingraphnn_amd import _lib
+    from graingraphnn_amd import vectorize as vz
+    dev = torch.device("cuda", 0)
+    lib = _lib.load()
+    d = np.load(os.path.join(os.path.dirname(HERE), "tests", "golden", "pf_frames_cfg1.npz"))
+    sequences = {"recorded, 7 frames 501 x 501": torch.from_numpy(d["frames"].astype(np.int32)).to(dev),
+                 f"drift, 64 frames {a.size} x {a.size}": lattice_frames(64, a.size, a.seed, dev)}
+
+    def by_events(call):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        call()
+        t1.record()
+        t1.synchronize()
+        return t0.elapsed_time(t1) * 1e3
+
+    def by_clock(call):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        call()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e6
+
+    for name, ids in sequences.items():
+        T, ny, nx = ids.shape
+        cap = 256                                                   # room per frame: both sequences hold fewer than 128 grains
+        per_frame = [vz._label(ids[t], None, None, None, 1, 64, "periodic", cap) for t in range(T)]
+        labels = torch.stack([v["image"] for v in per_frame])
+        n_local = torch.stack([v["status"] for v in per_frame])[:, 4].contiguous()
+
+        def host_route():
+            r = lk.link(labels.cpu().numpy(), n_local.tolist(), local_capacity=cap)
+            out = torch.from_numpy(r["frames"]).to(dev)
+            torch.cuda.synchronize()
+            return out, r
+
+        frames, n_grain, _, report = vz.link_labels(labels, n_local, local_capacity=cap)
+        whole = {n: vz._link_checked(labels[:n].contiguous(), n_local[:n].contiguous(), None, None, 1, "periodic", cap, None) for n in sorted({2, T})}
+        torch.cuda.synchronize()
+        A = whole[T]["calls"][0]
+        total = {k: sum(s[k] for s in report["frames"]) for k in vz.LINK_FRAME_WORDS[1:]}
+        print(f"# {name}: {report['frames'][0]['n_local']} grains falling to {report['frames'][-1]['n_local']}, {n_grain} global; totals "
+              f"{total}; workspace {lib.ggnn_link_workspace_bytes(T, cap, 0) / 1e6:.2f} MB", flush=True)
+        if not a.no_host:
+            h_frames, r = host_route()
+            print(f"# the host route gives the same frames: {bool(torch.equal(h_frames, frames))}; status equal: "
+                  f"{r['status'] == report['frames']}", flush=True)
+        arms = {"call": lambda: by_events(lambda: _lib.check(lib.ggnn_link_labels(ctypes.byref(A), _lib.current_stream()), "link")),
+                "link": lambda: by_clock(lambda: vz.link_labels(labels, n_local, local_capacity=cap)),
+                "host": lambda: by_clock(host_route),
+                "sequence": lambda: by_clock(lambda: vz.label_sequence(ids=ids, grain_capacity=cap))}
+        if a.no_host:
+            del arms["host"]
+        times = {k: [] for k in arms}
+        for rnd in range(a.rounds + 3):
+            for arm, call in arms.items():
+                t = call()
+                if rnd >= 3:
+                    times[arm].append(t)
+        for arm, t in times.items():
+            t = np.array(t)
+            print(f"{arm:8s} us ({len(t)} rounds): median {np.median(t):12.1f}  min {t.min():12.1f}  max {t.max():12.1f}", flush=True)
+        if not a.no_host:
+            print(f"# host / link = {np.median(times['host']) / np.median(times['link']):.1f}", flush=True)
+        try:
+            from torch.profiler import ProfilerActivity, profile
+            for n in sorted(whole):
+                An = whole[n]["calls"][0]
+                with profile(activities=[ProfilerActivity.CUDA]) as prof:
+                    _lib.check(lib.ggnn_link_labels(ctypes.byref(An), _lib.current_stream()), "link")
+                    torch.cuda.synchronize()
+                k = sum(1 for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA)
+                print(f"T = {n:3d}  device activities (kernels, memsets) of one call: {k}", flush=True)
+                if n == T:
+                    for e in sorted(prof.key_averages(), key=lambda e: e.key):
+                        t = getattr(e, "device_time_total", None)
+                        t = getattr(e, "cuda_time_total", 0.0) if t is None else t
+                        if t:
+                            print(f"    {e.count:3d} x {e.key[:110]}: {t:.1f} us by the tracer", flush=True)
+        except Exception as exc:   # (a build of torch without the tracer)
+            print(f"# launches not counted: {type(exc).__name__}: {exc}", flush=True)
+    print(f"# torch {torch.__version__}, {torch.cuda.get_device_name()}", flush=True)
 
 
 def label_floor(nx, ny, K, status, max_sweeps):
