@@ -31,6 +31,7 @@ GGNN_INTERP_MAX_JOBS = 256
 GGNN_JUNCTION_SEGMENT, GGNN_JUNCTION_STATUS_WORDS, GGNN_JUNCTION_MAX_BLOCKS = 256, 7, 1 << 22
 GGNN_TRACE_COUNTERS = 3
 GGNN_LABEL_TILE_X, GGNN_LABEL_TILE_Y, GGNN_LABEL_STATUS_WORDS, GGNN_LABEL_MAX_SWEEPS = 64, 16, 9, 1024
+GGNN_SYM_NONE, GGNN_SYM_CUBIC, GGNN_ORIENT_OPS, GGNN_ORIENT_H = 0, 1, 24, 0.70710678
 GGNN_LINK_SLOTS, GGNN_LINK_RUN, GGNN_LINK_FRAME_WORDS, GGNN_LINK_GLOBAL_WORDS = 16, 4, 6, 2
 GGNN_ADAM_CHUNK, GGNN_ADAM_MAX_TENSORS, GGNN_ADAM_MAX_GROUPS = 4096, 384, 8
 GGNN_ROWGEMM_MAX_PACK = 8
@@ -67,6 +68,7 @@ EXPORTED_SYMBOLS = (
     "ggnn_image_junctions_traj", "ggnn_junction_links_traj", "ggnn_track_junctions", "ggnn_track_targets",
     "ggnn_image_junction_windows_traj", "ggnn_junction_links_trace_traj",
     "ggnn_label_workspace_bytes", "ggnn_label_grains", "ggnn_link_workspace_bytes", "ggnn_link_labels",
+    "ggnn_label_orient_workspace_bytes", "ggnn_label_orientations",
     "ggnn_metric_record",
     "ggnn_masked_mse_rows", "ggnn_collate_batch", "ggnn_reverse_slots",
 )
@@ -512,6 +514,16 @@ class LabelArgs(Structure):
     ]
 
 
+class LabelOrientArgs(Structure):
+    """Mirror of `ggnn_label_orient_args`."""
+    _fields_ = [
+        ("quats", c_void_p), ("valid", c_void_p), ("image", c_void_p), ("mean_quats", c_void_p),
+        ("status", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_size_t),
+        ("nx", c_int64), ("ny", c_int64), ("grain_capacity", c_int64), ("min_pixels", c_int64),
+        ("cos_half_tol", c_float), ("symmetry", c_int32), ("max_sweeps", c_int32), ("boundary", c_int32),
+    ]
+
+
 class LinkLabelsArgs(Structure):
     """Mirror of `ggnn_link_labels_args` (`LinkArgs` is the junction linking's)."""
     _fields_ = [
@@ -700,6 +712,10 @@ def _declare(lib):
     lib.ggnn_label_workspace_bytes.argtypes = [c_int64, c_int64, c_int32]
     lib.ggnn_label_grains.restype = c_int
     lib.ggnn_label_grains.argtypes = [POINTER(LabelArgs), c_void_p]
+    lib.ggnn_label_orient_workspace_bytes.restype = c_size_t
+    lib.ggnn_label_orient_workspace_bytes.argtypes = [c_int64, c_int64]
+    lib.ggnn_label_orientations.restype = c_int
+    lib.ggnn_label_orientations.argtypes = [POINTER(LabelOrientArgs), c_void_p]
     lib.ggnn_link_workspace_bytes.restype = c_size_t
     lib.ggnn_link_workspace_bytes.argtypes = [c_int64, c_int64, c_int32]
     lib.ggnn_link_labels.restype = c_int

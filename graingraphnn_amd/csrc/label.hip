@@ -12,6 +12,10 @@
 //             one that assigned nothing returns on a device word
 //   rank      block sums, scan of the sums, add (and the means, at the roots); then the image
 //
+// ggnn_label_orientations (full orientations under cubic symmetry; tests/orientcheck.py) runs the same stages with K = 0 behind
+// a links kernel of its own (the disorientation of two quaternions in closed form), and adds three launches: the sums zeroed at
+// the roots and every closed pixel aligned to its root and accumulated (after classify), the means normalised (after the rank).
+//
 // No kernel waits on another workgroup: the order between workgroups is the order of the launches.  Every loop that follows
 // parents carries a budget of hops derived from the number of pixels; a thread that spends it counts itself in n_bound_hits
 // and leaves.  Parent words that another workgroup may write in the same launch (the seam merge) are read and written with
@@ -488,6 +492,152 @@ __global__ __launch_bounds__(LABEL_BLOCK) void label_image_kernel(const int32_t*
   count_to(status + ST_UNFILLED, unfilled);
 }
 
+// ---- orientations under crystal symmetry (ggnn_label_orientations) ------------------------------------------------------------
+// The links byte decided from quaternions, and the per-grain mean quaternion; every stage between is the one above with K = 0.
+struct Quat {
+  float w, x, y, z;
+};
+__constant__ float ORIENT_OPS[GGNN_ORIENT_OPS][4] = {
+    {1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1},
+    {GGNN_ORIENT_H, GGNN_ORIENT_H, 0, 0}, {GGNN_ORIENT_H, -GGNN_ORIENT_H, 0, 0}, {GGNN_ORIENT_H, 0, GGNN_ORIENT_H, 0},
+    {GGNN_ORIENT_H, 0, -GGNN_ORIENT_H, 0}, {GGNN_ORIENT_H, 0, 0, GGNN_ORIENT_H}, {GGNN_ORIENT_H, 0, 0, -GGNN_ORIENT_H},
+    {0, GGNN_ORIENT_H, GGNN_ORIENT_H, 0}, {0, GGNN_ORIENT_H, -GGNN_ORIENT_H, 0}, {0, GGNN_ORIENT_H, 0, GGNN_ORIENT_H},
+    {0, GGNN_ORIENT_H, 0, -GGNN_ORIENT_H}, {0, 0, GGNN_ORIENT_H, GGNN_ORIENT_H}, {0, 0, GGNN_ORIENT_H, -GGNN_ORIENT_H},
+    {0.5f, 0.5f, 0.5f, 0.5f}, {0.5f, 0.5f, 0.5f, -0.5f}, {0.5f, 0.5f, -0.5f, 0.5f}, {0.5f, 0.5f, -0.5f, -0.5f},
+    {0.5f, -0.5f, 0.5f, 0.5f}, {0.5f, -0.5f, 0.5f, -0.5f}, {0.5f, -0.5f, -0.5f, 0.5f}, {0.5f, -0.5f, -0.5f, -0.5f}};
+
+__device__ __forceinline__ Quat quat_load(const float* __restrict__ quats, int64_t p, int64_t N) {
+  return Quat{quats[p], quats[N + p], quats[2 * N + p], quats[3 * N + p]};
+}
+__device__ __forceinline__ Quat quat_conj(const Quat& q) { return Quat{q.w, -q.x, -q.y, -q.z}; }
+// the header's one product: four products a component, combined left to right, each operation rounded on its own
+__device__ __forceinline__ float quat_mul_w(const Quat& p, const Quat& q) {
+  return __fsub_rn(__fsub_rn(__fsub_rn(__fmul_rn(p.w, q.w), __fmul_rn(p.x, q.x)), __fmul_rn(p.y, q.y)), __fmul_rn(p.z, q.z));
+}
+__device__ __forceinline__ Quat quat_mul(const Quat& p, const Quat& q) {
+  Quat r;
+  r.w = quat_mul_w(p, q);
+  r.x = __fsub_rn(__fadd_rn(__fadd_rn(__fmul_rn(p.w, q.x), __fmul_rn(p.x, q.w)), __fmul_rn(p.y, q.z)), __fmul_rn(p.z, q.y));
+  r.y = __fadd_rn(__fadd_rn(__fsub_rn(__fmul_rn(p.w, q.y), __fmul_rn(p.x, q.z)), __fmul_rn(p.y, q.w)), __fmul_rn(p.z, q.x));
+  r.z = __fadd_rn(__fsub_rn(__fadd_rn(__fmul_rn(p.w, q.z), __fmul_rn(p.x, q.y)), __fmul_rn(p.y, q.x)), __fmul_rn(p.z, q.w));
+  return r;
+}
+__device__ __forceinline__ bool quat_valid(const Quat& q, const uint8_t* __restrict__ mask, int64_t p) {
+  if (mask && !mask[p]) return false;
+  const float n = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(q.w, q.w), __fmul_rn(q.x, q.x)), __fmul_rn(q.y, q.y)), __fmul_rn(q.z, q.z));
+  return fabsf(__fsub_rn(n, 1.0f)) <= 1e-3f;   // (NaN and inf fail the comparison)
+}
+// cos of half the disorientation of two valid pixels: the largest |w| of r over the group, in closed form
+__device__ __forceinline__ float quat_alike(const Quat& a, const Quat& b, bool cubic) {
+  const Quat r = quat_mul(quat_conj(a), b);
+  if (!cubic) return fabsf(r.w);
+  float m1 = fabsf(r.w), m2 = fabsf(r.x), m3 = fabsf(r.y), m4 = fabsf(r.z), t;
+#define GGNN_ORDER(hi, lo) t = fmaxf(hi, lo), lo = fminf(hi, lo), hi = t
+  GGNN_ORDER(m1, m2);
+  GGNN_ORDER(m3, m4);
+  GGNN_ORDER(m1, m3);
+  GGNN_ORDER(m2, m4);
+  GGNN_ORDER(m2, m3);
+#undef GGNN_ORDER
+  const float s12 = __fadd_rn(m1, m2);
+  return fmaxf(m1, fmaxf(__fmul_rn(s12, GGNN_ORIENT_H), __fmul_rn(0.5f, __fadd_rn(s12, __fadd_rn(m3, m4)))));
+}
+
+__global__ __launch_bounds__(LABEL_BLOCK) void orient_links_kernel(const float* __restrict__ quats, const uint8_t* __restrict__ mask,
+                                                                   uint8_t* __restrict__ links, LabelDims D, float cos_half_tol,
+                                                                   bool cubic) {
+  const int64_t N = D.N;
+  for (int64_t p = (int64_t)blockIdx.x * LABEL_BLOCK + threadIdx.x; p < N; p += (int64_t)gridDim.x * LABEL_BLOCK) {
+    uint8_t b = 0;
+    const Quat a = quat_load(quats, p, N);
+    if (quat_valid(a, mask, p)) {
+      b = LINK_VALID;
+      const int x = (int)(p % D.nx), y = (int)(p / D.nx);
+      if (x + 1 < D.nx || D.periodic) {
+        const int64_t q = (int64_t)y * D.nx + (x + 1 < D.nx ? x + 1 : 0);
+        const Quat o = quat_load(quats, q, N);
+        if (quat_valid(o, mask, q) && quat_alike(a, o, cubic) >= cos_half_tol) b |= LINK_RIGHT;
+      }
+      if (y + 1 < D.ny || D.periodic) {
+        const int64_t q = (int64_t)(y + 1 < D.ny ? y + 1 : 0) * D.nx + x;
+        const Quat o = quat_load(quats, q, N);
+        if (quat_valid(o, mask, q) && quat_alike(a, o, cubic) >= cos_half_tol) b |= LINK_DOWN;
+      }
+    }
+    links[p] = b;
+  }
+}
+
+// after classify: lab[p] == p at the roots of the closed components; their four sums, sums[4 root + k], start from 0
+__global__ __launch_bounds__(LABEL_BLOCK) void orient_zero_kernel(const int32_t* __restrict__ lab, long long* __restrict__ sums, LabelDims D) {
+  for (int64_t p = (int64_t)blockIdx.x * LABEL_BLOCK + threadIdx.x; p < D.N; p += (int64_t)gridDim.x * LABEL_BLOCK)
+    if (lab[p] == (int)p)
+      for (int k = 0; k < 4; ++k) sums[4 * p + k] = 0;
+}
+
+// A thread a pixel, consecutive lanes consecutive raster indices.  A closed pixel (lab >= 0: a pixel of an original component)
+// is aligned to its root's equivalent; a wave sums every run of lanes with one root towards the run's first lane -- 64 values
+// below 2^24 (1 + 1e-3) fit 32 bits -- and that lane adds the four sums to the root's.  Integers: no order shows in the result.
+__global__ __launch_bounds__(LABEL_BLOCK) void orient_accumulate_kernel(const float* __restrict__ quats, const int32_t* __restrict__ lab,
+                                                                        long long* sums, LabelDims D, int n_ops) {
+  const int lane = threadIdx.x & 63;
+  const int64_t N = D.N;
+  for (int64_t base = (int64_t)blockIdx.x * LABEL_BLOCK; base < N; base += (int64_t)gridDim.x * LABEL_BLOCK) {   // (uniform in the block)
+    const int64_t p = base + threadIdx.x;
+    int key = -1, v[4] = {0, 0, 0, 0};
+    if (p < N) {
+      const int root = lab[p];
+      if ((unsigned)root < (unsigned)D.N) {
+        key = root;
+        const Quat q = quat_load(quats, p, N);
+        const Quat r = quat_mul(quat_conj(quat_load(quats, root, N)), q);
+        Quat s{ORIENT_OPS[0][0], ORIENT_OPS[0][1], ORIENT_OPS[0][2], ORIENT_OPS[0][3]};
+        float c = quat_mul_w(r, s), best = fabsf(c);
+        for (int i = 1; i < n_ops; ++i) {
+          const Quat si{ORIENT_OPS[i][0], ORIENT_OPS[i][1], ORIENT_OPS[i][2], ORIENT_OPS[i][3]};
+          const float ci = quat_mul_w(r, si);
+          if (fabsf(ci) > best) best = fabsf(ci), c = ci, s = si;   // (strictly: the first of the largest)
+        }
+        const Quat a = quat_mul(q, s);
+        const float sign = c < 0.0f ? -16777216.0f : 16777216.0f;
+        v[0] = (int)__float2ll_rn(__fmul_rn(a.w, sign)), v[1] = (int)__float2ll_rn(__fmul_rn(a.x, sign));
+        v[2] = (int)__float2ll_rn(__fmul_rn(a.y, sign)), v[3] = (int)__float2ll_rn(__fmul_rn(a.z, sign));
+      }
+    }
+    const int before = __shfl_up(key, 1);
+    const bool head = lane == 0 || before != key;
+    const unsigned long long heads = __ballot(head);
+    const unsigned long long above = lane == 63 ? 0ull : heads >> (lane + 1);
+    const int end = above ? lane + __ffsll((long long)above) : 64;    // the first lane of the next run
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int o = __shfl_down(v[k], d);
+        if (lane + d < end) v[k] += o;
+      }
+    if (head && key >= 0)
+      for (int k = 0; k < 4; ++k) atomicAdd((unsigned long long*)(sums + 4 * (int64_t)key + k), (unsigned long long)(long long)v[k]);
+  }
+}
+
+// after the rank: the mean of grain root p at row rank[p] (+ 1 with walls, where row 0 is the boundary grain's identity)
+__global__ __launch_bounds__(LABEL_BLOCK) void orient_means_kernel(const float* __restrict__ quats, const int32_t* __restrict__ lab,
+                                                                   const int32_t* __restrict__ rank, const long long* __restrict__ sums,
+                                                                   float* __restrict__ means, LabelDims D, int64_t capacity, int noflux) {
+  if (noflux && blockIdx.x == 0 && threadIdx.x < 4) means[(int64_t)threadIdx.x * capacity] = threadIdx.x == 0 ? 1.0f : 0.0f;
+  for (int64_t p = (int64_t)blockIdx.x * LABEL_BLOCK + threadIdx.x; p < D.N; p += (int64_t)gridDim.x * LABEL_BLOCK) {
+    if (lab[p] != (int)p) continue;
+    const int64_t g = (int64_t)rank[p] + noflux;
+    if (g >= capacity) continue;
+    double d[4];
+    for (int k = 0; k < 4; ++k) d[k] = (double)sums[4 * p + k];
+    const double n2 = __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(d[0], d[0]), __dmul_rn(d[1], d[1])), __dmul_rn(d[2], d[2])), __dmul_rn(d[3], d[3]));
+    const double len = __dsqrt_rn(n2);
+    for (int k = 0; k < 4; ++k) means[(int64_t)k * capacity + g] = n2 == 0.0 ? quats[(int64_t)k * D.N + p] : (float)__ddiv_rn(d[k], len);
+  }
+}
+
 }  // namespace ggnn
 
 extern "C" size_t ggnn_label_workspace_bytes(int64_t nx, int64_t ny, int32_t K) {
@@ -543,6 +693,64 @@ extern "C" int ggnn_label_grains(const ggnn_label_args* args, ggnn_stream_t stre
   hipLaunchKernelGGL(label_rank_scan_kernel, dim3(1), block, 0, st, W.bsum, chunks, A.status, A.mean_angles, A.K, A.grain_capacity, noflux);
   hipLaunchKernelGGL(label_rank_add_kernel, dim3((unsigned)chunks), block, 0, st, W.lab, W.bsum, W.size, W.sums, W.rank, A.mean_angles, D,
                      A.grain_capacity, noflux);
+  hipLaunchKernelGGL(label_image_kernel, pass, block, 0, st, W.lab, W.rank, A.image, A.status, D, D.periodic ? 1 : 2);
+  return launch_status();
+}
+
+extern "C" size_t ggnn_label_orient_workspace_bytes(int64_t nx, int64_t ny) {
+  if (nx < 3 || ny < 3 || nx >= (1 << 15) || ny >= (1 << 15)) return 0;
+  return ggnn::label_carve(nullptr, nullptr, nx * ny, 4);
+}
+
+extern "C" int ggnn_label_orientations(const ggnn_label_orient_args* args, ggnn_stream_t stream) {
+  using namespace ggnn;
+  if (!args) return GGNN_EINVAL;
+  const ggnn_label_orient_args& A = *args;
+  if (!A.quats || !A.image || !A.mean_quats || !A.status || !A.workspace) return GGNN_EINVAL;
+  if (A.nx < 3 || A.ny < 3 || A.nx >= (1 << 15) || A.ny >= (1 << 15)) return GGNN_EINVAL;
+  if (!(A.cos_half_tol > GGNN_ORIENT_H && A.cos_half_tol <= 1.0f)) return GGNN_EINVAL;
+  if (A.symmetry != GGNN_SYM_NONE && A.symmetry != GGNN_SYM_CUBIC) return GGNN_EINVAL;
+  if (A.min_pixels < 1 || A.max_sweeps < 0 || A.max_sweeps > GGNN_LABEL_MAX_SWEEPS) return GGNN_EINVAL;
+  if (A.grain_capacity < 1 || A.grain_capacity >= INT32_MAX) return GGNN_EINVAL;
+  if (A.boundary != GGNN_BC_PERIODIC && A.boundary != GGNN_BC_NOFLUX) return GGNN_EINVAL;
+  if ((reinterpret_cast<uintptr_t>(A.status) & 7u) || (reinterpret_cast<uintptr_t>(A.workspace) & 7u) ||
+      (reinterpret_cast<uintptr_t>(A.image) & 3u) || (reinterpret_cast<uintptr_t>(A.quats) & 3u) ||
+      (reinterpret_cast<uintptr_t>(A.mean_quats) & 3u))
+    return GGNN_EINVAL;
+  const int64_t N = A.nx * A.ny;
+  LabelWs W;
+  if (A.workspace_bytes < label_carve(&W, (char*)A.workspace, N, 4)) return GGNN_EINVAL;
+  const LabelDims D{(int)A.nx, (int)A.ny, (int)N, 0, A.boundary == GGNN_BC_PERIODIC};   // K = 0: the stages carry no angle sums
+  const int noflux = D.periodic ? 0 : 1;
+  const bool cubic = A.symmetry == GGNN_SYM_CUBIC;
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(A.status, 0, GGNN_LABEL_STATUS_WORDS * sizeof(int64_t), st) != hipSuccess) return GGNN_ELAUNCH;
+  if (hipMemsetAsync(W.words, 0, label_words_bytes(), st) != hipSuccess) return GGNN_ELAUNCH;
+  const int64_t wide = std::min<int64_t>((N + LABEL_BLOCK - 1) / LABEL_BLOCK, 16 * (int64_t)num_cu());
+  const dim3 pass((unsigned)wide), block(LABEL_BLOCK);
+  hipLaunchKernelGGL(orient_links_kernel, pass, block, 0, st, A.quats, A.valid, W.links, D, A.cos_half_tol, cubic);
+  const int tiles_x = (D.nx + LABEL_TX - 1) / LABEL_TX, tiles_y = (D.ny + LABEL_TY - 1) / LABEL_TY;
+  hipLaunchKernelGGL(label_tile_kernel, dim3((unsigned)(tiles_x * tiles_y)), block, (size_t)LABEL_TILE * 8, st, (const float*)nullptr,
+                     W.links, W.parent, W.size, W.sums, A.status, D, tiles_x);
+  const int64_t seams = (int64_t)D.ny * tiles_x + (int64_t)D.nx * tiles_y;
+  hipLaunchKernelGGL(label_seam_kernel, dim3((unsigned)std::min<int64_t>((seams + LABEL_BLOCK - 1) / LABEL_BLOCK, wide)), block, 0, st,
+                     W.links, W.parent, A.status, D, tiles_x, tiles_y);
+  hipLaunchKernelGGL(label_flatten_kernel, pass, block, 0, st, W.links, W.parent, W.size, W.sums, W.lab, A.status, D);
+  hipLaunchKernelGGL(label_classify_kernel, pass, block, 0, st, W.links, W.size, W.lab, W.list, W.open, A.status, D, A.min_pixels);
+  hipLaunchKernelGGL(orient_zero_kernel, pass, block, 0, st, W.lab, W.sums, D);      // (lab still marks the open pixels with -1)
+  hipLaunchKernelGGL(orient_accumulate_kernel, pass, block, 0, st, A.quats, W.lab, W.sums, D, cubic ? GGNN_ORIENT_OPS : 1);
+  int32_t* pend = W.parent;
+  const dim3 few((unsigned)std::min<int64_t>(wide, 2 * (int64_t)num_cu()));
+  for (int s = 0; s < A.max_sweeps; ++s) {
+    hipLaunchKernelGGL(label_decide_kernel, few, block, 0, st, W.lab, W.list, W.open, pend, W.words, D, s);
+    hipLaunchKernelGGL(label_commit_kernel, few, block, 0, st, W.lab, W.list, W.open, pend, W.words, A.status, D, s);
+  }
+  const int64_t chunks = (N + SCAN_CHUNK - 1) / SCAN_CHUNK;
+  hipLaunchKernelGGL(label_rank_sums_kernel, dim3((unsigned)chunks), block, 0, st, W.lab, W.bsum, D);
+  hipLaunchKernelGGL(label_rank_scan_kernel, dim3(1), block, 0, st, W.bsum, chunks, A.status, (float*)nullptr, 0, A.grain_capacity, noflux);
+  hipLaunchKernelGGL(label_rank_add_kernel, dim3((unsigned)chunks), block, 0, st, W.lab, W.bsum, W.size, W.sums, W.rank, (float*)nullptr, D,
+                     A.grain_capacity, noflux);
+  hipLaunchKernelGGL(orient_means_kernel, pass, block, 0, st, A.quats, W.lab, W.rank, W.sums, A.mean_quats, D, A.grain_capacity, noflux);
   hipLaunchKernelGGL(label_image_kernel, pass, block, 0, st, W.lab, W.rank, A.image, A.status, D, D.periodic ? 1 : 2);
   return launch_status();
 }

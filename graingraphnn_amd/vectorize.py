@@ -43,11 +43,19 @@ per-grain mean angles as exact fixed-point sums -- on the device, exact in integ
 with `sample_from_image`.  One wrong pixel on a boundary no longer drops a frame: it is repaired before the vectoriser,
 whose own contract -- an invalid structure is reported, not repaired -- stands.
 
+An EBSD map carries a full orientation per pixel, a Bunge triple that the indexing software reports as any of the 24 cubic
+equivalents, changing from pixel to pixel inside one grain.  `label_orientations` (ggnn_label_orientations;
+tests/orientcheck.py) is `label_grains` with the link decided by the disorientation of two neighbouring quaternions
+under the cubic group, and a symmetry-aware mean orientation per grain; `quaternions_from_bunge` makes its input,
+`growth_angles` turns a mean orientation into the model's theta_x and theta_z (the <100> direction nearest the sample's z),
+`sample_from_euler_map` chains them with `sample_from_image`, and `label_orientation_sequence` /
+`samples_from_euler_sequence` do for a series of such maps what `label_sequence` / `samples_from_orientation_sequence` do below.
+
 Not covered: stacks of mixed image shapes, resolving a quadruple from a history (the diagonal is fixed, and counted in the
 status), the reference's `edge` length target (its edge_len head is disabled in every shipped configuration) and its
 `elim_list` scaling of shrinking grains (commented out in the reference); for the labelling: stacks of maps in one launch,
-symmetry-reduced misorientation, 8-connectivity, Euler-angle triples with crystal symmetry; for the linking: merging grains, a
-grain that reappears keeping its id, matching across more than one frame back, crystal symmetry in the gate.
+8-connectivity, hexagonal and other symmetry groups; for the linking: merging grains, a grain that reappears keeping its id,
+matching across more than one frame back, crystal symmetry in the gate.
 
 A SEQUENCE of measured maps gets ids that persist from frame to frame (`link_labels`, `label_sequence`,
 `samples_from_orientation_sequence`; ggnn_link_labels; tests/linkcheck.py): every frame is labelled on its own, the
@@ -776,8 +784,8 @@ def label_grains(ids=None, angles=None, tol=None, valid=None, min_pixels=1, max_
     Device tensors in, device tensors out, ONE read-back (the status); 9 + 2 max_sweeps launches whatever the image holds.
 
     Not covered: stacks of maps in one launch (`label_sequence` labels a sequence frame by frame and gives its grains the ids
-    that persist across the frames, which `frames_to_samples` needs), symmetry-reduced misorientation (reduce the angles to a
-    fundamental zone first), 8-connectivity, Euler-angle triples with crystal symmetry."""
+    that persist across the frames, which `frames_to_samples` needs), 8-connectivity.  The per-channel rule knows no crystal
+    symmetry: Euler-angle triples or quaternions under cubic symmetry are `label_orientations`."""
     v = _label(ids, angles, tol, valid, min_pixels, max_sweeps, boundary, grain_capacity)
     status = dict(zip(LABEL_STATUS_WORDS, v["status"].tolist()))   # the one read-back
     if status["n_bound_hits"]:
@@ -807,6 +815,147 @@ def sample_from_orientations(theta_x_map, theta_z_map, G, R, tol, min_pixels=1, 
     theta = means.cpu().numpy()
     x, ei, ea = sample_from_image(image, theta[0], theta[1], G, R, n_grain=n_grain, **kw)
     return x, ei, ea, image, dict(status, theta_x=theta[0], theta_z=theta[1])
+
+
+# ---- a measured map of full orientations under crystal symmetry ---------------------------------------------------------
+
+SYMMETRIES = {"none": _lib.GGNN_SYM_NONE, "cubic": _lib.GGNN_SYM_CUBIC}
+
+
+def quaternions_from_bunge(phi1, Phi, phi2, degrees=False):
+    """Bunge Euler angles (phi1, Phi, phi2: equal-shaped tensors or arrays, [ny, nx] or [T, ny, nx]) -> the unit quaternions
+    float32 [4, ny, nx] (or [T, 4, ny, nx]) that `label_orientations` takes: crystal to sample, Rz(phi1) Rx(Phi) Rz(phi2), formed
+    in fp64 and rounded once:  w = cos(Phi/2) cos((phi1+phi2)/2), x = sin(Phi/2) cos((phi1-phi2)/2), y = sin(Phi/2)
+    sin((phi1-phi2)/2), z = cos(Phi/2) sin((phi1+phi2)/2).  The result lies where the inputs lie."""
+    a, B, c = (torch.as_tensor(v).to(torch.float64) for v in (phi1, Phi, phi2))
+    if a.shape != B.shape or a.shape != c.shape:
+        raise _lib.GGNNError("phi1, Phi and phi2 must be equal-shaped")
+    if degrees:
+        a, B, c = (torch.deg2rad(v) for v in (a, B, c))
+    half, plus, minus = B / 2, (a + c) / 2, (a - c) / 2
+    q = [torch.cos(half) * torch.cos(plus), torch.sin(half) * torch.cos(minus), torch.sin(half) * torch.sin(minus),
+         torch.cos(half) * torch.sin(plus)]
+    return torch.stack(q, max(a.dim() - 2, 0)).to(torch.float32).contiguous()
+
+
+def growth_angles(mean_quats):
+    """The model's per-grain angles from orientations: mean_quats [4, n] (a tensor or an array; crystal to sample, normalised
+    here) -> (theta_x, theta_z) float64 [n], of the input's kind.  The six directions +c0, +c1, +c2, -c0, -c1, -c2, c_j the
+    columns of R(q), are the crystal's <100> axes in the sample frame; u is the one with the largest z component (the first on a
+    tie): the preferred growth direction nearest the sample's z.  theta_x = arctan2(u_y, u_x) % (pi/2), theta_z =
+    arctan2(hypot(u_x, u_y), u_z) <= 54.74 degrees, as the reference derives them from its drawn direction.  Equal for the 24
+    cubic equivalents of one orientation.  fp64 on the host: a row a grain, no hot path."""
+    as_tensor = isinstance(mean_quats, torch.Tensor)
+    q = (mean_quats.detach().cpu().numpy() if as_tensor else np.asarray(mean_quats)).astype(np.float64)
+    if q.ndim != 2 or q.shape[0] != 4:
+        raise _lib.GGNNError("mean_quats must be [4, n]")
+    w, x, y, z = q / np.sqrt((q * q).sum(0))
+    cols = np.stack([np.stack([1 - 2 * (y * y + z * z), 2 * (x * y + w * z), 2 * (x * z - w * y)]),
+                     np.stack([2 * (x * y - w * z), 1 - 2 * (x * x + z * z), 2 * (y * z + w * x)]),
+                     np.stack([2 * (x * z + w * y), 2 * (y * z - w * x), 1 - 2 * (x * x + y * y)])])   # [column, component, n]
+    six = np.concatenate([cols, -cols])
+    u = six[np.argmax(six[:, 2], 0), :, np.arange(q.shape[1])]                                         # [n, 3]
+    theta_x, theta_z = np.arctan2(u[:, 1], u[:, 0]) % (np.pi / 2), np.arctan2(np.hypot(u[:, 0], u[:, 1]), u[:, 2])
+    if as_tensor:
+        return torch.from_numpy(theta_x).to(mean_quats.device), torch.from_numpy(theta_z).to(mean_quats.device)
+    return theta_x, theta_z
+
+
+def _label_orient(quats, tol, valid, min_pixels, max_sweeps, boundary, grain_capacity, symmetry):
+    """Every launch of `label_orientations`, no read-back: -> dict of the image, the capacity-sized mean quaternions, the status
+    words on the device, and the call's arguments with what they point to (tools/vectorize_cost.py)."""
+    be = default_backend()
+    _check_boundary(boundary)
+    if symmetry not in SYMMETRIES:
+        raise _lib.GGNNError(f"symmetry must be one of {sorted(SYMMETRIES)}")
+    if tol is None or not 0.0 < float(tol) < math.pi / 2:
+        raise _lib.GGNNError("tol, the largest disorientation in radians that still links two neighbours, must lie in (0, pi/2)")
+    cos_half_tol = float(np.float32(np.cos(np.float64(tol) / 2)))                       # the one number formed on the host
+    if not cos_half_tol > float(np.float32(_lib.GGNN_ORIENT_H)):
+        raise _lib.GGNNError(f"tol {tol} is pi/2 to float32: cos(tol / 2) rounds to {cos_half_tol}, which the library refuses")
+    if not isinstance(quats, torch.Tensor) or not quats.is_cuda or quats.dim() != 3 or quats.size(0) != 4 or quats.dtype != torch.float32:
+        raise _lib.GGNNError("quats must be a float32 [4, ny, nx] device tensor")
+    quats = quats.contiguous()
+    _, ny, nx = quats.shape
+    if nx < 3 or ny < 3:
+        raise _lib.GGNNError("the map must have at least 3 x 3 pixels")
+    dev = quats.device
+    if valid is not None:
+        if not isinstance(valid, torch.Tensor) or not valid.is_cuda or valid.shape != (ny, nx):
+            raise _lib.GGNNError("valid must be a [ny, nx] device mask")
+        valid = (valid != 0).to(torch.uint8).contiguous()
+    min_pixels, max_sweeps = int(min_pixels), int(max_sweeps)
+    if min_pixels < 1:
+        raise _lib.GGNNError("min_pixels must be at least 1")
+    if not 0 <= max_sweeps <= _lib.GGNN_LABEL_MAX_SWEEPS:
+        raise _lib.GGNNError(f"max_sweeps must lie in [0, {_lib.GGNN_LABEL_MAX_SWEEPS}]")
+    cap = ny * nx // min_pixels + 2 if grain_capacity is None else int(grain_capacity)
+    if cap < 1:
+        raise _lib.GGNNError("grain_capacity must be at least 1")
+    image = torch.empty(ny, nx, dtype=torch.int32, device=dev)
+    means = torch.zeros(4, cap, dtype=torch.float32, device=dev)
+    status = torch.empty(_lib.GGNN_LABEL_STATUS_WORDS, dtype=torch.int64, device=dev)   # (zeroed by the call)
+    ws = torch.empty(be.lib.ggnn_label_orient_workspace_bytes(nx, ny), dtype=torch.uint8, device=dev)
+    A = _lib.LabelOrientArgs()
+    A.quats, A.valid, A.image, A.mean_quats = _lib.ptr(quats), _lib.ptr(valid), _lib.ptr(image), _lib.ptr(means)
+    A.status, A.workspace, A.workspace_bytes = _lib.ptr(status), _lib.ptr(ws), ws.numel()
+    A.nx, A.ny, A.grain_capacity, A.min_pixels = nx, ny, cap, min_pixels
+    A.cos_half_tol = cos_half_tol
+    A.symmetry, A.max_sweeps, A.boundary = SYMMETRIES[symmetry], max_sweeps, BOUNDARIES[boundary]
+    _lib.check(be.lib.ggnn_label_orientations(ctypes.byref(A), _lib.current_stream()), "ggnn_label_orientations")
+    return {"image": image, "means": means, "status": status, "capacity": cap, "boundary": boundary,
+            "calls": (A, quats, valid, ws)}
+
+
+def label_orientations(quats, tol, valid=None, min_pixels=1, max_sweeps=64, boundary="periodic", grain_capacity=None,
+                       symmetry="cubic"):
+    """Segment a map of full crystal orientations into a grain-ID image on the device (ggnn_label_orientations; include/ggnn.h
+    states the rule, tests/orientcheck.py restates it): `label_grains` with the link decided by the DISORIENTATION of
+    two neighbours under crystal symmetry, and a symmetry-aware mean orientation per grain.
+
+    quats: float32 [4, ny, nx] on the device (w, x, y, z planes; crystal to sample; q and -q are one orientation;
+    `quaternions_from_bunge` makes them from Euler angles); a pixel is valid when | |q|^2 - 1 | <= 1e-3 (NaN: non-indexed) and
+    the optional mask `valid` allows it.  tol: two 4-neighbours are linked when their disorientation angle is at most tol
+    (radians, in (0, pi/2); fp32 resolves about 1e-5 rad at 1 degree).  symmetry: "cubic" (the 24 proper rotations: the indexing
+    software may report any equivalent at any pixel) or "none".  min_pixels, max_sweeps, boundary, grain_capacity: as in
+    `label_grains`.
+
+    -> (image int32 [ny, nx], n_grain, mean_quats float32 [4, n_grain], status dict) as `label_grains` gives them; a grain's
+    mean runs over the pixels of its original component, each aligned to the equivalent nearest the component's first pixel,
+    and is normalised (no-flux: row 0, the boundary grain's, is the identity); `growth_angles` turns it into theta_x and theta_z.
+    Device tensors in, device tensors out, ONE read-back (the status); 12 + 2 max_sweeps launches whatever the map holds.
+
+    Not covered: hexagonal and other groups, stacks of maps in one launch, 8-connectivity.  A component whose pixels drift more
+    than about 20 degrees from its first pixel can align a pixel to the wrong equivalent."""
+    v = _label_orient(quats, tol, valid, min_pixels, max_sweeps, boundary, grain_capacity, symmetry)
+    status = dict(zip(LABEL_STATUS_WORDS, v["status"].tolist()))   # the one read-back
+    if status["n_bound_hits"]:
+        raise _lib.GGNNError(f"ggnn_label_orientations: {status['n_bound_hits']} threads reached the bound of a parent walk: {status}")
+    n_grain = status["n_grains"] + (1 if boundary == "noflux" else 0)
+    return v["image"], n_grain, v["means"][:, :min(n_grain, v["capacity"])].contiguous(), status
+
+
+def sample_from_euler_map(phi1, Phi, phi2, G, R, tol, min_pixels=1, degrees=False, **kw):
+    """A rollout's first state from an EBSD map: `quaternions_from_bunge` on the three Euler-angle maps ([ny, nx]),
+    `label_orientations` (tol in radians; symmetry, valid, max_sweeps and grain_capacity go to it), `growth_angles` of the mean
+    orientations read back, and `sample_from_image` on the labelled image with everything it takes (span, patch_pixels, grid,
+    merge_radius, boundary, links, ...).
+
+    -> (x_dict, edge_index_dict, edge_attr, image, status): the first three are bit for bit what
+    `sample_from_image(image, theta_x, theta_z, ...)` gives on the returned image and the float32 growth angles; status is the
+    labelling's, with "mean_quats" (device float32 [4, n_grain]), "theta_x" and "theta_z" (host float32)."""
+    boundary = kw.get("boundary", "periodic")
+    label_kw = {k: kw.pop(k) for k in ("valid", "max_sweeps", "grain_capacity", "symmetry") if k in kw}
+    quats = quaternions_from_bunge(phi1, Phi, phi2, degrees)
+    quats = quats if quats.is_cuda else quats.cuda()
+    if quats.dim() != 3:
+        raise _lib.GGNNError("phi1, Phi and phi2 must be [ny, nx] maps")
+    image, n_grain, means, status = label_orientations(quats, tol, min_pixels=min_pixels, boundary=boundary, **label_kw)
+    if status["overflow"]:
+        raise ValueError(f"the map has more grains than grain_capacity: {status}")
+    theta_x, theta_z = (t.cpu().numpy().astype(np.float32) for t in growth_angles(means))
+    x, ei, ea = sample_from_image(image, theta_x, theta_z, G, R, n_grain=n_grain, **kw)
+    return x, ei, ea, image, dict(status, mean_quats=means, theta_x=theta_x, theta_z=theta_z)
 
 
 # ---- ids that persist across a sequence of labelled maps --------------------------------------------------------------------
@@ -974,11 +1123,18 @@ def label_sequence(ids=None, angles=None, tol=None, valid=None, min_pixels=1, ma
         raise _lib.GGNNError("grain_capacity must hold at least one grain")
     per_frame = [_label(None if ids is None else ids[t], None if angles is None else angles[t], tol, None if valid is None else valid[t],
                         min_pixels, max_sweeps, boundary, cap) for t in range(T)]
+    return _link_frames(per_frame, angles is not None, match_tol, min_overlap, boundary, cap, "ggnn_label_grains")
+
+
+def _link_frames(per_frame, with_means, match_tol, min_overlap, boundary, cap, entry):
+    """The frames of a sequence, each labelled on its own by `entry` (the dicts of `_label` or `_label_orient`), linked on the
+    device, and the ONE read-back of both statuses -> what `label_sequence` returns."""
+    T, noflux = len(per_frame), boundary == "noflux"
     labels = torch.stack([v["image"] for v in per_frame])
     label_status = torch.stack([v["status"] for v in per_frame])
     n_local = label_status[:, LABEL_STATUS_WORDS.index("n_grains")].contiguous()
     means = None
-    if angles is not None:
+    if with_means:
         means = torch.stack([v["means"] for v in per_frame])
         if noflux:                                         # (row 0 is the boundary grain's: local grain b is row b - 2 from here on)
             means = means[:, :, 1:].contiguous()
@@ -988,7 +1144,7 @@ def label_sequence(ids=None, angles=None, tol=None, valid=None, min_pixels=1, ma
     label_report = [dict(zip(LABEL_STATUS_WORDS, words[n * t:n * t + n])) for t in range(T)]
     for t, s in enumerate(label_report):
         if s["n_bound_hits"]:
-            raise _lib.GGNNError(f"ggnn_label_grains: frame {t}: {s['n_bound_hits']} threads reached the bound of a parent walk: {s}")
+            raise _lib.GGNNError(f"{entry}: frame {t}: {s['n_bound_hits']} threads reached the bound of a parent walk: {s}")
         if s["overflow"]:
             raise _lib.GGNNError(f"frame {t} has more grains than grain_capacity {cap}: {s}")
     frames, n_grain, theta, report = _link_report(v, words[n * T:])
@@ -1015,4 +1171,55 @@ def samples_from_orientation_sequence(theta_x_maps, theta_z_maps, G, R, tol, min
     angles_host = theta.cpu().numpy()
     samples, report = frames_to_samples(frames, angles_host[0], angles_host[1], G, R, **kw)
     report["sequence"] = dict(sequence, theta_x=angles_host[0], theta_z=angles_host[1])
+    return samples, report, frames
+
+
+def label_orientation_sequence(quats, tol, valid=None, min_pixels=1, max_sweeps=64, boundary="periodic", match_tol=None,
+                               min_overlap=1, grain_capacity=None, symmetry="cubic"):
+    """`label_sequence` for maps of full orientations: `label_orientations`' launches once per frame of quats (float32
+    [T, 4, ny, nx] on the device), then `link_labels`' on the stack by pixel overlap alone, with ONE read-back at the end.
+
+    -> (frames, n_grain, quat float32 [4, n_grain], report) as `label_sequence` gives them: quat is every grain's mean
+    orientation in its first frame, copied (no-flux: row 0 is the identity).  match_tol raises: a per-channel gate on quaternion
+    components means nothing (a grain's mean may land on another equivalent in the next frame); a symmetry-aware gate is not
+    covered."""
+    _check_boundary(boundary)
+    if match_tol is not None:
+        raise _lib.GGNNError("match_tol is a per-channel gate and means nothing on quaternion components: frames of orientations "
+                             "are linked by overlap alone")
+    if not isinstance(quats, torch.Tensor) or not quats.is_cuda or quats.dim() != 4 or quats.size(0) < 1:
+        raise _lib.GGNNError("quats must be a float32 [T, 4, ny, nx] device tensor")
+    T, (ny, nx) = quats.size(0), quats.shape[-2:]
+    if valid is not None and (not isinstance(valid, torch.Tensor) or valid.shape != (T, ny, nx)):
+        raise _lib.GGNNError("valid must be a [T, ny, nx] device mask")
+    noflux = boundary == "noflux"
+    cap = min(ny * nx // max(int(min_pixels), 1) + 2, LINK_MAX_DEFAULT_CAPACITY) if grain_capacity is None else int(grain_capacity)
+    if cap < (2 if noflux else 1):
+        raise _lib.GGNNError("grain_capacity must hold at least one grain")
+    per_frame = [_label_orient(quats[t], tol, None if valid is None else valid[t], min_pixels, max_sweeps, boundary, cap, symmetry)
+                 for t in range(T)]
+    frames, n_grain, quat, report = _link_frames(per_frame, True, None, min_overlap, boundary, cap, "ggnn_label_orientations")
+    if noflux:
+        quat[0, 0] = 1.0                                   # the boundary grain's row, as label_orientations writes it
+    return frames, n_grain, quat, report
+
+
+def samples_from_euler_sequence(phi1, Phi, phi2, G, R, tol, min_pixels=1, degrees=False, **kw):
+    """A training set from a recorded sequence of EBSD maps: `quaternions_from_bunge` on the three stacks of Euler angles
+    ([T, ny, nx]), `label_orientation_sequence`, `growth_angles` of every grain's orientation in its first frame, and
+    `frames_to_samples` on the relabelled frames with everything it takes; valid, max_sweeps, min_overlap, grain_capacity and
+    symmetry go to `label_orientation_sequence`.
+
+    -> (samples, report, frames): samples and report as `frames_to_samples` gives them on the returned frames; report["sequence"]
+    is `label_orientation_sequence`'s report, with "quat" (device float32 [4, n_grain]), "theta_x" and "theta_z" (host float32)."""
+    seq_kw = {k: kw.pop(k) for k in ("valid", "max_sweeps", "match_tol", "min_overlap", "grain_capacity", "symmetry") if k in kw}
+    quats = quaternions_from_bunge(phi1, Phi, phi2, degrees)
+    quats = quats if quats.is_cuda else quats.cuda()
+    if quats.dim() != 4:
+        raise _lib.GGNNError("phi1, Phi and phi2 must be [T, ny, nx] stacks of maps")
+    frames, n_grain, quat, sequence = label_orientation_sequence(quats, tol, min_pixels=min_pixels, boundary=kw.get("boundary", "periodic"),
+                                                                 **seq_kw)
+    theta_x, theta_z = (t.cpu().numpy().astype(np.float32) for t in growth_angles(quat))
+    samples, report = frames_to_samples(frames, theta_x, theta_z, G, R, **kw)
+    report["sequence"] = dict(sequence, quat=quat, theta_x=theta_x, theta_z=theta_z)
     return samples, report, frames

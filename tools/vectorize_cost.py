@@ -63,7 +63,10 @@ in ids mode on two sequences: the seven recorded frames of tests/golden/pf_frame
 The arms alternate within a round; median of the rounds after three warm-up rounds.  Then the device activities of one call
 at T = 2 and at T (they must not differ).  --no-host leaves the host arm out (a profiler's run: per-launch times come from
 rocprofv3 --kernel-trace --stats around this tool).
-    python tools/vectorize_cost.py --link [--rounds 20] [--size 128] [--no-host]"""
+    python tools/vectorize_cost.py --link [--rounds 20] [--size 128] [--no-host]
+--label-orient times segmenting a map of full orientations under cubic symmetry (vectorize.label_orientations,
+ggnn_label_orientations) beside --label's angle call on --label's two maps, the two alternating within a round (label_orient_cost).
+    python tools/vectorize_cost.py --label-orient [--rounds 20] [--size 4096]"""
 import argparse
 import ctypes
 import os
@@ -83,6 +86,7 @@ def main():
     ap.add_argument("--trace", action="store_true", help="the links=\"trace\" arms")
     ap.add_argument("--label", action="store_true", help="the cost of label_grains")
     ap.add_argument("--link", action="store_true", help="the cost of link_labels and label_sequence")
+    ap.add_argument("--label-orient", action="store_true", help="the cost of label_orientations beside label_grains")
     ap.add_argument("--host-rounds", type=int, default=2, help="--label: timed rounds of the host route on the large map")
     ap.add_argument("--no-host", action="store_true", help="--label: leave the host route out (a profiler's run)")
     a = ap.parse_args()
@@ -91,6 +95,8 @@ def main():
         a.size = 128 if a.union or a.track or a.link else 4096
     if a.link:
         return link_cost(a)
+    if a.label_orient:
+        return label_orient_cost(a)
     if a.label:
         return label_cost(a)
     if a.track:
@@ -533,22 +539,14 @@ def label_floor(nx, ny, K, status, max_sweeps):
     return out
 
 
-def label_cost(a):
-    import time
+def measured_maps(a, dev):
+    """The two maps of --label and --label-orient -> (frame 0 of the recorded run as ids from 1, its (theta_x, theta_z) per grain,
+    the ids of the noisy Voronoi map with 0 = non-indexed, its (theta_x, theta_z) per cell, its cells, the random state)."""
     import numpy as np
     import torch
-    from scipy.sparse import coo_matrix
-    from scipy.sparse.csgraph import connected_components
-    sys.path[:0] = [os.path.join(os.path.dirname(HERE), "tests")]
-    import labelcheck as lc
-    from graingraphnn_amd import _lib
-    from graingraphnn_amd import vectorize as vz
-    dev = torch.device("cuda", 0)
-    lib = _lib.load()
     d = np.load(os.path.join(os.path.dirname(HERE), "tests", "golden", "pf_frames_cfg1.npz"))
     frame = d["frames"][0].astype(np.int64)
     theta = np.stack([d["theta_x"], d["theta_z"]]).astype(np.float32)
-    maps = {"golden 501 x 501": (np.ascontiguousarray(theta[:, frame - 1]), 1e-3, 1)}
     rs = np.random.RandomState(a.seed)
     n = max(4, a.size * a.size // 8192)
     seeds = torch.from_numpy(rs.uniform(0, a.size, (n, 2)).astype(np.float32)).to(dev)   # nearest seed on the torus, in slabs of rows
@@ -566,6 +564,124 @@ def label_cost(a):
     ids[m < 0.005] = 0
     wrong = (m >= 0.005) & (m < 0.01)
     ids[wrong] = rs.randint(1, n + 1, int(wrong.sum()))
+    return frame, theta, ids, th, n, rs
+
+
+def label_orient_cost(a):
+    """--label-orient: ggnn_label_orientations against ggnn_label_grains (angles, K = 2) on the two maps of --label, the
+    orientations by the recipe of tests/orientcheck.py (an orientation a cell more than 5 degrees from every other; per pixel at
+    most 0.3 degrees of noise, a random one of the 24 equivalents and a random sign; tol = 2 degrees).  The two calls alternate
+    within a round, by events; median, min and max of the rounds after three warm-up rounds; then the device activities of one
+    call, the tracer's time of every kernel and the traffic floors of the two added passes (links: four planes read, a byte
+    written, 17 bytes a pixel; accumulate: the label and four planes of a closed pixel, 20 bytes, gathers of the root counted
+    as hits, plus 32 bytes of atomics a run).  Per-launch times: rocprofv3 --kernel-trace --stats around this tool."""
+    import numpy as np
+    import torch
+    sys.path[:0] = [os.path.join(os.path.dirname(HERE), "tests")]
+    import orientcheck as oc
+    from graingraphnn_amd import _lib
+    from graingraphnn_amd import vectorize as vz
+    dev = torch.device("cuda", 0)
+    lib = _lib.load()
+    frame, theta, ids, th, n, rs = measured_maps(a, dev)
+    tol = float(np.deg2rad(2.0))
+
+    def cell_quats(count):
+        q = oc.random_quats(rs, count)
+        for i in range(1, count):
+            while oc.disorientation(q[:, :i], np.repeat(q[:, i:i + 1], i, 1)).min() <= np.deg2rad(5.0):
+                q[:, i] = oc.random_quats(rs, 1)[:, 0]
+        return q
+
+    def qmul(p, q):
+        return torch.stack([p[0] * q[0] - p[1] * q[1] - p[2] * q[2] - p[3] * q[3], p[0] * q[1] + p[1] * q[0] + p[2] * q[3] - p[3] * q[2],
+                            p[0] * q[2] - p[1] * q[3] + p[2] * q[0] + p[3] * q[1], p[0] * q[3] + p[1] * q[2] - p[2] * q[1] + p[3] * q[0]])
+
+    def orientations(cells, cq):
+        """cells [ny, nx] (ids from 1, 0 = non-indexed) -> float32 [4, ny, nx] on the device, by the recipe, in float64 there."""
+        g = torch.Generator(device=dev).manual_seed(a.seed)
+        flat = torch.from_numpy(cells.reshape(-1)).to(dev)
+        N = flat.numel()
+        axis = torch.randn(3, N, dtype=torch.float64, device=dev, generator=g)
+        half = torch.rand(N, dtype=torch.float64, device=dev, generator=g) * (np.deg2rad(0.3) / 2)
+        noise = torch.cat([torch.cos(half)[None], axis / axis.norm(dim=0) * torch.sin(half)])
+        ops = torch.from_numpy(oc.ops64()).to(dev)[torch.randint(0, 24, (N,), device=dev, generator=g)].T
+        sign = torch.randint(0, 2, (N,), device=dev, generator=g).to(torch.float64) * 2 - 1
+        q = qmul(qmul(torch.from_numpy(cq).to(dev)[:, flat.clamp(min=1) - 1], noise), ops) * sign
+        q[:, flat == 0] = float("nan")
+        return q.to(torch.float32).reshape(4, *cells.shape).contiguous()
+
+    maps = {"golden 501 x 501": (orientations(frame, cell_quats(theta.shape[1])), torch.from_numpy(np.ascontiguousarray(theta[:, frame - 1])).to(dev),
+                                 1e-3, 1),
+            f"voronoi {a.size} x {a.size}, {n} cells, 1 % noise": (orientations(ids, cell_quats(n)), None, 0.5 * 1.45 / n, 8)}
+    big = torch.from_numpy(np.ascontiguousarray(th[:, np.maximum(ids, 1) - 1])).to(dev)
+    big[:, torch.from_numpy(ids == 0).to(dev)] = float("nan")
+    key = list(maps)[1]
+    maps[key] = (maps[key][0], big) + maps[key][2:]
+
+    def by_events(call):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        call()
+        t1.record()
+        t1.synchronize()
+        return t0.elapsed_time(t1) * 1e3
+
+    for name, (quats, angles, angle_tol, mp) in maps.items():
+        _, ny, nx = quats.shape
+        image, n_grain, means, status = vz.label_orientations(quats, tol, min_pixels=mp)
+        a_image, a_n, _, a_status = vz.label_grains(angles=angles, tol=angle_tol, min_pixels=mp)
+        print(f"# {name}: orientations {n_grain} grains, status {status}; angles {a_n} grains; the same image: "
+              f"{bool(torch.equal(image, a_image))}; workspace {lib.ggnn_label_orient_workspace_bytes(nx, ny) / 1e6:.1f} MB", flush=True)
+        O = vz._label_orient(quats, tol, None, mp, 64, "periodic", None, "cubic")["calls"][0]
+        A = vz._label(None, angles, angle_tol, None, mp, 64, "periodic", None)["calls"][0]
+        arms = {"orient": lambda: _lib.check(lib.ggnn_label_orientations(ctypes.byref(O), _lib.current_stream()), "orient"),
+                "angles": lambda: _lib.check(lib.ggnn_label_grains(ctypes.byref(A), _lib.current_stream()), "label")}
+        times = {k: [] for k in arms}
+        for rnd in range(a.rounds + 3):
+            for arm, call in arms.items():
+                t = by_events(call)
+                if rnd >= 3:
+                    times[arm].append(t)
+        for arm, t in times.items():
+            t = np.array(t)
+            print(f"{arm:6s} us ({len(t)} rounds): median {np.median(t):12.1f}  min {t.min():12.1f}  max {t.max():12.1f}", flush=True)
+        N, closed = nx * ny, nx * ny - status["n_invalid_in"] - status["n_speck_pixels"]
+        print(f"# traffic floors at 8 TB/s: orientation links {17 * N / 8e6:.2f} us ({17 * N / 1e6:.1f} MB), angle links (K = 2) "
+              f"{9 * N / 8e6:.2f} us, accumulate {(4 * N + 16 * closed) / 8e6:.2f} us ({closed} closed pixels) plus the atomics, "
+              f"zero {4 * N / 8e6:.2f} us, means {4 * N / 8e6:.2f} us", flush=True)
+        try:
+            from torch.profiler import ProfilerActivity, profile
+            for arm, call in arms.items():
+                with profile(activities=[ProfilerActivity.CUDA]) as prof:
+                    call()
+                    torch.cuda.synchronize()
+                count = sum(1 for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA)
+                print(f"{arm}: device activities (kernels, memsets) of one call: {count}", flush=True)
+                for e in sorted(prof.key_averages(), key=lambda e: e.key):
+                    t = getattr(e, "device_time_total", None)
+                    t = getattr(e, "cuda_time_total", 0.0) if t is None else t
+                    if t:
+                        print(f"    {e.count:3d} x {e.key[:100]}: {t:.1f} us by the tracer", flush=True)
+        except Exception as exc:   # (a build of torch without the tracer)
+            print(f"# launches not counted: {type(exc).__name__}: {exc}", flush=True)
+    print(f"# torch {torch.__version__}, {torch.cuda.get_device_name()}", flush=True)
+
+
+def label_cost(a):
+    import time
+    import numpy as np
+    import torch
+    from scipy.sparse import coo_matrix
+    from scipy.sparse.csgraph import connected_components
+    sys.path[:0] = [os.path.join(os.path.dirname(HERE), "tests")]
+    import labelcheck as lc
+    from graingraphnn_amd import _lib
+    from graingraphnn_amd import vectorize as vz
+    dev = torch.device("cuda", 0)
+    lib = _lib.load()
+    frame, theta, ids, th, n, _ = measured_maps(a, dev)
+    maps = {"golden 501 x 501": (np.ascontiguousarray(theta[:, frame - 1]), 1e-3, 1)}
     big = np.ascontiguousarray(th[:, np.maximum(ids, 1) - 1])
     big[:, ids == 0] = np.nan
     maps[f"voronoi {a.size} x {a.size}, {n} cells, 1 % noise"] = (big, 0.5 * 1.45 / n, 8)
