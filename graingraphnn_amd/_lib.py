@@ -69,6 +69,8 @@ EXPORTED_SYMBOLS = (
     "ggnn_image_junction_windows_traj", "ggnn_junction_links_trace_traj",
     "ggnn_label_workspace_bytes", "ggnn_label_grains", "ggnn_link_workspace_bytes", "ggnn_link_labels",
     "ggnn_label_orient_workspace_bytes", "ggnn_label_orientations",
+    "ggnn_label_stack_workspace_bytes", "ggnn_label_grains_stack", "ggnn_label_orient_stack_workspace_bytes",
+    "ggnn_label_orientations_stack",
     "ggnn_metric_record",
     "ggnn_masked_mse_rows", "ggnn_collate_batch", "ggnn_reverse_slots",
 )
@@ -524,6 +526,26 @@ class LabelOrientArgs(Structure):
     ]
 
 
+class LabelStackArgs(Structure):
+    """Mirror of `ggnn_label_stack_args`."""
+    _fields_ = [
+        ("ids", c_void_p), ("angles", c_void_p), ("valid", c_void_p), ("image", c_void_p), ("mean_angles", c_void_p),
+        ("status", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_size_t), ("T", c_int64),
+        ("nx", c_int64), ("ny", c_int64), ("grain_capacity", c_int64), ("min_pixels", c_int64),
+        ("tol", c_float), ("K", c_int32), ("max_sweeps", c_int32), ("boundary", c_int32),
+    ]
+
+
+class LabelOrientStackArgs(Structure):
+    """Mirror of `ggnn_label_orient_stack_args`."""
+    _fields_ = [
+        ("quats", c_void_p), ("valid", c_void_p), ("image", c_void_p), ("mean_quats", c_void_p),
+        ("status", c_void_p), ("workspace", c_void_p), ("workspace_bytes", c_size_t), ("T", c_int64),
+        ("nx", c_int64), ("ny", c_int64), ("grain_capacity", c_int64), ("min_pixels", c_int64),
+        ("cos_half_tol", c_float), ("symmetry", c_int32), ("max_sweeps", c_int32), ("boundary", c_int32),
+    ]
+
+
 class LinkLabelsArgs(Structure):
     """Mirror of `ggnn_link_labels_args` (`LinkArgs` is the junction linking's)."""
     _fields_ = [
@@ -716,6 +738,14 @@ def _declare(lib):
     lib.ggnn_label_orient_workspace_bytes.argtypes = [c_int64, c_int64]
     lib.ggnn_label_orientations.restype = c_int
     lib.ggnn_label_orientations.argtypes = [POINTER(LabelOrientArgs), c_void_p]
+    lib.ggnn_label_stack_workspace_bytes.restype = c_size_t
+    lib.ggnn_label_stack_workspace_bytes.argtypes = [c_int64, c_int64, c_int64, c_int32]
+    lib.ggnn_label_grains_stack.restype = c_int
+    lib.ggnn_label_grains_stack.argtypes = [POINTER(LabelStackArgs), c_void_p]
+    lib.ggnn_label_orient_stack_workspace_bytes.restype = c_size_t
+    lib.ggnn_label_orient_stack_workspace_bytes.argtypes = [c_int64, c_int64, c_int64]
+    lib.ggnn_label_orientations_stack.restype = c_int
+    lib.ggnn_label_orientations_stack.argtypes = [POINTER(LabelOrientStackArgs), c_void_p]
     lib.ggnn_link_workspace_bytes.restype = c_size_t
     lib.ggnn_link_workspace_bytes.argtypes = [c_int64, c_int64, c_int32]
     lib.ggnn_link_labels.restype = c_int

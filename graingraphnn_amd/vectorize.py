@@ -711,35 +711,17 @@ LABEL_STATUS_WORDS = ("n_components", "n_specks", "n_speck_pixels", "n_invalid_i
                       "overflow", "n_bound_hits")
 
 
-def _label(ids, angles, tol, valid, min_pixels, max_sweeps, boundary, grain_capacity):
-    """Every launch of `label_grains`, no read-back: -> dict of the image, the capacity-sized means (None with ids), the
-    status words on the device, and the call's arguments with what they point to (tools/vectorize_cost.py)."""
-    be = default_backend()
-    _check_boundary(boundary)
-    if (ids is None) == (angles is None):
-        raise _lib.GGNNError("exactly one of ids and angles must be given")
-    src = ids if angles is None else angles
-    if not isinstance(src, torch.Tensor) or not src.is_cuda:
-        raise _lib.GGNNError("ids / angles must be device tensors")
-    if angles is None:
-        if ids.dim() != 2 or ids.dtype not in (torch.int16, torch.int32, torch.int64, torch.uint8, torch.int8):
-            raise _lib.GGNNError("ids must be an integer [ny, nx] device tensor")
-        ids = ids.to(torch.int32).contiguous()
-        K, (ny, nx) = 0, ids.shape
-    else:
-        if tol is None:
-            raise _lib.GGNNError("angles need tol, the largest difference per channel that still links two neighbours")
-        if angles.dim() != 3 or not 1 <= angles.size(0) <= 4 or angles.dtype != torch.float32:
-            raise _lib.GGNNError("angles must be a float32 [K, ny, nx] device tensor with 1 <= K <= 4")
-        angles = angles.contiguous()
-        K, ny, nx = angles.shape
-    if nx < 3 or ny < 3:
-        raise _lib.GGNNError("the image must have at least 3 x 3 pixels")
-    dev = src.device
-    if valid is not None:
-        if not isinstance(valid, torch.Tensor) or not valid.is_cuda or valid.shape != (ny, nx):
-            raise _lib.GGNNError("valid must be a [ny, nx] device mask")
-        valid = (valid != 0).to(torch.uint8).contiguous()
+def _label_mask(valid, shape, text):
+    """The optional mask of a labelling call as contiguous bytes; shape: the map's, or the stack's."""
+    if valid is None:
+        return None
+    if not isinstance(valid, torch.Tensor) or not valid.is_cuda or valid.shape != tuple(shape):
+        raise _lib.GGNNError(f"valid must be a {text} device mask")
+    return (valid != 0).to(torch.uint8).contiguous()
+
+
+def _label_cleanup(ny, nx, min_pixels, max_sweeps, grain_capacity):
+    """min_pixels, max_sweeps and the rows per map of a labelling call, checked."""
     min_pixels, max_sweeps = int(min_pixels), int(max_sweeps)
     if min_pixels < 1:
         raise _lib.GGNNError("min_pixels must be at least 1")
@@ -748,6 +730,45 @@ def _label(ids, angles, tol, valid, min_pixels, max_sweeps, boundary, grain_capa
     cap = ny * nx // min_pixels + 2 if grain_capacity is None else int(grain_capacity)
     if cap < 1:
         raise _lib.GGNNError("grain_capacity must be at least 1")
+    return min_pixels, max_sweeps, cap
+
+
+def _label_inputs(ids, angles, tol, valid, boundary, stack):
+    """What `_label` (one map) and `_label_stack` (stack: a leading T) check of their inputs: -> (ids, angles, valid) as the
+    library takes them, K, and the shape of ids (of angles without K)."""
+    _check_boundary(boundary)
+    if (ids is None) == (angles is None):
+        raise _lib.GGNNError("exactly one of ids and angles must be given")
+    src = ids if angles is None else angles
+    if not isinstance(src, torch.Tensor) or not src.is_cuda:
+        raise _lib.GGNNError("ids / angles must be device tensors")
+    lead, dims = ("[T, ", 3) if stack else ("[", 2)
+    if angles is None:
+        if ids.dim() != dims or ids.dtype not in (torch.int16, torch.int32, torch.int64, torch.uint8, torch.int8):
+            raise _lib.GGNNError(f"ids must be an integer {lead}ny, nx] device tensor")
+        ids = ids.to(torch.int32).contiguous()
+        K, shape = 0, tuple(ids.shape)
+    else:
+        if tol is None:
+            raise _lib.GGNNError("angles need tol, the largest difference per channel that still links two neighbours")
+        if angles.dim() != dims + 1 or not 1 <= angles.size(-3) <= 4 or angles.dtype != torch.float32:
+            raise _lib.GGNNError(f"angles must be a float32 {lead}K, ny, nx] device tensor with 1 <= K <= 4")
+        angles = angles.contiguous()
+        K, shape = angles.size(-3), tuple(angles.shape[:-3]) + tuple(angles.shape[-2:])
+    if shape[-1] < 3 or shape[-2] < 3:
+        raise _lib.GGNNError("the image must have at least 3 x 3 pixels")
+    if stack and shape[0] < 1:
+        raise _lib.GGNNError("a stack holds at least one map")
+    return ids, angles, _label_mask(valid, shape, f"{lead}ny, nx]"), K, shape
+
+
+def _label(ids, angles, tol, valid, min_pixels, max_sweeps, boundary, grain_capacity):
+    """Every launch of `label_grains`, no read-back: -> dict of the image, the capacity-sized means (None with ids), the
+    status words on the device, and the call's arguments with what they point to (tools/vectorize_cost.py)."""
+    be = default_backend()
+    ids, angles, valid, K, (ny, nx) = _label_inputs(ids, angles, tol, valid, boundary, False)
+    dev = (ids if angles is None else angles).device
+    min_pixels, max_sweeps, cap = _label_cleanup(ny, nx, min_pixels, max_sweeps, grain_capacity)
     image = torch.empty(ny, nx, dtype=torch.int32, device=dev)
     means = torch.zeros(K, cap, dtype=torch.float32, device=dev) if K else None
     status = torch.empty(_lib.GGNN_LABEL_STATUS_WORDS, dtype=torch.int64, device=dev)   # (zeroed by the call)
@@ -760,6 +781,68 @@ def _label(ids, angles, tol, valid, min_pixels, max_sweeps, boundary, grain_capa
     _lib.check(be.lib.ggnn_label_grains(ctypes.byref(A), _lib.current_stream()), "ggnn_label_grains")
     return {"image": image, "means": means, "status": status, "capacity": cap, "boundary": boundary,
             "calls": (A, ids, angles, valid, ws)}
+
+
+def _stack_workspace(need, T, ny, nx):
+    """The scratch of a stacked labelling call of `need` bytes (0: the library takes no such stack)."""
+    if need == 0:
+        raise _lib.GGNNError(f"a stack of {T} maps of {ny} x {nx} pixels is beyond what one labelling call takes (T ny nx <= "
+                             f"{2 ** 31 - 1}, nx and ny below {1 << 15}): split it")
+    return need
+
+
+def _label_stack(ids, angles, tol, valid, min_pixels, max_sweeps, boundary, grain_capacity):
+    """Every launch of `label_maps` (ggnn_label_grains_stack), no read-back: `_label`'s dict with stacked tensors -- the images
+    [T, ny, nx], the capacity-sized means [T, K, capacity] (None with ids), the status words [T, 9] on the device."""
+    be = default_backend()
+    ids, angles, valid, K, (T, ny, nx) = _label_inputs(ids, angles, tol, valid, boundary, True)
+    dev = (ids if angles is None else angles).device
+    min_pixels, max_sweeps, cap = _label_cleanup(ny, nx, min_pixels, max_sweeps, grain_capacity)
+    need = _stack_workspace(be.lib.ggnn_label_stack_workspace_bytes(T, nx, ny, K), T, ny, nx)
+    image = torch.empty(T, ny, nx, dtype=torch.int32, device=dev)
+    means = torch.zeros(T, K, cap, dtype=torch.float32, device=dev) if K else None
+    status = torch.empty(T, _lib.GGNN_LABEL_STATUS_WORDS, dtype=torch.int64, device=dev)   # (zeroed by the call)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    A = _lib.LabelStackArgs()
+    A.ids, A.angles, A.valid, A.image, A.mean_angles = _lib.ptr(ids), _lib.ptr(angles), _lib.ptr(valid), _lib.ptr(image), _lib.ptr(means)
+    A.status, A.workspace, A.workspace_bytes = _lib.ptr(status), _lib.ptr(ws), ws.numel()
+    A.T, A.nx, A.ny, A.grain_capacity, A.min_pixels = T, nx, ny, cap, min_pixels
+    A.tol, A.K, A.max_sweeps, A.boundary = (0.0 if tol is None else float(np.float32(tol))), K, max_sweeps, BOUNDARIES[boundary]
+    _lib.check(be.lib.ggnn_label_grains_stack(ctypes.byref(A), _lib.current_stream()), "ggnn_label_grains_stack")
+    return {"image": image, "means": means, "status": status, "capacity": cap, "boundary": boundary,
+            "calls": (A, ids, angles, valid, ws)}
+
+
+def _stack_statuses(v, words, entry):
+    """The status rows of a stacked labelling, read back as `words` -> (n_grains, statuses), a count and a dict per map; raises
+    on a parent walk that reached its bound and names the map."""
+    n = len(LABEL_STATUS_WORDS)
+    statuses = [dict(zip(LABEL_STATUS_WORDS, words[n * t:n * t + n])) for t in range(v["image"].size(0))]
+    for t, s in enumerate(statuses):
+        if s["n_bound_hits"]:
+            raise _lib.GGNNError(f"{entry}: frame {t}: {s['n_bound_hits']} threads reached the bound of a parent walk: {s}")
+    noflux = 1 if v["boundary"] == "noflux" else 0
+    return [s["n_grains"] + noflux for s in statuses], statuses
+
+
+def label_maps(ids=None, angles=None, tol=None, valid=None, min_pixels=1, max_sweeps=64, boundary="periodic", grain_capacity=None):
+    """`label_grains` for a STACK of T equal-shaped maps -- a recorded sequence, or an ensemble of scans for one union rollout
+    -- in the launches of one map (ggnn_label_grains_stack): every map comes out bit for bit as `label_grains`
+    gives it alone.  Maps never interact: the periodic wrap of a map goes to its own first row and column.
+
+    Exactly one of ids -- integer [T, ny, nx] -- and angles -- float32 [T, K, ny, nx] with tol --, on the device; valid: an
+    optional [T, ny, nx] mask; min_pixels, max_sweeps, boundary: as in `label_grains`, the same for every map; grain_capacity:
+    rows PER MAP (default ny nx // min_pixels + 2, which cannot overflow).
+
+    -> (images int32 [T, ny, nx], n_grains: a list of T ints, mean_angles float32 [T, K, capacity] or None with ids, statuses: a
+    list of T dicts as `label_grains` gives them).  Ids restart in every map; map t's means are mean_angles[t, :, :n_grains[t]],
+    the rows beyond are zero.  Device tensors in, device tensors out, ONE read-back (the T status rows); two memsets and
+    9 + 2 max_sweeps launches whatever T.  Raises on a non-zero n_bound_hits and names the map.
+
+    Not covered: stacks of mixed shapes, and stacks of more than 2^31 - 1 pixels: the caller splits those."""
+    v = _label_stack(ids, angles, tol, valid, min_pixels, max_sweeps, boundary, grain_capacity)
+    n_grains, statuses = _stack_statuses(v, v["status"].reshape(-1).tolist(), "ggnn_label_grains_stack")   # the one read-back
+    return v["image"], n_grains, v["means"], statuses
 
 
 def label_grains(ids=None, angles=None, tol=None, valid=None, min_pixels=1, max_sweeps=64, boundary="periodic",
@@ -783,8 +866,8 @@ def label_grains(ids=None, angles=None, tol=None, valid=None, min_pixels=1, max_
     n_sweeps, n_unfilled, overflow (more grains than grain_capacity: the image is complete, the means hold the first rows).
     Device tensors in, device tensors out, ONE read-back (the status); 9 + 2 max_sweeps launches whatever the image holds.
 
-    Not covered: stacks of maps in one launch (`label_sequence` labels a sequence frame by frame and gives its grains the ids
-    that persist across the frames, which `frames_to_samples` needs), 8-connectivity.  The per-channel rule knows no crystal
+    A stack of equal-shaped maps in the same launches is `label_maps` (`label_sequence` also gives a sequence's grains the ids
+    that persist across the frames, which `frames_to_samples` needs).  Not covered: 8-connectivity.  The per-channel rule knows no crystal
     symmetry: Euler-angle triples or quaternions under cubic symmetry are `label_orientations`."""
     v = _label(ids, angles, tol, valid, min_pixels, max_sweeps, boundary, grain_capacity)
     status = dict(zip(LABEL_STATUS_WORDS, v["status"].tolist()))   # the one read-back
@@ -815,6 +898,46 @@ def sample_from_orientations(theta_x_map, theta_z_map, G, R, tol, min_pixels=1, 
     theta = means.cpu().numpy()
     x, ei, ea = sample_from_image(image, theta[0], theta[1], G, R, n_grain=n_grain, **kw)
     return x, ei, ea, image, dict(status, theta_x=theta[0], theta_z=theta[1])
+
+
+def _no_map_overflows(statuses):
+    """Raises on the first map of a labelled stack that has more grains than rows, and names it."""
+    for t, s in enumerate(statuses):
+        if s["overflow"]:
+            raise ValueError(f"map {t} has more grains than grain_capacity: {s}")
+
+
+def _union_from_labelled(images, n_grains, statuses, theta, G, R, kw):
+    """`samples_from_images` on a labelled stack: theta, a (theta_x, theta_z) pair of host arrays per map -> what
+    `samples_from_orientation_maps` returns."""
+    x, ei, ea, traj_offsets = samples_from_images(images, [a for a, _ in theta], [b for _, b in theta], G, R, n_grains=n_grains, **kw)
+    statuses = [dict(s, theta_x=a, theta_z=b) for s, (a, b) in zip(statuses, theta)]
+    return x, ei, ea, traj_offsets, images, statuses
+
+
+def samples_from_orientation_maps(theta_x_maps, theta_z_maps, G, R, tol, min_pixels=1, **kw):
+    """A union rollout's first state from a stack of orientation maps (an ensemble of scans): `label_maps` on the two stacks of
+    angle maps ([T, ny, nx] float32 on the device, radians), the per-grain mean angles read back once, and
+    `samples_from_images` on the labelled images with everything it takes (span, patch_pixels, grid, merge_radius,
+    joint_capacity, boundary, links, max_trace; G and R: scalars or one value per map); valid, max_sweeps and grain_capacity
+    go to `label_maps`.
+
+    -> (x_dict, edge_index_dict, edge_attr, traj_offsets, images, statuses): the first four as `samples_from_images` gives
+    them -- every trajectory's rows are, bit for bit, `sample_from_orientations`' on that map alone --; images int32
+    [T, ny, nx]; statuses: per map the labelling's status with the means under "theta_x" and "theta_z" (host float32).  Three
+    read-backs whatever T: the label status, the means, the vectoriser's status.  A map that overflows grain_capacity raises
+    and is named; a map whose labelled image is no valid structure raises, as `samples_from_images` does.  One shape a stack."""
+    if (not isinstance(theta_x_maps, torch.Tensor) or not isinstance(theta_z_maps, torch.Tensor) or theta_x_maps.dim() != 3
+            or theta_x_maps.shape != theta_z_maps.shape):
+        raise _lib.GGNNError("theta_x_maps and theta_z_maps must be equal-shaped [T, ny, nx] device tensors")
+    label_kw = {k: kw.pop(k) for k in ("valid", "max_sweeps", "grain_capacity") if k in kw}
+    angles = torch.stack([theta_x_maps.to(torch.float32), theta_z_maps.to(torch.float32)], 1)
+    images, n_grains, means, statuses = label_maps(angles=angles, tol=tol, min_pixels=min_pixels, boundary=kw.get("boundary", "periodic"),
+                                                   **label_kw)
+    _no_map_overflows(statuses)
+    host = means[:, :, :max(n_grains)].cpu().numpy()                       # every map's rows in one read-back
+    theta = [(host[t, 0, :n].copy(), host[t, 1, :n].copy()) for t, n in enumerate(n_grains)]
+    return _union_from_labelled(images, n_grains, statuses, theta, G, R, kw)
 
 
 # ---- a measured map of full orientations under crystal symmetry ---------------------------------------------------------
@@ -861,10 +984,9 @@ def growth_angles(mean_quats):
     return theta_x, theta_z
 
 
-def _label_orient(quats, tol, valid, min_pixels, max_sweeps, boundary, grain_capacity, symmetry):
-    """Every launch of `label_orientations`, no read-back: -> dict of the image, the capacity-sized mean quaternions, the status
-    words on the device, and the call's arguments with what they point to (tools/vectorize_cost.py)."""
-    be = default_backend()
+def _orient_inputs(quats, tol, valid, boundary, symmetry, stack):
+    """What `_label_orient` (one map) and `_label_orient_stack` (stack: a leading T) check of their inputs: -> (quats, valid) as
+    the library takes them, cos(tol / 2), and the shape of the map or of the stack."""
     _check_boundary(boundary)
     if symmetry not in SYMMETRIES:
         raise _lib.GGNNError(f"symmetry must be one of {sorted(SYMMETRIES)}")
@@ -873,25 +995,24 @@ def _label_orient(quats, tol, valid, min_pixels, max_sweeps, boundary, grain_cap
     cos_half_tol = float(np.float32(np.cos(np.float64(tol) / 2)))                       # the one number formed on the host
     if not cos_half_tol > float(np.float32(_lib.GGNN_ORIENT_H)):
         raise _lib.GGNNError(f"tol {tol} is pi/2 to float32: cos(tol / 2) rounds to {cos_half_tol}, which the library refuses")
-    if not isinstance(quats, torch.Tensor) or not quats.is_cuda or quats.dim() != 3 or quats.size(0) != 4 or quats.dtype != torch.float32:
-        raise _lib.GGNNError("quats must be a float32 [4, ny, nx] device tensor")
+    lead, dims = ("[T, ", 4) if stack else ("[", 3)
+    if (not isinstance(quats, torch.Tensor) or not quats.is_cuda or quats.dim() != dims or quats.size(-3) != 4 or quats.dtype != torch.float32
+            or (stack and quats.size(0) < 1)):
+        raise _lib.GGNNError(f"quats must be a float32 {lead}4, ny, nx] device tensor")
     quats = quats.contiguous()
-    _, ny, nx = quats.shape
-    if nx < 3 or ny < 3:
+    shape = tuple(quats.shape[:-3]) + tuple(quats.shape[-2:])
+    if shape[-1] < 3 or shape[-2] < 3:
         raise _lib.GGNNError("the map must have at least 3 x 3 pixels")
+    return quats, _label_mask(valid, shape, f"{lead}ny, nx]"), cos_half_tol, shape
+
+
+def _label_orient(quats, tol, valid, min_pixels, max_sweeps, boundary, grain_capacity, symmetry):
+    """Every launch of `label_orientations`, no read-back: -> dict of the image, the capacity-sized mean quaternions, the status
+    words on the device, and the call's arguments with what they point to (tools/vectorize_cost.py)."""
+    be = default_backend()
+    quats, valid, cos_half_tol, (ny, nx) = _orient_inputs(quats, tol, valid, boundary, symmetry, False)
     dev = quats.device
-    if valid is not None:
-        if not isinstance(valid, torch.Tensor) or not valid.is_cuda or valid.shape != (ny, nx):
-            raise _lib.GGNNError("valid must be a [ny, nx] device mask")
-        valid = (valid != 0).to(torch.uint8).contiguous()
-    min_pixels, max_sweeps = int(min_pixels), int(max_sweeps)
-    if min_pixels < 1:
-        raise _lib.GGNNError("min_pixels must be at least 1")
-    if not 0 <= max_sweeps <= _lib.GGNN_LABEL_MAX_SWEEPS:
-        raise _lib.GGNNError(f"max_sweeps must lie in [0, {_lib.GGNN_LABEL_MAX_SWEEPS}]")
-    cap = ny * nx // min_pixels + 2 if grain_capacity is None else int(grain_capacity)
-    if cap < 1:
-        raise _lib.GGNNError("grain_capacity must be at least 1")
+    min_pixels, max_sweeps, cap = _label_cleanup(ny, nx, min_pixels, max_sweeps, grain_capacity)
     image = torch.empty(ny, nx, dtype=torch.int32, device=dev)
     means = torch.zeros(4, cap, dtype=torch.float32, device=dev)
     status = torch.empty(_lib.GGNN_LABEL_STATUS_WORDS, dtype=torch.int64, device=dev)   # (zeroed by the call)
@@ -905,6 +1026,48 @@ def _label_orient(quats, tol, valid, min_pixels, max_sweeps, boundary, grain_cap
     _lib.check(be.lib.ggnn_label_orientations(ctypes.byref(A), _lib.current_stream()), "ggnn_label_orientations")
     return {"image": image, "means": means, "status": status, "capacity": cap, "boundary": boundary,
             "calls": (A, quats, valid, ws)}
+
+
+def _label_orient_stack(quats, tol, valid, min_pixels, max_sweeps, boundary, grain_capacity, symmetry):
+    """Every launch of `label_orientation_maps` (ggnn_label_orientations_stack), no read-back: `_label_orient`'s dict with
+    stacked tensors -- the images [T, ny, nx], the mean quaternions [T, 4, capacity], the status words [T, 9] on the device."""
+    be = default_backend()
+    quats, valid, cos_half_tol, (T, ny, nx) = _orient_inputs(quats, tol, valid, boundary, symmetry, True)
+    dev = quats.device
+    min_pixels, max_sweeps, cap = _label_cleanup(ny, nx, min_pixels, max_sweeps, grain_capacity)
+    need = _stack_workspace(be.lib.ggnn_label_orient_stack_workspace_bytes(T, nx, ny), T, ny, nx)
+    image = torch.empty(T, ny, nx, dtype=torch.int32, device=dev)
+    means = torch.zeros(T, 4, cap, dtype=torch.float32, device=dev)
+    status = torch.empty(T, _lib.GGNN_LABEL_STATUS_WORDS, dtype=torch.int64, device=dev)   # (zeroed by the call)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    A = _lib.LabelOrientStackArgs()
+    A.quats, A.valid, A.image, A.mean_quats = _lib.ptr(quats), _lib.ptr(valid), _lib.ptr(image), _lib.ptr(means)
+    A.status, A.workspace, A.workspace_bytes = _lib.ptr(status), _lib.ptr(ws), ws.numel()
+    A.T, A.nx, A.ny, A.grain_capacity, A.min_pixels = T, nx, ny, cap, min_pixels
+    A.cos_half_tol = cos_half_tol
+    A.symmetry, A.max_sweeps, A.boundary = SYMMETRIES[symmetry], max_sweeps, BOUNDARIES[boundary]
+    _lib.check(be.lib.ggnn_label_orientations_stack(ctypes.byref(A), _lib.current_stream()), "ggnn_label_orientations_stack")
+    return {"image": image, "means": means, "status": status, "capacity": cap, "boundary": boundary,
+            "calls": (A, quats, valid, ws)}
+
+
+def label_orientation_maps(quats, tol, valid=None, min_pixels=1, max_sweeps=64, boundary="periodic", grain_capacity=None,
+                           symmetry="cubic"):
+    """`label_orientations` for a STACK of T equal-shaped maps in the launches of one map (ggnn_label_orientations_stack; DESIGN
+    8r): every map comes out bit for bit as `label_orientations` gives it alone; the alignment target of a grain's mean is the
+    first pixel of its component in its own map.
+
+    quats: float32 [T, 4, ny, nx] on the device; valid: an optional [T, ny, nx] mask; everything else as in
+    `label_orientations`, the same for every map; grain_capacity: rows PER MAP.
+
+    -> (images int32 [T, ny, nx], n_grains: a list of T ints, mean_quats float32 [T, 4, capacity], statuses: a list of T dicts):
+    map t's means are mean_quats[t, :, :n_grains[t]], the rows beyond are zero.  ONE read-back (the T status rows); two
+    memsets and 12 + 2 max_sweeps launches whatever T.  Raises on a non-zero n_bound_hits and names the map.
+
+    Not covered: stacks of mixed shapes, and stacks of more than 2^31 - 1 pixels: the caller splits those."""
+    v = _label_orient_stack(quats, tol, valid, min_pixels, max_sweeps, boundary, grain_capacity, symmetry)
+    n_grains, statuses = _stack_statuses(v, v["status"].reshape(-1).tolist(), "ggnn_label_orientations_stack")   # the one read-back
+    return v["image"], n_grains, v["means"], statuses
 
 
 def label_orientations(quats, tol, valid=None, min_pixels=1, max_sweeps=64, boundary="periodic", grain_capacity=None,
@@ -925,7 +1088,8 @@ def label_orientations(quats, tol, valid=None, min_pixels=1, max_sweeps=64, boun
     and is normalised (no-flux: row 0, the boundary grain's, is the identity); `growth_angles` turns it into theta_x and theta_z.
     Device tensors in, device tensors out, ONE read-back (the status); 12 + 2 max_sweeps launches whatever the map holds.
 
-    Not covered: hexagonal and other groups, stacks of maps in one launch, 8-connectivity.  A component whose pixels drift more
+    A stack of equal-shaped maps in the same launches is `label_orientation_maps`.  Not covered: hexagonal and other groups,
+    8-connectivity.  A component whose pixels drift more
     than about 20 degrees from its first pixel can align a pixel to the wrong equivalent."""
     v = _label_orient(quats, tol, valid, min_pixels, max_sweeps, boundary, grain_capacity, symmetry)
     status = dict(zip(LABEL_STATUS_WORDS, v["status"].tolist()))   # the one read-back
@@ -956,6 +1120,29 @@ def sample_from_euler_map(phi1, Phi, phi2, G, R, tol, min_pixels=1, degrees=Fals
     theta_x, theta_z = (t.cpu().numpy().astype(np.float32) for t in growth_angles(means))
     x, ei, ea = sample_from_image(image, theta_x, theta_z, G, R, n_grain=n_grain, **kw)
     return x, ei, ea, image, dict(status, mean_quats=means, theta_x=theta_x, theta_z=theta_z)
+
+
+def samples_from_euler_maps(phi1, Phi, phi2, G, R, tol, min_pixels=1, degrees=False, **kw):
+    """A union rollout's first state from a stack of EBSD maps: `quaternions_from_bunge` on the three stacks of Euler angles
+    ([T, ny, nx]), `label_orientation_maps` (tol in radians; symmetry, valid, max_sweeps and grain_capacity go to it),
+    `growth_angles` of the mean orientations read back once, and `samples_from_images` on the labelled images with
+    everything it takes (G and R: scalars or one value per map).
+
+    -> (x_dict, edge_index_dict, edge_attr, traj_offsets, images, statuses) as `samples_from_orientation_maps` gives them:
+    every trajectory's rows are, bit for bit, `sample_from_euler_map`'s on that map alone; every status also holds "mean_quats"
+    (device float32 [4, n_grain]).  Three read-backs whatever T.  A map that overflows grain_capacity raises and is named."""
+    label_kw = {k: kw.pop(k) for k in ("valid", "max_sweeps", "grain_capacity", "symmetry") if k in kw}
+    quats = quaternions_from_bunge(phi1, Phi, phi2, degrees)
+    quats = quats if quats.is_cuda else quats.cuda()
+    if quats.dim() != 4:
+        raise _lib.GGNNError("phi1, Phi and phi2 must be [T, ny, nx] stacks of maps")
+    images, n_grains, means, statuses = label_orientation_maps(quats, tol, min_pixels=min_pixels, boundary=kw.get("boundary", "periodic"),
+                                                               **label_kw)
+    _no_map_overflows(statuses)
+    host = means[:, :, :max(n_grains)].cpu().numpy()                       # every map's rows in one read-back
+    theta = [tuple(a.astype(np.float32) for a in growth_angles(host[t, :, :n])) for t, n in enumerate(n_grains)]
+    statuses = [dict(s, mean_quats=means[t, :, :n].contiguous()) for t, (s, n) in enumerate(zip(statuses, n_grains))]
+    return _union_from_labelled(images, n_grains, statuses, theta, G, R, kw)
 
 
 # ---- ids that persist across a sequence of labelled maps --------------------------------------------------------------------
@@ -1097,8 +1284,8 @@ def link_labels(labels, n_local, means=None, match_tol=None, min_overlap=1, boun
 def label_sequence(ids=None, angles=None, tol=None, valid=None, min_pixels=1, max_sweeps=64, boundary="periodic", match_tol=None,
                    min_overlap=1, grain_capacity=None):
     """A sequence of measured maps -- in-situ EBSD, serial sections, a phase-field run exported as orientations -- into grain-ID
-    images whose ids persist: `label_grains`' launches once per frame on the current stream, then `link_labels`' on the stack,
-    with nothing read back in between (every frame's number of grains goes from the labelling's status to the linking on the
+    images whose ids persist: ONE stacked labelling call (`label_maps`' launches) on the current stream, then `link_labels`' on
+    the stack, with nothing read back in between (every frame's number of grains goes from the labelling's status to the linking on the
     device) and ONE read-back at the end, of the T label status rows and the link status together.
 
     Exactly one of ids -- integer [T, ny, nx] -- and angles -- float32 [T, K, ny, nx] with tol --, on the device; valid: an
@@ -1106,8 +1293,8 @@ def label_sequence(ids=None, angles=None, tol=None, valid=None, min_pixels=1, ma
     `link_labels`, the means being the labelling's.  grain_capacity: room per frame (default min(ny nx // min_pixels + 2, 65536)).
 
     -> (frames, n_grain, theta, report) as `link_labels` gives them; report["label"] is the per-frame `label_grains` status.
-    Raises on n_bound_hits, as `label_grains` does, and on an overflow of a frame's labelling.  The labelling launches grow with
-    T (stacked labelling in one launch is not covered); the linking launches do not."""
+    Raises on n_bound_hits, as `label_grains` does, and on an overflow of a frame's labelling.  Neither the labelling launches
+    nor the linking launches grow with T."""
     _check_boundary(boundary)
     if (ids is None) == (angles is None):
         raise _lib.GGNNError("exactly one of ids and angles must be given")
@@ -1121,30 +1308,23 @@ def label_sequence(ids=None, angles=None, tol=None, valid=None, min_pixels=1, ma
     cap = min(ny * nx // max(int(min_pixels), 1) + 2, LINK_MAX_DEFAULT_CAPACITY) if grain_capacity is None else int(grain_capacity)
     if cap < (2 if noflux else 1):
         raise _lib.GGNNError("grain_capacity must hold at least one grain")
-    per_frame = [_label(None if ids is None else ids[t], None if angles is None else angles[t], tol, None if valid is None else valid[t],
-                        min_pixels, max_sweeps, boundary, cap) for t in range(T)]
-    return _link_frames(per_frame, angles is not None, match_tol, min_overlap, boundary, cap, "ggnn_label_grains")
+    stacked = _label_stack(ids, angles, tol, valid, min_pixels, max_sweeps, boundary, cap)
+    return _link_frames(stacked, match_tol, min_overlap, boundary, cap, "ggnn_label_grains_stack")
 
 
-def _link_frames(per_frame, with_means, match_tol, min_overlap, boundary, cap, entry):
-    """The frames of a sequence, each labelled on its own by `entry` (the dicts of `_label` or `_label_orient`), linked on the
-    device, and the ONE read-back of both statuses -> what `label_sequence` returns."""
-    T, noflux = len(per_frame), boundary == "noflux"
-    labels = torch.stack([v["image"] for v in per_frame])
-    label_status = torch.stack([v["status"] for v in per_frame])
+def _link_frames(stacked, match_tol, min_overlap, boundary, cap, entry):
+    """The frames of a sequence, labelled as a stack by `entry` (the dict of `_label_stack` or `_label_orient_stack`), linked on
+    the device, and the ONE read-back of both statuses -> what `label_sequence` returns."""
+    labels, label_status, means = stacked["image"], stacked["status"], stacked["means"]
+    T, noflux = labels.size(0), boundary == "noflux"
     n_local = label_status[:, LABEL_STATUS_WORDS.index("n_grains")].contiguous()
-    means = None
-    if with_means:
-        means = torch.stack([v["means"] for v in per_frame])
-        if noflux:                                         # (row 0 is the boundary grain's: local grain b is row b - 2 from here on)
-            means = means[:, :, 1:].contiguous()
+    if means is not None and noflux:                       # (row 0 is the boundary grain's: local grain b is row b - 2 from here on)
+        means = means[:, :, 1:].contiguous()
     v = _link_checked(labels, n_local, means, match_tol, min_overlap, boundary, cap - 1 if noflux else cap, None)
     words = torch.cat([label_status.reshape(-1), v["status"]]).tolist()   # the one read-back
     n = len(LABEL_STATUS_WORDS)
-    label_report = [dict(zip(LABEL_STATUS_WORDS, words[n * t:n * t + n])) for t in range(T)]
+    _, label_report = _stack_statuses(stacked, words[:n * T], entry)
     for t, s in enumerate(label_report):
-        if s["n_bound_hits"]:
-            raise _lib.GGNNError(f"{entry}: frame {t}: {s['n_bound_hits']} threads reached the bound of a parent walk: {s}")
         if s["overflow"]:
             raise _lib.GGNNError(f"frame {t} has more grains than grain_capacity {cap}: {s}")
     frames, n_grain, theta, report = _link_report(v, words[n * T:])
@@ -1176,8 +1356,9 @@ def samples_from_orientation_sequence(theta_x_maps, theta_z_maps, G, R, tol, min
 
 def label_orientation_sequence(quats, tol, valid=None, min_pixels=1, max_sweeps=64, boundary="periodic", match_tol=None,
                                min_overlap=1, grain_capacity=None, symmetry="cubic"):
-    """`label_sequence` for maps of full orientations: `label_orientations`' launches once per frame of quats (float32
-    [T, 4, ny, nx] on the device), then `link_labels`' on the stack by pixel overlap alone, with ONE read-back at the end.
+    """`label_sequence` for maps of full orientations: ONE stacked labelling call (`label_orientation_maps`' launches) on quats
+    (float32 [T, 4, ny, nx] on the device), then `link_labels`' on the stack by pixel overlap alone, with ONE read-back at the
+    end.
 
     -> (frames, n_grain, quat float32 [4, n_grain], report) as `label_sequence` gives them: quat is every grain's mean
     orientation in its first frame, copied (no-flux: row 0 is the identity).  match_tol raises: a per-channel gate on quaternion
@@ -1196,9 +1377,8 @@ def label_orientation_sequence(quats, tol, valid=None, min_pixels=1, max_sweeps=
     cap = min(ny * nx // max(int(min_pixels), 1) + 2, LINK_MAX_DEFAULT_CAPACITY) if grain_capacity is None else int(grain_capacity)
     if cap < (2 if noflux else 1):
         raise _lib.GGNNError("grain_capacity must hold at least one grain")
-    per_frame = [_label_orient(quats[t], tol, None if valid is None else valid[t], min_pixels, max_sweeps, boundary, cap, symmetry)
-                 for t in range(T)]
-    frames, n_grain, quat, report = _link_frames(per_frame, True, None, min_overlap, boundary, cap, "ggnn_label_orientations")
+    stacked = _label_orient_stack(quats, tol, valid, min_pixels, max_sweeps, boundary, cap, symmetry)
+    frames, n_grain, quat, report = _link_frames(stacked, None, min_overlap, boundary, cap, "ggnn_label_orientations_stack")
     if noflux:
         quat[0, 0] = 1.0                                   # the boundary grain's row, as label_orientations writes it
     return frames, n_grain, quat, report

@@ -1239,7 +1239,8 @@ int ggnn_track_targets(const ggnn_track_targets_args* args, ggnn_stream_t stream
 /* ------------------------------------------------------------------------------------
  * The way in from a MEASURED map: an orientation map (an EBSD scan: angles per pixel, non-indexed points, speckle) or a noisy
  * id image becomes the grain-ID image and the per-grain angles that the calls above take.  Setup work, on `stream`, nothing
- * through the host, exact in integers; tests/labelcheck.py restates the rule.  One image a call.
+ * through the host, exact in integers; tests/labelcheck.py restates the rule.  One image a call (T images a call:
+ * ggnn_label_grains_stack, after ggnn_label_orientations).
  *   input     : one image [ny, nx], nx, ny >= 3, `boundary` GGNN_BC_PERIODIC or GGNN_BC_NOFLUX, in one of two forms.
  *               ids: int32; a pixel is VALID when id >= 1 and the optional byte mask `valid` is non-zero there; two
  *               4-neighbours are LINKED when both are valid and their ids are equal.
@@ -1284,8 +1285,8 @@ int ggnn_track_targets(const ggnn_track_targets_args* args, ggnn_stream_t stream
  * outside [0, GGNN_LABEL_MAX_SWEEPS], grain_capacity outside [1, INT32_MAX), an unknown boundary, status or workspace not
  * 8-byte aligned, a 32-bit array not 4-byte aligned, a workspace below ggnn_label_workspace_bytes(nx, ny, K) (which is 0 for
  * sizes the call refuses).
- * Not covered: stacks of maps in one launch (a sequence is labelled frame by frame; ggnn_link_labels below then gives its
- * grains ids that persist across the frames), 8-connectivity.  The per-channel rule knows no crystal symmetry (a grain that
+ * A stack of equal-shaped maps in the same launches is ggnn_label_grains_stack below (ggnn_link_labels then gives a sequence's
+ * grains ids that persist across the frames).  Not covered: 8-connectivity.  The per-channel rule knows no crystal symmetry (a grain that
  * straddles the wrap of an angle comes out as two): full orientations under cubic symmetry are ggnn_label_orientations below. */
 #define GGNN_LABEL_TILE_X 64
 #define GGNN_LABEL_TILE_Y 16
@@ -1366,7 +1367,8 @@ int ggnn_label_grains(const ggnn_label_args* args, ggnn_stream_t stream);
  * outside [0, GGNN_LABEL_MAX_SWEEPS], grain_capacity outside [1, INT32_MAX), status or workspace not 8-byte aligned, a 32-bit
  * array not 4-byte aligned, a workspace below ggnn_label_orient_workspace_bytes(nx, ny) (which is 0 for sizes the call
  * refuses).
- * Not covered: hexagonal and other groups, a symmetry-aware gate in ggnn_link_labels, stacks in one launch, 8-connectivity. */
+ * A stack of maps in the same launches is ggnn_label_orientations_stack below.
+ * Not covered: hexagonal and other groups, a symmetry-aware gate in ggnn_link_labels, 8-connectivity. */
 #define GGNN_SYM_NONE 0
 #define GGNN_SYM_CUBIC 1
 #define GGNN_ORIENT_OPS 24
@@ -1387,6 +1389,76 @@ typedef struct ggnn_label_orient_args {
 } ggnn_label_orient_args;
 size_t ggnn_label_orient_workspace_bytes(int64_t nx, int64_t ny);
 int ggnn_label_orientations(const ggnn_label_orient_args* args, ggnn_stream_t stream);
+/* ------------------------------------------------------------------------------------
+ * The two segmentations above for a STACK of T equal-shaped maps -- a recorded sequence, or an ensemble of scans that goes into
+ * one union rollout -- in launches that do not grow with T.  The rule is the single call's, by reference:
+ *     frame t's image, means and nine words are ggnn_label_grains' (ggnn_label_orientations') on frame t, bit for bit.
+ * Frames never interact: no link, seam, vote or neighbour crosses a frame edge, and the periodic wrap of frame t goes to frame
+ * t's own row 0 or column 0.  tests/labelcheck.py and tests/orientcheck.py, frame by frame, restate it.
+ *   input     : T >= 1 frames of [ny, nx], N = ny nx; pixel p of frame t has index t N + p.  ids int32 [T, ny, nx] or angles
+ *               float32 [T, K, ny, nx] (channel k of frame t at (t K + k) N), valid bytes [T, ny, nx] or NULL; quats float32
+ *               [T, 4, ny, nx].  Every other field means what it means in the single call and holds for every frame alike
+ *               (grain_capacity: rows PER FRAME).
+ *   outputs   : image int32 [T, ny, nx]: ids restart in every frame (periodic from 1, no-flux from 2).  mean_angles float32
+ *               [T, K, grain_capacity], row g of channel k of frame t at (t K + k) grain_capacity + g (mean_quats: K = 4);
+ *               no-flux: row 0 of every frame is 0 (the identity).  Rows from a frame's n_grain on are not written.
+ *               status int64 [T, GGNN_LABEL_STATUS_WORDS], zeroed by the call: row t holds frame t's nine words; n_grains,
+ *               n_sweeps (the sweeps that assigned something IN FRAME t), overflow and n_bound_hits are per frame.
+ *   limits    : T nx ny <= INT32_MAX (parents, roots and list entries stay int32); nx, ny in [3, 2^15).  A larger stack, or
+ *               maps of different shapes, are split by the caller.  The workspace is the single call's per-frame carve times
+ *               T (about 21 + 8 K bytes a pixel, 4 100 bytes of sweep words a frame), with no counter shared between
+ *               workgroups; ggnn_label_stack_workspace_bytes(1, nx, ny, K) == ggnn_label_workspace_bytes(nx, ny, K).
+ * ggnn_label_grains_stack = two memsets and 9 + 2 max_sweeps launches, ggnn_label_orientations_stack = two memsets and 12 + 2
+ * max_sweeps launches, whatever T and whatever the maps hold: the single call's stages, each with a frame dimension (one kernel
+ * body a stage; the single calls ARE the T = 1 call of the same host routine).  Tiles: T tiles workgroups.  Seams: a thread a
+ * pair of every frame.  A chunk of 1 024 pixels (classify, the open lists, the sweeps, the rank) never straddles two frames:
+ * ceil(N / 1 024) chunks a frame, the last one partial.  Sweeps: a word per (frame, sweep) and one per sweep summed over the
+ * frames; a launch after a sweep that assigned nothing in any frame returns on the summed word without walking a list, and the
+ * chunks of a frame that has gone quiet are skipped on the frame's word.  Rank: the scan of the block sums is one workgroup a
+ * frame.  Counters: a wave whose lanes lie in several frames (N no multiple of 64) issues an atomic a lane into each lane's own
+ * row, a wave inside one frame one atomic.  The budgets of the parent walks are those of ONE frame (4 x 1 024 hops in a tile,
+ * 2 N + 64 in a seam, N + 1 in flatten).  No kernel waits on another workgroup; parent words that another workgroup may write in
+ * the same launch are touched with agent-scope atomics alone; nothing outside the named arrays is addressed, whatever the inputs
+ * hold; the call can be captured, and a replay gives the same bits.
+ * GGNN_EINVAL without a launch: everything ggnn_label_grains (ggnn_label_orientations) refuses, T < 1, T nx ny > INT32_MAX, a
+ * workspace below ggnn_label_stack_workspace_bytes(T, nx, ny, K) (ggnn_label_orient_stack_workspace_bytes(T, nx, ny)), which is
+ * 0 for what the call refuses.
+ * Not covered: stacks of mixed shapes, stacks beyond INT32_MAX pixels (no automatic splitter), 8-connectivity. */
+typedef struct ggnn_label_stack_args {
+  const int32_t* ids;            /* [T, ny, nx], device, or NULL */
+  const float* angles;           /* [T, K, ny, nx], device, or NULL: exactly one of the two */
+  const uint8_t* valid;          /* [T, ny, nx] bytes, device, or NULL: every pixel allowed */
+  int32_t* image;                /* [T, ny, nx] out */
+  float* mean_angles;            /* [T, K, grain_capacity] out (NULL with ids) */
+  int64_t* status;               /* [T, GGNN_LABEL_STATUS_WORDS] out */
+  void* workspace;               /* ggnn_label_stack_workspace_bytes(T, nx, ny, K) of device scratch */
+  size_t workspace_bytes;
+  int64_t T;
+  int64_t nx, ny, grain_capacity, min_pixels;
+  float tol;
+  int32_t K;                     /* channels of angles; 0 with ids */
+  int32_t max_sweeps;
+  int32_t boundary;              /* GGNN_BC_PERIODIC / GGNN_BC_NOFLUX */
+} ggnn_label_stack_args;
+size_t ggnn_label_stack_workspace_bytes(int64_t T, int64_t nx, int64_t ny, int32_t K);
+int ggnn_label_grains_stack(const ggnn_label_stack_args* args, ggnn_stream_t stream);
+typedef struct ggnn_label_orient_stack_args {
+  const float* quats;            /* [T, 4, ny, nx], device */
+  const uint8_t* valid;          /* [T, ny, nx] bytes, device, or NULL: every pixel allowed */
+  int32_t* image;                /* [T, ny, nx] out */
+  float* mean_quats;             /* [T, 4, grain_capacity] out */
+  int64_t* status;               /* [T, GGNN_LABEL_STATUS_WORDS] out */
+  void* workspace;               /* ggnn_label_orient_stack_workspace_bytes(T, nx, ny) of device scratch */
+  size_t workspace_bytes;
+  int64_t T;
+  int64_t nx, ny, grain_capacity, min_pixels;
+  float cos_half_tol;            /* (float)cos((double)tol / 2) */
+  int32_t symmetry;              /* GGNN_SYM_NONE / GGNN_SYM_CUBIC */
+  int32_t max_sweeps;
+  int32_t boundary;              /* GGNN_BC_PERIODIC / GGNN_BC_NOFLUX */
+} ggnn_label_orient_stack_args;
+size_t ggnn_label_orient_stack_workspace_bytes(int64_t T, int64_t nx, int64_t ny);
+int ggnn_label_orientations_stack(const ggnn_label_orient_stack_args* args, ggnn_stream_t stream);
 /* ------------------------------------------------------------------------------------
  * Grain ids that PERSIST across a sequence of labelled maps: ggnn_label_grains numbers every frame by the raster order of its
  * grains' first pixels, so the numbering changes as soon as a boundary moves or a grain vanishes, and ggnn_track_targets needs
@@ -1449,7 +1521,8 @@ int ggnn_label_orientations(const ggnn_label_orient_args* args, ggnn_stream_t st
  * >= 0, an unknown boundary, n_local, status or workspace not 8-byte aligned, a 32-bit array not 4-byte aligned, a workspace
  * below ggnn_link_workspace_bytes(T, local_capacity, K) (which is 0 for sizes the call refuses).
  * Not covered: merging grains (two grains that become one: the smaller one is gone), a grain that reappears keeping its id,
- * matching across more than one frame back, crystal symmetry in the gate, labelling the stack in one launch. */
+ * matching across more than one frame back, crystal symmetry in the gate.  (The stack itself is labelled in launches that do
+ * not grow with T by ggnn_label_grains_stack / ggnn_label_orientations_stack above.) */
 #define GGNN_LINK_SLOTS 16
 #define GGNN_LINK_RUN 4
 #define GGNN_LINK_FRAME_WORDS 6

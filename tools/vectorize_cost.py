@@ -66,7 +66,17 @@ rocprofv3 --kernel-trace --stats around this tool).
     python tools/vectorize_cost.py --link [--rounds 20] [--size 128] [--no-host]
 --label-orient times segmenting a map of full orientations under cubic symmetry (vectorize.label_orientations,
 ggnn_label_orientations) beside --label's angle call on --label's two maps, the two alternating within a round (label_orient_cost).
-    python tools/vectorize_cost.py --label-orient [--rounds 20] [--size 4096]"""
+    python tools/vectorize_cost.py --label-orient [--rounds 20] [--size 4096]
+--label-stack times labelling a STACK of maps in one call (vectorize.label_maps, ggnn_label_grains_stack) in ids mode on --link's
+two sequences and, with --big B, on B copies of --label's 4 096 x 4 096 Voronoi map (min_pixels 8; there the work dominates, not
+the launches); and prints
+  stack      ggnn_label_grains_stack on prepared arguments, by events
+  singles    T x ggnn_label_grains on prepared arguments, by events
+  sequence   one label_sequence (the stacked labelling, the linking, the read-back), by the host clock
+The arms alternate within a round; median (min - max) of the rounds after three warm-up rounds.  Then, in a pass of their
+own, the device activities of one stacked call at T = 2 and at T, for ids and for orientations (they must not differ, and
+must be 2 memsets + 9 + 2 max_sweeps and 12 + 2 max_sweeps kernels), and the device time of every kernel at T.
+    python tools/vectorize_cost.py --label-stack [--rounds 20] [--size 128] [--big 8]"""
 import argparse
 import ctypes
 import os
@@ -87,12 +97,16 @@ def main():
     ap.add_argument("--label", action="store_true", help="the cost of label_grains")
     ap.add_argument("--link", action="store_true", help="the cost of link_labels and label_sequence")
     ap.add_argument("--label-orient", action="store_true", help="the cost of label_orientations beside label_grains")
+    ap.add_argument("--label-stack", action="store_true", help="the cost of label_maps against T x label_grains and label_sequence")
+    ap.add_argument("--big", type=int, default=0, metavar="B", help="--label-stack: also B copies of the 4 096 x 4 096 Voronoi map")
     ap.add_argument("--host-rounds", type=int, default=2, help="--label: timed rounds of the host route on the large map")
     ap.add_argument("--no-host", action="store_true", help="--label: leave the host route out (a profiler's run)")
     a = ap.parse_args()
     sys.path[:0] = [os.path.dirname(HERE)]
     if a.size is None:
-        a.size = 128 if a.union or a.track or a.link else 4096
+        a.size = 128 if a.union or a.track or a.link or a.label_stack else 4096
+    if a.label_stack:
+        return label_stack_cost(a)
     if a.link:
         return link_cost(a)
     if a.label_orient:
@@ -524,6 +538,99 @@ def link_cost(a):
                             print(f"    {e.count:3d} x {e.key[:110]}: {t:.1f} us by the tracer", flush=True)
         except Exception as exc:   # (a build of torch without the tracer)
             print(f"# launches not counted: {type(exc).__name__}: {exc}", flush=True)
+    print(f"# torch {torch.__version__}, {torch.cuda.get_device_name()}", flush=True)
+
+
+def label_stack_cost(a):
+    import time
+    import numpy as np
+    import torch
+    from graingraphnn_amd import _lib
+    from graingraphnn_amd import vectorize as vz
+    dev = torch.device("cuda", 0)
+    lib = _lib.load()
+    d = np.load(os.path.join(os.path.dirname(HERE), "tests", "golden", "pf_frames_cfg1.npz"))
+    sequences = {"recorded, 7 frames 501 x 501": (torch.from_numpy(d["frames"].astype(np.int32)).to(dev), 1, 256, a.rounds),
+                 f"drift, 64 frames {a.size} x {a.size}": (lattice_frames(64, a.size, a.seed, dev), 1, 256, a.rounds)}
+    if a.big:
+        big = argparse.Namespace(size=4096, seed=a.seed)
+        ids = torch.from_numpy(measured_maps(big, dev)[2].astype(np.int32)).to(dev)
+        sequences[f"Voronoi with 1 % noise, {a.big} frames 4096 x 4096"] = (ids[None].repeat(a.big, 1, 1), 8, 4096 * 4096 // 8 + 2,
+                                                                           max(3, a.rounds // 4))
+
+    def by_events(call):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        call()
+        t1.record()
+        t1.synchronize()
+        return t0.elapsed_time(t1) * 1e3
+
+    def by_clock(call):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        call()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e6
+
+    def activities(call):
+        from torch.profiler import ProfilerActivity, profile
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            call()
+            torch.cuda.synchronize()
+        return sum(1 for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA), prof
+
+    for name, (ids, mp, cap, rounds) in sequences.items():
+        T, ny, nx = ids.shape
+        stacked = vz._label_stack(ids, None, None, None, mp, 64, "periodic", cap)
+        singles = [vz._label(ids[t], None, None, None, mp, 64, "periodic", cap) for t in range(T)]
+        torch.cuda.synchronize()
+        same = all(torch.equal(stacked["image"][t], v["image"]) and torch.equal(stacked["status"][t], v["status"]) for t, v in enumerate(singles))
+        grains = stacked["status"][:, 4].tolist()
+        print(f"# {name}: grains per frame {grains[0]} .. {grains[-1]}, sweeps {stacked['status'][:, 5].tolist()}; the stacked call equals the "
+              f"{T} single calls: {same}; workspace {lib.ggnn_label_stack_workspace_bytes(T, nx, ny, 0) / 1e6:.1f} MB against "
+              f"{lib.ggnn_label_workspace_bytes(nx, ny, 0) / 1e6:.1f} MB a frame", flush=True)
+        A, As = stacked["calls"][0], [v["calls"][0] for v in singles]
+
+        def all_singles():
+            for At in As:
+                _lib.check(lib.ggnn_label_grains(ctypes.byref(At), _lib.current_stream()), "label")
+        arms = {"stack": lambda: by_events(lambda: _lib.check(lib.ggnn_label_grains_stack(ctypes.byref(A), _lib.current_stream()), "stack")),
+                "singles": lambda: by_events(all_singles)}
+        if cap <= vz.LINK_MAX_DEFAULT_CAPACITY:                       # (the linking takes at most 65 536 rows a frame)
+            arms["sequence"] = lambda: by_clock(lambda: vz.label_sequence(ids=ids, min_pixels=mp, grain_capacity=cap))
+        times = {k: [] for k in arms}
+        for rnd in range(rounds + 3):
+            for arm, call in arms.items():
+                t = call()
+                if rnd >= 3:
+                    times[arm].append(t)
+        for arm, t in times.items():
+            t = np.array(t)
+            print(f"{arm:8s} us ({len(t)} rounds): median {np.median(t):12.1f}  ({t.min():.1f} - {t.max():.1f})", flush=True)
+        print(f"# singles / stack = {np.median(times['singles']) / np.median(times['stack']):.2f}", flush=True)
+        try:
+            table = torch.randn(4, int(ids.max()) + 1, device=dev)
+            table = (table / table.norm(dim=0)).to(torch.float32)
+            for n in sorted({2, T}):
+                few = ids[:n].contiguous()
+                An = vz._label_stack(few, None, None, None, mp, 64, "periodic", cap)["calls"]
+                k, prof = activities(lambda: _lib.check(lib.ggnn_label_grains_stack(ctypes.byref(An[0]), _lib.current_stream()), "stack"))
+                quats = table[:, few.long()].permute(1, 0, 2, 3).contiguous()
+                On = vz._label_orient_stack(quats, float(np.deg2rad(2.0)), None, mp, 64, "periodic", cap, "cubic")["calls"]
+                ko, _ = activities(lambda: _lib.check(lib.ggnn_label_orientations_stack(ctypes.byref(On[0]), _lib.current_stream()), "stack"))
+                print(f"T = {n:3d}  device activities (kernels, memsets) of one stacked call: ids {k} (2 + 9 + 2 x 64 = 139), orientations {ko} "
+                      f"(2 + 12 + 2 x 64 = 142)", flush=True)
+                del quats, On
+                if n == T:
+                    for e in sorted(prof.key_averages(), key=lambda e: e.key):
+                        t = getattr(e, "device_time_total", None)
+                        t = getattr(e, "cuda_time_total", 0.0) if t is None else t
+                        if t:
+                            print(f"    {e.count:3d} x {e.key[:110]}: {t:.1f} us by the tracer", flush=True)
+        except Exception as exc:   # (a build of torch without the tracer)
+            print(f"# launches not counted: {type(exc).__name__}: {exc}", flush=True)
+        del stacked, singles
     print(f"# torch {torch.__version__}, {torch.cuda.get_device_name()}", flush=True)
 
 
