@@ -30,6 +30,7 @@ GGNN_FLAG_POLYGON_OVERFLOW = 4
 GGNN_INTERP_MAX_JOBS = 256
 GGNN_JUNCTION_SEGMENT, GGNN_JUNCTION_STATUS_WORDS, GGNN_JUNCTION_MAX_BLOCKS = 256, 7, 1 << 22
 GGNN_TRACE_COUNTERS = 3
+GGNN_PINCH_JUNCTION, GGNN_PINCH_NECK = 0, 1
 GGNN_LABEL_TILE_X, GGNN_LABEL_TILE_Y, GGNN_LABEL_STATUS_WORDS, GGNN_LABEL_MAX_SWEEPS = 64, 16, 9, 1024
 GGNN_SYM_NONE, GGNN_SYM_CUBIC, GGNN_ORIENT_OPS, GGNN_ORIENT_H = 0, 1, 24, 0.70710678
 GGNN_LINK_SLOTS, GGNN_LINK_RUN, GGNN_LINK_FRAME_WORDS, GGNN_LINK_GLOBAL_WORDS = 16, 4, 6, 2
@@ -67,6 +68,7 @@ EXPORTED_SYMBOLS = (
     "ggnn_polygons_rasterize", "ggnn_image_compare", "ggnn_image_junctions", "ggnn_junction_links",
     "ggnn_image_junctions_traj", "ggnn_junction_links_traj", "ggnn_track_junctions", "ggnn_track_targets",
     "ggnn_image_junction_windows_traj", "ggnn_junction_links_trace_traj",
+    "ggnn_image_junctions_pinch_traj", "ggnn_image_junction_windows_pinch_traj", "ggnn_junction_links_trace_pinch_traj",
     "ggnn_label_workspace_bytes", "ggnn_label_grains", "ggnn_link_workspace_bytes", "ggnn_link_labels",
     "ggnn_label_orient_workspace_bytes", "ggnn_label_orientations",
     "ggnn_label_stack_workspace_bytes", "ggnn_label_grains_stack", "ggnn_label_orient_stack_workspace_bytes",
@@ -726,6 +728,12 @@ def _declare(lib):
     lib.ggnn_image_junction_windows_traj.argtypes = [POINTER(JunctionTrajArgs), c_void_p, c_void_p]
     lib.ggnn_junction_links_trace_traj.restype = c_int
     lib.ggnn_junction_links_trace_traj.argtypes = [POINTER(LinkTraceArgs), c_void_p]
+    lib.ggnn_image_junctions_pinch_traj.restype = c_int
+    lib.ggnn_image_junctions_pinch_traj.argtypes = [POINTER(JunctionTrajArgs), c_int32, c_void_p, c_void_p]
+    lib.ggnn_image_junction_windows_pinch_traj.restype = c_int
+    lib.ggnn_image_junction_windows_pinch_traj.argtypes = [POINTER(JunctionTrajArgs), c_void_p, c_int32, c_void_p, c_void_p]
+    lib.ggnn_junction_links_trace_pinch_traj.restype = c_int
+    lib.ggnn_junction_links_trace_pinch_traj.argtypes = [POINTER(LinkTraceArgs), c_int32, c_void_p]
     lib.ggnn_track_junctions.restype = c_int
     lib.ggnn_track_junctions.argtypes = [POINTER(TrackArgs), c_void_p]
     lib.ggnn_track_targets.restype = c_int

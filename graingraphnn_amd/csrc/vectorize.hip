@@ -30,6 +30,9 @@
 // adds the length of its run of equal ids in the wave, so a row inside a grain is one atomic and not 64.  A single image is
 // the stack of one with the image's own ids: no grain_off and no joint_off exist for it, and every read or write of either
 // stands in code that STACK = false compiles out.
+// PINCH is a compile-time mode too (the _pinch_traj entry points; tests/pinchcheck.py restates it): GGNN_PINCH_NECK gives a
+// window of three ids whose repeated id sits on a diagonal no key -- a grain's neck through a pixel corner is no junction --,
+// in window_keys alone, which everything else reads; instantiated for stacks, and the default keeps its instruction stream.
 // Every index is clamped as elsewhere: a pixel outside [1, n_grain] voids its windows, nothing is written at or beyond
 // joint_capacity, and ggnn_junction_links bounds every row and column it reads by the tables' sizes.
 #include <algorithm>
@@ -67,20 +70,28 @@ __device__ __forceinline__ int32_t pixel_at(const int32_t* __restrict__ image, i
   return inside ? (v == 1 ? 0 : v) : 1;
 }
 
-// The keys of window (y, x), 0-based grains, ascending: -> how many (0, 1 or 2 = a quadruple).
-template <int BC>
+// The keys of window (y, x), 0-based grains, ascending: -> how many (0, 1 or 2 = a quadruple).  This is the one place that
+// says what a window CARRIES.  PINCH = GGNN_PINCH_NECK: a window of three distinct valid ids whose repeated id sits on a
+// diagonal ([a b; c a] or [b a; a c]: grain a runs through the corner as a neck one pixel wide) carries nothing, and `pinch`
+// says so, false for every other window; GGNN_PINCH_JUNCTION never writes it, and its instruction stream is the one it was.
+template <int BC, int PINCH>
 __device__ __forceinline__ int window_keys(const int32_t* __restrict__ image, int y, int x, int nx, int ny, int32_t n_grain,
-                                           int32_t (&k)[2][3], bool& tl_invalid) {
+                                           int32_t (&k)[2][3], bool& tl_invalid, bool& pinch) {
   const int x1 = BC == GGNN_BC_PERIODIC && x + 1 == nx ? 0 : x + 1, y1 = BC == GGNN_BC_PERIODIC && y + 1 == ny ? 0 : y + 1;
   const int32_t tl = pixel_at<BC>(image, y, x, nx, ny), tr = pixel_at<BC>(image, y, x1, nx, ny);
   const int32_t bl = pixel_at<BC>(image, y1, x, nx, ny), br = pixel_at<BC>(image, y1, x1, nx, ny);
   tl_invalid = tl < 1 || tl > n_grain;
+  if (PINCH == GGNN_PINCH_NECK) pinch = false;
   if (tl == tr && tl == bl && tl == br) return 0;
   if (tl_invalid || tr < 1 || tr > n_grain || bl < 1 || bl > n_grain || br < 1 || br > n_grain) return 0;
   const bool e01 = tl == tr, e02 = tl == bl, e03 = tl == br, e12 = tr == bl, e13 = tr == br, e23 = bl == br;
   const int equal = e01 + e02 + e03 + e12 + e13 + e23;   // 0: four distinct ids, 1: three, more: fewer
   if (equal > 1) return 0;
   if (equal == 1) {   // the three distinct ones: all but the second pixel of the equal pair
+    if (PINCH == GGNN_PINCH_NECK && (e03 || e12)) {
+      pinch = true;
+      return 0;
+    }
     k[0][0] = tl - 1;
     k[0][1] = (e01 ? bl : tr) - 1;
     k[0][2] = (e01 || e02 || e12 ? br : bl) - 1;
@@ -99,12 +110,12 @@ __device__ __forceinline__ int window_keys(const int32_t* __restrict__ image, in
   return 2;
 }
 
-template <int BC>
+template <int BC, int PINCH>
 __device__ __forceinline__ bool window_carries(const int32_t* __restrict__ image, int y, int x, int nx, int ny, int32_t n_grain,
                                                const int32_t (&key)[3]) {
   int32_t k[2][3];
-  bool unused;
-  const int n = window_keys<BC>(image, y, x, nx, ny, n_grain, k, unused);
+  bool unused, no_key = false;
+  const int n = window_keys<BC, PINCH>(image, y, x, nx, ny, n_grain, k, unused, no_key);
   for (int i = 0; i < n; ++i)
     if (k[i][0] == key[0] && k[i][1] == key[1] && k[i][2] == key[2]) return true;
   return false;
@@ -112,7 +123,7 @@ __device__ __forceinline__ bool window_carries(const int32_t* __restrict__ image
 
 // Is window (y, x) the representative of `key`; m, sx, sy = the carriers at offsets within R (itself included) and the sums
 // of their offsets.  Periodic: the offsets wrap.  No-flux: the window range [-1, ny - 1] x [-1, nx - 1] clips them.
-template <int BC>
+template <int BC, int PINCH>
 __device__ __forceinline__ bool window_represents(const int32_t* __restrict__ image, int y, int x, int nx, int ny, int32_t n_grain,
                                                   int R, const int32_t (&key)[3], int& m, int& sx, int& sy) {
   bool rep = true;
@@ -130,7 +141,7 @@ __device__ __forceinline__ bool window_represents(const int32_t* __restrict__ im
         xx += xx < 0 ? nx : xx >= nx ? -nx : 0;
       else if (xx < -1 || xx >= nx)
         continue;
-      if (!window_carries<BC>(image, yy, xx, nx, ny, n_grain, key)) continue;
+      if (!window_carries<BC, PINCH>(image, yy, xx, nx, ny, n_grain, key)) continue;
       if (yy < y || (yy == y && xx < x)) rep = false;   // a smaller raster index
       ++m, sx += dx, sy += dy;
     }
@@ -160,6 +171,7 @@ struct junction_kargs {
   float offset, pitch;
   int32_t merge_radius;
   int32_t segments, rows;        // the blocks of a row of windows, the rows of windows of an image
+  int64_t* pinch_windows;        // [n_image], PINCH = GGNN_PINCH_NECK alone: the pinch windows of every image
 };
 
 // The grains of image b: -> the first one, n = how many (0 when the offsets do not rise).
@@ -174,7 +186,8 @@ __device__ __forceinline__ int64_t image_grains(const int64_t* __restrict__ grai
 // EMIT = true : block_count holds the exclusive scan; the junctions are written.
 // BC = GGNN_BC_NOFLUX: the grid is ny + 1 rows of segments of the nx + 1 windows of a row, and window (y, x) begins at -1.
 // STACK = false: the image is the one image, its grains are 0 .. n_grain - 1 and its status row is the one row.
-template <bool EMIT, int BC, bool STACK>
+// PINCH = GGNN_PINCH_NECK (stacks alone): the count pass also sums the pinch windows of every image, as it does the quadruples.
+template <bool EMIT, int BC, bool STACK, int PINCH = GGNN_PINCH_JUNCTION>
 __global__ __launch_bounds__(VEC_BLOCK) void image_junctions_kernel(const junction_kargs A) {
   __shared__ int wave_total[VEC_WAVES];
   constexpr int FIRST = BC == GGNN_BC_PERIODIC ? 0 : -1;
@@ -195,10 +208,11 @@ __global__ __launch_bounds__(VEC_BLOCK) void image_junctions_kernel(const juncti
   const int y = row + FIRST, x = (in_image - row * segments) * VEC_BLOCK + threadIdx.x + FIRST;
   int32_t k[2][3];
   int n_keys = 0, m[2] = {0, 0}, sx[2] = {0, 0}, sy[2] = {0, 0};
-  bool rep[2] = {false, false}, tl_invalid = false;
+  bool rep[2] = {false, false}, tl_invalid = false, pinch = false;   // (pinch: window_keys<.., GGNN_PINCH_JUNCTION> leaves it)
   if (x < nx) {
-    n_keys = window_keys<BC>(image, y, x, nx, ny, n_grain, k, tl_invalid);
-    for (int i = 0; i < n_keys; ++i) rep[i] = window_represents<BC>(image, y, x, nx, ny, n_grain, R, k[i], m[i], sx[i], sy[i]);
+    n_keys = window_keys<BC, PINCH>(image, y, x, nx, ny, n_grain, k, tl_invalid, pinch);
+    for (int i = 0; i < n_keys; ++i)
+      rep[i] = window_represents<BC, PINCH>(image, y, x, nx, ny, n_grain, R, k[i], m[i], sx[i], sy[i]);
   }
   const int mine = (rep[0] ? 1 : 0) + (rep[1] ? 1 : 0);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -218,6 +232,10 @@ __global__ __launch_bounds__(VEC_BLOCK) void image_junctions_kernel(const juncti
       if (quads) atomicAdd(status + 1, quads);
       if (merged) atomicAdd(status + 2, merged);
       if (invalid) atomicAdd(status + 3, invalid);
+    }
+    if (PINCH == GGNN_PINCH_NECK) {
+      const unsigned long long pinches = wave_sum(pinch ? 1 : 0);
+      if (lane == 0 && pinches) atomicAdd((unsigned long long*)A.pinch_windows + b, pinches);
     }
     if (STACK) {
       // the pixel counts: the image's own word of the TL pixel (id 1 of a no-flux image included: the counts are a histogram)
@@ -470,15 +488,15 @@ TRACE_FN int64_t trace_owner(const trace_image& I, int y, int x, const int32_t (
   return best;
 }
 
-template <int BC>
+template <int BC, int PINCH>
 __device__ bool trace_owned(const trace_image& I, int64_t j, const int32_t (&key)[3], int y, int x) {
-  return trace_in_range<BC>(I, y, x) && window_carries<BC>(I.image, y, x, I.nx, I.ny, I.n_grain, key) &&
+  return trace_in_range<BC>(I, y, x) && window_carries<BC, PINCH>(I.image, y, x, I.nx, I.ny, I.n_grain, key) &&
          trace_owner<BC>(I, y, x, key) == j;
 }
 
 // The exits of junction j (local key) for the ids ia, ib -> how many, the last one as the vertex reached and the crack taken;
 // n_diag, (qy, qx): the quadruple windows owned by j whose TL and BR are the two ids, and the last of them.
-template <int BC>
+template <int BC, int PINCH>
 TRACE_FN int trace_exits(const trace_image& I, int64_t j, const int32_t (&key)[3], int32_t ia, int32_t ib, int& ey, int& ex,
                            int& ed, int& n_diag, int& qy, int& qx) {
   int n = 0, ry, rx;
@@ -491,7 +509,7 @@ TRACE_FN int trace_exits(const trace_image& I, int64_t j, const int32_t (&key)[3
         y += y < 0 ? I.ny : y >= I.ny ? -I.ny : 0;
         x += x < 0 ? I.nx : x >= I.nx ? -I.nx : 0;
       }
-      if (!trace_owned<BC>(I, j, key, y, x)) continue;
+      if (!trace_owned<BC, PINCH>(I, j, key, y, x)) continue;
       int32_t px[4];
       const int cracks = trace_cracks<BC>(I, y, x, ia, ib, px);
       const bool quad = px[0] != px[1] && px[0] != px[2] && px[0] != px[3] && px[1] != px[2] && px[1] != px[3] && px[2] != px[3];
@@ -500,29 +518,29 @@ TRACE_FN int trace_exits(const trace_image& I, int64_t j, const int32_t (&key)[3
         if (!(cracks >> d & 1)) continue;
         int y2, x2;
         trace_step<BC>(I, y, x, d, y2, x2);
-        if (!trace_owned<BC>(I, j, key, y2, x2)) ++n, ey = y2, ex = x2, ed = d;
+        if (!trace_owned<BC, PINCH>(I, j, key, y2, x2)) ++n, ey = y2, ex = x2, ed = d;
       }
     }
   return n;
 }
 
 // The partner of junction j (local key) for its local grains a, b -> TRACE_*; o: the partner when traced.
-template <int BC>
+template <int BC, int PINCH>
 TRACE_FN int trace_partner(const trace_image& I, int64_t j, const int32_t (&key)[3], int32_t a, int32_t b, int64_t max_trace,
                              int64_t& o) {
   const int32_t ia = a + 1, ib = b + 1;
   int y = 0, x = 0, d = 0, n_diag, qy = 0, qx = 0;
-  const int n_exit = trace_exits<BC>(I, j, key, ia, ib, y, x, d, n_diag, qy, qx);
+  const int n_exit = trace_exits<BC, PINCH>(I, j, key, ia, ib, y, x, d, n_diag, qy, qx);
   int32_t k[2][3];
-  bool unused;
+  bool unused, no_key = false;
   if (n_diag) {   // the diagonal of a quadruple window: its two junctions, when each has this one diagonal
     if (n_diag != 1) return TRACE_FAILED;
-    if (window_keys<BC>(I.image, qy, qx, I.nx, I.ny, I.n_grain, k, unused) != 2) return TRACE_FAILED;
+    if (window_keys<BC, PINCH>(I.image, qy, qx, I.nx, I.ny, I.n_grain, k, unused, no_key) != 2) return TRACE_FAILED;
     const int other = k[0][0] == key[0] && k[0][1] == key[1] && k[0][2] == key[2] ? 1 : 0;
     o = trace_owner<BC>(I, qy, qx, k[other]);
     if (o < 0 || o == j) return TRACE_FAILED;
     int ty, tx, td, their_diag, ry = 0, rx = 0;
-    trace_exits<BC>(I, o, k[other], ia, ib, ty, tx, td, their_diag, ry, rx);
+    trace_exits<BC, PINCH>(I, o, k[other], ia, ib, ty, tx, td, their_diag, ry, rx);
     return their_diag == 1 && ry == qy && rx == qx ? TRACE_TRACED : TRACE_FAILED;
   }
   if (n_exit != 1) return TRACE_FAILED;
@@ -530,14 +548,14 @@ TRACE_FN int trace_partner(const trace_image& I, int64_t j, const int32_t (&key)
   for (int64_t steps = 1;; ++steps) {
     if (steps > max_trace) return TRACE_OVERFLOW;
     if (!trace_in_range<BC>(I, y, x)) return TRACE_FAILED;
-    const int n_keys = window_keys<BC>(I.image, y, x, I.nx, I.ny, I.n_grain, k, unused);
+    const int n_keys = window_keys<BC, PINCH>(I.image, y, x, I.nx, I.ny, I.n_grain, k, unused, no_key);
     for (int i = 0; i < n_keys; ++i) {
       const bool has_a = k[i][0] == a || k[i][1] == a || k[i][2] == a, has_b = k[i][0] == b || k[i][1] == b || k[i][2] == b;
       if (!(has_a && has_b)) continue;
       o = trace_owner<BC>(I, y, x, k[i]);   // the junction at the other end
       if (o < 0 || o == j) return TRACE_FAILED;
       int ty, tx, td, their_diag, ry, rx;
-      const int theirs = trace_exits<BC>(I, o, k[i], ia, ib, ty, tx, td, their_diag, ry, rx);
+      const int theirs = trace_exits<BC, PINCH>(I, o, k[i], ia, ib, ty, tx, td, their_diag, ry, rx);
       return their_diag == 0 && theirs == 1 ? TRACE_TRACED : TRACE_FAILED;
     }
     int32_t px[4];
@@ -550,7 +568,7 @@ TRACE_FN int trace_partner(const trace_image& I, int64_t j, const int32_t (&key)
   }
 }
 
-template <int BC>
+template <int BC, int PINCH = GGNN_PINCH_JUNCTION>
 __global__ __launch_bounds__(256) void junction_trace_kernel(const ggnn_link_trace_args A) {
   const int64_t* joint_off = A.status + A.n_image * GGNN_JUNCTION_STATUS_WORDS;
   const int64_t n = min(max(joint_off[A.n_image], (int64_t)0), A.joint_capacity);
@@ -576,7 +594,7 @@ __global__ __launch_bounds__(256) void junction_trace_kernel(const ggnn_link_tra
     key[i] = (int32_t)g;
   }
   int64_t o = -1;
-  const int what = inside ? trace_partner<BC>(I, j, key, key[c == 2 ? 1 : 0], key[c == 0 ? 1 : 2], A.max_trace, o) : TRACE_FAILED;
+  const int what = inside ? trace_partner<BC, PINCH>(I, j, key, key[c == 2 ? 1 : 0], key[c == 0 ? 1 : 2], A.max_trace, o) : TRACE_FAILED;
   atomicAdd((unsigned long long*)A.counters + GGNN_TRACE_COUNTERS * b + what, 1ull);
   if (what != TRACE_TRACED) return;
   *slot = o;
@@ -609,13 +627,15 @@ static int64_t junction_blocks(ggnn::junction_kargs& K, size_t workspace_bytes, 
   return n_blocks;
 }
 
-// Count, scan, emit.
-template <bool STACK>
+// Count, scan, emit.  PINCH: the window rule, a compile-time mode like the two above; the default is the kernels that were.
+template <bool STACK, int PINCH = GGNN_PINCH_JUNCTION>
 static int launch_junctions(const ggnn::junction_kargs& K, int64_t n_blocks, int32_t boundary, hipStream_t st) {
   using namespace ggnn;
   const bool periodic = boundary == GGNN_BC_PERIODIC;
-  const auto count = periodic ? image_junctions_kernel<false, GGNN_BC_PERIODIC, STACK> : image_junctions_kernel<false, GGNN_BC_NOFLUX, STACK>;
-  const auto emit = periodic ? image_junctions_kernel<true, GGNN_BC_PERIODIC, STACK> : image_junctions_kernel<true, GGNN_BC_NOFLUX, STACK>;
+  const auto count = periodic ? image_junctions_kernel<false, GGNN_BC_PERIODIC, STACK, PINCH>
+                              : image_junctions_kernel<false, GGNN_BC_NOFLUX, STACK, PINCH>;
+  const auto emit = periodic ? image_junctions_kernel<true, GGNN_BC_PERIODIC, STACK, PINCH>
+                             : image_junctions_kernel<true, GGNN_BC_NOFLUX, STACK, PINCH>;
   hipLaunchKernelGGL(count, dim3((unsigned)n_blocks), dim3(VEC_BLOCK), 0, st, K);
   hipLaunchKernelGGL(junction_scan_kernel<STACK>, dim3(1), dim3(VEC_SCAN_BLOCK), 0, st, K, (int64_t)(periodic ? 0 : 1));
   hipLaunchKernelGGL(emit, dim3((unsigned)n_blocks), dim3(VEC_BLOCK), 0, st, K);
@@ -627,7 +647,7 @@ extern "C" int ggnn_image_junctions(const ggnn_junction_args* args, ggnn_stream_
   if (!args) return GGNN_EINVAL;
   const ggnn_junction_args& A = *args;
   junction_kargs K{A.image, nullptr, const_cast<uint64_t*>(A.pixel_counts), A.xy, A.triples, A.edge_gj, A.status, A.workspace,
-                   nullptr, A.nx, A.ny, 1, A.n_grain, A.joint_capacity, A.offset, A.pitch, A.merge_radius, 0, 0};
+                   nullptr, A.nx, A.ny, 1, A.n_grain, A.joint_capacity, A.offset, A.pitch, A.merge_radius, 0, 0, nullptr};
   const int64_t n_blocks = junction_blocks(K, A.workspace_bytes, A.boundary);
   if (!n_blocks) return GGNN_EINVAL;
   hipStream_t st = (hipStream_t)stream;
@@ -635,21 +655,43 @@ extern "C" int ggnn_image_junctions(const ggnn_junction_args* args, ggnn_stream_
   return launch_junctions<false>(K, n_blocks, A.boundary, st);
 }
 
-// ggnn_image_junctions_traj (rep NULL) and ggnn_image_junction_windows_traj: the same checks, the same launches.
-static int image_junctions_traj(const ggnn_junction_traj_args* args, int32_t* rep, ggnn_stream_t stream) {
+// ggnn_image_junctions_traj (rep NULL) and ggnn_image_junction_windows_traj: the same checks, the same launches.  Their
+// _pinch twins come here with a mode and their counters, which take one memset more; GGNN_PINCH_NECK runs its own kernels.
+static int image_junctions_traj(const ggnn_junction_traj_args* args, int32_t* rep, ggnn_stream_t stream,
+                                int32_t pinch = GGNN_PINCH_JUNCTION, int64_t* pinch_windows = nullptr) {
   using namespace ggnn;
   if (!args) return GGNN_EINVAL;
   const ggnn_junction_traj_args& A = *args;
   if (!A.grain_off || (reinterpret_cast<uintptr_t>(A.grain_off) & 7u)) return GGNN_EINVAL;
   junction_kargs K{A.images, A.grain_off, A.pixel_counts, A.xy, A.triples, A.edge_gj, A.status, A.workspace,
-                   rep, A.nx, A.ny, A.n_image, A.n_grain, A.joint_capacity, A.offset, A.pitch, A.merge_radius, 0, 0};
+                   rep, A.nx, A.ny, A.n_image, A.n_grain, A.joint_capacity, A.offset, A.pitch, A.merge_radius, 0, 0, pinch_windows};
   const int64_t n_blocks = junction_blocks(K, A.workspace_bytes, A.boundary);
   if (!n_blocks) return GGNN_EINVAL;
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(A.status, 0, (size_t)A.n_image * GGNN_JUNCTION_STATUS_WORDS * sizeof(int64_t), st) != hipSuccess)
     return GGNN_ELAUNCH;
   if (hipMemsetAsync(A.pixel_counts, 0, (size_t)A.n_grain * sizeof(uint64_t), st) != hipSuccess) return GGNN_ELAUNCH;
+  if (pinch_windows && hipMemsetAsync(pinch_windows, 0, (size_t)A.n_image * sizeof(int64_t), st) != hipSuccess) return GGNN_ELAUNCH;
+  if (pinch == GGNN_PINCH_NECK) return launch_junctions<true, GGNN_PINCH_NECK>(K, n_blocks, A.boundary, st);
   return launch_junctions<true>(K, n_blocks, A.boundary, st);
+}
+
+// The checks the two _pinch twins add: a known mode comes with counters, 8-byte aligned.
+static bool pinch_valid(int32_t pinch, const int64_t* pinch_windows) {
+  if (pinch != GGNN_PINCH_JUNCTION && pinch != GGNN_PINCH_NECK) return false;
+  return pinch_windows && !(reinterpret_cast<uintptr_t>(pinch_windows) & 7u);
+}
+
+extern "C" int ggnn_image_junctions_pinch_traj(const ggnn_junction_traj_args* args, int32_t pinch, int64_t* n_pinch_windows,
+                                               ggnn_stream_t stream) {
+  if (!pinch_valid(pinch, n_pinch_windows)) return GGNN_EINVAL;
+  return image_junctions_traj(args, nullptr, stream, pinch, n_pinch_windows);
+}
+
+extern "C" int ggnn_image_junction_windows_pinch_traj(const ggnn_junction_traj_args* args, int32_t* rep, int32_t pinch,
+                                                      int64_t* n_pinch_windows, ggnn_stream_t stream) {
+  if (!rep || !pinch_valid(pinch, n_pinch_windows)) return GGNN_EINVAL;
+  return image_junctions_traj(args, rep, stream, pinch, n_pinch_windows);
 }
 
 extern "C" int ggnn_image_junctions_traj(const ggnn_junction_traj_args* args, ggnn_stream_t stream) {
@@ -695,9 +737,11 @@ extern "C" int ggnn_junction_links_traj(const ggnn_link_traj_args* args, ggnn_st
   return launch_status();
 }
 
-extern "C" int ggnn_junction_links_trace_traj(const ggnn_link_trace_args* args, ggnn_stream_t stream) {
+// ggnn_junction_links_trace_traj and its _pinch twin: the same checks, the same memset and launch.
+static int junction_links_trace(const ggnn_link_trace_args* args, int32_t pinch, ggnn_stream_t stream) {
   using namespace ggnn;
   if (!args) return GGNN_EINVAL;
+  if (pinch != GGNN_PINCH_JUNCTION && pinch != GGNN_PINCH_NECK) return GGNN_EINVAL;
   const ggnn_link_trace_args& A = *args;
   if (!A.images || !A.grain_off || !A.triples || !A.rep || !A.rowptr || !A.col || !A.edge_jj || !A.status || !A.counters)
     return GGNN_EINVAL;
@@ -718,7 +762,18 @@ extern "C" int ggnn_junction_links_trace_traj(const ggnn_link_trace_args* args, 
   if (hipMemsetAsync(A.counters, 0, (size_t)A.n_image * GGNN_TRACE_COUNTERS * sizeof(int64_t), st) != hipSuccess)
     return GGNN_ELAUNCH;
   const int64_t blocks = (3 * A.joint_capacity + 255) / 256;
-  const auto trace = A.boundary == GGNN_BC_PERIODIC ? junction_trace_kernel<GGNN_BC_PERIODIC> : junction_trace_kernel<GGNN_BC_NOFLUX>;
+  const bool periodic = A.boundary == GGNN_BC_PERIODIC;
+  auto trace = periodic ? junction_trace_kernel<GGNN_BC_PERIODIC> : junction_trace_kernel<GGNN_BC_NOFLUX>;
+  if (pinch == GGNN_PINCH_NECK)
+    trace = periodic ? junction_trace_kernel<GGNN_BC_PERIODIC, GGNN_PINCH_NECK> : junction_trace_kernel<GGNN_BC_NOFLUX, GGNN_PINCH_NECK>;
   hipLaunchKernelGGL(trace, dim3((unsigned)blocks), dim3(256), 0, st, A);
   return launch_status();
+}
+
+extern "C" int ggnn_junction_links_trace_traj(const ggnn_link_trace_args* args, ggnn_stream_t stream) {
+  return junction_links_trace(args, GGNN_PINCH_JUNCTION, stream);
+}
+
+extern "C" int ggnn_junction_links_trace_pinch_traj(const ggnn_link_trace_args* args, int32_t pinch, ggnn_stream_t stream) {
+  return junction_links_trace(args, pinch, stream);
 }

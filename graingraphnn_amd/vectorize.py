@@ -35,6 +35,12 @@ tests/tracecheck.py): a pair of grains that more than one other junct
 stretches of boundary: a lens on a boundary, a band from wall to wall -- is linked by following the boundary through the image,
 on the device and exact in integers; the default `links="unique"` is the rule above, launch for launch.
 
+`pinch="neck"` reads one window pattern differently in all of these (the _pinch_traj entry points; tests/pinchcheck.py; DESIGN
+8s): three ids in a 2 x 2 window with the repeated one on a diagonal, [a b; c a], is grain a running through the pixel corner as
+a neck, not a junction of a, b and c, and carries no key.  That is what an image looks like whose cell edges drift below a
+pixel, and what the junction rule calls invalid by one junction too many; no pixel changes and no grain is renumbered.  The
+default `pinch="junction"` is the rule above, launch for launch.
+
 A MEASURED map is not a grain-ID image: it carries orientations per pixel, non-indexed points and speckle.  `label_grains`
 (ggnn_label_grains; tests/labelcheck.py) is the stage before all of the above: connected components of an
 orientation map (two neighbours are linked when every angle differs by at most `tol`) or of a noisy id image, periodic or with
@@ -81,6 +87,7 @@ GRIDS = {"cells": lambda nx: (np.float32(1.0), np.float32(1.0) / np.float32(nx))
 BOUNDARIES = {"periodic": _lib.BC_PERIODIC, "noflux": _lib.BC_NOFLUX}
 LINKS = ("unique", "trace")
 TRACE_COUNTERS = ("n_traced", "n_trace_failed", "n_trace_overflow")
+PINCHES = {"junction": _lib.GGNN_PINCH_JUNCTION, "neck": _lib.GGNN_PINCH_NECK}
 EULER = {"periodic": "n_joint == 2 n_present_grains", "noflux": "n_joint == 2 n_present_grains - 2"}
 
 
@@ -107,6 +114,11 @@ def _check_links(links, max_trace, nx, ny):
     if max_trace < 1:
         raise ValueError(f"max_trace must be at least 1, got {max_trace}")
     return max_trace
+
+
+def _check_pinch(pinch):
+    if pinch not in PINCHES:
+        raise ValueError(f"pinch must be 'junction' or 'neck', got {pinch!r}")
 
 
 def image_max_y(nx, ny, grid):
@@ -188,7 +200,7 @@ def _vectorize(image, n_grain, grid, merge_radius, joint_capacity, boundary="per
 
 
 def graph_from_image(image, n_grain=None, grid="cells", merge_radius=2, joint_capacity=None, strict=True,
-                     boundary="periodic", links="unique", max_trace=None):
+                     boundary="periodic", links="unique", max_trace=None, pinch="junction"):
     """The junction graph of a grain-ID image, periodic or (boundary="noflux") with walls.
 
     image: integer [ny, nx] on the device, pixel p = grain p - 1 (what `grain_image` writes); n_grain: the number of grains
@@ -216,30 +228,41 @@ def graph_from_image(image, n_grain=None, grid="cells", merge_radius=2, joint_ca
     device and exact in integers; max_trace bounds a walk (None: 4 (nx + ny) vertices).  The image goes through the one-image
     union, which equals this path bit for bit; a structure without open pairs comes out as with "unique".  The status gains
     n_traced, n_trace_failed and n_trace_overflow (directed columns), n_open_pairs is what is still open, and strict judges
-    that.  Still one read-back.  Any other value raises ValueError."""
-    xy, triples, ei, status, v = _graph(image, n_grain, grid, merge_radius, joint_capacity, strict, boundary, links, max_trace)
+    that.  Still one read-back.  Any other value raises ValueError.
+
+    pinch="junction" (the default) reads a PINCH WINDOW -- three distinct ids whose repeated id sits on a diagonal, [a b; c a] or
+    [b a; a c] -- as the rule above does, as a junction of a, b and c.  It is none: grain a runs through the pixel corner as a
+    neck, b and c do not meet, and the junction is one too many for Euler's formula, which is what an image with cell edges
+    shorter than a pixel fails by.  pinch="neck" gives such a window no key (include/ggnn.h; tests/pinchcheck.py):
+    no pixel changes and no grain is renumbered, the image goes through the one-image union as with links="trace", the status
+    gains n_pinch_windows, and it combines with links="trace" and both boundaries.  A grain with a part that is not even
+    corner-connected to its body stays invalid.  Any other value raises ValueError."""
+    xy, triples, ei, status, v = _graph(image, n_grain, grid, merge_radius, joint_capacity, strict, boundary, links, max_trace,
+                                        pinch)
     if boundary == "noflux":
         return xy, triples, ei, status, v["corner_grains"], v["max_y"]
     return xy, triples, ei, status
 
 
-def _graph(image, n_grain, grid, merge_radius, joint_capacity, strict, boundary="periodic", links="unique", max_trace=None):
+def _graph(image, n_grain, grid, merge_radius, joint_capacity, strict, boundary="periodic", links="unique", max_trace=None,
+           pinch="junction"):
     """graph_from_image's four, with the capacity-sized arrays behind its results as a fifth."""
     _check_links(links, max_trace, 1, 1)
-    if links == "unique":
+    _check_pinch(pinch)
+    if links == "unique" and pinch == "junction":
         v = _vectorize(image, n_grain, grid, merge_radius, joint_capacity, boundary)
         words = v["status"].tolist()
         status = dict(zip(STATUS_WORDS, words))
         v["corner_grains"] = tuple(words[len(STATUS_WORDS):]) if boundary == "noflux" else None
         v["grain_counts"] = v["counts"][1:]   # (ggnn_image_compare's histogram is by id, from 0; a union's is by grain)
-    else:   # the one-image union: the same bits, and the trace call exists for unions alone
+    else:   # the one-image union: the same bits, and the trace and pinch calls exist for unions alone
         _check_boundary(boundary)
         image = _image_tensor(image, 2, IMAGE_2D, "images")
         _check_links(links, max_trace, image.size(1), image.size(0))
         if n_grain is None:
             n_grain = int(image.max())   # (a read-back of its own: pass n_grain to avoid it)
         v = _vectorize_union(_stack(image[None]), [int(n_grain)], grid, merge_radius, joint_capacity, boundary, links=links,
-                             max_trace=max_trace)
+                             max_trace=max_trace, pinch=pinch)
         res, _ = _graphs_of(v, v["status"].tolist(), False)   # the one read-back
         status = res["status"][0]
         v["corner_grains"] = res["corner_grains"][0] if boundary == "noflux" else None
@@ -266,8 +289,8 @@ def sample_from_image(image, theta_x, theta_z, G, R, span=None, patch_pixels=Non
     of one training-size patch, the area feature being fp32(count / patch_pixels) of a double quotient (None: nx ny).
     Grain centres come from ggnn_grain_centres on the junctions found, edge lengths from the rollout's own edge refresh;
     the gradient columns are 0.  Other keywords go to `graph_from_image` (links="trace" among them: a grain with two sides, a
-    lens, and the doubled joint->joint column between its two junctions are plain list entries); an invalid structure always
-    raises.
+    lens, and the doubled joint->joint column between its two junctions are plain list entries; and pinch="neck": a raster with
+    sub-pixel edges is read, not refused); an invalid structure always raises.
 
     boundary="noflux": the angles count the boundary grain, theta[0], and the result is what
     `GrainRollout(..., boundary="noflux", max_y=image_max_y(nx, ny, grid))` takes: the FULL edge lists, grain 0's edges
@@ -282,7 +305,8 @@ def sample_from_image(image, theta_x, theta_z, G, R, span=None, patch_pixels=Non
     kw.pop("strict", None)
     boundary = kw.pop("boundary", "periodic")
     xy, _, ei, _, v = _graph(image, n_grain, kw.pop("grid", "cells"), kw.pop("merge_radius", 2),
-                             kw.pop("joint_capacity", None), True, boundary, kw.pop("links", "unique"), kw.pop("max_trace", None))
+                             kw.pop("joint_capacity", None), True, boundary, kw.pop("links", "unique"), kw.pop("max_trace", None),
+                             kw.pop("pinch", "junction"))
     if kw:
         raise TypeError(f"sample_from_image: unknown keywords {sorted(kw)}")
     if span is None:
@@ -315,15 +339,19 @@ def grain_offsets(n_grains, device):
 
 
 def _vectorize_union(images, n_grains, grid, merge_radius, joint_capacity, boundary="periodic", grain_off=None, extra_words=0,
-                     links="unique", max_trace=None):
+                     links="unique", max_trace=None, pinch="junction"):
     """`_vectorize` for a stack: every launch, no read-back.  images: what `_stack` returns; grain_off: what `grain_offsets`
     returns (None: formed here, an upload -- pass it to a stream capture).  The status tensor holds the B status rows, behind
     them joint_off [B + 1] and, for no-flux, the 4 B corner pixels: one read-back fetches them all (extra_words: zeroed room
     behind those, for the counters of a caller that wants them in the same read-back).  links="trace": the vectorisation also
     writes `rep`, ggnn_junction_links_trace_traj follows the links call, and its 3 B counters lie behind the corner pixels, at
-    v["trace_words"] (None for "unique", whose launches and words are what they were)."""
+    v["trace_words"] (None for "unique", whose launches and words are what they were).  pinch="neck": the _pinch_traj entry
+    points take the place of their namesakes, and their B counters lie behind everything else, extra_words included, at
+    v["pinch_words"] (None for "junction", whose launches and words are what they were)."""
     be = default_backend()
     _check_boundary(boundary)
+    _check_pinch(pinch)
+    neck = pinch == "neck"
     noflux = boundary == "noflux"
     if grid not in GRIDS:
         raise _lib.GGNNError(f"grid must be 'cells' or 'points', got {grid!r}")
@@ -339,8 +367,10 @@ def _vectorize_union(images, n_grains, grid, merge_radius, joint_capacity, bound
     counts = torch.empty(n_total, dtype=torch.int64, device=dev)       # (zeroed by the call)
     W = _lib.GGNN_JUNCTION_STATUS_WORDS
     trace_words = B * W + B + 1 + (4 * B if noflux else 0) if trace else None
-    xy, triples, gj, jj, status, ws = _arrays(dev, n_total, cap, B, ny, nx, noflux, B * W + B + 1 + (4 * B if noflux else 0)
-                                              + (_lib.GGNN_TRACE_COUNTERS * B if trace else 0) + extra_words)
+    words = B * W + B + 1 + (4 * B if noflux else 0) + (_lib.GGNN_TRACE_COUNTERS * B if trace else 0) + extra_words
+    pinch_words = words if neck else None
+    xy, triples, gj, jj, status, ws = _arrays(dev, n_total, cap, B, ny, nx, noflux, words + (B if neck else 0))
+    mode, pinched = PINCHES[pinch], (_lib.ptr(status[pinch_words:]) if neck else None)
     if noflux:   # per image, the order of grain_image(corner_grains=)
         status[B * W + B + 1:B * W + 5 * B + 1] = torch.stack([images[:, 0, 0], images[:, 0, -1], images[:, -1, 0], images[:, -1, -1]], 1).reshape(-1)
     off, pitch = GRIDS[grid](nx)
@@ -353,8 +383,15 @@ def _vectorize_union(images, n_grains, grid, merge_radius, joint_capacity, bound
     rep = None
     if trace:
         rep = torch.zeros(cap, dtype=torch.int32, device=dev)
-        _lib.check(be.lib.ggnn_image_junction_windows_traj(ctypes.byref(A), _lib.ptr(rep), _lib.current_stream()),
-                   "ggnn_image_junction_windows_traj")
+        if neck:
+            _lib.check(be.lib.ggnn_image_junction_windows_pinch_traj(ctypes.byref(A), _lib.ptr(rep), mode, pinched,
+                                                                     _lib.current_stream()), "ggnn_image_junction_windows_pinch_traj")
+        else:
+            _lib.check(be.lib.ggnn_image_junction_windows_traj(ctypes.byref(A), _lib.ptr(rep), _lib.current_stream()),
+                       "ggnn_image_junction_windows_traj")
+    elif neck:
+        _lib.check(be.lib.ggnn_image_junctions_pinch_traj(ctypes.byref(A), mode, pinched, _lib.current_stream()),
+                   "ggnn_image_junctions_pinch_traj")
     else:
         _lib.check(be.lib.ggnn_image_junctions_traj(ctypes.byref(A), _lib.current_stream()), "ggnn_image_junctions_traj")
     csr = be.build_csr_batch([(gj.flip(0).contiguous(), cap, n_total + cap)], check=False)[0]
@@ -370,22 +407,29 @@ def _vectorize_union(images, n_grains, grid, merge_radius, joint_capacity, bound
         T.edge_jj, T.status, T.counters = L.edge_jj, L.status, _lib.ptr(status[trace_words:])
         T.nx, T.ny, T.n_image, T.n_grain, T.joint_capacity, T.E_cap = nx, ny, B, n_total, cap, L.E_cap
         T.max_trace, T.merge_radius, T.boundary = max_trace, R, BOUNDARIES[boundary]
-        _lib.check(be.lib.ggnn_junction_links_trace_traj(ctypes.byref(T), _lib.current_stream()), "ggnn_junction_links_trace_traj")
+        if neck:
+            _lib.check(be.lib.ggnn_junction_links_trace_pinch_traj(ctypes.byref(T), mode, _lib.current_stream()),
+                       "ggnn_junction_links_trace_pinch_traj")
+        else:
+            _lib.check(be.lib.ggnn_junction_links_trace_traj(ctypes.byref(T), _lib.current_stream()), "ggnn_junction_links_trace_traj")
     return {"xy": xy, "triples": triples, "gj": gj, "jj": jj, "status": status, "counts": counts, "csr": csr,
             "n_grain": n_total, "n_image": B, "grain_off": off_host, "grain_off_dev": off_dev, "capacity": cap,
             "shape": (ny, nx), "boundary": boundary, "max_y": image_max_y(nx, ny, grid) if noflux else None,
-            "rep": rep, "trace_words": trace_words, "trace_call": T,
+            "rep": rep, "trace_words": trace_words, "trace_call": T, "pinch_words": pinch_words, "pinch": pinch,
             "calls": (A, L, images, ws)}
 
 
-def _graphs(images, n_grains, grid, merge_radius, joint_capacity, strict, boundary="periodic", links="unique", max_trace=None):
+def _graphs(images, n_grains, grid, merge_radius, joint_capacity, strict, boundary="periodic", links="unique", max_trace=None,
+            pinch="junction"):
     """graphs_from_images' dict, with the capacity-sized arrays behind it as a second result."""
     _check_boundary(boundary)
     _check_links(links, max_trace, 1, 1)
+    _check_pinch(pinch)
     images = _stack(images)
     if n_grains is None:
         n_grains = images.amax(dim=(1, 2)).tolist()   # (a read-back of its own: pass n_grains to avoid it)
-    v = _vectorize_union(images, n_grains, grid, merge_radius, joint_capacity, boundary, links=links, max_trace=max_trace)
+    v = _vectorize_union(images, n_grains, grid, merge_radius, joint_capacity, boundary, links=links, max_trace=max_trace,
+                         pinch=pinch)
     return _graphs_of(v, v["status"].tolist(), strict)   # the one read-back
 
 
@@ -398,6 +442,9 @@ def _graphs_of(v, words, strict):
         t0, C = v["trace_words"], len(TRACE_COUNTERS)
         for b in range(B):
             status[b].update(zip(TRACE_COUNTERS, words[t0 + C * b:t0 + C * (b + 1)]))
+    if v.get("pinch_words") is not None:   # pinch="neck": the pinch windows of every image
+        for b in range(B):
+            status[b]["n_pinch_windows"] = words[v["pinch_words"] + b]
     joint_off = [min(o, cap) for o in words[B * W:B * W + B + 1]]
     corners = None
     if boundary == "noflux":
@@ -418,7 +465,7 @@ def _graphs_of(v, words, strict):
 
 
 def graphs_from_images(images, n_grains=None, grid="cells", merge_radius=2, joint_capacity=None, strict=True,
-                       boundary="periodic", links="unique", max_trace=None):
+                       boundary="periodic", links="unique", max_trace=None, pinch="junction"):
     """The junction graphs of a stack of grain-ID images as ONE disjoint union: `graph_from_image`'s rule per image, in a
     number of launches that does not depend on the number of images, with one read-back.
 
@@ -439,8 +486,11 @@ def graphs_from_images(images, n_grains=None, grid="cells", merge_radius=2, join
 
     links="trace", max_trace: as in `graph_from_image`, per image: every status dict gains n_traced, n_trace_failed and
     n_trace_overflow, and its n_open_pairs is what is still open after tracing.  One more launch and one memset, whatever the
-    number of images or of open pairs; still one read-back."""
-    return _graphs(images, n_grains, grid, merge_radius, joint_capacity, strict, boundary, links, max_trace)[0]
+    number of images or of open pairs; still one read-back.
+
+    pinch="neck": as in `graph_from_image`, per image: every status dict gains n_pinch_windows.  The same launches and one
+    memset more; still one read-back."""
+    return _graphs(images, n_grains, grid, merge_radius, joint_capacity, strict, boundary, links, max_trace, pinch)[0]
 
 
 def union_member(result, t):
@@ -488,7 +538,7 @@ def samples_from_images(images, theta_x, theta_z, G, R, span=None, patch_pixels=
     kw.pop("strict", None)
     boundary = kw.pop("boundary", "periodic")
     res, v = _graphs(images, n_grains, kw.pop("grid", "cells"), kw.pop("merge_radius", 2), kw.pop("joint_capacity", None),
-                     True, boundary, kw.pop("links", "unique"), kw.pop("max_trace", None))
+                     True, boundary, kw.pop("links", "unique"), kw.pop("max_trace", None), kw.pop("pinch", "junction"))
     if kw:
         raise TypeError(f"samples_from_images: unknown keywords {sorted(kw)}")
     x, ei, ea = _union_state(res["xy"], res["edge_index_dict"], res["traj_offsets"]["joint"], v, v["counts"],
@@ -553,22 +603,24 @@ PAIR_COUNTERS = ("n_matched", "n_ambiguous", "n_label0", "n_label1", "n_unlabell
 
 
 def _track(frames, n_grain, grid, merge_radius, joint_capacity, boundary, extra_volume=None, patch_pixels=None, targets=True,
-           links="unique", max_trace=None):
+           links="unique", max_trace=None, pinch="junction"):
     """Every launch of a tracked sequence, no read-back: `_vectorize_union`'s dict with the frames as its images, plus
     next_joint / prev_joint and, with `targets`, the capacity-sized target arrays.  The counters of ggnn_track_junctions
-    [T, 2] and of ggnn_track_targets [T, 4] lie behind the union's status words, at v["counter_words"]."""
+    [T, 2] and of ggnn_track_targets [T, 4] lie behind the union's status words, at v["counter_words"] (and, with pinch="neck",
+    in front of the T pinch counters)."""
     be = default_backend()
     _check_links(links, max_trace, 1, 1)
+    _check_pinch(pinch)
     frames = _stack(frames)
     T, ny, nx = frames.shape
     n_grain = int(n_grain)
     if T < 2:
         raise _lib.GGNNError("a sequence needs at least two frames")
     v = _vectorize_union(frames, [n_grain] * T, grid, merge_radius, joint_capacity, boundary, extra_words=6 * T, links=links,
-                         max_trace=max_trace)
+                         max_trace=max_trace, pinch=pinch)
     dev, cap, n_total, csr, status = frames.device, v["capacity"], v["n_grain"], v["csr"], v["status"]
-    v["counter_words"] = status.numel() - 6 * T
-    counters = status[v["counter_words"]:]
+    v["counter_words"] = (status.numel() if v["pinch_words"] is None else v["pinch_words"]) - 6 * T
+    counters = status[v["counter_words"]:v["counter_words"] + 6 * T]
     v["next_joint"] = torch.full((cap,), -1, dtype=torch.int64, device=dev)
     v["prev_joint"] = torch.full((cap,), -1, dtype=torch.int64, device=dev)
     K = _lib.TrackArgs()
@@ -604,7 +656,7 @@ def _track(frames, n_grain, grid, merge_radius, joint_capacity, boundary, extra_
 
 
 def track_frames(frames, n_grain, grid="cells", merge_radius=2, joint_capacity=None, boundary="periodic", links="unique",
-                 max_trace=None):
+                 max_trace=None, pinch="junction"):
     """The frame-to-frame correspondence of a recorded sequence of grain-ID images (ggnn_track_junctions; tests/trackcheck.py
     restates the rule): -> (`graphs_from_images(frames, [n_grain] * T, strict=False)`'s dict, next_joint, prev_joint).
 
@@ -617,15 +669,19 @@ def track_frames(frames, n_grain, grid="cells", merge_radius=2, joint_capacity=N
     links="trace", max_trace: as in `graphs_from_images`; the frames are traced before they are judged, so a frame with a lens
     or a wall-to-wall band is valid and its pairs are tracked.  The tracker itself is the same: the two junctions of a lens
     share a triple, so they are counted in n_ambiguous and stay unmatched (mask 0), and the links around them are labelled by
-    the rule above."""
-    v = _track(frames, n_grain, grid, merge_radius, joint_capacity, boundary, targets=False, links=links, max_trace=max_trace)
+    the rule above.
+
+    pinch="neck": as in `graphs_from_images`; the frames are read with it before they are judged, so a frame in which a drifting
+    cell edge is a neck through a pixel corner is valid and its pairs are tracked.  The tracker itself is the same."""
+    v = _track(frames, n_grain, grid, merge_radius, joint_capacity, boundary, targets=False, links=links, max_trace=max_trace,
+               pinch=pinch)
     res, _ = _graphs_of(v, v["status"].tolist(), False)   # the one read-back
     n = res["traj_offsets"]["joint"][-1]
     return res, v["next_joint"][:n].contiguous(), v["prev_joint"][:n].contiguous()
 
 
 def frames_to_samples(frames, theta_x, theta_z, G, R, span=None, patch_pixels=None, extra_volume=None, z=None, grid="cells",
-                      merge_radius=2, joint_capacity=None, boundary="periodic", links="unique", max_trace=None):
+                      merge_radius=2, joint_capacity=None, boundary="periodic", links="unique", max_trace=None, pinch="junction"):
     """A training set from a recorded sequence of grain-ID images -- a phase-field run, a serial-section series, the
     `grain_images()` of a rollout --: -> (samples, report), one sample per pair of consecutive VALID frames (t, t + 1), each the
     (x, edge_index, edge_attr, y, mask) of device tensors with local indices that `training.DeviceDataset` takes.  What the
@@ -656,18 +712,24 @@ def frames_to_samples(frames, theta_x, theta_z, G, R, span=None, patch_pixels=No
     the frame in which a grain is a lens on a boundary, one frame before it vanishes, is valid and keeps its two pairs -- the
     ones that carry the classifier's positive labels; report["status"] carries n_traced, n_trace_failed and n_trace_overflow
     per frame.  The tracker itself is the same: the two junctions of a lens share a triple, so they are counted in n_ambiguous
-    and stay unmatched (mask 0), and the links around them are labelled by the rule above."""
+    and stay unmatched (mask 0), and the links around them are labelled by the rule above.
+
+    pinch="neck": as in `graphs_from_images`: a frame in which a drifting cell edge is a neck through a pixel corner is read as
+    the valid structure it is and keeps its two pairs, with no pixel changed and no grain renumbered; report["status"] carries
+    n_pinch_windows per frame and report["n_pinch_windows"] lists them.  The tracker itself is the same.  With the default the
+    report is what it was."""
     tx, tz = np.asarray(theta_x, np.float64).ravel(), np.asarray(theta_z, np.float64).ravel()
     n_grain = len(tx)
     if n_grain < 1 or len(tz) != n_grain:
         raise _lib.GGNNError("theta_x and theta_z must hold one angle per grain")
     _check_boundary(boundary)
     _check_links(links, max_trace, 1, 1)
+    _check_pinch(pinch)
     frames = _stack(frames)
     T = frames.size(0)
     Gs, Rs, zs, span = _process_columns(T, G, R, z, span, "G, R and z", "frame", "sequence")
     v = _track(frames, n_grain, grid, merge_radius, joint_capacity, boundary, extra_volume, patch_pixels, links=links,
-               max_trace=max_trace)
+               max_trace=max_trace, pinch=pinch)
     words = v["status"].tolist()                      # the one read-back
     res, _ = _graphs_of(v, words, False)
     oj, n = res["traj_offsets"]["joint"], res["traj_offsets"]["joint"][-1]
@@ -683,6 +745,8 @@ def frames_to_samples(frames, theta_x, theta_z, G, R, span=None, patch_pixels=No
             x["joint"][oj[t]:oj[t + 1], 2] = zs[t]
     c0 = v["counter_words"]
     report = {"status": res["status"], "pairs": [], "skipped": [], "counts": []}
+    if pinch == "neck":
+        report["n_pinch_windows"] = [s["n_pinch_windows"] for s in res["status"]]
     samples = []
     for t in range(T - 1):
         if not (valid[t] and valid[t + 1]):

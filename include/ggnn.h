@@ -1138,7 +1138,8 @@ int ggnn_junction_links_traj(const ggnn_link_traj_args* args, ggnn_stream_t stre
  * NULL, a 64-bit array not 8-byte aligned or a 32-bit one not 4-byte aligned, n_grain, joint_capacity, E_cap, n_image as in
  * ggnn_junction_links_traj, nx, ny, merge_radius, boundary as in ggnn_image_junctions_traj, max_trace < 1.
  * Not covered: matching the two junctions of a lens between frames (they share a triple: ggnn_track_junctions counts them as
- * ambiguous and leaves them unmatched), structures that fail Euler's formula (a sub-pixel edge that loses a junction). */
+ * ambiguous and leaves them unmatched), structures that fail Euler's formula (a grain with a part that is not even
+ * corner-connected to its body; a neck through a pixel corner is read by GGNN_PINCH_NECK below). */
 #define GGNN_TRACE_COUNTERS 3
 int ggnn_image_junction_windows_traj(const ggnn_junction_traj_args* args, int32_t* rep, ggnn_stream_t stream);
 typedef struct ggnn_link_trace_args {
@@ -1157,6 +1158,36 @@ typedef struct ggnn_link_trace_args {
   int32_t boundary;              /* GGNN_BC_PERIODIC / GGNN_BC_NOFLUX */
 } ggnn_link_trace_args;
 int ggnn_junction_links_trace_traj(const ggnn_link_trace_args* args, ggnn_stream_t stream);
+/* PINCH WINDOWS: a second reading of one window pattern, beside the junction rule above and a mode of the same kernels.  A
+ * pinch window is a window of three distinct valid ids whose repeated id sits on a diagonal: [a b; c a] (TL == BR) or
+ * [b a; a c] (TR == BL).  The junction rule gives it the key {a, b, c}: a junction where grains b and c meet.  They do not
+ * meet: grain a runs through the corner as a neck one pixel wide, and the a | b boundary and the a | c boundary each turn
+ * through the vertex.  (The other reading, b touching c, would cut grain a in two, which the graph cannot hold either.)  A
+ * grain-ID image whose cell edges drift below a pixel shows such windows, and each is one junction too many for Euler's formula.
+ *   GGNN_PINCH_JUNCTION : the rule above, its kernels, launch for launch and bit for bit.
+ *   GGNN_PINCH_NECK     : a window of three distinct valid ids CARRIES NO KEY when TL == BR or TR == BL.  Valid ids, the
+ *                         periodic wrap and the no-flux outside-reads-as-id-1 convention are unchanged, and so are quadruple
+ *                         windows and the two-id checkerboard [a b; b a].  "Carries" is the one predicate every part of the
+ *                         rule reads, so a pinch window is no candidate; it is no carrier in the representative test of another
+ *                         window; it is not in m, Sx, Sy of a junction's position; it is not counted as merged; in the trace rule
+ *                         it owns nothing and nobody owns it, and a walk that reaches it finds a vertex with exactly two a | b
+ *                         cracks and leaves by the other, as the walk rule above says of any vertex without a key.
+ *   n_pinch_windows     : int64 [n_image], zeroed by the call (one memset more): under GGNN_PINCH_NECK the pinch windows of every
+ *                         image, each counted once, an integer sum of the count pass (one atomic a wave, as n_quad_windows; no
+ *                         result is ordered by it); under GGNN_PINCH_JUNCTION the call is the plain one and the words stay 0.
+ *                         The status row keeps its GGNN_JUNCTION_STATUS_WORDS words; the counters may lie in the caller's
+ *                         status buffer behind everything else, so that one read-back fetches them too.
+ * The _pinch_traj entry points are their namesakes with the mode (the single-image entry points have no twin: an image is the
+ * union of one).  ggnn_junction_links_trace_pinch_traj takes the mode the images were vectorised with and no counters: it counts
+ * nothing new.  GGNN_EINVAL without a launch: as their namesakes, a mode that is neither of the two, n_pinch_windows NULL or not
+ * 8-byte aligned.  tests/pinchcheck.py restates the rule. */
+#define GGNN_PINCH_JUNCTION 0
+#define GGNN_PINCH_NECK 1
+int ggnn_image_junctions_pinch_traj(const ggnn_junction_traj_args* args, int32_t pinch, int64_t* n_pinch_windows,
+                                    ggnn_stream_t stream);
+int ggnn_image_junction_windows_pinch_traj(const ggnn_junction_traj_args* args, int32_t* rep, int32_t pinch,
+                                           int64_t* n_pinch_windows, ggnn_stream_t stream);
+int ggnn_junction_links_trace_pinch_traj(const ggnn_link_trace_args* args, int32_t pinch, ggnn_stream_t stream);
 /* ------------------------------------------------------------------------------------
  * Training targets from a recorded SEQUENCE of grain-ID images: the n_frame images of one union above are the frames of a
  * sequence in which a grain keeps its id (local grain g of every frame is the same grain; an eliminated grain no longer

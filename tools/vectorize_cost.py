@@ -39,6 +39,14 @@ so every thread of the trace call reads its column and returns.  With --track T:
 links="trace" alternating, the pairs each emits, and what the frames that are still invalid fail by.
     python tools/vectorize_cost.py --trace [--rounds 50]
     python tools/vectorize_cost.py --track 64 --trace [--rounds 20]
+--pinch neck adds the arms that read pinch windows as necks (pinch="neck", the _pinch_traj entry points).  On the 4 096 x 4 096
+image, read as a one-image union: ggnn_image_junctions_traj and ggnn_image_junctions_pinch_traj(GGNN_PINCH_NECK) on prepared
+arguments, by events, alternating with the other arms, and the image's n_pinch_windows.  With --track T: frames_to_samples with
+pinch="junction" and with pinch="neck" alternating, and the pairs each emits.
+--against LIB adds one arm to the plain run: ggnn_image_junctions of another build of the library (the parent commit's, say) on
+the same prepared arguments, alternating with this build's within every round.
+    python tools/vectorize_cost.py --pinch neck [--against /path/to/libggnn.so] [--rounds 20]
+    python tools/vectorize_cost.py --track 64 --pinch neck [--rounds 20]
 --label times the stage before all of these, segmenting a measured map (vectorize.label_grains, ggnn_label_grains), in angles mode
 with K = 2 on two maps: frame 0 of tests/golden/pf_frames_cfg1.npz (501 x 501, 118 grains, as it is) and a --size x --size periodic
 Voronoi map of size^2 / 8192 cells with 1 % of the pixels non-indexed or wrong (half each) and min_pixels = 8; and prints
@@ -94,6 +102,8 @@ def main():
     ap.add_argument("--track", type=int, default=0, metavar="T")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--trace", action="store_true", help="the links=\"trace\" arms")
+    ap.add_argument("--pinch", choices=("junction", "neck"), default="junction", help="neck: the pinch=\"neck\" arms")
+    ap.add_argument("--against", metavar="LIB", help="another build of libggnn.so: its ggnn_image_junctions as one more arm")
     ap.add_argument("--label", action="store_true", help="the cost of label_grains")
     ap.add_argument("--link", action="store_true", help="the cost of link_labels and label_sequence")
     ap.add_argument("--label-orient", action="store_true", help="the cost of label_orientations beside label_grains")
@@ -144,6 +154,20 @@ def main():
                 "junctions": lambda: _lib.check(lib.ggnn_image_junctions(ctypes.byref(A), _lib.current_stream()), "junctions"),
                 "links": lambda: _lib.check(lib.ggnn_junction_links(ctypes.byref(L), _lib.current_stream()), "links"),
                 "launches": lambda: vz._vectorize(image, n_grain, "cells", 2, None, a.boundary)}
+        if a.against:
+            other = ctypes.CDLL(a.against)
+            other.ggnn_image_junctions.restype = ctypes.c_int
+            other.ggnn_image_junctions.argtypes = lib.ggnn_image_junctions.argtypes
+            arms["junctions, --against"] = lambda: _lib.check(other.ggnn_image_junctions(ctypes.byref(A), _lib.current_stream()), "against")
+        if a.pinch == "neck":
+            u = vz._vectorize_union(vz._stack(image[None]), [n_grain], "cells", 2, None, a.boundary, pinch="neck")
+            res, _ = vz._graphs_of(u, u["status"].tolist(), False)
+            print(f"# one-image union, pinch=\"neck\": status {res['status'][0]}, valid {vz.status_is_valid(res['status'][0], a.boundary)}",
+                  flush=True)
+            U, pinched = u["calls"][0], _lib.ptr(u["status"][u["pinch_words"]:])
+            arms["junctions_traj"] = lambda: _lib.check(lib.ggnn_image_junctions_traj(ctypes.byref(U), _lib.current_stream()), "traj")
+            arms["junctions_pinch_traj, neck"] = lambda: _lib.check(lib.ggnn_image_junctions_pinch_traj(
+                ctypes.byref(U), _lib.GGNN_PINCH_NECK, pinched, _lib.current_stream()), "pinch_traj")
         times = {k: [] for k in arms}
         for rnd in range(a.rounds + 3):
             for name, call in arms.items():
@@ -156,7 +180,7 @@ def main():
                     times[name].append(t0.elapsed_time(t1) * 1e3)
         for name, t in times.items():
             t = np.array(t)
-            print(f"{name:9s} us/call by events: median {np.median(t):8.1f}  min {t.min():8.1f}  max {t.max():8.1f}", flush=True)
+            print(f"{name:26s} us/call by events: median {np.median(t):8.1f}  min {t.min():8.1f}  max {t.max():8.1f}", flush=True)
         if a.trace:
             trace_call_cost(a, image, n_grain)
         print(f"# torch {torch.__version__}, {torch.cuda.get_device_name()}", flush=True)
@@ -372,8 +396,8 @@ def track_cost(a):
                  "joint_off": res["traj_offsets"]["joint"]}
             return tc.track(u, n_grain, "periodic", shape=(size, size))
 
-        def samples(frames=frames, links="unique"):
-            out = vz.frames_to_samples(frames, theta_x, theta_z, G, R, span=span, links=links)
+        def samples(frames=frames, links="unique", pinch="junction"):
+            out = vz.frames_to_samples(frames, theta_x, theta_z, G, R, span=span, links=links, pinch=pinch)
             torch.cuda.synchronize()
             return out
 
@@ -420,6 +444,15 @@ def track_cost(a):
                   f"by Euler's formula, with {sum(s['n_trace_failed'] for s in still)} failed and "
                   f"{sum(s['n_trace_overflow'] for s in still)} overflowed columns", flush=True)
             arms["samples, trace"] = lambda: by_clock(lambda: samples(links="trace"))
+        if a.pinch == "neck":
+            _, necked = samples(pinch="neck")
+            still = [t for t, s in enumerate(necked["status"]) if not vz.status_is_valid(s)]
+            print(f"# pinch=\"neck\": {len(necked['pairs'])} pairs emitted, {len(necked['skipped'])} skipped (pinch=\"junction\": "
+                  f"{len(report['pairs'])} and {len(report['skipped'])}); {sum(necked['n_pinch_windows'])} pinch windows in "
+                  f"{sum(1 for p in necked['n_pinch_windows'] if p)} frames; {sum(s['n_joint'] for s in necked['status'])} junctions; "
+                  f"frames still invalid: {still}; totals "
+                  f"{ {k: sum(c[k] for c in necked['counts']) for k in vz.PAIR_COUNTERS} }", flush=True)
+            arms["samples, neck"] = lambda: by_clock(lambda: samples(pinch="neck"))
         times = {k: [] for k in arms}
         for rnd in range(a.rounds + 3):
             for name, arm in arms.items():
@@ -428,7 +461,7 @@ def track_cost(a):
                     times[name].append(t)
         for name, t in times.items():
             t = np.array(t)
-            print(f"{name:10s} us: median {np.median(t):10.1f}  min {t.min():10.1f}  max {t.max():10.1f}", flush=True)
+            print(f"{name:14s} us: median {np.median(t):10.1f}  min {t.min():10.1f}  max {t.max():10.1f}", flush=True)
         print(f"# host / samples = {np.median(times['host']) / np.median(times['samples']):.1f}", flush=True)
         try:
             from torch.profiler import ProfilerActivity, profile
